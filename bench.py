@@ -19,6 +19,9 @@ Multi-GPU, default (--mode prove): independent proofs per GPU (replicas, no data
   barrier / max-over-ranks timing): weak scaling.  --mode shard: ONE proof across the GPUs by LDE coset with RCCL all-gathers of
   leaf digests, merged evaluations and query rows: strong scaling.
 Prints ONE JSON line on rank 0.
+A plain run does only the headline: set-up, warm-up, the timed steps, the result line.  --full adds the reports that take runs of their
+  own after the timed region: two proofs in flight, BASELINE's other configurations and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64; see dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -298,6 +301,48 @@ class PmcValu:
         return e
 
 
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def _u64_halves(a):
+    """uint64 field elements -> float64 [..., 2] (low and high 32-bit halves): exact, where float64 of the whole value is not"""
+    a = np.ascontiguousarray(a).view(np.uint64)
+    return np.stack([(a & np.uint64(0xFFFFFFFF)).astype(np.float64), (a >> np.uint64(32)).astype(np.float64)], axis=-1)
+
+
+def _sample(t, k, salt):
+    """A fixed, seeded sample of k elements of the flattened device tensor t (sorted flat indices), as a host numpy array"""
+    import torch
+    numel = t.numel()
+    if numel <= k:
+        return t.reshape(-1).cpu().numpy()
+    idx = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED + salt).integers(0, numel, size=k, dtype=np.int64))
+    return t.reshape(-1).index_select(0, torch.from_numpy(idx).to(t.device)).cpu().numpy()
+
+
+def dump_outputs(d, proof, bufs):
+    """What the timed path handed its caller in the last step, as DIR/<name>.npy (at most about 40 MB in all):
+    prove / shard: proof.npy = the proof bytes as float32 (one byte per element);
+    hotpath: merkle_root.npy (32 bytes as float32) and fixed, seeded samples (DUMP_SAMPLE_SEED) of the trace, its LDE, the combined
+    constraint evaluations (uint64 field elements in Montgomery form as float64 [k, 2] = low / high 32-bit halves) and of the Merkle
+    tree nodes (float32 [k, 32], one digest byte per element)."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    out = {}
+    if proof is not None:
+        out["proof"] = np.frombuffer(bytes(proof), dtype=np.uint8).astype(np.float32)
+    if bufs is not None:
+        nodes = bufs["nodes"]
+        out["merkle_root"] = nodes[1].cpu().numpy().astype(np.float32)
+        out["trace_sample"] = _u64_halves(_sample(bufs["trace"], 1 << 19, 1))
+        out["lde_sample"] = _u64_halves(_sample(bufs["lde"], 1 << 20, 2))
+        out["combined_sample"] = _u64_halves(_sample(bufs["combined"], 1 << 19, 3))
+        rows = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED + 4).integers(1, nodes.shape[0], size=1 << 16, dtype=np.int64))
+        out["merkle_nodes_sample"] = nodes.index_select(0, torch.from_numpy(rows).to(nodes.device)).cpu().numpy().astype(np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def spawn_ranks(n):
     """--gpus N without a torch.distributed environment: start the N ranks as a fresh child process tree (this process has not
     imported torch and never touches the GPU), pass the child's output through, and return its exit code."""
@@ -334,9 +379,16 @@ def main():
     ap.add_argument("--cpu-sample-tx", type=int, default=1024,
                     help="transactions the CPU baseline proves (default: the whole 1024-transaction witness, no extrapolation; about 25 s on the GPU "
                          "box's host cores)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the reports that take runs of their own: two proofs in flight, BASELINE.json's "
+                         "configs 1-3 and the CPU baseline (N = 1; --no-cpu-baseline / --no-other-configs leave them out again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (prove / shard: the proof bytes; hotpath: the Merkle "
+                         "root and fixed, seeded samples of the trace, LDE, tree and combined evaluations)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip BASELINE.json's configs 1-3 (range / merkle / schnorr proofs, about 2 s after the timed region; N = 1, --mode prove only)")
+                    help="with --full: skip BASELINE.json's configs 1-3 (range / merkle / schnorr proofs, about 2 s after the timed region; N = 1, "
+                         "--mode prove only) and the two-proofs-in-flight report")
     ap.add_argument("--with-composition", action="store_true",
                     help="also time the next stage of prove(): composition polynomial columns + their LDE + Blake3 commitment "
                          "(reported as extra_stage_ms, not part of the hot-path metric)")
@@ -352,6 +404,8 @@ def main():
                          "at a time, the reference benchmark's shape; 2 was measured +7%% proofs/s, see DESIGN.md). --steps must be a multiple")
     ap.add_argument("--queries", type=int, default=96, help="FRI queries (BASELINE.json: 96; the reference's get_example: 42)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -419,6 +473,7 @@ def main():
     def step_coset(timed):
         """one complete proof over all ranks (cstark_tx_shard_* phases, RCCL all-gathers in between); bytes on rank 0"""
         proof = sharding.prove_sharded(prover.backend, prover.options)
+        last_proof[0] = proof
         if proof is not None:
             proof_len[0] = len(proof)
             if timed:
@@ -430,9 +485,11 @@ def main():
     pstages = list(Backend.PROVE_STAGES)
     pacc = {k: 0.0 for k in pstages}
     proof_len = [0]
+    last_proof = [None]
 
     def step_prove(timed):
         proof = prover.prove()
+        last_proof[0] = proof
         proof_len[0] = len(proof)
         if timed:
             for k, v in prover.backend.prove_stage_ms().items():
@@ -517,6 +574,8 @@ def main():
         t = torch.tensor([elapsed], device="cpu" if rehearse else "cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_proof[0] if prove_mode else None, None if prove_mode else prover._bufs)
     if prove_mode:
         stage_ms = {k: pacc[k] / (args.steps // inflight) for k in pstages}
     else:
@@ -674,12 +733,12 @@ def main():
         }
         if extra:
             out["extra_stage_ms"] = extra
-        if world == 1 and args.mode == "prove" and inflight == 1 and not args.no_other_configs:
+        if args.full and world == 1 and args.mode == "prove" and inflight == 1 and not args.no_other_configs:
             try:
                 out["two_proofs_in_flight"] = two_in_flight(meta, prover.options, local)
             except Exception as e:
                 out["two_proofs_in_flight"] = {"failed": repr(e)}
-        if world == 1 and args.mode == "prove" and not args.no_other_configs:
+        if args.full and world == 1 and args.mode == "prove" and not args.no_other_configs:
             try:  # after the timed region and on its own context; a report beside the headline, never a reason to lose it
                 with torch.cuda.stream(torch.cuda.Stream()):  # a stream of its own, as a caller with several contexts would give it
                     ob = Backend(local)
@@ -687,7 +746,7 @@ def main():
                     ob.close()
             except Exception as e:
                 out["other_configs"] = {"failed": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(meta_full, min(args.cpu_sample_tx, n_tx),
                                                    (args.queries, 8, 0, hash_fn, field_ext, 4, 256) if prove_mode else None)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Measurement set of one build, run on the GPU box:  bash tools/profile.sh <tag>      (e.g. r02_v1)
 # Writes under gpurun_out/ (copy what is to be judged into profiles/):
-#   <tag>_bench_prove.json          bench.py, default arguments (un-profiled: the number that counts)
+#   <tag>_bench_prove.json          bench.py --full, default arguments otherwise (un-profiled: the number that counts)
 #   <tag>_kernel_stats.csv          rocprofv3 --kernel-trace --stats of the same command
 #   <tag>_hbm_traffic_pmc.csv       FETCH_SIZE / WRITE_SIZE per kernel, SEPARATE passes (they do not fit one pass); on gfx950
 #                                   FETCH_SIZE reports half of a wide coalesced read stream (MI355X_MICROARCH.md, HBM): the last
@@ -17,7 +17,7 @@ R=$PWD
 O=$R/gpurun_out
 mkdir -p $O
 ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-other-configs"
-python3 bench.py > $O/${TAG}_bench_prove.json 2> $O/${TAG}_bench_prove.err || exit 1
+python3 bench.py --full > $O/${TAG}_bench_prove.json 2> $O/${TAG}_bench_prove.err || exit 1
 python3 tools/modmul_bench.py > $O/${TAG}_modmul.txt 2>&1 || exit 1
 rm -rf $O/prof_$TAG
 (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$TAG/stats -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs > $O/${TAG}_bench_under_rocprof.json 2> $O/prof_$TAG.stats.err) || exit 1
