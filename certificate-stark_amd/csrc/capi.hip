@@ -1087,6 +1087,14 @@ int cstark_tx_evaluate_constraints_ext(cstark_ctx *c, const uint64_t *d_lde, con
     return tx_evaluate_constraints_sets(c, d_lde, coeffs, m, pub_inputs, outs, merkle_depth, log_n, log_blowup, k0, nk, false);
 }
 
+int cstark_tx_evaluate_constraints_ext_lde(cstark_ctx *c, const uint64_t *d_lde, const cstark_tx_coeffs *coeffs, uint32_t m,
+                                           const uint64_t pub_inputs[4], uint64_t *d_out, uint32_t merkle_depth, uint32_t log_n) {
+    if (!d_out || m < 1 || m > 3) return fail(CSTARK_ERR_INVALID_ARG, "cstark_tx_evaluate_constraints_ext_lde: bad argument");
+    const size_t comp = (size_t)8 << log_n;
+    uint64_t *outs[3] = {d_out, d_out + comp, d_out + 2 * comp};
+    return tx_evaluate_constraints_sets(c, d_lde, coeffs, m, pub_inputs, outs, merkle_depth, log_n, 3, 0, 8, true);
+}
+
 // ---- standalone sub-AIRs -------------------------------------------------------------
 int cstark_merkle_build_trace(cstark_ctx *c, uint64_t *d_trace) {
     if (!c || !d_trace) return fail(CSTARK_ERR_INVALID_ARG, "cstark_merkle_build_trace: null argument");

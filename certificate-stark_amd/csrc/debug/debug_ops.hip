@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "../../../include/cstark.h"
 #include "../tower.cuh"
+#include "../rescue.cuh"
 
 namespace cs {
 namespace {
@@ -26,6 +27,8 @@ __global__ void k_fp_op(const fp *a, const fp *b, fp *out, size_t n, int op) {
         case 10: r = fp_mul(fp_sub_lazy(x, y), y); break; // the product takes an unreduced first factor in (0, 2p): (x - y) * y
         case 11: { Acc128 acc; acc.lo = x; acc.hi = y; r = acc_reduce_below_p(acc); break; } // (y 2^64 + x) / 2^64 mod p, y <= p - 2^32
         case 12: { Acc128 acc; acc.lo = x; acc.hi = y; r = acc_reduce(acc); break; }         // the same for y < 2p
+        case 13: r = fp_mul_lazy(x, y); break; // raw: no final subtraction, any words (the bounds are the caller's)
+        case 14: r = fp_cube(x); break;
     }
     out[i] = r;
 }
@@ -95,7 +98,6 @@ int cstark_debug_modmul_bench(void *stream, uint64_t *d_out, int blocks, int ite
 
 // ---- experiment: INV_MDS * d on the matrix cores vs the limb dot products -------------------------------------------------------
 #include "../mds_mfma.cuh"
-#include "../rescue.cuh"
 namespace cs {
 namespace {
 __global__ void k_mds_table(uint8_t *tab) { mdsmfma::build_table_entry(tab, c_inv_mds, 14, blockIdx.x, threadIdx.x); }

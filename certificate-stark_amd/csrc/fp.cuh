@@ -47,8 +47,12 @@ __device__ __forceinline__ uint32_t fp_opaque_one() {
 }
 #define CS_KEEP(x) asm("" : "+v"(x))
 
-// Montgomery product without the final conditional subtraction: result in (0, 2p) for a < 2p, b < p; in general the result is
-// below a b / 2^64 + p for a, b < 2p (every intermediate sum below keeps its headroom up to b1 < 3 * 2^30): fp_inv_sbox's lazy chain.
+// Montgomery product without the final conditional subtraction: result in (0, 2p) for a < 2p, b < p; in general
+// r = (a b + q p) / 2^64 <= a b / 2^64 + p + p / 2^32 for a, b < 2p: fp_inv_sbox's lazy chain.  Not "< a b / 2^64 + p": the two word
+// quotients lie in [1, 2^32], so q = q0 + 2^32 q1 reaches 2^64 and beyond (a = b = 2p - 2 gives exactly a b / 2^64 + p).
+// The tightest sum is the 32-bit c = (w >> 32) + K below: w < 2^32 (b1 + 1) gives w >> 32 <= b1, so c does not wrap for
+// b1 <= 2^32 - 1 - K = 0xBE7FFFFE (2.977 * 2^30, NOT 3 * 2^30); a second factor below 2p has b1 <= 0x83000000.
+// tests/test_bounds_model.py checks these sums on a word-exact model, tests/test_gpu_extremes.py the device at the bounds.
 // Word-serial REDC with q = 2^32 - t0 (never 0): (T + q p) / 2^32 = (T >> 32) + q P1 + 1 exactly, and
 // q P1 + 1 = ~t0 * P1 + (P1 + 1), so a reduction step is one NOT folded into one v_mad_u64_u32 whose addend
 // carries the constant K = P1 + 1 -- no carry bit to materialise.  (q = 2^32 when t0 = 0 merely adds p.)
@@ -135,9 +139,10 @@ __device__ inline fp fp_inv_sbox(fp x) {
         return fp_mul(fp_sqr(fp_sqr(fp_sqr(r))), y3);
     }
 #endif
-    // The chain runs on UNREDUCED values: fp_mul_lazy(a, b) < a b / 2^64 + p holds for both factors below 2p (its word sums keep
-    // their headroom: b1 < 3 * 2^30), and with p / 2^64 = 0.2559 a chain of squarings of a value below 1.78 p interrupted by products
-    // with reduced elements stays below 1.78 p (six squarings from 1.45 p: 1.54, 1.61, 1.66, 1.71, 1.74, 1.78; times x^42: 1.46).
+    // The chain runs on UNREDUCED values: fp_mul_lazy(a, b) <= a b / 2^64 + p + p / 2^32 holds for both factors below 2p (its word
+    // sums keep their headroom: b1 <= 0x83000000 < 0xBE7FFFFE), and with p / 2^64 = 0.2559 a chain of squarings of a value below 1.78 p
+    // interrupted by products with reduced elements stays below 1.78 p (six squarings from 1.45 p: 1.54, 1.61, 1.66, 1.71, 1.74, 1.78;
+    // times x^42: 1.46; the p / 2^32 is far below the rounding of these figures).
     // Only the elements that are second factors again and again (x^2, x^3, x^42) and the result are reduced: 5 conditional
     // subtractions instead of 74 on a chain in which every instruction waits for the one before it.
     const fp x2 = fp_sqr(x), x3 = fp_mul(x2, x);

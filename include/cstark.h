@@ -190,6 +190,10 @@ int cstark_tx_evaluate_constraints_lde(cstark_ctx *ctx, const uint64_t *d_lde, c
 int cstark_tx_evaluate_constraints_ext(cstark_ctx *ctx, const uint64_t *d_lde, const cstark_tx_coeffs *coeffs, uint32_t m,
                                        const uint64_t pub_inputs[4], uint64_t *d_out, uint32_t merkle_depth,
                                        uint32_t log_n, uint32_t log_blowup, uint32_t k0, uint32_t nk);
+/* Both at once: m = 1..3 coefficient sets on a table that IS the low-degree extension over all 8 cosets (the precondition of
+ * cstark_tx_evaluate_constraints_lde), evaluated by the degree-split path of an extension-field proof; d_out[(q * 8 + k) * n + j]. */
+int cstark_tx_evaluate_constraints_ext_lde(cstark_ctx *ctx, const uint64_t *d_lde, const cstark_tx_coeffs *coeffs, uint32_t m,
+                                           const uint64_t pub_inputs[4], uint64_t *d_out, uint32_t merkle_depth, uint32_t log_n);
 /* Measurement aid: when enabled, cstark_tx_evaluate_constraints records HIP events around each of its 9 launches
  * (Rescue windows; doubling / mixed addition of s*G; of h*P; final addition; three linear groups) on the context's
  * stream; cstark_tx_constraint_part_ms waits for the last one and returns the 9 durations in milliseconds. */
