@@ -534,6 +534,49 @@ class Backend:
         check(self.lib.cstark_prove_stage_ms(self.ctx, ms))
         return dict(zip(self.PROVE_STAGES, [float(v) for v in ms]))
 
+    # ---- verification (cstark_tx_verify) ---------------------------------------------------------------------------------------
+    def tx_verify(self, proofs, initial_roots, final_roots, options=None):
+        """TransactionExample::verify for a list of proofs (bytes) or a ProofBatch, in one call.  initial_roots / final_roots: [count][7]
+        (or [7] for every proof), memory form.  options: None = each proof's own options, else every proof must state exactly these.
+        Returns the verdicts, int32 [count] (0 = accepted; names: certificate_stark_amd.VERDICTS)."""
+        count = len(proofs)
+        verdicts = np.zeros(count, np.int32)
+        if count == 0:
+            check(self.lib.cstark_tx_verify(self.ctx, C.c_uint32(0), None, None, None, None, None, verdicts.ctypes.data_as(C.POINTER(C.c_int32))))
+            return verdicts
+        ptrs = (C.POINTER(C.c_uint8) * count)()
+        lens = (C.c_size_t * count)()
+        if isinstance(proofs, ProofBatch):
+            base = proofs._buf.ctypes.data
+            for i in range(count):
+                ptrs[i] = C.cast(C.c_void_p(base + i * proofs._stride), C.POINTER(C.c_uint8))
+                lens[i] = int(proofs._lens[i])
+            keep = proofs
+        else:
+            keep = [bytes(p) for p in proofs]
+            for i, p in enumerate(keep):
+                ptrs[i] = C.cast(C.c_char_p(p), C.POINTER(C.c_uint8))
+                lens[i] = len(p)
+        ir = np.ascontiguousarray(np.broadcast_to(np.asarray(initial_roots, np.uint64).reshape(-1, 7), (count, 7)))
+        fr = np.ascontiguousarray(np.broadcast_to(np.asarray(final_roots, np.uint64).reshape(-1, 7), (count, 7)))
+        o = None if options is None else C.byref(self._options_struct(options))
+        check(self.lib.cstark_tx_verify(self.ctx, C.c_uint32(count), ptrs, lens, ir.ctypes.data_as(u64p), fr.ctypes.data_as(u64p), o,
+                                        verdicts.ctypes.data_as(C.POINTER(C.c_int32))))
+        del keep
+        return verdicts
+
+    def verify_h2d_bytes(self):
+        """bytes the last tx_verify copied host -> device: proof bytes, descriptors and opening records"""
+        n = C.c_uint64(0)
+        check(self.lib.cstark_verify_h2d_bytes(self.ctx, C.byref(n)))
+        return int(n.value)
+
+    def verify_stage_ms(self):
+        from .verify import VERIFY_STAGES
+        ms = (C.c_float * len(VERIFY_STAGES))()
+        check(self.lib.cstark_verify_stage_ms(self.ctx, ms))
+        return dict(zip(VERIFY_STAGES, [float(v) for v in ms]))
+
     def air_prove(self, air, options, number=0):
         """cstark_air_prove: complete proof of the uploaded witness under MerkleAir / SchnorrAir, or of `number` (memory form)
         under RangeProofAir."""

@@ -101,6 +101,9 @@ hipError_t launch_eval_transitions_rescue(const uint64_t *lde, const uint64_t *p
                                           hipStream_t stream);
 
 hipError_t launch_eval_transitions(const CeParams &p, unsigned nk, hipStream_t stream);
+// All 115 transition-constraint values of TransactionAir on nf free-standing frames (the verifier's out-of-domain check): frame j is
+// cur[c * nf + j] (c < 94), next[c * nf + j] and the periodic values per[c * nf + j] (c < 48); out[i * nf + j], i < 115 (device memory)
+hipError_t launch_eval_frames(const uint64_t *cur, const uint64_t *next, const uint64_t *per, uint64_t *out, unsigned nf, hipStream_t stream);
 constexpr int CE_NUM_PARTS = 9; // launches of the fused evaluation: rounds, dbl0, add0, dbl1, add1, final, lin_a, lin_b, lin_c
 hipError_t launch_eval_constraints(const CeParams &p, unsigned nk, hipStream_t stream, hipEvent_t *part_events = nullptr, unsigned done_mask = 0,
                                    bool record_end = true);

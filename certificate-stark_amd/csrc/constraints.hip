@@ -374,6 +374,24 @@ __global__ __launch_bounds__(NT) void k_eval_transitions(CeParams p) {
     evaluate_transition(acc, f);
 }
 
+// The same evaluator on free-standing frames (the verifier's out-of-domain check): frame j is cur[c * nf + j], next[c * nf + j] and
+// per[c * nf + j]; all 115 slots out[i * nf + j] are written (zeroed here, then accumulated).  One lane per frame.
+__global__ __launch_bounds__(NT) void k_eval_frames(const fp *__restrict__ cur, const fp *__restrict__ next, const fp *__restrict__ per,
+                                                    fp *__restrict__ out, unsigned nf) {
+    const unsigned j = blockIdx.x * NT + threadIdx.x;
+    if (j >= nf) return;
+    Frame f;
+    f.n = nf;
+    f.cur_p = cur + j;
+    f.next_p = next + j;
+    f.per_p = per + j;
+    f.pcycle = nf;
+#pragma unroll 1
+    for (int i = 0; i < 115; i++) out[(size_t)i * nf + j] = 0;
+    AccAll acc{out + j, nf};
+    evaluate_transition(acc, f);
+}
+
 // =====================================================================================================
 // Production path: fused evaluation.  The work is split into four launches ("parts") so that each has a
 // small instruction footprint and register budget:  ROUNDS (the five Rescue windows), EC0 / EC1 (double +
@@ -2494,6 +2512,11 @@ hipError_t launch_eval_transitions(const CeParams &p, unsigned nk, hipStream_t s
     hipError_t e = hipMemsetAsync(p.out, 0, (size_t)nk * 115 * n * sizeof(fp), stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_eval_transitions, dim3((unsigned)(n / NT), nk), dim3(NT), 0, stream, p);
+    return hipGetLastError();
+}
+hipError_t launch_eval_frames(const uint64_t *cur, const uint64_t *next, const uint64_t *per, uint64_t *out, unsigned nf, hipStream_t stream) {
+    if (nf == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_eval_frames, dim3((nf + NT - 1) / NT), dim3(NT), 0, stream, cur, next, per, out, nf);
     return hipGetLastError();
 }
 hipError_t launch_eval_transitions_merkle(const uint64_t *lde, const uint64_t *ptab, uint64_t *out, unsigned log_n, unsigned k0, unsigned nk,

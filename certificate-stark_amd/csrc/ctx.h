@@ -108,6 +108,8 @@ struct AirCombineStatic {
 };
 struct ProveArena; // prove.hip
 void prove_arena_free(ProveArena *a);
+struct VerifyArena; // verify.hip: the verifier's staging and scratch (never shared with the prover's buffers)
+void verify_arena_free(VerifyArena *a);
 
 } // namespace cs
 
@@ -154,6 +156,7 @@ struct cstark_ctx {
     size_t tail_bytes = 0;
     size_t desc_bytes = 0;
     cs::ProveArena *arena = nullptr; // device buffers of cstark_tx_prove (prove.hip)
+    cs::VerifyArena *verify = nullptr; // buffers of cstark_tx_verify (verify.hip)
     void *ws = nullptr;
     size_t ws_bytes = 0;
     uint64_t *shard_bit37 = nullptr; // sharded split evaluation: register 37 on all eight cosets

@@ -1,0 +1,1145 @@
+// TransactionExample::verify (src/lib.rs:144-150) for proofs in this library's own layout (include/cstark.h, "Proof
+// layout"), many proofs per call.  Pipeline of one chunk of proofs:
+//   host    parse (structure only: every count against the stated options) and the per-proof constants of the domains; the raw
+//           proof bytes and one descriptor per proof go to one pinned staging block -> ONE host-to-device copy
+//   device  transcript replay, one workgroup per proof (Blake3 or Sha3 coin, vhash.cuh): coefficients, z, DEEP coefficients, layer
+//           alphas, remainder commitment, proof of work, query positions and their folded positions and slots
+//           per extension degree m present: out-of-domain frames (periodic columns at z^(n/1024) from cached coefficients, the frame
+//           sampled along t -> e(t) for m > 1) -> the 115 constraints on every frame (constraints.hip, launch_eval_frames) -> merge
+//           and compare with sum_i H_i z^i; DEEP + FRI, one lane per (proof, query)
+//           all proofs: Merkle openings, one lane per opened row (leaf hash + path walk, Blake3 or Sha3); remainder degree (exact,
+//           one workgroup per component); reduction to one verdict per proof -> ONE device-to-host copy
+// Every check writes one result slot with a plain store: the rank of its failure in the verdict order of cstark.h (or none); the
+// reduction takes the smallest.  The number of launches per chunk does not depend on the number of proofs.
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include <algorithm>
+#include <chrono>
+#include <vector>
+#include "../../include/cstark.h"
+#include "ctx.h"
+#include "constraints.h"
+#include "air_tx_host.h"
+#include "coin.h"
+#include "blake3_compress.cuh"
+#include "ext.cuh"
+#include "keccak.cuh"
+#include "vhash.cuh"
+
+namespace cs {
+
+// failure ranks: smaller = earlier in the verdict order of cstark.h
+enum : uint32_t {
+    RK_MALFORMED = 0, RK_OOD = 1, RK_REMAINDER_COMMITMENT = 2, RK_POW = 3,
+    RK_OPENING0 = 4,     // + 2 q (+ 1 for the composition opening)
+    RK_LAYER0 = 1000,    // + 3 l + (0 count, 1 opening, 2 folding)
+    RK_REMAINDER_FOLDING = 2000, RK_REMAINDER_DEGREE = 2001,
+    RK_NONE = 0xffffffffu
+};
+constexpr uint32_t VMAX_LAYERS = 16, TX_W = 94, TX_CE = 8, TX_NC = 115, TX_NA = 4;
+
+// ---- layout ---------------------------------------------------------------------------------------------------------------------
+struct Layout {
+    uint32_t air, width, log_n, word, opt[7];
+    uint32_t nq, log_b, log_f, f, m, ce, log_N, n_layers, R;
+    size_t ood, nonce, trows, tpaths, crows, cpaths, lrows[VMAX_LAYERS], lpaths[VMAX_LAYERS], rem;
+    uint32_t npos[VMAX_LAYERS];
+};
+
+static inline uint32_t rd32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
+static inline uint64_t rd64(const uint8_t *p) { uint64_t v; memcpy(&v, p, 8); return v; }
+static inline unsigned ilog2(uint32_t v) { unsigned l = 0; while ((1u << (l + 1)) <= v) l++; return l; }
+
+// the header bounds the prover enforces for TransactionAir's Merkle depth (cstark_tx_witness_upload)
+static inline bool tx_depth_ok(uint32_t d) { return d != 0 && ((d + 1) & d) == 0 && 8ull * d + 7 <= 511; }
+
+// Structure only, O(number of sections): returns CSTARK_PROOF_OK or CSTARK_PROOF_MALFORMED.  Every count is checked against the stated
+// options before it sizes anything; `need` never overflows (every factor is bounded first).
+static int parse_layout(const uint8_t *b, size_t len, Layout &L) {
+    memset(&L, 0, sizeof L);
+    if (len < 52 || memcmp(b, "CSTK", 4) != 0) return CSTARK_PROOF_MALFORMED;
+    const uint32_t version = rd32(b + 4);
+    L.air = rd32(b + 8); L.width = rd32(b + 12); L.log_n = rd32(b + 16); L.word = rd32(b + 20);
+    for (int i = 0; i < 7; i++) L.opt[i] = rd32(b + 24 + 4 * i);
+    static const uint32_t W[5] = {94, 65, 56, 2, 14}, CE[5] = {8, 4, 8, 2, 4};
+    if (version != CSTARK_PROOF_VERSION || L.air > 4 || L.width != W[L.air]) return CSTARK_PROOF_MALFORMED;
+    const uint32_t nq = L.opt[0], blowup = L.opt[1], grinding = L.opt[2], hash = L.opt[3], ext = L.opt[4], fold = L.opt[5], rem = L.opt[6];
+    L.ce = CE[L.air];
+    auto pow2 = [](uint32_t v) { return v != 0 && (v & (v - 1)) == 0; };
+    if (nq < 1 || nq > 128 || !pow2(blowup) || blowup < 2 || blowup > 16 || blowup < L.ce || grinding > 32 || hash > 1 || ext > 2 ||
+        (fold != 4 && fold != 8 && fold != 16) || !pow2(rem) || rem < 128 || rem > 1024 || L.log_n < 6 || L.log_n > 21)
+        return CSTARK_PROOF_MALFORMED;
+    if (L.air == CSTARK_AIR_STATE_TRANSITION && (L.log_n < 10 || !tx_depth_ok(L.word))) return CSTARK_PROOF_MALFORMED;
+    L.nq = nq; L.log_b = ilog2(blowup); L.log_f = ilog2(fold); L.f = fold; L.m = ext + 1; L.log_N = L.log_n + L.log_b;
+    unsigned lg = L.log_N, nl = 0;
+    const unsigned log_rem = ilog2(rem);
+    while (lg > log_rem) { lg -= L.log_f; nl++; }
+    L.R = 1u << lg;
+    size_t o = 116;
+    if (len < o + 4) return CSTARK_PROOF_MALFORMED;
+    if (rd32(b + o) != nl || nl > VMAX_LAYERS) return CSTARK_PROOF_MALFORMED;
+    L.n_layers = nl;
+    o += 4 + 32 * (size_t)nl + 32;
+    const size_t m = L.m, Wd = L.width;
+    L.ood = o; o += 8 * (2 * Wd + L.ce) * m;
+    L.nonce = o; o += 8;
+    L.trows = o; o += 8 * nq * Wd;
+    L.tpaths = o; o += 32 * (size_t)nq * L.log_N;
+    L.crows = o; o += 8 * nq * L.ce * m;
+    L.cpaths = o; o += 32 * (size_t)nq * L.log_N;
+    lg = L.log_N;
+    for (unsigned l = 0; l < nl; l++) {
+        if (len < o + 4) return CSTARK_PROOF_MALFORMED;
+        const uint32_t np = rd32(b + o);
+        if (np > nq || lg < L.log_f) return CSTARK_PROOF_MALFORMED;
+        L.npos[l] = np;
+        o += 4;
+        L.lrows[l] = o; o += 8 * (size_t)np * fold * m;
+        L.lpaths[l] = o; o += 32 * (size_t)np * (lg - L.log_f);
+        lg -= L.log_f;
+        if (o > len) return CSTARK_PROOF_MALFORMED;
+    }
+    if (len < o + 4) return CSTARK_PROOF_MALFORMED;
+    if (rd32(b + o) != L.R) return CSTARK_PROOF_MALFORMED;
+    o += 4;
+    L.rem = o; o += 8 * (size_t)L.R * m;
+    if (o != len) return CSTARK_PROOF_MALFORMED; // truncated or trailing bytes
+    return CSTARK_PROOF_OK;
+}
+
+// every field element section below p (the kernels check the same on the device; this host scan runs only where no kernel reads the
+// proof: a proof whose options differ from the expected ones)
+static bool elements_canonical(const uint8_t *b, const Layout &L) {
+    auto sec = [&](size_t off, size_t words) { for (size_t i = 0; i < words; i++) if (rd64(b + off + 8 * i) >= host::P) return false; return true; };
+    bool ok = sec(L.ood, (2 * (size_t)L.width + L.ce) * L.m) && sec(L.trows, (size_t)L.nq * L.width) && sec(L.crows, (size_t)L.nq * L.ce * L.m) &&
+              sec(L.rem, (size_t)L.R * L.m);
+    for (unsigned l = 0; ok && l < L.n_layers; l++) ok = sec(L.lrows[l], (size_t)L.npos[l] * L.f * L.m);
+    return ok;
+}
+
+// ---- what the device reads --------------------------------------------------------------------------------------------------------
+// Offsets (in words) of the replayed transcript block of a proof (device memory, written by k_vfy_transcript): z | t_alpha, t_beta [115] | b_alpha, b_beta [4] | DEEP alpha, beta [94]
+// | delta [8] | deg_a | deg_b | layer alphas [L] (all m words each) | constants | positions [nq] | slots [L][nq] | folded positions [L][nq]
+struct TOff { uint32_t z, ta, tb, ba, bb, da, db, dd, dga, dgb, alpha, k, pos, slot, lpos, st, words; };
+enum { K_WN, K_WNN, K_WLAST, K_G, K_ADJ /* 5 */, K_BADJ = K_ADJ + 5, K_INVF, K_ZETA_INV, K_WRINV, K_PUB /* 4 */, K_WL = K_PUB + 4 /* [L] */, K_WORDS = K_WL + VMAX_LAYERS };
+__host__ __device__ inline TOff toff(uint32_t m, uint32_t L, uint32_t nq) {
+    TOff t;
+    uint32_t o = 0;
+    t.z = o; o += m;
+    t.ta = o; o += TX_NC * m; t.tb = o; o += TX_NC * m; t.ba = o; o += TX_NA * m; t.bb = o; o += TX_NA * m;
+    t.da = o; o += TX_W * m; t.db = o; o += TX_W * m; t.dd = o; o += TX_CE * m; t.dga = o; o += m; t.dgb = o; o += m;
+    t.alpha = o; o += L * m;
+    t.k = o; o += K_WORDS;
+    t.pos = o; o += nq; t.slot = o; o += L * nq; t.lpos = o; o += L * nq;
+    t.st = o; o += 2; // layers whose count matched the derived positions | the first failure found by the replay (rank)
+    t.words = o;
+    return t;
+}
+
+struct VDesc {
+    uint64_t base;   // byte offset of the proof in the chunk's block (8-aligned)
+    uint64_t tb;     // word offset of its transcript block in the device region
+    uint64_t k[K_WORDS];  // constants of its domains (host; copied to the transcript block)
+    uint64_t pub[14];     // initial root | final root, memory form
+    uint32_t ood, trows, tpaths, crows, cpaths, rem;                 // byte offsets inside the proof
+    uint32_t lrows[VMAX_LAYERS];
+    uint32_t log_n, log_N, nq, log_f, n_layers, m, R, log_b, depth_slot, hash, grinding, log_rem, npos[VMAX_LAYERS];
+    uint32_t slot0;     // result slots: [0] out-of-domain, then openings, then nq queries, then m remainder components
+    uint32_t n_open, frame0;
+};
+struct VOpen {
+    uint32_t proof, row, path, root; // row / path / root: byte offsets inside the proof
+    uint32_t words, depth, layer, t, rank, slot, hash; // layer = VNO_LAYER: trace / composition row of query t; else row t of that layer
+};
+constexpr uint32_t VNO_LAYER = 0xffffffffu;
+
+// ---- device helpers ---------------------------------------------------------------------------------------------------------------
+// proof bytes are 4-aligned only (each layer's count word shifts what follows by 4)
+__device__ __forceinline__ uint64_t ld64(const uint8_t *p) {
+    const uint32_t *q = reinterpret_cast<const uint32_t *>(p);
+    return (uint64_t)q[0] | ((uint64_t)q[1] << 32);
+}
+template <int M> __device__ __forceinline__ Ext<M> ld_ext(const uint8_t *p) { Ext<M> r; for (int i = 0; i < M; i++) r.c[i] = ld64(p + 8 * i); return r; }
+template <int M> __device__ __forceinline__ Ext<M> x_base(fp v) { Ext<M> r = x_zero<M>(); r.c[0] = v; return r; }
+template <int M> __device__ __forceinline__ bool x_eq(const Ext<M> &a, const Ext<M> &b) {
+    bool e = true;
+    for (int i = 0; i < M; i++) e &= a.c[i] == b.c[i];
+    return e;
+}
+
+// Blake3 of `words` 64-bit words (one chunk: at most 128 words); canonical &= every word < p
+__device__ void b3_words(const uint8_t *p, uint32_t words, uint32_t (&cv)[8], bool &canonical) {
+    cv[0] = IV0; cv[1] = IV1; cv[2] = IV2; cv[3] = IV3; cv[4] = IV4; cv[5] = IV5; cv[6] = IV6; cv[7] = IV7;
+    const uint32_t nb = (words + 7) / 8;
+    for (uint32_t bk = 0; bk < nb; bk++) {
+        uint32_t m[16];
+        const uint32_t cnt = words - 8 * bk < 8 ? words - 8 * bk : 8;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            uint64_t v = 0;
+            if ((uint32_t)i < cnt) {
+                v = ld64(p + 8 * (8 * bk + i));
+                canonical &= v < FP_P;
+#if !CSTARK_CONV_HASHED_ELEMENT_BYTES_MONTGOMERY
+                v = fp_to_u64(v);
+#endif
+            }
+            m[2 * i] = (uint32_t)v;
+            m[2 * i + 1] = (uint32_t)(v >> 32);
+        }
+        compress(cv, m, cnt * 8, (bk == 0 ? CHUNK_START : 0u) | (bk + 1 == nb ? (CHUNK_END | ROOT) : 0u));
+    }
+}
+// SHA3-256 of `words` 64-bit words (the state stays in registers: every lane index below is a compile-time constant)
+__device__ void sha3_words(const uint8_t *p, uint32_t words, uint64_t (&h)[4], bool &canonical) {
+    uint64_t s[25];
+#pragma unroll
+    for (int i = 0; i < 25; i++) s[i] = 0;
+    for (uint32_t w0 = 0;; w0 += 17) {
+        const uint32_t cnt = words - w0 < 17 ? words - w0 : 17; // a full block is followed by at least the padding block
+#pragma unroll
+        for (uint32_t i = 0; i < 17; i++)
+            if (i < cnt) {
+                uint64_t v = ld64(p + 8 * (w0 + i));
+                canonical &= v < FP_P;
+#if !CSTARK_CONV_HASHED_ELEMENT_BYTES_MONTGOMERY
+                v = fp_to_u64(v);
+#endif
+                s[i] ^= v;
+            }
+        if (cnt < 17) {
+#pragma unroll
+            for (uint32_t i = 0; i < 17; i++) if (i == cnt) s[i] ^= 0x06;
+            s[16] ^= 0x80ull << 56;
+            keccak::permute(s);
+            break;
+        }
+        keccak::permute(s);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) h[i] = s[i];
+}
+
+// ---- kernels ----------------------------------------------------------------------------------------------------------------------
+// One lane per opened row: leaf hash, path walk, comparison with the root.  The list is sorted by (hash, leaf words, path length).
+// Leaf positions come from the replayed transcript; rows of layers from the first one whose count differs are checked for canonical
+// words only.
+__global__ __launch_bounds__(128) void k_vfy_openings(const uint8_t *__restrict__ buf, const VDesc *__restrict__ desc, const VOpen *__restrict__ opens,
+                                                      uint32_t n_open, const uint64_t *__restrict__ tbase, uint32_t *__restrict__ slots) {
+    const uint32_t t = blockIdx.x * 128 + threadIdx.x;
+    if (t >= n_open) return;
+    const VOpen o = opens[t];
+    const VDesc &d = desc[o.proof];
+    const uint8_t *pb = buf + d.base;
+    const uint64_t *tb = tbase + d.tb;
+    const TOff to = toff(d.m, d.n_layers, d.nq);
+    bool canonical = true, match = true;
+    uint32_t idx = 0, rank = o.rank;
+    if (o.layer == VNO_LAYER) idx = (uint32_t)tb[to.pos + o.t];
+    else if (o.layer < (uint32_t)tb[to.st]) idx = (uint32_t)tb[to.lpos + o.layer * d.nq + o.t];
+    else rank = RK_NONE;
+    if (o.hash == 0) {
+        uint32_t cv[8];
+        b3_words(pb + o.row, o.words, cv, canonical);
+        for (uint32_t lvl = 0; lvl < o.depth; lvl++) {
+            const uint32_t *sib = reinterpret_cast<const uint32_t *>(pb + o.path + 32 * lvl);
+            uint32_t m[16];
+            const bool right = idx & 1;
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const uint32_t sv = sib[i];
+                m[i] = right ? sv : cv[i];
+                m[8 + i] = right ? cv[i] : sv;
+            }
+            cv[0] = IV0; cv[1] = IV1; cv[2] = IV2; cv[3] = IV3; cv[4] = IV4; cv[5] = IV5; cv[6] = IV6; cv[7] = IV7;
+            compress(cv, m, 64, CHUNK_START | CHUNK_END | ROOT);
+            idx >>= 1;
+        }
+        const uint32_t *root = reinterpret_cast<const uint32_t *>(pb + o.root);
+        for (int i = 0; i < 8; i++) match &= cv[i] == root[i];
+    } else {
+        uint64_t h[4];
+        sha3_words(pb + o.row, o.words, h, canonical);
+        for (uint32_t lvl = 0; lvl < o.depth; lvl++) {
+            const uint8_t *sib = pb + o.path + 32 * lvl;
+            uint64_t s[25];
+#pragma unroll
+            for (int i = 0; i < 25; i++) s[i] = 0;
+            const bool right = idx & 1;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const uint64_t sv = ld64(sib + 8 * i);
+                s[i] = right ? sv : h[i];
+                s[4 + i] = right ? h[i] : sv;
+            }
+            s[8] ^= 0x06;
+            s[16] ^= 0x80ull << 56;
+            keccak::permute(s);
+            for (int i = 0; i < 4; i++) h[i] = s[i];
+            idx >>= 1;
+        }
+        const uint8_t *root = pb + o.root;
+        for (int i = 0; i < 4; i++) match &= h[i] == ld64(root + 8 * i);
+    }
+    slots[o.slot] = !canonical ? (uint32_t)RK_MALFORMED : match ? (uint32_t)RK_NONE : rank;
+}
+
+// Out-of-domain frames of the proofs gp[0..G) (one workgroup each): periodic values at z^(n/1024) from the coefficient table of the
+// proof's Merkle depth, then K frames t = 0..K-1 whose entries are e(t) = sum_q e_q t^q (K = 1 for m = 1); frame j of the group at
+// column stride F.  bad[g] = 1 if an out-of-domain word is not below p.
+template <int M>
+__global__ __launch_bounds__(128) void k_vfy_ood_frames(const uint8_t *__restrict__ buf, const VDesc *__restrict__ desc, const uint32_t *__restrict__ gp,
+                                                        const uint64_t *__restrict__ tbase, const uint64_t *__restrict__ pcoef, uint32_t K, uint32_t F, fp *__restrict__ cur,
+                                                        fp *__restrict__ nxt, fp *__restrict__ per, uint32_t *__restrict__ bad) {
+    __shared__ Ext<M> pv[48];
+    const VDesc &d = desc[gp[blockIdx.x]];
+    const uint8_t *pb = buf + d.base;
+    const uint64_t *tb = tbase + d.tb;
+    const TOff to = toff(d.m, d.n_layers, d.nq);
+    const uint32_t tid = threadIdx.x;
+    bool ok = true;
+    for (uint32_t i = tid; i < (2 * TX_W + TX_CE) * M; i += 128) ok &= ld64(pb + d.ood + 8 * i) < FP_P;
+    const int any_bad = __syncthreads_or(!ok);
+    if (tid < 48) {
+        Ext<M> zp = x_load<M>(tb + to.z);
+        for (uint32_t s = 10; s < d.log_n; s++) zp = x_mul(zp, zp);
+        const uint64_t *co = pcoef + ((size_t)d.depth_slot * 48 + tid) * 1024;
+        Ext<M> acc = x_zero<M>();
+        for (int i = 1023; i >= 0; i--) { acc = x_mul(acc, zp); acc.c[0] = fp_add(acc.c[0], co[i]); }
+        pv[tid] = acc;
+    }
+    __syncthreads();
+    if (tid == 0) bad[blockIdx.x] = any_bad ? 1u : 0u;
+    const uint32_t f0 = blockIdx.x * K;
+    for (uint32_t e = tid; e < K * (2 * TX_W + 48); e += 128) {
+        const uint32_t t = e / (2 * TX_W + 48), c = e % (2 * TX_W + 48);
+        Ext<M> v;
+        fp *dst;
+        if (c < TX_W) { v = ld_ext<M>(pb + d.ood + 8 * M * c); dst = cur + (size_t)c * F; }
+        else if (c < 2 * TX_W) { v = ld_ext<M>(pb + d.ood + 8 * M * c); dst = nxt + (size_t)(c - TX_W) * F; }
+        else { v = pv[c - 2 * TX_W]; dst = per + (size_t)(c - 2 * TX_W) * F; }
+        const fp tt = fp_from_u64(t);
+        fp r = v.c[M - 1];
+        for (int q = M - 2; q >= 0; q--) r = fp_add(fp_mul(r, tt), v.c[q]);
+        dst[f0 + t] = r;
+    }
+}
+
+template <int M> struct Lagrange { uint64_t w[18][M]; };
+
+// One lane per proof of the group: recombine the sampled constraint values, merge (transition divisor, degree adjustments, the four
+// boundary terms) and compare with sum_i H_i z^i.
+template <int M>
+__global__ __launch_bounds__(64) void k_vfy_ood_check(const uint8_t *__restrict__ buf, const VDesc *__restrict__ desc, const uint32_t *__restrict__ gp,
+                                                      uint32_t G, uint32_t K, uint32_t F, const fp *__restrict__ cvals, const uint32_t *__restrict__ bad,
+                                                      Lagrange<M> lag, const uint64_t *__restrict__ tbase, uint32_t *__restrict__ slots) {
+    const uint32_t g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= G) return;
+    const VDesc &d = desc[gp[g]];
+    const uint8_t *pb = buf + d.base;
+    const uint64_t *tb = tbase + d.tb;
+    const TOff to = toff(d.m, d.n_layers, d.nq);
+    const uint64_t *k = tb + to.k;
+    const Ext<M> z = x_load<M>(tb + to.z);
+    // constraint i's merge coefficient alpha_i + beta_i z^adj: the five degree groups one after the other (z^adj in registers)
+    Ext<M> acc = x_zero<M>();
+#pragma unroll 1
+    for (int grp = 0; grp < 5; grp++) {
+        const Ext<M> za = x_pow(z, k[K_ADJ + grp]);
+#pragma unroll 1
+        for (uint32_t i = 0; i < TX_NC; i++) {
+            if (tx_degree_group(i) != grp) continue;
+            Ext<M> cv = x_zero<M>();
+            for (uint32_t j = 0; j < K; j++) cv = x_add(cv, x_scale(x_load<M>(lag.w[j]), cvals[(size_t)i * F + g * K + j]));
+            const Ext<M> coef = x_add(x_load<M>(tb + to.ta + M * i), x_mul(x_load<M>(tb + to.tb + M * i), za));
+            acc = x_add(acc, x_mul(cv, coef));
+        }
+    }
+    const fp w_last = k[K_WLAST];
+    const Ext<M> one = x_one<M>();
+    Ext<M> zn = z;
+    for (uint32_t s = 0; s < d.log_n; s++) zn = x_mul(zn, zn);
+    acc = x_mul(acc, x_mul(x_sub(z, x_base<M>(w_last)), x_inv(x_sub(zn, one))));
+    const Ext<M> xb = x_pow(z, k[K_BADJ]);
+    Ext<M> first = x_zero<M>(), last = x_zero<M>();
+    for (int a = 0; a < 2; a++) {
+        const Ext<M> c = ld_ext<M>(pb + d.ood + 8 * M * (58 + a));
+        first = x_add(first, x_mul(x_sub(c, x_base<M>(k[K_PUB + a])), x_add(x_load<M>(tb + to.ba + M * a), x_mul(x_load<M>(tb + to.bb + M * a), xb))));
+        last = x_add(last, x_mul(x_sub(c, x_base<M>(k[K_PUB + 2 + a])),
+                                 x_add(x_load<M>(tb + to.ba + M * (2 + a)), x_mul(x_load<M>(tb + to.bb + M * (2 + a)), xb))));
+    }
+    const Ext<M> lhs = x_add(acc, x_add(x_mul(first, x_inv(x_sub(z, one))), x_mul(last, x_inv(x_sub(z, x_base<M>(w_last))))));
+    Ext<M> rhs = x_zero<M>(), zi = one;
+    for (uint32_t i = 0; i < TX_CE; i++) {
+        rhs = x_add(rhs, x_mul(ld_ext<M>(pb + d.ood + 8 * M * (2 * TX_W + i)), zi));
+        zi = x_mul(zi, z);
+    }
+    slots[d.slot0] = bad[g] ? (uint32_t)RK_MALFORMED : x_eq(lhs, rhs) ? (uint32_t)RK_NONE : (uint32_t)RK_OOD;
+}
+
+// One lane per (proof, query): DEEP value at x = g w_N^pos, then every layer -- the value against the opened row, the fold of the row
+// -- and finally the remainder.  Slots and positions come from the host's replay and were checked against the layer's row count.
+template <int M>
+__global__ __launch_bounds__(128) void k_vfy_fri(const uint8_t *__restrict__ buf, const VDesc *__restrict__ desc, const uint32_t *__restrict__ gp,
+                                                 const uint64_t *__restrict__ tbase, uint32_t *__restrict__ slots) {
+    const VDesc &d = desc[gp[blockIdx.y]]; // read in place: lrows[] is indexed by the layer
+    const uint32_t q = blockIdx.x * 128 + threadIdx.x;
+    if (q >= d.nq) return;
+    const uint8_t *pb = buf + d.base;
+    const uint64_t *tb = tbase + d.tb;
+    const TOff to = toff(d.m, d.n_layers, d.nq);
+    const uint64_t *k = tb + to.k;
+    uint32_t pos = (uint32_t)tb[to.pos + q];
+    const fp g = k[K_G];
+    fp x = fp_mul(g, fp_pow(k[K_WNN], pos));
+    const Ext<M> z = x_load<M>(tb + to.z);
+    const Ext<M> zw = x_scale(z, k[K_WN]);
+    Ext<M> zb = z;
+    for (int s = 0; s < 3; s++) zb = x_mul(zb, zb); // z^8: the composition columns of TransactionAir
+    Ext<M> s1 = x_zero<M>(), s2 = x_zero<M>(), s3 = x_zero<M>();
+    const uint8_t *row = pb + d.trows + 8 * (size_t)q * TX_W;
+    for (uint32_t c = 0; c < TX_W; c++) {
+        const Ext<M> rv = x_base<M>(ld64(row + 8 * c));
+        s1 = x_add(s1, x_mul(x_load<M>(tb + to.da + M * c), x_sub(rv, ld_ext<M>(pb + d.ood + 8 * M * c))));
+        s2 = x_add(s2, x_mul(x_load<M>(tb + to.db + M * c), x_sub(rv, ld_ext<M>(pb + d.ood + 8 * M * (TX_W + c)))));
+    }
+    const uint8_t *crow = pb + d.crows + 8 * (size_t)q * TX_CE * M;
+    for (uint32_t i = 0; i < TX_CE; i++)
+        s3 = x_add(s3, x_mul(x_load<M>(tb + to.dd + M * i), x_sub(ld_ext<M>(crow + 8 * M * i), ld_ext<M>(pb + d.ood + 8 * M * (2 * TX_W + i)))));
+    const Ext<M> bx = x_base<M>(x);
+    const Ext<M> t = x_add(x_add(x_mul(s1, x_inv(x_sub(bx, z))), x_mul(s2, x_inv(x_sub(bx, zw)))), x_mul(s3, x_inv(x_sub(bx, zb))));
+    Ext<M> val = x_mul(t, x_add(x_load<M>(tb + to.dga), x_scale(x_load<M>(tb + to.dgb), x)));
+
+    const uint32_t f = 1u << d.log_f;
+    fp offset = g;
+    uint32_t lgl = d.log_N, rank = RK_NONE;
+    for (uint32_t l = 0; l < d.n_layers && rank == RK_NONE; l++) {
+        if (l >= (uint32_t)tb[to.st]) { slots[d.slot0 + 1 + d.n_open + q] = RK_NONE; return; } // the replay reported LAYER_COUNT(l)
+        const uint32_t lr = lgl - d.log_f, slot = (uint32_t)tb[to.slot + l * d.nq + q];
+        const uint8_t *lrow = pb + d.lrows[l] + 8 * (size_t)slot * f * M;
+        const uint32_t kk = pos >> lr;
+        Ext<M> v;
+        for (int c = 0; c < M; c++) v.c[c] = ld64(lrow + 8 * ((size_t)f * c + kk));
+        if (!x_eq(v, val)) { rank = RK_LAYER0 + 3 * l + 2; break; }
+        const uint32_t rp = pos & ((1u << lr) - 1);
+        const fp xl = fp_mul(offset, fp_pow(k[K_WL + l], rp));
+        const Ext<M> r = x_scale(x_load<M>(tb + to.alpha + M * l), fp_inv(xl));
+        Ext<M> acc = x_zero<M>(), rs = x_one<M>();
+        fp zs = FP_ONE; // zeta^-s
+        for (uint32_t s = 0; s < f; s++) {
+            Ext<M> cs = x_zero<M>();
+            fp w = FP_ONE; // zeta^-(s j)
+            for (uint32_t j = 0; j < f; j++) {
+                Ext<M> e;
+                for (int c = 0; c < M; c++) e.c[c] = ld64(lrow + 8 * ((size_t)f * c + j));
+                cs = x_add(cs, x_scale(e, w));
+                w = fp_mul(w, zs);
+            }
+            acc = x_add(acc, x_mul(x_scale(cs, k[K_INVF]), rs));
+            rs = x_mul(rs, r);
+            zs = fp_mul(zs, k[K_ZETA_INV]);
+        }
+        val = acc;
+        pos = rp;
+        for (uint32_t s = 0; s < d.log_f; s++) offset = fp_sqr(offset);
+        lgl = lr;
+    }
+    if (rank == RK_NONE) {
+        Ext<M> rv;
+        for (int c = 0; c < M; c++) rv.c[c] = ld64(pb + d.rem + 8 * ((size_t)c * d.R + pos));
+        if (!x_eq(rv, val)) rank = RK_REMAINDER_FOLDING;
+    }
+    slots[d.slot0 + 1 + d.n_open + q] = rank;
+}
+
+// One workgroup per (proof, remainder component): every word below p, and the coefficients of degree >= R / blowup of the inverse
+// transform all zero (evaluations over offset * <w_R>: the offset does not change which coefficients vanish).
+__global__ __launch_bounds__(256) void k_vfy_remainder(const uint8_t *__restrict__ buf, const VDesc *__restrict__ desc, const uint64_t *__restrict__ tbase,
+                                                       uint32_t *__restrict__ slots) {
+    __shared__ fp v[1024], wt[1024];
+    const VDesc &d = desc[blockIdx.y];
+    const uint32_t comp = blockIdx.x;
+    if (comp >= d.m) return;
+    const uint8_t *pb = buf + d.base;
+    const uint64_t *tb = tbase + d.tb;
+    const TOff to = toff(d.m, d.n_layers, d.nq);
+    const fp wrinv = tb[to.k + K_WRINV];
+    const uint32_t R = d.R;
+    bool ok = true;
+    for (uint32_t j = threadIdx.x; j < R; j += 256) {
+        const fp e = ld64(pb + d.rem + 8 * ((size_t)comp * R + j));
+        ok &= e < FP_P;
+        v[j] = e;
+        wt[j] = fp_pow(wrinv, j);
+    }
+    const int any_bad = __syncthreads_or(!ok);
+    bool high = false;
+    if (!any_bad)
+        for (uint32_t c = (R >> d.log_b) + threadIdx.x; c < R; c += 256) {
+            fp s = 0;
+            for (uint32_t j = 0; j < R; j++) s = fp_add(s, fp_mul(v[j], wt[(j * c) & (R - 1)]));
+            high |= s != 0;
+        }
+    const int any_high = __syncthreads_or(high);
+    if (threadIdx.x == 0)
+        slots[d.slot0 + 1 + d.n_open + d.nq + comp] = any_bad ? (uint32_t)RK_MALFORMED : any_high ? (uint32_t)RK_REMAINDER_DEGREE : (uint32_t)RK_NONE;
+}
+
+__device__ __forceinline__ int32_t rank_verdict(uint32_t r) {
+    if (r == RK_NONE) return CSTARK_PROOF_OK;
+    if (r == RK_MALFORMED) return CSTARK_PROOF_MALFORMED;
+    if (r == RK_OOD) return CSTARK_PROOF_OOD;
+    if (r == RK_REMAINDER_COMMITMENT) return CSTARK_PROOF_REMAINDER_COMMITMENT;
+    if (r == RK_POW) return CSTARK_PROOF_POW;
+    if (r < RK_LAYER0) return ((r - RK_OPENING0) & 1) ? CSTARK_PROOF_COMPOSITION_OPENING : CSTARK_PROOF_TRACE_OPENING;
+    if (r < RK_REMAINDER_FOLDING) return CSTARK_PROOF_LAYER_COUNT + (int32_t)((r - RK_LAYER0) % 3);
+    return r == RK_REMAINDER_FOLDING ? CSTARK_PROOF_REMAINDER_FOLDING : CSTARK_PROOF_REMAINDER_DEGREE;
+}
+// one workgroup per proof: the smallest rank among its slots and the replay's
+__global__ __launch_bounds__(256) void k_vfy_reduce(const VDesc *__restrict__ desc, const uint64_t *__restrict__ tbase, const uint32_t *__restrict__ slots,
+                                                    int32_t *__restrict__ verdicts) {
+    __shared__ uint32_t red[256];
+    const VDesc &d = desc[blockIdx.x];
+    const uint32_t n = 1 + d.n_open + d.nq + d.m;
+    uint32_t r = threadIdx.x == 0 ? (uint32_t)tbase[d.tb + toff(d.m, d.n_layers, d.nq).st + 1] : RK_NONE;
+    for (uint32_t i = threadIdx.x; i < n; i += 256) r = min(r, slots[d.slot0 + i]);
+    red[threadIdx.x] = r;
+    __syncthreads();
+    for (uint32_t s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] = min(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) verdicts[blockIdx.x] = rank_verdict(red[0]);
+}
+
+
+// ---- transcript replay on the device ----------------------------------------------------------------------------------------------
+// The prover's coin (coin.h) in one workgroup per proof.  Thread 0 walks the reseed chain; the draws that follow one seed are
+// independent, so the 256 lanes hash 256 consecutive counters at once and thread 0 takes the accepted candidates in counter order.
+constexpr int VT = 256;
+// the hash routines as calls: inlined at every use in one kernel they exceed the register file
+__device__ __noinline__ void nb3_chunk(const uint8_t *p, uint32_t len, uint64_t chunk, bool root, uint32_t (&cv)[8]) { vh::b3_chunk(p, len, chunk, root, cv); }
+__device__ __noinline__ void nb3_merge(uint32_t (*cvs)[8], uint32_t n, uint32_t (&out)[8]) { vh::b3_merge(cvs, n, out); }
+__device__ __noinline__ void nsha3(const uint8_t *p, uint32_t len, uint64_t (&out)[4]) { vh::sha3(p, len, out); }
+struct TShared {
+    uint8_t msg[160];          // the seed message: context || public inputs (129 bytes)
+    uint32_t seed[8];
+    uint32_t dig[8];
+    uint64_t cand[VT];
+    uint32_t flag[VT];
+    uint32_t cvs[32][8];       // chunk chaining values of one multi-chunk Blake3 message (at most 32 KB: the cubic remainder is 24 KB)
+    uint32_t pos[128], lpos[128];
+    uint64_t counter;
+    uint32_t got, ok_layers, rank, n_lpos;
+};
+// H(a[0..8) || b) for a 32-byte b given as eight words, or as one 64-bit integer (nb = 2 words): the coin's two message shapes
+__device__ __noinline__ void coin_hash(uint32_t hash, const uint32_t *a, const uint32_t *b, uint32_t nb, uint32_t (&out)[8]) {
+    if (hash == 1) {
+        uint64_t st[25];
+#pragma unroll
+        for (int i = 0; i < 25; i++) st[i] = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) st[i] = (uint64_t)a[2 * i] | ((uint64_t)a[2 * i + 1] << 32);
+        if (nb == 8) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) st[4 + i] = (uint64_t)b[2 * i] | ((uint64_t)b[2 * i + 1] << 32);
+            st[8] ^= 0x06;
+        } else {
+            st[4] = (uint64_t)b[0] | ((uint64_t)b[1] << 32);
+            st[5] ^= 0x06;
+        }
+        st[16] ^= 0x80ull << 56;
+        keccak::permute(st);
+#pragma unroll
+        for (int i = 0; i < 4; i++) { out[2 * i] = (uint32_t)st[i]; out[2 * i + 1] = (uint32_t)(st[i] >> 32); }
+    } else {
+        uint32_t mw[16];
+#pragma unroll
+        for (int i = 0; i < 8; i++) { mw[i] = a[i]; mw[8 + i] = (nb == 8 || i < 2) ? b[i] : 0u; out[i] = vh::iv(i); }
+        vh::compress(out, mw, 0, 4 * (8 + nb), vh::B3_CHUNK_START | vh::B3_CHUNK_END | vh::B3_ROOT);
+    }
+}
+__device__ __forceinline__ uint64_t first_u64(const uint32_t (&h)[8]) { return (uint64_t)h[0] | ((uint64_t)h[1] << 32); }
+__device__ __forceinline__ void with_int(uint32_t hash, const uint32_t *seed, uint64_t v, uint32_t (&out)[8]) {
+    const uint32_t w[8] = {(uint32_t)v, (uint32_t)(v >> 32), 0, 0, 0, 0, 0, 0};
+    coin_hash(hash, seed, w, 2, out);
+}
+// digest of len bytes at p into sh.dig (all threads call; Blake3 chunks in parallel, then thread 0 merges)
+__device__ void block_digest(uint32_t hash, const uint8_t *p, uint32_t len, TShared &sh) {
+    const uint32_t n = len <= 1024 ? 1 : (len + 1023) / 1024;
+    if (hash == 0 && n > 1) {
+        for (uint32_t c = threadIdx.x; c < n; c += VT) {
+            uint32_t cv[8];
+            nb3_chunk(p + 1024 * (size_t)c, len - 1024 * c < 1024 ? len - 1024 * c : 1024, c, false, cv);
+            for (int k = 0; k < 8; k++) sh.cvs[c][k] = cv[k];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (hash == 1) {
+            uint64_t h[4];
+            nsha3(p, len, h);
+            for (int i = 0; i < 4; i++) { sh.dig[2 * i] = (uint32_t)h[i]; sh.dig[2 * i + 1] = (uint32_t)(h[i] >> 32); }
+        } else {
+            uint32_t h[8];
+            if (n == 1) nb3_chunk(p, len, 0, true, h);
+            else nb3_merge(sh.cvs, n, h);
+            for (int i = 0; i < 8; i++) sh.dig[i] = h[i];
+        }
+    }
+    __syncthreads();
+}
+// seed <- H(seed || d), d 32 bytes at a 4-aligned address (thread 0)
+__device__ void reseed(uint32_t hash, TShared &sh, const uint32_t *d) {
+    uint32_t h[8];
+    coin_hash(hash, sh.seed, d, 8, h);
+    for (int i = 0; i < 8; i++) sh.seed[i] = h[i];
+    sh.counter = CSTARK_CONV_COIN_FIRST_COUNTER - 1;
+}
+__device__ __forceinline__ const uint32_t *w32(const uint8_t *p) { return reinterpret_cast<const uint32_t *>(p); }
+// `count` field elements (memory form) in draw order; put(i, v) runs on thread 0
+template <class Put> __device__ void draws(uint32_t hash, TShared &sh, uint32_t count, Put put) {
+    if (threadIdx.x == 0) sh.got = 0;
+    __syncthreads();
+    while (sh.got < count) {
+        uint32_t h[8];
+        with_int(hash, sh.seed, sh.counter + 1 + threadIdx.x, h);
+        sh.cand[threadIdx.x] = first_u64(h);
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int t = 0; t < VT && sh.got < count; t++) {
+                sh.counter++;
+                const uint64_t v = sh.cand[t];
+                if (!CSTARK_CONV_COIN_REJECT_ABOVE_P || v < FP_P) put(sh.got++, fp_from_u64(v));
+            }
+        __syncthreads();
+    }
+}
+// distinct values of (list & (rows - 1)) in first-occurrence order, list[0..n) -> sh.lpos, count -> sh.n_lpos (all threads call)
+__device__ void fold_list(TShared &sh, const uint32_t *list, uint32_t n, uint32_t rows) {
+    const uint32_t i = threadIdx.x;
+    if (i < n) {
+        const uint32_t r = list[i] & (rows - 1);
+        bool first = true;
+        for (uint32_t j = 0; j < i; j++) first &= (list[j] & (rows - 1)) != r;
+        sh.flag[i] = first;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t c = 0;
+        for (uint32_t j = 0; j < n; j++) if (sh.flag[j]) sh.cand[c++] = list[j] & (rows - 1);
+        sh.n_lpos = c;
+    }
+    __syncthreads();
+    if (i < sh.n_lpos) sh.lpos[i] = (uint32_t)sh.cand[i];
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(VT) void k_vfy_transcript(const uint8_t *__restrict__ buf, const VDesc *__restrict__ desc, uint64_t *__restrict__ tbase) {
+    __shared__ TShared sh;
+    const VDesc &d = desc[blockIdx.x];
+    const uint8_t *pb = buf + d.base;
+    uint64_t *T = tbase + d.tb;
+    const uint32_t m = d.m, nq = d.nq, nl = d.n_layers, hash = d.hash, tid = threadIdx.x;
+    const TOff to = toff(m, nl, nq);
+    for (uint32_t i = tid; i < K_WORDS; i += VT) T[to.k + i] = d.k[i];
+    if (tid == 0) {
+        // seed = H(width, log n | p | nq, log b, grinding, hash, extension, folding, log remainder | 14 public inputs, canonical)
+        uint32_t o = 0;
+        sh.msg[o++] = (uint8_t)TX_W; sh.msg[o++] = (uint8_t)d.log_n;
+        for (int i = 0; i < 8; i++) sh.msg[o++] = (uint8_t)(FP_P >> (8 * i));
+        const uint32_t ob[7] = {nq, d.log_b, d.grinding, hash, m - 1, 1u << d.log_f, d.log_rem};
+        for (int i = 0; i < 7; i++) sh.msg[o++] = (uint8_t)ob[i];
+        for (int i = 0; i < 14; i++) {
+            const uint64_t v = fp_to_u64(d.pub[i]);
+            for (int k = 0; k < 8; k++) sh.msg[o++] = (uint8_t)(v >> (8 * k));
+        }
+        if (hash == 1) {
+            uint64_t h[4];
+            nsha3(sh.msg, o, h);
+            for (int i = 0; i < 4; i++) { sh.seed[2 * i] = (uint32_t)h[i]; sh.seed[2 * i + 1] = (uint32_t)(h[i] >> 32); }
+        } else {
+            uint32_t h[8];
+            nb3_chunk(sh.msg, o, 0, true, h);
+            for (int i = 0; i < 8; i++) sh.seed[i] = h[i];
+        }
+        reseed(hash, sh, w32(pb + 52)); // trace root
+        sh.rank = RK_NONE;
+    }
+    __syncthreads();
+    // (alpha, beta) per constraint, then per assertion: elements of E (m draws each)
+    draws(hash, sh, 2 * (TX_NC + TX_NA) * m, [&](uint32_t i, uint64_t v) {
+        const uint32_t e = i / m, q = i % m, pair = e / 2, which = e % 2;
+        if (pair < TX_NC) T[(which ? to.tb : to.ta) + m * pair + q] = v;
+        else T[(which ? to.bb : to.ba) + m * (pair - TX_NC) + q] = v;
+    });
+    if (tid == 0) reseed(hash, sh, w32(pb + 84)); // constraint root
+    __syncthreads();
+    draws(hash, sh, m, [&](uint32_t i, uint64_t v) { T[to.z + i] = v; });
+    block_digest(hash, pb + d.ood, 8 * 2 * TX_W * m, sh);
+    if (tid == 0) reseed(hash, sh, sh.dig);
+    __syncthreads();
+    block_digest(hash, pb + d.ood + 8 * 2 * TX_W * m, 8 * TX_CE * m, sh);
+    if (tid == 0) reseed(hash, sh, sh.dig);
+    __syncthreads();
+    constexpr uint32_t PER = CSTARK_CONV_DEEP_DRAWS_PER_REGISTER;
+    draws(hash, sh, (TX_W * PER + TX_CE + 2) * m, [&](uint32_t i, uint64_t v) {
+        const uint32_t e = i / m, q = i % m;
+        if (e < TX_W * PER) {
+            const uint32_t c = e / PER, k = e % PER;
+            if (k == 0) T[to.da + m * c + q] = v;
+            else if (k == 1) T[to.db + m * c + q] = v;
+        } else {
+            const uint32_t e2 = e - TX_W * PER;
+            if (e2 < TX_CE) T[to.dd + m * e2 + q] = v;
+            else if (e2 == TX_CE) T[to.dga + q] = v;
+            else T[to.dgb + q] = v;
+        }
+    });
+    for (uint32_t l = 0; l < nl; l++) {
+        if (tid == 0) reseed(hash, sh, w32(pb + 120 + 32 * l));
+        __syncthreads();
+        draws(hash, sh, m, [&](uint32_t i, uint64_t v) { T[to.alpha + m * l + i] = v; });
+    }
+    const uint8_t *rem_commit = pb + 120 + 32 * nl;
+    block_digest(hash, pb + d.rem, 8 * d.R * m, sh);
+    if (tid == 0) {
+        const uint32_t *rc = w32(rem_commit);
+        bool same = true;
+        for (int i = 0; i < 8; i++) same &= sh.dig[i] == rc[i];
+        if (!same) sh.rank = RK_REMAINDER_COMMITMENT;
+        reseed(hash, sh, rc);
+        const uint32_t *nw = w32(pb + d.ood + 8 * (2 * TX_W + TX_CE) * m);
+        const uint64_t nonce = (uint64_t)nw[0] | ((uint64_t)nw[1] << 32);
+        uint32_t h[8];
+        with_int(hash, sh.seed, nonce, h);
+        if (d.grinding && (first_u64(h) & ((1ull << d.grinding) - 1)) && sh.rank == RK_NONE) sh.rank = RK_POW;
+        for (int i = 0; i < 8; i++) sh.seed[i] = h[i]; // reseed_int(nonce)
+        sh.counter = CSTARK_CONV_COIN_FIRST_COUNTER - 1;
+        sh.got = 0;
+    }
+    __syncthreads();
+    // query positions: nq distinct integers below N (duplicates skipped: CSTARK_CONV_QUERY_DEDUP)
+    const uint32_t Nmask = (1u << d.log_N) - 1;
+    while (sh.got < nq) {
+        uint32_t h[8];
+        with_int(hash, sh.seed, sh.counter + 1 + tid, h);
+        const uint32_t v = (uint32_t)(first_u64(h) & Nmask);
+        sh.cand[tid] = v;
+        __syncthreads();
+        bool fresh = true;
+        if (CSTARK_CONV_QUERY_DEDUP) {
+            for (uint32_t j = 0; j < sh.got; j++) fresh &= sh.pos[j] != v;
+            for (uint32_t j = 0; j < tid; j++) fresh &= (uint32_t)sh.cand[j] != v;
+        }
+        sh.flag[tid] = fresh;
+        __syncthreads();
+        if (tid == 0)
+            for (int t = 0; t < VT && sh.got < nq; t++) {
+                sh.counter++;
+                if (sh.flag[t]) sh.pos[sh.got++] = (uint32_t)sh.cand[t];
+            }
+        __syncthreads();
+    }
+    for (uint32_t q = tid; q < nq; q += VT) T[to.pos + q] = sh.pos[q];
+    // folded positions of every layer and the row slot of each query, up to the first layer whose stated count differs
+    if (tid == 0) sh.ok_layers = nl;
+    __syncthreads();
+    uint32_t lg = d.log_N, prev_n = nq;
+    for (uint32_t l = 0; l < nl; l++) {
+        const uint32_t rows = 1u << (lg - d.log_f);
+        fold_list(sh, l == 0 ? sh.pos : sh.lpos, prev_n, rows);
+        if (sh.n_lpos != d.npos[l]) {
+            if (tid == 0) { sh.ok_layers = l; sh.rank = min(sh.rank, RK_LAYER0 + 3 * l); }
+            break;
+        }
+        for (uint32_t t = tid; t < sh.n_lpos; t += VT) T[to.lpos + l * nq + t] = sh.lpos[t];
+        for (uint32_t q = tid; q < nq; q += VT) {
+            const uint32_t r = sh.pos[q] & (rows - 1);
+            uint32_t slot = 0;
+            for (uint32_t j = 0; j < sh.n_lpos; j++) if (sh.lpos[j] == r) slot = j;
+            T[to.slot + l * nq + q] = slot;
+        }
+        prev_n = sh.n_lpos;
+        lg -= d.log_f;
+        __syncthreads();
+    }
+    __syncthreads();
+    if (tid == 0) { T[to.st] = sh.ok_layers; T[to.st + 1] = sh.rank; }
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------------
+constexpr size_t VFY_CHUNK_BYTES = 64ull << 20; // staging budget of one chunk: a large count never sizes more than this
+enum { VFY_EVENTS = CSTARK_VERIFY_NUM_STAGES };
+
+struct VerifyArena {
+    uint8_t *h_stage = nullptr, *d_stage = nullptr;
+    size_t stage_bytes = 0;
+    void *d_scratch = nullptr;
+    size_t scratch_bytes = 0;
+    int32_t *h_verdicts = nullptr;
+    size_t verdict_cap = 0;
+    uint64_t *d_pcoef = nullptr;           // periodic coefficients [depth slot][48][1024], depth = 2^(slot+1) - 1
+    bool pcoef_ready[6] = {};
+    hipEvent_t ev[VFY_EVENTS] = {};
+    float ms[CSTARK_VERIFY_NUM_STAGES] = {};
+    uint64_t h2d_bytes = 0;              // bytes copied host -> device by the last cstark_tx_verify
+    bool timed = false;
+};
+
+void verify_arena_free(VerifyArena *a) {
+    if (!a) return;
+    if (a->h_stage) (void)hipHostFree(a->h_stage);
+    if (a->d_stage) (void)hipFree(a->d_stage);
+    if (a->d_scratch) (void)hipFree(a->d_scratch);
+    if (a->h_verdicts) (void)hipHostFree(a->h_verdicts);
+    if (a->d_pcoef) (void)hipFree(a->d_pcoef);
+    for (hipEvent_t e : a->ev) if (e) (void)hipEventDestroy(e);
+    delete a;
+}
+
+namespace {
+
+struct Staged {
+    uint32_t index;     // position in the caller's arrays
+    const uint8_t *bytes;
+    Layout L;
+    VDesc d;
+};
+
+// what the device needs besides the proof bytes: the domain constants and the public inputs (the transcript itself is replayed on the
+// device, k_vfy_transcript)
+void describe(const Layout &L, const uint64_t *iroot, const uint64_t *froot, VDesc &d) {
+    using namespace host;
+    const uint64_t n = 1ull << L.log_n;
+    uint64_t *K = d.k;
+    K[K_WN] = root_of_unity(L.log_n);
+    K[K_WNN] = root_of_unity(L.log_N);
+    K[K_WLAST] = pow(K[K_WN], n - 1);
+    K[K_G] = lde_offset();
+    for (int g = 0; g < 5; g++) K[K_ADJ + g] = tx_group_adjustment(g, n, n * TX_CE);
+    K[K_BADJ] = tx_boundary_adjustment(n, n * TX_CE);
+    K[K_INVF] = inv(from_u64(L.f));
+    K[K_ZETA_INV] = inv(root_of_unity(L.log_f));
+    K[K_WRINV] = inv(root_of_unity(ilog2(L.R)));
+    K[K_PUB] = iroot[0]; K[K_PUB + 1] = iroot[1]; K[K_PUB + 2] = froot[0]; K[K_PUB + 3] = froot[1];
+    unsigned lg = L.log_N;
+    for (uint32_t l = 0; l < L.n_layers; l++) { K[K_WL + l] = root_of_unity(lg); lg -= L.log_f; }
+    for (int i = 0; i < 7; i++) { d.pub[i] = iroot[i]; d.pub[7 + i] = froot[i]; }
+    d.hash = L.opt[3]; d.grinding = L.opt[2]; d.log_rem = ilog2(L.opt[6]);
+    for (uint32_t l = 0; l < VMAX_LAYERS; l++) d.npos[l] = l < L.n_layers ? L.npos[l] : 0;
+}
+
+template <int M> Lagrange<M> lagrange_weights(uint32_t K) {
+    // weights of t -> (the adjoined root) for samples at t = 0..K-1: lag_j = prod_{q != j} (root - q) / (j - q)
+    using namespace host;
+    Lagrange<M> L{};
+    if (M == 1) { L.w[0][0] = ONE; return L; }
+    for (uint32_t j = 0; j < K; j++) {
+        EX num = ex_one();
+        uint64_t den = ONE;
+        for (uint32_t q = 0; q < K; q++) {
+            if (q == j) continue;
+            EX r = ex_zero();
+            r.c[0] = sub(0, from_u64(q));
+            r.c[1] = ONE;
+            num = ex_mul(num, r, M);
+            den = mul(den, j > q ? from_u64(j - q) : sub(0, from_u64(q - j)));
+        }
+        const EX w = ex_scale(num, inv(den));
+        for (int c = 0; c < M; c++) L.w[j][c] = w.c[c];
+    }
+    return L;
+}
+
+int ensure_pcoef(cstark_ctx *c, VerifyArena *a, uint32_t depth, uint32_t &slot) {
+    slot = ilog2(depth + 1) - 1;
+    if (!a->d_pcoef) HIP_TRY(hipMalloc(&a->d_pcoef, 6 * 48 * 1024 * 8));
+    if (a->pcoef_ready[slot]) return CSTARK_OK;
+    std::vector<uint64_t> cols;
+    if (!host::tx_periodic_columns(depth, cols)) return fail(CSTARK_ERR_INVALID_ARG, "unsupported Merkle depth");
+    for (int col = 0; col < 48; col++) host::intt_small(cols.data() + (size_t)col * 1024, 10);
+    HIP_TRY(hipMemcpyAsync(a->d_pcoef + (size_t)slot * 48 * 1024, cols.data(), cols.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    a->pcoef_ready[slot] = true;
+    return CSTARK_OK;
+}
+
+template <class T> T *carve(uint8_t *base, size_t &off, size_t count) {
+    off = (off + 15) & ~(size_t)15;
+    T *p = reinterpret_cast<T *>(base + off);
+    off += count * sizeof(T);
+    return p;
+}
+
+// Verifies the staged proofs of one chunk; verdicts[i] for staged[i].
+int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *out, double host_ms) {
+    const hipStream_t s = c->stream;
+    const uint32_t P = (uint32_t)st.size();
+    // ---- staging block: proofs | descriptors | openings | group lists; the transcript blocks live on the device only
+    size_t off = 0, t_words = 0;
+    std::vector<size_t> pofs(P), tofs(P);
+    size_t n_open = 0, n_slots = 0;
+    for (uint32_t i = 0; i < P; i++) {
+        const Layout &L = st[i].L;
+        off = (off + 15) & ~(size_t)15; pofs[i] = off; off += L.rem + 8 * (size_t)L.R * L.m;
+        tofs[i] = t_words; t_words += (toff(L.m, L.n_layers, L.nq).words + 1) & ~(size_t)1;
+        uint32_t no = 2 * L.nq;
+        for (uint32_t l = 0; l < L.n_layers; l++) no += L.npos[l];
+        st[i].d.n_open = no;
+        st[i].d.slot0 = (uint32_t)n_slots;
+        n_open += no;
+        n_slots += 1 + no + L.nq + L.m;
+    }
+    const size_t desc_off = (off + 15) & ~(size_t)15;
+    const size_t open_off = (desc_off + P * sizeof(VDesc) + 15) & ~(size_t)15;
+    const size_t grp_off = (open_off + n_open * sizeof(VOpen) + 15) & ~(size_t)15;
+    const size_t total = grp_off + 3 * (size_t)P * 4 + 16;
+    if (total > a->stage_bytes) {
+        HIP_TRY(hipStreamSynchronize(s));
+        if (a->h_stage) { HIP_TRY(hipHostFree(a->h_stage)); a->h_stage = nullptr; }
+        if (a->d_stage) { HIP_TRY(hipFree(a->d_stage)); a->d_stage = nullptr; }
+        a->stage_bytes = 0;
+        HIP_TRY(hipHostMalloc(&a->h_stage, total, hipHostMallocDefault));
+        HIP_TRY(hipMalloc(&a->d_stage, total));
+        a->stage_bytes = total;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    uint8_t *H = a->h_stage;
+    VDesc *hd = reinterpret_cast<VDesc *>(H + desc_off);
+    VOpen *ho = reinterpret_cast<VOpen *>(H + open_off);
+    uint32_t *hg = reinterpret_cast<uint32_t *>(H + grp_off); // [3][P]: proofs of each extension degree
+    uint32_t gcount[3] = {0, 0, 0}, frames[3] = {0, 0, 0};
+    const uint32_t KM[3] = {1, 7 * 1 + 4, 7 * 2 + 4}; // samples per frame: degree <= 7 (m - 1) along t
+    std::vector<VOpen> opens;
+    opens.reserve(n_open);
+    for (uint32_t i = 0; i < P; i++) {
+        Staged &S = st[i];
+        const Layout &L = S.L;
+        memcpy(H + pofs[i], S.bytes, L.rem + 8 * (size_t)L.R * L.m);
+        VDesc &d = S.d;
+        d.base = pofs[i]; d.tb = tofs[i];
+        d.ood = (uint32_t)L.ood; d.trows = (uint32_t)L.trows; d.tpaths = (uint32_t)L.tpaths; d.crows = (uint32_t)L.crows;
+        d.cpaths = (uint32_t)L.cpaths; d.rem = (uint32_t)L.rem;
+        for (uint32_t l = 0; l < VMAX_LAYERS; l++) d.lrows[l] = (uint32_t)L.lrows[l];
+        d.log_n = L.log_n; d.log_N = L.log_N; d.nq = L.nq; d.log_f = L.log_f; d.n_layers = L.n_layers; d.m = L.m; d.R = L.R; d.log_b = L.log_b;
+        const uint32_t mi = L.m - 1;
+        d.frame0 = frames[mi];
+        frames[mi] += KM[mi];
+        hg[mi * P + gcount[mi]++] = i;
+        hd[i] = d;
+        const uint32_t hash = L.opt[3];
+        uint32_t sl = d.slot0 + 1;
+        for (uint32_t q = 0; q < L.nq; q++) {
+            opens.push_back(VOpen{i, (uint32_t)(L.trows + 8 * (size_t)q * TX_W), (uint32_t)(L.tpaths + 32 * (size_t)q * L.log_N), 52u, TX_W, L.log_N,
+                                  VNO_LAYER, q, RK_OPENING0 + 2 * q, sl++, hash});
+            opens.push_back(VOpen{i, (uint32_t)(L.crows + 8 * (size_t)q * TX_CE * L.m), (uint32_t)(L.cpaths + 32 * (size_t)q * L.log_N), 84u,
+                                  TX_CE * L.m, L.log_N, VNO_LAYER, q, RK_OPENING0 + 2 * q + 1, sl++, hash});
+        }
+        unsigned lg = L.log_N;
+        // every layer's rows: from the first layer whose count differs (LAYER_COUNT, found by the replay) there are no positions to
+        // check the paths against, but their words must still be canonical -- those lanes report MALFORMED only
+        for (uint32_t l = 0; l < L.n_layers; l++) {
+            const uint32_t depth = lg - L.log_f;
+            for (uint32_t t = 0; t < L.npos[l]; t++)
+                opens.push_back(VOpen{i, (uint32_t)(L.lrows[l] + 8 * (size_t)t * L.f * L.m), (uint32_t)(L.lpaths[l] + 32 * (size_t)t * depth),
+                                      (uint32_t)(120 + 32 * l), L.f * L.m, depth, l, t, RK_LAYER0 + 3 * l + 1, sl++, hash});
+            lg = depth;
+        }
+    }
+    // the lanes of a wave walk paths of one hash and one length: no divergence between trace paths of 23 levels and layer paths of 7
+    std::stable_sort(opens.begin(), opens.end(), [](const VOpen &x, const VOpen &y) {
+        return x.hash != y.hash ? x.hash < y.hash : x.words != y.words ? x.words < y.words : x.depth < y.depth;
+    });
+    memcpy(ho, opens.data(), opens.size() * sizeof(VOpen));
+    const auto t1 = std::chrono::steady_clock::now();
+    host_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
+
+    // ---- device scratch: transcript blocks | slots | verdicts | per degree: frames cur, next, per, values | bad flags
+    size_t need = 8 * t_words + 16;
+    need += 4 * n_slots + 16;
+    need += 4 * (size_t)P + 16;
+    for (int g = 0; g < 3; g++) need += 8 * (size_t)frames[g] * (2 * TX_W + 48 + TX_NC) + 4 * (size_t)gcount[g] + 64;
+    if (need > a->scratch_bytes) {
+        HIP_TRY(hipStreamSynchronize(s));
+        if (a->d_scratch) { HIP_TRY(hipFree(a->d_scratch)); a->d_scratch = nullptr; }
+        a->scratch_bytes = 0;
+        HIP_TRY(hipMalloc(&a->d_scratch, need));
+        a->scratch_bytes = need;
+    }
+    if (P > a->verdict_cap) {
+        if (a->h_verdicts) { HIP_TRY(hipHostFree(a->h_verdicts)); a->h_verdicts = nullptr; }
+        a->verdict_cap = 0;
+        HIP_TRY(hipHostMalloc(&a->h_verdicts, 4 * (size_t)P, hipHostMallocDefault));
+        a->verdict_cap = P;
+    }
+    uint8_t *D = (uint8_t *)a->d_scratch;
+    size_t so = 0;
+    uint64_t *d_tb = carve<uint64_t>(D, so, t_words);
+    uint32_t *d_slots = carve<uint32_t>(D, so, n_slots);
+    int32_t *d_verd = carve<int32_t>(D, so, P);
+    fp *f_cur[3], *f_nxt[3], *f_per[3], *f_val[3];
+    uint32_t *f_bad[3];
+    for (int g = 0; g < 3; g++) {
+        f_cur[g] = carve<fp>(D, so, (size_t)frames[g] * TX_W);
+        f_nxt[g] = carve<fp>(D, so, (size_t)frames[g] * TX_W);
+        f_per[g] = carve<fp>(D, so, (size_t)frames[g] * 48);
+        f_val[g] = carve<fp>(D, so, (size_t)frames[g] * TX_NC);
+        f_bad[g] = carve<uint32_t>(D, so, gcount[g]);
+    }
+    const uint8_t *dbuf = a->d_stage;
+    const VDesc *d_desc = reinterpret_cast<const VDesc *>(dbuf + desc_off);
+    const VOpen *d_open = reinterpret_cast<const VOpen *>(dbuf + open_off);
+    const uint32_t *d_grp = reinterpret_cast<const uint32_t *>(dbuf + grp_off);
+
+    for (int e = 0; e < VFY_EVENTS; e++)
+        if (!a->ev[e]) HIP_TRY(hipEventCreate(&a->ev[e]));
+    HIP_TRY(hipEventRecord(a->ev[0], s));
+    const size_t copy_bytes = grp_off + 3 * (size_t)P * 4;
+    HIP_TRY(hipMemcpyAsync(a->d_stage, H, copy_bytes, hipMemcpyHostToDevice, s));
+    a->h2d_bytes += copy_bytes;
+    HIP_TRY(hipEventRecord(a->ev[1], s));
+    hipLaunchKernelGGL(k_vfy_transcript, dim3(P), dim3(VT), 0, s, dbuf, d_desc, d_tb);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(a->ev[2], s));
+    for (int g = 0; g < 3; g++) {
+        const uint32_t G = gcount[g];
+        if (!G) continue;
+        const uint32_t F = frames[g], K = KM[g];
+        const uint32_t *gp = d_grp + g * P;
+        if (g == 0) {
+            hipLaunchKernelGGL(k_vfy_ood_frames<1>, dim3(G), dim3(128), 0, s, dbuf, d_desc, gp, d_tb, a->d_pcoef, K, F, f_cur[g], f_nxt[g], f_per[g], f_bad[g]);
+        } else if (g == 1) {
+            hipLaunchKernelGGL(k_vfy_ood_frames<2>, dim3(G), dim3(128), 0, s, dbuf, d_desc, gp, d_tb, a->d_pcoef, K, F, f_cur[g], f_nxt[g], f_per[g], f_bad[g]);
+        } else {
+            hipLaunchKernelGGL(k_vfy_ood_frames<3>, dim3(G), dim3(128), 0, s, dbuf, d_desc, gp, d_tb, a->d_pcoef, K, F, f_cur[g], f_nxt[g], f_per[g], f_bad[g]);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_eval_frames(f_cur[g], f_nxt[g], f_per[g], f_val[g], F, s));
+        const dim3 cg((G + 63) / 64);
+        if (g == 0) hipLaunchKernelGGL(k_vfy_ood_check<1>, cg, dim3(64), 0, s, dbuf, d_desc, gp, G, K, F, f_val[g], f_bad[g], lagrange_weights<1>(K), d_tb, d_slots);
+        else if (g == 1) hipLaunchKernelGGL(k_vfy_ood_check<2>, cg, dim3(64), 0, s, dbuf, d_desc, gp, G, K, F, f_val[g], f_bad[g], lagrange_weights<2>(K), d_tb, d_slots);
+        else hipLaunchKernelGGL(k_vfy_ood_check<3>, cg, dim3(64), 0, s, dbuf, d_desc, gp, G, K, F, f_val[g], f_bad[g], lagrange_weights<3>(K), d_tb, d_slots);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(a->ev[3], s));
+    if (n_open) {
+        hipLaunchKernelGGL(k_vfy_openings, dim3((unsigned)((n_open + 127) / 128)), dim3(128), 0, s, dbuf, d_desc, d_open, (uint32_t)n_open, d_tb, d_slots);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(a->ev[4], s));
+    for (int g = 0; g < 3; g++) {
+        const uint32_t G = gcount[g];
+        if (!G) continue;
+        const dim3 grid(1, G); // num_queries <= 128: one workgroup per proof
+        if (g == 0) hipLaunchKernelGGL(k_vfy_fri<1>, grid, dim3(128), 0, s, dbuf, d_desc, d_grp + g * P, d_tb, d_slots);
+        else if (g == 1) hipLaunchKernelGGL(k_vfy_fri<2>, grid, dim3(128), 0, s, dbuf, d_desc, d_grp + g * P, d_tb, d_slots);
+        else hipLaunchKernelGGL(k_vfy_fri<3>, grid, dim3(128), 0, s, dbuf, d_desc, d_grp + g * P, d_tb, d_slots);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(a->ev[5], s));
+    hipLaunchKernelGGL(k_vfy_remainder, dim3(3, P), dim3(256), 0, s, dbuf, d_desc, d_tb, d_slots);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_vfy_reduce, dim3(P), dim3(256), 0, s, d_desc, d_tb, d_slots, d_verd);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(a->h_verdicts, d_verd, 4 * (size_t)P, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(a->ev[6], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (uint32_t i = 0; i < P; i++) out[st[i].index] = a->h_verdicts[i];
+    a->ms[0] += (float)host_ms;
+    for (int e = 1; e < VFY_EVENTS; e++) {
+        float t;
+        HIP_TRY(hipEventElapsedTime(&t, a->ev[e - 1], a->ev[e]));
+        a->ms[e] += t;
+    }
+    return CSTARK_OK;
+}
+
+} // namespace
+} // namespace cs
+
+using namespace cs;
+
+extern "C" {
+
+int cstark_proof_inspect(const uint8_t *proof, size_t len, cstark_proof_info *info, int32_t *verdict) {
+    if (!proof || !info || !verdict) return fail(CSTARK_ERR_INVALID_ARG, "cstark_proof_inspect: null argument");
+    Layout L;
+    *verdict = parse_layout(proof, len, L);
+    memset(info, 0, sizeof *info);
+    if (len >= 52 && memcmp(proof, "CSTK", 4) == 0) {
+        info->air = rd32(proof + 8); info->trace_width = rd32(proof + 12); info->log_n = rd32(proof + 16); info->header_word = rd32(proof + 20);
+        uint32_t *o = &info->options.num_queries;
+        for (int i = 0; i < 7; i++) o[i] = rd32(proof + 24 + 4 * i);
+    }
+    return CSTARK_OK;
+}
+
+int cstark_tx_verify(cstark_ctx *c, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens, const uint64_t *initial_roots,
+                     const uint64_t *final_roots, const cstark_options *expected, int32_t *verdicts) {
+    if (!c) return fail(CSTARK_ERR_INVALID_ARG, "cstark_tx_verify: null context");
+    if (count == 0) return CSTARK_OK;
+    if (!proofs || !proof_lens || !initial_roots || !final_roots || !verdicts) return fail(CSTARK_ERR_INVALID_ARG, "cstark_tx_verify: null argument");
+    for (size_t i = 0; i < 14 * (size_t)count; i++)
+        if ((i % 14 < 7 ? initial_roots[(i / 14) * 7 + i % 14] : final_roots[(i / 14) * 7 + i % 14 - 7]) >= host::P)
+            return fail(CSTARK_ERR_INVALID_ARG, "cstark_tx_verify: a root word is not a field element");
+    for (uint32_t i = 0; i < count; i++)
+        if (!proofs[i] && proof_lens[i]) return fail(CSTARK_ERR_INVALID_ARG, "cstark_tx_verify: null proof");
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->verify) c->verify = new VerifyArena();
+    VerifyArena *a = c->verify;
+    for (float &m : a->ms) m = 0;
+    a->h2d_bytes = 0;
+    a->timed = false;
+    std::vector<Staged> st;
+    size_t chunk_bytes = 0;
+    double host_ms = 0;
+    auto t0 = std::chrono::steady_clock::now();
+    for (uint32_t i = 0; i < count; i++) {
+        const uint8_t *b = proofs[i];
+        Staged S;
+        S.index = i;
+        S.bytes = b;
+        int v = b ? parse_layout(b, proof_lens[i], S.L) : CSTARK_PROOF_MALFORMED;
+        // another AIR's proof: no kernel reads it, so its elements are scanned here (a word >= p is MALFORMED before UNSUPPORTED)
+        if (v == CSTARK_PROOF_OK && S.L.air != CSTARK_AIR_STATE_TRANSITION) v = elements_canonical(b, S.L) ? CSTARK_PROOF_UNSUPPORTED : CSTARK_PROOF_MALFORMED;
+        if (v == CSTARK_PROOF_OK && expected) {
+            const uint32_t *e = &expected->num_queries;
+            if (memcmp(e, S.L.opt, sizeof S.L.opt) != 0) v = elements_canonical(b, S.L) ? CSTARK_PROOF_OPTIONS_MISMATCH : CSTARK_PROOF_MALFORMED;
+        }
+        if (v != CSTARK_PROOF_OK) { verdicts[i] = v; continue; }
+        memset(&S.d, 0, sizeof S.d);
+        RC_TRY(ensure_pcoef(c, a, S.L.word, S.d.depth_slot));
+        describe(S.L, initial_roots + 7 * (size_t)i, final_roots + 7 * (size_t)i, S.d);
+        const size_t bytes = proof_lens[i] + sizeof(VDesc) + sizeof(VOpen) * (2 + S.L.nq * (size_t)(2 + S.L.n_layers)) + 256;
+        if (!st.empty() && chunk_bytes + bytes > VFY_CHUNK_BYTES) {
+            host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            RC_TRY(run_chunk(c, a, st, verdicts, host_ms));
+            st.clear(); chunk_bytes = 0; host_ms = 0;
+            t0 = std::chrono::steady_clock::now();
+        }
+        st.push_back(std::move(S));
+        chunk_bytes += bytes;
+    }
+    host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (!st.empty()) RC_TRY(run_chunk(c, a, st, verdicts, host_ms));
+    else a->ms[0] += (float)host_ms;
+    a->timed = true;
+    return CSTARK_OK;
+}
+
+int cstark_verify_stage_ms(cstark_ctx *c, float *ms) {
+    if (!c || !ms) return fail(CSTARK_ERR_INVALID_ARG, "null argument");
+    if (!c->verify || !c->verify->timed) return fail(CSTARK_ERR_INVALID_ARG, "no verification has run on this context");
+    for (int i = 0; i < CSTARK_VERIFY_NUM_STAGES; i++) ms[i] = c->verify->ms[i];
+    return CSTARK_OK;
+}
+
+int cstark_verify_h2d_bytes(cstark_ctx *c, uint64_t *bytes) {
+    if (!c || !bytes) return fail(CSTARK_ERR_INVALID_ARG, "null argument");
+    if (!c->verify || !c->verify->timed) return fail(CSTARK_ERR_INVALID_ARG, "no verification has run on this context");
+    *bytes = c->verify->h2d_bytes;
+    return CSTARK_OK;
+}
+
+} // extern "C"

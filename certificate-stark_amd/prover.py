@@ -171,9 +171,9 @@ def get_example_options():
 
 
 class TransactionExample:
-    """src/lib.rs:92-150 without the random witness synthesis: holds options + metadata, proves on the GPU.
-    Verification is CPU work in the reference (winterfell::verify) and outside this backend; the tests use the
-    restated CPU verifier of the test suite."""
+    """src/lib.rs:92-150 without the random witness synthesis: holds options + metadata, proves and verifies on the GPU.
+    verify() checks a proof against this example's public inputs (first initial root, final root) with cstark_tx_verify and
+    raises VerifierError on rejection, as the reference's verify returns Err(VerifierError)."""
 
     def __init__(self, options, tx_metadata, backend=None):
         self.options, self.tx_metadata = options, tx_metadata
@@ -181,6 +181,14 @@ class TransactionExample:
 
     def prove(self):
         return self.prover.prove(self.tx_metadata)
+
+    def verify(self, proof):
+        """winterfell::verify::<TransactionAir>(proof, pub_inputs) (src/lib.rs:144-150): the proof's own options are accepted."""
+        from .verify import VerifierError
+        initial_root, final_root = self.pub_inputs()
+        v = int(self.prover.backend.tx_verify([proof], initial_root, final_root)[0])
+        if v != 0:
+            raise VerifierError(v)
 
     def pub_inputs(self):
         return self.tx_metadata.initial_roots[0], self.tx_metadata.final_root

@@ -413,6 +413,56 @@ int cstark_tx_witness_generate(cstark_tx_witness *w, uint64_t seed);
 /* n_sig messages [n][28] (public key || 16 elements) with their signatures (R.x [n][6], s [n][32]). */
 int cstark_schnorr_witness_generate(uint32_t n_sig, uint64_t seed, uint64_t *messages, uint64_t *sig_rx, uint8_t *sig_s);
 
+/* ---- verification (TransactionExample::verify, src/lib.rs:144-150: winterfell::verify over this library's own proof layout) -------
+ * The call's status (cstark_status) is kept apart from the proof's verdict.  A verdict names the FIRST check that fails, in this
+ * order: layout (MALFORMED, then UNSUPPORTED) | OPTIONS_MISMATCH | OOD | REMAINDER_COMMITMENT | POW | per query q = 0..nq-1:
+ * TRACE_OPENING(q), COMPOSITION_OPENING(q) | per FRI layer l: LAYER_COUNT(l), LAYER_OPENING(l), LAYER_FOLDING(l) (layer 0: the DEEP
+ * values against the layer-0 rows) | REMAINDER_FOLDING | REMAINDER_DEGREE.  A field element word >= p anywhere in the proof is
+ * MALFORMED (the prover never writes one). */
+typedef enum cstark_verdict {
+    CSTARK_PROOF_OK = 0,                 /* verify: accepted;  inspect: well-formed */
+    CSTARK_PROOF_MALFORMED = 1,          /* layout, counts, lengths, non-canonical field element, trailing bytes */
+    CSTARK_PROOF_UNSUPPORTED = 2,        /* well-formed proof of another AIR (MerkleAir, SchnorrAir, RangeProofAir, RescueAir) */
+    CSTARK_PROOF_OPTIONS_MISMATCH = 3,   /* differs from `expected` */
+    CSTARK_PROOF_OOD = 4,                /* out-of-domain constraint evaluations inconsistent (also: wrong public inputs) */
+    CSTARK_PROOF_REMAINDER_COMMITMENT = 5,
+    CSTARK_PROOF_POW = 6,
+    CSTARK_PROOF_TRACE_OPENING = 7,
+    CSTARK_PROOF_COMPOSITION_OPENING = 8,
+    CSTARK_PROOF_LAYER_COUNT = 9,        /* a layer's number of openings differs from the derived positions */
+    CSTARK_PROOF_LAYER_OPENING = 10,
+    CSTARK_PROOF_LAYER_FOLDING = 11,
+    CSTARK_PROOF_REMAINDER_FOLDING = 12,
+    CSTARK_PROOF_REMAINDER_DEGREE = 13
+} cstark_verdict;
+
+typedef struct cstark_proof_info {
+    uint32_t air, trace_width, log_n, header_word;   /* header_word: the Merkle depth for TransactionAir */
+    cstark_options options;
+} cstark_proof_info;
+
+/* Host only: no context, no device.  Checks the complete layout of a proof of any of the five AIRs (see "Proof layout" at
+ * cstark_tx_prove: every count against the stated options before anything is read, no trailing bytes, the header bounds the prover
+ * enforces) and fills *info (zeroed when the header cannot be read).  *verdict = CSTARK_PROOF_OK or CSTARK_PROOF_MALFORMED; field
+ * elements are not read (their canonical form is checked by cstark_tx_verify).  Returns CSTARK_ERR_INVALID_ARG only for null pointers. */
+int cstark_proof_inspect(const uint8_t *proof, size_t len, cstark_proof_info *info, int32_t *verdict);
+
+/* TransactionExample::verify for `count` proofs in one call (count = 1 for a single proof).  initial_roots / final_roots: [count][7],
+ * memory form.  expected: NULL = each proof's own options (the reference's semantics), else every proof must state exactly these.
+ * Proofs of one call may differ in every header field (sizes, depths, hashes, extensions); a proof's verdict does not depend on the
+ * others.  Synchronous: verdicts[count] are on the host when it returns CSTARK_OK.  Negative status only for misuse (null pointers with
+ * count > 0, a root word >= p) or a HIP failure.  The verifier's buffers belong to the context; the prover's are not touched. */
+int cstark_tx_verify(cstark_ctx *ctx, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens,
+                     const uint64_t *initial_roots, const uint64_t *final_roots, const cstark_options *expected,
+                     int32_t *verdicts);
+/* Stage times of the last cstark_tx_verify on this context, like cstark_prove_stage_ms (milliseconds, summed over its chunks):
+ * host parse + staging, host-to-device copy, transcript replay (on the device), out-of-domain check, Merkle openings, DEEP + FRI,
+ * remainder + reduction + device-to-host copy.  cstark_verify_h2d_bytes: the bytes the same call copied host -> device (proof bytes,
+ * descriptors, opening records). */
+#define CSTARK_VERIFY_NUM_STAGES 7
+int cstark_verify_stage_ms(cstark_ctx *ctx, float *ms /* [CSTARK_VERIFY_NUM_STAGES] */);
+int cstark_verify_h2d_bytes(cstark_ctx *ctx, uint64_t *bytes);
+
 /* ---- device memory helpers for callers without a HIP runtime of their own (the Rust shim) ---- */
 int cstark_malloc(cstark_ctx *ctx, size_t bytes, void **d_ptr);
 int cstark_free(cstark_ctx *ctx, void *d_ptr);

@@ -5,7 +5,7 @@
 //   ProofOptions            winterfell::ProofOptions::new(...) as used at /root/reference/src/lib.rs:78-86
 //   TransactionMetadata     src/lib.rs:183-232 (field for field), ::build_random src/lib.rs:235-465 (seeded)
 //   TransactionProver       src/prover.rs:20-134: new(options), build_trace, get_pub_inputs, prove
-//   TransactionExample      src/lib.rs:92-150: new(options, num_transactions), prove()
+//   TransactionExample      src/lib.rs:92-150: new(options, num_transactions), prove(), verify()
 //   get_example             src/lib.rs:75-89
 //   MerkleExample / SchnorrExample / RangeProofExample    the sub-AIR examples (src/merkle/update/mod.rs, src/schnorr/mod.rs,
 //                                                         src/range/mod.rs)
@@ -220,6 +220,33 @@ class ProverPool {
     bool stop_ = false;
 };
 
+// winterfell::VerifierError: a rejected proof; verdict = the cstark_verdict of the first failing check (include/cstark.h)
+struct VerifierError : std::runtime_error {
+    int verdict;
+    explicit VerifierError(int v) : std::runtime_error("proof rejected (verdict " + std::to_string(v) + ")"), verdict(v) {}
+};
+
+// cstark_tx_verify for many proofs in one call: one verdict per proof (CSTARK_PROOF_OK = accepted).  expected = nullptr: each proof's own
+// options; otherwise every proof must state exactly these.
+inline std::vector<int32_t> verify_batch(Context &ctx, const std::vector<std::vector<uint8_t>> &proofs, const std::vector<PublicInputs> &pub,
+                                         const ProofOptions *expected = nullptr) {
+    if (pub.size() != proofs.size()) throw Error(CSTARK_ERR_INVALID_ARG, "one PublicInputs per proof");
+    std::vector<const uint8_t *> ptrs(proofs.size());
+    std::vector<size_t> lens(proofs.size());
+    std::vector<uint64_t> r0(7 * proofs.size()), r1(7 * proofs.size());
+    for (size_t i = 0; i < proofs.size(); i++) {
+        ptrs[i] = proofs[i].data();
+        lens[i] = proofs[i].size();
+        for (int k = 0; k < 7; k++) { r0[7 * i + k] = pub[i].initial_root[k]; r1[7 * i + k] = pub[i].final_root[k]; }
+    }
+    std::vector<int32_t> verdicts(proofs.size());
+    cstark_options o{};
+    if (expected) o = expected->raw();
+    check(cstark_tx_verify(ctx.raw(), (uint32_t)proofs.size(), ptrs.data(), lens.data(), r0.data(), r1.data(), expected ? &o : nullptr,
+                           verdicts.data()));
+    return verdicts;
+}
+
 // src/lib.rs:92-150
 class TransactionExample {
   public:
@@ -228,6 +255,11 @@ class TransactionExample {
     std::vector<uint8_t> prove() { return TransactionProver(options_, ctx_).prove(tx_metadata_); }
     PublicInputs pub_inputs() const { return TransactionProver::get_pub_inputs(tx_metadata_); }
     const TransactionMetadata &metadata() const { return tx_metadata_; }
+    // winterfell::verify::<TransactionAir>(proof, pub_inputs) (src/lib.rs:144-150): throws VerifierError on rejection
+    void verify(const std::vector<uint8_t> &proof) const {
+        const int32_t v = verify_batch(ctx_, {proof}, {pub_inputs()})[0];
+        if (v != CSTARK_PROOF_OK) throw VerifierError(v);
+    }
 
   private:
     ProofOptions options_;

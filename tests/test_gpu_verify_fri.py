@@ -1,0 +1,86 @@
+"""The low-degree checks of cstark_tx_verify reject: proofs whose FRI layers or remainder were altered BEFORE their commitment (built by
+the CPU prover with a perturbed fold), so every opening and commitment holds and only LAYER_FOLDING, REMAINDER_FOLDING or
+REMAINDER_DEGREE can catch them.  Verdicts must equal the restated verifier's, alone and inside a mixed batch.  Also: a ProofBatch input."""
+import numpy as np
+import pytest
+
+from test_gpu_verify import backend, names, oracle_verdict  # noqa: F401  (module-scoped fixture)
+
+pytestmark = pytest.mark.gpu
+P = (1 << 62) + (1 << 56) + (1 << 55) + 1
+
+
+def _add_one(a, idx=None):
+    """a + 1 (memory form) at every element, or at idx only"""
+    from oracle import oracle as O
+    one = np.uint64(int(O.to_mont(np.array([1], np.uint64))[0]))
+    b = np.array(a, np.uint64, copy=True)
+    flat = b.reshape(-1)
+    sel = slice(None) if idx is None else idx
+    v = flat[sel].astype(object) + int(one)
+    flat[sel] = np.array([x - P if x >= P else x for x in np.atleast_1d(v)], np.uint64).reshape(np.shape(flat[sel]))
+    return b
+
+
+def _cheat(monkeypatch, w, options, call, idx=None):
+    """CPU proof whose `call`-th fold output (0 = layer 1; n_layers - 1 = the remainder) is perturbed before it is committed"""
+    from oracle import oracle as O
+    from oracle import prover as OP
+    name = "fri_fold_ext" if options[4] else "fri_fold"
+    real = getattr(O, name)
+    count = [0]
+
+    def fold(*a, **k):
+        out = real(*a, **k)
+        if count[0] == call:
+            out = _add_one(out, idx)
+        count[0] += 1
+        return out
+    monkeypatch.setattr(O, name, fold)
+    try:
+        return OP.prove(w, options)
+    finally:
+        monkeypatch.setattr(O, name, real)
+
+
+def test_fri_and_remainder_checks_reject(backend, oracle, monkeypatch):
+    w = oracle.TxWitness.generate(2, 3, seed=0x5EED)
+    r0, r1 = w.initial_roots[0], w.final_root
+    base, cubic = (8, 8, 0, 0, 0, 4, 256), (8, 8, 0, 1, 2, 4, 256)   # 3 layers, remainder of 256
+    cases = [_cheat(monkeypatch, w, base, 0), _cheat(monkeypatch, w, base, 1), _cheat(monkeypatch, w, base, 2),
+             _cheat(monkeypatch, w, cubic, 0), _cheat(monkeypatch, w, cubic, 2)]
+    # one remainder value changed: caught by the degree check unless that value is queried (then by the folding check)
+    for i in range(0, 256, 37):
+        cases.append(_cheat(monkeypatch, w, base, 2, idx=i))
+    expect = [oracle_verdict(p, r0, r1) for p in cases]
+    assert {"LAYER_FOLDING", "REMAINDER_FOLDING", "REMAINDER_DEGREE"} <= set(expect), expect
+    single = [names(backend.tx_verify([p], r0, r1))[0] for p in cases]
+    assert single == expect
+    honest = OP_prove(w, base)
+    mixed = [honest] + cases[:3] + [honest] + cases[3:]
+    got = names(backend.tx_verify(mixed, r0, r1))
+    assert got == ["OK"] + expect[:3] + ["OK"] + expect[3:]
+
+
+def OP_prove(w, options):
+    from oracle import prover as OP
+    return OP.prove(w, options)
+
+
+def test_proof_batch_input(backend, oracle):
+    """tx_verify reads a ProofBatch in place (its buffer, stride and lengths)"""
+    from certificate_stark_amd.backend import ProofBatch
+    w = oracle.TxWitness.generate(2, 3, seed=0x5EED)
+    proofs = [OP_prove(w, (8, 8, 0, 0, 0, 4, 256)), OP_prove(w, (12, 8, 0, 1, 1, 8, 128))]
+    stride = max(len(p) for p in proofs) + 24
+    buf = np.zeros(stride * 3, np.uint8)
+    lens = np.zeros(3, np.uint64)
+    bad = bytearray(proofs[0])
+    bad[-30] ^= 0x02
+    for i, p in enumerate(proofs + [bytes(bad)]):
+        buf[i * stride:i * stride + len(p)] = np.frombuffer(p, np.uint8)
+        lens[i] = len(p)
+    batch = ProofBatch(buf, stride, lens)
+    got = names(backend.tx_verify(batch, w.initial_roots[0], w.final_root))
+    assert got == names(backend.tx_verify(list(batch), w.initial_roots[0], w.final_root))
+    assert got[:2] == ["OK", "OK"] and got[2] != "OK"

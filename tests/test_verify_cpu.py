@@ -1,0 +1,158 @@
+"""cstark_proof_inspect (the verifier's host parser) and the verdict table, on the CPU: no GPU, no context."""
+import os
+import re
+import struct
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "proof_2tx_d3.npz")
+MALFORMED = 1
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return bytes(np.load(GOLDEN)["proof"].tobytes())
+
+
+def _inspect(p):
+    from certificate_stark_amd import inspect_proof
+    return inspect_proof(p)
+
+
+def _sections(p):
+    """byte offsets of every section boundary (restated here from the layout in include/cstark.h)"""
+    info = _inspect(p)
+    nq, blowup, _, _, ext, fold, _ = info.options
+    m, W, ce = ext + 1, 94, 8
+    log_N, log_f = info.log_n + blowup.bit_length() - 1, fold.bit_length() - 1
+    nl = struct.unpack_from("<I", p, 116)[0]
+    o, cuts, counts = 52, [0, 4, 8, 12, 16, 20, 24, 52], {}
+    o += 64; cuts.append(o)
+    counts["n_layers"] = o
+    o += 4 + 32 * nl + 32; cuts.append(o)
+    o += 8 * (2 * W + ce) * m; cuts.append(o)
+    o += 8; cuts.append(o)
+    for words in (nq * W, nq * log_N * 4, nq * ce * m, nq * log_N * 4):
+        o += 8 * words; cuts.append(o)
+    lg = log_N
+    for l in range(nl):
+        counts["n_positions_%d" % l] = o
+        npos = struct.unpack_from("<I", p, o)[0]
+        o += 4; cuts.append(o)
+        o += 8 * npos * fold * m; cuts.append(o)
+        o += 32 * npos * (lg - log_f); cuts.append(o)
+        lg -= log_f
+    counts["remainder_len"] = o
+    rem_len = struct.unpack_from("<I", p, o)[0]
+    o += 4; cuts.append(o)
+    o += 8 * rem_len * m
+    assert o == len(p)
+    cuts.append(o)
+    return cuts, counts
+
+
+def test_golden_proof_header(golden):
+    info = _inspect(golden)
+    assert info.verdict == 0
+    assert info.options == [42, 8, 0, 0, 0, 4, 256]
+    assert info.log_n == 11 and info.depth == 3 and info.air == 0 and info.trace_width == 94
+
+
+@pytest.mark.parametrize("options", [
+    (16, 8, 0, 1, 0, 4, 256),    # Sha3_256
+    (8, 8, 0, 0, 1, 4, 256),     # Quadratic
+    (8, 16, 0, 0, 2, 4, 256),    # Cubic, blowup 16
+    (8, 8, 0, 0, 0, 8, 128),     # folding 8, remainder 128
+    (8, 8, 0, 0, 0, 16, 1024),   # folding 16, remainder 1024
+    (8, 8, 6, 1, 2, 16, 512),    # grinding, Sha3, Cubic
+])
+def test_cpu_prover_proofs_read_back(oracle, witness_d3, options):
+    from oracle import prover as OP
+    p = OP.prove(witness_d3, options)
+    info = _inspect(p)
+    assert info.verdict == 0
+    assert info.options == list(options)
+    assert info.log_n == 11 and info.depth == 3 and info.air == 0
+    # every section boundary was derived from the header and the counts alone
+    cuts, _ = _sections(p)
+    assert cuts[-1] == len(p)
+
+
+def test_other_airs_read_back(oracle, witness_d3):
+    from oracle import prover as OP
+    merkle = OP.prove_air(oracle.AIR_MERKLE, witness_d3, (8, 8, 0, 0, 0, 4, 128))
+    info = _inspect(merkle)
+    assert (info.verdict, info.air, info.trace_width, info.header_word) == (0, 1, 65, 3)
+    rng = OP.prove_air(oracle.AIR_RANGE, 12345, (8, 8, 0, 0, 0, 4, 128))
+    info = _inspect(rng)
+    assert (info.verdict, info.air, info.trace_width, info.log_n) == (0, 3, 2, 6)
+    assert info.options == [8, 8, 0, 0, 0, 4, 128]
+
+
+def test_truncations_are_malformed(golden):
+    cuts, _ = _sections(golden)
+    lengths = set()
+    for c in cuts:
+        lengths.update((c - 1, c, c + 1))
+    rng = np.random.default_rng(7)
+    lengths.update(int(v) for v in rng.integers(0, len(golden), 500))
+    for n in sorted(lengths):
+        if 0 <= n < len(golden):
+            assert _inspect(golden[:n]).verdict == MALFORMED, n
+    assert _inspect(golden + b"\0").verdict == MALFORMED
+
+
+def test_count_words_are_checked_before_use(golden):
+    nq = 42
+    _, counts = _sections(golden)
+    assert len(counts) >= 3
+    for name, off in counts.items():
+        for v in (0, nq + 1, 1 << 31, (1 << 32) - 1):
+            bad = bytearray(golden)
+            struct.pack_into("<I", bad, off, v)
+            assert _inspect(bytes(bad)).verdict == MALFORMED, (name, v)
+
+
+@pytest.mark.parametrize("off,value", [
+    (0, 0x4B545344),        # magic
+    (4, 2),                 # version
+    (8, 5),                 # air id
+    (12, 93),               # trace width
+    (24 + 4 * 5, 2),        # folding factor
+    (24 + 4 * 5, 32),
+    (24 + 4 * 1, 4),        # blowup below the AIR's constraint-evaluation blowup
+    (24 + 4 * 1, 3),
+    (24 + 4 * 0, 0),        # no queries
+    (24 + 4 * 4, 3),        # field extension
+    (24 + 4 * 2, 33),       # grinding
+    (20, 4),                # Merkle depth the prover refuses
+])
+def test_bad_header_words_are_malformed(golden, off, value):
+    bad = bytearray(golden)
+    struct.pack_into("<I", bad, off, value)
+    assert _inspect(bytes(bad)).verdict == MALFORMED
+
+
+def test_empty_and_tiny_inputs(golden):
+    assert _inspect(b"").verdict == MALFORMED
+    assert _inspect(b"CSTK").verdict == MALFORMED
+    assert _inspect(golden[:52]).verdict == MALFORMED
+
+
+def test_verdict_table_matches_the_header():
+    from certificate_stark_amd import VERDICTS
+    hdr = open(os.path.join(ROOT, "include", "cstark.h")).read()
+    body = hdr[hdr.index("typedef enum cstark_verdict"):]
+    body = body[:body.index("} cstark_verdict;")]
+    pairs = re.findall(r"CSTARK_PROOF_([A-Z_]+)\s*=\s*(\d+)", body)
+    assert len(pairs) == 14
+    assert [int(v) for _, v in pairs] == list(range(14))
+    assert tuple(n for n, _ in pairs) == VERDICTS
+
+
+def test_verifier_error_carries_verdict_and_reason():
+    from certificate_stark_amd import VerifierError
+    e = VerifierError(4)
+    assert e.verdict == 4 and e.reason == "OOD"

@@ -1,0 +1,67 @@
+"""Verification throughput at the headline configuration (1024 transfers = 2^20 rows, depth 15; 96 queries, blowup 8, folding 4,
+remainder 256): single-proof latency, proofs/s at batch sizes 16, 64 and 256, bytes copied per call (proof bytes and the whole copy)
+and the achieved host-to-device rate of the whole copy, and cstark_verify_stage_ms.  Prints one JSON line.  Run on a GPU box.
+
+    python tools/bench_verify.py [--counts 1,64] [--min-seconds 1.0]
+
+cstark_tx_verify is synchronous (verdicts are on the host when it returns), so wall time around the call is the latency; every
+configuration is warmed up first and timed over at least --min-seconds of calls."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+
+from certificate_stark_amd.backend import Backend  # noqa: E402
+from certificate_stark_amd.prover import ProofOptions, TransactionExample, TransactionMetadata  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PCIE_GEN5_X16_GBPS = 63.0  # per direction, MI355X spec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--counts", default="1,16,64,256")
+    ap.add_argument("--min-seconds", type=float, default=1.0)
+    args = ap.parse_args()
+    b = Backend()
+    meta = TransactionMetadata.load(os.path.join(ROOT, "tests", "golden", "witness_1024_d15.npz"))
+    opt = ProofOptions(96, 8, 0, ProofOptions.BLAKE3_256, ProofOptions.EXT_NONE, 4, 256)
+    tx = TransactionExample(opt, meta, b)
+    proof = tx.prove()
+    r0, r1 = tx.pub_inputs()
+    out = {"config": "state_transition 1024 tx (2^20 rows), depth 15, options (96, 8, 0, Blake3, None, 4, 256)",
+           "proof_bytes": len(proof), "device": "MI355X", "results": {}}
+    for count in [int(c) for c in args.counts.split(",")]:
+        proofs = [proof] * count
+        for _ in range(3):  # warm-up: staging buffers, periodic coefficients, code objects
+            v = b.tx_verify(proofs, r0, r1, opt)
+        assert not v.any(), v
+        calls, t0 = 0, time.perf_counter()
+        while True:
+            b.tx_verify(proofs, r0, r1, opt)
+            calls += 1
+            dt = time.perf_counter() - t0
+            if dt >= args.min_seconds:
+                break
+        per_call = dt / calls
+        st = b.verify_stage_ms()
+        nbytes = count * len(proof)
+        copied = b.verify_h2d_bytes()   # the one host-to-device copy: proof bytes + descriptors + opening records
+        out["results"][str(count)] = {
+            "calls": calls, "ms_per_call": round(per_call * 1e3, 4), "proofs_per_s": round(count / per_call, 1),
+            "proof_bytes_per_call": nbytes, "h2d_bytes_per_call": copied,
+            "h2d_gbps": round(copied / (st["h2d"] * 1e-3) / 1e9, 2) if st["h2d"] > 0 else None,
+            "link_share": round(copied / (st["h2d"] * 1e-3) / 1e9 / PCIE_GEN5_X16_GBPS, 3) if st["h2d"] > 0 else None,
+            "stage_ms": {k: round(v, 4) for k, v in st.items()},
+        }
+    if "1" in out["results"]:
+        out["single_proof_latency_ms"] = out["results"]["1"]["ms_per_call"]
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
