@@ -15,7 +15,8 @@
 //             table is kept in BLOCK ORDER (blake3.h, lde_coset_slot) -- b / ce blocks of ce cosets, block 0 = the constraint-
 //             evaluation domain -- so the evaluators always read a plain [ce][width][n] table; commitment leaves, query positions and
 //             the proof bytes are in natural order (leaf b j + k)
-// The byte layout of the proof is this library's own (documented in include/cstark.h); the tests check it with a restated verifier.
+// The byte layout of the proof is this library's own (documented in include/cstark.h, written and parsed by proof_layout.h); the tests
+// check it with a restated verifier.
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <algorithm>
@@ -36,6 +37,7 @@
 #include "air_tx_host.h"
 #include "hostfield.h"
 #include "coin.h"
+#include "proof_layout.h"
 
 namespace cs {
 
@@ -74,24 +76,9 @@ void prove_arena_free(ProveArena *a) {
     for (hipEvent_t e : a->ev) if (e) (void)hipEventDestroy(e);
     delete a;
 }
+int grind_nonce(cstark_ctx *c, ProveArena *a, const Coin &coin, unsigned bits, uint64_t *nonce_out);
 
 namespace {
-
-struct Writer {
-    std::vector<uint8_t> b;
-    void raw(const void *p, size_t n) { const uint8_t *q = (const uint8_t *)p; b.insert(b.end(), q, q + n); }
-    void u32(uint32_t v) { raw(&v, 4); }
-    void u64(uint64_t v) { raw(&v, 8); }
-};
-// The proof bytes go straight into the caller's buffer: a first pass only counts (dst = null), so that a buffer that is too small is left
-// untouched and the required size is known; a 0.6 MB temporary per proof would be fresh pages from the allocator every time.
-struct ProofWriter {
-    uint8_t *dst = nullptr;
-    size_t len = 0;
-    void raw(const void *p, size_t n) { if (dst) memcpy(dst + len, p, n); len += n; }
-    void u32(uint32_t v) { raw(&v, 4); }
-    void u64(uint64_t v) { raw(&v, 8); }
-};
 
 __global__ void k_gather_rows(const uint64_t *__restrict__ lde, uint32_t width, uint32_t log_n, uint32_t log_b, const uint32_t *__restrict__ pos,
                               uint64_t *__restrict__ out) {
@@ -219,11 +206,6 @@ int arena_extra(cstark_ctx *c, ProveArena *a, size_t slot, T **p, size_t bytes) 
 }
 
 unsigned ceil_log2(uint64_t x) { unsigned l = 0; while ((1ull << l) < x) l++; return l; }
-unsigned num_fri_layers(unsigned log_domain, unsigned log_max_remainder, unsigned log_f) {
-    unsigned l = 0;
-    while (log_domain > log_max_remainder) { log_domain -= log_f; l++; }
-    return l;
-}
 
 // What differs between the AIRs: how the trace is built, what goes into the channel seed, and how the combined constraint
 // evaluations are produced from the extended trace and the drawn coefficients.
@@ -332,6 +314,117 @@ int check_options(const cstark_options *opt, unsigned log_ce, unsigned *log_rem_
     return CSTARK_OK;
 }
 
+// The channel seed (the verifier replays it): trace width, log2 n, p, the seven option bytes -- these 17 bytes are also the prefix the
+// device-side channel starts from (SEED_PREFIX) -- then the public inputs in canonical form (PublicInputs::write_into, src/air.rs:57-62
+// and the sub-AIRs' equivalents) and further public material verbatim (Schnorr: the s halves of the signatures).
+constexpr size_t SEED_PREFIX = 17;
+std::vector<uint8_t> channel_seed(uint32_t width, unsigned log_n, const cstark_options &opt, unsigned log_b, unsigned log_rem, const uint64_t *pub = nullptr,
+                                  size_t n_pub = 0, const uint8_t *pub_bytes = nullptr, size_t n_bytes = 0) {
+    std::vector<uint8_t> s(SEED_PREFIX + 8 * n_pub + n_bytes);
+    const uint8_t head[2] = {(uint8_t)width, (uint8_t)log_n};
+    const uint8_t options[7] = {(uint8_t)opt.num_queries, (uint8_t)log_b, (uint8_t)opt.grinding_factor, (uint8_t)opt.hash_fn,
+                                (uint8_t)opt.field_extension, (uint8_t)opt.fri_folding_factor, (uint8_t)log_rem};
+    memcpy(&s[0], head, 2); memcpy(&s[2], &host::P, 8); memcpy(&s[10], options, 7);
+    for (size_t i = 0; i < n_pub; i++) { const uint64_t v = host::to_u64(pub[i]); memcpy(&s[SEED_PREFIX + 8 * i], &v, 8); }
+    if (n_bytes) memcpy(&s[SEED_PREFIX + 8 * n_pub], pub_bytes, n_bytes);
+    return s;
+}
+std::vector<uint8_t> channel_seed(const AirJob &job, const cstark_options &opt, unsigned log_rem) {
+    return channel_seed(job.width, job.log_n, opt, job.log_b, log_rem, job.pub.data(), job.pub.size(), job.pub_bytes.data(), job.pub_bytes.size());
+}
+
+// The proof bytes from the pieces in hand (proof_layout.h), straight into the caller's buffer.
+int emit_proof(const ProofShape &S, const ProofParts &p, uint8_t *proof, size_t capacity, size_t *proof_len) {
+    if (write_proof(S, p, proof, capacity, proof_len)) return fail(CSTARK_ERR_INVALID_ARG, "proof buffer too small (required size returned in *proof_len)");
+    return CSTARK_OK;
+}
+
+// ---- query stage (host channel): proof of work, the query positions and their folded forms, on the device at a->d_pos --------------------
+struct Queries {
+    uint64_t nonce = 1;
+    uint32_t counts[VMAX_LAYERS] = {}; // distinct folded positions per FRI layer
+    std::vector<uint32_t> hpos;        // [1 + n_layers][256]: the drawn positions, then every layer's folded positions
+};
+// `coin`: after the reseed with the remainder commitment
+int query_stage(cstark_ctx *c, ProveArena *a, Coin &coin, const ProofShape &S, Queries &Q) {
+    RC_TRY(grind_nonce(c, a, coin, S.opt[2], &Q.nonce));
+    coin.reseed_int(Q.nonce);
+    std::vector<uint32_t> cur;
+    coin.draw_integers(S.nq, (size_t)1 << S.log_N, cur);
+    Q.hpos.assign(256 * (S.n_layers + 1), 0);
+    memcpy(Q.hpos.data(), cur.data(), S.nq * 4);
+    for (unsigned l = 0; l < S.n_layers; l++) {
+        cur = fold_positions(cur, 1u << layer_log_rows(S, l));
+        Q.counts[l] = (uint32_t)cur.size();
+        memcpy(Q.hpos.data() + 256 * (l + 1), cur.data(), cur.size() * 4);
+    }
+    HIP_TRY(hipMemcpyAsync(a->d_pos, Q.hpos.data(), Q.hpos.size() * 4, hipMemcpyHostToDevice, c->stream));
+    return CSTARK_OK;
+}
+
+// ---- opening stage: every opened row and authentication path gathered into one device block, one copy to the pinned a->h_open ----------
+// The block's offsets: the sections in proof order.  counts = null: room for nq positions in every layer (the device-side channel
+// knows the counts only on the device).  start / align: the device channel's result block holds more in front and aligns its pieces.
+struct OpenBlock { size_t trows, tpaths, crows, cpaths, lrows[VMAX_LAYERS], lpaths[VMAX_LAYERS], bytes; };
+OpenBlock open_block(const ProofShape &S, const uint32_t *counts, size_t start = 0, size_t align = 1) {
+    OpenBlock O;
+    size_t off = start;
+    auto take = [&off, align](size_t bytes) { const size_t o = off; off += (bytes + align - 1) / align * align; return o; };
+    O.trows = take(trace_row_bytes(S)); O.tpaths = take(path_bytes(S)); O.crows = take(comp_row_bytes(S)); O.cpaths = take(path_bytes(S));
+    for (unsigned l = 0; l < S.n_layers; l++) {
+        const uint32_t np = counts ? counts[l] : S.nq;
+        O.lrows[l] = take(layer_row_bytes(S, np)); O.lpaths[l] = take(layer_path_bytes(S, l, np));
+    }
+    O.bytes = off;
+    return O;
+}
+int host_open_block(ProveArena *a, size_t bytes) {
+    if (a->h_open_bytes < bytes) {
+        if (a->h_open) { HIP_TRY(hipHostFree(a->h_open)); a->h_open = nullptr; a->h_open_bytes = 0; }
+        HIP_TRY(hipHostMalloc((void **)&a->h_open, bytes, hipHostMallocDefault));
+        a->h_open_bytes = bytes;
+    }
+    return CSTARK_OK;
+}
+// What the callers' openings differ in: the composition table (S.ce S.m base columns) and the FRI layers (rows of S.f S.m words), the
+// block order of the trace table's cosets, trace rows that arrive from the ranks of a sharded proof (with the bottom shard_lvl0 levels
+// of their paths), and where the per-layer counts are: host numbers, or device counters dcount[l] with nq slots per layer.
+struct OpenSrc {
+    const uint64_t *clde; uint64_t *const *layer; unsigned log_s;
+    const uint32_t *counts, *dcount;
+    const uint64_t *shard_rows; uint32_t shard_lvl0;
+};
+// Gathers into d_block at the offsets O (positions: a->d_pos, 256 slots per layer) and enqueues the copy of d_block[0, O.bytes) to a->h_open.
+int open_stage(cstark_ctx *c, ProveArena *a, const ProofShape &S, const OpenSrc &src, uint8_t *d_block, const OpenBlock &O) {
+    hipStream_t st = c->stream;
+    const uint32_t nq = S.nq, W = S.width;
+    GatherList gl;
+    uint32_t trace_lvl0 = 0;
+    if (src.shard_rows) { // sharded: rows and the bottom levels of the paths come from the owning ranks
+        trace_lvl0 = src.shard_lvl0;
+        k_split_shard_rows<<<nq, 128, 0, st>>>(src.shard_rows, W, trace_lvl0, S.log_N, (uint64_t *)(d_block + O.trows), (uint64_t *)(d_block + O.tpaths));
+        HIP_TRY(hipGetLastError());
+    } else gl.rows(a->lde, W, S.log_n, S.log_b, a->d_pos, d_block + O.trows, nq, src.log_s);
+    gl.paths(a->tnodes, S.log_N, a->d_pos, d_block + O.tpaths, nq, nullptr, trace_lvl0);
+    gl.rows(src.clde, S.ce * S.m, S.log_n, S.log_b, a->d_pos, d_block + O.crows, nq);
+    gl.paths(a->cnodes, S.log_N, a->d_pos, d_block + O.cpaths, nq);
+    for (unsigned l = 0; l < S.n_layers; l++) {
+        const uint32_t np = src.counts ? src.counts[l] : nq, lr = layer_log_rows(S, l), *pos = a->d_pos + 256 * (l + 1), *dc = src.dcount ? src.dcount + l : nullptr;
+        gl.rows(src.layer[l], S.f * S.m, lr, 0, pos, d_block + O.lrows[l], np, 0, dc);
+        gl.paths(a->lnodes[l], lr, pos, d_block + O.lpaths[l], np, dc);
+    }
+    HIP_TRY(gl.launch(st));
+    RC_TRY(host_open_block(a, O.bytes));
+    HIP_TRY(hipMemcpyAsync(a->h_open, d_block, O.bytes, hipMemcpyDeviceToHost, st));
+    return CSTARK_OK;
+}
+// the opening sections of a proof, from the host copy of such a block
+void opened_parts(ProofParts &p, const ProofShape &S, const uint8_t *h, const OpenBlock &O, const uint32_t *counts) {
+    p.trows = h + O.trows; p.tpaths = h + O.tpaths; p.crows = h + O.crows; p.cpaths = h + O.cpaths;
+    p.counts = counts;
+    for (unsigned l = 0; l < S.n_layers; l++) { p.lrows[l] = h + O.lrows[l]; p.lpaths[l] = h + O.lpaths[l]; }
+}
+
 // Interpolation and extension of the trace columns (cosets [job.k0, job.k0 + job.nk)); records the two stage events (after the
 // interpolation, after the extension).  With column batches (AirJob::batches) the complete columns go first -- interpolated AND
 // extended while the internal streams still write the later ones -- so the "interpolate" stage time then also holds the extension
@@ -417,13 +510,12 @@ struct ProofRun {
     cstark_options opt{};
     AirJob job;
     unsigned log_rem = 0, n_layers = 0, log_b = 3, log_f = 2;
+    ProofShape shape{};
     Coin coin;
     uint8_t trace_root[32] = {}, cons_root[32] = {}, rem_commit[32] = {};
     std::vector<uint64_t> ta, tb, ba, bb, ood_trace, ood_comp, remainder;
     std::vector<uint8_t> layer_roots;
-    uint64_t nonce = 0;
-    std::vector<uint32_t> positions;
-    std::vector<std::vector<uint32_t>> lpos;
+    Queries q;
     int evi = 0, phase = 0; // phase: 1 commit, 2 evaluate, 3 compose done
     bool sharded() const { return job.sharded; }
     unsigned log_s() const { return job.sharded ? 0 : log_b - job.log_ce; } // block order of the trace table's cosets
@@ -473,7 +565,7 @@ int phase_commit(cstark_ctx *c, ProveArena *a, ProofRun &R, uint8_t *d_leaves_lo
 int phase_evaluate(cstark_ctx *c, ProveArena *a, ProofRun &R, const uint8_t *d_leaves_all, uint64_t *d_out) {
     AirJob &job = R.job;
     const unsigned log_n = job.log_n, log_b = R.log_b, log_N = log_n + log_b;
-    const size_t n = (size_t)1 << log_n, N = n << log_b, W = job.width;
+    const size_t n = (size_t)1 << log_n;
     hipStream_t st = c->stream;
     const uint32_t hf = R.opt.hash_fn;
     unsigned log_top = log_N; // leaves of the tree that is built here
@@ -494,16 +586,8 @@ int phase_evaluate(cstark_ctx *c, ProveArena *a, ProofRun &R, const uint8_t *d_l
     Coin &coin = R.coin;
     coin.hash_fn = hf;
     {
-        Writer s;
-        const uint8_t ctxb[2] = {(uint8_t)W, (uint8_t)log_n};
-        s.raw(ctxb, 2);
-        s.u64(host::P);
-        const uint8_t ob[7] = {(uint8_t)R.opt.num_queries, (uint8_t)log_b, (uint8_t)R.opt.grinding_factor, (uint8_t)R.opt.hash_fn,
-                               (uint8_t)R.opt.field_extension, (uint8_t)R.opt.fri_folding_factor, (uint8_t)R.log_rem};
-        s.raw(ob, 7);
-        for (uint64_t v : job.pub) s.u64(host::to_u64(v)); // PublicInputs::write_into (src/air.rs:57-62 and the sub-AIRs' equivalents)
-        s.raw(job.pub_bytes.data(), job.pub_bytes.size());
-        coin.init(s.b.data(), s.b.size());
+        const std::vector<uint8_t> seed = channel_seed(job, R.opt, R.log_rem);
+        coin.init(seed.data(), seed.size());
     }
     coin.reseed(R.trace_root);
     const size_t nc = job.n_constraints, na = job.n_assertions;
@@ -533,7 +617,7 @@ int phase_compose(cstark_ctx *c, ProveArena *a, ProofRun &R) {
     AirJob &job = R.job;
     const cstark_options *opt = &R.opt;
     const unsigned log_n = job.log_n, log_b = R.log_b, log_f = R.log_f, log_N = log_n + log_b, log_ce = job.log_ce, n_layers = R.n_layers;
-    const size_t n = (size_t)1 << log_n, b = (size_t)1 << log_b, N = n * b, W = job.width, ce = (size_t)1 << log_ce, nq = opt->num_queries;
+    const size_t n = (size_t)1 << log_n, b = (size_t)1 << log_b, N = n * b, W = job.width, ce = (size_t)1 << log_ce;
     const uint32_t fold = 1u << log_f;
     hipStream_t st = c->stream;
     const uint32_t hf = opt->hash_fn;
@@ -628,17 +712,7 @@ int phase_compose(cstark_ctx *c, ProveArena *a, ProofRun &R) {
     STAGE();
 
     // ---- proof of work, query positions -------------------------------------------------------------------------------------
-    uint64_t nonce = 1;
-    RC_TRY(grind_nonce(c, a, coin, opt->grinding_factor, &nonce));
-    R.nonce = nonce;
-    coin.reseed_int(nonce);
-    coin.draw_integers(nq, N, R.positions);
-    R.lpos.assign(n_layers, {});
-    {
-        std::vector<uint32_t> cur = R.positions;
-        unsigned g2 = log_N;
-        for (unsigned l = 0; l < n_layers; l++) { R.lpos[l] = fold_positions(cur, 1u << (g2 - log_f)); cur = R.lpos[l]; g2 -= log_f; }
-    }
+    RC_TRY(query_stage(c, a, coin, R.shape, R.q));
     R.phase = 3;
     return CSTARK_OK;
 }
@@ -646,89 +720,19 @@ int phase_compose(cstark_ctx *c, ProveArena *a, ProofRun &R) {
 // ---- phase 4: openings (gathered on the device, one copy back) and the proof bytes ---------------------------------------------------
 // d_trace_rows (sharded only): the opened rows of the extended trace [nq][W], complete (summed over the ranks).
 int phase_open(cstark_ctx *c, ProveArena *a, ProofRun &R, const uint64_t *d_trace_rows, uint8_t *proof, size_t capacity, size_t *proof_len) {
-    AirJob &job = R.job;
-    const cstark_options *opt = &R.opt;
-    const unsigned log_n = job.log_n, log_b = R.log_b, log_f = R.log_f, log_N = log_n + log_b, log_ce = job.log_ce, n_layers = R.n_layers;
-    const size_t W = job.width, ce = (size_t)1 << log_ce, nq = opt->num_queries, fold = (size_t)1 << log_f;
     hipStream_t st = c->stream;
-    const std::vector<uint32_t> &positions = R.positions;
-    const std::vector<std::vector<uint32_t>> &lpos = R.lpos;
-    std::vector<uint32_t> hpos(256 * (n_layers + 1), 0);
-    memcpy(hpos.data(), positions.data(), nq * 4);
-    for (unsigned l = 0; l < n_layers; l++) memcpy(hpos.data() + 256 * (l + 1), lpos[l].data(), lpos[l].size() * 4);
-    HIP_TRY(hipMemcpyAsync(a->d_pos, hpos.data(), hpos.size() * 4, hipMemcpyHostToDevice, st));
-    uint8_t *o = a->d_open;
-    size_t off = 0;
-    const size_t o_trows = off; off += nq * W * 8;
-    const size_t o_tpath = off; off += nq * log_N * 32;
-    const size_t o_crows = off; off += nq * ce * 8;
-    const size_t o_cpath = off; off += nq * log_N * 32;
-    if (2 * (size_t)n_layers + 4 > MAX_GATHER_JOBS) return fail(CSTARK_ERR_UNSUPPORTED, "too many FRI layers for one opening launch");
-    GatherList gl;
-    uint32_t trace_lvl0 = 0;
-    if (d_trace_rows) { // sharded: rows and the bottom levels of the paths come from the owning ranks
-        trace_lvl0 = ceil_log2(job.nk);
-        k_split_shard_rows<<<(unsigned)nq, 128, 0, st>>>(d_trace_rows, (uint32_t)W, trace_lvl0, log_N, (uint64_t *)(o + o_trows), (uint64_t *)(o + o_tpath));
-        HIP_TRY(hipGetLastError());
-    } else gl.rows(a->lde, (uint32_t)W, log_n, log_b, a->d_pos, o + o_trows, (uint32_t)nq, R.log_s());
-    gl.paths(a->tnodes, log_N, a->d_pos, o + o_tpath, (uint32_t)nq, nullptr, trace_lvl0);
-    gl.rows(a->clde, (uint32_t)ce, log_n, log_b, a->d_pos, o + o_crows, (uint32_t)nq);
-    gl.paths(a->cnodes, log_N, a->d_pos, o + o_cpath, (uint32_t)nq);
-    std::vector<size_t> o_lrows(n_layers), o_lpath(n_layers);
-    {
-        unsigned g2 = log_N;
-        for (unsigned l = 0; l < n_layers; l++) {
-            const unsigned np = (unsigned)lpos[l].size(), lr = g2 - log_f;
-            o_lrows[l] = off; off += (size_t)np * fold * 8;
-            o_lpath[l] = off; off += (size_t)np * lr * 32;
-            gl.rows(a->layer[l], (uint32_t)fold, lr, 0, a->d_pos + 256 * (l + 1), o + o_lrows[l], np);
-            gl.paths(a->lnodes[l], lr, a->d_pos + 256 * (l + 1), o + o_lpath[l], np);
-            g2 -= log_f;
-        }
-    }
-    HIP_TRY(gl.launch(st));
-    if (a->h_open_bytes < off) {
-        if (a->h_open) { HIP_TRY(hipHostFree(a->h_open)); a->h_open = nullptr; a->h_open_bytes = 0; }
-        HIP_TRY(hipHostMalloc((void **)&a->h_open, off, hipHostMallocDefault));
-        a->h_open_bytes = off;
-    }
-    const struct { const uint8_t *p; const uint8_t *data() const { return p; } } open{a->h_open};
-    HIP_TRY(hipMemcpyAsync(a->h_open, o, off, hipMemcpyDeviceToHost, st));
+    const ProofShape &S = R.shape;
+    const OpenBlock O = open_block(S, R.q.counts);
+    RC_TRY(open_stage(c, a, S, {a->clde, a->layer.data(), R.log_s(), R.q.counts, nullptr, d_trace_rows, ceil_log2(R.job.nk)}, a->d_open, O));
     STAGE();
     HIP_TRY(cs::stream_wait(st));
     a->timed = true;
 
-    // ---- serialise ----------------------------------------------------------------------------------------------------------------
-    auto emit = [&](ProofWriter &wr) {
-    wr.raw("CSTK", 4); wr.u32(CSTARK_PROOF_VERSION);
-    wr.u32((uint32_t)job.air); wr.u32((uint32_t)W); wr.u32(log_n); wr.u32(job.item);
-    wr.u32(opt->num_queries); wr.u32(opt->blowup_factor); wr.u32(opt->grinding_factor); wr.u32(opt->hash_fn); wr.u32(opt->field_extension);
-    wr.u32(opt->fri_folding_factor); wr.u32(opt->fri_max_remainder);
-    wr.raw(R.trace_root, 32); wr.raw(R.cons_root, 32);
-    wr.u32(n_layers); wr.raw(R.layer_roots.data(), R.layer_roots.size()); wr.raw(R.rem_commit, 32);
-    wr.raw(R.ood_trace.data(), R.ood_trace.size() * 8); wr.raw(R.ood_comp.data(), R.ood_comp.size() * 8);
-    wr.u64(R.nonce);
-    wr.raw(open.data() + o_trows, nq * W * 8); wr.raw(open.data() + o_tpath, nq * log_N * 32);
-    wr.raw(open.data() + o_crows, nq * ce * 8); wr.raw(open.data() + o_cpath, nq * log_N * 32);
-    {
-        unsigned g2 = log_N;
-        for (unsigned l = 0; l < n_layers; l++) {
-            const size_t np = lpos[l].size();
-            wr.u32((uint32_t)np);
-            wr.raw(open.data() + o_lrows[l], np * fold * 8);
-            wr.raw(open.data() + o_lpath[l], np * (g2 - log_f) * 32);
-            g2 -= log_f;
-        }
-    }
-    wr.u32((uint32_t)R.remainder.size()); wr.raw(R.remainder.data(), R.remainder.size() * 8);
-    };
-    ProofWriter count, out;
-    emit(count);
-    *proof_len = count.len;
-    if (!proof || capacity < count.len) return fail(CSTARK_ERR_INVALID_ARG, "proof buffer too small (required size returned in *proof_len)");
-    out.dst = proof;
-    emit(out);
-    return CSTARK_OK;
+    ProofParts p{};
+    p.trace_root = R.trace_root; p.cons_root = R.cons_root; p.layer_roots = R.layer_roots.data(); p.rem_commit = R.rem_commit;
+    p.ood_trace = R.ood_trace.data(); p.ood_comp = R.ood_comp.data(); p.nonce = R.q.nonce; p.remainder = R.remainder.data();
+    opened_parts(p, S, a->h_open, O, R.q.counts);
+    return emit_proof(S, p, proof, capacity, proof_len);
 }
 #undef STAGE
 
@@ -741,8 +745,12 @@ int run_setup(cstark_ctx *c, const cstark_options *opt, const AirJob &job, Proof
     R.opt = *opt; R.job = job;
     R.job.log_b = R.log_b;
     if (!job.sharded) { R.job.k0 = 0; R.job.nk = 1u << R.log_b; }
-    R.n_layers = num_fri_layers(log_N, R.log_rem, R.log_f);
+    R.shape = proof_shape((uint32_t)job.air, job.width, job.log_n, job.item, *opt);
+    R.n_layers = R.shape.n_layers;
     if (opt->num_queries > ((size_t)1 << log_N) / 2) return fail(CSTARK_ERR_INVALID_ARG, "more queries than the domain supports"); // (distinct positions are drawn)
+    // all openings are one launch (GatherBatch); no accepted option set reaches this (folding >= 4, 2^24 points: at most 9 layers)
+    static_assert((MAX_GATHER_JOBS - 4) / 2 <= (int)VMAX_LAYERS, "a proof that fits one opening launch fits the layout's per-layer tables");
+    if (2 * (size_t)R.n_layers + 4 > MAX_GATHER_JOBS) return fail(CSTARK_ERR_UNSUPPORTED, "too many FRI layers for one opening launch");
     HIP_TRY(hipSetDevice(c->device));
     return get_arena(c, R.job, R.log_b, R.log_f, R.n_layers, opt->num_queries, a);
 }
@@ -781,12 +789,9 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
     auto take = [&off](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_troot = take(32), o_croot = take(32), o_rem = take(32), o_cnt = take(4 * 64), o_ood = take(n_ood * 8), o_lroots = take(32 * (size_t)n_layers),
                  o_remainder = take(rem_len * 8);
-    const size_t o_trows = take(nq * W * 8), o_tpath = take(nq * log_N * 32), o_crows = take(nq * ce * 8), o_cpath = take(nq * log_N * 32);
-    std::vector<size_t> o_lrows(n_layers), o_lpath(n_layers);
-    {
-        unsigned g2 = log_N;
-        for (unsigned l = 0; l < n_layers; l++) { o_lrows[l] = take(nq * fold * 8); o_lpath[l] = take(nq * (g2 - log_f) * 32); g2 -= log_f; }
-    }
+    const ProofShape &S = R.shape;
+    const OpenBlock O = open_block(S, nullptr, off, 256); // the openings: the tail of the block, nq slots in every layer
+    off = O.bytes;
     uint8_t *d_res;
     uint32_t *d_fri;   // [seed 8 words][alpha: 2 words per layer x 32]: the coin and the layers' folding points
     uint64_t *d_chan;  // [pts 4][scal 8][deep coefficients 2 W + ce]
@@ -797,11 +802,7 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
     RC_TRY(arena_extra(c, a, 40, &dcoef, n * 8));
     uint64_t *d_pts = d_chan, *d_scal = d_chan + 4, *d_deepc = d_chan + 12, *d_ood = (uint64_t *)(d_res + o_ood);
     uint32_t *d_cnt = (uint32_t *)(d_res + o_cnt);
-    if (a->h_open_bytes < off) {
-        if (a->h_open) { HIP_TRY(hipHostFree(a->h_open)); a->h_open = nullptr; a->h_open_bytes = 0; }
-        HIP_TRY(hipHostMalloc((void **)&a->h_open, off, hipHostMallocDefault));
-        a->h_open_bytes = off;
-    }
+    RC_TRY(host_open_block(a, off)); // before the first launch: replacing a pinned block waits for the device
     // the coefficient block the channel draws into: TransactionAir's evaluator reads the context's cstark_tx_coeffs block; the sub-AIRs'
     // merge takes alpha[115] | beta[115] | b_alpha[na] | b_beta[na]
     uint64_t *d_coef_block;
@@ -824,28 +825,22 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
     {   // the coin: context || public inputs (read from the trace, on the device), the trace root, the coefficient pairs
         ChanStep s{};
         s.seed = d_fri;
+        const std::vector<uint8_t> prefix = channel_seed(job.width, log_n, *opt, log_b, R.log_rem); // the seed up to the public inputs
         if (job.air == CSTARK_AIR_SCHNORR) {
             // SchnorrAir's public inputs -- every message, R.x and s half: 304 bytes per signature -- are host data: the seed is hashed
             // here (once per uploaded witness and option set: c->schnorr_seed) and uploaded
-            uint8_t key[12] = {(uint8_t)W, (uint8_t)log_n, (uint8_t)opt->num_queries, (uint8_t)log_b, (uint8_t)opt->grinding_factor, (uint8_t)opt->hash_fn,
-                               (uint8_t)opt->field_extension, (uint8_t)opt->fri_folding_factor, (uint8_t)R.log_rem, 0, 0, 1};
+            uint8_t key[12] = {}; // width, log n, the seven option bytes, 0, 0, 1 (valid)
+            memcpy(key, prefix.data(), 2); memcpy(key + 2, prefix.data() + 10, 7); key[11] = 1;
             if (memcmp(key, c->schnorr_seed_key, sizeof key) != 0) {
-                Writer sd;
-                sd.raw(key, 2); sd.u64(host::P); sd.raw(key + 2, 7);
-                for (uint64_t v : job.pub) sd.u64(host::to_u64(v));
-                sd.raw(job.pub_bytes.data(), job.pub_bytes.size());
-                hostb3::hash(sd.b.data(), sd.b.size(), c->schnorr_seed);
+                const std::vector<uint8_t> seed = channel_seed(job, *opt, R.log_rem);
+                hostb3::hash(seed.data(), seed.size(), c->schnorr_seed);
                 memcpy(c->schnorr_seed_key, key, sizeof key);
             }
             HIP_TRY(hipMemcpyAsync(d_fri, c->schnorr_seed, 32, hipMemcpyHostToDevice, st));
         } else {
             s.init = 1; s.pub = a->d_pub; s.npub = job.air == CSTARK_AIR_RANGE ? 1 : 14;
         }
-        const uint8_t hdr[17] = {(uint8_t)W, (uint8_t)log_n, (uint8_t)host::P, (uint8_t)(host::P >> 8), (uint8_t)(host::P >> 16), (uint8_t)(host::P >> 24),
-                                 (uint8_t)(host::P >> 32), (uint8_t)(host::P >> 40), (uint8_t)(host::P >> 48), (uint8_t)(host::P >> 56),
-                                 (uint8_t)opt->num_queries, (uint8_t)log_b, (uint8_t)opt->grinding_factor, (uint8_t)opt->hash_fn, (uint8_t)opt->field_extension,
-                                 (uint8_t)opt->fri_folding_factor, (uint8_t)R.log_rem};
-        memcpy(s.prefix, hdr, sizeof hdr); s.prefix_len = sizeof hdr;
+        memcpy(s.prefix, prefix.data(), SEED_PREFIX); s.prefix_len = SEED_PREFIX;
         s.absorb[0].kind = CHAN_DIGEST; s.absorb[0].ptr = a->tnodes + 32; s.absorb[0].copy_out = d_res + o_troot;
         s.draw = CHAN_DRAW_COEFFS; s.a = job.n_constraints; s.b = job.n_assertions; s.stride = CSTARK_TX_NUM_CONSTRAINTS;
         s.count = 2 * (job.n_constraints + job.n_assertions); s.out = d_coef_block;
@@ -917,23 +912,8 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
         s.pos = a->d_pos; s.cnt = d_cnt;
         HIP_TRY(channel_step(s, st));
     }
-    if (2 * (size_t)n_layers + 4 > MAX_GATHER_JOBS) return fail(CSTARK_ERR_UNSUPPORTED, "too many FRI layers for one opening launch");
-    {
-        GatherList gl;
-        gl.rows(a->lde, (uint32_t)W, log_n, log_b, a->d_pos, d_res + o_trows, (uint32_t)nq, R.log_s());
-        gl.paths(a->tnodes, log_N, a->d_pos, d_res + o_tpath, (uint32_t)nq);
-        gl.rows(a->clde, (uint32_t)ce, log_n, log_b, a->d_pos, d_res + o_crows, (uint32_t)nq);
-        gl.paths(a->cnodes, log_N, a->d_pos, d_res + o_cpath, (uint32_t)nq);
-        unsigned g2 = log_N;
-        for (unsigned l = 0; l < n_layers; l++) { // at most nq rows per layer; how many: cnt[l + 1], on the device
-            const unsigned lr = g2 - log_f;
-            gl.rows(a->layer[l], fold, lr, 0, a->d_pos + 256 * (l + 1), d_res + o_lrows[l], (uint32_t)nq, 0, d_cnt + l + 1);
-            gl.paths(a->lnodes[l], lr, a->d_pos + 256 * (l + 1), d_res + o_lpath[l], (uint32_t)nq, d_cnt + l + 1);
-            g2 -= log_f;
-        }
-        HIP_TRY(gl.launch(st));
-    }
-    HIP_TRY(hipMemcpyAsync(a->h_open, d_res, off, hipMemcpyDeviceToHost, st));
+    // at most nq rows per layer; how many: cnt[l + 1], on the device.  The copy takes the whole result block.
+    RC_TRY(open_stage(c, a, S, {a->clde, a->layer.data(), R.log_s(), nullptr, d_cnt + 1, nullptr, 0}, d_res, O));
     STAGE();
     static const bool hostprof = getenv("CSTARK_HOSTPROF") != nullptr; // debugging: where the host's time goes
     const auto hp1 = std::chrono::steady_clock::now();
@@ -946,33 +926,12 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
     if (cnt[0] != nq) return fail(CSTARK_ERR_HIP, "device channel: the query positions could not be drawn");
     for (unsigned l = 0; l < n_layers; l++)
         if (cnt[l + 1] == 0 || cnt[l + 1] > nq) return fail(CSTARK_ERR_HIP, "device channel: bad folded position count");
-    auto emit = [&](ProofWriter &wr) {
-        wr.raw("CSTK", 4); wr.u32(CSTARK_PROOF_VERSION);
-        wr.u32((uint32_t)job.air); wr.u32((uint32_t)W); wr.u32(log_n); wr.u32(job.item);
-        wr.u32(opt->num_queries); wr.u32(opt->blowup_factor); wr.u32(opt->grinding_factor); wr.u32(opt->hash_fn); wr.u32(opt->field_extension);
-        wr.u32(opt->fri_folding_factor); wr.u32(opt->fri_max_remainder);
-        wr.raw(h + o_troot, 32); wr.raw(h + o_croot, 32);
-        wr.u32(n_layers); wr.raw(h + o_lroots, 32 * (size_t)n_layers); wr.raw(h + o_rem, 32);
-        wr.raw(h + o_ood, n_ood * 8);
-        wr.u64(1); // pow nonce: grinding_factor 0
-        wr.raw(h + o_trows, nq * W * 8); wr.raw(h + o_tpath, nq * log_N * 32);
-        wr.raw(h + o_crows, nq * ce * 8); wr.raw(h + o_cpath, nq * log_N * 32);
-        unsigned g2 = log_N;
-        for (unsigned l = 0; l < n_layers; l++) {
-            const size_t np = cnt[l + 1];
-            wr.u32((uint32_t)np);
-            wr.raw(h + o_lrows[l], np * fold * 8);
-            wr.raw(h + o_lpath[l], np * (g2 - log_f) * 32);
-            g2 -= log_f;
-        }
-        wr.u32((uint32_t)rem_len); wr.raw(h + o_remainder, rem_len * 8);
-    };
-    ProofWriter count, out;
-    emit(count);
-    *proof_len = count.len;
-    if (!proof || capacity < count.len) return fail(CSTARK_ERR_INVALID_ARG, "proof buffer too small (required size returned in *proof_len)");
-    out.dst = proof;
-    emit(out);
+    ProofParts p{};
+    p.trace_root = h + o_troot; p.cons_root = h + o_croot; p.layer_roots = h + o_lroots; p.rem_commit = h + o_rem;
+    p.ood_trace = h + o_ood; p.ood_comp = h + o_ood + ood_trace_bytes(S); p.remainder = h + o_remainder;
+    p.nonce = 1; // grinding_factor 0
+    opened_parts(p, S, h, O, cnt + 1);
+    RC_TRY(emit_proof(S, p, proof, capacity, proof_len));
     if (hostprof) {
         const auto hp3 = std::chrono::steady_clock::now();
         auto us = [](auto d) { return std::chrono::duration<double, std::micro>(d).count(); };
@@ -1185,23 +1144,21 @@ int schnorr_combine(cstark_ctx *c, ProveArena *a, AirJob &job, const uint64_t *t
 // TransactionAir merges all sets in one pass over the frame, the sub-AIRs merge their materialised evaluations m times.  Layout
 // differences of the proof: out-of-domain values are m-tuples, composition rows hold 8 m-tuples, FRI rows and the remainder are
 // component-major.
-int prove_ext(cstark_ctx *c, const cstark_options *opt, AirJob &job, uint8_t *proof, size_t capacity, size_t *proof_len) {
+int prove_ext(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8_t *proof, size_t capacity, size_t *proof_len) {
     using namespace host;
     const unsigned m = opt->field_extension + 1;
-    unsigned log_rem = 0, log_b = 3, log_f = 2;
-    RC_TRY(check_options(opt, job.log_ce, &log_rem, &log_b, &log_f));
-    job.log_b = log_b; job.k0 = 0; job.nk = 1u << log_b; job.sharded = false;
-    const unsigned log_n = job.log_n, log_N = log_n + log_b, log_ce = job.log_ce, log_s = log_b - log_ce;
-    if (log_N > 24) return fail(CSTARK_ERR_UNSUPPORTED, "the LDE domain holds at most 2^24 points (2^21 trace rows at blowup 8)");
+    ProofRun R;
+    ProveArena *a;
+    job0.sharded = false;
+    RC_TRY(run_setup(c, opt, job0, R, &a));
+    AirJob &job = R.job;
+    const ProofShape &S = R.shape;
+    const unsigned log_b = R.log_b, log_f = R.log_f, n_layers = R.n_layers;
+    const unsigned log_n = job.log_n, log_N = log_n + log_b, log_ce = job.log_ce, log_s = R.log_s();
     const size_t n = (size_t)1 << log_n, b = (size_t)1 << log_b, N = n * b, W = job.width, ce = (size_t)1 << log_ce, CW = m * ce; // CW: base columns of the composition table
     const size_t CN = ce * n; // points of the constraint-evaluation domain
-    const unsigned n_layers = num_fri_layers(log_N, log_rem, log_f);
     const uint32_t fold = 1u << log_f;
     const size_t nq = opt->num_queries;
-    if (nq > N / 2) return fail(CSTARK_ERR_INVALID_ARG, "more queries than the domain supports");
-    HIP_TRY(hipSetDevice(c->device));
-    ProveArena *a;
-    RC_TRY(get_arena(c, job, log_b, log_f, n_layers, nq, &a));
     uint64_t *combined_x, *ccoef_x, *ccoefs, *cldes, *deepx;
     uint8_t *d_open;
     RC_TRY(arena_extra(c, a, 16, &combined_x, 2 * CN * 8));  // components 1, 2 of the merged evaluations
@@ -1236,16 +1193,8 @@ int prove_ext(cstark_ctx *c, const cstark_options *opt, AirJob &job, uint8_t *pr
     Coin coin;
     coin.hash_fn = hf;
     {
-        Writer s;
-        const uint8_t ctxb[2] = {(uint8_t)W, (uint8_t)log_n};
-        s.raw(ctxb, 2);
-        s.u64(P);
-        const uint8_t ob[7] = {(uint8_t)opt->num_queries, (uint8_t)log_b, (uint8_t)opt->grinding_factor, (uint8_t)opt->hash_fn,
-                               (uint8_t)opt->field_extension, (uint8_t)opt->fri_folding_factor, (uint8_t)log_rem};
-        s.raw(ob, 7);
-        for (uint64_t v : job.pub) s.u64(to_u64(v));
-        s.raw(job.pub_bytes.data(), job.pub_bytes.size());
-        coin.init(s.b.data(), s.b.size());
+        const std::vector<uint8_t> seed = channel_seed(job, *opt, R.log_rem);
+        coin.init(seed.data(), seed.size());
     }
     coin.reseed(trace_root);
     auto draw_e = [&coin, m]() { EX x = ex_zero(); for (unsigned q = 0; q < m; q++) x.c[q] = coin.draw(); return x; };
@@ -1338,8 +1287,7 @@ int prove_ext(cstark_ctx *c, const cstark_options *opt, AirJob &job, uint8_t *pr
         offset = pow(offset, fold);
         lg -= log_f;
     }
-    const size_t R = (size_t)1 << lg;
-    std::vector<uint64_t> remainder(m * R);
+    std::vector<uint64_t> remainder(m * ((size_t)1 << lg));
     HIP_TRY(hipMemcpyAsync(remainder.data(), layer[n_layers], remainder.size() * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(cs::stream_wait(st));
     uint8_t rem_commit[32];
@@ -1347,85 +1295,19 @@ int prove_ext(cstark_ctx *c, const cstark_options *opt, AirJob &job, uint8_t *pr
     coin.reseed(rem_commit);
     STAGE();
 
-    uint64_t nonce = 1;
-    RC_TRY(grind_nonce(c, a, coin, opt->grinding_factor, &nonce));
-    coin.reseed_int(nonce);
-    std::vector<uint32_t> positions;
-    coin.draw_integers(nq, N, positions);
-    std::vector<std::vector<uint32_t>> lpos(n_layers);
-    {
-        std::vector<uint32_t> cur = positions;
-        unsigned g2 = log_N;
-        for (unsigned l = 0; l < n_layers; l++) { lpos[l] = fold_positions(cur, 1u << (g2 - log_f)); cur = lpos[l]; g2 -= log_f; }
-    }
-    std::vector<uint32_t> hpos(256 * (n_layers + 1), 0);
-    memcpy(hpos.data(), positions.data(), nq * 4);
-    for (unsigned l = 0; l < n_layers; l++) memcpy(hpos.data() + 256 * (l + 1), lpos[l].data(), lpos[l].size() * 4);
-    HIP_TRY(hipMemcpyAsync(a->d_pos, hpos.data(), hpos.size() * 4, hipMemcpyHostToDevice, st));
-    uint8_t *o = d_open;
-    size_t off = 0;
-    const size_t o_trows = off; off += nq * W * 8;
-    const size_t o_tpath = off; off += nq * log_N * 32;
-    const size_t o_crows = off; off += nq * CW * 8;
-    const size_t o_cpath = off; off += nq * log_N * 32;
-    if (2 * (size_t)n_layers + 4 > MAX_GATHER_JOBS) return fail(CSTARK_ERR_UNSUPPORTED, "too many FRI layers for one opening launch");
-    GatherList gl;
-    gl.rows(a->lde, (uint32_t)W, log_n, log_b, a->d_pos, o + o_trows, (uint32_t)nq, log_s);
-    gl.paths(a->tnodes, log_N, a->d_pos, o + o_tpath, (uint32_t)nq);
-    gl.rows(cldes, (uint32_t)CW, log_n, log_b, a->d_pos, o + o_crows, (uint32_t)nq);
-    gl.paths(a->cnodes, log_N, a->d_pos, o + o_cpath, (uint32_t)nq);
-    std::vector<size_t> o_lrows(n_layers), o_lpath(n_layers);
-    {
-        unsigned g2 = log_N;
-        for (unsigned l = 0; l < n_layers; l++) {
-            const unsigned np = (unsigned)lpos[l].size(), lr = g2 - log_f;
-            o_lrows[l] = off; off += (size_t)np * fold * 8 * m;
-            o_lpath[l] = off; off += (size_t)np * lr * 32;
-            gl.rows(layer[l], fold * m, lr, 0, a->d_pos + 256 * (l + 1), o + o_lrows[l], np);
-            gl.paths(a->lnodes[l], lr, a->d_pos + 256 * (l + 1), o + o_lpath[l], np);
-            g2 -= log_f;
-        }
-    }
-    HIP_TRY(gl.launch(st));
-    if (a->h_open_bytes < off) {
-        if (a->h_open) { HIP_TRY(hipHostFree(a->h_open)); a->h_open = nullptr; a->h_open_bytes = 0; }
-        HIP_TRY(hipHostMalloc((void **)&a->h_open, off, hipHostMallocDefault));
-        a->h_open_bytes = off;
-    }
-    const struct { const uint8_t *p; const uint8_t *data() const { return p; } } open{a->h_open};
-    HIP_TRY(hipMemcpyAsync(a->h_open, o, off, hipMemcpyDeviceToHost, st));
+    RC_TRY(query_stage(c, a, coin, S, R.q));
+    const OpenBlock O = open_block(S, R.q.counts);
+    RC_TRY(open_stage(c, a, S, {cldes, layer.data(), log_s, R.q.counts, nullptr, nullptr, 0}, d_open, O));
     STAGE();
     HIP_TRY(cs::stream_wait(st));
     a->timed = true;
 #undef STAGE
 
-    Writer wr;
-    wr.b.reserve(off + ((size_t)64 << 10) + 8 * ((size_t)opt->fri_max_remainder * (opt->field_extension + 1)));
-    wr.raw("CSTK", 4); wr.u32(CSTARK_PROOF_VERSION);
-    wr.u32((uint32_t)job.air); wr.u32((uint32_t)W); wr.u32(log_n); wr.u32(job.item);
-    wr.u32(opt->num_queries); wr.u32(opt->blowup_factor); wr.u32(opt->grinding_factor); wr.u32(opt->hash_fn); wr.u32(opt->field_extension);
-    wr.u32(opt->fri_folding_factor); wr.u32(opt->fri_max_remainder);
-    wr.raw(trace_root, 32); wr.raw(cons_root, 32);
-    wr.u32(n_layers); wr.raw(layer_roots.data(), layer_roots.size()); wr.raw(rem_commit, 32);
-    wr.raw(ood_trace.data(), ood_trace.size() * 8); wr.raw(ood_comp.data(), ood_comp.size() * 8);
-    wr.u64(nonce);
-    wr.raw(open.data() + o_trows, nq * W * 8); wr.raw(open.data() + o_tpath, nq * log_N * 32);
-    wr.raw(open.data() + o_crows, nq * CW * 8); wr.raw(open.data() + o_cpath, nq * log_N * 32);
-    {
-        unsigned g2 = log_N;
-        for (unsigned l = 0; l < n_layers; l++) {
-            const size_t np = lpos[l].size();
-            wr.u32((uint32_t)np);
-            wr.raw(open.data() + o_lrows[l], np * fold * 8 * m);
-            wr.raw(open.data() + o_lpath[l], np * (g2 - log_f) * 32);
-            g2 -= log_f;
-        }
-    }
-    wr.u32((uint32_t)R); wr.raw(remainder.data(), remainder.size() * 8);
-    *proof_len = wr.b.size();
-    if (!proof || capacity < wr.b.size()) return fail(CSTARK_ERR_INVALID_ARG, "proof buffer too small (required size returned in *proof_len)");
-    memcpy(proof, wr.b.data(), wr.b.size());
-    return CSTARK_OK;
+    ProofParts p{};
+    p.trace_root = trace_root; p.cons_root = cons_root; p.layer_roots = layer_roots.data(); p.rem_commit = rem_commit;
+    p.ood_trace = ood_trace.data(); p.ood_comp = ood_comp.data(); p.nonce = R.q.nonce; p.remainder = remainder.data();
+    opened_parts(p, S, a->h_open, O, R.q.counts);
+    return emit_proof(S, p, proof, capacity, proof_len);
 }
 
 } // namespace
@@ -1573,7 +1455,7 @@ int cstark_tx_shard_compose(cstark_ctx *c, const uint64_t *d_combined_all, uint3
     if (shard_split(R->job.nk)) RC_TRY(tx_shard_combine(c, d_combined_all, a->combined, R->job.log_n, R->job.nk)); // the ranks' shares -> [8][n]
     else if (d_combined_all != a->combined) HIP_TRY(hipMemcpyAsync(a->combined, d_combined_all, N * 8, hipMemcpyDeviceToDevice, c->stream));
     RC_TRY(phase_compose(c, a, *R));
-    memcpy(positions, R->positions.data(), R->positions.size() * 4);
+    memcpy(positions, R->q.hpos.data(), R->opt.num_queries * 4);
     return CSTARK_OK;
 }
 int cstark_tx_shard_open_rows(cstark_ctx *c, const uint32_t *positions, uint32_t nq, uint64_t *d_rows) {
@@ -1665,7 +1547,8 @@ int cstark_range_prove_batch(cstark_ctx *c, const cstark_options *opt, const uin
             RC_TRY(cstark_air_prove(c, CSTARK_AIR_RANGE, opt, numbers[t], proofs + stride * t, stride, &lens[t]));
         return CSTARK_OK;
     }
-    const unsigned log_n = RB_LOG_N, log_N = log_n + 3, n_layers = num_fri_layers(log_N, log_rem, 2);
+    const ProofShape S = proof_shape(CSTARK_AIR_RANGE, 2, RB_LOG_N, 0, *opt);
+    const unsigned log_n = RB_LOG_N, log_N = log_n + 3, n_layers = S.n_layers;
     const size_t B = count, n = RB_N, N = RB_LDE, nq = opt->num_queries, W = 2, ce = RB_CE;
     if (nq > N / 4) return fail(CSTARK_ERR_INVALID_ARG, "more queries than the domain supports");
     std::vector<uint64_t> canon(B);
@@ -1764,15 +1647,8 @@ int cstark_range_prove_batch(cstark_ctx *c, const cstark_options *opt, const uin
     RC_TRY(parallel_for(B, [&](size_t t) {
         Coin &coin = coins[t];
         coin.hash_fn = hf;
-        Writer sd;
-        const uint8_t ctxb[2] = {(uint8_t)W, (uint8_t)log_n};
-        sd.raw(ctxb, 2);
-        sd.u64(P);
-        const uint8_t ob[7] = {(uint8_t)opt->num_queries, 3, (uint8_t)opt->grinding_factor, (uint8_t)opt->hash_fn, (uint8_t)opt->field_extension,
-                               (uint8_t)opt->fri_folding_factor, (uint8_t)log_rem};
-        sd.raw(ob, 7);
-        sd.u64(canon[t]); // PublicInputs: the number (src/range/air.rs:26-36)
-        coin.init(sd.b.data(), sd.b.size());
+        const std::vector<uint8_t> seed = channel_seed((uint32_t)W, log_n, *opt, 3, log_rem, &numbers[t], 1); // PublicInputs: the number (src/range/air.rs:26-36)
+        coin.init(seed.data(), seed.size());
         coin.reseed(h_troot + 32 * t);
         uint64_t *cf = h_coefs + 8 * t; // t_alpha[2] t_beta[2] b_alpha[2] b_beta[2]
         for (int i = 0; i < 2; i++) { cf[i] = coin.draw(); cf[2 + i] = coin.draw(); }
@@ -1900,29 +1776,12 @@ int cstark_range_prove_batch(cstark_ctx *c, const cstark_options *opt, const uin
         const uint8_t *op = h_open + slot * t;
         const size_t o_trows = 0, o_tpath = o_trows + nq * 16, o_crows = o_tpath + nq * 288, o_cpath = o_crows + nq * 16, o_lrows = o_cpath + nq * 288,
                      o_lpath = o_lrows + nq * 32;
-        Writer wr;
-        wr.b.reserve(per_proof);
-        wr.raw("CSTK", 4); wr.u32(CSTARK_PROOF_VERSION);
-        wr.u32((uint32_t)CSTARK_AIR_RANGE); wr.u32((uint32_t)W); wr.u32(log_n); wr.u32(0);
-        wr.u32(opt->num_queries); wr.u32(opt->blowup_factor); wr.u32(opt->grinding_factor); wr.u32(opt->hash_fn); wr.u32(opt->field_extension);
-        wr.u32(opt->fri_folding_factor); wr.u32(opt->fri_max_remainder);
-        wr.raw(h_troot + 32 * t, 32); wr.raw(h_croot + 32 * t, 32);
-        wr.u32(n_layers);
-        if (n_layers) wr.raw(h_lroot + 32 * t, 32);
-        wr.raw(&rem_commit[32 * t], 32);
-        wr.raw(h_ood + 6 * t, 6 * 8);
-        wr.u64(nonces[t]);
-        wr.raw(op + o_trows, nq * 16); wr.raw(op + o_tpath, nq * log_N * 32);
-        wr.raw(op + o_crows, nq * 16); wr.raw(op + o_cpath, nq * log_N * 32);
-        if (n_layers) {
-            const size_t np = h_lcount[t];
-            wr.u32((uint32_t)np);
-            wr.raw(op + o_lrows, np * 32);
-            wr.raw(op + o_lpath, np * 7 * 32);
-        }
-        wr.u32((uint32_t)rem_len); wr.raw(h_rem + rem_len * t, rem_len * 8);
-        lens[t] = wr.b.size();
-        if (wr.b.size() <= stride) memcpy(proofs + stride * t, wr.b.data(), wr.b.size());
+        ProofParts p{};
+        p.trace_root = h_troot + 32 * t; p.cons_root = h_croot + 32 * t; p.layer_roots = h_lroot + 32 * t; p.rem_commit = &rem_commit[32 * t];
+        p.ood_trace = h_ood + 6 * t; p.ood_comp = h_ood + 6 * t + 4; p.nonce = nonces[t]; p.remainder = h_rem + rem_len * t;
+        p.trows = op + o_trows; p.tpaths = op + o_tpath; p.crows = op + o_crows; p.cpaths = op + o_cpath;
+        p.counts = h_lcount + t; p.lrows[0] = op + o_lrows; p.lpaths[0] = op + o_lpath;
+        (void)write_proof(S, p, proofs + stride * t, stride, &lens[t]); // a proof that does not fit its stride is left out: reported below
     }));
     mark("openings + serialise");
     for (size_t t = 0; t < B; t++)

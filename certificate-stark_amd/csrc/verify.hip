@@ -21,6 +21,7 @@
 #include "constraints.h"
 #include "air_tx_host.h"
 #include "coin.h"
+#include "proof_layout.h"
 #include "blake3_compress.cuh"
 #include "ext.cuh"
 #include "keccak.cuh"
@@ -36,86 +37,7 @@ enum : uint32_t {
     RK_REMAINDER_FOLDING = 2000, RK_REMAINDER_DEGREE = 2001,
     RK_NONE = 0xffffffffu
 };
-constexpr uint32_t VMAX_LAYERS = 16, TX_W = 94, TX_CE = 8, TX_NC = 115, TX_NA = 4;
-
-// ---- layout ---------------------------------------------------------------------------------------------------------------------
-struct Layout {
-    uint32_t air, width, log_n, word, opt[7];
-    uint32_t nq, log_b, log_f, f, m, ce, log_N, n_layers, R;
-    size_t ood, nonce, trows, tpaths, crows, cpaths, lrows[VMAX_LAYERS], lpaths[VMAX_LAYERS], rem;
-    uint32_t npos[VMAX_LAYERS];
-};
-
-static inline uint32_t rd32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
-static inline uint64_t rd64(const uint8_t *p) { uint64_t v; memcpy(&v, p, 8); return v; }
-static inline unsigned ilog2(uint32_t v) { unsigned l = 0; while ((1u << (l + 1)) <= v) l++; return l; }
-
-// the header bounds the prover enforces for TransactionAir's Merkle depth (cstark_tx_witness_upload)
-static inline bool tx_depth_ok(uint32_t d) { return d != 0 && ((d + 1) & d) == 0 && 8ull * d + 7 <= 511; }
-
-// Structure only, O(number of sections): returns CSTARK_PROOF_OK or CSTARK_PROOF_MALFORMED.  Every count is checked against the stated
-// options before it sizes anything; `need` never overflows (every factor is bounded first).
-static int parse_layout(const uint8_t *b, size_t len, Layout &L) {
-    memset(&L, 0, sizeof L);
-    if (len < 52 || memcmp(b, "CSTK", 4) != 0) return CSTARK_PROOF_MALFORMED;
-    const uint32_t version = rd32(b + 4);
-    L.air = rd32(b + 8); L.width = rd32(b + 12); L.log_n = rd32(b + 16); L.word = rd32(b + 20);
-    for (int i = 0; i < 7; i++) L.opt[i] = rd32(b + 24 + 4 * i);
-    static const uint32_t W[5] = {94, 65, 56, 2, 14}, CE[5] = {8, 4, 8, 2, 4};
-    if (version != CSTARK_PROOF_VERSION || L.air > 4 || L.width != W[L.air]) return CSTARK_PROOF_MALFORMED;
-    const uint32_t nq = L.opt[0], blowup = L.opt[1], grinding = L.opt[2], hash = L.opt[3], ext = L.opt[4], fold = L.opt[5], rem = L.opt[6];
-    L.ce = CE[L.air];
-    auto pow2 = [](uint32_t v) { return v != 0 && (v & (v - 1)) == 0; };
-    if (nq < 1 || nq > 128 || !pow2(blowup) || blowup < 2 || blowup > 16 || blowup < L.ce || grinding > 32 || hash > 1 || ext > 2 ||
-        (fold != 4 && fold != 8 && fold != 16) || !pow2(rem) || rem < 128 || rem > 1024 || L.log_n < 6 || L.log_n > 21)
-        return CSTARK_PROOF_MALFORMED;
-    if (L.air == CSTARK_AIR_STATE_TRANSITION && (L.log_n < 10 || !tx_depth_ok(L.word))) return CSTARK_PROOF_MALFORMED;
-    L.nq = nq; L.log_b = ilog2(blowup); L.log_f = ilog2(fold); L.f = fold; L.m = ext + 1; L.log_N = L.log_n + L.log_b;
-    unsigned lg = L.log_N, nl = 0;
-    const unsigned log_rem = ilog2(rem);
-    while (lg > log_rem) { lg -= L.log_f; nl++; }
-    L.R = 1u << lg;
-    size_t o = 116;
-    if (len < o + 4) return CSTARK_PROOF_MALFORMED;
-    if (rd32(b + o) != nl || nl > VMAX_LAYERS) return CSTARK_PROOF_MALFORMED;
-    L.n_layers = nl;
-    o += 4 + 32 * (size_t)nl + 32;
-    const size_t m = L.m, Wd = L.width;
-    L.ood = o; o += 8 * (2 * Wd + L.ce) * m;
-    L.nonce = o; o += 8;
-    L.trows = o; o += 8 * nq * Wd;
-    L.tpaths = o; o += 32 * (size_t)nq * L.log_N;
-    L.crows = o; o += 8 * nq * L.ce * m;
-    L.cpaths = o; o += 32 * (size_t)nq * L.log_N;
-    lg = L.log_N;
-    for (unsigned l = 0; l < nl; l++) {
-        if (len < o + 4) return CSTARK_PROOF_MALFORMED;
-        const uint32_t np = rd32(b + o);
-        if (np > nq || lg < L.log_f) return CSTARK_PROOF_MALFORMED;
-        L.npos[l] = np;
-        o += 4;
-        L.lrows[l] = o; o += 8 * (size_t)np * fold * m;
-        L.lpaths[l] = o; o += 32 * (size_t)np * (lg - L.log_f);
-        lg -= L.log_f;
-        if (o > len) return CSTARK_PROOF_MALFORMED;
-    }
-    if (len < o + 4) return CSTARK_PROOF_MALFORMED;
-    if (rd32(b + o) != L.R) return CSTARK_PROOF_MALFORMED;
-    o += 4;
-    L.rem = o; o += 8 * (size_t)L.R * m;
-    if (o != len) return CSTARK_PROOF_MALFORMED; // truncated or trailing bytes
-    return CSTARK_PROOF_OK;
-}
-
-// every field element section below p (the kernels check the same on the device; this host scan runs only where no kernel reads the
-// proof: a proof whose options differ from the expected ones)
-static bool elements_canonical(const uint8_t *b, const Layout &L) {
-    auto sec = [&](size_t off, size_t words) { for (size_t i = 0; i < words; i++) if (rd64(b + off + 8 * i) >= host::P) return false; return true; };
-    bool ok = sec(L.ood, (2 * (size_t)L.width + L.ce) * L.m) && sec(L.trows, (size_t)L.nq * L.width) && sec(L.crows, (size_t)L.nq * L.ce * L.m) &&
-              sec(L.rem, (size_t)L.R * L.m);
-    for (unsigned l = 0; ok && l < L.n_layers; l++) ok = sec(L.lrows[l], (size_t)L.npos[l] * L.f * L.m);
-    return ok;
-}
+constexpr uint32_t TX_W = 94, TX_CE = 8, TX_NC = 115, TX_NA = 4;
 
 // ---- what the device reads --------------------------------------------------------------------------------------------------------
 // Offsets (in words) of the replayed transcript block of a proof (device memory, written by k_vfy_transcript): z | t_alpha, t_beta [115] | b_alpha, b_beta [4] | DEEP alpha, beta [94]
@@ -1067,11 +989,9 @@ int cstark_proof_inspect(const uint8_t *proof, size_t len, cstark_proof_info *in
     Layout L;
     *verdict = parse_layout(proof, len, L);
     memset(info, 0, sizeof *info);
-    if (len >= 52 && memcmp(proof, "CSTK", 4) == 0) {
-        info->air = rd32(proof + 8); info->trace_width = rd32(proof + 12); info->log_n = rd32(proof + 16); info->header_word = rd32(proof + 20);
-        uint32_t *o = &info->options.num_queries;
-        for (int i = 0; i < 7; i++) o[i] = rd32(proof + 24 + 4 * i);
-    }
+    // the header words as read (all zero unless the magic matched)
+    info->air = L.air; info->trace_width = L.width; info->log_n = L.log_n; info->header_word = L.word;
+    memcpy(&info->options, L.opt, sizeof L.opt);
     return CSTARK_OK;
 }
 

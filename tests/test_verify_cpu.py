@@ -91,6 +91,19 @@ def test_other_airs_read_back(oracle, witness_d3):
     assert info.options == [8, 8, 0, 0, 0, 4, 128]
 
 
+def test_writer_and_parser_share_one_layout(golden, tmp_path):
+    """csrc/proof_layout.h alone (g++, host code only): write_proof -> parse_layout round trips over the five AIRs, the three extension
+    degrees and folding factors, with and without FRI layers; a pinned proof, parsed and written again from its sections, is the same
+    bytes; a buffer one byte short stays untouched and the needed length is reported (tests/cpp/proof_layout_check.cpp)."""
+    import subprocess
+    exe, dump = str(tmp_path / "proof_layout_check"), str(tmp_path / "proof.bin")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-o", exe, os.path.join(ROOT, "tests", "cpp", "proof_layout_check.cpp")])
+    with open(dump, "wb") as f:
+        f.write(golden)
+    out = subprocess.run([exe, dump], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("ok") and "golden proof rewritten byte for byte" in out.stdout, out.stdout + out.stderr
+
+
 def test_truncations_are_malformed(golden):
     cuts, _ = _sections(golden)
     lengths = set()
