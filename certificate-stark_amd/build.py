@@ -59,23 +59,31 @@ def build(force=False, verbose=False):
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             procs.append((s, subprocess.Popen(cmd)))
+    # the debug library's sources compile alongside; it is linked after (and to) the product library, whose kernels its extension test calls
+    dbg_dir = os.path.join(CSRC, "debug")
+    dbg_objs = []
+    for s in sorted(f for f in os.listdir(dbg_dir) if f.endswith(".hip")):
+        o = os.path.join(OBJ, "debug_" + s[:-4] + ".o")
+        dbg_objs.append(o)
+        if force or _stale(o, [os.path.join(dbg_dir, s)] + headers):
+            cmd = [hipcc()] + FLAGS + ["-c", os.path.join(dbg_dir, s), "-o", o]
+            if verbose:
+                print(" ".join(cmd), file=sys.stderr)
+            procs.append(("debug/" + s, subprocess.Popen(cmd)))
     failed = [s for s, p in procs if p.wait() != 0]
     if failed:
         raise RuntimeError("hipcc failed for: " + ", ".join(failed))
-    dbg_srcs = [os.path.join(CSRC, "debug", f) for f in sorted(os.listdir(os.path.join(CSRC, "debug"))) if f.endswith(".hip")]
-    dbg = None
-    if force or _stale(DEBUG_LIB, dbg_srcs + headers):
-        cmd = [hipcc()] + FLAGS + ["-shared", "-o", DEBUG_LIB] + dbg_srcs
-        if verbose:
-            print(" ".join(cmd), file=sys.stderr)
-        dbg = subprocess.Popen(cmd)
-    if force or procs or _stale(LIB, objs):
+    if force or _stale(LIB, objs):
         cmd = [hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.check_call(cmd)
-    if dbg is not None and dbg.wait() != 0:
-        raise RuntimeError("hipcc failed for the debug library")
+    if force or _stale(DEBUG_LIB, dbg_objs + [LIB]):
+        cmd = [hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", DEBUG_LIB] + dbg_objs + [
+            "-L" + HERE, "-l:" + os.path.basename(LIB), "-Wl,-rpath,$ORIGIN"]
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.check_call(cmd)
     return LIB
 
 

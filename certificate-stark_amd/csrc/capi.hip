@@ -877,6 +877,30 @@ static int upload_coeffs(cstark_ctx *c, const cstark_tx_coeffs *coeffs, uint32_t
     return CSTARK_OK;
 }
 
+// Descriptor of the merged extension (ntt.h: coset_even_to_odd_merged) for TransactionAir's thirteen split polynomials: five families,
+// the alpha table and the beta tables lifted by x^adj_g, g = 0, 1, 2 (the unreduced adjustments: quotient and remainder by n both
+// enter).  `hi`: the same term x^adj_0 for the high part of the final addition, which lives in z = y / w_8n (cosets k - 1 = 2, 4, 6).
+struct SplitMerge { unsigned log_n = 0; cs::CosetMergeDesc desc; cs::CosetMergeTerm hi; };
+static const SplitMerge &tx_split_merge(unsigned log_n) {
+    static thread_local SplitMerge sm; // host arithmetic only; rebuilt when the trace length changes
+    if (sm.log_n == log_n) return sm;
+    const uint64_t n = 1ull << log_n, g = cs::host::lde_offset();
+    uint64_t adj[3];
+    for (int i = 0; i < 3; i++) adj[i] = cs::host::tx_group_adjustment(i, n, 8 * n);
+    static const int first[cs::CE_SPLIT_FAMILIES] = {0, cs::CE_SPLIT_FAM0, 7, 9, 11}, count[cs::CE_SPLIT_FAMILIES] = {4, 3, 2, 2, 2};
+    sm.desc = cs::CosetMergeDesc{};
+    sm.desc.families = cs::CE_SPLIT_FAMILIES;
+    sm.desc.tables_per_set = cs::CE_SPLIT_TABLES;
+    sm.desc.raw_family = cs::CE_SPLIT_FAMILIES - 1;
+    for (int f = 0; f < cs::CE_SPLIT_FAMILIES; f++) {
+        sm.desc.terms[f] = count[f];
+        for (int t = 0; t < count[f]; t++) sm.desc.term[f][t] = cs::coset_merge_term(first[f] + t, t ? adj[t - 1] : 0, log_n, g);
+    }
+    sm.hi = cs::coset_merge_term(0, adj[0], log_n, cs::host::mul(g, cs::host::root_of_unity(log_n + 3)), 2);
+    sm.log_n = log_n;
+    return sm;
+}
+
 // (internal: declared in ctx.h for the prover)
 int tx_evaluate_constraints_sets(cstark_ctx *c, const uint64_t *d_lde, const cstark_tx_coeffs *coeffs, uint32_t m, const uint64_t pub_inputs[4],
                                  uint64_t *const *d_outs, uint32_t merkle_depth, uint32_t log_n, uint32_t log_blowup, uint32_t k0, uint32_t nk,
@@ -914,9 +938,21 @@ int tx_evaluate_constraints_sets(cstark_ctx *c, const uint64_t *d_lde, const cst
         RC_TRY(get_coset_table(c, log_n, 3, cs::host::from_u64(1), &t1));
         const size_t region = (size_t)T * 4 * n; // words per array of T x 4 columns
         const size_t hcol = (size_t)2 * m * n;   // the final addition's two sums per set: one n-point table each
-        RC_TRY(ensure_ws(c, (5 * region + 9 * hcol) * 8));
-        uint64_t *even = (uint64_t *)c->ws, *sa = even + region, *sb = sa + region, *sc = sb + region, *odd = sc + region;
-        uint64_t *fin_direct = odd + region, *fin_hi = fin_direct + hcol /* [4 odd cosets][2 m][n] */, *fin_co = fin_hi + 4 * hcol, *fin_scr = fin_co + hcol /* [3] */;
+        // CSTARK_SPLIT_MERGE=0 (tuning / debugging): every polynomial through its own transforms to the odd cosets
+        static const bool split_merge_env = [] { const char *e = getenv("CSTARK_SPLIT_MERGE"); return !e || atoi(e) != 0; }();
+        const unsigned F = cs::CE_SPLIT_FAMILIES * m;
+        const size_t fregion = (size_t)F * 4 * n; // merged: the families' vectors of the four odd cosets
+        uint64_t *even, *sa, *sb, *sc, *odd, *fin_direct, *fin_hi, *fin_co, *fin_scr, *fin_tco = nullptr, *fin_hm = nullptr;
+        if (split_merge_env) { // the transforms' input and scratch fit the interpolation's scratch: 2 fregion <= region
+            RC_TRY(ensure_ws(c, (3 * region + fregion + 8 * hcol) * 8));
+            even = (uint64_t *)c->ws; sa = even + region; sb = sa + region; sc = sa + fregion; odd = sb + region;
+            fin_direct = odd + fregion; fin_hi = fin_direct + hcol /* [4 odd cosets][m][n] */; fin_co = fin_hi + 2 * hcol; fin_tco = fin_co + hcol;
+            fin_hm = fin_tco + hcol /* [3][m][n] */; fin_scr = fin_hm + 3 * hcol / 2 /* [3][m][n] */;
+        } else {
+            RC_TRY(ensure_ws(c, (5 * region + 9 * hcol) * 8));
+            even = (uint64_t *)c->ws; sa = even + region; sb = sa + region; sc = sb + region; odd = sc + region;
+            fin_direct = odd + region; fin_hi = fin_direct + hcol /* [4 odd cosets][2 m][n] */; fin_co = fin_hi + 4 * hcol; fin_scr = fin_co + hcol /* [3] */;
+        }
         if (pev) HIP_TRY(hipEventRecord(pev[0], c->stream));
         HIP_TRY(cs::launch_rounds_setup(p, c->stream));
         HIP_TRY(cs::launch_rounds_split(p, even, c->stream));
@@ -951,30 +987,60 @@ int tx_evaluate_constraints_sets(cstark_ctx *c, const uint64_t *d_lde, const cst
         a.in = even; a.scratch = sa; a.out = sb; a.width = 4 * T; a.batch = 1; a.log_n = log_n; // every polynomial on every even coset
         a.w = pn->winv; a.post_scale = pn->n_inv; a.do_scale = true; a.inverse = true; a.aux = pn->aux_winv;
         HIP_TRY(cs::ntt_columns(a, c->stream));
-        // interpolants of the even cosets -> inputs of the odd cosets' transforms (the 4n coefficients are never written)
-        HIP_TRY(cs::coset_even_to_odd(sb, sa, log_n, T, p4->winv, p8->w, cs::host::inv(cs::host::from_u64(4)), c->stream)); // sa = [4 odd cosets][T][n]
-        cs::NttArgs f{};
-        f.in = sa; f.scratch = sc; f.out = odd; f.width = T; f.batch = 4; f.log_n = log_n;
-        f.w = pn->w; f.prescale = t1->s + n; f.prescale_batch_stride = 2 * n; f.do_scale = false; f.inverse = false;
-        f.aux = pn->aux_w; f.aux_ps = t1->aux ? t1->aux + t1->aux_words : nullptr; f.aux_ps_batch_stride = 2 * t1->aux_words;
-        f.in_batch_stride = (size_t)T * n; f.scratch_batch_stride = (size_t)T * n; f.out_batch_stride = (size_t)T * n;
-        HIP_TRY(cs::ntt_columns(f, c->stream));
-        {   // high parts of the final addition's sums: H = (T - Q) / 2 on LDE coset 1, interpolated there and extended to cosets 3, 5, 7
+        if (split_merge_env) {
+            // The recombination inside a flag family is a sum of monomial multiples, i.e. of rotated coefficient vectors: merged where the
+            // coefficients sit in registers, five vectors per odd coset and set go through the forward transforms instead of thirteen.
+            const SplitMerge &sm = tx_split_merge(log_n);
+            HIP_TRY(cs::coset_even_to_odd_merged(sb, sa, log_n, m, sm.desc, p4->winv, p8->w, cs::host::inv(cs::host::from_u64(4)), fin_tco, c->stream));
+            cs::NttArgs f{};
+            f.in = sa; f.scratch = sc; f.out = odd; f.width = F; f.batch = 4; f.log_n = log_n; // sa = [4 odd cosets][m][5][n]
+            f.w = pn->w; f.prescale = t1->s + n; f.prescale_batch_stride = 2 * n; f.do_scale = false; f.inverse = false;
+            f.aux = pn->aux_w; f.aux_ps = t1->aux ? t1->aux + t1->aux_words : nullptr; f.aux_ps_batch_stride = 2 * t1->aux_words;
+            f.in_batch_stride = (size_t)F * n; f.scratch_batch_stride = (size_t)F * n; f.out_batch_stride = (size_t)F * n;
+            HIP_TRY(cs::ntt_columns(f, c->stream));
+            // high part of the final addition, H' = h0 + x^adj_0 h1: on LDE coset 1 from the merged table and the merged direct sums;
+            // h0, h1 apart only as coefficients (interpolant of T over coset 1 from the extension kernel, minus that of the direct
+            // sums), merged there, then ONE transform per set to each of the cosets 3, 5, 7
+            const uint64_t half = cs::host::inv(cs::host::from_u64(2));
             HIP_TRY(cs::launch_final_split(p, 1, fin_direct, c->stream));
-            HIP_TRY(cs::launch_final_hi(p, odd, fin_direct, fin_hi, cs::host::inv(cs::host::from_u64(2)), c->stream));
+            HIP_TRY(cs::launch_final_hi_merged(p, odd, fin_direct, fin_hi, half, c->stream));
             cs::NttArgs hi_inv{};
-            hi_inv.in = fin_hi; hi_inv.scratch = fin_scr; hi_inv.out = fin_co; hi_inv.width = 2 * m; hi_inv.batch = 1; hi_inv.log_n = log_n;
+            hi_inv.in = fin_direct; hi_inv.scratch = fin_scr; hi_inv.out = fin_co; hi_inv.width = 2 * m; hi_inv.batch = 1; hi_inv.log_n = log_n;
             hi_inv.w = pn->winv; hi_inv.post_scale = pn->n_inv; hi_inv.do_scale = true; hi_inv.inverse = true; hi_inv.aux = pn->aux_winv;
             HIP_TRY(cs::ntt_columns(hi_inv, c->stream));
-            // coefficients of H(w_8n z) in z -> values on coset k: prescale by (w_8n^(k-1))^s, k - 1 = 2, 4, 6: rows 2, 4, 6 of the offset-1 table
+            HIP_TRY(cs::launch_final_hi_merge(p, fin_tco, fin_co, fin_hm, sm.hi, half, c->stream));
             cs::NttArgs hi_fwd{};
-            hi_fwd.in = fin_co; hi_fwd.scratch = fin_scr; hi_fwd.out = fin_hi + hcol; hi_fwd.width = 2 * m; hi_fwd.batch = 3; hi_fwd.log_n = log_n;
+            hi_fwd.in = fin_hm; hi_fwd.scratch = fin_scr; hi_fwd.out = fin_hi + (size_t)m * n; hi_fwd.width = m; hi_fwd.batch = 3; hi_fwd.log_n = log_n;
             hi_fwd.w = pn->w; hi_fwd.prescale = t1->s + 2 * n; hi_fwd.prescale_batch_stride = 2 * n; hi_fwd.do_scale = false; hi_fwd.inverse = false;
             hi_fwd.aux = pn->aux_w; hi_fwd.aux_ps = t1->aux ? t1->aux + 2 * t1->aux_words : nullptr; hi_fwd.aux_ps_batch_stride = 2 * t1->aux_words;
-            hi_fwd.in_batch_stride = 0; hi_fwd.scratch_batch_stride = hcol; hi_fwd.out_batch_stride = hcol;
+            hi_fwd.in_batch_stride = (size_t)m * n; hi_fwd.scratch_batch_stride = (size_t)m * n; hi_fwd.out_batch_stride = (size_t)m * n;
             HIP_TRY(cs::ntt_columns(hi_fwd, c->stream));
+        } else {
+            // interpolants of the even cosets -> inputs of the odd cosets' transforms (the 4n coefficients are never written)
+            HIP_TRY(cs::coset_even_to_odd(sb, sa, log_n, T, p4->winv, p8->w, cs::host::inv(cs::host::from_u64(4)), c->stream)); // sa = [4 odd cosets][T][n]
+            cs::NttArgs f{};
+            f.in = sa; f.scratch = sc; f.out = odd; f.width = T; f.batch = 4; f.log_n = log_n;
+            f.w = pn->w; f.prescale = t1->s + n; f.prescale_batch_stride = 2 * n; f.do_scale = false; f.inverse = false;
+            f.aux = pn->aux_w; f.aux_ps = t1->aux ? t1->aux + t1->aux_words : nullptr; f.aux_ps_batch_stride = 2 * t1->aux_words;
+            f.in_batch_stride = (size_t)T * n; f.scratch_batch_stride = (size_t)T * n; f.out_batch_stride = (size_t)T * n;
+            HIP_TRY(cs::ntt_columns(f, c->stream));
+            {   // high parts of the final addition's sums: H = (T - Q) / 2 on LDE coset 1, interpolated there and extended to cosets 3, 5, 7
+                HIP_TRY(cs::launch_final_split(p, 1, fin_direct, c->stream));
+                HIP_TRY(cs::launch_final_hi(p, odd, fin_direct, fin_hi, cs::host::inv(cs::host::from_u64(2)), c->stream));
+                cs::NttArgs hi_inv{};
+                hi_inv.in = fin_hi; hi_inv.scratch = fin_scr; hi_inv.out = fin_co; hi_inv.width = 2 * m; hi_inv.batch = 1; hi_inv.log_n = log_n;
+                hi_inv.w = pn->winv; hi_inv.post_scale = pn->n_inv; hi_inv.do_scale = true; hi_inv.inverse = true; hi_inv.aux = pn->aux_winv;
+                HIP_TRY(cs::ntt_columns(hi_inv, c->stream));
+                // coefficients of H(w_8n z) in z -> values on coset k: prescale by (w_8n^(k-1))^s, k - 1 = 2, 4, 6: rows 2, 4, 6 of the offset-1 table
+                cs::NttArgs hi_fwd{};
+                hi_fwd.in = fin_co; hi_fwd.scratch = fin_scr; hi_fwd.out = fin_hi + hcol; hi_fwd.width = 2 * m; hi_fwd.batch = 3; hi_fwd.log_n = log_n;
+                hi_fwd.w = pn->w; hi_fwd.prescale = t1->s + 2 * n; hi_fwd.prescale_batch_stride = 2 * n; hi_fwd.do_scale = false; hi_fwd.inverse = false;
+                hi_fwd.aux = pn->aux_w; hi_fwd.aux_ps = t1->aux ? t1->aux + 2 * t1->aux_words : nullptr; hi_fwd.aux_ps_batch_stride = 2 * t1->aux_words;
+                hi_fwd.in_batch_stride = 0; hi_fwd.scratch_batch_stride = hcol; hi_fwd.out_batch_stride = hcol;
+                HIP_TRY(cs::ntt_columns(hi_fwd, c->stream));
+            }
         }
-        HIP_TRY(cs::launch_split_finish(p, even, odd, fin_hi, c->stream));
+        HIP_TRY(cs::launch_split_finish(p, even, odd, fin_hi, c->stream, split_merge_env));
         if (pev) HIP_TRY(hipEventRecord(pev[cs::CE_NUM_PARTS], c->stream));
     } else {
         HIP_TRY(cs::launch_eval_constraints(p, nk, c->stream, pev));

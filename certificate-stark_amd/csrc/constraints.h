@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "ntt.h" // CosetMergeTerm
 
 namespace cs {
 
@@ -129,7 +130,11 @@ hipError_t launch_split_finish_shard(const CeParams &p, const uint64_t *d_even, 
 // the ranks' rows [4 / nkc][nkc + 4][n] -> merged evaluations of all cosets [8][n]
 hipError_t launch_shard_combine(const uint64_t *d_parts, uint64_t *d_out, unsigned log_n, unsigned nkc, hipStream_t stream);
 // d_hi = [4 odd cosets][2 m][n]: the high parts of the final-addition polynomials on the odd cosets (launch_final_hi + their extension)
-hipError_t launch_split_finish(const CeParams &p, const uint64_t *d_even, const uint64_t *d_odd, const uint64_t *d_hi, hipStream_t stream);
+// merged: the family sums of the odd cosets were formed before their transforms (ntt.h: coset_even_to_odd_merged with the families
+// table 0..3 | 4..6 | 7, 8 | 9, 10 | 11, 12, terms 1 + x^adj_0 + x^adj_1 + x^adj_2): d_odd = [4][m][CE_SPLIT_FAMILIES][n], d_hi = [4][m][n]
+constexpr int CE_SPLIT_FAMILIES = 5;
+hipError_t launch_split_finish(const CeParams &p, const uint64_t *d_even, const uint64_t *d_odd, const uint64_t *d_hi, hipStream_t stream,
+                               bool merged = false);
 // Final addition (degree 5 (n - 1): one n-coefficient block above the 4n the even cosets determine).  coset < 0: the two sums
 // (alpha; beta of groups 0, 1 merged) on the four even cosets into the family's tables d_out = [2][4][n] (per set: stride of the
 // table block); coset >= 0: on that one coset, d_out = [m][2][n].
@@ -138,6 +143,13 @@ hipError_t launch_final_split(const CeParams &p, int coset, uint64_t *d_out, hip
 // launch_split_finish, d_direct = launch_final_split(coset 1), d_hi = [m][2][n]
 hipError_t launch_final_hi(const CeParams &p, const uint64_t *d_odd, const uint64_t *d_direct, uint64_t *d_hi, uint64_t half /* 1/2, memory form */,
                            hipStream_t stream);
+// The same for the merged tables: d_hi[c][j] = (family 4 of d_odd on coset 1 - (direct[c][0] + x^adj_0 direct[c][1])) / 2, d_hi = [m][n]
+hipError_t launch_final_hi_merged(const CeParams &p, const uint64_t *d_odd, const uint64_t *d_direct, uint64_t *d_hi, uint64_t half, hipStream_t stream);
+// inputs of the high part's transforms over cosets 3, 5, 7, d_out = [3][m][n]: with h = (d_tco - d_qco) / 2 ([m][2][n] each: the
+// interpolants over LDE coset 1 of the family's two tables -- the raw output of coset_even_to_odd_merged -- and of the direct sums),
+// h[c][0] + x^adj_0 h[c][1] merged on the coefficients; tm = coset_merge_term(0, adj_0, log_n, g w_8n, 2)
+hipError_t launch_final_hi_merge(const CeParams &p, const uint64_t *d_tco, const uint64_t *d_qco, uint64_t *d_out, const CosetMergeTerm &tm, uint64_t half,
+                                 hipStream_t stream);
 hipError_t build_boundary_inverses(uint64_t *d_table, const uint64_t *d_w, const uint64_t *d_coset, uint64_t w_last, unsigned log_n, unsigned log_b,
                                    hipStream_t stream);
 

@@ -699,7 +699,7 @@ __device__ __forceinline__ fp split_lift(const CeParams &p, unsigned k, size_t j
 // tables per coefficient set: first family 4 (alpha, beta of groups 0, 1, beta of groups 2..4 merged; Rescue windows + linear groups,
 // flags inside) | doubling 3 (alpha, beta of groups 0, 1) | addition 2 (alpha, beta of groups 0, 1 merged) | addition x bit 2 (alpha,
 // beta of group 0) | final addition 2 (alpha, beta of groups 0, 1 merged; below)
-constexpr int SPLIT_TABLES = 13, SPLIT_FAM0 = 4, SPLIT_FINAL = 11;
+constexpr int SPLIT_TABLES = 13, SPLIT_FAM0 = 4, SPLIT_FINAL = 11, SPLIT_FAMILIES = CE_SPLIT_FAMILIES;
 // M coefficient sets (the components of an extension proof): the windows' values are computed once, every set has its own tables
 // (rtab + c * CE_RTAB_WORDS) and its own block of SPLIT_TABLES output polynomials (out + c * SPLIT_TABLES * 4 n).
 template <int M>
@@ -848,7 +848,10 @@ __global__ __launch_bounds__(FNT, M == 1 ? CS_ROUNDS_SPLIT_WAVES : 2) void k_rou
 // values come from the split evaluations (even cosets, [11][4][n]: the first family of four -- alpha, beta of groups 0, 1, beta of
 // groups 2..4 merged -- then doubling (3), addition (2: beta of groups 0, 1 merged), addition x bit (2)) or from their extension
 // (odd cosets, [4 cosets][11][n]).  ADDS to p.out.
-template <int M>
+// MERGED: on the odd cosets the monomial sums inside a flag family were formed before the transforms (ntt.h, coset_even_to_odd_merged):
+// odd = [4 cosets][M][SPLIT_FAMILIES][n] (family 0, doubling, addition, addition x bit, final addition), hi = [4 cosets][M][n] the
+// high part h0 + x^adj_0 h1 of the final addition.  The even cosets keep the thirteen tables.
+template <int M, bool MERGED>
 __global__ __launch_bounds__(256) void k_split_finish(CeParams p, const fp *__restrict__ even, const fp *__restrict__ odd, const fp *__restrict__ hi) {
     const size_t n = (size_t)1 << p.log_n;
     const size_t j = blockIdx.x * (size_t)256 + threadIdx.x;
@@ -872,25 +875,35 @@ __global__ __launch_bounds__(256) void k_split_finish(CeParams p, const fp *__re
     for (int c = 0; c < M; c++) {
         auto value = [&](int tb) {
             const int t = c * SPLIT_TABLES + tb;
-            return (k & 1) ? odd[((size_t)(k >> 1) * T + t) * n + j] : even[((size_t)t * 4 + (k >> 1)) * n + j];
+            return (!MERGED && (k & 1)) ? odd[((size_t)(k >> 1) * T + t) * n + j] : even[((size_t)t * 4 + (k >> 1)) * n + j];
         };
-        fp total = value(0);
+        fp total, dbl, add, addbit, fin;
+        if (MERGED && (k & 1)) { // (uniform: the coset is the block's row)
+            const fp *f = odd + (((size_t)(k >> 1) * M + c) * SPLIT_FAMILIES) * n + j;
+            total = f[0];
+            dbl = f[n];
+            add = f[2 * n];
+            addbit = f[3 * n];
+            fin = fp_sub(f[4 * n], fp_dbl(hi[((size_t)(k >> 1) * M + c) * n + j]));
+        } else {
+            total = value(0);
 #pragma unroll
-        for (int g = 0; g < 3; g++) total = fp_add(total, fp_mul(value(1 + g), xp[g])); // table 3 = groups 2, 3, 4 merged relative to x^adj_2
-        const fp dbl = fp_add(value(4), fp_add(fp_mul(value(5), xp[0]), fp_mul(value(6), xp[1])));
-        const fp add = fp_add(value(7), fp_mul(value(8), xp[0]));                      // table 8 = groups 0, 1 merged relative to x^adj_0
-        const fp addbit = fp_add(value(9), fp_mul(value(10), xp[0]));
-        total = fp_add(total, fp_mul(doubling, dbl));
-        total = fp_add(total, fp_mul(addition, fp_sub(add, fp_mul(bit37, addbit))));
-        {   // final addition: Q = T on the even cosets, T - 2 H on the odd ones (k_final_split); flag = (1 - scalar_mult) schnorr
+            for (int g = 0; g < 3; g++) total = fp_add(total, fp_mul(value(1 + g), xp[g])); // table 3 = groups 2, 3, 4 merged relative to x^adj_2
+            dbl = fp_add(value(4), fp_add(fp_mul(value(5), xp[0]), fp_mul(value(6), xp[1])));
+            add = fp_add(value(7), fp_mul(value(8), xp[0]));                               // table 8 = groups 0, 1 merged relative to x^adj_0
+            addbit = fp_add(value(9), fp_mul(value(10), xp[0]));
+            // final addition: Q = T on the even cosets, T - 2 H on the odd ones (k_final_split)
             fp fa = value(SPLIT_FINAL), fb = value(SPLIT_FINAL + 1);
-            if (k & 1) {
+            if (!MERGED && (k & 1)) {
                 const fp *h = hi + (((size_t)(k >> 1) * M + c) * 2) * n + j;
                 fa = fp_sub(fa, fp_dbl(h[0]));
                 fb = fp_sub(fb, fp_dbl(h[n]));
             }
-            total = fp_add(total, fp_mul(fp_mul(c_not(scalar_mult), per[(size_t)P_SCHNORR * 1024]), fp_add(fa, fp_mul(fb, xp[0]))));
+            fin = fp_add(fa, fp_mul(fb, xp[0]));
         }
+        total = fp_add(total, fp_mul(doubling, dbl));
+        total = fp_add(total, fp_mul(addition, fp_sub(add, fp_mul(bit37, addbit))));
+        total = fp_add(total, fp_mul(fp_mul(c_not(scalar_mult), per[(size_t)P_SCHNORR * 1024]), fin)); // flag = (1 - scalar_mult) schnorr
         fp t = fp_mul(total, divisor);
         // boundary constraints on registers 58, 59 at the first and last step (src/air.rs:175-184), as in the last linear group
         const fp *ba = p.coef + c * CE_COEF_WORDS + 230, *bb = ba + 4;
@@ -1168,6 +1181,32 @@ __global__ __launch_bounds__(256) void k_final_hi(CeParams p, const fp *__restri
     const unsigned q = blockIdx.y % 2, c = blockIdx.y / 2;
     const fp t = odd[((size_t)c * SPLIT_TABLES + SPLIT_FINAL + q) * n + j]; // LDE coset 1 = the first odd coset of `odd`
     hi[((size_t)c * 2 + q) * n + j] = fp_mul(fp_sub(t, direct[((size_t)c * 2 + q) * n + j]), half);
+}
+
+// The merged form (k_split_finish<M, true>): the high part enters the odd cosets only as H' = h0 + x^adj_0 h1.  On LDE coset 1 it
+// follows from the merged table F4 = T_a + x^adj_0 T_b of `odd` and the merged direct sums; grid = (n / 256, M), hi = [M][n].
+template <int M>
+__global__ __launch_bounds__(256) void k_final_hi_merged(CeParams p, const fp *__restrict__ odd, const fp *__restrict__ direct, fp *__restrict__ hi, fp half) {
+    const size_t n = (size_t)1 << p.log_n;
+    const size_t j = blockIdx.x * (size_t)256 + threadIdx.x;
+    const unsigned c = blockIdx.y;
+    const fp xp0 = fp_mul(p.coset[CE_COSET_CONSTS + 2], p.w[(j * p.adj_mod_n[0]) & (n - 1)]); // x^adj_0 on LDE coset 1
+    const fp q = fp_add(direct[((size_t)c * 2) * n + j], fp_mul(direct[((size_t)c * 2 + 1) * n + j], xp0));
+    hi[(size_t)c * n + j] = fp_mul(fp_sub(odd[((size_t)c * SPLIT_FAMILIES + SPLIT_FAMILIES - 1) * n + j], q), half);
+}
+// Cosets 3, 5, 7 need h0 and h1 apart: as polynomials in z (y = w_8n z) their coefficients are (T - Q) / 2 of the interpolants over
+// LDE coset 1 -- tco from the extension kernel (its raw output), qco the interpolated direct sums, both [M][2][n].  The monomial is then
+// merged as in coset_even_to_odd_merged (term: base g w_8n, cosets k - 1 = 2, 4, 6): out = [3][M][n], inputs of ONE transform per coset.
+template <int M>
+__global__ __launch_bounds__(256) void k_final_hi_merge(const fp *__restrict__ tco, const fp *__restrict__ qco, fp *__restrict__ out, size_t n,
+                                                        CosetMergeTerm tm, fp half) {
+    const size_t q = blockIdx.x * (size_t)256 + threadIdx.x;
+    const unsigned c = blockIdx.y;
+    const size_t qs = (q - tm.r) & (n - 1);
+    const size_t i0 = ((size_t)c * 2) * n + q, i1 = ((size_t)c * 2 + 1) * n + qs;
+    const fp h0 = fp_mul(fp_sub(tco[i0], qco[i0]), half), h1 = fp_mul(fp_sub(tco[i1], qco[i1]), half);
+#pragma unroll
+    for (int i = 0; i < 3; i++) out[((size_t)i * M + c) * n + q] = fp_add(h0, fp_mul(h1, tm.c[i][q < tm.r ? 1 : 0]));
 }
 
 // A: Fused<M>, or any accumulator with its interface for M sets (AirSumView below: the standalone MerkleAir)
@@ -2734,13 +2773,39 @@ hipError_t launch_lin_split(const CeParams &p, int part, uint64_t *d_even_family
     }
     return hipGetLastError();
 }
-hipError_t launch_split_finish(const CeParams &p, const uint64_t *d_even, const uint64_t *d_odd, const uint64_t *d_hi, hipStream_t stream) {
+hipError_t launch_split_finish(const CeParams &p, const uint64_t *d_even, const uint64_t *d_odd, const uint64_t *d_hi, hipStream_t stream, bool merged) {
     const size_t n = (size_t)1 << p.log_n;
     const dim3 grid((unsigned)(n / 256), 8), block(256);
     const unsigned m = p.m ? p.m : 1;
-    if (m == 1) hipLaunchKernelGGL(k_split_finish<1>, grid, block, 0, stream, p, d_even, d_odd, d_hi);
-    else if (m == 2) hipLaunchKernelGGL(k_split_finish<2>, grid, block, 0, stream, p, d_even, d_odd, d_hi);
-    else if (m == 3) hipLaunchKernelGGL(k_split_finish<3>, grid, block, 0, stream, p, d_even, d_odd, d_hi);
+    if (m == 1 && merged) hipLaunchKernelGGL((k_split_finish<1, true>), grid, block, 0, stream, p, d_even, d_odd, d_hi);
+    else if (m == 2 && merged) hipLaunchKernelGGL((k_split_finish<2, true>), grid, block, 0, stream, p, d_even, d_odd, d_hi);
+    else if (m == 3 && merged) hipLaunchKernelGGL((k_split_finish<3, true>), grid, block, 0, stream, p, d_even, d_odd, d_hi);
+    else if (m == 1) hipLaunchKernelGGL((k_split_finish<1, false>), grid, block, 0, stream, p, d_even, d_odd, d_hi);
+    else if (m == 2) hipLaunchKernelGGL((k_split_finish<2, false>), grid, block, 0, stream, p, d_even, d_odd, d_hi);
+    else if (m == 3) hipLaunchKernelGGL((k_split_finish<3, false>), grid, block, 0, stream, p, d_even, d_odd, d_hi);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+hipError_t launch_final_hi_merged(const CeParams &p, const uint64_t *d_odd, const uint64_t *d_direct, uint64_t *d_hi, uint64_t half_m, hipStream_t stream) {
+    const size_t n = (size_t)1 << p.log_n;
+    const unsigned m = p.m ? p.m : 1;
+    const dim3 grid((unsigned)(n / 256), m), block(256);
+    if (p.k0 != 0) return hipErrorInvalidValue; // p.coset is indexed by LDE coset
+    if (m == 1) hipLaunchKernelGGL(k_final_hi_merged<1>, grid, block, 0, stream, p, d_odd, d_direct, d_hi, half_m);
+    else if (m == 2) hipLaunchKernelGGL(k_final_hi_merged<2>, grid, block, 0, stream, p, d_odd, d_direct, d_hi, half_m);
+    else if (m == 3) hipLaunchKernelGGL(k_final_hi_merged<3>, grid, block, 0, stream, p, d_odd, d_direct, d_hi, half_m);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+hipError_t launch_final_hi_merge(const CeParams &p, const uint64_t *d_tco, const uint64_t *d_qco, uint64_t *d_out, const CosetMergeTerm &tm, uint64_t half_m,
+                                 hipStream_t stream) {
+    const size_t n = (size_t)1 << p.log_n;
+    const unsigned m = p.m ? p.m : 1;
+    const dim3 grid((unsigned)(n / 256), m), block(256);
+    if (tm.r >= n) return hipErrorInvalidValue;
+    if (m == 1) hipLaunchKernelGGL(k_final_hi_merge<1>, grid, block, 0, stream, d_tco, d_qco, d_out, n, tm, half_m);
+    else if (m == 2) hipLaunchKernelGGL(k_final_hi_merge<2>, grid, block, 0, stream, d_tco, d_qco, d_out, n, tm, half_m);
+    else if (m == 3) hipLaunchKernelGGL(k_final_hi_merge<3>, grid, block, 0, stream, d_tco, d_qco, d_out, n, tm, half_m);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

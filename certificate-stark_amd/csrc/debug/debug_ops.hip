@@ -188,3 +188,32 @@ extern "C" int cstark_debug_mds(void *stream, const uint64_t *d_in, uint64_t *d_
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     return err == hipSuccess ? CSTARK_OK : CSTARK_ERR_HIP;
 }
+
+// ---- the merged even -> odd extension (ntt.h) next to the plain one ---------------------------------------------------------------
+#include "../../../include/cstark_debug_ntt.h"
+#include "../hostfield.h"
+#include "../ntt.h"
+extern "C" int cstark_debug_split_merge(void *stream, const uint64_t *d_in, uint64_t *d_plain, uint64_t *d_merged, uint32_t log_n, const uint64_t *e) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!d_in || !d_plain || !d_merged || !e || log_n < 8 || log_n + 3 > cs::NTT_MAX_LOG_N) return CSTARK_ERR_INVALID_ARG;
+    const size_t n = (size_t)1 << log_n;
+    uint64_t *winv4n = nullptr, *w8n = nullptr;
+    if (hipMalloc((void **)&winv4n, 4 * n * 8) != hipSuccess) return CSTARK_ERR_OOM;
+    if (hipMalloc((void **)&w8n, 8 * n * 8) != hipSuccess) { (void)hipFree(winv4n); return CSTARK_ERR_OOM; }
+    const uint64_t quarter = cs::host::inv(cs::host::from_u64(4)), g = cs::host::lde_offset();
+    cs::CosetMergeDesc d{};
+    d.families = 2; d.tables_per_set = 4; d.raw_family = -1;
+    d.terms[0] = 3; d.terms[1] = 1;
+    d.term[0][0] = cs::coset_merge_term(0, 0, log_n, g);
+    d.term[0][1] = cs::coset_merge_term(1, e[0], log_n, g);
+    d.term[0][2] = cs::coset_merge_term(2, e[1], log_n, g);
+    d.term[1][0] = cs::coset_merge_term(3, e[2], log_n, g);
+    hipError_t err = cs::ntt_power_table(winv4n, 4 * n, cs::host::inv(cs::host::root_of_unity(log_n + 2)), s);
+    if (err == hipSuccess) err = cs::ntt_power_table(w8n, 8 * n, cs::host::root_of_unity(log_n + 3), s);
+    if (err == hipSuccess) err = cs::coset_even_to_odd(d_in, d_plain, log_n, 4, winv4n, w8n, quarter, s);
+    if (err == hipSuccess) err = cs::coset_even_to_odd_merged(d_in, d_merged, log_n, 1, d, winv4n, w8n, quarter, nullptr, s);
+    if (err == hipSuccess) err = hipStreamSynchronize(s);
+    (void)hipFree(winv4n);
+    (void)hipFree(w8n);
+    return err == hipSuccess ? CSTARK_OK : CSTARK_ERR_HIP;
+}

@@ -53,6 +53,27 @@ hipError_t coset_combine(const uint64_t *d_b, uint64_t *d_h, unsigned log_n, uns
 // 4n coefficients are never written.  d_out [4 odd cosets][tables][n]; d_winv_4n = powers of w_4n^-1, d_w_8n = powers of w_8n, quarter = 1/4.
 hipError_t coset_even_to_odd(const uint64_t *d_b, uint64_t *d_out, unsigned log_n, unsigned tables, const uint64_t *d_winv_4n, const uint64_t *d_w_8n,
                              uint64_t quarter, hipStream_t stream, unsigned kc0 = 0, unsigned nkc = 4); // (only even cosets [kc0, kc0 + nkc) present)
+// coset_even_to_odd with the monomial recombination of a flag family done on the coefficient vectors, before any transform: a family
+// sum_t x^(e_t) S_t(x) (x = g y) becomes ONE input vector per odd coset.  With e = n d + r (0 <= r < n) and y^n = w_8^k on coset k,
+//   x^e S_t on coset k = sum_q' y^q' c_k[q' < r] s_k[(q' - r) mod n],   c_k[0] = base^e w_8^(k d),  c_k[1] = c_k[0] w_8^k
+// (s_k = what coset_even_to_odd writes for the table; base = g): a rotation by r, the wrapped entries picking up y^n.
+struct CosetMergeTerm {
+    uint32_t table, r; // table within its set; rotation
+    uint64_t c[4][2];  // per coset slot i (coset k0 + 2 i): the factor of the entries that did not / did wrap
+};
+constexpr int COSET_MERGE_MAX_FAMILIES = 5, COSET_MERGE_MAX_TERMS = 4;
+struct CosetMergeDesc {
+    uint32_t families, tables_per_set;
+    uint32_t terms[COSET_MERGE_MAX_FAMILIES];
+    CosetMergeTerm term[COSET_MERGE_MAX_FAMILIES][COSET_MERGE_MAX_TERMS];
+    int32_t raw_family; // the family whose tables are also written unmerged for the first odd coset (d_raw), -1: none
+};
+// host: the term x^e S_table for the cosets k0, k0 + 2, k0 + 4, k0 + 6 of the 8n-point domain (base: see above)
+CosetMergeTerm coset_merge_term(unsigned table, uint64_t e, unsigned log_n, uint64_t base, unsigned k0 = 1);
+// d_b [sets][tables_per_set][4][n] -> d_out [4 odd cosets][sets][families][n].  d_raw (with raw_family >= 0) [sets][terms][n]:
+// w_8n^q s_1[q] of the family's tables, the coefficients of S_t(g w_8n z) mod (z^n - 1): the table's interpolant over the first odd coset.
+hipError_t coset_even_to_odd_merged(const uint64_t *d_b, uint64_t *d_out, unsigned log_n, unsigned sets, const CosetMergeDesc &desc,
+                                    const uint64_t *d_winv_4n, const uint64_t *d_w_8n, uint64_t quarter, uint64_t *d_raw, hipStream_t stream);
 hipError_t split_columns(const uint64_t *d_h, uint64_t *d_out, unsigned log_n, unsigned log_b, uint64_t ginv, hipStream_t stream);
 
 } // namespace cs

@@ -14,6 +14,7 @@
 // coset-scaling tables (8 MB each at n = 2^20) are shared by all columns and stay in L2 / Infinity Cache.
 #include "ntt.h"
 #include "fp.cuh"
+#include "hostfield.h"
 #include "../../include/cstark_conventions.h"
 #include <stdlib.h>
 #ifdef CS_NTT_NOMATH // measurement build (tools/build_variant_fast.py): the kernels' memory / LDS traffic without their field arithmetic
@@ -947,6 +948,80 @@ hipError_t coset_even_to_odd(const fp *d_b, fp *d_out, unsigned log_n, unsigned 
     const size_t n = (size_t)1 << log_n;
     hipLaunchKernelGGL(k_coset_even_to_odd, dim3((unsigned)((n + 255) / 256), tables), dim3(256), 0, stream, d_b, d_out, n, tables, d_winv_4n, d_w_8n, quarter,
                        kc0, nkc);
+    return hipGetLastError();
+}
+// grid = (n / 256, families, sets): a thread owns output index q' of one family.  Per term the four interpolants are read at
+// (q' - r) mod n (shifted, still coalesced) and taken to the odd cosets as in k_coset_even_to_odd; the term's constant (the wrapped
+// entries: times y^n) and the sum over the family follow in registers.
+__global__ __launch_bounds__(256) void k_coset_even_to_odd_merged(const fp *__restrict__ in, fp *__restrict__ out, size_t n, CosetMergeDesc d,
+                                                                  const fp *__restrict__ winv4n, const fp *__restrict__ w8n, fp quarter,
+                                                                  fp *__restrict__ raw) {
+    const size_t q = blockIdx.x * (size_t)256 + threadIdx.x;
+    if (q >= n) return;
+    const unsigned fam = blockIdx.y, set = blockIdx.z;
+    fp w4[4], w8[8], acc[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 4; k++) w4[k] = winv4n[(size_t)k * n]; // w_4^-k
+#pragma unroll
+    for (int e = 0; e < 8; e++) w8[e] = w8n[(size_t)e * n]; // w_8^e
+    const unsigned terms = d.terms[fam];
+#pragma unroll 1
+    for (unsigned t = 0; t < terms; t++) {
+        const CosetMergeTerm &tm = d.term[fam][t];
+        const size_t qs = (q - tm.r) & (n - 1);
+        const bool wrapped = q < tm.r;
+        const fp *tab = in + ((size_t)set * d.tables_per_set + tm.table) * 4 * n + qs;
+        fp v[4], a[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const fp x = fp_mul(tab[(size_t)k * n], quarter);
+            v[k] = k == 0 ? x : fp_mul(x, winv4n[(size_t)k * qs]);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) { // coefficient a_{qs + n i}
+            fp s = v[0];
+#pragma unroll
+            for (int k = 1; k < 4; k++) s = fp_add(s, fp_mul(v[k], w4[(k * i) & 3]));
+            a[i] = s;
+        }
+#pragma unroll
+        for (int kc = 0; kc < 4; kc++) {
+            const int k = 2 * kc + 1;
+            fp s = a[0];
+#pragma unroll
+            for (int i = 1; i < 4; i++) s = fp_add(s, fp_mul(a[i], w8[(k * i) & 7]));
+            if (kc == 0 && raw && (int)fam == d.raw_family) raw[((size_t)set * terms + t) * n + qs] = fp_mul(s, w8n[qs]);
+            acc[kc] = fp_add(acc[kc], fp_mul(s, tm.c[kc][wrapped ? 1 : 0]));
+        }
+    }
+#pragma unroll
+    for (int kc = 0; kc < 4; kc++) out[(((size_t)kc * gridDim.z + set) * d.families + fam) * n + q] = acc[kc];
+}
+CosetMergeTerm coset_merge_term(unsigned table, uint64_t e, unsigned log_n, uint64_t base, unsigned k0) {
+    CosetMergeTerm t{};
+    const uint64_t n = 1ull << log_n, dq = e >> log_n, w8 = host::root_of_unity(3);
+    t.table = table;
+    t.r = (uint32_t)(e & (n - 1));
+    const uint64_t be = host::pow(base, e);
+    for (unsigned i = 0; i < 4; i++) {
+        const uint64_t k = k0 + 2 * i;
+        t.c[i][0] = host::mul(be, host::pow(w8, (k * (dq & 7)) & 7));
+        t.c[i][1] = host::mul(t.c[i][0], host::pow(w8, k & 7));
+    }
+    return t;
+}
+hipError_t coset_even_to_odd_merged(const fp *d_b, fp *d_out, unsigned log_n, unsigned sets, const CosetMergeDesc &desc, const fp *d_winv_4n,
+                                    const fp *d_w_8n, fp quarter, fp *d_raw, hipStream_t stream) {
+    const size_t n = (size_t)1 << log_n;
+    if (desc.families == 0 || desc.families > (unsigned)COSET_MERGE_MAX_FAMILIES || sets == 0) return hipErrorInvalidValue;
+    for (unsigned f = 0; f < desc.families; f++) {
+        if (desc.terms[f] == 0 || desc.terms[f] > (unsigned)COSET_MERGE_MAX_TERMS) return hipErrorInvalidValue;
+        for (unsigned t = 0; t < desc.terms[f]; t++)
+            if (desc.term[f][t].table >= desc.tables_per_set || desc.term[f][t].r >= n) return hipErrorInvalidValue;
+    }
+    if (desc.raw_family >= (int)desc.families) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_coset_even_to_odd_merged, dim3((unsigned)((n + 255) / 256), desc.families, sets), dim3(256), 0, stream, d_b, d_out, n, desc,
+                       d_winv_4n, d_w_8n, quarter, d_raw);
     return hipGetLastError();
 }
 hipError_t coset_combine(const fp *d_b, fp *d_h, unsigned log_n, unsigned log_b, const fp *d_winv_N, fp b_inv, hipStream_t stream, unsigned tables) {

@@ -4,6 +4,7 @@
  * every primitive against the oracle, and two micro-benchmarks.  None of this is in the product library libcstark_hip.so and
  * nothing in the product calls it.  Field elements: uint64_t in BaseElement memory form (see cstark.h); F_p6 elements are six
  * consecutive base elements; `stream` is a hipStream_t; all pointers are device memory unless noted.  Return: cstark_status.
+ * (The entry point that drives kernels of the product library is declared apart, in cstark_debug_ntt.h.)
  */
 #ifndef CSTARK_DEBUG_H
 #define CSTARK_DEBUG_H
