@@ -901,6 +901,125 @@ static const SplitMerge &tx_split_merge(unsigned log_n) {
     return sm;
 }
 
+// ---- host steps of the degree-split constraint stage --------------------------------------------------------------------------------
+// Low-degree parts are evaluated on the four even cosets, interpolated over that 4n-point sub-domain, extended to the odd cosets and
+// recombined; the final addition reaches degree 5 (n - 1), so its high part is pinned on LDE coset 1 (constraints.hip, k_final_split).
+// TransactionAir (merged and unmerged), its sharded form and SchnorrAir are lists of the steps below.
+namespace {
+
+struct SplitStage {
+    unsigned log_n;
+    size_t n;
+    const NttPlan *pn, *p4, *p8; // transforms of n, 4n and 8n points
+    const CosetTable *t1;        // offset 1, blowup 8: row k holds the powers of w_8n^k
+    hipStream_t stream;
+};
+int split_stage(cstark_ctx *c, unsigned log_n, SplitStage *s) {
+    *s = SplitStage{log_n, (size_t)1 << log_n, nullptr, nullptr, nullptr, nullptr, c->stream};
+    RC_TRY(get_plan(c, log_n, &s->pn));
+    RC_TRY(get_plan(c, log_n + 2, &s->p4));
+    RC_TRY(get_plan(c, log_n + 3, &s->p8));
+    return get_coset_table(c, log_n, 3, cs::host::from_u64(1), &s->t1);
+}
+
+// Inverse n-point transforms with the 1 / n scaling: `batch` blocks of `width` columns, `batch_stride` words apart in all three arrays
+int inverse_columns(const SplitStage &s, const uint64_t *in, uint64_t *scratch, uint64_t *out, unsigned width, unsigned batch = 1, size_t batch_stride = 0) {
+    cs::NttArgs a{};
+    a.in = in; a.scratch = scratch; a.out = out; a.width = width; a.batch = batch; a.log_n = s.log_n;
+    a.in_batch_stride = batch_stride; a.scratch_batch_stride = batch_stride; a.out_batch_stride = batch_stride;
+    a.w = s.pn->winv; a.post_scale = s.pn->n_inv; a.do_scale = true; a.inverse = true; a.aux = s.pn->aux_winv;
+    HIP_TRY(cs::ntt_columns(a, s.stream));
+    return CSTARK_OK;
+}
+
+// Coefficient vectors -> values on odd cosets, one batch of `width` columns per coset (scratch and out: width n words apart; in:
+// in_batch_stride, 0 = every coset from the same coefficients).  The prescale of batch i is row first + 2 i of the offset-1 table:
+//   first = 1: LDE cosets 1, 3, 5, 7 from the coefficients in y = x / g (what coset_even_to_odd writes);
+//   first = 2: cosets 3, 5, 7 from the coefficients in z = y / w_8n of a polynomial interpolated on LDE coset 1 -- on coset k the
+//              prescale is (w_8n^(k-1))^s, k - 1 = 2, 4, 6.
+int forward_to_cosets(const SplitStage &s, unsigned first, const uint64_t *in, uint64_t *scratch, uint64_t *out, unsigned width, size_t in_batch_stride) {
+    const CosetTable *t1 = s.t1;
+    cs::NttArgs f{};
+    f.in = in; f.scratch = scratch; f.out = out; f.width = width; f.batch = first == 1 ? 4 : 3; f.log_n = s.log_n;
+    f.w = s.pn->w; f.prescale = t1->s + first * s.n; f.prescale_batch_stride = 2 * s.n; f.do_scale = false; f.inverse = false;
+    f.aux = s.pn->aux_w; f.aux_ps = t1->aux ? t1->aux + first * t1->aux_words : nullptr; f.aux_ps_batch_stride = 2 * t1->aux_words;
+    f.in_batch_stride = in_batch_stride; f.scratch_batch_stride = (size_t)width * s.n; f.out_batch_stride = (size_t)width * s.n;
+    HIP_TRY(cs::ntt_columns(f, s.stream));
+    return CSTARK_OK;
+}
+
+// interpolants of the even cosets [kc0, kc0 + nkc) -> inputs of the odd cosets' transforms, out = [4 odd cosets][tables][n] (the 4n
+// coefficients are never written)
+int even_to_odd(const SplitStage &s, const uint64_t *in, uint64_t *out, unsigned tables, unsigned kc0 = 0, unsigned nkc = 4) {
+    HIP_TRY(cs::coset_even_to_odd(in, out, s.log_n, tables, s.p4->winv, s.p8->w, cs::host::inv(cs::host::from_u64(4)), s.stream, kc0, nkc));
+    return CSTARK_OK;
+}
+
+// The stage's arrays in the context's workspace.  region = words of an array of tables x 4 columns, hcol = words of the final addition's
+// sums as n-point tables.  fin_hi = [4 odd cosets][hcol]; fin_tco, fin_hm: merged layout only.
+struct SplitWs { uint64_t *even, *sa, *sb, *sc, *odd, *fin_direct, *fin_hi, *fin_co, *fin_scr, *fin_tco, *fin_hm; };
+int split_ws_unmerged(cstark_ctx *c, size_t region, size_t hcol, SplitWs *w) {
+    RC_TRY(ensure_ws(c, (5 * region + 9 * hcol) * 8));
+    *w = SplitWs{};
+    w->even = (uint64_t *)c->ws; w->sa = w->even + region; w->sb = w->sa + region; w->sc = w->sb + region; w->odd = w->sc + region;
+    w->fin_direct = w->odd + region; w->fin_hi = w->fin_direct + hcol; w->fin_co = w->fin_hi + 4 * hcol; w->fin_scr = w->fin_co + hcol /* [3] */;
+    return CSTARK_OK;
+}
+// merged (hcol = 2 m n): the odd cosets hold fregion words of family vectors; the transforms' input and scratch fit the interpolation's
+// scratch (2 fregion <= region); fin_hi = [4 odd cosets][m][n], fin_hm and fin_scr = [3][m][n]
+int split_ws_merged(cstark_ctx *c, size_t region, size_t fregion, size_t hcol, SplitWs *w) {
+    RC_TRY(ensure_ws(c, (3 * region + fregion + 8 * hcol) * 8));
+    *w = SplitWs{};
+    w->even = (uint64_t *)c->ws; w->sa = w->even + region; w->sb = w->sa + region; w->sc = w->sa + fregion; w->odd = w->sb + region;
+    w->fin_direct = w->odd + fregion; w->fin_hi = w->fin_direct + hcol; w->fin_co = w->fin_hi + 2 * hcol; w->fin_tco = w->fin_co + hcol;
+    w->fin_hm = w->fin_tco + hcol; w->fin_scr = w->fin_hm + 3 * hcol / 2;
+    return CSTARK_OK;
+}
+
+// High parts of the final addition's `rows` sums, one transform per sum: with w.fin_direct = their direct evaluation on LDE coset 1 (zero on
+// a shard rank that does not hold it), H = (T - Q) / 2 there, interpolated and extended to cosets 3, 5, 7: w.fin_hi = [4 odd cosets][rows][n].
+// (first, per_set, tables_per_set): where the sums' tables sit in w.odd (constraints.h, launch_final_hi)
+int final_hi_unmerged(const SplitStage &s, const SplitWs &w, unsigned rows, unsigned first, unsigned per_set, unsigned tables_per_set) {
+    HIP_TRY(cs::launch_final_hi(w.odd, w.fin_direct, w.fin_hi, cs::host::inv(cs::host::from_u64(2)), s.log_n, rows, first, per_set, tables_per_set, s.stream));
+    RC_TRY(inverse_columns(s, w.fin_hi, w.fin_scr, w.fin_co, rows));
+    return forward_to_cosets(s, 2, w.fin_co, w.fin_scr, w.fin_hi + (size_t)rows * s.n, rows, 0);
+}
+
+// TransactionAir's parts on the even cosets into even = [CE_SPLIT_TABLES m][4][n]: those whose merged polynomials have degree < 4n
+// (constraints.hip: the Rescue windows with their flags; the doublings and the additions with the flag factored out), the final addition's
+// two sums (they join the tables; their high part follows after the extension) and the three linear groups -- in one pass over the
+// frame (k_lin_all) or, !lin_one_pass, the three launches of round 2.  pev: part timing; the one pass is reported as lin_a, lin_b = 0.
+int tx_even_cosets(const cs::CeParams &p, uint64_t *even, size_t n, hipStream_t stream, hipEvent_t *pev, bool lin_one_pass) {
+    if (pev) HIP_TRY(hipEventRecord(pev[0], stream));
+    HIP_TRY(cs::launch_rounds_setup(p, stream));
+    HIP_TRY(cs::launch_rounds_split(p, even, stream));
+    if (pev) HIP_TRY(hipEventRecord(pev[1], stream));
+    uint64_t *fam_dbl = even + (size_t)cs::CE_SPLIT_FAM0 * 4 * n, *fam_add = fam_dbl + 12 * n, *fam_addbit = fam_add + 8 * n; // 3 | 2 | 2 tables
+    HIP_TRY(cs::launch_ec_split(p, 1, fam_dbl, nullptr, stream));
+    if (pev) HIP_TRY(hipEventRecord(pev[2], stream));
+    HIP_TRY(cs::launch_ec_split(p, 2, fam_add, nullptr, stream));
+    if (pev) HIP_TRY(hipEventRecord(pev[3], stream));
+    HIP_TRY(cs::launch_ec_split(p, 3, fam_dbl, nullptr, stream));
+    if (pev) HIP_TRY(hipEventRecord(pev[4], stream));
+    HIP_TRY(cs::launch_ec_split(p, 4, fam_addbit, fam_add, stream));
+    if (pev) HIP_TRY(hipEventRecord(pev[5], stream));
+    uint64_t *fam_final = fam_addbit + 8 * n;
+    HIP_TRY(cs::launch_final_split(p, -1, fam_final, stream));
+    if (lin_one_pass) {
+        if (pev) HIP_TRY(hipEventRecord(pev[6], stream));
+        HIP_TRY(cs::launch_lin_all(p, even, stream));
+        if (pev) { HIP_TRY(hipEventRecord(pev[7], stream)); HIP_TRY(hipEventRecord(pev[8], stream)); }
+    } else {
+        for (int part = 6; part <= 8; part++) {
+            if (pev) HIP_TRY(hipEventRecord(pev[part], stream));
+            HIP_TRY(cs::launch_lin_split(p, part, even, stream));
+        }
+    }
+    return CSTARK_OK;
+}
+
+} // namespace
+
 // (internal: declared in ctx.h for the prover)
 int tx_evaluate_constraints_sets(cstark_ctx *c, const uint64_t *d_lde, const cstark_tx_coeffs *coeffs, uint32_t m, const uint64_t pub_inputs[4],
                                  uint64_t *const *d_outs, uint32_t merkle_depth, uint32_t log_n, uint32_t log_blowup, uint32_t k0, uint32_t nk,
@@ -924,123 +1043,45 @@ int tx_evaluate_constraints_sets(cstark_ctx *c, const uint64_t *d_lde, const cst
     // the public stage entry points evaluate every point directly and are exact for ANY table
     static const bool split_ext_env = [] { const char *e = getenv("CSTARK_ROUNDS_SPLIT_EXT"); return !e || atoi(e) != 0; }();
     if (split_env && input_is_lde && (m == 1 || split_ext_env) && k0 == 0 && nk == 8 && log_n + 3 <= cs::NTT_MAX_LOG_N) { // (twiddle tables of size 8n)
-        // Parts whose merged polynomials have degree < 4n (constraints.hip: the Rescue windows with their flags; the doublings and the
-        // addition of the generator with the flag factored out) run on the even cosets only; their thirteen polynomials are
-        // interpolated over that 4n-point sub-domain, extended to the odd cosets by transforms of thirteen columns and recombined
-        // at every point.  (Part timing: the extension and the recombination are counted with the last of these parts.)
-        const size_t n = (size_t)1 << log_n;
+        // (Part timing: the extension and the recombination are counted with the last part, lin_c.)
+        SplitStage st;
+        RC_TRY(split_stage(c, log_n, &st));
+        const size_t n = st.n;
         const unsigned T = cs::CE_SPLIT_TABLES * m; // every coefficient set has its own block of polynomials
-        const NttPlan *pn, *p4, *p8;
-        const CosetTable *t1;
-        RC_TRY(get_plan(c, log_n, &pn));
-        RC_TRY(get_plan(c, log_n + 2, &p4));
-        RC_TRY(get_plan(c, log_n + 3, &p8));
-        RC_TRY(get_coset_table(c, log_n, 3, cs::host::from_u64(1), &t1));
         const size_t region = (size_t)T * 4 * n; // words per array of T x 4 columns
         const size_t hcol = (size_t)2 * m * n;   // the final addition's two sums per set: one n-point table each
         // CSTARK_SPLIT_MERGE=0 (tuning / debugging): every polynomial through its own transforms to the odd cosets
         static const bool split_merge_env = [] { const char *e = getenv("CSTARK_SPLIT_MERGE"); return !e || atoi(e) != 0; }();
         const unsigned F = cs::CE_SPLIT_FAMILIES * m;
-        const size_t fregion = (size_t)F * 4 * n; // merged: the families' vectors of the four odd cosets
-        uint64_t *even, *sa, *sb, *sc, *odd, *fin_direct, *fin_hi, *fin_co, *fin_scr, *fin_tco = nullptr, *fin_hm = nullptr;
-        if (split_merge_env) { // the transforms' input and scratch fit the interpolation's scratch: 2 fregion <= region
-            RC_TRY(ensure_ws(c, (3 * region + fregion + 8 * hcol) * 8));
-            even = (uint64_t *)c->ws; sa = even + region; sb = sa + region; sc = sa + fregion; odd = sb + region;
-            fin_direct = odd + fregion; fin_hi = fin_direct + hcol /* [4 odd cosets][m][n] */; fin_co = fin_hi + 2 * hcol; fin_tco = fin_co + hcol;
-            fin_hm = fin_tco + hcol /* [3][m][n] */; fin_scr = fin_hm + 3 * hcol / 2 /* [3][m][n] */;
-        } else {
-            RC_TRY(ensure_ws(c, (5 * region + 9 * hcol) * 8));
-            even = (uint64_t *)c->ws; sa = even + region; sb = sa + region; sc = sb + region; odd = sc + region;
-            fin_direct = odd + region; fin_hi = fin_direct + hcol /* [4 odd cosets][2 m][n] */; fin_co = fin_hi + 4 * hcol; fin_scr = fin_co + hcol /* [3] */;
-        }
-        if (pev) HIP_TRY(hipEventRecord(pev[0], c->stream));
-        HIP_TRY(cs::launch_rounds_setup(p, c->stream));
-        HIP_TRY(cs::launch_rounds_split(p, even, c->stream));
-        if (pev) HIP_TRY(hipEventRecord(pev[1], c->stream));
-        uint64_t *fam_dbl = even + (size_t)cs::CE_SPLIT_FAM0 * 4 * n, *fam_add = fam_dbl + 12 * n, *fam_addbit = fam_add + 8 * n; // 3 | 2 | 2 tables
-        HIP_TRY(cs::launch_ec_split(p, 1, fam_dbl, nullptr, c->stream));
-        if (pev) HIP_TRY(hipEventRecord(pev[2], c->stream));
-        HIP_TRY(cs::launch_ec_split(p, 2, fam_add, nullptr, c->stream));
-        if (pev) HIP_TRY(hipEventRecord(pev[3], c->stream));
-        HIP_TRY(cs::launch_ec_split(p, 3, fam_dbl, nullptr, c->stream));
-        if (pev) HIP_TRY(hipEventRecord(pev[4], c->stream));
-        HIP_TRY(cs::launch_ec_split(p, 4, fam_addbit, fam_add, c->stream));
-        // the final addition reaches degree 5 (n - 1): its two sums on the four even cosets join the tables, ONE odd coset pins the
-        // n coefficients above 4n (below, after the extension); constraints.hip, k_final_split
-        if (pev) HIP_TRY(hipEventRecord(pev[5], c->stream));
-        uint64_t *fam_final = fam_addbit + 8 * n;
-        HIP_TRY(cs::launch_final_split(p, -1, fam_final, c->stream));
-        // the three linear groups: one pass over the frame (k_lin_all); CSTARK_LIN_MERGED=0 (tuning / debugging): the three launches
-        // of round 2.  Part timing: the merged pass is reported as lin_a, lin_b = 0, lin_c = the extension and recombination below.
+        SplitWs w;
+        if (split_merge_env) RC_TRY(split_ws_merged(c, region, (size_t)F * 4 * n, hcol, &w));
+        else RC_TRY(split_ws_unmerged(c, region, hcol, &w));
+        // CSTARK_LIN_MERGED=0 (tuning / debugging): the linear groups in three launches
         static const bool lin_merged = [] { const char *e = getenv("CSTARK_LIN_MERGED"); return !e || atoi(e) != 0; }();
-        if (lin_merged) {
-            if (pev) HIP_TRY(hipEventRecord(pev[6], c->stream));
-            HIP_TRY(cs::launch_lin_all(p, even, c->stream));
-            if (pev) { HIP_TRY(hipEventRecord(pev[7], c->stream)); HIP_TRY(hipEventRecord(pev[8], c->stream)); }
-        } else {
-            for (int part = 6; part <= 8; part++) {
-                if (pev) HIP_TRY(hipEventRecord(pev[part], c->stream));
-                HIP_TRY(cs::launch_lin_split(p, part, even, c->stream));
-            }
-        }
-        cs::NttArgs a{};
-        a.in = even; a.scratch = sa; a.out = sb; a.width = 4 * T; a.batch = 1; a.log_n = log_n; // every polynomial on every even coset
-        a.w = pn->winv; a.post_scale = pn->n_inv; a.do_scale = true; a.inverse = true; a.aux = pn->aux_winv;
-        HIP_TRY(cs::ntt_columns(a, c->stream));
+        RC_TRY(tx_even_cosets(p, w.even, n, c->stream, pev, lin_merged));
+        RC_TRY(inverse_columns(st, w.even, w.sa, w.sb, 4 * T)); // every polynomial on every even coset
         if (split_merge_env) {
             // The recombination inside a flag family is a sum of monomial multiples, i.e. of rotated coefficient vectors: merged where the
             // coefficients sit in registers, five vectors per odd coset and set go through the forward transforms instead of thirteen.
             const SplitMerge &sm = tx_split_merge(log_n);
-            HIP_TRY(cs::coset_even_to_odd_merged(sb, sa, log_n, m, sm.desc, p4->winv, p8->w, cs::host::inv(cs::host::from_u64(4)), fin_tco, c->stream));
-            cs::NttArgs f{};
-            f.in = sa; f.scratch = sc; f.out = odd; f.width = F; f.batch = 4; f.log_n = log_n; // sa = [4 odd cosets][m][5][n]
-            f.w = pn->w; f.prescale = t1->s + n; f.prescale_batch_stride = 2 * n; f.do_scale = false; f.inverse = false;
-            f.aux = pn->aux_w; f.aux_ps = t1->aux ? t1->aux + t1->aux_words : nullptr; f.aux_ps_batch_stride = 2 * t1->aux_words;
-            f.in_batch_stride = (size_t)F * n; f.scratch_batch_stride = (size_t)F * n; f.out_batch_stride = (size_t)F * n;
-            HIP_TRY(cs::ntt_columns(f, c->stream));
+            HIP_TRY(cs::coset_even_to_odd_merged(w.sb, w.sa, log_n, m, sm.desc, st.p4->winv, st.p8->w, cs::host::inv(cs::host::from_u64(4)), w.fin_tco, c->stream));
+            RC_TRY(forward_to_cosets(st, 1, w.sa, w.sc, w.odd, F, (size_t)F * n)); // sa = [4 odd cosets][m][5][n]
             // high part of the final addition, H' = h0 + x^adj_0 h1: on LDE coset 1 from the merged table and the merged direct sums;
             // h0, h1 apart only as coefficients (interpolant of T over coset 1 from the extension kernel, minus that of the direct
             // sums), merged there, then ONE transform per set to each of the cosets 3, 5, 7
             const uint64_t half = cs::host::inv(cs::host::from_u64(2));
-            HIP_TRY(cs::launch_final_split(p, 1, fin_direct, c->stream));
-            HIP_TRY(cs::launch_final_hi_merged(p, odd, fin_direct, fin_hi, half, c->stream));
-            cs::NttArgs hi_inv{};
-            hi_inv.in = fin_direct; hi_inv.scratch = fin_scr; hi_inv.out = fin_co; hi_inv.width = 2 * m; hi_inv.batch = 1; hi_inv.log_n = log_n;
-            hi_inv.w = pn->winv; hi_inv.post_scale = pn->n_inv; hi_inv.do_scale = true; hi_inv.inverse = true; hi_inv.aux = pn->aux_winv;
-            HIP_TRY(cs::ntt_columns(hi_inv, c->stream));
-            HIP_TRY(cs::launch_final_hi_merge(p, fin_tco, fin_co, fin_hm, sm.hi, half, c->stream));
-            cs::NttArgs hi_fwd{};
-            hi_fwd.in = fin_hm; hi_fwd.scratch = fin_scr; hi_fwd.out = fin_hi + (size_t)m * n; hi_fwd.width = m; hi_fwd.batch = 3; hi_fwd.log_n = log_n;
-            hi_fwd.w = pn->w; hi_fwd.prescale = t1->s + 2 * n; hi_fwd.prescale_batch_stride = 2 * n; hi_fwd.do_scale = false; hi_fwd.inverse = false;
-            hi_fwd.aux = pn->aux_w; hi_fwd.aux_ps = t1->aux ? t1->aux + 2 * t1->aux_words : nullptr; hi_fwd.aux_ps_batch_stride = 2 * t1->aux_words;
-            hi_fwd.in_batch_stride = (size_t)m * n; hi_fwd.scratch_batch_stride = (size_t)m * n; hi_fwd.out_batch_stride = (size_t)m * n;
-            HIP_TRY(cs::ntt_columns(hi_fwd, c->stream));
+            HIP_TRY(cs::launch_final_split(p, 1, w.fin_direct, c->stream));
+            HIP_TRY(cs::launch_final_hi_merged(p, w.odd, w.fin_direct, w.fin_hi, half, c->stream));
+            RC_TRY(inverse_columns(st, w.fin_direct, w.fin_scr, w.fin_co, 2 * m));
+            HIP_TRY(cs::launch_final_hi_merge(p, w.fin_tco, w.fin_co, w.fin_hm, sm.hi, half, c->stream));
+            RC_TRY(forward_to_cosets(st, 2, w.fin_hm, w.fin_scr, w.fin_hi + (size_t)m * n, m, (size_t)m * n));
         } else {
-            // interpolants of the even cosets -> inputs of the odd cosets' transforms (the 4n coefficients are never written)
-            HIP_TRY(cs::coset_even_to_odd(sb, sa, log_n, T, p4->winv, p8->w, cs::host::inv(cs::host::from_u64(4)), c->stream)); // sa = [4 odd cosets][T][n]
-            cs::NttArgs f{};
-            f.in = sa; f.scratch = sc; f.out = odd; f.width = T; f.batch = 4; f.log_n = log_n;
-            f.w = pn->w; f.prescale = t1->s + n; f.prescale_batch_stride = 2 * n; f.do_scale = false; f.inverse = false;
-            f.aux = pn->aux_w; f.aux_ps = t1->aux ? t1->aux + t1->aux_words : nullptr; f.aux_ps_batch_stride = 2 * t1->aux_words;
-            f.in_batch_stride = (size_t)T * n; f.scratch_batch_stride = (size_t)T * n; f.out_batch_stride = (size_t)T * n;
-            HIP_TRY(cs::ntt_columns(f, c->stream));
-            {   // high parts of the final addition's sums: H = (T - Q) / 2 on LDE coset 1, interpolated there and extended to cosets 3, 5, 7
-                HIP_TRY(cs::launch_final_split(p, 1, fin_direct, c->stream));
-                HIP_TRY(cs::launch_final_hi(p, odd, fin_direct, fin_hi, cs::host::inv(cs::host::from_u64(2)), c->stream));
-                cs::NttArgs hi_inv{};
-                hi_inv.in = fin_hi; hi_inv.scratch = fin_scr; hi_inv.out = fin_co; hi_inv.width = 2 * m; hi_inv.batch = 1; hi_inv.log_n = log_n;
-                hi_inv.w = pn->winv; hi_inv.post_scale = pn->n_inv; hi_inv.do_scale = true; hi_inv.inverse = true; hi_inv.aux = pn->aux_winv;
-                HIP_TRY(cs::ntt_columns(hi_inv, c->stream));
-                // coefficients of H(w_8n z) in z -> values on coset k: prescale by (w_8n^(k-1))^s, k - 1 = 2, 4, 6: rows 2, 4, 6 of the offset-1 table
-                cs::NttArgs hi_fwd{};
-                hi_fwd.in = fin_co; hi_fwd.scratch = fin_scr; hi_fwd.out = fin_hi + hcol; hi_fwd.width = 2 * m; hi_fwd.batch = 3; hi_fwd.log_n = log_n;
-                hi_fwd.w = pn->w; hi_fwd.prescale = t1->s + 2 * n; hi_fwd.prescale_batch_stride = 2 * n; hi_fwd.do_scale = false; hi_fwd.inverse = false;
-                hi_fwd.aux = pn->aux_w; hi_fwd.aux_ps = t1->aux ? t1->aux + 2 * t1->aux_words : nullptr; hi_fwd.aux_ps_batch_stride = 2 * t1->aux_words;
-                hi_fwd.in_batch_stride = 0; hi_fwd.scratch_batch_stride = hcol; hi_fwd.out_batch_stride = hcol;
-                HIP_TRY(cs::ntt_columns(hi_fwd, c->stream));
-            }
+            RC_TRY(even_to_odd(st, w.sb, w.sa, T)); // sa = [4 odd cosets][T][n]
+            RC_TRY(forward_to_cosets(st, 1, w.sa, w.sc, w.odd, T, (size_t)T * n));
+            HIP_TRY(cs::launch_final_split(p, 1, w.fin_direct, c->stream));
+            RC_TRY(final_hi_unmerged(st, w, 2 * m, cs::CE_SPLIT_FINAL, 2, cs::CE_SPLIT_TABLES));
         }
-        HIP_TRY(cs::launch_split_finish(p, even, odd, fin_hi, c->stream, split_merge_env));
+        HIP_TRY(cs::launch_split_finish(p, w.even, w.odd, w.fin_hi, c->stream, split_merge_env));
         if (pev) HIP_TRY(hipEventRecord(pev[cs::CE_NUM_PARTS], c->stream));
     } else {
         HIP_TRY(cs::launch_eval_constraints(p, nk, c->stream, pev));
@@ -1063,14 +1104,10 @@ int tx_evaluate_constraints_shard(cstark_ctx *c, const uint64_t *d_lde, const ui
     for (int i = 0; i < 4; i++) p.pub[i] = pub_inputs[i];
     p.nkc = nk / 2;
     const unsigned kc0 = k0 / 2, nkc = nk / 2;
-    const size_t n = (size_t)1 << log_n;
+    SplitStage st;
+    RC_TRY(split_stage(c, log_n, &st));
+    const size_t n = st.n;
     const unsigned T = cs::CE_SPLIT_TABLES;
-    const NttPlan *pn, *p4, *p8;
-    const CosetTable *t1;
-    RC_TRY(get_plan(c, log_n, &pn));
-    RC_TRY(get_plan(c, log_n + 2, &p4));
-    RC_TRY(get_plan(c, log_n + 3, &p8));
-    RC_TRY(get_coset_table(c, log_n, 3, cs::host::from_u64(1), &t1));
     const size_t region = (size_t)T * 4 * n, hcol = (size_t)2 * n;
     // register 37 on all eight cosets first: the extension uses the workspace itself
     uint64_t *bit37 = nullptr;
@@ -1083,47 +1120,18 @@ int tx_evaluate_constraints_shard(cstark_ctx *c, const uint64_t *d_lde, const ui
         bit37 = c->shard_bit37;
         RC_TRY(lde_impl(c, d_coeffs + (size_t)37 * n, bit37, 1, 0, 1, log_n, 3, cs::host::lde_offset(), 0, 8));
     }
-    RC_TRY(ensure_ws(c, (5 * region + 9 * hcol) * 8));
-    uint64_t *even = (uint64_t *)c->ws, *sa = even + region, *sb = sa + region, *sc = sb + region, *odd = sc + region;
-    uint64_t *fin_direct = odd + region, *fin_hi = fin_direct + hcol, *fin_co = fin_hi + 4 * hcol, *fin_scr = fin_co + hcol;
-    HIP_TRY(cs::launch_rounds_setup(p, c->stream));
-    HIP_TRY(cs::launch_rounds_split(p, even, c->stream));
-    uint64_t *fam_dbl = even + (size_t)cs::CE_SPLIT_FAM0 * 4 * n, *fam_add = fam_dbl + 12 * n, *fam_addbit = fam_add + 8 * n, *fam_final = fam_addbit + 8 * n;
-    HIP_TRY(cs::launch_ec_split(p, 1, fam_dbl, nullptr, c->stream));
-    HIP_TRY(cs::launch_ec_split(p, 2, fam_add, nullptr, c->stream));
-    HIP_TRY(cs::launch_ec_split(p, 3, fam_dbl, nullptr, c->stream));
-    HIP_TRY(cs::launch_ec_split(p, 4, fam_addbit, fam_add, c->stream));
-    HIP_TRY(cs::launch_final_split(p, -1, fam_final, c->stream));
-    HIP_TRY(cs::launch_lin_all(p, even, c->stream));
+    SplitWs w;
+    RC_TRY(split_ws_unmerged(c, region, hcol, &w));
+    RC_TRY(tx_even_cosets(p, w.even, n, c->stream, nullptr, true)); // no part timing; always the one-pass linear kernel
     // interpolation of every table on the rank's even cosets: columns [kc0, kc0 + nkc) of each table's four (batch = table)
-    cs::NttArgs a{};
-    a.in = even + (size_t)kc0 * n; a.scratch = sa + (size_t)kc0 * n; a.out = sb + (size_t)kc0 * n; a.width = nkc; a.batch = T; a.log_n = log_n;
-    a.in_batch_stride = 4 * n; a.scratch_batch_stride = 4 * n; a.out_batch_stride = 4 * n;
-    a.w = pn->winv; a.post_scale = pn->n_inv; a.do_scale = true; a.inverse = true; a.aux = pn->aux_winv;
-    HIP_TRY(cs::ntt_columns(a, c->stream));
-    HIP_TRY(cs::coset_even_to_odd(sb, sa, log_n, T, p4->winv, p8->w, cs::host::inv(cs::host::from_u64(4)), c->stream, kc0, nkc));
-    cs::NttArgs f{};
-    f.in = sa; f.scratch = sc; f.out = odd; f.width = T; f.batch = 4; f.log_n = log_n;
-    f.w = pn->w; f.prescale = t1->s + n; f.prescale_batch_stride = 2 * n; f.do_scale = false; f.inverse = false;
-    f.aux = pn->aux_w; f.aux_ps = t1->aux ? t1->aux + t1->aux_words : nullptr; f.aux_ps_batch_stride = 2 * t1->aux_words;
-    f.in_batch_stride = (size_t)T * n; f.scratch_batch_stride = (size_t)T * n; f.out_batch_stride = (size_t)T * n;
-    HIP_TRY(cs::ntt_columns(f, c->stream));
-    {   // high parts of the final addition: H = (T - Q) / 2 on LDE coset 1 -- Q (the direct evaluation there) only on the rank that holds coset 1
-        if (k0 == 0) HIP_TRY(cs::launch_final_split(p, 1, fin_direct, c->stream));
-        else HIP_TRY(hipMemsetAsync(fin_direct, 0, hcol * 8, c->stream));
-        HIP_TRY(cs::launch_final_hi(p, odd, fin_direct, fin_hi, cs::host::inv(cs::host::from_u64(2)), c->stream));
-        cs::NttArgs hi_inv{};
-        hi_inv.in = fin_hi; hi_inv.scratch = fin_scr; hi_inv.out = fin_co; hi_inv.width = 2; hi_inv.batch = 1; hi_inv.log_n = log_n;
-        hi_inv.w = pn->winv; hi_inv.post_scale = pn->n_inv; hi_inv.do_scale = true; hi_inv.inverse = true; hi_inv.aux = pn->aux_winv;
-        HIP_TRY(cs::ntt_columns(hi_inv, c->stream));
-        cs::NttArgs hi_fwd{};
-        hi_fwd.in = fin_co; hi_fwd.scratch = fin_scr; hi_fwd.out = fin_hi + hcol; hi_fwd.width = 2; hi_fwd.batch = 3; hi_fwd.log_n = log_n;
-        hi_fwd.w = pn->w; hi_fwd.prescale = t1->s + 2 * n; hi_fwd.prescale_batch_stride = 2 * n; hi_fwd.do_scale = false; hi_fwd.inverse = false;
-        hi_fwd.aux = pn->aux_w; hi_fwd.aux_ps = t1->aux ? t1->aux + 2 * t1->aux_words : nullptr; hi_fwd.aux_ps_batch_stride = 2 * t1->aux_words;
-        hi_fwd.in_batch_stride = 0; hi_fwd.scratch_batch_stride = hcol; hi_fwd.out_batch_stride = hcol;
-        HIP_TRY(cs::ntt_columns(hi_fwd, c->stream));
-    }
-    HIP_TRY(cs::launch_split_finish_shard(p, even, odd, fin_hi, bit37, d_out, c->stream));
+    RC_TRY(inverse_columns(st, w.even + (size_t)kc0 * n, w.sa + (size_t)kc0 * n, w.sb + (size_t)kc0 * n, nkc, T, 4 * n));
+    RC_TRY(even_to_odd(st, w.sb, w.sa, T, kc0, nkc));
+    RC_TRY(forward_to_cosets(st, 1, w.sa, w.sc, w.odd, T, (size_t)T * n));
+    // Q, the direct evaluation on LDE coset 1, only on the rank that holds that coset: the ranks' shares of H add up
+    if (k0 == 0) HIP_TRY(cs::launch_final_split(p, 1, w.fin_direct, c->stream));
+    else HIP_TRY(hipMemsetAsync(w.fin_direct, 0, hcol * 8, c->stream));
+    RC_TRY(final_hi_unmerged(st, w, 2, cs::CE_SPLIT_FINAL, 2, cs::CE_SPLIT_TABLES));
+    HIP_TRY(cs::launch_split_finish_shard(p, w.even, w.odd, w.fin_hi, bit37, d_out, c->stream));
     return CSTARK_OK;
 }
 int tx_shard_combine(cstark_ctx *c, const uint64_t *d_parts, uint64_t *d_out, uint32_t log_n, uint32_t nk) {
@@ -1628,47 +1636,24 @@ static int air_combine_impl(cstark_ctx *c, int air, uint32_t n_items, const uint
             // directly (CSTARK_SCHNORR_FINAL5=0: on all eight cosets through the frame evaluator)
             static const bool final5 = [] { const char *e = getenv("CSTARK_SCHNORR_FINAL5"); return !e || atoi(e) != 0; }();
             const unsigned T = final5 ? cs::SCHNORR_SPLIT_TABLES : cs::SCHNORR_SPLIT_EC_TABLES;
-            const NttPlan *pn, *p4, *p8;
-            const CosetTable *t1;
-            RC_TRY(get_plan(c, log_n, &pn));
-            RC_TRY(get_plan(c, log_n + 2, &p4));
-            RC_TRY(get_plan(c, log_n + 3, &p8));
-            RC_TRY(get_coset_table(c, log_n, 3, cs::host::from_u64(1), &t1));
+            SplitStage st;
+            RC_TRY(split_stage(c, log_n, &st));
             const size_t region = (size_t)T * 4 * n, hcol = (size_t)3 * n; // hcol: the final addition's three sums, one n-point table each
-            RC_TRY(ensure_ws(c, (5 * region + 9 * hcol) * 8));
-            uint64_t *even = (uint64_t *)c->ws, *sa = even + region, *sb = sa + region, *sc = sb + region, *odd = sc + region;
-            uint64_t *fin_direct = odd + region, *fin_hi = fin_direct + hcol /* [4 odd cosets][3][n] */, *fin_co = fin_hi + 4 * hcol, *fin_scr = fin_co + hcol /* [3] */;
-            HIP_TRY(cs::launch_schnorr_ec_split(p, d_schnorr_aux_lde, d_txl, even, c->stream));
-            if (final5) HIP_TRY(cs::launch_schnorr_final_split(p, d_txl, even + (size_t)cs::SCHNORR_SPLIT_EC_TABLES * 4 * n, -1, c->stream));
-            cs::NttArgs a{};
-            a.in = even; a.scratch = sa; a.out = sb; a.width = 4 * T; a.batch = 1; a.log_n = log_n;
-            a.w = pn->winv; a.post_scale = pn->n_inv; a.do_scale = true; a.inverse = true; a.aux = pn->aux_winv;
-            HIP_TRY(cs::ntt_columns(a, c->stream));
-            HIP_TRY(cs::coset_even_to_odd(sb, sa, log_n, T, p4->winv, p8->w, cs::host::inv(cs::host::from_u64(4)), c->stream));
-            cs::NttArgs f{};
-            f.in = sa; f.scratch = sc; f.out = odd; f.width = T; f.batch = 4; f.log_n = log_n;
-            f.w = pn->w; f.prescale = t1->s + n; f.prescale_batch_stride = 2 * n; f.do_scale = false; f.inverse = false;
-            f.aux = pn->aux_w; f.aux_ps = t1->aux ? t1->aux + t1->aux_words : nullptr; f.aux_ps_batch_stride = 2 * t1->aux_words;
-            f.in_batch_stride = (size_t)T * n; f.scratch_batch_stride = (size_t)T * n; f.out_batch_stride = (size_t)T * n;
-            HIP_TRY(cs::ntt_columns(f, c->stream));
-            if (final5) { // H = (T - F) / 2 on LDE coset 1, interpolated there and extended to cosets 3, 5, 7 (as for TransactionAir)
-                HIP_TRY(cs::launch_schnorr_final_split(p, d_txl, fin_direct, 1, c->stream));
-                HIP_TRY(cs::launch_schnorr_final_hi(p, odd, fin_direct, fin_hi, cs::host::inv(cs::host::from_u64(2)), c->stream));
-                cs::NttArgs hi_inv{};
-                hi_inv.in = fin_hi; hi_inv.scratch = fin_scr; hi_inv.out = fin_co; hi_inv.width = 3; hi_inv.batch = 1; hi_inv.log_n = log_n;
-                hi_inv.w = pn->winv; hi_inv.post_scale = pn->n_inv; hi_inv.do_scale = true; hi_inv.inverse = true; hi_inv.aux = pn->aux_winv;
-                HIP_TRY(cs::ntt_columns(hi_inv, c->stream));
-                cs::NttArgs hi_fwd{}; // coefficients of H(w_8n z) in z -> coset k: prescale by (w_8n^(k-1))^s, k - 1 = 2, 4, 6: rows 2, 4, 6 of the offset-1 table
-                hi_fwd.in = fin_co; hi_fwd.scratch = fin_scr; hi_fwd.out = fin_hi + hcol; hi_fwd.width = 3; hi_fwd.batch = 3; hi_fwd.log_n = log_n;
-                hi_fwd.w = pn->w; hi_fwd.prescale = t1->s + 2 * n; hi_fwd.prescale_batch_stride = 2 * n; hi_fwd.do_scale = false; hi_fwd.inverse = false;
-                hi_fwd.aux = pn->aux_w; hi_fwd.aux_ps = t1->aux ? t1->aux + 2 * t1->aux_words : nullptr; hi_fwd.aux_ps_batch_stride = 2 * t1->aux_words;
-                hi_fwd.in_batch_stride = 0; hi_fwd.scratch_batch_stride = hcol; hi_fwd.out_batch_stride = hcol;
-                HIP_TRY(cs::ntt_columns(hi_fwd, c->stream));
+            SplitWs w;
+            RC_TRY(split_ws_unmerged(c, region, hcol, &w));
+            HIP_TRY(cs::launch_schnorr_ec_split(p, d_schnorr_aux_lde, d_txl, w.even, c->stream));
+            if (final5) HIP_TRY(cs::launch_schnorr_final_split(p, d_txl, w.even + (size_t)cs::SCHNORR_SPLIT_EC_TABLES * 4 * n, -1, c->stream));
+            RC_TRY(inverse_columns(st, w.even, w.sa, w.sb, 4 * T));
+            RC_TRY(even_to_odd(st, w.sb, w.sa, T));
+            RC_TRY(forward_to_cosets(st, 1, w.sa, w.sc, w.odd, T, (size_t)T * n));
+            if (final5) { // the three sums directly on LDE coset 1, then their high parts as for TransactionAir
+                HIP_TRY(cs::launch_schnorr_final_split(p, d_txl, w.fin_direct, 1, c->stream));
+                RC_TRY(final_hi_unmerged(st, w, 3, cs::SCHNORR_SPLIT_EC_TABLES, 3, cs::SCHNORR_SPLIT_TABLES));
             }
             // the round gadget of the message hash in the folded form (CSTARK_SCHNORR_ROUNDS=0: inside the frame evaluator)
             static const bool rounds_env = [] { const char *e = getenv("CSTARK_SCHNORR_ROUNDS"); return !e || atoi(e) != 0; }();
-            HIP_TRY(cs::launch_schnorr_split_finish(p, d_schnorr_aux_lde, pt->tab, even, odd, t_grp[0], t_grp[6], c->stream,
-                                                    rounds_env ? c->air_coef_buf + mrt_off : nullptr, t_grp[42], final5 ? fin_hi : nullptr));
+            HIP_TRY(cs::launch_schnorr_split_finish(p, d_schnorr_aux_lde, pt->tab, w.even, w.odd, t_grp[0], t_grp[6], c->stream,
+                                                    rounds_env ? c->air_coef_buf + mrt_off : nullptr, t_grp[42], final5 ? w.fin_hi : nullptr));
         } else {
             HIP_TRY(cs::launch_schnorr_fused(p, d_schnorr_aux_lde, pt->tab, nk, c->stream));
         }

@@ -91,11 +91,10 @@ hipError_t launch_schnorr_split_finish(const AirCombineParams &p, const uint64_t
                                        unsigned g0, unsigned g1, hipStream_t stream, uint64_t *d_rtab = nullptr, unsigned round_group = 0,
                                        const uint64_t *d_hi = nullptr);
 // The final addition on five cosets: its three sums on the even cosets (coset < 0: d_out = tables 8..10 of d_even, [3][4][n]) or directly
-// on LDE coset 1 (coset = 1: d_out = [3][n]); launch_schnorr_final_hi: d_hi[q] = (d_odd's table 8 + q on coset 1 - d_direct[q]) / 2.
-// With d_hi = [4 odd cosets][3][n] (coset 1 from launch_schnorr_final_hi, cosets 3, 5, 7 its extension) launch_schnorr_split_finish
+// on LDE coset 1 (coset = 1: d_out = [3][n]); launch_final_hi(rows 3, first 8, per_set 3): d_hi[q] = (d_odd's table 8 + q on coset 1 - d_direct[q]) / 2.
+// With d_hi = [4 odd cosets][3][n] (coset 1 from launch_final_hi, cosets 3, 5, 7 its extension) launch_schnorr_split_finish
 // recombines the final addition too (tables of SCHNORR_SPLIT_TABLES); without it the tables are SCHNORR_SPLIT_EC_TABLES wide.
 hipError_t launch_schnorr_final_split(const AirCombineParams &p, const uint64_t *d_coefs_tx_layout, uint64_t *d_out, int coset, hipStream_t stream);
-hipError_t launch_schnorr_final_hi(const AirCombineParams &p, const uint64_t *d_odd, const uint64_t *d_direct, uint64_t *d_hi, uint64_t half_m, hipStream_t stream);
 hipError_t launch_eval_transitions_range(const uint64_t *lde, uint64_t *out, unsigned log_n, unsigned nk, hipStream_t stream);
 // RescueAir (benches/rescue.rs): ptab [b][29][8]
 hipError_t launch_eval_transitions_rescue(const uint64_t *lde, const uint64_t *ptab, uint64_t *out, unsigned log_n, unsigned k0, unsigned nk,
@@ -106,8 +105,7 @@ hipError_t launch_eval_transitions(const CeParams &p, unsigned nk, hipStream_t s
 // cur[c * nf + j] (c < 94), next[c * nf + j] and the periodic values per[c * nf + j] (c < 48); out[i * nf + j], i < 115 (device memory)
 hipError_t launch_eval_frames(const uint64_t *cur, const uint64_t *next, const uint64_t *per, uint64_t *out, unsigned nf, hipStream_t stream);
 constexpr int CE_NUM_PARTS = 9; // launches of the fused evaluation: rounds, dbl0, add0, dbl1, add1, final, lin_a, lin_b, lin_c
-hipError_t launch_eval_constraints(const CeParams &p, unsigned nk, hipStream_t stream, hipEvent_t *part_events = nullptr, unsigned done_mask = 0,
-                                   bool record_end = true);
+hipError_t launch_eval_constraints(const CeParams &p, unsigned nk, hipStream_t stream, hipEvent_t *part_events = nullptr);
 // Split evaluation of the Rescue windows (m = 1, all 8 cosets, k0 = 0; constraints.hip): setup of the per-proof tables; the four
 // low-degree polynomials on the even cosets, d_even = [4][4][n]; recombination over all cosets from d_even and their extension to
 // the odd cosets d_odd = [4 cosets][4][n] (writes p.out, like the first part of launch_eval_constraints).
@@ -118,7 +116,7 @@ hipError_t launch_rounds_split(const CeParams &p, uint64_t *d_even, hipStream_t 
 // part 4 = addition of the public key: its quartic half is a family of its own (d_even_family), its linear half is ADDED to the
 // addition family d_even_linear (after part 2 wrote it)
 hipError_t launch_ec_split(const CeParams &p, int part, uint64_t *d_even_family, uint64_t *d_even_linear, hipStream_t stream);
-constexpr int CE_SPLIT_TABLES = 13, CE_SPLIT_FAM0 = 4; // first family (Rescue windows + linear groups): four polynomials; doubling 3 | addition 2 | addition x bit 2 | final addition 2
+constexpr int CE_SPLIT_TABLES = 13, CE_SPLIT_FAM0 = 4, CE_SPLIT_FINAL = 11; // first family (Rescue windows + linear groups): four polynomials; doubling 3 | addition 2 | addition x bit 2 | final addition 2
 // split evaluation of a linear group (part 6, 7, 8): adds to the first family, d_even_family0 = [4][4][n]
 hipError_t launch_lin_split(const CeParams &p, int part, uint64_t *d_even_family0, hipStream_t stream);
 // the three linear groups in one pass over the frame (k_lin_all); same four polynomials as the three launch_lin_split parts
@@ -139,10 +137,12 @@ hipError_t launch_split_finish(const CeParams &p, const uint64_t *d_even, const 
 // (alpha; beta of groups 0, 1 merged) on the four even cosets into the family's tables d_out = [2][4][n] (per set: stride of the
 // table block); coset >= 0: on that one coset, d_out = [m][2][n].
 hipError_t launch_final_split(const CeParams &p, int coset, uint64_t *d_out, hipStream_t stream);
-// hi[c][q][j] = (T(coset 1)[c][q][j] - direct[c][q][j]) / 2: values of the high-part polynomials on LDE coset 1; d_odd as for
-// launch_split_finish, d_direct = launch_final_split(coset 1), d_hi = [m][2][n]
-hipError_t launch_final_hi(const CeParams &p, const uint64_t *d_odd, const uint64_t *d_direct, uint64_t *d_hi, uint64_t half /* 1/2, memory form */,
-                           hipStream_t stream);
+// Values of the high-part polynomials on LDE coset 1, for either AIR: d_hi[r][j] = (T_r(coset 1)[j] - d_direct[r][j]) / 2, r < rows, where
+// T_r is table first + r % per_set of set r / per_set in d_odd = [4 odd cosets][sets][tables_per_set][n] (coset 1 first) and d_direct the
+// direct evaluation on coset 1.  TransactionAir: rows = 2 m, (first, per_set, tables_per_set) = (11, 2, CE_SPLIT_TABLES); SchnorrAir:
+// rows = 3, (SCHNORR_SPLIT_EC_TABLES, 3, SCHNORR_SPLIT_TABLES).
+hipError_t launch_final_hi(const uint64_t *d_odd, const uint64_t *d_direct, uint64_t *d_hi, uint64_t half /* 1/2, memory form */, unsigned log_n,
+                           unsigned rows, unsigned first, unsigned per_set, unsigned tables_per_set, hipStream_t stream);
 // The same for the merged tables: d_hi[c][j] = (family 4 of d_odd on coset 1 - (direct[c][0] + x^adj_0 direct[c][1])) / 2, d_hi = [m][n]
 hipError_t launch_final_hi_merged(const CeParams &p, const uint64_t *d_odd, const uint64_t *d_direct, uint64_t *d_hi, uint64_t half, hipStream_t stream);
 // inputs of the high part's transforms over cosets 3, 5, 7, d_out = [3][m][n]: with h = (d_tco - d_qco) / 2 ([m][2][n] each: the

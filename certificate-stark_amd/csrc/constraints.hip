@@ -699,7 +699,7 @@ __device__ __forceinline__ fp split_lift(const CeParams &p, unsigned k, size_t j
 // tables per coefficient set: first family 4 (alpha, beta of groups 0, 1, beta of groups 2..4 merged; Rescue windows + linear groups,
 // flags inside) | doubling 3 (alpha, beta of groups 0, 1) | addition 2 (alpha, beta of groups 0, 1 merged) | addition x bit 2 (alpha,
 // beta of group 0) | final addition 2 (alpha, beta of groups 0, 1 merged; below)
-constexpr int SPLIT_TABLES = 13, SPLIT_FAM0 = 4, SPLIT_FINAL = 11, SPLIT_FAMILIES = CE_SPLIT_FAMILIES;
+constexpr int SPLIT_TABLES = 13, SPLIT_FAM0 = 4, SPLIT_FINAL = CE_SPLIT_FINAL, SPLIT_FAMILIES = CE_SPLIT_FAMILIES;
 // M coefficient sets (the components of an extension proof): the windows' values are computed once, every set has its own tables
 // (rtab + c * CE_RTAB_WORDS) and its own block of SPLIT_TABLES output polynomials (out + c * SPLIT_TABLES * 4 n).
 template <int M>
@@ -1174,13 +1174,15 @@ __global__ __launch_bounds__(FNT, CS_EC_WAVES) void k_final_split(CeParams p, fp
         }
     }
 }
-template <int M>
-__global__ __launch_bounds__(256) void k_final_hi(CeParams p, const fp *__restrict__ odd, const fp *__restrict__ direct, fp *__restrict__ hi, fp half) {
-    const size_t n = (size_t)1 << p.log_n;
+// hi[r][j] = (T_r - Q_r) / 2 on LDE coset 1, the first odd coset of `odd`; grid = (n / 256, rows).  Row r is sum r % per_set of set
+// r / per_set, table `first` + r % per_set of the set's `tables_per_set`: (11, 2, 13) for TransactionAir, (8, 3, 11) for SchnorrAir.
+__global__ __launch_bounds__(256) void k_final_hi(const fp *__restrict__ odd, const fp *__restrict__ direct, fp *__restrict__ hi, fp half, unsigned log_n,
+                                                  unsigned first, unsigned per_set, unsigned tables_per_set) {
+    const size_t n = (size_t)1 << log_n;
     const size_t j = blockIdx.x * (size_t)256 + threadIdx.x;
-    const unsigned q = blockIdx.y % 2, c = blockIdx.y / 2;
-    const fp t = odd[((size_t)c * SPLIT_TABLES + SPLIT_FINAL + q) * n + j]; // LDE coset 1 = the first odd coset of `odd`
-    hi[((size_t)c * 2 + q) * n + j] = fp_mul(fp_sub(t, direct[((size_t)c * 2 + q) * n + j]), half);
+    const unsigned r = blockIdx.y;
+    const fp t = odd[((size_t)(r / per_set) * tables_per_set + first + r % per_set) * n + j];
+    hi[(size_t)r * n + j] = fp_mul(fp_sub(t, direct[(size_t)r * n + j]), half);
 }
 
 // The merged form (k_split_finish<M, true>): the high part enters the odd cosets only as H' = h0 + x^adj_0 h1.  On LDE coset 1 it
@@ -2260,13 +2262,6 @@ __global__ __launch_bounds__(FNT, CS_EC_WAVES) void k_schnorr_final_split(const 
         else out[(size_t)q * n + j] = acc.result(0, q);
     }
 }
-// hi[q][j] = (T_q - F_q) / 2 on LDE coset 1: odd = [4 odd cosets][T][n] (coset 1 first), direct = [3][n]
-__global__ __launch_bounds__(256) void k_schnorr_final_hi(const fp *__restrict__ odd, const fp *__restrict__ direct, fp *__restrict__ hi, fp half, unsigned log_n) {
-    const size_t n = (size_t)1 << log_n;
-    const size_t j = blockIdx.x * (size_t)256 + threadIdx.x;
-    const unsigned q = blockIdx.y;
-    hi[(size_t)q * n + j] = fp_mul(fp_sub(odd[((size_t)SCH_SPLIT_EC_TABLES + q) * n + j], direct[(size_t)q * n + j]), half);
-}
 // recombination over all cosets: out[k][j] = doubling(x) (D_a + x^adj_0 D_b0 + x^adj_1 D_b1) + addition(x) [(A_a + x^adj_0 A_b0 + x^adj_1 A_b1)
 // - bit37 (Q_a + x^adj_0 Q_b0)] + final(x) (F_a + x^adj_0 F_b0 + x^adj_1 F_b1), F = T on the even cosets and T - 2 H on the odd ones
 // (hi = [4 odd cosets][3][n]; null: the final addition is left to k_schnorr_fused<SF_FINAL>); the remaining parts (hash / limb
@@ -2608,11 +2603,6 @@ hipError_t launch_schnorr_final_split(const AirCombineParams &p, const uint64_t 
     hipLaunchKernelGGL(k_schnorr_final_split, dim3((unsigned)(n / FNT), coset < 0 ? 4 : 1), dim3(FNT), 0, stream, p.lde, d_coefs_tx_layout, d_out, p.log_n, coset);
     return hipGetLastError();
 }
-hipError_t launch_schnorr_final_hi(const AirCombineParams &p, const uint64_t *d_odd, const uint64_t *d_direct, uint64_t *d_hi, uint64_t half_m, hipStream_t stream) {
-    const size_t n = (size_t)1 << p.log_n;
-    hipLaunchKernelGGL(k_schnorr_final_hi, dim3((unsigned)(n / 256), 3), dim3(256), 0, stream, d_odd, d_direct, d_hi, half_m, p.log_n);
-    return hipGetLastError();
-}
 // the folded round gadgets of the sub-AIRs on the matrix cores (rounds_mfma.hip; same values).  CSTARK_ROUNDS_MFMA=0: vector-ALU kernels
 static bool merkle_rounds_on_matrix_cores(size_t n) {
     static const bool env = [] { const char *e = getenv("CSTARK_ROUNDS_MFMA"); return !e || atoi(e) != 0; }();
@@ -2712,6 +2702,17 @@ hipError_t launch_air_combine(const AirCombineParams &p, unsigned nk, hipStream_
     return hipGetLastError();
 }
 
+// The run-time number of coefficient sets as a template argument: fn(std::integral_constant<int, M>{}) for m = M in 1 .. CE_MAX_SETS,
+// then the launch status; hipErrorInvalidValue for any other m.
+template <class Fn>
+static hipError_t with_sets(unsigned m, Fn fn) {
+    if (m == 1) fn(std::integral_constant<int, 1>{});
+    else if (m == 2) fn(std::integral_constant<int, 2>{});
+    else if (m == 3) fn(std::integral_constant<int, 3>{});
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 hipError_t launch_rounds_setup(const CeParams &p, hipStream_t stream) {
     const unsigned m = p.m ? p.m : 1;
     if (m > 3) return hipErrorInvalidValue;
@@ -2730,25 +2731,19 @@ hipError_t launch_rounds_split(const CeParams &p, uint64_t *d_even, hipStream_t 
     // the matrix-core kernel (rounds_mfma.hip; same values).  CSTARK_ROUNDS_MFMA=0: the vector-ALU kernels below
     static const bool mfma_env = [] { const char *e = getenv("CSTARK_ROUNDS_MFMA"); return !e || atoi(e) != 0; }();
     if (m <= 3 && mfma_env && n % 512 == 0) return launch_rounds_mfma(p, d_even, stream);
-    if (m == 1) hipLaunchKernelGGL(k_rounds_split<1>, grid, block, 0, stream, p, d_even);
-    else if (m == 2) hipLaunchKernelGGL(k_rounds_split<2>, grid, block, 0, stream, p, d_even);
-    else if (m == 3) hipLaunchKernelGGL(k_rounds_split<3>, grid, block, 0, stream, p, d_even);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return with_sets(m, [&](auto M) { hipLaunchKernelGGL(k_rounds_split<M>, grid, block, 0, stream, p, d_even); });
 }
 hipError_t launch_ec_split(const CeParams &p, int part, uint64_t *d_even_family, uint64_t *d_even_linear, hipStream_t stream) {
     const size_t n = (size_t)1 << p.log_n;
     const dim3 grid((unsigned)(n / FNT), p.nkc ? p.nkc : 4), block(FNT);
     const unsigned m = p.m ? p.m : 1;
-#define CS_EC(M)                                                                                                                                      \
-    if (part == PART_DBL0) hipLaunchKernelGGL((k_ec_split<PART_DBL0, false, M>), grid, block, 0, stream, p, d_even_family, d_even_linear);           \
-    else if (part == PART_DBL1) hipLaunchKernelGGL((k_ec_split<PART_DBL1, true, M>), grid, block, 0, stream, p, d_even_family, d_even_linear);       \
-    else if (part == PART_ADD0) hipLaunchKernelGGL((k_ec_split<PART_ADD0, false, M>), grid, block, 0, stream, p, d_even_family, d_even_linear);      \
-    else if (part == PART_ADD1) hipLaunchKernelGGL((k_ec_split<PART_ADD1, false, M>), grid, block, 0, stream, p, d_even_family, d_even_linear);      \
-    else return hipErrorInvalidValue;
-    if (m == 1) { CS_EC(1) } else if (m == 2) { CS_EC(2) } else if (m == 3) { CS_EC(3) } else return hipErrorInvalidValue;
-#undef CS_EC
-    return hipGetLastError();
+    if (part != PART_DBL0 && part != PART_DBL1 && part != PART_ADD0 && part != PART_ADD1) return hipErrorInvalidValue;
+    return with_sets(m, [&](auto M) {
+        if (part == PART_DBL0) hipLaunchKernelGGL((k_ec_split<PART_DBL0, false, M>), grid, block, 0, stream, p, d_even_family, d_even_linear);
+        else if (part == PART_DBL1) hipLaunchKernelGGL((k_ec_split<PART_DBL1, true, M>), grid, block, 0, stream, p, d_even_family, d_even_linear);
+        else if (part == PART_ADD0) hipLaunchKernelGGL((k_ec_split<PART_ADD0, false, M>), grid, block, 0, stream, p, d_even_family, d_even_linear);
+        else hipLaunchKernelGGL((k_ec_split<PART_ADD1, false, M>), grid, block, 0, stream, p, d_even_family, d_even_linear);
+    });
 }
 hipError_t launch_lin_all(const CeParams &p, uint64_t *d_even_family0, hipStream_t stream) {
     const size_t n = (size_t)1 << p.log_n;
@@ -2777,25 +2772,17 @@ hipError_t launch_split_finish(const CeParams &p, const uint64_t *d_even, const 
     const size_t n = (size_t)1 << p.log_n;
     const dim3 grid((unsigned)(n / 256), 8), block(256);
     const unsigned m = p.m ? p.m : 1;
-    if (m == 1 && merged) hipLaunchKernelGGL((k_split_finish<1, true>), grid, block, 0, stream, p, d_even, d_odd, d_hi);
-    else if (m == 2 && merged) hipLaunchKernelGGL((k_split_finish<2, true>), grid, block, 0, stream, p, d_even, d_odd, d_hi);
-    else if (m == 3 && merged) hipLaunchKernelGGL((k_split_finish<3, true>), grid, block, 0, stream, p, d_even, d_odd, d_hi);
-    else if (m == 1) hipLaunchKernelGGL((k_split_finish<1, false>), grid, block, 0, stream, p, d_even, d_odd, d_hi);
-    else if (m == 2) hipLaunchKernelGGL((k_split_finish<2, false>), grid, block, 0, stream, p, d_even, d_odd, d_hi);
-    else if (m == 3) hipLaunchKernelGGL((k_split_finish<3, false>), grid, block, 0, stream, p, d_even, d_odd, d_hi);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return with_sets(m, [&](auto M) {
+        if (merged) hipLaunchKernelGGL((k_split_finish<M, true>), grid, block, 0, stream, p, d_even, d_odd, d_hi);
+        else hipLaunchKernelGGL((k_split_finish<M, false>), grid, block, 0, stream, p, d_even, d_odd, d_hi);
+    });
 }
 hipError_t launch_final_hi_merged(const CeParams &p, const uint64_t *d_odd, const uint64_t *d_direct, uint64_t *d_hi, uint64_t half_m, hipStream_t stream) {
     const size_t n = (size_t)1 << p.log_n;
     const unsigned m = p.m ? p.m : 1;
     const dim3 grid((unsigned)(n / 256), m), block(256);
     if (p.k0 != 0) return hipErrorInvalidValue; // p.coset is indexed by LDE coset
-    if (m == 1) hipLaunchKernelGGL(k_final_hi_merged<1>, grid, block, 0, stream, p, d_odd, d_direct, d_hi, half_m);
-    else if (m == 2) hipLaunchKernelGGL(k_final_hi_merged<2>, grid, block, 0, stream, p, d_odd, d_direct, d_hi, half_m);
-    else if (m == 3) hipLaunchKernelGGL(k_final_hi_merged<3>, grid, block, 0, stream, p, d_odd, d_direct, d_hi, half_m);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return with_sets(m, [&](auto M) { hipLaunchKernelGGL(k_final_hi_merged<M>, grid, block, 0, stream, p, d_odd, d_direct, d_hi, half_m); });
 }
 hipError_t launch_final_hi_merge(const CeParams &p, const uint64_t *d_tco, const uint64_t *d_qco, uint64_t *d_out, const CosetMergeTerm &tm, uint64_t half_m,
                                  hipStream_t stream) {
@@ -2803,11 +2790,7 @@ hipError_t launch_final_hi_merge(const CeParams &p, const uint64_t *d_tco, const
     const unsigned m = p.m ? p.m : 1;
     const dim3 grid((unsigned)(n / 256), m), block(256);
     if (tm.r >= n) return hipErrorInvalidValue;
-    if (m == 1) hipLaunchKernelGGL(k_final_hi_merge<1>, grid, block, 0, stream, d_tco, d_qco, d_out, n, tm, half_m);
-    else if (m == 2) hipLaunchKernelGGL(k_final_hi_merge<2>, grid, block, 0, stream, d_tco, d_qco, d_out, n, tm, half_m);
-    else if (m == 3) hipLaunchKernelGGL(k_final_hi_merge<3>, grid, block, 0, stream, d_tco, d_qco, d_out, n, tm, half_m);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return with_sets(m, [&](auto M) { hipLaunchKernelGGL(k_final_hi_merge<M>, grid, block, 0, stream, d_tco, d_qco, d_out, n, tm, half_m); });
 }
 hipError_t launch_split_finish_shard(const CeParams &p, const uint64_t *d_even, const uint64_t *d_odd, const uint64_t *d_hi, const uint64_t *d_bit37_all,
                                      uint64_t *d_out, hipStream_t stream) {
@@ -2827,56 +2810,35 @@ hipError_t launch_final_split(const CeParams &p, int coset, uint64_t *d_out, hip
     const unsigned even_rows = p.nkc ? p.nkc : 4;
     const dim3 grid((unsigned)(n / FNT), coset < 0 ? even_rows : 1), block(FNT);
     const unsigned m = p.m ? p.m : 1;
-    if (m == 1) hipLaunchKernelGGL(k_final_split<1>, grid, block, 0, stream, p, d_out, coset);
-    else if (m == 2) hipLaunchKernelGGL(k_final_split<2>, grid, block, 0, stream, p, d_out, coset);
-    else if (m == 3) hipLaunchKernelGGL(k_final_split<3>, grid, block, 0, stream, p, d_out, coset);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return with_sets(m, [&](auto M) { hipLaunchKernelGGL(k_final_split<M>, grid, block, 0, stream, p, d_out, coset); });
 }
-hipError_t launch_final_hi(const CeParams &p, const uint64_t *d_odd, const uint64_t *d_direct, uint64_t *d_hi, uint64_t half_m, hipStream_t stream) {
-    const size_t n = (size_t)1 << p.log_n;
-    const unsigned m = p.m ? p.m : 1;
-    const dim3 grid((unsigned)(n / 256), 2 * m), block(256);
-    if (m == 1) hipLaunchKernelGGL(k_final_hi<1>, grid, block, 0, stream, p, d_odd, d_direct, d_hi, half_m);
-    else if (m == 2) hipLaunchKernelGGL(k_final_hi<2>, grid, block, 0, stream, p, d_odd, d_direct, d_hi, half_m);
-    else if (m == 3) hipLaunchKernelGGL(k_final_hi<3>, grid, block, 0, stream, p, d_odd, d_direct, d_hi, half_m);
-    else return hipErrorInvalidValue;
+hipError_t launch_final_hi(const uint64_t *d_odd, const uint64_t *d_direct, uint64_t *d_hi, uint64_t half_m, unsigned log_n, unsigned rows, unsigned first,
+                           unsigned per_set, unsigned tables_per_set, hipStream_t stream) {
+    const size_t n = (size_t)1 << log_n;
+    if (n % 256 || rows == 0 || per_set == 0 || rows % per_set || first + per_set > tables_per_set) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_final_hi, dim3((unsigned)(n / 256), rows), dim3(256), 0, stream, d_odd, d_direct, d_hi, half_m, log_n, first, per_set, tables_per_set);
     return hipGetLastError();
 }
 
-hipError_t launch_eval_constraints(const CeParams &p, unsigned nk, hipStream_t stream, hipEvent_t *part_events, unsigned done_mask, bool record_end) {
-    const bool rounds_done = done_mask & 1u; // done_mask: bit PART = that part was evaluated by the caller (split evaluation), its event recorded
+hipError_t launch_eval_constraints(const CeParams &p, unsigned nk, hipStream_t stream, hipEvent_t *part_events) {
     const size_t n = (size_t)1 << p.log_n;
     const dim3 grid((unsigned)(n / FNT), nk), block(FNT);
     // part_events (optional, CE_NUM_PARTS + 1 events): recorded around every part so that callers can time each launch
     const unsigned m = p.m ? p.m : 1;
-    if (m > 3) return hipErrorInvalidValue;
-    // rounds_done: the caller ran launch_rounds_setup and the split evaluation of the Rescue windows (and recorded part_events[0])
-    if (!rounds_done) {
-        const hipError_t e = launch_rounds_setup(p, stream);
-        if (e != hipSuccess) return e;
-    }
+    hipError_t e = launch_rounds_setup(p, stream); // (m > 3 fails here)
+    if (e != hipSuccess) return e;
 #define CS_PART(PART)                                                                                                                   \
-    if ((done_mask >> PART) & 1u) {                                                                                                     \
-    } else if (part_events) (void)hipEventRecord(part_events[PART], stream);                                                            \
-    if ((done_mask >> PART) & 1u) {                                                                                                     \
-    } else if (m == 1) {                                                                                                                       \
+    if (part_events) (void)hipEventRecord(part_events[PART], stream);                                                                   \
+    e = with_sets(m, [&](auto M) {                                                                                                      \
         if (PART == PART_ROUNDS && ROUNDS_DYN_LDS)                                                                                      \
-            (void)hipFuncSetAttribute((const void *)k_eval_fused<PART, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROUNDS_LDS); \
-        hipLaunchKernelGGL((k_eval_fused<PART, 1>), grid, block, PART == PART_ROUNDS ? ROUNDS_DYN_LDS : 0, stream, p);                    \
-    } else if (m == 2) {                                                                                                                \
-        if (PART == PART_ROUNDS && ROUNDS_DYN_LDS)                                                                                      \
-            (void)hipFuncSetAttribute((const void *)k_eval_fused<PART, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROUNDS_LDS); \
-        hipLaunchKernelGGL((k_eval_fused<PART, 2>), grid, block, PART == PART_ROUNDS ? ROUNDS_DYN_LDS : 0, stream, p);                    \
-    } else {                                                                                                                            \
-        if (PART == PART_ROUNDS && ROUNDS_DYN_LDS)                                                                                      \
-            (void)hipFuncSetAttribute((const void *)k_eval_fused<PART, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROUNDS_LDS); \
-        hipLaunchKernelGGL((k_eval_fused<PART, 3>), grid, block, PART == PART_ROUNDS ? ROUNDS_DYN_LDS : 0, stream, p);                    \
-    }
+            (void)hipFuncSetAttribute((const void *)k_eval_fused<PART, M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROUNDS_LDS); \
+        hipLaunchKernelGGL((k_eval_fused<PART, M>), grid, block, PART == PART_ROUNDS ? ROUNDS_DYN_LDS : 0, stream, p);                  \
+    });                                                                                                                                 \
+    if (e != hipSuccess) return e;
     CS_PART(PART_ROUNDS) CS_PART(PART_DBL0) CS_PART(PART_ADD0) CS_PART(PART_DBL1) CS_PART(PART_ADD1) CS_PART(PART_FINAL)
     CS_PART(PART_LIN_A) CS_PART(PART_LIN_B) CS_PART(PART_LIN_C)
 #undef CS_PART
-    if (part_events && record_end) (void)hipEventRecord(part_events[NUM_PARTS], stream);
+    if (part_events) (void)hipEventRecord(part_events[NUM_PARTS], stream);
     static_assert(NUM_PARTS == CE_NUM_PARTS, "part count");
     return hipGetLastError();
 }

@@ -144,6 +144,36 @@ def test_merged_stage_for_several_coefficient_sets(oracle, backend, stage_cases,
         assert (got[q] == oracle.tx_evaluate_constraints(lde, sets[q], pub, 3, 3)).all(), "coefficient set %d" % q
 
 
+def test_unmerged_stage_for_several_coefficient_sets(oracle, stage_cases, tmp_path):
+    """CSTARK_SPLIT_MERGE=0 with m = 2, 3: the high part's transforms to cosets 3, 5, 7 then read ONE block of 2 m coefficient columns
+    for all three cosets.  The switch is read once per process, hence the child, which leaves its outputs in a file."""
+    _, pub, ldes = stage_cases[(1, 3)]
+    lde = ldes[0]
+    assert_adjustments_exercise_the_carry(lde.shape[2])
+    np.save(tmp_path / "lde.npy", lde)
+    np.save(tmp_path / "pub.npy", pub)
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "import numpy as np\n"
+            "from oracle import oracle as O\n"
+            "from certificate_stark_amd.backend import Backend, to_numpy_u64\n"
+            "b = Backend()\n"
+            "lde, pub = np.load(sys.argv[1] + '/lde.npy'), np.load(sys.argv[1] + '/pub.npy')\n"
+            "for m in (2, 3):\n"
+            "    sets = [O.make_coeffs(100 + q) for q in range(m)]\n"
+            "    got = to_numpy_u64(b.evaluate_constraints_ext(b.from_numpy_u64(lde), sets, pub, 3, input_is_lde=True))\n"
+            "    np.save(sys.argv[1] + '/got%%d.npy' %% m, got)\n"
+            "b.close()\n") % ROOT
+    child = subprocess.run([sys.executable, "-c", code, str(tmp_path)], env=dict(os.environ, CSTARK_SPLIT_MERGE="0"), capture_output=True, text=True,
+                           timeout=600)
+    assert child.returncode == 0, child.stderr[-2000:]
+    for m in (2, 3):
+        got = np.load(tmp_path / ("got%d.npy" % m))
+        assert got.shape == (m, 8, lde.shape[2])
+        for q in range(m):
+            ref = oracle.tx_evaluate_constraints(lde, oracle.make_coeffs(100 + q), pub, 3, 3)
+            assert (got[q] == ref).all(), "m = %d, coefficient set %d: cosets that differ: %s" % (m, q, sorted(set(np.argwhere(got[q] != ref)[:, 0].tolist())))
+
+
 # ---- 3. both paths write the same proof -----------------------------------------------------------------------------------------
 
 def test_merged_and_unmerged_paths_give_the_same_proof_bytes():
