@@ -77,6 +77,7 @@ void prove_arena_free(ProveArena *a) {
     delete a;
 }
 int grind_nonce(cstark_ctx *c, ProveArena *a, const Coin &coin, unsigned bits, uint64_t *nonce_out);
+uint64_t host_nonce(const Coin &coin, unsigned bits);
 
 namespace {
 
@@ -333,12 +334,6 @@ std::vector<uint8_t> channel_seed(const AirJob &job, const cstark_options &opt, 
     return channel_seed(job.width, job.log_n, opt, job.log_b, log_rem, job.pub.data(), job.pub.size(), job.pub_bytes.data(), job.pub_bytes.size());
 }
 
-// The proof bytes from the pieces in hand (proof_layout.h), straight into the caller's buffer.
-int emit_proof(const ProofShape &S, const ProofParts &p, uint8_t *proof, size_t capacity, size_t *proof_len) {
-    if (write_proof(S, p, proof, capacity, proof_len)) return fail(CSTARK_ERR_INVALID_ARG, "proof buffer too small (required size returned in *proof_len)");
-    return CSTARK_OK;
-}
-
 // ---- query stage (host channel): proof of work, the query positions and their folded forms, on the device at a->d_pos --------------------
 struct Queries {
     uint64_t nonce = 1;
@@ -418,17 +413,7 @@ int open_stage(cstark_ctx *c, ProveArena *a, const ProofShape &S, const OpenSrc 
     HIP_TRY(hipMemcpyAsync(a->h_open, d_block, O.bytes, hipMemcpyDeviceToHost, st));
     return CSTARK_OK;
 }
-// the opening sections of a proof, from the host copy of such a block
-void opened_parts(ProofParts &p, const ProofShape &S, const uint8_t *h, const OpenBlock &O, const uint32_t *counts) {
-    p.trows = h + O.trows; p.tpaths = h + O.tpaths; p.crows = h + O.crows; p.cpaths = h + O.cpaths;
-    p.counts = counts;
-    for (unsigned l = 0; l < S.n_layers; l++) { p.lrows[l] = h + O.lrows[l]; p.lpaths[l] = h + O.lpaths[l]; }
-}
 
-// Interpolation and extension of the trace columns (cosets [job.k0, job.k0 + job.nk)); records the two stage events (after the
-// interpolation, after the extension).  With column batches (AirJob::batches) the complete columns go first -- interpolated AND
-// extended while the internal streams still write the later ones -- so the "interpolate" stage time then also holds the extension
-// of the earlier batches.
 // Extension of columns [col0, col0 + ncols) of the trace: the cosets [k0, k0 + nk) of a sharded proof, or all of them -- in block
 // order when the blowup factor exceeds the AIR's constraint-evaluation blowup: block r = the blowup-ce extension with offset g w_(b n)^r
 int lde_trace(cstark_ctx *c, ProveArena *a, const AirJob &job, uint32_t col0, uint32_t ncols) {
@@ -443,6 +428,10 @@ int lde_trace(cstark_ctx *c, ProveArena *a, const AirJob &job, uint32_t col0, ui
     }
     return CSTARK_OK;
 }
+// Interpolation and extension of the trace columns (cosets [job.k0, job.k0 + job.nk)); records the two stage events (after the
+// interpolation, after the extension).  With column batches (AirJob::batches) the complete columns go first -- interpolated AND
+// extended while the internal streams still write the later ones -- so the "interpolate" stage time then also holds the extension
+// of the earlier batches.
 int commit_columns(cstark_ctx *c, ProveArena *a, AirJob &job, hipStream_t st, int &evi) {
     const uint32_t W = job.width, log_n = job.log_n;
     const size_t n = (size_t)1 << log_n;
@@ -467,6 +456,16 @@ int commit_columns(cstark_ctx *c, ProveArena *a, AirJob &job, hipStream_t st, in
 
 } // namespace
 
+// the sequential search on the host (also what the batched range prover runs per proof below 12 bits)
+uint64_t host_nonce(const Coin &coin, unsigned bits) {
+    for (uint64_t nonce = 1;; nonce++) {
+        uint8_t out[32];
+        coin.with_int(coin.seed, nonce, out);
+        uint64_t v = 0;
+        for (int i = 0; i < 8; i++) v |= (uint64_t)out[i] << (8 * i);
+        if (bits == 0 || (v & ((1ull << bits) - 1)) == 0) return nonce;
+    }
+}
 // Proof of work: the smallest nonce >= 1 whose digest with the seed has `bits` low zero bits (0 bits: nonce 1).  A search of 2^bits
 // hashes in sequence on the host costs 10 ms at 16 bits (43 ms with the Sha3 coin); from 12 bits on the GPU searches 2^22 nonces per launch --
 // chunks in increasing order and an atomic minimum inside a chunk, so the nonce is the one the sequential search finds.
@@ -474,15 +473,7 @@ int commit_columns(cstark_ctx *c, ProveArena *a, AirJob &job, hipStream_t st, in
 int grind_nonce(cstark_ctx *c, ProveArena *a, const Coin &coin, unsigned bits, uint64_t *nonce_out) {
     static const bool dev_env = [] { const char *e = getenv("CSTARK_GRIND_DEVICE"); return !e || atoi(e) != 0; }();
     if (bits == 0 || !dev_env || bits < 12) {
-        uint64_t nonce = 1;
-        for (;; nonce++) {
-            uint8_t out[32];
-            coin.with_int(coin.seed, nonce, out);
-            uint64_t v = 0;
-            for (int i = 0; i < 8; i++) v |= (uint64_t)out[i] << (8 * i);
-            if (bits == 0 || (v & ((1ull << bits) - 1)) == 0) break;
-        }
-        *nonce_out = nonce;
+        *nonce_out = host_nonce(coin, bits);
         return CSTARK_OK;
     }
     unsigned long long *d_found; // [found | seed (Sha3 coin: read from device memory)]
@@ -503,18 +494,29 @@ int grind_nonce(cstark_ctx *c, ProveArena *a, const Coin &coin, unsigned bits, u
     }
 }
 
-// Prover::prove for any of the AIRs over the base field, as a sequence of phases.  On one GPU (prove_core) they run back to back;
-// the sharded entry points (cstark_tx_shard_*: one proof across several GPUs by LDE coset) run them with the ranks' all-gathers in
-// between -- leaf digests after `commit`, merged evaluations after `evaluate`, the opened trace rows after `compose`.
+// Prover::prove for any of the AIRs, as a sequence of phases.  On one GPU (prove_core) they run back to back; the sharded entry points
+// (cstark_tx_shard_*: one proof across several GPUs by LDE coset) run them with the ranks' all-gathers in between -- leaf digests after
+// `commit`, merged evaluations after `evaluate`, the opened trace rows after `compose`.
+// FieldExtension::Quadratic / Cubic (m = 2, 3): base-field trace; everything the coin draws lives in the degree-m extension (ext.hip).
+// Coefficients multiply base-field constraint values, so the merged evaluations are the AIR's evaluator applied with m coefficient sets
+// (one per component): TransactionAir merges all sets in one pass over the frame, the sub-AIRs merge their materialised evaluations m
+// times.  Layout differences of the proof: out-of-domain values are m-tuples, composition rows hold ce m-tuples, FRI rows and the
+// remainder are component-major.
 struct ProofRun {
     cstark_options opt{};
     AirJob job;
-    unsigned log_rem = 0, n_layers = 0, log_b = 3, log_f = 2;
+    unsigned log_rem = 0, n_layers = 0, log_b = 3, log_f = 2, m = 1; // m: base-field words of a drawn element (field_extension + 1)
     ProofShape shape{};
     Coin coin;
     uint8_t trace_root[32] = {}, cons_root[32] = {}, rem_commit[32] = {};
-    std::vector<uint64_t> ta, tb, ba, bb, ood_trace, ood_comp, remainder;
+    std::vector<uint64_t> ta[3], tb[3], ba[3], bb[3], ood_trace, ood_comp, remainder; // ta .. bb: one coefficient set per component
     std::vector<uint8_t> layer_roots;
+    // device buffers (run_buffers): the arena's own for m = 1, slots of its per-AIR list sized for three components otherwise
+    uint64_t *comb[3] = {}, *cco[3] = {}; // per component: merged evaluations [ce][n], their column coefficients
+    uint64_t *ccoefs = nullptr;           // the m ce coefficient columns of the composition table: column m i + q = component q of column i
+    uint64_t *clde = nullptr, *deep = nullptr; // its extension [b][m ce][n]; the DEEP composition [m][b n], coset-major
+    std::vector<uint64_t *> layer;        // FRI layer evaluations, rows of m f words (component-major), last = remainder
+    uint8_t *d_open = nullptr;
     Queries q;
     int evi = 0, phase = 0; // phase: 1 commit, 2 evaluate, 3 compose done
     bool sharded() const { return job.sharded; }
@@ -524,7 +526,170 @@ void proof_run_free(ProofRun *r) { delete r; }
 
 namespace {
 
-#define STAGE() HIP_TRY(hipEventRecord(a->ev[R.evi++], st))
+int run_buffers(cstark_ctx *c, ProveArena *a, ProofRun &R) {
+    const unsigned m = R.m, n_layers = R.n_layers, log_N = R.job.log_n + R.log_b;
+    if (m == 1) {
+        R.comb[0] = a->combined; R.cco[0] = R.ccoefs = a->ccoef; R.clde = a->clde; R.deep = a->deep; R.layer = a->layer; R.d_open = a->d_open;
+        return CSTARK_OK;
+    }
+    const size_t b = (size_t)1 << R.log_b, N = b << R.job.log_n, W = R.job.width, CN = (size_t)1 << (R.job.log_ce + R.job.log_n), nq = R.opt.num_queries;
+    const uint32_t fold = 1u << R.log_f;
+    uint64_t *combined_x, *ccoef_x;
+    RC_TRY(arena_extra(c, a, 16, &combined_x, 2 * CN * 8)); // components 1, 2 of the merged evaluations
+    RC_TRY(arena_extra(c, a, 17, &ccoef_x, 2 * CN * 8));    // their column coefficients
+    RC_TRY(arena_extra(c, a, 18, &R.ccoefs, 3 * CN * 8));
+    RC_TRY(arena_extra(c, a, 19, &R.clde, 3 * b * CN * 8));
+    RC_TRY(arena_extra(c, a, 20, &R.deep, 3 * N * 8));
+    RC_TRY(arena_extra(c, a, 21, &R.d_open, nq * (W * 8 + 192 + 2 * log_N * 32 + (size_t)n_layers * (fold * 24 + log_N * 32)) + 256));
+    R.layer.resize(n_layers + 1);
+    size_t sz = N;
+    for (unsigned l = 0; l <= n_layers; l++) { RC_TRY(arena_extra(c, a, 22 + l, &R.layer[l], 3 * sz * 8)); sz >>= R.log_f; }
+    for (unsigned q = 0; q < 3; q++) { R.comb[q] = q ? combined_x + (q - 1) * CN : a->combined; R.cco[q] = q ? ccoef_x + (q - 1) * CN : a->ccoef; }
+    return CSTARK_OK;
+}
+
+// options / sizes of a run, its arena and buffers
+int run_setup(cstark_ctx *c, const cstark_options *opt, const AirJob &job, ProofRun &R, ProveArena **a) {
+    RC_TRY(check_options(opt, job.log_ce, &R.log_rem, &R.log_b, &R.log_f));
+    const unsigned log_N = job.log_n + R.log_b;
+    if (log_N > 24) return fail(CSTARK_ERR_UNSUPPORTED, "the LDE domain holds at most 2^24 points (2^21 trace rows at blowup 8)");
+    if (job.sharded && R.log_b != 3) return fail(CSTARK_ERR_UNSUPPORTED, "sharded proofs use blowup factor 8 (one to four of its eight cosets per rank)");
+    R.opt = *opt; R.job = job;
+    R.job.log_b = R.log_b;
+    R.m = opt->field_extension + 1;
+    if (!job.sharded) { R.job.k0 = 0; R.job.nk = 1u << R.log_b; }
+    R.shape = proof_shape((uint32_t)job.air, job.width, job.log_n, job.item, *opt);
+    R.n_layers = R.shape.n_layers;
+    if (opt->num_queries > ((size_t)1 << log_N) / 2) return fail(CSTARK_ERR_INVALID_ARG, "more queries than the domain supports"); // (distinct positions are drawn)
+    // all openings are one launch (GatherBatch); no accepted option set reaches this (folding >= 4, 2^24 points: at most 9 layers)
+    static_assert((MAX_GATHER_JOBS - 4) / 2 <= (int)VMAX_LAYERS, "a proof that fits one opening launch fits the layout's per-layer tables");
+    if (2 * (size_t)R.n_layers + 4 > MAX_GATHER_JOBS) return fail(CSTARK_ERR_UNSUPPORTED, "too many FRI layers for one opening launch");
+    HIP_TRY(hipSetDevice(c->device));
+    RC_TRY(get_arena(c, R.job, R.log_b, R.log_f, R.n_layers, opt->num_queries, a));
+    return run_buffers(c, *a, R);
+}
+
+// ---- host steps of a proof -----------------------------------------------------------------------------------------------------------
+// What the host-channel phases below and the device-channel prover (prove_core_dev) share: every step enqueues on the context's stream
+// and reads its buffers from the run.  What differs between the two -- who absorbs a root and draws -- stays with the callers.
+
+// the end of a stage: the next of the arena's events, in stream order (cstark_prove_stage_ms reads the times between them)
+#define STAGE() HIP_TRY(hipEventRecord(a->ev[R.evi++], c->stream))
+
+// The first step of every run.  Trace, interpolation and extension (three stages), then the row hashes of the whole table straight into
+// the trace tree's leaf level; a sharded run hashes its own cosets instead (phase_commit).
+int commit_trace_leaves(cstark_ctx *c, ProveArena *a, ProofRun &R) {
+    AirJob &job = R.job;
+    a->timed = false;
+    R.evi = 0;
+    STAGE();
+    RC_TRY(job.build(c, a, job));
+    STAGE();
+    RC_TRY(commit_columns(c, a, job, c->stream, R.evi));
+    if (R.sharded()) return CSTARK_OK;
+    return hash_rows_slots(c, R.opt.hash_fn, a->lde, a->tnodes + ((size_t)32 << (job.log_n + R.log_b)), job.width, job.log_n, R.log_b, R.log_s());
+}
+
+// The host coin after the trace commitment: seeded with context || public inputs, reseeded with the trace root.  Call after the wait
+// for the root, which also completes the public-input copy of job.build.
+void open_host_channel(ProofRun &R) {
+    AirJob &job = R.job;
+    if (job.pub_staging) job.pub.assign(job.pub_staging, job.pub_staging + 14);
+    R.coin.hash_fn = R.opt.hash_fn;
+    const std::vector<uint8_t> seed = channel_seed(job, R.opt, R.log_rem);
+    R.coin.init(seed.data(), seed.size());
+    R.coin.reseed(R.trace_root);
+}
+
+// one element of the drawn field: m draws
+host::EX draw_ext(Coin &coin, unsigned m) {
+    host::EX x = host::ex_zero();
+    for (unsigned q = 0; q < m; q++) x.c[q] = coin.draw();
+    return x;
+}
+
+// (alpha, beta) per transition constraint, then per assertion, in the coin's order: 2 m (nc + na) draws; component q of every element
+// goes to coefficient set q
+void draw_coefficient_sets(ProofRun &R) {
+    const size_t nc = R.job.n_constraints, na = R.job.n_assertions, m = R.m;
+    std::vector<uint64_t> dr(2 * m * (nc + na));
+    R.coin.draw_many(dr.size(), dr.data());
+    const uint64_t *t = dr.data(), *b = dr.data() + 2 * m * nc;
+    for (size_t q = 0; q < m; q++) {
+        R.ta[q].resize(nc); R.tb[q].resize(nc); R.ba[q].resize(na); R.bb[q].resize(na);
+        for (size_t i = 0; i < nc; i++) { R.ta[q][i] = t[m * 2 * i + q]; R.tb[q][i] = t[m * (2 * i + 1) + q]; }
+        for (size_t i = 0; i < na; i++) { R.ba[q][i] = b[m * 2 * i + q]; R.bb[q][i] = b[m * (2 * i + 1) + q]; }
+    }
+}
+
+// Merged evaluations [ce][n] per component (R.comb) -> the composition table and its tree: column coefficients per component, one
+// extension of the m ce columns, row hashes, tree.  The committed table is R.clde (rows of ce m-tuples).
+int commit_composition(cstark_ctx *c, ProveArena *a, ProofRun &R) {
+    const unsigned m = R.m, log_n = R.job.log_n, log_ce = R.job.log_ce, log_b = R.log_b;
+    const uint32_t hf = R.opt.hash_fn, b = 1u << log_b, cw = m << log_ce;
+    for (unsigned q = 0; q < m; q++) RC_TRY(cstark_composition_columns(c, R.comb[q], R.cco[q], log_n, log_ce));
+    if (m > 1) HIP_TRY(cs::interleave_set_columns(R.ccoefs, R.cco, m, 1u << log_ce, (size_t)1 << log_n, c->stream));
+    RC_TRY(cstark_lde_columns(c, R.ccoefs, R.clde, cw, log_n, log_b, host::lde_offset(), 0, b));
+    RC_TRY(cstark_hash_rows_fn(c, hf, R.clde, a->cnodes + ((size_t)32 << (log_n + log_b)), cw, log_n, log_b, 0, b));
+    return cstark_merkle_build_fn(c, hf, a->cnodes, log_n + log_b);
+}
+
+// The DEEP composition polynomial has degree < n in every component (quotients of degree n - 2 times the linear degree adjustment): its
+// values on ONE coset determine it.  The callers evaluate the quotient sums on coset 0 only (1/8 of the extended trace read) into `sums`
+// [m][n]; here they are interpolated (the coefficients of P(g y), dcoef [m][n]) and extended to all cosets with offset 1 -- the same
+// values as evaluating the sums at every point -- then put in natural order: FRI layer 0.
+int deep_extend(cstark_ctx *c, ProofRun &R, uint64_t *sums, uint64_t *dcoef) {
+    const unsigned log_n = R.job.log_n, log_b = R.log_b;
+    const size_t n = (size_t)1 << log_n, N = n << log_b;
+    RC_TRY(cstark_interpolate_columns(c, sums, dcoef, R.m, log_n));
+    for (unsigned q = 0; q < R.m; q++) {
+        RC_TRY(cstark_lde_columns(c, dcoef + q * n, R.deep + q * N, 1, log_n, log_b, host::from_u64(1), 0, 1u << log_b));
+        RC_TRY(cstark_interleave_cosets(c, R.deep + q * N, R.layer[0] + q * N, log_n, log_b));
+    }
+    return CSTARK_OK;
+}
+
+// FRI commit phase: per layer the row hashes, the tree, and the fold at the point the coin draws after the layer's root.  `last`: where
+// the last fold lands (the remainder).  The coin is the run's:
+//   d_fri != null  a coin block on the device, [seed 8 words][alpha: 2 words per layer x 32]: k_fri_coin reseeds with the layer's root,
+//                  draws the folding point and copies the root to d_roots + 8 l, so all layers are enqueued at once and nothing waits
+//                  (base field, Blake3);
+//   d_fri == null  the host coin R.coin: one wait per layer for the root (-> R.layer_roots), the point drawn between two launches.
+int fri_commit(cstark_ctx *c, ProveArena *a, ProofRun &R, uint32_t *d_fri, uint32_t *d_roots, uint64_t *last) {
+    const unsigned m = R.m, log_f = R.log_f;
+    const uint32_t hf = R.opt.hash_fn, fold = 1u << log_f;
+    uint64_t offset = host::lde_offset();
+    unsigned lg = R.job.log_n + R.log_b;
+    for (unsigned l = 0; l < R.n_layers; l++) {
+        const size_t rows = (size_t)1 << (lg - log_f);
+        uint64_t *next = l + 1 == R.n_layers ? last : R.layer[l + 1];
+        RC_TRY(cstark_hash_rows_fn(c, hf, R.layer[l], a->lnodes[l] + 32 * rows, fold * m, lg - log_f, 0, 0, 1));
+        RC_TRY(cstark_merkle_build_fn(c, hf, a->lnodes[l], lg - log_f));
+        if (d_fri) {
+            RC_TRY(fri_coin_fold_dev(c, d_fri, a->lnodes[l] + 32, (uint64_t *)(d_fri + 8) + l, d_roots + 8 * l, R.layer[l], next, lg, log_f, offset));
+        } else {
+            HIP_TRY(hipMemcpyAsync(&R.layer_roots[32 * l], a->lnodes[l] + 32, 32, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(cs::stream_wait(c->stream));
+            R.coin.reseed(&R.layer_roots[32 * l]);
+            const host::EX alpha = draw_ext(R.coin, m);
+            if (m == 1) RC_TRY(cstark_fri_fold(c, R.layer[l], next, lg, fold, offset, alpha.c[0]));
+            else RC_TRY(cstark_fri_fold_ext(c, R.layer[l], next, lg, fold, offset, m, alpha.c));
+        }
+        offset = host::pow(offset, fold);
+        lg -= log_f;
+    }
+    return CSTARK_OK;
+}
+
+// The proof bytes (proof_layout.h), straight into the caller's buffer.  `p`: roots, frame, nonce and remainder; the openings are the
+// sections O of the host copy `h` of an opening block, `counts` positions per layer.
+int finish_proof(const ProofShape &S, ProofParts p, const uint8_t *h, const OpenBlock &O, const uint32_t *counts, uint8_t *proof, size_t capacity, size_t *proof_len) {
+    p.trows = h + O.trows; p.tpaths = h + O.tpaths; p.crows = h + O.crows; p.cpaths = h + O.cpaths;
+    p.counts = counts;
+    for (unsigned l = 0; l < S.n_layers; l++) { p.lrows[l] = h + O.lrows[l]; p.lpaths[l] = h + O.lpaths[l]; }
+    if (write_proof(S, p, proof, capacity, proof_len)) return fail(CSTARK_ERR_INVALID_ARG, "proof buffer too small (required size returned in *proof_len)");
+    return CSTARK_OK;
+}
 
 // ---- phase 1: trace, its interpolation and extension, row hashes of the owned cosets ---------------------------------------------
 // d_leaves_local (sharded only): [n][32], the roots of the rank's subtrees -- the nk leaves 8 j + k0 .. 8 j + k0 + nk - 1 of row j are a
@@ -532,19 +697,11 @@ namespace {
 // and the all-gather moves 32 n bytes per rank at every world size.  Otherwise the leaves go straight into the tree.
 int phase_commit(cstark_ctx *c, ProveArena *a, ProofRun &R, uint8_t *d_leaves_local) {
     AirJob &job = R.job;
-    const unsigned log_n = job.log_n, log_b = R.log_b;
-    const size_t n = (size_t)1 << log_n, N = n << log_b, W = job.width;
-    hipStream_t st = c->stream;
-    a->timed = false;
-    R.evi = 0;
-    STAGE();
-    RC_TRY(job.build(c, a, job));
-    STAGE();
-    RC_TRY(commit_columns(c, a, job, st, R.evi));
+    const unsigned log_n = job.log_n;
+    const size_t n = (size_t)1 << log_n, W = job.width;
     const uint32_t hf = R.opt.hash_fn;
-    if (!R.sharded()) {
-        RC_TRY(hash_rows_slots(c, hf, a->lde, a->tnodes + 32 * N, (uint32_t)W, log_n, log_b, R.log_s()));
-    } else {
+    RC_TRY(commit_trace_leaves(c, a, R));
+    if (R.sharded()) {
         const unsigned log_nk = ceil_log2(job.nk);
         if (log_nk == 0) { // one coset: its row digests are the subtree roots
             RC_TRY(cstark_hash_rows_fn(c, hf, a->lde, d_leaves_local, (uint32_t)W, log_n, 0, 0, 1));
@@ -553,7 +710,7 @@ int phase_commit(cstark_ctx *c, ProveArena *a, ProofRun &R, uint8_t *d_leaves_lo
             RC_TRY(arena_extra(c, a, 45, &sub, 2 * ((size_t)job.nk << log_n) * 32));
             RC_TRY(cstark_hash_rows_fn(c, hf, a->lde, sub + 32 * ((size_t)job.nk << log_n), (uint32_t)W, log_n, log_nk, 0, job.nk));
             RC_TRY(cstark_merkle_build_fn(c, hf, sub, log_n + log_nk));
-            HIP_TRY(hipMemcpyAsync(d_leaves_local, sub + 32 * n, n * 32, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_leaves_local, sub + 32 * n, n * 32, hipMemcpyDeviceToDevice, c->stream));
         }
     }
     R.phase = 1;
@@ -561,13 +718,13 @@ int phase_commit(cstark_ctx *c, ProveArena *a, ProofRun &R, uint8_t *d_leaves_lo
 }
 
 // ---- phase 2: trace tree, channel, coefficients, merged constraint evaluations of the owned cosets -----------------------------------
-// d_leaves_all (sharded only): the all-gathered subtree roots [W][n][32], rank-major (W = 8 / nk).  d_out: [nk][n].
+// d_leaves_all (sharded only): the all-gathered subtree roots [W][n][32], rank-major (W = 8 / nk).  d_out: [nk][n], component 0 of the
+// merged evaluations (the further components of an extension proof: R.comb).
 int phase_evaluate(cstark_ctx *c, ProveArena *a, ProofRun &R, const uint8_t *d_leaves_all, uint64_t *d_out) {
     AirJob &job = R.job;
-    const unsigned log_n = job.log_n, log_b = R.log_b, log_N = log_n + log_b;
+    const unsigned m = R.m, log_n = job.log_n, log_b = R.log_b, log_N = log_n + log_b;
     const size_t n = (size_t)1 << log_n;
     hipStream_t st = c->stream;
-    const uint32_t hf = R.opt.hash_fn;
     unsigned log_top = log_N; // leaves of the tree that is built here
     if (R.sharded()) { // node W j + r of the level with W n nodes = rank r's subtree root of row j; the levels from there up
         const unsigned log_w = log_b - ceil_log2(job.nk);
@@ -575,31 +732,23 @@ int phase_evaluate(cstark_ctx *c, ProveArena *a, ProofRun &R, const uint8_t *d_l
         k_interleave_leaves<<<(unsigned)(((2 * n << log_w) + 255) / 256), 256, 0, st>>>((const uint4 *)d_leaves_all, (uint4 *)(a->tnodes + 32 * (n << log_w)), n, log_w);
         HIP_TRY(hipGetLastError());
     }
-    RC_TRY(cstark_merkle_build_fn(c, hf, a->tnodes, log_top));
+    RC_TRY(cstark_merkle_build_fn(c, R.opt.hash_fn, a->tnodes, log_top));
     HIP_TRY(hipMemcpyAsync(R.trace_root, a->tnodes + 32, 32, hipMemcpyDeviceToHost, st));
     STAGE();
-    HIP_TRY(cs::stream_wait(st)); // also completes the public-input copy of job.build
+    HIP_TRY(cs::stream_wait(st));
     static const bool hostprof = getenv("CSTARK_HOSTPROF") != nullptr; // debugging: host time between the root and the evaluation launches
     const auto hp0 = std::chrono::steady_clock::now();
-    if (job.pub_staging) job.pub.assign(job.pub_staging, job.pub_staging + 14);
-
-    Coin &coin = R.coin;
-    coin.hash_fn = hf;
-    {
-        const std::vector<uint8_t> seed = channel_seed(job, R.opt, R.log_rem);
-        coin.init(seed.data(), seed.size());
-    }
-    coin.reseed(R.trace_root);
-    const size_t nc = job.n_constraints, na = job.n_assertions;
-    R.ta.resize(nc); R.tb.resize(nc); R.ba.resize(na); R.bb.resize(na);
-    {   // (alpha, beta) per transition constraint, then per assertion: 2 (nc + na) draws in the coin's order
-        std::vector<uint64_t> dr(2 * (nc + na));
-        coin.draw_many(dr.size(), dr.data());
-        for (size_t i = 0; i < nc; i++) { R.ta[i] = dr[2 * i]; R.tb[i] = dr[2 * i + 1]; }
-        for (size_t i = 0; i < na; i++) { R.ba[i] = dr[2 * nc + 2 * i]; R.bb[i] = dr[2 * nc + 2 * i + 1]; }
-    }
+    open_host_channel(R);
+    draw_coefficient_sets(R);
     const auto hp1 = std::chrono::steady_clock::now();
-    RC_TRY(job.combine(c, a, job, R.ta.data(), R.tb.data(), R.ba.data(), R.bb.data(), d_out));
+    uint64_t *outs[3] = {d_out, R.comb[1], R.comb[2]};
+    if (job.combine_sets) {
+        const uint64_t *pa[3], *pb[3], *qa[3], *qb[3];
+        for (unsigned q = 0; q < m; q++) { pa[q] = R.ta[q].data(); pb[q] = R.tb[q].data(); qa[q] = R.ba[q].data(); qb[q] = R.bb[q].data(); }
+        RC_TRY(job.combine_sets(c, a, job, m, pa, pb, qa, qb, outs));
+    } else {
+        for (unsigned q = 0; q < m; q++) RC_TRY(job.combine(c, a, job, R.ta[q].data(), R.tb[q].data(), R.ba[q].data(), R.bb[q].data(), outs[q]));
+    }
     if (hostprof) {
         const auto hp2 = std::chrono::steady_clock::now();
         fprintf(stderr, "[cstark hostprof] coefficients drawn in %.1f us, evaluation enqueued in %.1f us\n",
@@ -611,99 +760,97 @@ int phase_evaluate(cstark_ctx *c, ProveArena *a, ProofRun &R, const uint8_t *d_l
 }
 
 // ---- phase 3: composition polynomial and its commitment, out-of-domain frame, DEEP composition, FRI, query positions -----------------
-// Needs the merged evaluations on the constraint-evaluation domain, [ce][n], in a->combined and coset 0 of the extended trace at a->lde
-// (the owner of coset 0).
+// Needs the merged evaluations on the constraint-evaluation domain, [ce][n] per component, in R.comb and coset 0 of the extended trace at
+// a->lde (the owner of coset 0).
 int phase_compose(cstark_ctx *c, ProveArena *a, ProofRun &R) {
+    using host::EX;
     AirJob &job = R.job;
-    const cstark_options *opt = &R.opt;
-    const unsigned log_n = job.log_n, log_b = R.log_b, log_f = R.log_f, log_N = log_n + log_b, log_ce = job.log_ce, n_layers = R.n_layers;
-    const size_t n = (size_t)1 << log_n, b = (size_t)1 << log_b, N = n * b, W = job.width, ce = (size_t)1 << log_ce;
-    const uint32_t fold = 1u << log_f;
+    const unsigned m = R.m, log_n = job.log_n, log_b = R.log_b, log_N = log_n + log_b, n_layers = R.n_layers;
+    const size_t n = (size_t)1 << log_n, W = job.width, ce = (size_t)1 << job.log_ce;
     hipStream_t st = c->stream;
-    const uint32_t hf = opt->hash_fn;
+    const uint32_t hf = R.opt.hash_fn;
     Coin &coin = R.coin;
     if (job.k0 != 0) return fail(CSTARK_ERR_INVALID_ARG, "the composition phase runs on the rank that owns coset 0");
-    RC_TRY(cstark_composition_columns(c, a->combined, a->ccoef, log_n, log_ce));
-    RC_TRY(cstark_lde_columns(c, a->ccoef, a->clde, (uint32_t)ce, log_n, log_b, host::lde_offset(), 0, (uint32_t)b));
-    RC_TRY(cstark_hash_rows_fn(c, hf, a->clde, a->cnodes + 32 * N, (uint32_t)ce, log_n, log_b, 0, (uint32_t)b));
-    RC_TRY(cstark_merkle_build_fn(c, hf, a->cnodes, log_N));
+    RC_TRY(commit_composition(c, a, R));
     HIP_TRY(hipMemcpyAsync(R.cons_root, a->cnodes + 32, 32, hipMemcpyDeviceToHost, st));
     STAGE();
     HIP_TRY(cs::stream_wait(st));
     coin.reseed(R.cons_root);
 
-    // ---- out-of-domain frame ----------------------------------------------------------------------------------------------
-    const uint64_t z = coin.draw();
-    const uint64_t zpts[2] = {z, host::mul(z, host::root_of_unity(log_n))};
-    const uint64_t zb = host::pow(z, ce);
+    // ---- out-of-domain frame: T(z) | T(z w), then H_i(z^ce) -----------------------------------------------------------------
+    const EX z = draw_ext(coin, m);
     std::vector<uint64_t> &ood_trace = R.ood_trace, &ood_comp = R.ood_comp;
-    ood_trace.assign(2 * W, 0); ood_comp.assign(ce, 0);
-    RC_TRY(evaluate_ood_frames(c, a->coeffs, (uint32_t)W, a->ccoef, (uint32_t)ce, log_n, zpts, zb, ood_trace.data(), ood_comp.data()));
+    ood_trace.assign(2 * m * W, 0); ood_comp.assign(m * ce, 0);
+    if (m == 1) {
+        const uint64_t zpts[2] = {z.c[0], host::mul(z.c[0], host::root_of_unity(log_n))};
+        RC_TRY(evaluate_ood_frames(c, a->coeffs, (uint32_t)W, R.ccoefs, (uint32_t)ce, log_n, zpts, host::pow(z.c[0], ce), ood_trace.data(), ood_comp.data()));
+    } else {
+        const EX zw = host::ex_scale(z, host::root_of_unity(log_n)), zb = host::ex_pow(z, ce, m);
+        std::vector<uint64_t> raw(m * m * ce);
+        RC_TRY(cstark_evaluate_polys_at_ext(c, a->coeffs, (uint32_t)W, log_n, m, z.c, ood_trace.data()));
+        RC_TRY(cstark_evaluate_polys_at_ext(c, a->coeffs, (uint32_t)W, log_n, m, zw.c, ood_trace.data() + m * W));
+        RC_TRY(cstark_evaluate_polys_at_ext(c, R.ccoefs, (uint32_t)(m * ce), log_n, m, zb.c, raw.data()));
+        EX gen = host::ex_zero();
+        gen.c[1] = host::ONE; // the adjoined root
+        for (size_t i = 0; i < ce; i++) { // H_i = sum_q root^q H_i,q, each component polynomial evaluated at z^ce
+            EX h = host::ex_zero(), gq = host::ex_one();
+            for (unsigned q = 0; q < m; q++) {
+                h = host::ex_add(h, host::ex_mul(gq, host::ex_load(raw.data() + m * (m * i + q), m), m));
+                gq = host::ex_mul(gq, gen, m);
+            }
+            for (unsigned q = 0; q < m; q++) ood_comp[m * i + q] = h.c[q];
+        }
+    }
     uint8_t dg[32];
-    hash_elements(hf, ood_trace.data(), 2 * W, dg); coin.reseed(dg);
-    hash_elements(hf, ood_comp.data(), ce, dg); coin.reseed(dg);
+    hash_elements(hf, ood_trace.data(), ood_trace.size(), dg); coin.reseed(dg);
+    hash_elements(hf, ood_comp.data(), ood_comp.size(), dg); coin.reseed(dg);
     STAGE();
 
     // ---- DEEP composition -------------------------------------------------------------------------------------------------
-    std::vector<uint64_t> d_alpha(W), d_beta(W), d_delta(ce);
-    uint64_t deg_a, deg_b;
-    {   // per register: alpha (point z), beta (point z w), then the draws only extension fields use (conjugate term); one per composition
-        // column; two for the degree adjustment -- drawn in this order
+    std::vector<uint64_t> d_alpha(m * W), d_beta(m * W), d_delta(m * ce);
+    EX deg_a, deg_b;
+    {   // per register: alpha (point z), beta (point z w), then the draws only the engine's conjugate term uses; one per composition
+        // column; two for the degree adjustment -- drawn in this order, m words each
         constexpr size_t PER = CSTARK_CONV_DEEP_DRAWS_PER_REGISTER;
-        std::vector<uint64_t> dr(PER * W + ce + 2);
+        std::vector<uint64_t> dr(m * (PER * W + ce + 2));
         coin.draw_many(dr.size(), dr.data());
-        for (size_t i = 0; i < W; i++) { d_alpha[i] = dr[PER * i]; d_beta[i] = dr[PER * i + 1]; }
-        for (size_t i = 0; i < ce; i++) d_delta[i] = dr[PER * W + i];
-        deg_a = dr[PER * W + ce]; deg_b = dr[PER * W + ce + 1];
+        for (size_t i = 0; i < W; i++)
+            for (unsigned q = 0; q < m; q++) { d_alpha[m * i + q] = dr[m * PER * i + q]; d_beta[m * i + q] = dr[m * (PER * i + 1) + q]; }
+        for (size_t i = 0; i < m * ce; i++) d_delta[i] = dr[m * PER * W + i];
+        deg_a = host::ex_load(&dr[m * (PER * W + ce)], m); deg_b = host::ex_load(&dr[m * (PER * W + ce + 1)], m);
     }
-    // The DEEP composition polynomial has degree < n (quotients of degree n - 2 times the linear degree adjustment): its values on
-    // ONE coset determine it.  Evaluate the quotient sums on coset 0 only (1/8 of the extended trace read), interpolate there (the
-    // coefficients of P(g y)) and extend to all cosets with offset 1 -- the same values as evaluating the sums at every point.
-    {
-        uint64_t *dcoef;
+    uint64_t *sums, *dcoef; // the quotient sums on coset 0 and their coefficients (deep_extend)
+    if (m == 1) {
+        sums = R.deep;
         RC_TRY(arena_extra(c, a, 40, &dcoef, n * 8));
-        RC_TRY(cstark_deep_composition(c, a->lde, a->clde, (uint32_t)W, (uint32_t)ce, z, ood_trace.data(), ood_comp.data(), d_alpha.data(),
-                                       d_beta.data(), d_delta.data(), deg_a, deg_b, a->deep, log_n, log_b, 0, 1));
-        RC_TRY(cstark_interpolate_columns(c, a->deep, dcoef, 1, log_n));
-        RC_TRY(cstark_lde_columns(c, dcoef, a->deep, 1, log_n, log_b, host::from_u64(1), 0, (uint32_t)b));
+        RC_TRY(cstark_deep_composition(c, a->lde, R.clde, (uint32_t)W, (uint32_t)ce, z.c[0], ood_trace.data(), ood_comp.data(), d_alpha.data(),
+                                       d_beta.data(), d_delta.data(), deg_a.c[0], deg_b.c[0], sums, log_n, log_b, 0, 1));
+    } else {
+        RC_TRY(arena_extra(c, a, 40, &sums, 3 * n * 8));
+        RC_TRY(arena_extra(c, a, 41, &dcoef, 3 * n * 8));
+        RC_TRY(deep_composition_ext_cosets(c, a->lde, R.clde, (uint32_t)W, (uint32_t)ce, m, z.c, ood_trace.data(), ood_comp.data(), d_alpha.data(),
+                                           d_beta.data(), d_delta.data(), deg_a.c, deg_b.c, sums, log_n, log_b, 1));
     }
-    RC_TRY(cstark_interleave_cosets(c, a->deep, a->layer[0], log_n, log_b));
+    RC_TRY(deep_extend(c, R, sums, dcoef));
     STAGE();
 
     // ---- FRI commit phase -----------------------------------------------------------------------------------------------------
-    R.layer_roots.assign(32 * (size_t)n_layers, 0);
-    uint64_t offset = host::lde_offset();
-    unsigned lg = log_N;
-    // Blake3 coin: the layers' coin lives on the device (k_fri_coin: reseed with the layer's root, draw the folding point), so the host
-    // enqueues all layers at once and collects the roots with the remainder -- one wait instead of one per layer (8 x ~20 us of GPU
-    // idle time at 2^20 steps); it then replays the reseeds on its own coin.  CSTARK_FRI_DEVICE_COIN=0, and the Sha3 coin: the host
-    // draws every folding point between two launches.
+    // Base field, Blake3 coin: the layers' coin lives on the device (fri_commit), so the host enqueues all layers at once and collects the
+    // roots with the remainder -- one wait instead of one per layer (8 x ~20 us of GPU idle time at 2^20 steps); it then replays the
+    // reseeds on its own coin.  CSTARK_FRI_DEVICE_COIN=0, the Sha3 coin and extension fields: the host draws every folding point.
     static const bool dev_coin_env = [] { const char *e = getenv("CSTARK_FRI_DEVICE_COIN"); return !e || atoi(e) != 0; }();
-    const bool dev_coin = dev_coin_env && hf == 0 && n_layers > 0;
-    uint32_t *d_fri = nullptr; // [seed 8 words][alpha: 2 words per layer][roots: 8 words per layer]
+    const bool dev_coin = dev_coin_env && hf == 0 && m == 1 && n_layers > 0;
+    uint32_t *d_fri = nullptr, *d_roots = nullptr; // [seed 8 words][alpha: 2 words per layer x 32][roots: 8 words per layer]
+    R.layer_roots.assign(32 * (size_t)n_layers, 0);
     if (dev_coin) {
         RC_TRY(arena_extra(c, a, 41, &d_fri, (size_t)(8 + 10 * 32) * 4));
         HIP_TRY(hipMemcpyAsync(d_fri, coin.seed, 32, hipMemcpyHostToDevice, st));
+        d_roots = d_fri + 8 + 2 * 32;
     }
-    for (unsigned l = 0; l < n_layers; l++) {
-        const size_t rows = (size_t)1 << (lg - log_f);
-        RC_TRY(cstark_hash_rows_fn(c, hf, a->layer[l], a->lnodes[l] + 32 * rows, fold, lg - log_f, 0, 0, 1));
-        RC_TRY(cstark_merkle_build_fn(c, hf, a->lnodes[l], lg - log_f));
-        if (dev_coin) {
-            RC_TRY(fri_coin_fold_dev(c, d_fri, a->lnodes[l] + 32, (uint64_t *)(d_fri + 8) + l, d_fri + 8 + 2 * 32 + 8 * l, a->layer[l], a->layer[l + 1], lg, log_f, offset));
-        } else {
-            HIP_TRY(hipMemcpyAsync(&R.layer_roots[32 * l], a->lnodes[l] + 32, 32, hipMemcpyDeviceToHost, st));
-            HIP_TRY(cs::stream_wait(st));
-            coin.reseed(&R.layer_roots[32 * l]);
-            const uint64_t alpha = coin.draw();
-            RC_TRY(cstark_fri_fold(c, a->layer[l], a->layer[l + 1], lg, fold, offset, alpha));
-        }
-        offset = host::pow(offset, fold);
-        lg -= log_f;
-    }
-    R.remainder.assign((size_t)1 << lg, 0);
-    if (dev_coin) HIP_TRY(hipMemcpyAsync(R.layer_roots.data(), d_fri + 8 + 2 * 32, 32 * (size_t)n_layers, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(R.remainder.data(), a->layer[n_layers], R.remainder.size() * 8, hipMemcpyDeviceToHost, st));
+    RC_TRY(fri_commit(c, a, R, d_fri, d_roots, R.layer[n_layers]));
+    R.remainder.assign((size_t)m << (log_N - n_layers * R.log_f), 0);
+    if (dev_coin) HIP_TRY(hipMemcpyAsync(R.layer_roots.data(), d_roots, 32 * (size_t)n_layers, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(R.remainder.data(), R.layer[n_layers], R.remainder.size() * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(cs::stream_wait(st));
     if (dev_coin)
         for (unsigned l = 0; l < n_layers; l++) coin.reseed(&R.layer_roots[32 * l]); // the draws in between left no trace: reseed resets the counter
@@ -720,41 +867,20 @@ int phase_compose(cstark_ctx *c, ProveArena *a, ProofRun &R) {
 // ---- phase 4: openings (gathered on the device, one copy back) and the proof bytes ---------------------------------------------------
 // d_trace_rows (sharded only): the opened rows of the extended trace [nq][W], complete (summed over the ranks).
 int phase_open(cstark_ctx *c, ProveArena *a, ProofRun &R, const uint64_t *d_trace_rows, uint8_t *proof, size_t capacity, size_t *proof_len) {
-    hipStream_t st = c->stream;
     const ProofShape &S = R.shape;
     const OpenBlock O = open_block(S, R.q.counts);
-    RC_TRY(open_stage(c, a, S, {a->clde, a->layer.data(), R.log_s(), R.q.counts, nullptr, d_trace_rows, ceil_log2(R.job.nk)}, a->d_open, O));
+    RC_TRY(open_stage(c, a, S, {R.clde, R.layer.data(), R.log_s(), R.q.counts, nullptr, d_trace_rows, ceil_log2(R.job.nk)}, R.d_open, O));
     STAGE();
-    HIP_TRY(cs::stream_wait(st));
+    HIP_TRY(cs::stream_wait(c->stream));
     a->timed = true;
 
     ProofParts p{};
     p.trace_root = R.trace_root; p.cons_root = R.cons_root; p.layer_roots = R.layer_roots.data(); p.rem_commit = R.rem_commit;
     p.ood_trace = R.ood_trace.data(); p.ood_comp = R.ood_comp.data(); p.nonce = R.q.nonce; p.remainder = R.remainder.data();
-    opened_parts(p, S, a->h_open, O, R.q.counts);
-    return emit_proof(S, p, proof, capacity, proof_len);
-}
-#undef STAGE
-
-// options / sizes of a run, its arena
-int run_setup(cstark_ctx *c, const cstark_options *opt, const AirJob &job, ProofRun &R, ProveArena **a) {
-    RC_TRY(check_options(opt, job.log_ce, &R.log_rem, &R.log_b, &R.log_f));
-    const unsigned log_N = job.log_n + R.log_b;
-    if (log_N > 24) return fail(CSTARK_ERR_UNSUPPORTED, "the LDE domain holds at most 2^24 points (2^21 trace rows at blowup 8)");
-    if (job.sharded && R.log_b != 3) return fail(CSTARK_ERR_UNSUPPORTED, "sharded proofs use blowup factor 8 (one to four of its eight cosets per rank)");
-    R.opt = *opt; R.job = job;
-    R.job.log_b = R.log_b;
-    if (!job.sharded) { R.job.k0 = 0; R.job.nk = 1u << R.log_b; }
-    R.shape = proof_shape((uint32_t)job.air, job.width, job.log_n, job.item, *opt);
-    R.n_layers = R.shape.n_layers;
-    if (opt->num_queries > ((size_t)1 << log_N) / 2) return fail(CSTARK_ERR_INVALID_ARG, "more queries than the domain supports"); // (distinct positions are drawn)
-    // all openings are one launch (GatherBatch); no accepted option set reaches this (folding >= 4, 2^24 points: at most 9 layers)
-    static_assert((MAX_GATHER_JOBS - 4) / 2 <= (int)VMAX_LAYERS, "a proof that fits one opening launch fits the layout's per-layer tables");
-    if (2 * (size_t)R.n_layers + 4 > MAX_GATHER_JOBS) return fail(CSTARK_ERR_UNSUPPORTED, "too many FRI layers for one opening launch");
-    HIP_TRY(hipSetDevice(c->device));
-    return get_arena(c, R.job, R.log_b, R.log_f, R.n_layers, opt->num_queries, a);
+    return finish_proof(S, p, a->h_open, O, R.q.counts, proof, capacity, proof_len);
 }
 
+// every host-channel proof on one GPU
 int prove_core(cstark_ctx *c, const cstark_options *opt, AirJob &job, uint8_t *proof, size_t capacity, size_t *proof_len) {
     ProofRun R;
     ProveArena *a;
@@ -764,7 +890,6 @@ int prove_core(cstark_ctx *c, const cstark_options *opt, AirJob &job, uint8_t *p
     RC_TRY(phase_compose(c, a, R));
     return phase_open(c, a, R, nullptr, proof, capacity, proof_len);
 }
-
 // ---- the same proof with the Fiat-Shamir channel on the device (channel.hip) ---------------------------------------------------------
 // Any of the AIRs, base field, Blake3 coin, no proof of work: every channel step -- seed, reseeds, the 238 coefficient draws, the
 // out-of-domain point, the DEEP coefficients, the FRI layers' folding points (k_fri_coin), the remainder commitment, the query positions
@@ -772,6 +897,7 @@ int prove_core(cstark_ctx *c, const cstark_options *opt, AirJob &job, uint8_t *p
 // ONCE, for the block that holds everything the proof bytes are written from.  Same bytes as prove_core (the tests compare both with the
 // CPU prover); CSTARK_HOST_CHANNEL=1 keeps the host channel for the A/B.  One-at-a-time proving on the host channel leaves the GPU idle
 // for 0.6 ms of a 28.4 ms proof, 0.39 ms of it in the five waits (profiles/r04_timeline_host_channel.txt).
+// The stages between the four channel steps are the host steps above.
 int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8_t *proof, size_t capacity, size_t *proof_len) {
     const auto hp0 = std::chrono::steady_clock::now();
     ProofRun R;
@@ -779,10 +905,9 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
     job0.dev_channel = true;
     RC_TRY(run_setup(c, opt, job0, R, &a));
     AirJob &job = R.job;
-    const unsigned log_n = job.log_n, log_b = R.log_b, log_f = R.log_f, log_N = log_n + log_b, log_ce = job.log_ce, n_layers = R.n_layers;
-    const size_t n = (size_t)1 << log_n, b = (size_t)1 << log_b, N = n * b, W = job.width, ce = (size_t)1 << log_ce, nq = opt->num_queries;
-    const uint32_t fold = 1u << log_f, hf = 0;
-    const size_t rem_len = (size_t)1 << (log_N - n_layers * log_f), n_ood = 2 * W + ce;
+    const unsigned log_n = job.log_n, log_b = R.log_b, log_N = log_n + log_b, n_layers = R.n_layers;
+    const size_t n = (size_t)1 << log_n, W = job.width, ce = (size_t)1 << job.log_ce, nq = opt->num_queries;
+    const size_t rem_len = (size_t)1 << (log_N - n_layers * R.log_f), n_ood = 2 * W + ce;
     hipStream_t st = c->stream;
     // ---- the result block: everything the proof bytes are written from, one copy to the host at the end ------------------------------------
     size_t off = 0;
@@ -812,15 +937,8 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
     const uint64_t *pw, *pwinv;
     RC_TRY(plan_tables(c, log_n, &pw, &pwinv));
 
-#define STAGE() HIP_TRY(hipEventRecord(a->ev[R.evi++], st))
-    a->timed = false;
-    R.evi = 0;
-    STAGE();
-    RC_TRY(job.build(c, a, job));
-    STAGE();
-    RC_TRY(commit_columns(c, a, job, st, R.evi));
-    RC_TRY(hash_rows_slots(c, hf, a->lde, a->tnodes + 32 * N, (uint32_t)W, log_n, log_b, R.log_s()));
-    RC_TRY(cstark_merkle_build_fn(c, hf, a->tnodes, log_N));
+    RC_TRY(commit_trace_leaves(c, a, R));
+    RC_TRY(cstark_merkle_build_fn(c, R.opt.hash_fn, a->tnodes, log_N));
     STAGE();
     {   // the coin: context || public inputs (read from the trace, on the device), the trace root, the coefficient pairs
         ChanStep s{};
@@ -847,18 +965,14 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
         HIP_TRY(channel_step(s, st));
     }
     if (is_tx) {
-        uint64_t *outs[1] = {a->combined};
-        RC_TRY(tx_evaluate_constraints_sets(c, a->lde, nullptr, 1, nullptr, outs, job.item, log_n, 3, 0, 8, true, a->d_pub));
+        RC_TRY(tx_evaluate_constraints_sets(c, a->lde, nullptr, 1, nullptr, R.comb, job.item, log_n, 3, 0, 8, true, a->d_pub));
     } else { // the sub-AIRs: the assertion values are the public inputs (MerkleAir, RescueAir), (0, number) (RangeProofAir) or built in (SchnorrAir)
         job.d_coefs = d_coef_block;
         job.d_avalues = job.air == CSTARK_AIR_RANGE ? a->d_pub + 1 : job.air == CSTARK_AIR_SCHNORR ? nullptr : a->d_pub;
-        RC_TRY(job.combine(c, a, job, nullptr, nullptr, nullptr, nullptr, a->combined));
+        RC_TRY(job.combine(c, a, job, nullptr, nullptr, nullptr, nullptr, R.comb[0]));
     }
     STAGE();
-    RC_TRY(cstark_composition_columns(c, a->combined, a->ccoef, log_n, log_ce));
-    RC_TRY(cstark_lde_columns(c, a->ccoef, a->clde, (uint32_t)ce, log_n, log_b, host::lde_offset(), 0, (uint32_t)b));
-    RC_TRY(cstark_hash_rows_fn(c, hf, a->clde, a->cnodes + 32 * N, (uint32_t)ce, log_n, log_b, 0, (uint32_t)b));
-    RC_TRY(cstark_merkle_build_fn(c, hf, a->cnodes, log_N));
+    RC_TRY(commit_composition(c, a, R));
     STAGE();
     {   // the constraint root -> the out-of-domain point z; z w and z^ce beside it
         ChanStep s{};
@@ -867,7 +981,7 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
         s.draw = CHAN_DRAW_POINT; s.count = 1; s.b = (uint32_t)ce; s.w = host::root_of_unity(log_n); s.out = d_pts; s.out2 = d_scal;
         HIP_TRY(channel_step(s, st));
     }
-    RC_TRY(ood_frames_dev(c, a->coeffs, (uint32_t)W, a->ccoef, (uint32_t)ce, log_n, d_pts, d_ood));
+    RC_TRY(ood_frames_dev(c, a->coeffs, (uint32_t)W, R.ccoefs, (uint32_t)ce, log_n, d_pts, d_ood));
     STAGE();
     {   // the two halves of the frame -> the DEEP coefficients
         ChanStep s{};
@@ -878,49 +992,35 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
         s.count = (uint32_t)(s.per * W + ce + 2); s.out = d_deepc; s.out2 = d_scal;
         HIP_TRY(channel_step(s, st));
     }
-    {   // degree < n: the quotient sums on coset 0, interpolation, extension (prove_core)
+    {   // the quotient sums on coset 0, read from the channel's blocks
         cs::DeepParams p{};
-        p.trace_lde = a->lde; p.comp_lde = a->clde; p.w = pw; p.coef = d_deepc; p.ood = d_ood; p.shifts = a->d_shifts; p.out = a->deep;
+        p.trace_lde = a->lde; p.comp_lde = R.clde; p.w = pw; p.coef = d_deepc; p.ood = d_ood; p.shifts = a->d_shifts; p.out = R.deep;
         p.width = (uint32_t)W; p.nb = (uint32_t)ce; p.log_n = log_n; p.k0 = 0; p.scal = d_scal;
         HIP_TRY(cs::deep_composition(p, 1, st));
-        RC_TRY(cstark_interpolate_columns(c, a->deep, dcoef, 1, log_n));
-        RC_TRY(cstark_lde_columns(c, dcoef, a->deep, 1, log_n, log_b, host::from_u64(1), 0, (uint32_t)b));
     }
-    RC_TRY(cstark_interleave_cosets(c, a->deep, a->layer[0], log_n, log_b));
+    RC_TRY(deep_extend(c, R, R.deep, dcoef));
+    const hipEvent_t deep_done = a->ev[R.evi]; // the end of the DEEP stage: what the tail wait below sleeps on
     STAGE();
-    {
-        uint64_t offset = host::lde_offset();
-        unsigned lg = log_N;
-        for (unsigned l = 0; l < n_layers; l++) {
-            const size_t rows = (size_t)1 << (lg - log_f);
-            RC_TRY(cstark_hash_rows_fn(c, hf, a->layer[l], a->lnodes[l] + 32 * rows, fold, lg - log_f, 0, 0, 1));
-            RC_TRY(cstark_merkle_build_fn(c, hf, a->lnodes[l], lg - log_f));
-            uint64_t *next = l + 1 == n_layers ? (uint64_t *)(d_res + o_remainder) : a->layer[l + 1]; // the remainder lands in the result block
-            RC_TRY(fri_coin_fold_dev(c, d_fri, a->lnodes[l] + 32, (uint64_t *)(d_fri + 8) + l, (uint32_t *)(d_res + o_lroots + 32 * (size_t)l), a->layer[l], next, lg,
-                                     log_f, offset));
-            offset = host::pow(offset, fold);
-            lg -= log_f;
-        }
-    }
+    // the layers' roots and the remainder land in the result block
+    RC_TRY(fri_commit(c, a, R, d_fri, (uint32_t *)(d_res + o_lroots), (uint64_t *)(d_res + o_remainder)));
     STAGE();
     {   // remainder commitment, proof of work (none: nonce 1), query positions and their folded forms
         ChanStep s{};
         s.seed = d_fri;
         s.absorb[0].kind = CHAN_ELEMS; s.absorb[0].ptr = d_res + o_remainder; s.absorb[0].count = (uint32_t)rem_len; s.absorb[0].copy_out = d_res + o_rem;
         s.absorb[1].kind = CHAN_INT; s.absorb[1].value = 1;
-        s.draw = CHAN_DRAW_QUERIES; s.count = (uint32_t)nq; s.log_domain = log_N; s.log_f = log_f; s.n_layers = n_layers; s.slot = 256;
+        s.draw = CHAN_DRAW_QUERIES; s.count = (uint32_t)nq; s.log_domain = log_N; s.log_f = R.log_f; s.n_layers = n_layers; s.slot = 256;
         s.pos = a->d_pos; s.cnt = d_cnt;
         HIP_TRY(channel_step(s, st));
     }
     // at most nq rows per layer; how many: cnt[l + 1], on the device.  The copy takes the whole result block.
-    RC_TRY(open_stage(c, a, S, {a->clde, a->layer.data(), R.log_s(), nullptr, d_cnt + 1, nullptr, 0}, d_res, O));
+    RC_TRY(open_stage(c, a, S, {R.clde, R.layer.data(), R.log_s(), nullptr, d_cnt + 1, nullptr, 0}, d_res, O));
     STAGE();
     static const bool hostprof = getenv("CSTARK_HOSTPROF") != nullptr; // debugging: where the host's time goes
     const auto hp1 = std::chrono::steady_clock::now();
-    HIP_TRY(cs::stream_wait_tail(st, a->ev[8])); // the only wait of the proof: sleep until the DEEP stage is done (event 8), poll through the FRI tail
+    HIP_TRY(cs::stream_wait_tail(st, deep_done)); // the only wait of the proof: sleep until the DEEP stage is done, poll through the FRI tail
     const auto hp2 = std::chrono::steady_clock::now();
     a->timed = true;
-#undef STAGE
     const uint8_t *h = a->h_open;
     const uint32_t *cnt = (const uint32_t *)(h + o_cnt);
     if (cnt[0] != nq) return fail(CSTARK_ERR_HIP, "device channel: the query positions could not be drawn");
@@ -930,8 +1030,7 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
     p.trace_root = h + o_troot; p.cons_root = h + o_croot; p.layer_roots = h + o_lroots; p.rem_commit = h + o_rem;
     p.ood_trace = h + o_ood; p.ood_comp = h + o_ood + ood_trace_bytes(S); p.remainder = h + o_remainder;
     p.nonce = 1; // grinding_factor 0
-    opened_parts(p, S, h, O, cnt + 1);
-    RC_TRY(emit_proof(S, p, proof, capacity, proof_len));
+    RC_TRY(finish_proof(S, p, h, O, cnt + 1, proof, capacity, proof_len));
     if (hostprof) {
         const auto hp3 = std::chrono::steady_clock::now();
         auto us = [](auto d) { return std::chrono::duration<double, std::micro>(d).count(); };
@@ -939,6 +1038,7 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
     }
     return CSTARK_OK;
 }
+#undef STAGE
 // which channel: the device's for what prove_core_dev covers, unless CSTARK_HOST_CHANNEL=1
 bool use_dev_channel(const cstark_options *opt, const AirJob &job) {
     static const bool host_env = [] { const char *e = getenv("CSTARK_HOST_CHANNEL"); return e && atoi(e) != 0; }();
@@ -1137,177 +1237,9 @@ int schnorr_combine(cstark_ctx *c, ProveArena *a, AirJob &job, const uint64_t *t
     return cstark_air_combine(c, CSTARK_AIR_SCHNORR, job.item, a->lde, evals, ta, tb, ba, bb, nullptr, av_lde, 12, out, job.log_n, 3, 0, 8);
 }
 
-
-// ---- any AIR with FieldExtension::Quadratic / Cubic ------------------------------------------------------------------------------
-// Base-field trace; everything the coin draws lives in the degree-m extension (ext.hip).  Coefficients multiply base-field
-// constraint values, so the merged evaluations are the AIR's evaluator applied with m coefficient sets (one per component):
-// TransactionAir merges all sets in one pass over the frame, the sub-AIRs merge their materialised evaluations m times.  Layout
-// differences of the proof: out-of-domain values are m-tuples, composition rows hold 8 m-tuples, FRI rows and the remainder are
-// component-major.
-int prove_ext(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8_t *proof, size_t capacity, size_t *proof_len) {
-    using namespace host;
-    const unsigned m = opt->field_extension + 1;
-    ProofRun R;
-    ProveArena *a;
-    job0.sharded = false;
-    RC_TRY(run_setup(c, opt, job0, R, &a));
-    AirJob &job = R.job;
-    const ProofShape &S = R.shape;
-    const unsigned log_b = R.log_b, log_f = R.log_f, n_layers = R.n_layers;
-    const unsigned log_n = job.log_n, log_N = log_n + log_b, log_ce = job.log_ce, log_s = R.log_s();
-    const size_t n = (size_t)1 << log_n, b = (size_t)1 << log_b, N = n * b, W = job.width, ce = (size_t)1 << log_ce, CW = m * ce; // CW: base columns of the composition table
-    const size_t CN = ce * n; // points of the constraint-evaluation domain
-    const uint32_t fold = 1u << log_f;
-    const size_t nq = opt->num_queries;
-    uint64_t *combined_x, *ccoef_x, *ccoefs, *cldes, *deepx;
-    uint8_t *d_open;
-    RC_TRY(arena_extra(c, a, 16, &combined_x, 2 * CN * 8));  // components 1, 2 of the merged evaluations
-    RC_TRY(arena_extra(c, a, 17, &ccoef_x, 2 * CN * 8));     // their column coefficients
-    RC_TRY(arena_extra(c, a, 18, &ccoefs, 3 * CN * 8));      // interleaved: column m i + k
-    RC_TRY(arena_extra(c, a, 19, &cldes, 3 * b * CN * 8));
-    RC_TRY(arena_extra(c, a, 20, &deepx, 3 * N * 8));
-    RC_TRY(arena_extra(c, a, 21, &d_open, nq * (W * 8 + 192 + 2 * log_N * 32 + (size_t)n_layers * (fold * 24 + log_N * 32)) + 256));
-    std::vector<uint64_t *> layer(n_layers + 1);
-    {
-        size_t sz = N;
-        for (unsigned l = 0; l <= n_layers; l++) { RC_TRY(arena_extra(c, a, 22 + l, &layer[l], 3 * sz * 8)); sz >>= log_f; }
-    }
-    hipStream_t st = c->stream;
-    int evi = 0;
-#define STAGE() HIP_TRY(hipEventRecord(a->ev[evi++], st))
-    a->timed = false;
-    const uint32_t hf = opt->hash_fn;
-
-    STAGE();
-    RC_TRY(job.build(c, a, job));
-    STAGE();
-    RC_TRY(commit_columns(c, a, job, st, evi));
-    RC_TRY(hash_rows_slots(c, hf, a->lde, a->tnodes + 32 * N, (uint32_t)W, log_n, log_b, log_s));
-    RC_TRY(cstark_merkle_build_fn(c, hf, a->tnodes, log_N));
-    uint8_t trace_root[32], cons_root[32];
-    HIP_TRY(hipMemcpyAsync(trace_root, a->tnodes + 32, 32, hipMemcpyDeviceToHost, st));
-    STAGE();
-    HIP_TRY(cs::stream_wait(st));
-    if (job.pub_staging) job.pub.assign(job.pub_staging, job.pub_staging + 14);
-
-    Coin coin;
-    coin.hash_fn = hf;
-    {
-        const std::vector<uint8_t> seed = channel_seed(job, *opt, R.log_rem);
-        coin.init(seed.data(), seed.size());
-    }
-    coin.reseed(trace_root);
-    auto draw_e = [&coin, m]() { EX x = ex_zero(); for (unsigned q = 0; q < m; q++) x.c[q] = coin.draw(); return x; };
-    const size_t nc = job.n_constraints, na = job.n_assertions;
-    std::vector<uint64_t> ta[3], tb[3], ba[3], bb[3];
-    for (unsigned q = 0; q < m; q++) { ta[q].resize(nc); tb[q].resize(nc); ba[q].resize(na); bb[q].resize(na); }
-    for (size_t i = 0; i < nc; i++) {
-        const EX al = draw_e(), be = draw_e();
-        for (unsigned q = 0; q < m; q++) { ta[q][i] = al.c[q]; tb[q][i] = be.c[q]; }
-    }
-    for (size_t i = 0; i < na; i++) {
-        const EX al = draw_e(), be = draw_e();
-        for (unsigned q = 0; q < m; q++) { ba[q][i] = al.c[q]; bb[q][i] = be.c[q]; }
-    }
-    uint64_t *comb[3] = {a->combined, combined_x, combined_x + CN}, *cco[3] = {a->ccoef, ccoef_x, ccoef_x + CN};
-    if (job.combine_sets) {
-        const uint64_t *pa[3], *pb[3], *qa[3], *qb[3];
-        for (unsigned q = 0; q < m; q++) { pa[q] = ta[q].data(); pb[q] = tb[q].data(); qa[q] = ba[q].data(); qb[q] = bb[q].data(); }
-        RC_TRY(job.combine_sets(c, a, job, m, pa, pb, qa, qb, comb));
-    } else {
-        for (unsigned q = 0; q < m; q++) RC_TRY(job.combine(c, a, job, ta[q].data(), tb[q].data(), ba[q].data(), bb[q].data(), comb[q]));
-    }
-    STAGE();
-    for (unsigned q = 0; q < m; q++) RC_TRY(cstark_composition_columns(c, comb[q], cco[q], log_n, log_ce)); // [ce][n] each
-    HIP_TRY(cs::interleave_set_columns(ccoefs, cco, m, (unsigned)ce, n, st)); // column m i + q = component q of composition column i
-    RC_TRY(cstark_lde_columns(c, ccoefs, cldes, (uint32_t)CW, log_n, log_b, lde_offset(), 0, (uint32_t)b));
-    RC_TRY(cstark_hash_rows_fn(c, hf, cldes, a->cnodes + 32 * N, (uint32_t)CW, log_n, log_b, 0, (uint32_t)b));
-    RC_TRY(cstark_merkle_build_fn(c, hf, a->cnodes, log_N));
-    HIP_TRY(hipMemcpyAsync(cons_root, a->cnodes + 32, 32, hipMemcpyDeviceToHost, st));
-    STAGE();
-    HIP_TRY(cs::stream_wait(st));
-    coin.reseed(cons_root);
-
-    const EX z = draw_e(), zw = ex_scale(z, root_of_unity(log_n)), zb = ex_pow(z, ce, m);
-    std::vector<uint64_t> ood_trace(2 * m * W), raw(m * CW), ood_comp(m * ce);
-    RC_TRY(cstark_evaluate_polys_at_ext(c, a->coeffs, (uint32_t)W, log_n, m, z.c, ood_trace.data()));
-    RC_TRY(cstark_evaluate_polys_at_ext(c, a->coeffs, (uint32_t)W, log_n, m, zw.c, ood_trace.data() + m * W));
-    RC_TRY(cstark_evaluate_polys_at_ext(c, ccoefs, (uint32_t)CW, log_n, m, zb.c, raw.data()));
-    {
-        EX gen = ex_zero();
-        gen.c[1] = ONE; // the adjoined root
-        for (size_t i = 0; i < ce; i++) { // H_i = sum_q root^q H_i,q, each component polynomial evaluated at z^ce
-            EX h = ex_zero(), gq = ex_one();
-            for (unsigned q = 0; q < m; q++) {
-                h = ex_add(h, ex_mul(gq, ex_load(raw.data() + m * (m * i + q), m), m));
-                gq = ex_mul(gq, gen, m);
-            }
-            for (unsigned q = 0; q < m; q++) ood_comp[m * i + q] = h.c[q];
-        }
-    }
-    uint8_t dg[32];
-    hash_elements(hf, ood_trace.data(), ood_trace.size(), dg); coin.reseed(dg);
-    hash_elements(hf, ood_comp.data(), ood_comp.size(), dg); coin.reseed(dg);
-    STAGE();
-
-    std::vector<uint64_t> d_alpha(m * W), d_beta(m * W), d_delta(m * ce);
-    for (size_t i = 0; i < W; i++) {
-        const EX al = draw_e(), be = draw_e();
-        for (int k = 2; k < CSTARK_CONV_DEEP_DRAWS_PER_REGISTER; k++) (void)draw_e(); // conjugate-term coefficient of the engine, unused here
-        for (unsigned q = 0; q < m; q++) { d_alpha[m * i + q] = al.c[q]; d_beta[m * i + q] = be.c[q]; }
-    }
-    for (size_t i = 0; i < ce; i++) { const EX dl = draw_e(); for (unsigned q = 0; q < m; q++) d_delta[m * i + q] = dl.c[q]; }
-    const EX dga = draw_e(), dgb = draw_e();
-    {   // degree < n in every component: coset 0 only, then interpolation and extension per component (see prove_core)
-        uint64_t *dev0, *dcoef;
-        RC_TRY(arena_extra(c, a, 40, &dev0, 3 * n * 8));
-        RC_TRY(arena_extra(c, a, 41, &dcoef, 3 * n * 8));
-        RC_TRY(deep_composition_ext_cosets(c, a->lde, cldes, (uint32_t)W, (uint32_t)ce, m, z.c, ood_trace.data(), ood_comp.data(), d_alpha.data(),
-                                           d_beta.data(), d_delta.data(), dga.c, dgb.c, dev0, log_n, log_b, 1));
-        RC_TRY(cstark_interpolate_columns(c, dev0, dcoef, m, log_n));
-        for (unsigned q = 0; q < m; q++) {
-            RC_TRY(cstark_lde_columns(c, dcoef + q * n, deepx + q * N, 1, log_n, log_b, from_u64(1), 0, (uint32_t)b));
-            RC_TRY(cstark_interleave_cosets(c, deepx + q * N, layer[0] + q * N, log_n, log_b));
-        }
-    }
-    STAGE();
-
-    std::vector<uint8_t> layer_roots(32 * (size_t)n_layers);
-    uint64_t offset = lde_offset();
-    unsigned lg = log_N;
-    for (unsigned l = 0; l < n_layers; l++) {
-        const size_t rows = (size_t)1 << (lg - log_f);
-        RC_TRY(cstark_hash_rows_fn(c, hf, layer[l], a->lnodes[l] + 32 * rows, fold * m, lg - log_f, 0, 0, 1)); // [m][f][rows]: component-major rows
-        RC_TRY(cstark_merkle_build_fn(c, hf, a->lnodes[l], lg - log_f));
-        HIP_TRY(hipMemcpyAsync(&layer_roots[32 * l], a->lnodes[l] + 32, 32, hipMemcpyDeviceToHost, st));
-        HIP_TRY(cs::stream_wait(st));
-        coin.reseed(&layer_roots[32 * l]);
-        const EX alpha = draw_e();
-        RC_TRY(cstark_fri_fold_ext(c, layer[l], layer[l + 1], lg, fold, offset, m, alpha.c));
-        offset = pow(offset, fold);
-        lg -= log_f;
-    }
-    std::vector<uint64_t> remainder(m * ((size_t)1 << lg));
-    HIP_TRY(hipMemcpyAsync(remainder.data(), layer[n_layers], remainder.size() * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(cs::stream_wait(st));
-    uint8_t rem_commit[32];
-    hash_elements(hf, remainder.data(), remainder.size(), rem_commit);
-    coin.reseed(rem_commit);
-    STAGE();
-
-    RC_TRY(query_stage(c, a, coin, S, R.q));
-    const OpenBlock O = open_block(S, R.q.counts);
-    RC_TRY(open_stage(c, a, S, {cldes, layer.data(), log_s, R.q.counts, nullptr, nullptr, 0}, d_open, O));
-    STAGE();
-    HIP_TRY(cs::stream_wait(st));
-    a->timed = true;
-#undef STAGE
-
-    ProofParts p{};
-    p.trace_root = trace_root; p.cons_root = cons_root; p.layer_roots = layer_roots.data(); p.rem_commit = rem_commit;
-    p.ood_trace = ood_trace.data(); p.ood_comp = ood_comp.data(); p.nonce = R.q.nonce; p.remainder = remainder.data();
-    opened_parts(p, S, a->h_open, O, R.q.counts);
-    return emit_proof(S, p, proof, capacity, proof_len);
+// one proof on this GPU, on the channel its options allow
+int prove(cstark_ctx *c, const cstark_options *opt, AirJob &job, uint8_t *proof, size_t capacity, size_t *proof_len) {
+    return use_dev_channel(opt, job) ? prove_core_dev(c, opt, job, proof, capacity, proof_len) : prove_core(c, opt, job, proof, capacity, proof_len);
 }
 
 } // namespace
@@ -1356,9 +1288,7 @@ int cstark_tx_prove(cstark_ctx *c, const cstark_options *opt, uint8_t *proof, si
     job.air = CSTARK_AIR_STATE_TRANSITION; job.width = CSTARK_TX_TRACE_WIDTH; job.log_n = 10 + ceil_log2(c->wit.n_tx); job.log_ce = 3;
     job.n_constraints = CSTARK_TX_NUM_CONSTRAINTS; job.n_assertions = 4; job.item = c->wit.depth;
     job.build = tx_build; job.combine = tx_combine; job.combine_sets = tx_combine_sets;
-    if (opt->field_extension == 1 || opt->field_extension == 2) return prove_ext(c, opt, job, proof, capacity, proof_len);
-    if (use_dev_channel(opt, job)) return prove_core_dev(c, opt, job, proof, capacity, proof_len);
-    return prove_core(c, opt, job, proof, capacity, proof_len);
+    return prove(c, opt, job, proof, capacity, proof_len);
 }
 
 int cstark_air_prove(cstark_ctx *c, int air, const cstark_options *opt, uint64_t number, uint8_t *proof, size_t capacity, size_t *proof_len) {
@@ -1398,9 +1328,7 @@ int cstark_air_prove(cstark_ctx *c, int air, const cstark_options *opt, uint64_t
         return fail(CSTARK_ERR_UNSUPPORTED, "no prover for this AIR");
     }
     job.width = s.width; job.n_constraints = s.n_constraints; job.n_assertions = (uint32_t)s.a_reg.size(); job.log_ce = s.log_ce_blowup();
-    if (opt->field_extension == 1 || opt->field_extension == 2) return prove_ext(c, opt, job, proof, capacity, proof_len);
-    if (use_dev_channel(opt, job)) return prove_core_dev(c, opt, job, proof, capacity, proof_len);
-    return prove_core(c, opt, job, proof, capacity, proof_len);
+    return prove(c, opt, job, proof, capacity, proof_len);
 }
 
 // ---- one proof across several GPUs by LDE coset -------------------------------------------------------------------------
@@ -1501,9 +1429,7 @@ int cstark_rescue_prove(cstark_ctx *c, const cstark_options *opt, const uint64_t
     memcpy(job.seed, seed, sizeof job.seed);
     job.build = rescue_build; job.combine = rescue_combine;
     job.width = s.width; job.n_constraints = s.n_constraints; job.n_assertions = (uint32_t)s.a_reg.size(); job.log_ce = s.log_ce_blowup();
-    if (opt->field_extension == 1 || opt->field_extension == 2) return prove_ext(c, opt, job, proof, capacity, proof_len);
-    if (use_dev_channel(opt, job)) return prove_core_dev(c, opt, job, proof, capacity, proof_len);
-    return prove_core(c, opt, job, proof, capacity, proof_len);
+    return prove(c, opt, job, proof, capacity, proof_len);
 }
 
 // RangeProofAir over 2^log_n rows (synthetic long form; log_n = 6 with a one-word value is cstark_air_prove(CSTARK_AIR_RANGE))
@@ -1523,9 +1449,7 @@ int cstark_range_prove_bits(cstark_ctx *c, const cstark_options *opt, const uint
     job.pub = {number};
     job.build = range_build; job.combine = range_combine;
     job.width = s.width; job.n_constraints = s.n_constraints; job.n_assertions = (uint32_t)s.a_reg.size(); job.log_ce = s.log_ce_blowup();
-    if (opt->field_extension == 1 || opt->field_extension == 2) return prove_ext(c, opt, job, proof, capacity, proof_len);
-    if (use_dev_channel(opt, job)) return prove_core_dev(c, opt, job, proof, capacity, proof_len);
-    return prove_core(c, opt, job, proof, capacity, proof_len);
+    return prove(c, opt, job, proof, capacity, proof_len);
 }
 
 // ---- B reference-shaped range proofs in one call (RangeProofExample::prove, src/range/mod.rs:75-100, benches/range.rs:15-37) ---------
@@ -1736,19 +1660,13 @@ int cstark_range_prove_batch(cstark_ctx *c, const cstark_options *opt, const uin
     }
     RC_TRY(parallel_for(B, [&](size_t t) {
         Coin &coin = coins[t];
-        uint64_t nonce = 1;
+        uint64_t nonce;
         if (grind_dev) {
             nonce = h_gfound[t];
         } else {
             hash_elements(hf, h_rem + rem_len * t, rem_len, &rem_commit[32 * t]);
             coin.reseed(&rem_commit[32 * t]);
-            for (;; nonce++) {
-                uint8_t out[32];
-                coin.with_int(coin.seed, nonce, out);
-                uint64_t v = 0;
-                for (int i = 0; i < 8; i++) v |= (uint64_t)out[i] << (8 * i);
-                if (opt->grinding_factor == 0 || (v & ((1ull << opt->grinding_factor) - 1)) == 0) break;
-            }
+            nonce = host_nonce(coin, opt->grinding_factor);
         }
         nonces[t] = nonce;
         coin.reseed_int(nonce);

@@ -122,9 +122,12 @@ def test_proof_bytes_equal_the_cpu_restatement(n_tx, depth, opts):
 
 def test_one_context_across_options_reuses_its_arena_safely():
     """One Backend (one cstark_ctx, one arena) proving under changing options: a base-field proof with 96 queries, a cubic proof
-    with 42 queries, a cubic proof with 96 queries, a base-field proof again.  The arena's per-option buffers must grow with the
-    request (the openings buffer of the extension path was once sized by the first extension proof's query count); every proof
-    equals the CPU restatement's bytes and verifies."""
+    with 42 queries, a cubic proof with 96 queries, a quadratic one, a Sha3 base-field proof (the host channel over the base field,
+    which shares the arena with the device channel's and the extension proofs' buffers), a base-field proof again.  The arena's
+    per-option buffers must grow with the request (the openings buffer of the extension path was once sized by the first extension
+    proof's query count); every proof equals the CPU restatement's bytes and verifies, and every path leaves the stage times of
+    its proof behind: all stages, each finite and not negative."""
+    import math
     from oracle import oracle as O
     from oracle import prover as OP
     from oracle import verifier as V
@@ -134,10 +137,13 @@ def test_one_context_across_options_reuses_its_arena_safely():
     meta = TransactionMetadata(*[getattr(w, f) for f in TransactionMetadata.FIELDS])
     b = Backend()
     b.upload_witness(meta)
-    for opts in ((96, 8, 0, 0, 0, 4, 256), (42, 8, 0, 0, 2, 4, 256), (96, 8, 0, 0, 2, 4, 256), (128, 8, 0, 0, 1, 4, 256), (96, 8, 0, 0, 0, 4, 256)):
+    for opts in ((96, 8, 0, 0, 0, 4, 256), (42, 8, 0, 0, 2, 4, 256), (96, 8, 0, 0, 2, 4, 256), (128, 8, 0, 0, 1, 4, 256), (96, 8, 0, 1, 0, 4, 256),
+                 (96, 8, 0, 0, 0, 4, 256)):
         proof = b.prove(ProofOptions(*opts))
         assert proof == OP.prove(w, opts), opts
         assert V.verify(proof, w.initial_roots[0], w.final_root, options=list(opts))
+        stages = b.prove_stage_ms()
+        assert set(stages) == set(b.PROVE_STAGES) and all(v >= 0 and math.isfinite(v) for v in stages.values()), (opts, stages)
     b.close()
 
 
