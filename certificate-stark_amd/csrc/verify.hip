@@ -691,7 +691,7 @@ __global__ __launch_bounds__(VT) void k_vfy_transcript(const uint8_t *__restrict
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
-constexpr size_t VFY_CHUNK_BYTES = 64ull << 20; // staging budget of one chunk: a large count never sizes more than this
+constexpr size_t VFY_CHUNK_BYTES = CSTARK_VERIFY_CHUNK_BYTES; // staging budget of one chunk (cstark.h)
 enum { VFY_EVENTS = CSTARK_VERIFY_NUM_STAGES };
 
 struct VerifyArena {

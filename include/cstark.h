@@ -460,6 +460,10 @@ int cstark_tx_verify(cstark_ctx *ctx, uint32_t count, const uint8_t *const *proo
  * remainder + reduction + device-to-host copy.  cstark_verify_h2d_bytes: the bytes the same call copied host -> device (proof bytes,
  * descriptors, opening records). */
 #define CSTARK_VERIFY_NUM_STAGES 7
+/* Batches of any size: cstark_tx_verify stages proofs (their bytes, descriptors and opening records) for the device in chunks of at
+ * most this many bytes and verifies one chunk after the other, so a large count never sizes its buffers beyond one chunk (a single
+ * larger proof is a chunk of its own).  Verdicts do not depend on where the chunks divide. */
+#define CSTARK_VERIFY_CHUNK_BYTES 67108864 /* 64 MiB */
 int cstark_verify_stage_ms(cstark_ctx *ctx, float *ms /* [CSTARK_VERIFY_NUM_STAGES] */);
 int cstark_verify_h2d_bytes(cstark_ctx *ctx, uint64_t *bytes);
 

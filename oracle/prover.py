@@ -169,15 +169,41 @@ def _path(nodes, leaves_log, pos):
     return b"".join(nodes[((L + pos) >> lvl) ^ 1].tobytes() for lvl in range(leaves_log))
 
 
+NONCE_SEARCH_LIMIT = 1 << 16
+
+
+def _nonce_and_positions(coin, H, grinding, nq, N, choose_nonce=None):
+    """The proof-of-work nonce and the query positions it yields.  With grinding > 0 the nonce is the smallest one whose hash has
+    `grinding` low zero bits.  With grinding 0 the verifier accepts any nonce, so a prover may search the field: choose_nonce(positions,
+    draws) -- positions: the nq positions a nonce yields; draws: every integer the coin produced for them, skipped repeats included --
+    returns True for the nonce to keep (None: nonce 1, as before).  The search is bounded; an exhausted one is an error."""
+    if choose_nonce is not None:
+        assert grinding == 0, "the nonce is free only without proof of work"
+        seed = coin.seed
+        for nonce in range(1, NONCE_SEARCH_LIMIT + 1):
+            coin.seed = seed
+            coin.reseed_int(nonce)
+            draws = []
+            positions = coin.draw_integers(nq, N, draws)
+            if choose_nonce(positions, draws):
+                return nonce, positions
+        raise RuntimeError("no nonce below %d yields the wanted query positions" % NONCE_SEARCH_LIMIT)
+    nonce = 1
+    while grinding and struct.unpack("<Q", H(coin.seed + struct.pack("<Q", nonce))[:8])[0] & ((1 << grinding) - 1):
+        nonce += 1
+    coin.reseed_int(nonce)
+    return nonce, coin.draw_integers(nq, N)
+
+
 class ShardedProver:
     """The base-field prover as the phases of the product's sharded entry points (cstark_tx_shard_*, include/cstark.h): one proof
     across `world` ranks by LDE coset.  Rank r owns cosets [k0, k0 + nk); prove() below is the one-rank case (nk = blowup: any supported
     blowup factor; several ranks: blowup 8).  A phase's output that other ranks need is returned as a numpy array; the caller exchanges
     it (all-gather / broadcast / sum)."""
 
-    def __init__(self, w, options, k0=0, nk=None, job=None):
+    def __init__(self, w, options, k0=0, nk=None, job=None, choose_nonce=None):
         nq, blowup, grinding, hash_fn, ext, folding, max_rem = options
-        self.job = job if job is not None else TxJob(w)
+        self.job, self.choose_nonce = job if job is not None else TxJob(w), choose_nonce
         check_options(options, self.job)
         assert ext == 0
         self.b, self.log_b, self.log_f = blowup, blowup.bit_length() - 1, folding.bit_length() - 1
@@ -299,12 +325,7 @@ class ShardedProver:
         self.remainder = layer
         self.rem_commit = H(V.elem_bytes(layer))
         coin.reseed(self.rem_commit)
-        nonce = 1
-        while grinding and struct.unpack("<Q", H(coin.seed + struct.pack("<Q", nonce))[:8])[0] & ((1 << grinding) - 1):
-            nonce += 1
-        self.nonce = nonce
-        coin.reseed_int(nonce)
-        self.positions = coin.draw_integers(nq, N)
+        self.nonce, self.positions = _nonce_and_positions(coin, H, grinding, nq, N, self.choose_nonce)
         return np.array(self.positions, np.uint32)
 
     def open_rows(self, positions):
@@ -354,19 +375,20 @@ class ShardedProver:
         return b"".join(out)
 
 
-def _prove_job(job, options):
+def _prove_job(job, options, choose_nonce=None):
     if options[4] in (1, 2):
-        return prove_ext(job, options)
-    p = ShardedProver(None, options, job=job)
+        return prove_ext(job, options, choose_nonce)
+    p = ShardedProver(None, options, job=job, choose_nonce=choose_nonce)
     roots = p.commit()
     combined = p.evaluate(roots)
     positions = p.compose(combined)
     return p.finish(p.open_rows(positions))
 
 
-def prove(w, options=(42, 8, 0, 0, 0, 4, 256)):
-    """TransactionExample::prove (src/lib.rs:116-141)"""
-    return _prove_job(TxJob(w), options)
+def prove(w, options=(42, 8, 0, 0, 0, 4, 256), choose_nonce=None, job=None):
+    """TransactionExample::prove (src/lib.rs:116-141).  choose_nonce: see _nonce_and_positions; job: a TxJob of the caller's (tests that
+    need a prover which deviates from the protocol subclass it)."""
+    return _prove_job(job if job is not None else TxJob(w), options, choose_nonce)
 
 
 def prove_air(air, witness, options=(42, 8, 0, 0, 0, 4, 256), log_n=6):
@@ -391,7 +413,7 @@ def prove_air(air, witness, options=(42, 8, 0, 0, 0, 4, 256), log_n=6):
     raise ValueError("no prover for this AIR")
 
 
-def prove_ext(job, options):
+def prove_ext(job, options, choose_nonce=None):
     """FieldExtension::Quadratic / Cubic: base-field trace, everything drawn from the coin in the degree-m extension (oracle/ext.c).
     Layout differences: out-of-domain values are m-tuples; composition rows hold ce m-tuples; FRI rows and the remainder are
     component-major (component 0 of the `folding` points, then component 1, ...)."""
@@ -478,11 +500,7 @@ def prove_ext(job, options):
     remainder = layer
     rem_commit = H(V.elem_bytes(remainder))
     coin.reseed(rem_commit)
-    nonce = 1
-    while grinding and struct.unpack("<Q", H(coin.seed + struct.pack("<Q", nonce))[:8])[0] & ((1 << grinding) - 1):
-        nonce += 1
-    coin.reseed_int(nonce)
-    positions = coin.draw_integers(nq, N)
+    nonce, positions = _nonce_and_positions(coin, H, grinding, nq, N, choose_nonce)
 
     def row(tab, pos):
         return np.ascontiguousarray(tab[pos & (b - 1), :, pos >> log_b]).tobytes()

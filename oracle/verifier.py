@@ -173,10 +173,13 @@ class Coin:
         """an element of the degree-m extension: m base draws"""
         return tuple(self.draw() for _ in range(m))
 
-    def draw_integers(self, count, domain):
+    def draw_integers(self, count, domain, draws=None):
+        """draws: a list that receives every integer produced, the skipped repeats included"""
         out = []
         while len(out) < count:
             v = self._next() & (domain - 1)
+            if draws is not None:
+                draws.append(v)
             if not CONV["query_dedup"] or v not in out:
                 out.append(v)
         return out
@@ -558,16 +561,19 @@ def _schnorr_ood_combined_ext(self, d, log_n, z, ta, tb, ba, bb, m):
 _SchnorrAir.ood_combined_ext = _schnorr_ood_combined_ext
 
 
-def verify(proof, initial_root, final_root, options=None):
+def verify(proof, initial_root, final_root, options=None, probe=None):
     """TransactionAir.  Raises VerifierError unless `proof` shows that a valid 94-register trace links initial_root to final_root.
     initial_root / final_root: 7 field elements each, memory form (as TransactionMetadata holds them).
-    options: the 7 ProofOptions values the verifier expects (None = accept what the proof states)."""
+    options: the 7 ProofOptions values the verifier expects (None = accept what the proof states).
+    probe: a dict that receives the out-of-domain point "z" and both sides of the out-of-domain equation, "ood_lhs" (the constraints
+    on the frame) and "ood_rhs" (sum_i z^i H_i), before they are compared (canonical integers, or m-tuples of them), and the query
+    "positions" once the proof of work has passed, with "draws": every integer the coin produced for them, skipped repeats included."""
     d = parse(proof)
     if d["air"] != 0:
         raise VerifierError("not a TransactionAir proof")
     if d["options"][4] in (1, 2):
-        return _verify_ext(d, _TxAir(d, initial_root, final_root), options)
-    return _verify(d, _TxAir(d, initial_root, final_root), options)
+        return _verify_ext(d, _TxAir(d, initial_root, final_root), options, probe)
+    return _verify(d, _TxAir(d, initial_root, final_root), options, probe)
 
 
 def verify_merkle(proof, initial_root, final_root, options=None):
@@ -610,7 +616,7 @@ def verify_schnorr(proof, witness, options=None):
     return _verify(d, _SchnorrAir(d, witness), options)
 
 
-def _verify(d, air, options):
+def _verify(d, air, options, probe=None):
     nq, blowup, grinding, hash_fn, ext, folding, max_rem = d["options"]
     if options is not None and list(options) != d["options"]:
         raise VerifierError("proof options differ from the expected ones")
@@ -647,6 +653,8 @@ def _verify(d, air, options):
     cur, nxt = np.ascontiguousarray(d["ood_cur"]), np.ascontiguousarray(d["ood_next"])
     hz = [from_mont(v) for v in d["ood_comp"]]
     rhs = sum(h * pow(z, i, P) for i, h in enumerate(hz)) % P
+    if probe is not None:
+        probe.update(z=z, ood_lhs=lhs, ood_rhs=rhs)
     if lhs != rhs:
         raise VerifierError("out-of-domain constraint evaluations are inconsistent")
     coin.reseed(H(elem_bytes(cur) + elem_bytes(nxt)))
@@ -668,7 +676,10 @@ def _verify(d, air, options):
         if v & ((1 << grinding) - 1):
             raise VerifierError("proof of work not satisfied")
     coin.reseed_int(d["nonce"])
-    positions = coin.draw_integers(nq, N)
+    draws = []
+    positions = coin.draw_integers(nq, N, draws)
+    if probe is not None:
+        probe.update(positions=list(positions), draws=draws)
 
     # 3. trace / composition openings
     for q, pos in enumerate(positions):
@@ -778,7 +789,7 @@ def _tx_constraints_over_e(cur, nxt, per, m):
     return out
 
 
-def _verify_ext(d, air, options):
+def _verify_ext(d, air, options, probe=None):
     """FieldExtension::Quadratic / Cubic proofs of any of the AIRs (layout: oracle/prover.py prove_ext)."""
     nq, blowup, grinding, hash_fn, ext, folding, max_rem = d["options"]
     m = ext + 1
@@ -818,6 +829,8 @@ def _verify_ext(d, air, options):
     for h in hz:
         rhs = e_add(rhs, e_mul(h, zi))
         zi = e_mul(zi, z)
+    if probe is not None:
+        probe.update(z=z, ood_lhs=lhs, ood_rhs=rhs)
     if lhs != rhs:
         raise VerifierError("out-of-domain constraint evaluations are inconsistent")
     coin.reseed(H(elem_bytes(d["ood_cur"]) + elem_bytes(d["ood_next"])))
@@ -839,7 +852,10 @@ def _verify_ext(d, air, options):
         if v & ((1 << grinding) - 1):
             raise VerifierError("proof of work not satisfied")
     coin.reseed_int(d["nonce"])
-    positions = coin.draw_integers(nq, N)
+    draws = []
+    positions = coin.draw_integers(nq, N, draws)
+    if probe is not None:
+        probe.update(positions=list(positions), draws=draws)
     for q, pos in enumerate(positions):
         if merkle_root_from_path(H(elem_bytes(d["trace_rows"][q])), pos, d["trace_paths"][q], hash_fn) != d["trace_root"]:
             raise VerifierError("trace opening %d does not match the trace commitment" % q)

@@ -7,40 +7,12 @@ import pytest
 from test_gpu_verify import backend, names, oracle_verdict  # noqa: F401  (module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
-P = (1 << 62) + (1 << 56) + (1 << 55) + 1
-
-
-def _add_one(a, idx=None):
-    """a + 1 (memory form) at every element, or at idx only"""
-    from oracle import oracle as O
-    one = np.uint64(int(O.to_mont(np.array([1], np.uint64))[0]))
-    b = np.array(a, np.uint64, copy=True)
-    flat = b.reshape(-1)
-    sel = slice(None) if idx is None else idx
-    v = flat[sel].astype(object) + int(one)
-    flat[sel] = np.array([x - P if x >= P else x for x in np.atleast_1d(v)], np.uint64).reshape(np.shape(flat[sel]))
-    return b
 
 
 def _cheat(monkeypatch, w, options, call, idx=None):
     """CPU proof whose `call`-th fold output (0 = layer 1; n_layers - 1 = the remainder) is perturbed before it is committed"""
-    from oracle import oracle as O
-    from oracle import prover as OP
-    name = "fri_fold_ext" if options[4] else "fri_fold"
-    real = getattr(O, name)
-    count = [0]
-
-    def fold(*a, **k):
-        out = real(*a, **k)
-        if count[0] == call:
-            out = _add_one(out, idx)
-        count[0] += 1
-        return out
-    monkeypatch.setattr(O, name, fold)
-    try:
-        return OP.prove(w, options)
-    finally:
-        monkeypatch.setattr(O, name, real)
+    from cheating_prover import perturbed_fold
+    return perturbed_fold(w, options, call, idx)
 
 
 def test_fri_and_remainder_checks_reject(backend, oracle, monkeypatch):
