@@ -1,5 +1,6 @@
 // The Fiat-Shamir coin on the host, shared by the prover (prove.hip) and the verifier (verify.hip) so that both replay the same
-// transcript from the same code.  Protocol: see the header of prove.hip.
+// transcript from the same code.  The coin's rules: the header of prove.hip; the order of the transcript, as steps over this coin:
+// transcript.h.
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>

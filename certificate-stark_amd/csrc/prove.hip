@@ -6,9 +6,8 @@
 // Protocol [UPSTREAM-RECALL winterfell v0.3, parity unpinned -- the engine is absent from the reference tree]:
 //   coin      seed = H(context || public inputs); reseed(d) = H(seed || d); reseed_int(v) = H(seed || v_le64);
 //             draw: counter += 1, H(seed || counter_le64), first 8 bytes LE as integer, rejected unless < p
-//   order     trace root -> 115+4 coefficient pairs -> constraint root -> z -> H(T(z) || T(z w)), H(H_i(z^b)) ->
-//             DEEP coefficients (alpha, beta, gamma per register; one per composition column; two for the degree
-//             adjustment) -> per FRI layer: root, alpha -> H(remainder) -> proof-of-work nonce -> query positions
+//   order     what enters the coin and what is drawn after it, step by step: transcript.h (the host channel calls those steps;
+//             channel.hip states the same order for the device-side channel)
 //   FRI       folding factor f = 4, 8 or 16, layers while the domain exceeds fri_max_remainder; layer rows are the f evaluations
 //             { e[i + t N/f] } that fold into position i
 //   domains   blowup factor b = 2, 4, 8 or 16, at least the AIR's constraint-evaluation blowup ce (8 / 4 / 8 / 2).  b > ce: the trace
@@ -38,6 +37,7 @@
 #include "hostfield.h"
 #include "coin.h"
 #include "proof_layout.h"
+#include "transcript.h"
 
 namespace cs {
 
@@ -77,7 +77,6 @@ void prove_arena_free(ProveArena *a) {
     delete a;
 }
 int grind_nonce(cstark_ctx *c, ProveArena *a, const Coin &coin, unsigned bits, uint64_t *nonce_out);
-uint64_t host_nonce(const Coin &coin, unsigned bits);
 
 namespace {
 
@@ -315,21 +314,9 @@ int check_options(const cstark_options *opt, unsigned log_ce, unsigned *log_rem_
     return CSTARK_OK;
 }
 
-// The channel seed (the verifier replays it): trace width, log2 n, p, the seven option bytes -- these 17 bytes are also the prefix the
-// device-side channel starts from (SEED_PREFIX) -- then the public inputs in canonical form (PublicInputs::write_into, src/air.rs:57-62
-// and the sub-AIRs' equivalents) and further public material verbatim (Schnorr: the s halves of the signatures).
-constexpr size_t SEED_PREFIX = 17;
-std::vector<uint8_t> channel_seed(uint32_t width, unsigned log_n, const cstark_options &opt, unsigned log_b, unsigned log_rem, const uint64_t *pub = nullptr,
-                                  size_t n_pub = 0, const uint8_t *pub_bytes = nullptr, size_t n_bytes = 0) {
-    std::vector<uint8_t> s(SEED_PREFIX + 8 * n_pub + n_bytes);
-    const uint8_t head[2] = {(uint8_t)width, (uint8_t)log_n};
-    const uint8_t options[7] = {(uint8_t)opt.num_queries, (uint8_t)log_b, (uint8_t)opt.grinding_factor, (uint8_t)opt.hash_fn,
-                                (uint8_t)opt.field_extension, (uint8_t)opt.fri_folding_factor, (uint8_t)log_rem};
-    memcpy(&s[0], head, 2); memcpy(&s[2], &host::P, 8); memcpy(&s[10], options, 7);
-    for (size_t i = 0; i < n_pub; i++) { const uint64_t v = host::to_u64(pub[i]); memcpy(&s[SEED_PREFIX + 8 * i], &v, 8); }
-    if (n_bytes) memcpy(&s[SEED_PREFIX + 8 * n_pub], pub_bytes, n_bytes);
-    return s;
-}
+// the channel seed (transcript.h), and a job's
+using transcript::channel_seed;
+using transcript::SEED_PREFIX;
 std::vector<uint8_t> channel_seed(const AirJob &job, const cstark_options &opt, unsigned log_rem) {
     return channel_seed(job.width, job.log_n, opt, job.log_b, log_rem, job.pub.data(), job.pub.size(), job.pub_bytes.data(), job.pub_bytes.size());
 }
@@ -343,16 +330,8 @@ struct Queries {
 // `coin`: after the reseed with the remainder commitment
 int query_stage(cstark_ctx *c, ProveArena *a, Coin &coin, const ProofShape &S, Queries &Q) {
     RC_TRY(grind_nonce(c, a, coin, S.opt[2], &Q.nonce));
-    coin.reseed_int(Q.nonce);
-    std::vector<uint32_t> cur;
-    coin.draw_integers(S.nq, (size_t)1 << S.log_N, cur);
     Q.hpos.assign(256 * (S.n_layers + 1), 0);
-    memcpy(Q.hpos.data(), cur.data(), S.nq * 4);
-    for (unsigned l = 0; l < S.n_layers; l++) {
-        cur = fold_positions(cur, 1u << layer_log_rows(S, l));
-        Q.counts[l] = (uint32_t)cur.size();
-        memcpy(Q.hpos.data() + 256 * (l + 1), cur.data(), cur.size() * 4);
-    }
+    transcript::draw_queries(coin, S, Q.nonce, Q.hpos.data(), Q.hpos.data() + 256, 256, Q.counts);
     HIP_TRY(hipMemcpyAsync(a->d_pos, Q.hpos.data(), Q.hpos.size() * 4, hipMemcpyHostToDevice, c->stream));
     return CSTARK_OK;
 }
@@ -456,24 +435,14 @@ int commit_columns(cstark_ctx *c, ProveArena *a, AirJob &job, hipStream_t st, in
 
 } // namespace
 
-// the sequential search on the host (also what the batched range prover runs per proof below 12 bits)
-uint64_t host_nonce(const Coin &coin, unsigned bits) {
-    for (uint64_t nonce = 1;; nonce++) {
-        uint8_t out[32];
-        coin.with_int(coin.seed, nonce, out);
-        uint64_t v = 0;
-        for (int i = 0; i < 8; i++) v |= (uint64_t)out[i] << (8 * i);
-        if (bits == 0 || (v & ((1ull << bits) - 1)) == 0) return nonce;
-    }
-}
 // Proof of work: the smallest nonce >= 1 whose digest with the seed has `bits` low zero bits (0 bits: nonce 1).  A search of 2^bits
-// hashes in sequence on the host costs 10 ms at 16 bits (43 ms with the Sha3 coin); from 12 bits on the GPU searches 2^22 nonces per launch --
+// hashes in sequence on the host (transcript::host_nonce) costs 10 ms at 16 bits (43 ms with the Sha3 coin); from 12 bits on the GPU searches 2^22 nonces per launch --
 // chunks in increasing order and an atomic minimum inside a chunk, so the nonce is the one the sequential search finds.
 // CSTARK_GRIND_DEVICE=0: always on the host.
 int grind_nonce(cstark_ctx *c, ProveArena *a, const Coin &coin, unsigned bits, uint64_t *nonce_out) {
     static const bool dev_env = [] { const char *e = getenv("CSTARK_GRIND_DEVICE"); return !e || atoi(e) != 0; }();
     if (bits == 0 || !dev_env || bits < 12) {
-        *nonce_out = host_nonce(coin, bits);
+        *nonce_out = transcript::host_nonce(coin, bits);
         return CSTARK_OK;
     }
     unsigned long long *d_found; // [found | seed (Sha3 coin: read from device memory)]
@@ -590,36 +559,21 @@ int commit_trace_leaves(cstark_ctx *c, ProveArena *a, ProofRun &R) {
     return hash_rows_slots(c, R.opt.hash_fn, a->lde, a->tnodes + ((size_t)32 << (job.log_n + R.log_b)), job.width, job.log_n, R.log_b, R.log_s());
 }
 
-// The host coin after the trace commitment: seeded with context || public inputs, reseeded with the trace root.  Call after the wait
-// for the root, which also completes the public-input copy of job.build.
+// The host coin after the trace commitment, and the coefficient sets drawn from it.  Call after the wait for the root, which also
+// completes the public-input copy of job.build.
 void open_host_channel(ProofRun &R) {
     AirJob &job = R.job;
+    const size_t nc = job.n_constraints, na = job.n_assertions;
     if (job.pub_staging) job.pub.assign(job.pub_staging, job.pub_staging + 14);
-    R.coin.hash_fn = R.opt.hash_fn;
     const std::vector<uint8_t> seed = channel_seed(job, R.opt, R.log_rem);
-    R.coin.init(seed.data(), seed.size());
-    R.coin.reseed(R.trace_root);
-}
-
-// one element of the drawn field: m draws
-host::EX draw_ext(Coin &coin, unsigned m) {
-    host::EX x = host::ex_zero();
-    for (unsigned q = 0; q < m; q++) x.c[q] = coin.draw();
-    return x;
-}
-
-// (alpha, beta) per transition constraint, then per assertion, in the coin's order: 2 m (nc + na) draws; component q of every element
-// goes to coefficient set q
-void draw_coefficient_sets(ProofRun &R) {
-    const size_t nc = R.job.n_constraints, na = R.job.n_assertions, m = R.m;
-    std::vector<uint64_t> dr(2 * m * (nc + na));
-    R.coin.draw_many(dr.size(), dr.data());
-    const uint64_t *t = dr.data(), *b = dr.data() + 2 * m * nc;
-    for (size_t q = 0; q < m; q++) {
+    transcript::open(R.coin, R.opt.hash_fn, seed.data(), seed.size(), R.trace_root);
+    transcript::CoefficientSets cs{};
+    for (unsigned q = 0; q < R.m; q++) {
         R.ta[q].resize(nc); R.tb[q].resize(nc); R.ba[q].resize(na); R.bb[q].resize(na);
-        for (size_t i = 0; i < nc; i++) { R.ta[q][i] = t[m * 2 * i + q]; R.tb[q][i] = t[m * (2 * i + 1) + q]; }
-        for (size_t i = 0; i < na; i++) { R.ba[q][i] = b[m * 2 * i + q]; R.bb[q][i] = b[m * (2 * i + 1) + q]; }
+        cs.ta[q] = R.ta[q].data(); cs.tb[q] = R.tb[q].data(); cs.ba[q] = R.ba[q].data(); cs.bb[q] = R.bb[q].data();
     }
+    std::vector<uint64_t> dr(R.m * transcript::coefficient_draws(nc, na));
+    transcript::draw_coefficients(R.coin, R.m, nc, na, dr.data(), cs);
 }
 
 // Merged evaluations [ce][n] per component (R.comb) -> the composition table and its tree: column coefficients per component, one
@@ -670,8 +624,8 @@ int fri_commit(cstark_ctx *c, ProveArena *a, ProofRun &R, uint32_t *d_fri, uint3
         } else {
             HIP_TRY(hipMemcpyAsync(&R.layer_roots[32 * l], a->lnodes[l] + 32, 32, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(cs::stream_wait(c->stream));
-            R.coin.reseed(&R.layer_roots[32 * l]);
-            const host::EX alpha = draw_ext(R.coin, m);
+            host::EX alpha = host::ex_zero();
+            transcript::fri_layer(R.coin, &R.layer_roots[32 * l], m, alpha.c);
             if (m == 1) RC_TRY(cstark_fri_fold(c, R.layer[l], next, lg, fold, offset, alpha.c[0]));
             else RC_TRY(cstark_fri_fold_ext(c, R.layer[l], next, lg, fold, offset, m, alpha.c));
         }
@@ -739,7 +693,6 @@ int phase_evaluate(cstark_ctx *c, ProveArena *a, ProofRun &R, const uint8_t *d_l
     static const bool hostprof = getenv("CSTARK_HOSTPROF") != nullptr; // debugging: host time between the root and the evaluation launches
     const auto hp0 = std::chrono::steady_clock::now();
     open_host_channel(R);
-    draw_coefficient_sets(R);
     const auto hp1 = std::chrono::steady_clock::now();
     uint64_t *outs[3] = {d_out, R.comb[1], R.comb[2]};
     if (job.combine_sets) {
@@ -775,10 +728,10 @@ int phase_compose(cstark_ctx *c, ProveArena *a, ProofRun &R) {
     HIP_TRY(hipMemcpyAsync(R.cons_root, a->cnodes + 32, 32, hipMemcpyDeviceToHost, st));
     STAGE();
     HIP_TRY(cs::stream_wait(st));
-    coin.reseed(R.cons_root);
 
     // ---- out-of-domain frame: T(z) | T(z w), then H_i(z^ce) -----------------------------------------------------------------
-    const EX z = draw_ext(coin, m);
+    EX z = host::ex_zero();
+    transcript::draw_ood_point(coin, R.cons_root, m, z.c);
     std::vector<uint64_t> &ood_trace = R.ood_trace, &ood_comp = R.ood_comp;
     ood_trace.assign(2 * m * W, 0); ood_comp.assign(m * ce, 0);
     if (m == 1) {
@@ -801,24 +754,13 @@ int phase_compose(cstark_ctx *c, ProveArena *a, ProofRun &R) {
             for (unsigned q = 0; q < m; q++) ood_comp[m * i + q] = h.c[q];
         }
     }
-    uint8_t dg[32];
-    hash_elements(hf, ood_trace.data(), ood_trace.size(), dg); coin.reseed(dg);
-    hash_elements(hf, ood_comp.data(), ood_comp.size(), dg); coin.reseed(dg);
+    transcript::absorb_frame(coin, m, W, ce, ood_trace.data(), ood_comp.data());
     STAGE();
 
     // ---- DEEP composition -------------------------------------------------------------------------------------------------
-    std::vector<uint64_t> d_alpha(m * W), d_beta(m * W), d_delta(m * ce);
-    EX deg_a, deg_b;
-    {   // per register: alpha (point z), beta (point z w), then the draws only the engine's conjugate term uses; one per composition
-        // column; two for the degree adjustment -- drawn in this order, m words each
-        constexpr size_t PER = CSTARK_CONV_DEEP_DRAWS_PER_REGISTER;
-        std::vector<uint64_t> dr(m * (PER * W + ce + 2));
-        coin.draw_many(dr.size(), dr.data());
-        for (size_t i = 0; i < W; i++)
-            for (unsigned q = 0; q < m; q++) { d_alpha[m * i + q] = dr[m * PER * i + q]; d_beta[m * i + q] = dr[m * (PER * i + 1) + q]; }
-        for (size_t i = 0; i < m * ce; i++) d_delta[i] = dr[m * PER * W + i];
-        deg_a = host::ex_load(&dr[m * (PER * W + ce)], m); deg_b = host::ex_load(&dr[m * (PER * W + ce + 1)], m);
-    }
+    std::vector<uint64_t> d_alpha(m * W), d_beta(m * W), d_delta(m * ce), dr(m * transcript::deep_draws(W, ce));
+    EX deg_a = host::ex_zero(), deg_b = host::ex_zero();
+    transcript::draw_deep(coin, m, W, ce, dr.data(), d_alpha.data(), d_beta.data(), d_delta.data(), deg_a.c, deg_b.c);
     uint64_t *sums, *dcoef; // the quotient sums on coset 0 and their coefficients (deep_extend)
     if (m == 1) {
         sums = R.deep;
@@ -852,10 +794,9 @@ int phase_compose(cstark_ctx *c, ProveArena *a, ProofRun &R) {
     if (dev_coin) HIP_TRY(hipMemcpyAsync(R.layer_roots.data(), d_roots, 32 * (size_t)n_layers, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(R.remainder.data(), R.layer[n_layers], R.remainder.size() * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(cs::stream_wait(st));
-    if (dev_coin)
-        for (unsigned l = 0; l < n_layers; l++) coin.reseed(&R.layer_roots[32 * l]); // the draws in between left no trace: reseed resets the counter
-    hash_elements(hf, R.remainder.data(), R.remainder.size(), R.rem_commit);
-    coin.reseed(R.rem_commit);
+    if (dev_coin) // the layers' points were drawn on the device: the same steps without their draws
+        for (unsigned l = 0; l < n_layers; l++) transcript::fri_layer(coin, &R.layer_roots[32 * l], m, nullptr);
+    transcript::commit_remainder(coin, R.remainder.data(), R.remainder.size(), R.rem_commit);
     STAGE();
 
     // ---- proof of work, query positions -------------------------------------------------------------------------------------
@@ -961,7 +902,7 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
         memcpy(s.prefix, prefix.data(), SEED_PREFIX); s.prefix_len = SEED_PREFIX;
         s.absorb[0].kind = CHAN_DIGEST; s.absorb[0].ptr = a->tnodes + 32; s.absorb[0].copy_out = d_res + o_troot;
         s.draw = CHAN_DRAW_COEFFS; s.a = job.n_constraints; s.b = job.n_assertions; s.stride = CSTARK_TX_NUM_CONSTRAINTS;
-        s.count = 2 * (job.n_constraints + job.n_assertions); s.out = d_coef_block;
+        s.count = (uint32_t)transcript::coefficient_draws(job.n_constraints, job.n_assertions); s.out = d_coef_block;
         HIP_TRY(channel_step(s, st));
     }
     if (is_tx) {
@@ -989,7 +930,7 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
         s.absorb[0].kind = CHAN_ELEMS; s.absorb[0].ptr = d_ood; s.absorb[0].count = (uint32_t)(2 * W);
         s.absorb[1].kind = CHAN_ELEMS; s.absorb[1].ptr = d_ood + 2 * W; s.absorb[1].count = (uint32_t)ce;
         s.draw = CHAN_DRAW_DEEP; s.a = (uint32_t)W; s.b = (uint32_t)ce; s.per = CSTARK_CONV_DEEP_DRAWS_PER_REGISTER;
-        s.count = (uint32_t)(s.per * W + ce + 2); s.out = d_deepc; s.out2 = d_scal;
+        s.count = (uint32_t)transcript::deep_draws(W, ce); s.out = d_deepc; s.out2 = d_scal;
         HIP_TRY(channel_step(s, st));
     }
     {   // the quotient sums on coset 0, read from the channel's blocks
@@ -1242,10 +1183,11 @@ int prove(cstark_ctx *c, const cstark_options *opt, AirJob &job, uint8_t *proof,
     return use_dev_channel(opt, job) ? prove_core_dev(c, opt, job, proof, capacity, proof_len) : prove_core(c, opt, job, proof, capacity, proof_len);
 }
 
-} // namespace
-} // namespace cs
 
-namespace {
+// ---- host steps of the batched range prover (cstark_range_prove_batch) ---------------------------------------------------------------------
+// B proofs of the reference's 64-row shape (range_batch.h: RB_N rows, RB_LDE points, W = RB_CE = 2 columns, base field): every device
+// stage is one launch over the batch, every channel step a walk over the B coins on a few host threads (transcript.h with m = 1).
+
 // f(i) for every i < count on up to eight host threads.  Nothing escapes: an exception inside a worker (the channel code allocates) or a
 // thread that cannot be created ends in CSTARK_ERR_OOM -- these lambdas run inside extern "C" functions, where an escaping exception
 // would be std::terminate.
@@ -1270,11 +1212,235 @@ int parallel_for(size_t count, F f) {
     }
     return failed.load() ? cs::fail(CSTARK_ERR_OOM, "host allocation or thread creation failed inside a batched channel step") : CSTARK_OK;
 }
-struct Carver { // consecutive 256-byte aligned pieces of one block
+struct Carver { // consecutive 256-byte aligned pieces of one block; base = null: only the offsets advance (off = the bytes a block needs)
     uint8_t *base; size_t off = 0;
-    template <class T> T *take(size_t bytes) { T *q = (T *)(base + off); off += (bytes + 255) & ~(size_t)255; return q; }
+    template <class T> T *take(size_t bytes) { T *q = base ? (T *)(base + off) : nullptr; off += (bytes + 255) & ~(size_t)255; return q; }
 };
+
+constexpr size_t RB_W = 2, RB_NC = 2, RB_NA = 2;                   // registers, transition constraints, assertions (src/range/air.rs:60-105)
+constexpr size_t RB_COEFS = transcript::coefficient_draws(RB_NC, RB_NA); // t_alpha[2] t_beta[2] b_alpha[2] b_beta[2]
+constexpr size_t RB_FRAME = 2 * RB_W + RB_CE;                      // T(z) | T(z w) | H_i(z^2)
+constexpr size_t RB_DEEP = RB_FRAME + 2;                           // alpha[2] beta[2] delta[2] deg_a deg_b
+
+struct RangeBatch {
+    cstark_ctx *c; const cstark_options *opt; const uint64_t *numbers; size_t B;
+    ProofShape S; OpenBlock O; // O: one proof's slot of the opening block, room for nq positions in the layer
+    unsigned log_rem;
+    hipStream_t st;
+    RangeBatchConsts K{};
+    std::vector<Coin> coins;
+    std::vector<uint64_t> nonces;
+    std::vector<uint8_t> rem_commit;
+    // the device block: per proof the tables, trees and channel values of range_batch.h
+    uint64_t *d_canon, *d_num, *d_trace, *d_coeffs, *d_lde, *d_coefs, *d_comb, *d_ccoef, *d_clde, *d_z, *d_ood, *d_dcoef, *d_layer, *d_alpha, *d_rem;
+    uint8_t *d_tnodes, *d_cnodes, *d_lnodes, *d_open;
+    uint32_t *d_pos, *d_lpos, *d_lcount, *d_gseed;
+    unsigned long long *d_gfound;
+    // the pinned host block: what the channel reads and the proof bytes are written from
+    uint8_t *h_troot, *h_croot, *h_lroot, *h_open;
+    uint64_t *h_coefs, *h_ood, *h_dcoef, *h_z, *h_alpha, *h_rem;
+    uint32_t *h_pos, *h_lpos, *h_lcount, *h_gseed;
+    unsigned long long *h_gfound;
+    size_t dev_bytes, host_bytes;
+
+
+    // every piece of both blocks, once: over null bases this measures them, over the blocks it places the pointers
+    void carve(uint8_t *dev, uint8_t *host) {
+        Carver D{dev}, H{host};
+        const size_t col = RB_N * 8, ext = RB_LDE * 8, tree = 2 * RB_LDE * 32, nq = S.nq; // bytes: a column, its extension, a tree over RB_LDE leaves
+        d_canon = D.take<uint64_t>(B * 8); d_num = D.take<uint64_t>(B * 8);
+        d_trace = D.take<uint64_t>(B * RB_W * col); d_coeffs = D.take<uint64_t>(B * RB_W * col); d_lde = D.take<uint64_t>(B * RB_W * ext);
+        d_coefs = D.take<uint64_t>(B * RB_COEFS * 8);
+        d_comb = D.take<uint64_t>(B * RB_CE * col); d_ccoef = D.take<uint64_t>(B * RB_CE * col); d_clde = D.take<uint64_t>(B * RB_CE * ext);
+        d_z = D.take<uint64_t>(B * 8); d_ood = D.take<uint64_t>(B * RB_FRAME * 8); d_dcoef = D.take<uint64_t>(B * RB_DEEP * 8);
+        d_layer = D.take<uint64_t>(B * ext); d_alpha = D.take<uint64_t>(B * 8); d_rem = D.take<uint64_t>(B * remainder_bytes(S));
+        d_tnodes = D.take<uint8_t>(B * tree); d_cnodes = D.take<uint8_t>(B * tree); d_lnodes = D.take<uint8_t>(B * ((size_t)64 << layer_log_rows(S, 0)));
+        d_pos = D.take<uint32_t>(B * nq * 4); d_lpos = D.take<uint32_t>(B * nq * 4); d_lcount = D.take<uint32_t>(B * 4);
+        d_open = D.take<uint8_t>(B * O.bytes);
+        d_gseed = D.take<uint32_t>(B * 32); d_gfound = D.take<unsigned long long>(B * 8);
+        h_troot = H.take<uint8_t>(B * 32); h_croot = H.take<uint8_t>(B * 32); h_lroot = H.take<uint8_t>(B * 32);
+        h_coefs = H.take<uint64_t>(B * RB_COEFS * 8); h_ood = H.take<uint64_t>(B * RB_FRAME * 8); h_dcoef = H.take<uint64_t>(B * RB_DEEP * 8);
+        h_z = H.take<uint64_t>(B * 8); h_alpha = H.take<uint64_t>(B * 8); h_rem = H.take<uint64_t>(B * remainder_bytes(S));
+        h_pos = H.take<uint32_t>(B * nq * 4); h_lpos = H.take<uint32_t>(B * nq * 4); h_lcount = H.take<uint32_t>(B * 4);
+        h_open = H.take<uint8_t>(B * O.bytes);
+        h_gseed = H.take<uint32_t>(B * 32); h_gfound = H.take<unsigned long long>(B * 8);
+        dev_bytes = D.off; host_bytes = H.off;
+    }
+    // one device block and one pinned host block of the context, kept across calls and replaced when a call needs more; the constants
+    int buffers() {
+        carve(nullptr, nullptr);
+        if (c->rb_dev_bytes < dev_bytes) {
+            HIP_TRY(hipStreamSynchronize(st));
+            if (c->rb_dev) { HIP_TRY(hipFree(c->rb_dev)); c->rb_dev = nullptr; c->rb_dev_bytes = 0; }
+            HIP_TRY(hipMalloc(&c->rb_dev, dev_bytes));
+            c->rb_dev_bytes = dev_bytes;
+        }
+        if (c->rb_host_bytes < host_bytes) {
+            HIP_TRY(hipStreamSynchronize(st));
+            if (c->rb_host) { HIP_TRY(hipHostFree(c->rb_host)); c->rb_host = nullptr; c->rb_host_bytes = 0; }
+            HIP_TRY(hipHostMalloc(&c->rb_host, host_bytes, hipHostMallocDefault));
+            c->rb_host_bytes = host_bytes;
+        }
+        carve((uint8_t *)c->rb_dev, (uint8_t *)c->rb_host);
+        coins.resize(B); nonces.resize(B); rem_commit.resize(32 * B);
+
+        using namespace cs::host;
+        const uint64_t n = RB_N, cen = n * RB_CE, wN = root_of_unity(S.log_N), g = lde_offset();
+        uint64_t sh = g;
+        for (int k = 0; k < 8; k++) { K.shift[k] = sh; K.zinv[k] = inv(sub(pow(sh, n), ONE)); sh = mul(sh, wN); }
+        K.w_last = inv(root_of_unity(RB_LOG_N));
+        K.adj[0] = CSTARK_CONV_TRANSITION_ADJUSTMENT(cen, n, 2 * (n - 1)); // degrees (2), (1): src/range/air.rs:100-105
+        K.adj[1] = CSTARK_CONV_TRANSITION_ADJUSTMENT(cen, n, 1 * (n - 1));
+        K.badj = CSTARK_CONV_BOUNDARY_ADJUSTMENT(cen, n, 1);
+        K.inv128 = inv(from_u64(cen)); K.ginv = inv(g); K.offset_inv = inv(g); K.inv4 = inv(from_u64(4));
+        const uint64_t *unused;
+        RC_TRY(plan_tables(c, RB_LOG_N, &K.w64, &unused));
+        RC_TRY(plan_tables(c, RB_LOG_N + 1, &unused, &K.winv128));
+        return plan_tables(c, S.log_N, &unused, &K.winv512);
+    }
+    // the rows of B tables [2^lb cosets][gw columns][2^ln] hashed into the leaves of B trees, the trees, their roots to the host
+    int commit_rows(const uint64_t *tab, unsigned gw, unsigned ln, unsigned lb, uint8_t *nodes, uint8_t *h_root) {
+        const size_t leaves = (size_t)1 << (ln + lb), tree = 2 * leaves * 32;
+        const unsigned nb = (unsigned)B;
+        if (opt->hash_fn == 1) {
+            HIP_TRY(hash_rows_batch_sha3(tab, nodes + 32 * leaves, gw, gw * nb, ln, lb, nb, tree, st));
+            HIP_TRY(merkle_build_batch_sha3(nodes, ln + lb, nb, tree, st));
+        } else {
+            HIP_TRY(hash_rows_batch(tab, nodes + 32 * leaves, gw, gw * nb, ln, lb, nb, tree, st));
+            HIP_TRY(merkle_build_batch(nodes, ln + lb, nb, tree, st));
+        }
+        HIP_TRY(hipMemcpy2DAsync(h_root, 32, nodes + 32, tree, 32, B, hipMemcpyDeviceToHost, st));
+        return CSTARK_OK;
+    }
+    int extend(const uint64_t *coef, uint64_t *lde) {
+        return cstark_lde_columns(c, coef, lde, (uint32_t)(2 * B), RB_LOG_N, RB_LOG_B, host::lde_offset(), 0, 1u << RB_LOG_B);
+    }
+
+    // trace, interpolation, extension, commitment; returns once the roots are on the host (`canon` and the caller's numbers have been read)
+    int trace_to_root(const uint64_t *canon) {
+        HIP_TRY(hipMemcpyAsync(d_canon, canon, B * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_num, numbers, B * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(rb_trace(d_canon, d_trace, (unsigned)B, st));
+        RC_TRY(cstark_interpolate_columns(c, d_trace, d_coeffs, (uint32_t)(RB_W * B), RB_LOG_N));
+        RC_TRY(extend(d_coeffs, d_lde));
+        RC_TRY(commit_rows(d_lde, RB_W, RB_LOG_N, RB_LOG_B, d_tnodes, h_troot));
+        HIP_TRY(cs::stream_wait(st));
+        return CSTARK_OK;
+    }
+    int coefficients() {
+        return parallel_for(B, [&](size_t t) {
+            const std::vector<uint8_t> seed = channel_seed(S.width, S.log_n, *opt, S.log_b, log_rem, &numbers[t], 1); // PublicInputs: the number (src/range/air.rs:26-36)
+            transcript::open(coins[t], opt->hash_fn, seed.data(), seed.size(), h_troot + 32 * t);
+            uint64_t dr[RB_COEFS], *cf = h_coefs + RB_COEFS * t;
+            transcript::draw_coefficients(coins[t], 1, RB_NC, RB_NA, dr, {{cf}, {cf + RB_NC}, {cf + 2 * RB_NC}, {cf + 2 * RB_NC + RB_NA}});
+        });
+    }
+    // constraint evaluation, composition polynomial and its commitment; returns once the roots are on the host
+    int constraints_to_root() {
+        HIP_TRY(hipMemcpyAsync(d_coefs, h_coefs, B * RB_COEFS * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(rb_combine(K, d_lde, d_coefs, d_num, d_comb, (unsigned)B, st));
+        HIP_TRY(rb_composition(K, d_comb, d_ccoef, (unsigned)B, st));
+        RC_TRY(extend(d_ccoef, d_clde));
+        RC_TRY(commit_rows(d_clde, RB_CE, RB_LOG_N, RB_LOG_B, d_cnodes, h_croot));
+        HIP_TRY(cs::stream_wait(st));
+        return CSTARK_OK;
+    }
+    // the out-of-domain points, the frames, and the DEEP coefficients drawn after them
+    int frame() {
+        RC_TRY(parallel_for(B, [&](size_t t) { transcript::draw_ood_point(coins[t], h_croot + 32 * t, 1, h_z + t); }));
+        HIP_TRY(hipMemcpyAsync(d_z, h_z, B * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(rb_ood(K, d_coeffs, d_ccoef, d_z, d_ood, (unsigned)B, st));
+        HIP_TRY(hipMemcpyAsync(h_ood, d_ood, B * RB_FRAME * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(cs::stream_wait(st));
+        return parallel_for(B, [&](size_t t) {
+            const uint64_t *f = h_ood + RB_FRAME * t;
+            transcript::absorb_frame(coins[t], 1, RB_W, RB_CE, f, f + 2 * RB_W);
+            uint64_t dr[transcript::deep_draws(RB_W, RB_CE)], *cf = h_dcoef + RB_DEEP * t;
+            transcript::draw_deep(coins[t], 1, RB_W, RB_CE, dr, cf, cf + RB_W, cf + 2 * RB_W, cf + RB_FRAME, cf + RB_FRAME + 1);
+        });
+    }
+    int deep() {
+        HIP_TRY(hipMemcpyAsync(d_dcoef, h_dcoef, B * RB_DEEP * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(rb_deep(K, d_lde, d_clde, d_z, d_ood, d_dcoef, d_layer, (unsigned)B, st));
+        return CSTARK_OK;
+    }
+    // at most one layer for a 512-point domain (remainder 128 .. 1024); returns once the remainders are on the host
+    int fri() {
+        if (S.n_layers) { // rows { e[i + t rows] }: table t = [f][rows] inside its 512 words
+            RC_TRY(commit_rows(d_layer, S.f, layer_log_rows(S, 0), 0, d_lnodes, h_lroot));
+            HIP_TRY(cs::stream_wait(st));
+            RC_TRY(parallel_for(B, [&](size_t t) { transcript::fri_layer(coins[t], h_lroot + 32 * t, 1, h_alpha + t); }));
+            HIP_TRY(hipMemcpyAsync(d_alpha, h_alpha, B * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(rb_fold(K, d_layer, d_alpha, d_rem, (unsigned)B, st));
+        }
+        HIP_TRY(hipMemcpyAsync(h_rem, S.n_layers ? d_rem : d_layer, B * remainder_bytes(S), hipMemcpyDeviceToHost, st));
+        HIP_TRY(cs::stream_wait(st));
+        return CSTARK_OK;
+    }
+    // Remainder commitments, proof of work, query positions.  From 12 bits on all B searches run on the device, chunk after chunk in
+    // increasing order, until every proof has its smallest nonce (grind_nonce above: the single-proof form); below, each proof's
+    // sequential search on its host thread.
+    int queries() {
+        static const bool grind_dev_env = [] { const char *e = getenv("CSTARK_GRIND_DEVICE"); return !e || atoi(e) != 0; }();
+        const unsigned bits = opt->grinding_factor;
+        const bool grind_dev = grind_dev_env && bits >= 12;
+        auto commit = [&](size_t t) { transcript::commit_remainder(coins[t], h_rem + S.R * t, S.R, &rem_commit[32 * t]); };
+        if (grind_dev) {
+            RC_TRY(parallel_for(B, [&](size_t t) {
+                commit(t);
+                memcpy(h_gseed + 8 * t, coins[t].seed, 32);
+                h_gfound[t] = ~0ull;
+            }));
+            HIP_TRY(hipMemcpyAsync(d_gseed, h_gseed, B * 32, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_gfound, h_gfound, B * 8, hipMemcpyHostToDevice, st));
+            uint64_t chunk = (uint64_t)4 << bits;                // four expected hits per proof and chunk
+            while (chunk * B > ((uint64_t)1 << 28)) chunk >>= 1; // at most 2^28 nonces per launch
+            if (chunk < 256) chunk = 256;
+            for (uint64_t base = 1;; base += chunk) {
+                if (opt->hash_fn == 1) HIP_TRY(cs::grind_batch_chunk_sha3((const uint64_t *)d_gseed, (unsigned)B, base, chunk, bits, d_gfound, st));
+                else HIP_TRY(cs::grind_batch_chunk(d_gseed, (unsigned)B, base, chunk, bits, d_gfound, st));
+                HIP_TRY(hipMemcpyAsync(h_gfound, d_gfound, B * 8, hipMemcpyDeviceToHost, st));
+                HIP_TRY(cs::stream_wait(st));
+                bool all = true;
+                for (size_t t = 0; t < B; t++) all = all && h_gfound[t] != ~0ull;
+                if (all) break;
+                if (base > ((uint64_t)1 << 44)) return fail(CSTARK_ERR_HIP, "proof of work: no nonce found");
+            }
+        }
+        return parallel_for(B, [&](size_t t) {
+            if (grind_dev) nonces[t] = h_gfound[t];
+            else { commit(t); nonces[t] = transcript::host_nonce(coins[t], bits); }
+            h_lcount[t] = 0;
+            transcript::draw_queries(coins[t], S, nonces[t], h_pos + S.nq * t, h_lpos + S.nq * t, 0, h_lcount + t);
+        });
+    }
+    // the openings of every proof into its slot of the block, the block to the host
+    int open() {
+        const size_t nq = S.nq;
+        HIP_TRY(hipMemcpyAsync(d_pos, h_pos, B * nq * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_lpos, h_lpos, B * nq * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_lcount, h_lcount, B * 4, hipMemcpyHostToDevice, st));
+        const RangeBatchOpen o{d_lde, d_clde, d_layer, d_tnodes, d_cnodes, d_lnodes, d_pos, d_lpos, d_lcount, d_open, (uint32_t)nq, (uint32_t)B, S.n_layers,
+                               O.bytes, O.trows, O.tpaths, O.crows, O.cpaths, O.lrows[0], O.lpaths[0]};
+        HIP_TRY(rb_open(o, st));
+        HIP_TRY(hipMemcpyAsync(h_open, d_open, B * O.bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(cs::stream_wait(st));
+        return CSTARK_OK;
+    }
+    // the proof bytes, proof t at proofs + stride t (the caller has checked that any proof of this shape fits a stride)
+    int write(uint8_t *proofs, size_t stride, size_t *lens) {
+        return parallel_for(B, [&](size_t t) {
+            const uint64_t *f = h_ood + RB_FRAME * t;
+            ProofParts p{};
+            p.trace_root = h_troot + 32 * t; p.cons_root = h_croot + 32 * t; p.layer_roots = h_lroot + 32 * t; p.rem_commit = &rem_commit[32 * t];
+            p.ood_trace = f; p.ood_comp = f + 2 * RB_W; p.nonce = nonces[t]; p.remainder = h_rem + S.R * t;
+            (void)finish_proof(S, p, h_open + O.bytes * t, O, h_lcount + t, proofs + stride * t, stride, &lens[t]);
+        });
+    }
+};
+
 } // namespace
+} // namespace cs
 
 using namespace cs;
 
@@ -1455,96 +1621,36 @@ int cstark_range_prove_bits(cstark_ctx *c, const cstark_options *opt, const uint
 // ---- B reference-shaped range proofs in one call (RangeProofExample::prove, src/range/mod.rs:75-100, benches/range.rs:15-37) ---------
 // Every stage is one launch over the batch (range_batch.hip; interpolation and extension of the 2 B columns through the generic
 // transform kernels), the host walks the B Fiat-Shamir channels between the stages on a few threads.  Same protocol, same bytes as
-// prove_core for CSTARK_AIR_RANGE: the channel order, the proof layout and every formula are the ones documented there.
+// prove_core for CSTARK_AIR_RANGE, from the same pieces: the channel steps are transcript.h's, the sizes proof_layout.h's, the opening
+// slot an OpenBlock, the bytes finish_proof's.  The stages (RangeBatch above): buffers; trace to root; coefficients; constraints to
+// root; frame and DEEP coefficients; DEEP composition; FRI; remainder, nonce and positions; openings; bytes.
 int cstark_range_prove_batch(cstark_ctx *c, const cstark_options *opt, const uint64_t *numbers, uint32_t count, uint8_t *proofs, size_t stride, size_t *lens) {
-    using namespace cs::host;
     if (!c || !opt || !numbers || !proofs || !lens || count == 0) return fail(CSTARK_ERR_INVALID_ARG, "cstark_range_prove_batch: null argument");
     // the transforms of the 2 * count columns are one launch with the column index in grid.y (at most 65535): 32768 proofs per call
     if (count > 32768) return fail(CSTARK_ERR_INVALID_ARG, "cstark_range_prove_batch: at most 32768 proofs per call");
     if (opt->field_extension != 0) return fail(CSTARK_ERR_UNSUPPORTED, "cstark_range_prove_batch: FieldExtension::None only (use cstark_air_prove)");
     unsigned log_rem = 0, log_b_opt = 3, log_f_opt = 2;
     RC_TRY(check_options(opt, 1, &log_rem, &log_b_opt, &log_f_opt));
-    if (log_b_opt != 3 || log_f_opt != 2) {
+    if (log_b_opt != RB_LOG_B || log_f_opt != 2) {
         // the one-launch-per-stage kernels (range_batch.hip) are laid out for the reference's get_example options (blowup 8, folding 4,
         // src/range/mod.rs:44-50); other option values go through the generic prover one proof at a time -- same bytes
         for (uint32_t t = 0; t < count; t++)
             RC_TRY(cstark_air_prove(c, CSTARK_AIR_RANGE, opt, numbers[t], proofs + stride * t, stride, &lens[t]));
         return CSTARK_OK;
     }
-    const ProofShape S = proof_shape(CSTARK_AIR_RANGE, 2, RB_LOG_N, 0, *opt);
-    const unsigned log_n = RB_LOG_N, log_N = log_n + 3, n_layers = S.n_layers;
-    const size_t B = count, n = RB_N, N = RB_LDE, nq = opt->num_queries, W = 2, ce = RB_CE;
-    if (nq > N / 4) return fail(CSTARK_ERR_INVALID_ARG, "more queries than the domain supports");
-    std::vector<uint64_t> canon(B);
-    for (size_t t = 0; t < B; t++) {
-        if (numbers[t] >= P) return fail(CSTARK_ERR_INVALID_ARG, "number is not a field element");
-        canon[t] = to_u64(numbers[t]);
+    const ProofShape S = proof_shape(CSTARK_AIR_RANGE, AIR_WIDTH[CSTARK_AIR_RANGE], RB_LOG_N, 0, *opt);
+    if (S.nq > RB_LDE / 4) return fail(CSTARK_ERR_INVALID_ARG, "more queries than the domain supports");
+    std::vector<uint64_t> canon(count);
+    for (size_t t = 0; t < count; t++) {
+        if (numbers[t] >= host::P) return fail(CSTARK_ERR_INVALID_ARG, "number is not a field element");
+        canon[t] = host::to_u64(numbers[t]);
         if (canon[t] >> 63) return fail(CSTARK_ERR_INVALID_ARG, "range proofs cover 63-bit field elements (src/range/tests.rs:54-62)");
     }
-    const size_t rem_len = n_layers ? N / 4 : N, slot = nq * 864;
-    const size_t per_proof = 4096 + 32 * 3 + 8 * (2 * W + ce) + nq * (W * 8 + ce * 8 + 2 * log_N * 32) + n_layers * (4 + nq * (32 + 7 * 32)) + 4 + 8 * rem_len;
-    if (stride < per_proof) return fail(CSTARK_ERR_INVALID_ARG, "cstark_range_prove_batch: stride too small (cstark_tx_proof_size_bound(1, opt) is sufficient)");
+    uint32_t all_nq[VMAX_LAYERS]; // the longest proof of this shape: nq distinct positions in every layer
+    std::fill(all_nq, all_nq + VMAX_LAYERS, S.nq);
+    if (stride < proof_size(S, all_nq)) return fail(CSTARK_ERR_INVALID_ARG, "cstark_range_prove_batch: stride too small (cstark_tx_proof_size_bound(1, opt) is sufficient)");
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const uint32_t hf = opt->hash_fn;
     if (c->arena) c->arena->timed = false; // cstark_prove_stage_ms describes the generic prover's last proof: none after a batch
-
-    // ---- buffers: one device block, one pinned host block ----------------------------------------------------------------------------
-    const size_t dev_need = B * (16 + 1024 * 2 + 8192 + 32768 + 64 + 1024 + 1024 + 8192 + 32768 + 8 + 48 + 64 + 4096 + 8192 + 8 + 8 * rem_len + 8 * nq + 4 + slot + 40) + 66 * 256;
-    const size_t host_need = B * (32 * 3 + 64 + 48 + 64 + 8 + 8 + 8 * rem_len + 8 * nq + 4 + slot + 40) + 34 * 256;
-    if (c->rb_dev_bytes < dev_need) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (c->rb_dev) { HIP_TRY(hipFree(c->rb_dev)); c->rb_dev = nullptr; c->rb_dev_bytes = 0; }
-        HIP_TRY(hipMalloc(&c->rb_dev, dev_need));
-        c->rb_dev_bytes = dev_need;
-    }
-    if (c->rb_host_bytes < host_need) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (c->rb_host) { HIP_TRY(hipHostFree(c->rb_host)); c->rb_host = nullptr; c->rb_host_bytes = 0; }
-        HIP_TRY(hipHostMalloc(&c->rb_host, host_need, hipHostMallocDefault));
-        c->rb_host_bytes = host_need;
-    }
-    Carver D{(uint8_t *)c->rb_dev}, H{(uint8_t *)c->rb_host};
-    uint64_t *d_canon = D.take<uint64_t>(B * 8), *d_num = D.take<uint64_t>(B * 8), *d_trace = D.take<uint64_t>(B * 1024), *d_coeffs = D.take<uint64_t>(B * 1024);
-    uint64_t *d_lde = D.take<uint64_t>(B * 8192), *d_coefs = D.take<uint64_t>(B * 64), *d_comb = D.take<uint64_t>(B * 1024), *d_ccoef = D.take<uint64_t>(B * 1024);
-    uint64_t *d_clde = D.take<uint64_t>(B * 8192), *d_z = D.take<uint64_t>(B * 8), *d_ood = D.take<uint64_t>(B * 48), *d_dcoef = D.take<uint64_t>(B * 64);
-    uint64_t *d_layer = D.take<uint64_t>(B * 4096), *d_alpha = D.take<uint64_t>(B * 8), *d_rem = D.take<uint64_t>(B * 8 * rem_len);
-    uint8_t *d_tnodes = D.take<uint8_t>(B * 32768), *d_cnodes = D.take<uint8_t>(B * 32768), *d_lnodes = D.take<uint8_t>(B * 8192);
-    uint32_t *d_pos = D.take<uint32_t>(B * nq * 4), *d_lpos = D.take<uint32_t>(B * nq * 4), *d_lcount = D.take<uint32_t>(B * 4);
-    uint8_t *d_open = D.take<uint8_t>(B * slot);
-    uint32_t *d_gseed = D.take<uint32_t>(B * 32);
-    unsigned long long *d_gfound = D.take<unsigned long long>(B * 8);
-    uint8_t *h_troot = H.take<uint8_t>(B * 32), *h_croot = H.take<uint8_t>(B * 32), *h_lroot = H.take<uint8_t>(B * 32);
-    uint64_t *h_coefs = H.take<uint64_t>(B * 64), *h_ood = H.take<uint64_t>(B * 48), *h_dcoef = H.take<uint64_t>(B * 64), *h_z = H.take<uint64_t>(B * 8);
-    uint64_t *h_alpha = H.take<uint64_t>(B * 8), *h_rem = H.take<uint64_t>(B * 8 * rem_len);
-    uint32_t *h_pos = H.take<uint32_t>(B * nq * 4), *h_lpos = H.take<uint32_t>(B * nq * 4), *h_lcount = H.take<uint32_t>(B * 4);
-    uint8_t *h_open = H.take<uint8_t>(B * slot);
-    uint32_t *h_gseed = H.take<uint32_t>(B * 32);
-    unsigned long long *h_gfound = H.take<unsigned long long>(B * 8);
-
-    RangeBatchConsts K{};
-    {
-        const uint64_t wN = root_of_unity(log_N), g = lde_offset();
-        uint64_t sh = g;
-        for (int k = 0; k < 8; k++) { K.shift[k] = sh; K.zinv[k] = inv(sub(pow(sh, n), ONE)); sh = mul(sh, wN); }
-        K.w_last = inv(root_of_unity(log_n));
-        const uint64_t cen = n * ce;
-        K.adj[0] = CSTARK_CONV_TRANSITION_ADJUSTMENT(cen, n, 2 * (n - 1)); // degrees (2), (1): src/range/air.rs:100-105
-        K.adj[1] = CSTARK_CONV_TRANSITION_ADJUSTMENT(cen, n, 1 * (n - 1));
-        K.badj = CSTARK_CONV_BOUNDARY_ADJUSTMENT(cen, n, 1);
-        K.inv128 = inv(from_u64(cen)); K.ginv = inv(g); K.offset_inv = inv(g); K.inv4 = inv(from_u64(4));
-        const uint64_t *unused;
-        RC_TRY(plan_tables(c, log_n, &K.w64, &unused));
-        RC_TRY(plan_tables(c, log_n + 1, &unused, &K.winv128));
-        RC_TRY(plan_tables(c, log_N, &unused, &K.winv512));
-    }
-    auto hash_rows_b = [&](const uint64_t *tab, uint8_t *leaves, unsigned gw, unsigned ln, unsigned lb, size_t leaf_stride) {
-        return hf == 1 ? hash_rows_batch_sha3(tab, leaves, gw, (unsigned)(gw * B), ln, lb, (unsigned)B, leaf_stride, st)
-                       : hash_rows_batch(tab, leaves, gw, (unsigned)(gw * B), ln, lb, (unsigned)B, leaf_stride, st);
-    };
-    auto merkle_b = [&](uint8_t *nodes, unsigned log_leaves, size_t node_stride) {
-        return hf == 1 ? merkle_build_batch_sha3(nodes, log_leaves, (unsigned)B, node_stride, st) : merkle_build_batch(nodes, log_leaves, (unsigned)B, node_stride, st);
-    };
 
     static const bool rb_prof = getenv("CSTARK_RB_PROF") != nullptr; // debugging: host wall-clock of the phases on stderr
     auto t_prev = std::chrono::steady_clock::now();
@@ -1554,156 +1660,25 @@ int cstark_range_prove_batch(cstark_ctx *c, const cstark_options *opt, const uin
         fprintf(stderr, "[cstark range batch] %-28s %8.1f us\n", what, std::chrono::duration<double, std::micro>(now - t_prev).count());
         t_prev = now;
     };
+    RangeBatch R{c, opt, numbers, count, S, open_block(S, nullptr), log_rem, c->stream};
+    RC_TRY(R.buffers());
     mark("setup");
-    // ---- trace, extension, commitment ----------------------------------------------------------------------------------------------------
-    HIP_TRY(hipMemcpyAsync(d_canon, canon.data(), B * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_num, numbers, B * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(rb_trace(d_canon, d_trace, (unsigned)B, st));
-    RC_TRY(cstark_interpolate_columns(c, d_trace, d_coeffs, (uint32_t)(2 * B), log_n));
-    RC_TRY(cstark_lde_columns(c, d_coeffs, d_lde, (uint32_t)(2 * B), log_n, 3, lde_offset(), 0, 8));
-    HIP_TRY(hash_rows_b(d_lde, d_tnodes + 32 * N, 2, log_n, 3, 2 * N * 32));
-    HIP_TRY(merkle_b(d_tnodes, log_N, 2 * N * 32));
-    HIP_TRY(hipMemcpy2DAsync(h_troot, 32, d_tnodes + 32, 2 * N * 32, 32, B, hipMemcpyDeviceToHost, st));
-    HIP_TRY(cs::stream_wait(st)); // (also: `canon` and the caller's numbers have been read)
-
+    RC_TRY(R.trace_to_root(canon.data()));
     mark("trace..trace roots (gpu)");
-    std::vector<Coin> coins(B);
-    RC_TRY(parallel_for(B, [&](size_t t) {
-        Coin &coin = coins[t];
-        coin.hash_fn = hf;
-        const std::vector<uint8_t> seed = channel_seed((uint32_t)W, log_n, *opt, 3, log_rem, &numbers[t], 1); // PublicInputs: the number (src/range/air.rs:26-36)
-        coin.init(seed.data(), seed.size());
-        coin.reseed(h_troot + 32 * t);
-        uint64_t *cf = h_coefs + 8 * t; // t_alpha[2] t_beta[2] b_alpha[2] b_beta[2]
-        for (int i = 0; i < 2; i++) { cf[i] = coin.draw(); cf[2 + i] = coin.draw(); }
-        for (int i = 0; i < 2; i++) { cf[4 + i] = coin.draw(); cf[6 + i] = coin.draw(); }
-    }));
+    RC_TRY(R.coefficients());
     mark("coefficients (host)");
-    HIP_TRY(hipMemcpyAsync(d_coefs, h_coefs, B * 64, hipMemcpyHostToDevice, st));
-
-    // ---- constraint evaluation, composition polynomial and its commitment -------------------------------------------------------------
-    HIP_TRY(rb_combine(K, d_lde, d_coefs, d_num, d_comb, (unsigned)B, st));
-    HIP_TRY(rb_composition(K, d_comb, d_ccoef, (unsigned)B, st));
-    RC_TRY(cstark_lde_columns(c, d_ccoef, d_clde, (uint32_t)(2 * B), log_n, 3, lde_offset(), 0, 8));
-    HIP_TRY(hash_rows_b(d_clde, d_cnodes + 32 * N, 2, log_n, 3, 2 * N * 32));
-    HIP_TRY(merkle_b(d_cnodes, log_N, 2 * N * 32));
-    HIP_TRY(hipMemcpy2DAsync(h_croot, 32, d_cnodes + 32, 2 * N * 32, 32, B, hipMemcpyDeviceToHost, st));
-    HIP_TRY(cs::stream_wait(st));
+    RC_TRY(R.constraints_to_root());
     mark("constraints..comp roots (gpu)");
-    RC_TRY(parallel_for(B, [&](size_t t) { coins[t].reseed(h_croot + 32 * t); h_z[t] = coins[t].draw(); }));
-    HIP_TRY(hipMemcpyAsync(d_z, h_z, B * 8, hipMemcpyHostToDevice, st));
-
-    // ---- out-of-domain frame, DEEP composition -----------------------------------------------------------------------------------------
-    HIP_TRY(rb_ood(K, d_coeffs, d_ccoef, d_z, d_ood, (unsigned)B, st));
-    HIP_TRY(hipMemcpyAsync(h_ood, d_ood, B * 48, hipMemcpyDeviceToHost, st));
-    HIP_TRY(cs::stream_wait(st));
-    RC_TRY(parallel_for(B, [&](size_t t) {
-        Coin &coin = coins[t];
-        uint8_t dg[32];
-        hash_elements(hf, h_ood + 6 * t, 4, dg); coin.reseed(dg);
-        hash_elements(hf, h_ood + 6 * t + 4, 2, dg); coin.reseed(dg);
-        uint64_t *cf = h_dcoef + 8 * t; // alpha[2] beta[2] delta[2] deg_a deg_b
-        for (int i = 0; i < 2; i++) {
-            cf[i] = coin.draw(); cf[2 + i] = coin.draw();
-            for (int k = 2; k < CSTARK_CONV_DEEP_DRAWS_PER_REGISTER; k++) (void)coin.draw();
-        }
-        for (int i = 0; i < 2; i++) cf[4 + i] = coin.draw();
-        cf[6] = coin.draw(); cf[7] = coin.draw();
-    }));
+    RC_TRY(R.frame());
     mark("ood + deep coefficients");
-    HIP_TRY(hipMemcpyAsync(d_dcoef, h_dcoef, B * 64, hipMemcpyHostToDevice, st));
-    HIP_TRY(rb_deep(K, d_lde, d_clde, d_z, d_ood, d_dcoef, d_layer, (unsigned)B, st));
-
-    // ---- FRI: at most one layer for a 512-point domain (remainder 128 .. 1024) ----------------------------------------------------------
-    if (n_layers) {
-        HIP_TRY(hash_rows_b(d_layer, d_lnodes + 32 * 128, 4, 7, 0, 256 * 32)); // rows { e[i + t 128] }: table t = [4][128] inside its 512 words
-        HIP_TRY(merkle_b(d_lnodes, 7, 256 * 32));
-        HIP_TRY(hipMemcpy2DAsync(h_lroot, 32, d_lnodes + 32, 256 * 32, 32, B, hipMemcpyDeviceToHost, st));
-        HIP_TRY(cs::stream_wait(st));
-        RC_TRY(parallel_for(B, [&](size_t t) { coins[t].reseed(h_lroot + 32 * t); h_alpha[t] = coins[t].draw(); }));
-        HIP_TRY(hipMemcpyAsync(d_alpha, h_alpha, B * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(rb_fold(K, d_layer, d_alpha, d_rem, (unsigned)B, st));
-        HIP_TRY(hipMemcpyAsync(h_rem, d_rem, B * 8 * rem_len, hipMemcpyDeviceToHost, st));
-    } else {
-        HIP_TRY(hipMemcpyAsync(h_rem, d_layer, B * 8 * rem_len, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(cs::stream_wait(st));
+    RC_TRY(R.deep());
+    RC_TRY(R.fri());
     mark("deep + fri (gpu + host)");
-    std::vector<uint64_t> nonces(B);
-    std::vector<uint8_t> rem_commit(32 * B);
-    // proof of work: from 12 bits on (Blake3 coin) all B searches run on the device, chunk after chunk in increasing order, until every
-    // proof has its smallest nonce (grind_nonce above: the single-proof form)
-    static const bool grind_dev_env = [] { const char *e = getenv("CSTARK_GRIND_DEVICE"); return !e || atoi(e) != 0; }();
-    const bool grind_dev = grind_dev_env && opt->grinding_factor >= 12;
-    if (grind_dev) {
-        RC_TRY(parallel_for(B, [&](size_t t) {
-            hash_elements(hf, h_rem + rem_len * t, rem_len, &rem_commit[32 * t]);
-            coins[t].reseed(&rem_commit[32 * t]);
-            memcpy(h_gseed + 8 * t, coins[t].seed, 32);
-            h_gfound[t] = ~0ull;
-        }));
-        HIP_TRY(hipMemcpyAsync(d_gseed, h_gseed, B * 32, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_gfound, h_gfound, B * 8, hipMemcpyHostToDevice, st));
-        uint64_t chunk = (uint64_t)4 << opt->grinding_factor; // four expected hits per proof and chunk
-        while (chunk * B > ((uint64_t)1 << 28)) chunk >>= 1;   // at most 2^28 nonces per launch
-        if (chunk < 256) chunk = 256;
-        for (uint64_t base = 1;; base += chunk) {
-            if (hf == 1) HIP_TRY(cs::grind_batch_chunk_sha3((const uint64_t *)d_gseed, (unsigned)B, base, chunk, opt->grinding_factor, d_gfound, st));
-            else HIP_TRY(cs::grind_batch_chunk(d_gseed, (unsigned)B, base, chunk, opt->grinding_factor, d_gfound, st));
-            HIP_TRY(hipMemcpyAsync(h_gfound, d_gfound, B * 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(cs::stream_wait(st));
-            bool all = true;
-            for (size_t t = 0; t < B; t++) all = all && h_gfound[t] != ~0ull;
-            if (all) break;
-            if (base > ((uint64_t)1 << 44)) return fail(CSTARK_ERR_HIP, "proof of work: no nonce found");
-        }
-    }
-    RC_TRY(parallel_for(B, [&](size_t t) {
-        Coin &coin = coins[t];
-        uint64_t nonce;
-        if (grind_dev) {
-            nonce = h_gfound[t];
-        } else {
-            hash_elements(hf, h_rem + rem_len * t, rem_len, &rem_commit[32 * t]);
-            coin.reseed(&rem_commit[32 * t]);
-            nonce = host_nonce(coin, opt->grinding_factor);
-        }
-        nonces[t] = nonce;
-        coin.reseed_int(nonce);
-        std::vector<uint32_t> pos;
-        coin.draw_integers(nq, N, pos);
-        memcpy(h_pos + nq * t, pos.data(), nq * 4);
-        if (n_layers) {
-            const std::vector<uint32_t> lp = fold_positions(pos, 128);
-            h_lcount[t] = (uint32_t)lp.size();
-            memcpy(h_lpos + nq * t, lp.data(), lp.size() * 4);
-            for (size_t q = lp.size(); q < nq; q++) h_lpos[nq * t + q] = 0;
-        } else h_lcount[t] = 0;
-    }));
-
+    RC_TRY(R.queries());
     mark("remainder, positions (host)");
-    // ---- openings, proof bytes ----------------------------------------------------------------------------------------------------------------
-    HIP_TRY(hipMemcpyAsync(d_pos, h_pos, B * nq * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_lpos, h_lpos, B * nq * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_lcount, h_lcount, B * 4, hipMemcpyHostToDevice, st));
-    RangeBatchOpen o{d_lde, d_clde, d_layer, d_tnodes, d_cnodes, d_lnodes, d_pos, d_lpos, d_lcount, d_open, (uint32_t)nq, (uint32_t)B, n_layers, slot};
-    HIP_TRY(rb_open(o, st));
-    HIP_TRY(hipMemcpyAsync(h_open, d_open, B * slot, hipMemcpyDeviceToHost, st));
-    HIP_TRY(cs::stream_wait(st));
-    RC_TRY(parallel_for(B, [&](size_t t) {
-        const uint8_t *op = h_open + slot * t;
-        const size_t o_trows = 0, o_tpath = o_trows + nq * 16, o_crows = o_tpath + nq * 288, o_cpath = o_crows + nq * 16, o_lrows = o_cpath + nq * 288,
-                     o_lpath = o_lrows + nq * 32;
-        ProofParts p{};
-        p.trace_root = h_troot + 32 * t; p.cons_root = h_croot + 32 * t; p.layer_roots = h_lroot + 32 * t; p.rem_commit = &rem_commit[32 * t];
-        p.ood_trace = h_ood + 6 * t; p.ood_comp = h_ood + 6 * t + 4; p.nonce = nonces[t]; p.remainder = h_rem + rem_len * t;
-        p.trows = op + o_trows; p.tpaths = op + o_tpath; p.crows = op + o_crows; p.cpaths = op + o_cpath;
-        p.counts = h_lcount + t; p.lrows[0] = op + o_lrows; p.lpaths[0] = op + o_lpath;
-        (void)write_proof(S, p, proofs + stride * t, stride, &lens[t]); // a proof that does not fit its stride is left out: reported below
-    }));
+    RC_TRY(R.open());
+    RC_TRY(R.write(proofs, stride, lens));
     mark("openings + serialise");
-    for (size_t t = 0; t < B; t++)
-        if (lens[t] > stride) return fail(CSTARK_ERR_INVALID_ARG, "cstark_range_prove_batch: stride too small");
     return CSTARK_OK;
 }
 

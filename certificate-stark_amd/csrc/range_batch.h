@@ -35,14 +35,14 @@ hipError_t rb_deep(const RangeBatchConsts &c, const uint64_t *d_lde, const uint6
 // FRI folding of each proof's 512 evaluations with its own alpha: d_out[t][128]
 hipError_t rb_fold(const RangeBatchConsts &c, const uint64_t *d_layer, const uint64_t *d_alpha, uint64_t *d_out, unsigned batch, hipStream_t stream);
 // openings: per proof nq trace rows [2] + paths [9][32], nq composition rows [2] + paths, np layer rows [4] + paths [7][32] into a slot
-// of `slot` bytes (layout: rb_open_layout)
+// of `slot` bytes, each section at its offset inside the slot (the host's opening block: open_block in prove.hip)
 struct RangeBatchOpen {
     const uint64_t *lde, *clde, *layer;       // [8][2 B][64], [8][2 B][64], [B][512]
     const uint8_t *tnodes, *cnodes, *lnodes;  // [B][1024][32], [B][1024][32], [B][256][32]
     const uint32_t *pos, *lpos, *lcount;      // [B][nq], [B][nq], [B]
     uint8_t *out;
     uint32_t nq, batch, n_layers;
-    size_t slot;
+    size_t slot, trows, tpaths, crows, cpaths, lrows, lpaths;
 };
 hipError_t rb_open(const RangeBatchOpen &o, hipStream_t stream);
 

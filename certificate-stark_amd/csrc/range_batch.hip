@@ -121,13 +121,12 @@ __global__ __launch_bounds__(128) void k_rb_fold(RangeBatchConsts c, const fp *_
     out[(size_t)t * 128 + i] = fp_mul(acc, c.inv4);
 }
 
-// slot layout (bytes): trace rows [nq][16] | trace paths [nq][9][32] | composition rows [nq][16] | paths [nq][9][32] | layer rows
-// [nq][32] | layer paths [nq][7][32]   (the last two hold lcount[t] entries)
+// the slot's sections (offsets: RangeBatchOpen): trace rows [nq][2] | trace paths [nq][9][32] | composition rows [nq][2] | paths
+// [nq][9][32] | layer rows [nq][4] | layer paths [nq][7][32]   (the last two hold lcount[t] entries)
 __global__ __launch_bounds__(64) void k_rb_open(RangeBatchOpen o) {
     const unsigned t = blockIdx.y, qi = blockIdx.x, W = 2 * o.batch, nq = o.nq;
     uint8_t *slot = o.out + (size_t)t * o.slot;
-    const size_t o_trows = 0, o_tpath = o_trows + (size_t)nq * 16, o_crows = o_tpath + (size_t)nq * 288, o_cpath = o_crows + (size_t)nq * 16,
-                 o_lrows = o_cpath + (size_t)nq * 288, o_lpath = o_lrows + (size_t)nq * 32;
+    const size_t o_trows = o.trows, o_tpath = o.tpaths, o_crows = o.crows, o_cpath = o.cpaths, o_lrows = o.lrows, o_lpath = o.lpaths;
     const unsigned pos = o.pos[(size_t)t * nq + qi], k = pos & 7, j = pos >> 3, lane = threadIdx.x;
     if (lane < 2) {
         reinterpret_cast<uint64_t *>(slot + o_trows)[qi * 2 + lane] = o.lde[((size_t)k * W + 2 * t + lane) * 64 + j];

@@ -567,7 +567,9 @@ def verify(proof, initial_root, final_root, options=None, probe=None):
     options: the 7 ProofOptions values the verifier expects (None = accept what the proof states).
     probe: a dict that receives the out-of-domain point "z" and both sides of the out-of-domain equation, "ood_lhs" (the constraints
     on the frame) and "ood_rhs" (sum_i z^i H_i), before they are compared (canonical integers, or m-tuples of them), and the query
-    "positions" once the proof of work has passed, with "draws": every integer the coin produced for them, skipped repeats included."""
+    "positions" once the proof of work has passed, with "draws": every integer the coin produced for them, skipped repeats included,
+    and everything else the coin drew on the way: "coefficients" (t_alpha, t_beta, b_alpha, b_beta), "deep" (alpha, beta, delta, deg_a,
+    deg_b) and "layer_points" (one folding point per FRI layer)."""
     d = parse(proof)
     if d["air"] != 0:
         raise VerifierError("not a TransactionAir proof")
@@ -586,14 +588,14 @@ def verify_merkle(proof, initial_root, final_root, options=None):
     return _verify(d, _MerkleAir(d, initial_root, final_root), options)
 
 
-def verify_range(proof, number, options=None):
-    """RangeProofAir (src/range/mod.rs:103-110); number in memory form."""
+def verify_range(proof, number, options=None, probe=None):
+    """RangeProofAir (src/range/mod.rs:103-110); number in memory form.  probe: as for verify."""
     d = parse(proof)
     if d["air"] != 3:
         raise VerifierError("not a RangeProofAir proof")
     if d["options"][4] in (1, 2):
-        return _verify_ext(d, _RangeAir(d, number), options)
-    return _verify(d, _RangeAir(d, number), options)
+        return _verify_ext(d, _RangeAir(d, number), options, probe)
+    return _verify(d, _RangeAir(d, number), options, probe)
 
 
 def verify_rescue(proof, seed, result, options=None):
@@ -679,7 +681,8 @@ def _verify(d, air, options, probe=None):
     draws = []
     positions = coin.draw_integers(nq, N, draws)
     if probe is not None:
-        probe.update(positions=list(positions), draws=draws)
+        probe.update(positions=list(positions), draws=draws, coefficients=(ta, tb, ba, bb), deep=(d_alpha, d_beta, d_delta, deg_a, deg_b),
+                     layer_points=alphas)
 
     # 3. trace / composition openings
     for q, pos in enumerate(positions):
@@ -855,7 +858,8 @@ def _verify_ext(d, air, options, probe=None):
     draws = []
     positions = coin.draw_integers(nq, N, draws)
     if probe is not None:
-        probe.update(positions=list(positions), draws=draws)
+        probe.update(positions=list(positions), draws=draws, coefficients=(ta, tb, ba, bb), deep=(d_alpha, d_beta, d_delta, deg_a, deg_b),
+                     layer_points=alphas)
     for q, pos in enumerate(positions):
         if merkle_root_from_path(H(elem_bytes(d["trace_rows"][q])), pos, d["trace_paths"][q], hash_fn) != d["trace_root"]:
             raise VerifierError("trace opening %d does not match the trace commitment" % q)

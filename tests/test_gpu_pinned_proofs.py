@@ -255,6 +255,26 @@ def test_batched_range_proofs_equal_single_proofs(oracle, backend, opts):
     assert backend.range_prove_batch(options(opts), numbers[:3]) == proofs[:3]   # a smaller batch on the same context
 
 
+@pytest.mark.parametrize("num_queries", [1, 128])     # 128: the most the options allow, and exactly the N / 4 the batch permits
+@pytest.mark.parametrize("max_remainder", [128, 1024])   # one FRI layer, none
+def test_batched_range_prover_at_the_extremes_of_its_layout(oracle, backend, num_queries, max_remainder):
+    """The batch's buffers, opening slots and proof sizes all come from the proof layout: the extremes of the shape -- one query and
+    128, with and without the FRI layer -- in batches of 1 and of 5 (not a multiple of the trace kernel's four proofs per workgroup),
+    at the extreme values.  Every proof equals cstark_air_prove's bytes, the 1-query proofs also the CPU prover's."""
+    from oracle import prover as OP
+    from certificate_stark_amd.backend import Backend
+    opts = (num_queries, 8, 0, 0, 0, 4, max_remainder)
+    values = [0, 1, 2**63 - 1, oracle.P - 1, 17]
+    numbers = oracle.to_mont(np.array([v % oracle.P for v in values], np.uint64))
+    single = [backend.air_prove(Backend.AIR_RANGE, options(opts), int(v)) for v in numbers]
+    assert list(backend.range_prove_batch(options(opts), numbers)) == single
+    for i in range(4):
+        assert list(backend.range_prove_batch(options(opts), numbers[i:i + 1])) == single[i:i + 1], i
+    if num_queries == 1:
+        for i, v in enumerate(numbers):
+            assert single[i] == OP.prove_air(oracle.AIR_RANGE, int(v), opts), i
+
+
 def test_batched_range_prover_at_baseline_size_and_its_errors(oracle, backend):
     """BASELINE 'range, 2^16 steps' in the reference's own shape: 1024 proofs of 64 rows in ONE call; every proof parsed, a sample
     compared with the single-proof path and verified.  Non-elements and values of 64 bits are refused as by the single prover."""

@@ -104,6 +104,77 @@ def test_writer_and_parser_share_one_layout(golden, tmp_path):
     assert out.returncode == 0 and out.stdout.startswith("ok") and "golden proof rewritten byte for byte" in out.stdout, out.stdout + out.stderr
 
 
+@pytest.fixture(scope="module")
+def transcript_check(tmp_path_factory):
+    """tests/cpp/transcript_check.cpp: csrc/transcript.h and csrc/proof_layout.h alone under g++ (host code only)"""
+    import subprocess
+    exe = str(tmp_path_factory.mktemp("transcript") / "transcript_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-o", exe,
+                           os.path.join(ROOT, "tests", "cpp", "transcript_check.cpp")])
+    return exe
+
+
+def _transcript_case(name, oracle, witness_d3):
+    """proof, the AIR as the restated verifier sees it, and the call that verifies the proof with a probe"""
+    from oracle import prover as OP
+    from oracle import verifier as V
+    if name == "golden":   # TransactionAir, Blake3, base field
+        z = np.load(GOLDEN)
+        proof, r0, r1 = bytes(z["proof"].tobytes()), z["initial_root"], z["final_root"]
+        return proof, V._TxAir(V.parse(proof), r0, r1), lambda probe: V.verify(proof, r0, r1, probe=probe)
+    options = {"range_sha3_pow": (30, 8, 3, 1, 0, 4, 128),        # Sha3, 3 bits of proof of work, one FRI layer
+               "range_quadratic": (20, 8, 0, 0, 1, 4, 1024)}[name]   # quadratic extension, no layer
+    number = int(oracle.to_mont(np.array([0x1234567890ABCDEF], np.uint64))[0])
+    proof = OP.prove_air(oracle.AIR_RANGE, number, options)
+    return proof, V._RangeAir(V.parse(proof), number), lambda probe: V.verify_range(proof, number, options=list(options), probe=probe)
+
+
+@pytest.mark.parametrize("case", ["golden", "range_sha3_pow", "range_quadratic"])
+def test_host_transcript_draws_what_the_restated_verifier_draws(oracle, witness_d3, transcript_check, tmp_path, case):
+    """csrc/transcript.h, the steps every host-channel prover calls, replayed from a proof's own roots, frame, layer roots, remainder
+    and nonce: EVERY value drawn -- coefficients, z, DEEP coefficients, FRI folding points, query positions and each layer's folded
+    positions -- equals what oracle/verifier.py draws for the same proof.  The values, not only the positions: every reseed resets the
+    draw counter, so a step with a wrong number of draws leaves no trace in what is drawn after it."""
+    import subprocess
+    from oracle import verifier as V
+    proof, air, verify = _transcript_case(case, oracle, witness_d3)
+    probe = {}
+    assert verify(probe)
+    dump = str(tmp_path / "proof.bin")
+    with open(dump, "wb") as f:
+        f.write(proof)
+    pub = [str(int(v)) for v in oracle.to_mont(np.array(air.pub, np.uint64))]
+    out = subprocess.run([transcript_check, dump, str(air.nc), str(air.na)] + pub, capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    got = {}
+    for ln in out.stdout.splitlines():
+        name, *vals = ln.split()
+        got[name] = [int(v) for v in vals]
+
+    d = V.parse(proof)
+    m, nq, n_layers = d["options"][4] + 1, d["options"][0], len(d["layer_roots"])
+    flat = lambda elems: [int(w) for e in elems for w in (e if isinstance(e, tuple) else (e,))]
+    ta, tb, ba, bb = probe["coefficients"]
+    d_alpha, d_beta, d_delta, deg_a, deg_b = probe["deep"]
+    want = {"t_alpha": flat(ta), "t_beta": flat(tb), "b_alpha": flat(ba), "b_beta": flat(bb), "z": flat([probe["z"]]),
+            "deep_alpha": flat(d_alpha), "deep_beta": flat(d_beta), "deep_delta": flat(d_delta), "deg_a": flat([deg_a]), "deg_b": flat([deg_b]),
+            "layer_points": flat(probe["layer_points"]), "positions": list(probe["positions"])}
+    assert len(want["t_alpha"]) == m * air.nc and len(want["b_beta"]) == m * air.na and len(want["deep_alpha"]) == m * air.width
+    assert len(want["deep_delta"]) == m * air.ce and len(want["layer_points"]) == m * n_layers and len(want["positions"]) == nq
+    log_N, log_f = d["log_n"] + d["options"][1].bit_length() - 1, d["options"][5].bit_length() - 1
+    cur, counts = want["positions"], []
+    for l in range(n_layers):
+        cur = V.fold_positions(cur, 1 << (log_N - (l + 1) * log_f))
+        want["folded_%d" % l] = cur
+        counts.append(len(cur))
+        assert len(d["layers"][l][0]) == len(cur)
+    want["folded_counts"] = counts
+    assert {"golden": 2, "range_sha3_pow": 1, "range_quadratic": 0}[case] <= n_layers and (case != "range_quadratic" or n_layers == 0)
+    assert sorted(got) == sorted(want)
+    for name in want:
+        assert got[name] == want[name], name
+
+
 def test_truncations_are_malformed(golden):
     cuts, _ = _sections(golden)
     lengths = set()
