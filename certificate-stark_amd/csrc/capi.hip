@@ -227,6 +227,24 @@ int lde_impl_inner(cstark_ctx *c, const uint64_t *d_coeffs, uint64_t *d_lde, uin
     return CSTARK_OK;
 }
 
+// Periodic columns over the LDE domain: host columns [ncols][2^log_cycle] -> *d_tab = [b][ncols][cycle], an allocation of `keep`.  A
+// column of period `cycle` is a polynomial of degree < cycle in x^(n/cycle): interpolated over the cycle, then evaluated over
+// offset' * <w_{b*cycle}>, offset' = g^(n/cycle).  Returns with the stream idle: `cols` may go out of scope, the scratch is freed.
+int extend_periodic_columns(cstark_ctx *c, const std::vector<uint64_t> &cols, uint32_t ncols, uint32_t log_cycle, unsigned log_n, unsigned log_b,
+                            DevGuard &keep, uint64_t **d_tab) {
+    const size_t words = (size_t)ncols << log_cycle, n = (size_t)1 << log_n;
+    uint64_t *d_cols = nullptr, *d_poly = nullptr;
+    DevGuard tmp; // never released: frees the scratch on every path
+    HIP_TRY(tmp.alloc(&d_cols, words * 8));
+    HIP_TRY(tmp.alloc(&d_poly, words * 8));
+    HIP_TRY(keep.alloc(d_tab, (words << log_b) * 8));
+    HIP_TRY(hipMemcpyAsync(d_cols, cols.data(), words * 8, hipMemcpyHostToDevice, c->stream));
+    RC_TRY(interpolate_impl(c, d_cols, d_poly, ncols, log_cycle));
+    RC_TRY(lde_impl(c, d_poly, *d_tab, ncols, 0, ncols, log_cycle, log_b, cs::host::pow(cs::host::lde_offset(), n >> log_cycle), 0, 1u << log_b));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CSTARK_OK;
+}
+
 // K7: periodic values of the 48 mask / round-constant columns over the constraint-evaluation domain, plus the
 // per-coset scalars of the driver.  Built once per (depth, trace length, blowup) and cached.
 int get_periodic(cstark_ctx *c, unsigned depth, unsigned log_n, unsigned log_b, const PeriodicTable **out) {
@@ -235,19 +253,13 @@ int get_periodic(cstark_ctx *c, unsigned depth, unsigned log_n, unsigned log_b, 
     if (log_n < 10) return fail(CSTARK_ERR_INVALID_ARG, "the trace must hold at least one 1024-row transaction");
     std::vector<uint64_t> cols;
     if (!cs::host::tx_periodic_columns(depth, cols)) return fail(CSTARK_ERR_INVALID_ARG, "unsupported Merkle depth");
-    const size_t n = (size_t)1 << log_n, b = (size_t)1 << log_b, C = cs::host::TX_CYCLE, NP = cs::host::TX_NUM_PERIODIC;
+    static_assert(cs::host::TX_CYCLE == 1 << 10, "the cycle of TransactionAir's periodic columns");
+    const size_t n = (size_t)1 << log_n, b = (size_t)1 << log_b;
     PeriodicTable t{depth, log_n, log_b, nullptr, nullptr, nullptr};
-    uint64_t *d_cols = nullptr, *d_poly = nullptr;
-    DevGuard keep, tmp; // g: the table (kept on success); tmp: scratch (always freed)
-    HIP_TRY(tmp.alloc(&d_cols, NP * C * 8));
-    HIP_TRY(tmp.alloc(&d_poly, NP * C * 8));
-    HIP_TRY(keep.alloc(&t.tab, b * NP * C * 8));
+    DevGuard keep;
+    RC_TRY(extend_periodic_columns(c, cols, cs::host::TX_NUM_PERIODIC, 10, log_n, log_b, keep, &t.tab));
     HIP_TRY(keep.alloc(&t.coset, b * cs::CE_COSET_CONSTS * 8));
-    HIP_TRY(hipMemcpyAsync(d_cols, cols.data(), NP * C * 8, hipMemcpyHostToDevice, c->stream));
-    RC_TRY(interpolate_impl(c, d_cols, d_poly, (uint32_t)NP, 10));
-    // a column of period 1024 is a polynomial in x^(n/1024): evaluate it over offset' * <w_{b*1024}>, offset' = g^(n/1024)
     const uint64_t g = cs::host::lde_offset();
-    RC_TRY(lde_impl(c, d_poly, t.tab, (uint32_t)NP, 0, (uint32_t)NP, 10, log_b, cs::host::pow(g, n / C), 0, (uint32_t)b));
     // per-coset scalars: shift_k = g w_{bn}^k, 1/(shift^n - 1), shift^adj_g, shift^badj
     std::vector<uint64_t> cc(b * cs::CE_COSET_CONSTS);
     const uint64_t wbn = cs::host::root_of_unity(log_n + log_b);
@@ -267,10 +279,58 @@ int get_periodic(cstark_ctx *c, unsigned depth, unsigned log_n, unsigned log_b, 
     RC_TRY(get_plan(c, log_n, &plan));
     HIP_TRY(keep.alloc(&t.binv, b * 2 * n * 8));
     HIP_TRY(cs::build_boundary_inverses(t.binv, plan->w, t.coset, cs::host::inv(cs::host::root_of_unity(log_n)), log_n, log_b, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream)); // cc / cols go out of scope; tmp frees the scratch
+    HIP_TRY(hipStreamSynchronize(c->stream)); // cc goes out of scope
     keep.release();
     c->periodic.push_back(t);
     *out = &c->periodic.back();
+    return CSTARK_OK;
+}
+
+// The standalone sub-AIRs' periodic columns over the LDE domain, built once per (AIR, depth, trace length, blowup): MerkleAir
+// [b][33][512] (depth: its hash length), SchnorrAir [b][36][512], RescueAir [b][29][8] (both: depth 0)
+int get_small_periodic(cstark_ctx *c, int air, unsigned depth, unsigned log_n, unsigned log_b, const PeriodicTable **out) {
+    for (const PeriodicTable &t : c->small_periodic)
+        if (t.air == air && t.depth == depth && t.log_n == log_n && t.log_b == log_b) { *out = &t; return CSTARK_OK; }
+    PeriodicTable t{depth, log_n, log_b, nullptr, nullptr, nullptr, air};
+    std::vector<uint64_t> cols;
+    DevGuard keep;
+    if (air == CSTARK_AIR_MERKLE_UPDATE) {
+        if (!cs::host::merkle_periodic_columns(depth, cols)) return fail(CSTARK_ERR_INVALID_ARG, "unsupported Merkle depth");
+        RC_TRY(extend_periodic_columns(c, cols, 33, 9, log_n, log_b, keep, &t.tab));
+    } else if (air == CSTARK_AIR_SCHNORR) {
+        cs::host::schnorr_mask_columns(cols);
+        RC_TRY(extend_periodic_columns(c, cols, 36, 9, log_n, log_b, keep, &t.tab));
+    } else if (air == CSTARK_AIR_RESCUE_CHAIN) {
+        // 8 x 29 x b values, computed on the host: the transform kernels start at 64 points
+        using namespace cs::host;
+        rescue_chain_periodic_columns(cols);
+        const size_t n = (size_t)1 << log_n, b = (size_t)1 << log_b;
+        for (int cidx = 0; cidx < 29; cidx++) intt_small(cols.data() + (size_t)cidx * 8, 3);
+        std::vector<uint64_t> tab(b * 29 * 8);
+        const uint64_t wbn = root_of_unity(log_n + log_b), w8 = root_of_unity(3);
+        uint64_t shift = lde_offset();
+        for (size_t k = 0; k < b; k++) {
+            uint64_t x = pow(shift, n / 8); // point m of coset k in the variable x^(n/8): shift^(n/8) w_8^m
+            for (int m = 0; m < 8; m++) {
+                for (int cidx = 0; cidx < 29; cidx++) {
+                    const uint64_t *co = cols.data() + (size_t)cidx * 8;
+                    uint64_t v = 0;
+                    for (int d = 7; d >= 0; d--) v = add(mul(v, x), co[d]);
+                    tab[(k * 29 + cidx) * 8 + m] = v;
+                }
+                x = mul(x, w8);
+            }
+            shift = mul(shift, wbn);
+        }
+        HIP_TRY(keep.alloc(&t.tab, tab.size() * 8));
+        HIP_TRY(hipMemcpyAsync(t.tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    } else {
+        return fail(CSTARK_ERR_UNSUPPORTED, "AIR not available through the generic entry points");
+    }
+    keep.release();
+    c->small_periodic.push_back(t);
+    *out = &c->small_periodic.back();
     return CSTARK_OK;
 }
 
@@ -987,9 +1047,9 @@ int final_hi_unmerged(const SplitStage &s, const SplitWs &w, unsigned rows, unsi
 
 // TransactionAir's parts on the even cosets into even = [CE_SPLIT_TABLES m][4][n]: those whose merged polynomials have degree < 4n
 // (constraints.hip: the Rescue windows with their flags; the doublings and the additions with the flag factored out), the final addition's
-// two sums (they join the tables; their high part follows after the extension) and the three linear groups -- in one pass over the
-// frame (k_lin_all) or, !lin_one_pass, the three launches of round 2.  pev: part timing; the one pass is reported as lin_a, lin_b = 0.
-int tx_even_cosets(const cs::CeParams &p, uint64_t *even, size_t n, hipStream_t stream, hipEvent_t *pev, bool lin_one_pass) {
+// two sums (they join the tables; their high part follows after the extension) and the three linear groups in one pass over the
+// frame (k_lin_all).  pev: part timing; the one pass is reported as lin_a, lin_b = 0.
+int tx_even_cosets(const cs::CeParams &p, uint64_t *even, size_t n, hipStream_t stream, hipEvent_t *pev) {
     if (pev) HIP_TRY(hipEventRecord(pev[0], stream));
     HIP_TRY(cs::launch_rounds_setup(p, stream));
     HIP_TRY(cs::launch_rounds_split(p, even, stream));
@@ -1005,16 +1065,9 @@ int tx_even_cosets(const cs::CeParams &p, uint64_t *even, size_t n, hipStream_t 
     if (pev) HIP_TRY(hipEventRecord(pev[5], stream));
     uint64_t *fam_final = fam_addbit + 8 * n;
     HIP_TRY(cs::launch_final_split(p, -1, fam_final, stream));
-    if (lin_one_pass) {
-        if (pev) HIP_TRY(hipEventRecord(pev[6], stream));
-        HIP_TRY(cs::launch_lin_all(p, even, stream));
-        if (pev) { HIP_TRY(hipEventRecord(pev[7], stream)); HIP_TRY(hipEventRecord(pev[8], stream)); }
-    } else {
-        for (int part = 6; part <= 8; part++) {
-            if (pev) HIP_TRY(hipEventRecord(pev[part], stream));
-            HIP_TRY(cs::launch_lin_split(p, part, even, stream));
-        }
-    }
+    if (pev) HIP_TRY(hipEventRecord(pev[6], stream));
+    HIP_TRY(cs::launch_lin_all(p, even, stream));
+    if (pev) { HIP_TRY(hipEventRecord(pev[7], stream)); HIP_TRY(hipEventRecord(pev[8], stream)); }
     return CSTARK_OK;
 }
 
@@ -1041,8 +1094,7 @@ int tx_evaluate_constraints_sets(cstark_ctx *c, const uint64_t *d_lde, const cst
     hipEvent_t *pev = c->part_timing ? c->part_ev : nullptr;
     // input_is_lde: d_lde is the extension of columns of degree < n (the prover's own table), which the split evaluation relies on;
     // the public stage entry points evaluate every point directly and are exact for ANY table
-    static const bool split_ext_env = [] { const char *e = getenv("CSTARK_ROUNDS_SPLIT_EXT"); return !e || atoi(e) != 0; }();
-    if (split_env && input_is_lde && (m == 1 || split_ext_env) && k0 == 0 && nk == 8 && log_n + 3 <= cs::NTT_MAX_LOG_N) { // (twiddle tables of size 8n)
+    if (split_env && input_is_lde && k0 == 0 && nk == 8 && log_n + 3 <= cs::NTT_MAX_LOG_N) { // (twiddle tables of size 8n)
         // (Part timing: the extension and the recombination are counted with the last part, lin_c.)
         SplitStage st;
         RC_TRY(split_stage(c, log_n, &st));
@@ -1056,9 +1108,7 @@ int tx_evaluate_constraints_sets(cstark_ctx *c, const uint64_t *d_lde, const cst
         SplitWs w;
         if (split_merge_env) RC_TRY(split_ws_merged(c, region, (size_t)F * 4 * n, hcol, &w));
         else RC_TRY(split_ws_unmerged(c, region, hcol, &w));
-        // CSTARK_LIN_MERGED=0 (tuning / debugging): the linear groups in three launches
-        static const bool lin_merged = [] { const char *e = getenv("CSTARK_LIN_MERGED"); return !e || atoi(e) != 0; }();
-        RC_TRY(tx_even_cosets(p, w.even, n, c->stream, pev, lin_merged));
+        RC_TRY(tx_even_cosets(p, w.even, n, c->stream, pev));
         RC_TRY(inverse_columns(st, w.even, w.sa, w.sb, 4 * T)); // every polynomial on every even coset
         if (split_merge_env) {
             // The recombination inside a flag family is a sum of monomial multiples, i.e. of rotated coefficient vectors: merged where the
@@ -1122,7 +1172,7 @@ int tx_evaluate_constraints_shard(cstark_ctx *c, const uint64_t *d_lde, const ui
     }
     SplitWs w;
     RC_TRY(split_ws_unmerged(c, region, hcol, &w));
-    RC_TRY(tx_even_cosets(p, w.even, n, c->stream, nullptr, true)); // no part timing; always the one-pass linear kernel
+    RC_TRY(tx_even_cosets(p, w.even, n, c->stream, nullptr)); // no part timing
     // interpolation of every table on the rank's even cosets: columns [kc0, kc0 + nkc) of each table's four (batch = table)
     RC_TRY(inverse_columns(st, w.even + (size_t)kc0 * n, w.sa + (size_t)kc0 * n, w.sb + (size_t)kc0 * n, nkc, T, 4 * n));
     RC_TRY(even_to_odd(st, w.sb, w.sa, T, kc0, nkc));
@@ -1266,39 +1316,13 @@ int cstark_schnorr_mask_columns(uint64_t *out /* [36][512] host */) {
     memcpy(out, cols.data(), cols.size() * 8);
     return CSTARK_OK;
 }
-// SchnorrAir's 36 periodic columns over the LDE domain, [b][36][512]; built once per (trace length, blowup)
-static int schnorr_periodic(cstark_ctx *c, uint32_t log_n, uint32_t log_blowup, const PeriodicTable **out) {
-    const PeriodicTable *pt = nullptr;
-    for (const PeriodicTable &t : c->small_periodic)
-        if (t.air == CSTARK_AIR_SCHNORR && t.log_n == log_n && t.log_b == log_blowup) pt = &t;
-    if (!pt) {
-        std::vector<uint64_t> cols;
-        cs::host::schnorr_mask_columns(cols);
-        const size_t n = (size_t)1 << log_n, b = (size_t)1 << log_blowup;
-        PeriodicTable t{0, log_n, log_blowup, nullptr, nullptr, nullptr, CSTARK_AIR_SCHNORR};
-        uint64_t *d_cols = nullptr, *d_poly = nullptr;
-        HIP_TRY(hipMalloc((void **)&d_cols, cols.size() * 8));
-        HIP_TRY(hipMalloc((void **)&d_poly, cols.size() * 8));
-        HIP_TRY(hipMalloc((void **)&t.tab, b * cols.size() * 8));
-        HIP_TRY(hipMemcpyAsync(d_cols, cols.data(), cols.size() * 8, hipMemcpyHostToDevice, c->stream));
-        RC_TRY(interpolate_impl(c, d_cols, d_poly, 36, 9));
-        RC_TRY(lde_impl(c, d_poly, t.tab, 36, 0, 36, 9, log_blowup, cs::host::pow(cs::host::lde_offset(), n / 512), 0, (uint32_t)b));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipFree(d_cols));
-        HIP_TRY(hipFree(d_poly));
-        c->small_periodic.push_back(t);
-        pt = &c->small_periodic.back();
-    }
-    *out = pt;
-    return CSTARK_OK;
-}
 int cstark_schnorr_evaluate_transitions(cstark_ctx *c, const uint64_t *d_lde, const uint64_t *d_aux_lde, uint64_t *d_out, uint32_t log_n,
                                         uint32_t log_blowup, uint32_t k0, uint32_t nk) {
     if (!c || !d_lde || !d_aux_lde || !d_out || nk == 0) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_evaluate_transitions: bad argument");
     if (log_n < 9 || log_n > cs::NTT_MAX_LOG_N || log_blowup > 6 || (uint64_t)k0 + nk > (1ull << log_blowup)) return fail(CSTARK_ERR_INVALID_ARG, "bad domain parameters");
     HIP_TRY(hipSetDevice(c->device));
     const PeriodicTable *pt;
-    RC_TRY(schnorr_periodic(c, log_n, log_blowup, &pt));
+    RC_TRY(get_small_periodic(c, CSTARK_AIR_SCHNORR, 0, log_n, log_blowup, &pt));
     HIP_TRY(cs::launch_eval_transitions_schnorr(d_lde, d_aux_lde, pt->tab, d_out, log_n, k0, nk, c->stream));
     return CSTARK_OK;
 }
@@ -1322,42 +1346,6 @@ int cstark_merkle_periodic_columns(uint32_t merkle_depth, uint64_t *out /* [33][
     return CSTARK_OK;
 }
 
-static int merkle_periodic(cstark_ctx *c, uint32_t merkle_depth, uint32_t log_n, uint32_t log_blowup, const PeriodicTable **out);
-// RescueAir's 29 periodic columns (cycle 8) over the LDE domain, [b][29][8]: a column of period 8 is a polynomial of degree < 8 in
-// x^(n/8); 8 x 8 x 29 x b values, computed on the host (the transform kernels start at 64 points)
-static int rescue_periodic(cstark_ctx *c, uint32_t log_n, uint32_t log_blowup, const PeriodicTable **out) {
-    const int air = CSTARK_AIR_RESCUE_CHAIN;
-    for (const PeriodicTable &t : c->small_periodic)
-        if (t.air == air && t.log_n == log_n && t.log_b == log_blowup) { *out = &t; return CSTARK_OK; }
-    using namespace cs::host;
-    std::vector<uint64_t> cols;
-    rescue_chain_periodic_columns(cols);
-    const size_t n = (size_t)1 << log_n, b = (size_t)1 << log_blowup;
-    for (int cidx = 0; cidx < 29; cidx++) intt_small(cols.data() + (size_t)cidx * 8, 3);
-    std::vector<uint64_t> tab(b * 29 * 8);
-    const uint64_t wbn = root_of_unity(log_n + log_blowup), w8 = root_of_unity(3);
-    uint64_t shift = lde_offset();
-    for (size_t k = 0; k < b; k++) {
-        uint64_t x = pow(shift, n / 8); // point m of coset k in the variable x^(n/8): shift^(n/8) w_8^m
-        for (int m = 0; m < 8; m++) {
-            for (int cidx = 0; cidx < 29; cidx++) {
-                const uint64_t *co = cols.data() + (size_t)cidx * 8;
-                uint64_t v = 0;
-                for (int d = 7; d >= 0; d--) v = add(mul(v, x), co[d]);
-                tab[(k * 29 + cidx) * 8 + m] = v;
-            }
-            x = mul(x, w8);
-        }
-        shift = mul(shift, wbn);
-    }
-    PeriodicTable t{0, log_n, log_blowup, nullptr, nullptr, nullptr, air};
-    HIP_TRY(hipMalloc((void **)&t.tab, tab.size() * 8));
-    HIP_TRY(hipMemcpyAsync(t.tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->small_periodic.push_back(t);
-    *out = &c->small_periodic.back();
-    return CSTARK_OK;
-}
 int cstark_rescue_chain_periodic_columns(uint64_t *out /* [29][8] host */) {
     if (!out) return fail(CSTARK_ERR_INVALID_ARG, "null argument");
     std::vector<uint64_t> cols;
@@ -1387,45 +1375,17 @@ int cstark_air_evaluate_transitions(cstark_ctx *c, int air, const uint64_t *d_ld
     }
     if (air == CSTARK_AIR_RESCUE_CHAIN) {
         const PeriodicTable *pt;
-        RC_TRY(rescue_periodic(c, log_n, log_blowup, &pt));
+        RC_TRY(get_small_periodic(c, air, 0, log_n, log_blowup, &pt));
         HIP_TRY(cs::launch_eval_transitions_rescue(d_lde, pt->tab, d_out, log_n, k0, nk, c->stream));
         return CSTARK_OK;
     }
     if (air != CSTARK_AIR_MERKLE_UPDATE) return fail(CSTARK_ERR_UNSUPPORTED, "AIR not available through the generic entry points");
     if (log_n < 9) return fail(CSTARK_ERR_INVALID_ARG, "the trace must hold at least one 512-row transaction");
     const PeriodicTable *pt;
-    RC_TRY(merkle_periodic(c, merkle_depth, log_n, log_blowup, &pt));
+    RC_TRY(get_small_periodic(c, air, merkle_depth, log_n, log_blowup, &pt));
     HIP_TRY(cs::launch_eval_transitions_merkle(d_lde, pt->tab, d_out, log_n, k0, nk, c->stream));
     return CSTARK_OK;
 }
-// MerkleAir's 33 periodic columns over the LDE domain, [b][33][512]; built once per (depth, trace length, blowup)
-static int merkle_periodic(cstark_ctx *c, uint32_t merkle_depth, uint32_t log_n, uint32_t log_blowup, const PeriodicTable **out) {
-    const int air = CSTARK_AIR_MERKLE_UPDATE;
-    const PeriodicTable *pt = nullptr;
-    for (const PeriodicTable &t : c->small_periodic)
-        if (t.air == air && t.depth == merkle_depth && t.log_n == log_n && t.log_b == log_blowup) pt = &t;
-    if (!pt) {
-        std::vector<uint64_t> cols;
-        if (!cs::host::merkle_periodic_columns(merkle_depth, cols)) return fail(CSTARK_ERR_INVALID_ARG, "unsupported Merkle depth");
-        const size_t n = (size_t)1 << log_n, b = (size_t)1 << log_blowup;
-        PeriodicTable t{merkle_depth, log_n, log_blowup, nullptr, nullptr, nullptr, air};
-        uint64_t *d_cols = nullptr, *d_poly = nullptr;
-        HIP_TRY(hipMalloc((void **)&d_cols, cols.size() * 8));
-        HIP_TRY(hipMalloc((void **)&d_poly, cols.size() * 8));
-        HIP_TRY(hipMalloc((void **)&t.tab, b * cols.size() * 8));
-        HIP_TRY(hipMemcpyAsync(d_cols, cols.data(), cols.size() * 8, hipMemcpyHostToDevice, c->stream));
-        RC_TRY(interpolate_impl(c, d_cols, d_poly, 33, 9));
-        RC_TRY(lde_impl(c, d_poly, t.tab, 33, 0, 33, 9, log_blowup, cs::host::pow(cs::host::lde_offset(), n / 512), 0, (uint32_t)b));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipFree(d_cols));
-        HIP_TRY(hipFree(d_poly));
-        c->small_periodic.push_back(t);
-        pt = &c->small_periodic.back();
-    }
-    *out = pt;
-    return CSTARK_OK;
-}
-
 // coefficient columns [12][n] of the value polynomials of SchnorrAir's sequence assertions (R.x at step 0 and at step 511 of
 // every 512-row block, src/schnorr/air.rs:172-224); the caller extends them with cstark_lde_columns
 int cstark_schnorr_assertion_polys(cstark_ctx *c, uint64_t *d_out, uint32_t log_n) {
@@ -1456,138 +1416,116 @@ int cstark_schnorr_assertion_polys(cstark_ctx *c, uint64_t *d_out, uint32_t log_
     return CSTARK_OK;
 }
 
-// d_schnorr_aux_lde != null (SchnorrAir only): the transition sum comes from the fused evaluator instead of d_evals
-static int air_combine_impl(cstark_ctx *c, int air, uint32_t n_items, const uint64_t *d_lde, const uint64_t *d_evals, const uint64_t *t_alpha,
-                            const uint64_t *t_beta, const uint64_t *b_alpha, const uint64_t *b_beta, const uint64_t *assertion_values,
-                            const uint64_t *d_avals_lde, uint32_t n_avals, uint64_t *d_out, uint32_t log_n, uint32_t log_blowup, uint32_t k0, uint32_t nk,
-                            const uint64_t *d_schnorr_aux_lde, int merkle_depth_fused = -1, bool schnorr_input_is_lde = false,
-                            const uint64_t *d_coefs = nullptr, const uint64_t *d_avalues = nullptr) {
-    // d_coefs != null (the device-side channel of prove.hip): the coefficients are already on the device, in the cstark_tx_coeffs-like
-    // block alpha[115] | beta[115] | b_alpha[na] | b_beta[na] (what channel.hip draws with stride 115); d_avalues: the assertion values on
-    // the device (null: the AIR's built-in constants)
-    const bool fused_merkle = merkle_depth_fused >= 0;
-    if (!c || !d_lde || (!d_evals && !d_schnorr_aux_lde && !fused_merkle) || (!d_coefs && (!t_alpha || !t_beta || !b_alpha || !b_beta)) || !d_out || nk == 0)
+} // extern "C"
+
+// ---- host steps of the sub-AIR constraint stage (ctx.h: AirStageRequest) --------------------------------------------------------------
+namespace {
+
+static_assert(cs::AIR_MAX_GROUPS == cs::host::AIR_MAX_GROUPS, "air_groups.h groups for the parameter block of constraints.h");
+using cs::AirStageRequest;
+using cs::AirTransitions;
+
+// the checks of a request, in the order their status codes have always had; fills the AIR's shape
+int air_stage_validate(cstark_ctx *c, const AirStageRequest &rq, cs::host::AirShape &s) {
+    const bool no_source = (rq.source == AirTransitions::Materialised && !rq.d_evals) || (rq.source == AirTransitions::SchnorrFused && !rq.d_aux_lde);
+    if (!c || !rq.d_lde || no_source || (!rq.d_coefs && (!rq.t_alpha || !rq.t_beta || !rq.b_alpha || !rq.b_beta)) || !rq.d_out || rq.nk == 0)
         return fail(CSTARK_ERR_INVALID_ARG, "cstark_air_combine: null argument");
-    if (d_schnorr_aux_lde && (air != CSTARK_AIR_SCHNORR || log_n < 9)) return fail(CSTARK_ERR_INVALID_ARG, "the fused evaluator is SchnorrAir's");
-    if (fused_merkle && (air != CSTARK_AIR_MERKLE_UPDATE || log_n < 9)) return fail(CSTARK_ERR_INVALID_ARG, "the fused evaluator is MerkleAir's");
-    cs::host::AirShape s;
-    if (!cs::host::air_shape(air, s, n_items)) return fail(CSTARK_ERR_UNSUPPORTED, "AIR not available through the generic entry points");
-    if (s.a_const.empty() && !assertion_values && !d_avalues) return fail(CSTARK_ERR_INVALID_ARG, "cstark_air_combine: assertion values required");
-    if (d_coefs && s.n_constraints > 115) return fail(CSTARK_ERR_UNSUPPORTED, "cstark_air_combine: device coefficient block holds at most 115 constraints");
-    const uint32_t log_ce = s.log_ce_blowup();
-    if (log_blowup < log_ce || log_blowup > 6 || (uint64_t)k0 + nk > (1ull << log_blowup)) return fail(CSTARK_ERR_INVALID_ARG, "blowup factor below the constraint degree");
-    if (log_n < cs::NTT_MIN_LOG_N || log_n > cs::NTT_MAX_LOG_N) return fail(CSTARK_ERR_INVALID_ARG, "bad trace length");
-    const uint64_t n = 1ull << log_n, ce = n << log_ce, b = 1ull << log_blowup;
-    const size_t nc = s.n_constraints, na = s.a_reg.size();
+    if (rq.source == AirTransitions::SchnorrFused && (rq.air != CSTARK_AIR_SCHNORR || rq.log_n < 9)) return fail(CSTARK_ERR_INVALID_ARG, "the fused evaluator is SchnorrAir's");
+    if (rq.source == AirTransitions::MerkleFused && (rq.air != CSTARK_AIR_MERKLE_UPDATE || rq.log_n < 9)) return fail(CSTARK_ERR_INVALID_ARG, "the fused evaluator is MerkleAir's");
+    if (!cs::host::air_shape(rq.air, s, rq.n_items)) return fail(CSTARK_ERR_UNSUPPORTED, "AIR not available through the generic entry points");
+    if (s.a_const.empty() && !rq.assertion_values && !rq.d_avalues) return fail(CSTARK_ERR_INVALID_ARG, "cstark_air_combine: assertion values required");
+    if (rq.d_coefs && s.n_constraints > 115) return fail(CSTARK_ERR_UNSUPPORTED, "cstark_air_combine: device coefficient block holds at most 115 constraints");
+    if (rq.log_blowup < s.log_ce_blowup() || rq.log_blowup > 6 || (uint64_t)rq.k0 + rq.nk > (1ull << rq.log_blowup))
+        return fail(CSTARK_ERR_INVALID_ARG, "blowup factor below the constraint degree");
+    if (rq.log_n < cs::NTT_MIN_LOG_N || rq.log_n > cs::NTT_MAX_LOG_N) return fail(CSTARK_ERR_INVALID_ARG, "bad trace length");
     bool needs_avals = false;
     for (int32_t q : s.a_seq) needs_avals |= q >= 0;
-    if (needs_avals && (!d_avals_lde || n_avals == 0)) return fail(CSTARK_ERR_INVALID_ARG, "this AIR has sequence assertions: pass the extended value polynomials");
-    if (b > 8) return fail(CSTARK_ERR_UNSUPPORTED, "cstark_air_combine: blowup factor at most 8");
-    HIP_TRY(hipSetDevice(c->device));
+    if (needs_avals && (!rq.d_avals_lde || rq.n_avals == 0)) return fail(CSTARK_ERR_INVALID_ARG, "this AIR has sequence assertions: pass the extended value polynomials");
+    if (rq.log_blowup > 3) return fail(CSTARK_ERR_UNSUPPORTED, "cstark_air_combine: blowup factor at most 8");
+    return CSTARK_OK;
+}
+
+// Everything that depends on (AIR, items, trace length, blowup) only: the degree / divisor groups and the powers of the coset offsets
+// (air_groups.h), the assertion tables on the device, the cached divisor inverses -- built once per context and key (rebuilt per call
+// it was ~150 modular exponentiations and a blocking upload between the trace root and the evaluation launches of EVERY sub-AIR
+// proof).  Nothing enters the context's caches before the whole entry is complete.
+int get_air_static(cstark_ctx *c, const AirStageRequest &rq, const cs::host::AirShape &s, const cs::AirCombineStatic **out) {
+    const uint32_t log_n = rq.log_n, log_b = rq.log_blowup;
+    for (const cs::AirCombineStatic &q : c->air_static)
+        if (q.air == rq.air && q.n_items == rq.n_items && q.log_n == log_n && q.log_b == log_b) { *out = &q; return CSTARK_OK; }
     const NttPlan *plan;
     RC_TRY(get_plan(c, log_n, &plan));
-    // ---- everything that depends on (AIR, trace length, blowup) only: degree / divisor groups, the powers of the coset offsets, the
-    // assertion tables on the device, the cached divisor inverses -- built once per context and key (round 3 rebuilt it per call: ~150
-    // modular exponentiations and a blocking upload between the trace root and the evaluation launches of EVERY sub-AIR proof)
-    cs::AirCombineStatic *st = nullptr;
-    for (cs::AirCombineStatic &q : c->air_static)
-        if (q.air == air && q.n_items == n_items && q.log_n == log_n && q.log_b == log_blowup) st = &q;
-    if (!st) {
-        cs::AirCombineStatic q{};
-        q.air = air; q.n_items = n_items; q.log_n = log_n; q.log_b = log_blowup;
-        cs::AirCombineParams &p = q.p;
-        const uint64_t wn = cs::host::root_of_unity(log_n);
-        q.t_grp.resize(nc);
-        std::vector<uint32_t> a_grp(na);
-        for (size_t i = 0; i < nc; i++) { // distinct degree adjustments
-            const uint64_t adj = CSTARK_CONV_TRANSITION_ADJUSTMENT(ce, n, s.eval_degree(i, n));
-            uint32_t g = 0;
-            while (g < p.n_tgrp && p.tgrp_adj[g] != adj) g++;
-            if (g == p.n_tgrp) {
-                if (g == cs::AIR_MAX_GROUPS) return fail(CSTARK_ERR_UNSUPPORTED, "too many distinct constraint degrees");
-                p.tgrp_adj[p.n_tgrp++] = adj;
-            }
-            q.t_grp[i] = g;
-        }
-        for (size_t a = 0; a < na; a++) { // distinct assertion divisors x^m - w^(first m)
-            const uint64_t first = s.a_stride.empty() ? (s.a_last[a] ? n - 1 : 0) : s.a_first[a];
-            const uint64_t m = (!s.a_stride.empty() && s.a_stride[a]) ? n / s.a_stride[a] : 1;
-            const uint64_t zc = cs::host::pow(wn, (first * m) % n);
-            uint32_t g = 0;
-            while (g < p.n_agrp && !(p.agrp_m[g] == m && p.agrp_zc[g] == zc)) g++;
-            if (g == p.n_agrp) {
-                if (g == cs::AIR_MAX_GROUPS) return fail(CSTARK_ERR_UNSUPPORTED, "too many distinct assertion divisors");
-                p.agrp_m[g] = m; p.agrp_zc[g] = zc; p.agrp_badj[g] = CSTARK_CONV_BOUNDARY_ADJUSTMENT(ce, n, m);
-                p.n_agrp++;
-            }
-            a_grp[a] = g;
-        }
-        // device block of the static part: shifts[b] | built-in assertion constants[na] (u64), then u32: a_reg | a_seq | a_grp | t_grp
-        std::vector<uint64_t> blk(b + na + (3 * na + nc + 1) / 2 + 1);
-        const uint64_t wbn = cs::host::root_of_unity(log_n + log_blowup);
-        {
-            uint64_t shift = cs::host::lde_offset();
-            for (uint64_t k = 0; k < b; k++) { blk[k] = shift; shift = cs::host::mul(shift, wbn); }
-        }
-        for (size_t a = 0; a < na; a++) blk[b + a] = s.a_const.empty() ? 0 : s.a_const[a];
-        uint32_t *q32 = (uint32_t *)(blk.data() + b + na);
-        for (size_t a = 0; a < na; a++) q32[a] = s.a_reg[a];
-        for (size_t a = 0; a < na; a++) ((int32_t *)q32)[na + a] = s.a_seq.empty() ? -1 : s.a_seq[a];
-        for (size_t a = 0; a < na; a++) q32[2 * na + a] = a_grp[a];
-        for (size_t i = 0; i < nc; i++) q32[3 * na + i] = q.t_grp[i];
-        HIP_TRY(hipMalloc((void **)&q.d_static, blk.size() * 8));
-        HIP_TRY(hipMemcpy(q.d_static, blk.data(), blk.size() * 8, hipMemcpyHostToDevice));
-        p.shifts = q.d_static;
-        p.a_reg = (const uint32_t *)(q.d_static + b + na); p.a_seq = (const int32_t *)(p.a_reg + na);
-        p.a_grp = p.a_reg + 2 * na; p.t_grp = p.a_reg + 3 * na;
-        p.w = plan->w;
-        p.w_last = cs::host::inv(wn);
-        p.width = s.width; p.n_constraints = (uint32_t)nc; p.n_assertions = (uint32_t)na;
-        p.stride = 1u << (log_blowup - log_ce); p.log_n = log_n;
-        {   // per-coset powers of the coset shift (the kernel completes them with a twiddle-table product per point)
-            uint64_t sh = cs::host::lde_offset();
-            for (uint64_t k = 0; k < b; k++) {
-                for (uint32_t g = 0; g < p.n_tgrp; g++) p.tgrp_shift[k][g] = cs::host::pow(sh, p.tgrp_adj[g]);
-                for (uint32_t g = 0; g < p.n_agrp; g++) {
-                    p.agrp_bshift[k][g] = cs::host::pow(sh, p.agrp_badj[g]);
-                    p.agrp_mshift[k][g] = cs::host::pow(sh, p.agrp_m[g]);
-                }
-                p.zinv_coset[k] = cs::host::inv(cs::host::sub(cs::host::pow(sh, n), cs::host::ONE));
-                sh = cs::host::mul(sh, wbn);
-            }
-        }
-        {   // 1 / (x^m - zc) of every assertion divisor over the domain: cached per (m, zc, trace length, blowup).
-            // CSTARK_AIR_INV_TABLES=0 (tuning / debugging): one inversion per point inside k_air_combine
-            static const bool inv_tables = [] { const char *e = getenv("CSTARK_AIR_INV_TABLES"); return !e || atoi(e) != 0; }();
-            for (uint32_t g = 0; inv_tables && g < p.n_agrp; g++) {
-                const cs::AssertInverseTable *t = nullptr;
-                for (const cs::AssertInverseTable &qq : c->assert_inv)
-                    if (qq.log_n == log_n && qq.log_b == log_blowup && qq.m == p.agrp_m[g] && qq.zc == p.agrp_zc[g]) t = &qq;
-                if (!t) {
-                    cs::AssertInverseTable qq{log_n, log_blowup, p.agrp_m[g], p.agrp_zc[g], nullptr};
-                    HIP_TRY(hipMalloc((void **)&qq.tab, (size_t)b * (n / qq.m) * 8));
-                    uint64_t sm[8] = {};
-                    for (uint64_t k = 0; k < b; k++) sm[k] = p.agrp_mshift[k][g];
-                    const hipError_t e = cs::launch_assert_inverses(qq.tab, plan->w, sm, (unsigned)b, qq.m, qq.zc, log_n, c->stream);
-                    if (e != hipSuccess) { (void)hipFree(qq.tab); HIP_TRY(e); }
-                    c->assert_inv.push_back(qq);
-                    t = &c->assert_inv.back();
-                }
-                p.agrp_inv[g] = t->tab;
-            }
-        }
-        c->air_static.push_back(std::move(q));
-        st = &c->air_static.back();
+    cs::host::AirGroups grp;
+    switch (cs::host::air_groups(s, log_n, log_b, grp)) {
+    case cs::host::AIR_GROUPS_TOO_MANY_DEGREES: return fail(CSTARK_ERR_UNSUPPORTED, "too many distinct constraint degrees");
+    case cs::host::AIR_GROUPS_TOO_MANY_DIVISORS: return fail(CSTARK_ERR_UNSUPPORTED, "too many distinct assertion divisors");
+    case cs::host::AIR_GROUPS_OK: break;
     }
-    const std::vector<uint32_t> &t_grp = st->t_grp;
-    // ---- per proof: coefficients and assertion values through a pinned staging block into the context's device block, no wait:
-    // t_alpha | t_beta | b_alpha | b_beta | a_value | the transition coefficients once more in the cstark_tx_coeffs layout (SchnorrAir's
-    // split evaluation reads alpha[i] at word i, beta[i] at word 115 + i) | device scratch of k_merkle_rounds
+    const uint64_t n = 1ull << log_n, b = 1ull << log_b;
+    const size_t nc = s.n_constraints, na = s.a_reg.size();
+    cs::AirCombineStatic q{};
+    q.air = rq.air; q.n_items = rq.n_items; q.log_n = log_n; q.log_b = log_b;
+    q.t_grp = grp.t_grp;
+    cs::AirCombineParams &p = q.p;
+    p.n_tgrp = grp.n_tgrp; p.n_agrp = grp.n_agrp;
+    memcpy(p.tgrp_adj, grp.tgrp_adj, sizeof p.tgrp_adj); memcpy(p.agrp_m, grp.agrp_m, sizeof p.agrp_m);
+    memcpy(p.agrp_zc, grp.agrp_zc, sizeof p.agrp_zc); memcpy(p.agrp_badj, grp.agrp_badj, sizeof p.agrp_badj);
+    memcpy(p.tgrp_shift, grp.tgrp_shift, sizeof p.tgrp_shift); memcpy(p.agrp_bshift, grp.agrp_bshift, sizeof p.agrp_bshift);
+    memcpy(p.agrp_mshift, grp.agrp_mshift, sizeof p.agrp_mshift); memcpy(p.zinv_coset, grp.zinv_coset, sizeof p.zinv_coset);
+    // device block of the static part: shifts[b] | built-in assertion constants[na] (u64), then u32: a_reg | a_seq | a_grp | t_grp
+    std::vector<uint64_t> blk(b + na + (3 * na + nc + 1) / 2 + 1);
+    for (uint64_t k = 0; k < b; k++) blk[k] = grp.shifts[k];
+    for (size_t a = 0; a < na; a++) blk[b + a] = s.a_const.empty() ? 0 : s.a_const[a];
+    uint32_t *q32 = (uint32_t *)(blk.data() + b + na);
+    for (size_t a = 0; a < na; a++) q32[a] = s.a_reg[a];
+    for (size_t a = 0; a < na; a++) ((int32_t *)q32)[na + a] = s.a_seq.empty() ? -1 : s.a_seq[a];
+    for (size_t a = 0; a < na; a++) q32[2 * na + a] = grp.a_grp[a];
+    for (size_t i = 0; i < nc; i++) q32[3 * na + i] = grp.t_grp[i];
+    DevGuard g;
+    HIP_TRY(g.alloc(&q.d_static, blk.size() * 8));
+    HIP_TRY(hipMemcpy(q.d_static, blk.data(), blk.size() * 8, hipMemcpyHostToDevice));
+    p.shifts = q.d_static;
+    p.a_reg = (const uint32_t *)(q.d_static + b + na); p.a_seq = (const int32_t *)(p.a_reg + na);
+    p.a_grp = p.a_reg + 2 * na; p.t_grp = p.a_reg + 3 * na;
+    p.w = plan->w;
+    p.w_last = cs::host::inv(cs::host::root_of_unity(log_n));
+    p.width = s.width; p.n_constraints = (uint32_t)nc; p.n_assertions = (uint32_t)na;
+    p.stride = 1u << (log_b - s.log_ce_blowup()); p.log_n = log_n;
+    // 1 / (x^m - zc) of every assertion divisor over the domain: cached per (m, zc, trace length, blowup).
+    // CSTARK_AIR_INV_TABLES=0 (tuning / debugging): one inversion per point inside k_air_combine
+    static const bool inv_tables = [] { const char *e = getenv("CSTARK_AIR_INV_TABLES"); return !e || atoi(e) != 0; }();
+    std::vector<cs::AssertInverseTable> built; // the divisors no earlier AIR of this context has had
+    for (uint32_t gi = 0; inv_tables && gi < p.n_agrp; gi++) {
+        for (const cs::AssertInverseTable &t : c->assert_inv)
+            if (t.log_n == log_n && t.log_b == log_b && t.m == p.agrp_m[gi] && t.zc == p.agrp_zc[gi]) p.agrp_inv[gi] = t.tab;
+        if (p.agrp_inv[gi]) continue;
+        cs::AssertInverseTable t{log_n, log_b, p.agrp_m[gi], p.agrp_zc[gi], nullptr};
+        HIP_TRY(g.alloc(&t.tab, (size_t)b * (n / t.m) * 8));
+        uint64_t sm[8] = {};
+        for (uint64_t k = 0; k < b; k++) sm[k] = p.agrp_mshift[k][gi];
+        HIP_TRY(cs::launch_assert_inverses(t.tab, plan->w, sm, (unsigned)b, t.m, t.zc, log_n, c->stream));
+        p.agrp_inv[gi] = t.tab;
+        built.push_back(t);
+    }
+    g.release();
+    for (const cs::AssertInverseTable &t : built) c->assert_inv.push_back(t);
+    c->air_static.push_back(std::move(q));
+    *out = &c->air_static.back();
+    return CSTARK_OK;
+}
+
+// The per-proof block of the context: t_alpha | t_beta | b_alpha | b_beta | a_value | the transition coefficients once more in the
+// cstark_tx_coeffs layout (SchnorrAir's split evaluation reads alpha[i] at word i, beta[i] at word 115 + i) | device scratch of
+// k_merkle_rounds.  Host coefficients go through a pinned staging block, no wait for the caller's arrays; device coefficients
+// (rq.d_coefs = alpha[115] | beta[115] | b_alpha[na] | b_beta[na], what channel.hip draws with stride 115) are read where they are,
+// the block then serves as the scratch alone.  Sets p's coefficient pointers; *d_txl: the cstark_tx_coeffs layout, *d_rtab: the scratch.
+int stage_air_coefs(cstark_ctx *c, const AirStageRequest &rq, const cs::host::AirShape &s, const cs::AirCombineStatic &st, cs::AirCombineParams &p,
+                    const uint64_t **d_txl, uint64_t **d_rtab) {
     constexpr size_t TXL = 230;
+    const size_t nc = s.n_constraints, na = s.a_reg.size();
     const size_t words = 2 * nc + 3 * na + TXL, total = words + cs::MERKLE_RTAB_WORDS;
-    const size_t txl_off = 2 * nc + 3 * na, mrt_off = words;
     if (c->air_coef_words < total) {
-        if (d_coefs && c->air_coef_words) HIP_TRY(hipEventSynchronize(c->air_coef_ev));
+        if (rq.d_coefs && c->air_coef_words) HIP_TRY(hipEventSynchronize(c->air_coef_ev));
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (c->air_coef_buf) { HIP_TRY(hipFree(c->air_coef_buf)); c->air_coef_buf = nullptr; }
         if (c->air_coef_stage) { HIP_TRY(hipHostFree(c->air_coef_stage)); c->air_coef_stage = nullptr; }
@@ -1596,127 +1534,160 @@ static int air_combine_impl(cstark_ctx *c, int air, uint32_t n_items, const uint
         HIP_TRY(hipHostMalloc((void **)&c->air_coef_stage, total * 8, hipHostMallocDefault));
         if (!c->air_coef_ev) HIP_TRY(hipEventCreateWithFlags(&c->air_coef_ev, hipEventDisableTiming));
         c->air_coef_words = total;
-    } else if (!d_coefs) {
+    } else if (!rq.d_coefs) {
         HIP_TRY(hipEventSynchronize(c->air_coef_ev)); // the previous upload has left the staging block (long ago, normally)
     }
-    if (!d_coefs) {
-        uint64_t *q = c->air_coef_stage;
-        memcpy(q, t_alpha, nc * 8); q += nc;
-        memcpy(q, t_beta, nc * 8); q += nc;
-        memcpy(q, b_alpha, na * 8); q += na;
-        memcpy(q, b_beta, na * 8); q += na;
-        for (size_t a = 0; a < na; a++) *q++ = s.a_const.empty() ? assertion_values[a] : s.a_const[a];
-        memset(q, 0, TXL * 8);
-        if (nc <= 115) { memcpy(q, t_alpha, nc * 8); memcpy(q + 115, t_beta, nc * 8); }
-        HIP_TRY(hipMemcpyAsync(c->air_coef_buf, c->air_coef_stage, words * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipEventRecord(c->air_coef_ev, c->stream));
-    }
     const uint64_t *d = c->air_coef_buf;
-    cs::AirCombineParams p = st->p;
-    p.lde = d_lde; p.evals = d_evals; p.out = d_out; p.avals = d_avals_lde; p.n_avals = n_avals; p.k0 = k0;
-    if (d_coefs) {
-        p.t_alpha = d_coefs; p.t_beta = d_coefs + 115; p.b_alpha = d_coefs + 230; p.b_beta = d_coefs + 230 + na;
-        p.a_value = d_avalues ? d_avalues : st->d_static + b;
-    } else {
-        p.t_alpha = d; p.t_beta = d + nc;
-        p.b_alpha = d + 2 * nc; p.b_beta = d + 2 * nc + na; p.a_value = d + 2 * nc + 2 * na;
+    *d_rtab = c->air_coef_buf + words;
+    if (rq.d_coefs) {
+        p.t_alpha = rq.d_coefs; p.t_beta = rq.d_coefs + 115; p.b_alpha = rq.d_coefs + 230; p.b_beta = rq.d_coefs + 230 + na;
+        p.a_value = rq.d_avalues ? rq.d_avalues : st.d_static + ((size_t)1 << rq.log_blowup); // null: the AIR's built-in constants
+        *d_txl = rq.d_coefs;
+        return CSTARK_OK;
     }
-    const uint64_t *d_txl = d_coefs ? d_coefs : d + txl_off; // the transition coefficients in the cstark_tx_coeffs layout
-    if (d_schnorr_aux_lde) {
-        const PeriodicTable *pt;
-        RC_TRY(schnorr_periodic(c, log_n, log_blowup, &pt));
-        // The doubling / addition gadgets in the degree-split form of the TransactionAir evaluator when the whole extension is at hand
-        // (every coset, blowup 8, at least eight signatures): their sums have degree < 4n without the periodic flags, so they are
-        // evaluated on the four even cosets, interpolated, extended to the odd cosets and recombined (constraints.hip,
-        // k_schnorr_ec_split).  The table must be a genuine extension -- it is the prover's own; the stage entry point passes any table,
-        // so it takes this path only under CSTARK_SCHNORR_SPLIT_STAGE=1 (tests).  CSTARK_SCHNORR_SPLIT=0: every point directly.
-        static const bool split_env = [] { const char *e = getenv("CSTARK_SCHNORR_SPLIT"); return !e || atoi(e) != 0; }();
-        if (split_env && schnorr_input_is_lde && k0 == 0 && nk == 8 && log_blowup == 3 && log_n >= 12 && log_n + 3 <= cs::NTT_MAX_LOG_N && n_items > 1) {
-            // the final addition (degree 5 (n - 1) without its flag) on five cosets: three more tables on the even cosets, LDE coset 1
-            // directly (CSTARK_SCHNORR_FINAL5=0: on all eight cosets through the frame evaluator)
-            static const bool final5 = [] { const char *e = getenv("CSTARK_SCHNORR_FINAL5"); return !e || atoi(e) != 0; }();
-            const unsigned T = final5 ? cs::SCHNORR_SPLIT_TABLES : cs::SCHNORR_SPLIT_EC_TABLES;
-            SplitStage st;
-            RC_TRY(split_stage(c, log_n, &st));
-            const size_t region = (size_t)T * 4 * n, hcol = (size_t)3 * n; // hcol: the final addition's three sums, one n-point table each
-            SplitWs w;
-            RC_TRY(split_ws_unmerged(c, region, hcol, &w));
-            HIP_TRY(cs::launch_schnorr_ec_split(p, d_schnorr_aux_lde, d_txl, w.even, c->stream));
-            if (final5) HIP_TRY(cs::launch_schnorr_final_split(p, d_txl, w.even + (size_t)cs::SCHNORR_SPLIT_EC_TABLES * 4 * n, -1, c->stream));
-            RC_TRY(inverse_columns(st, w.even, w.sa, w.sb, 4 * T));
-            RC_TRY(even_to_odd(st, w.sb, w.sa, T));
-            RC_TRY(forward_to_cosets(st, 1, w.sa, w.sc, w.odd, T, (size_t)T * n));
-            if (final5) { // the three sums directly on LDE coset 1, then their high parts as for TransactionAir
-                HIP_TRY(cs::launch_schnorr_final_split(p, d_txl, w.fin_direct, 1, c->stream));
-                RC_TRY(final_hi_unmerged(st, w, 3, cs::SCHNORR_SPLIT_EC_TABLES, 3, cs::SCHNORR_SPLIT_TABLES));
-            }
-            // the round gadget of the message hash in the folded form (CSTARK_SCHNORR_ROUNDS=0: inside the frame evaluator)
-            static const bool rounds_env = [] { const char *e = getenv("CSTARK_SCHNORR_ROUNDS"); return !e || atoi(e) != 0; }();
-            HIP_TRY(cs::launch_schnorr_split_finish(p, d_schnorr_aux_lde, pt->tab, w.even, w.odd, t_grp[0], t_grp[6], c->stream,
-                                                    rounds_env ? c->air_coef_buf + mrt_off : nullptr, t_grp[42], final5 ? w.fin_hi : nullptr));
-        } else {
-            HIP_TRY(cs::launch_schnorr_fused(p, d_schnorr_aux_lde, pt->tab, nk, c->stream));
-        }
-        p.tsum = d_out;
-    }
-    if (fused_merkle) {
-        const PeriodicTable *pt;
-        RC_TRY(merkle_periodic(c, (uint32_t)merkle_depth_fused, log_n, log_blowup, &pt));
-        // the round gadgets in the folded form of the TransactionAir evaluator (CSTARK_MERKLE_ROUNDS=0: the generic frame evaluator)
-        static const bool rounds_env = [] { const char *e = getenv("CSTARK_MERKLE_ROUNDS"); return !e || atoi(e) != 0; }();
-        const bool folded = rounds_env && b <= 8 && log_n >= 9;
-        HIP_TRY(cs::launch_merkle_fused(p, pt->tab, nk, c->stream, folded ? c->air_coef_buf + mrt_off : nullptr, t_grp[0]));
-        p.tsum = d_out;
-    }
-    HIP_TRY(cs::launch_air_combine(p, nk, c->stream));
+    uint64_t *q = c->air_coef_stage;
+    memcpy(q, rq.t_alpha, nc * 8); q += nc;
+    memcpy(q, rq.t_beta, nc * 8); q += nc;
+    memcpy(q, rq.b_alpha, na * 8); q += na;
+    memcpy(q, rq.b_beta, na * 8); q += na;
+    for (size_t a = 0; a < na; a++) *q++ = s.a_const.empty() ? rq.assertion_values[a] : s.a_const[a];
+    memset(q, 0, TXL * 8);
+    if (nc <= 115) { memcpy(q, rq.t_alpha, nc * 8); memcpy(q + 115, rq.t_beta, nc * 8); }
+    HIP_TRY(hipMemcpyAsync(c->air_coef_buf, c->air_coef_stage, words * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(c->air_coef_ev, c->stream));
+    p.t_alpha = d; p.t_beta = d + nc;
+    p.b_alpha = d + 2 * nc; p.b_beta = d + 2 * nc + na; p.a_value = d + 2 * nc + 2 * na;
+    *d_txl = d + 2 * nc + 3 * na;
     return CSTARK_OK;
 }
+
+// SchnorrAir's transition sum into p.out
+int schnorr_transition_sum(cstark_ctx *c, const AirStageRequest &rq, const cs::AirCombineParams &p, const std::vector<uint32_t> &t_grp, const uint64_t *d_txl,
+                           uint64_t *d_rtab) {
+    const PeriodicTable *pt;
+    RC_TRY(get_small_periodic(c, CSTARK_AIR_SCHNORR, 0, rq.log_n, rq.log_blowup, &pt));
+    // The doubling / addition gadgets in the degree-split form of the TransactionAir evaluator when the whole extension is at hand
+    // (every coset, blowup 8, at least eight signatures): their sums have degree < 4n without the periodic flags, so they are
+    // evaluated on the four even cosets, interpolated, extended to the odd cosets and recombined (constraints.hip,
+    // k_schnorr_ec_split).  The table must be a genuine extension (rq.own_extension: the prover's own, or what the caller of
+    // cstark_schnorr_evaluate_constraints_lde vouches for); cstark_schnorr_evaluate_constraints takes any table and every point
+    // directly.  CSTARK_SCHNORR_SPLIT=0: every point directly.
+    static const bool split_env = [] { const char *e = getenv("CSTARK_SCHNORR_SPLIT"); return !e || atoi(e) != 0; }();
+    if (!(split_env && rq.own_extension && rq.k0 == 0 && rq.nk == 8 && rq.log_blowup == 3 && rq.log_n >= 12 && rq.log_n + 3 <= cs::NTT_MAX_LOG_N && rq.n_items > 1)) {
+        HIP_TRY(cs::launch_schnorr_fused(p, rq.d_aux_lde, pt->tab, rq.nk, c->stream));
+        return CSTARK_OK;
+    }
+    // the final addition (degree 5 (n - 1) without its flag) on five cosets: three more tables on the even cosets, LDE coset 1
+    // directly (CSTARK_SCHNORR_FINAL5=0: on all eight cosets through the frame evaluator)
+    static const bool final5 = [] { const char *e = getenv("CSTARK_SCHNORR_FINAL5"); return !e || atoi(e) != 0; }();
+    const unsigned T = final5 ? cs::SCHNORR_SPLIT_TABLES : cs::SCHNORR_SPLIT_EC_TABLES;
+    SplitStage st;
+    RC_TRY(split_stage(c, rq.log_n, &st));
+    const size_t n = st.n, region = (size_t)T * 4 * n, hcol = (size_t)3 * n; // hcol: the final addition's three sums, one n-point table each
+    SplitWs w;
+    RC_TRY(split_ws_unmerged(c, region, hcol, &w));
+    HIP_TRY(cs::launch_schnorr_ec_split(p, rq.d_aux_lde, d_txl, w.even, c->stream));
+    if (final5) HIP_TRY(cs::launch_schnorr_final_split(p, d_txl, w.even + (size_t)cs::SCHNORR_SPLIT_EC_TABLES * 4 * n, -1, c->stream));
+    RC_TRY(inverse_columns(st, w.even, w.sa, w.sb, 4 * T));
+    RC_TRY(even_to_odd(st, w.sb, w.sa, T));
+    RC_TRY(forward_to_cosets(st, 1, w.sa, w.sc, w.odd, T, (size_t)T * n));
+    if (final5) { // the three sums directly on LDE coset 1, then their high parts as for TransactionAir
+        HIP_TRY(cs::launch_schnorr_final_split(p, d_txl, w.fin_direct, 1, c->stream));
+        RC_TRY(final_hi_unmerged(st, w, 3, cs::SCHNORR_SPLIT_EC_TABLES, 3, cs::SCHNORR_SPLIT_TABLES));
+    }
+    // the round gadget of the message hash in the folded form (CSTARK_SCHNORR_ROUNDS=0: inside the frame evaluator)
+    static const bool rounds_env = [] { const char *e = getenv("CSTARK_SCHNORR_ROUNDS"); return !e || atoi(e) != 0; }();
+    HIP_TRY(cs::launch_schnorr_split_finish(p, rq.d_aux_lde, pt->tab, w.even, w.odd, t_grp[0], t_grp[6], c->stream, rounds_env ? d_rtab : nullptr, t_grp[42],
+                                            final5 ? w.fin_hi : nullptr));
+    return CSTARK_OK;
+}
+
+// MerkleAir's transition sum into p.out
+int merkle_transition_sum(cstark_ctx *c, const AirStageRequest &rq, const cs::AirCombineParams &p, const std::vector<uint32_t> &t_grp, uint64_t *d_rtab) {
+    const PeriodicTable *pt;
+    RC_TRY(get_small_periodic(c, CSTARK_AIR_MERKLE_UPDATE, rq.merkle_depth, rq.log_n, rq.log_blowup, &pt));
+    // the round gadgets in the folded form of the TransactionAir evaluator (CSTARK_MERKLE_ROUNDS=0: the generic frame evaluator)
+    static const bool rounds_env = [] { const char *e = getenv("CSTARK_MERKLE_ROUNDS"); return !e || atoi(e) != 0; }();
+    HIP_TRY(cs::launch_merkle_fused(p, pt->tab, rq.nk, c->stream, rounds_env ? d_rtab : nullptr, t_grp[0]));
+    return CSTARK_OK;
+}
+
+} // namespace
+
+// (internal: declared in ctx.h for the prover)
+int air_stage(cstark_ctx *c, const AirStageRequest &rq) {
+    cs::host::AirShape s;
+    RC_TRY(air_stage_validate(c, rq, s));
+    HIP_TRY(hipSetDevice(c->device));
+    const cs::AirCombineStatic *st;
+    RC_TRY(get_air_static(c, rq, s, &st));
+    cs::AirCombineParams p = st->p;
+    p.lde = rq.d_lde; p.evals = rq.d_evals; p.out = rq.d_out; p.avals = rq.d_avals_lde; p.n_avals = rq.n_avals; p.k0 = rq.k0;
+    const uint64_t *d_txl;
+    uint64_t *d_rtab;
+    RC_TRY(stage_air_coefs(c, rq, s, *st, p, &d_txl, &d_rtab));
+    if (rq.source == AirTransitions::SchnorrFused) RC_TRY(schnorr_transition_sum(c, rq, p, st->t_grp, d_txl, d_rtab));
+    if (rq.source == AirTransitions::MerkleFused) RC_TRY(merkle_transition_sum(c, rq, p, st->t_grp, d_rtab));
+    if (rq.source != AirTransitions::Materialised) p.tsum = rq.d_out;
+    HIP_TRY(cs::launch_air_combine(p, rq.nk, c->stream));
+    return CSTARK_OK;
+}
+
+extern "C" {
+
 int cstark_air_combine(cstark_ctx *c, int air, uint32_t n_items, const uint64_t *d_lde, const uint64_t *d_evals, const uint64_t *t_alpha,
                        const uint64_t *t_beta, const uint64_t *b_alpha, const uint64_t *b_beta, const uint64_t *assertion_values,
                        const uint64_t *d_avals_lde, uint32_t n_avals, uint64_t *d_out, uint32_t log_n, uint32_t log_blowup, uint32_t k0, uint32_t nk) {
     if (!d_evals) return fail(CSTARK_ERR_INVALID_ARG, "cstark_air_combine: null argument");
-    return air_combine_impl(c, air, n_items, d_lde, d_evals, t_alpha, t_beta, b_alpha, b_beta, assertion_values, d_avals_lde, n_avals, d_out, log_n,
-                            log_blowup, k0, nk, nullptr);
+    AirStageRequest rq;
+    rq.air = air; rq.n_items = n_items;
+    rq.log_n = log_n; rq.log_blowup = log_blowup; rq.k0 = k0; rq.nk = nk;
+    rq.d_lde = d_lde; rq.d_out = d_out;
+    rq.source = AirTransitions::Materialised; rq.d_evals = d_evals;
+    rq.t_alpha = t_alpha; rq.t_beta = t_beta; rq.b_alpha = b_alpha; rq.b_beta = b_beta; rq.assertion_values = assertion_values;
+    rq.d_avals_lde = d_avals_lde; rq.n_avals = n_avals;
+    return air_stage(c, rq);
 }
 int cstark_merkle_evaluate_constraints(cstark_ctx *c, uint32_t merkle_depth, const uint64_t *d_lde, const uint64_t *t_alpha, const uint64_t *t_beta,
                                        const uint64_t *b_alpha, const uint64_t *b_beta, const uint64_t *assertion_values, uint64_t *d_out, uint32_t log_n,
                                        uint32_t log_blowup, uint32_t k0, uint32_t nk) {
     if (merkle_depth > 31) return fail(CSTARK_ERR_INVALID_ARG, "cstark_merkle_evaluate_constraints: unsupported Merkle depth");
-    return air_combine_impl(c, CSTARK_AIR_MERKLE_UPDATE, 0, d_lde, nullptr, t_alpha, t_beta, b_alpha, b_beta, assertion_values, nullptr, 0, d_out, log_n,
-                            log_blowup, k0, nk, nullptr, (int)merkle_depth);
+    AirStageRequest rq;
+    rq.air = CSTARK_AIR_MERKLE_UPDATE;
+    rq.log_n = log_n; rq.log_blowup = log_blowup; rq.k0 = k0; rq.nk = nk;
+    rq.d_lde = d_lde; rq.d_out = d_out;
+    rq.source = AirTransitions::MerkleFused; rq.merkle_depth = merkle_depth;
+    rq.t_alpha = t_alpha; rq.t_beta = t_beta; rq.b_alpha = b_alpha; rq.b_beta = b_beta; rq.assertion_values = assertion_values;
+    return air_stage(c, rq);
 }
+// any table: every point directly
 int cstark_schnorr_evaluate_constraints(cstark_ctx *c, uint32_t n_sig, const uint64_t *d_lde, const uint64_t *d_aux_lde, const uint64_t *t_alpha,
                                         const uint64_t *t_beta, const uint64_t *b_alpha, const uint64_t *b_beta, const uint64_t *d_avals_lde,
                                         uint32_t n_avals, uint64_t *d_out, uint32_t log_n, uint32_t log_blowup, uint32_t k0, uint32_t nk) {
     if (!d_aux_lde) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_evaluate_constraints: null argument");
-    return air_combine_impl(c, CSTARK_AIR_SCHNORR, n_sig, d_lde, nullptr, t_alpha, t_beta, b_alpha, b_beta, nullptr, d_avals_lde, n_avals, d_out, log_n,
-                            log_blowup, k0, nk, d_aux_lde);
+    AirStageRequest rq;
+    rq.air = CSTARK_AIR_SCHNORR; rq.n_items = n_sig;
+    rq.log_n = log_n; rq.log_blowup = log_blowup; rq.k0 = k0; rq.nk = nk;
+    rq.d_lde = d_lde; rq.d_out = d_out;
+    rq.source = AirTransitions::SchnorrFused; rq.d_aux_lde = d_aux_lde;
+    rq.t_alpha = t_alpha; rq.t_beta = t_beta; rq.b_alpha = b_alpha; rq.b_beta = b_beta;
+    rq.d_avals_lde = d_avals_lde; rq.n_avals = n_avals;
+    return air_stage(c, rq);
 }
-
+// the caller's tables are extensions of columns of degree < n: all eight cosets of blowup 8
 int cstark_schnorr_evaluate_constraints_lde(cstark_ctx *c, uint32_t n_sig, const uint64_t *d_lde, const uint64_t *d_aux_lde, const uint64_t *t_alpha,
                                             const uint64_t *t_beta, const uint64_t *b_alpha, const uint64_t *b_beta, const uint64_t *d_avals_lde,
                                             uint32_t n_avals, uint64_t *d_out, uint32_t log_n) {
     if (!d_aux_lde) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_evaluate_constraints_lde: null argument");
-    return air_combine_impl(c, CSTARK_AIR_SCHNORR, n_sig, d_lde, nullptr, t_alpha, t_beta, b_alpha, b_beta, nullptr, d_avals_lde, n_avals, d_out, log_n, 3, 0,
-                            8, d_aux_lde, -1, true);
+    AirStageRequest rq;
+    rq.air = CSTARK_AIR_SCHNORR; rq.n_items = n_sig;
+    rq.log_n = log_n; rq.log_blowup = 3; rq.k0 = 0; rq.nk = 8;
+    rq.d_lde = d_lde; rq.d_out = d_out;
+    rq.source = AirTransitions::SchnorrFused; rq.d_aux_lde = d_aux_lde; rq.own_extension = true;
+    rq.t_alpha = t_alpha; rq.t_beta = t_beta; rq.b_alpha = b_alpha; rq.b_beta = b_beta;
+    rq.d_avals_lde = d_avals_lde; rq.n_avals = n_avals;
+    return air_stage(c, rq);
 }
-
-} // extern "C"
-// internal (ctx.h): the merged evaluations of a sub-AIR with the coefficients already on the device (drawn there by the device-side
-// channel): d_coefs = alpha[115] | beta[115] | b_alpha[na] | b_beta[na]; d_avalues = the assertion values (null: built-in constants).
-// mode 0: from materialised transition values d_evals; 1: MerkleAir fused (depth); 2: SchnorrAir fused on the prover's own extensions
-int air_combine_dev(cstark_ctx *c, int air, uint32_t n_items, int mode, uint32_t merkle_depth, const uint64_t *d_lde, const uint64_t *d_evals,
-                    const uint64_t *d_aux_lde, const uint64_t *d_coefs, const uint64_t *d_avalues, const uint64_t *d_avals_lde, uint32_t n_avals, uint64_t *d_out,
-                    uint32_t log_n, uint32_t log_blowup, uint32_t nk) {
-    if (!d_coefs) return fail(CSTARK_ERR_INVALID_ARG, "air_combine_dev: null argument");
-    if (mode == 1) return air_combine_impl(c, air, n_items, d_lde, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, d_out, log_n, log_blowup, 0, nk,
-                                           nullptr, (int)merkle_depth, false, d_coefs, d_avalues);
-    if (mode == 2) return air_combine_impl(c, air, n_items, d_lde, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_avals_lde, n_avals, d_out, log_n, log_blowup, 0,
-                                           nk, d_aux_lde, -1, true, d_coefs, d_avalues);
-    return air_combine_impl(c, air, n_items, d_lde, d_evals, nullptr, nullptr, nullptr, nullptr, nullptr, d_avals_lde, n_avals, d_out, log_n, log_blowup, 0, nk, nullptr,
-                            -1, false, d_coefs, d_avalues);
-}
-extern "C" {
 
 // per-launch timing of the fused constraint evaluation (HIP events on the context's stream)
 int cstark_ctx_set_part_timing(cstark_ctx *c, int enable) {

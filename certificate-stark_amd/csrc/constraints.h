@@ -104,7 +104,8 @@ hipError_t launch_eval_transitions(const CeParams &p, unsigned nk, hipStream_t s
 // All 115 transition-constraint values of TransactionAir on nf free-standing frames (the verifier's out-of-domain check): frame j is
 // cur[c * nf + j] (c < 94), next[c * nf + j] and the periodic values per[c * nf + j] (c < 48); out[i * nf + j], i < 115 (device memory)
 hipError_t launch_eval_frames(const uint64_t *cur, const uint64_t *next, const uint64_t *per, uint64_t *out, unsigned nf, hipStream_t stream);
-constexpr int CE_NUM_PARTS = 9; // launches of the fused evaluation: rounds, dbl0, add0, dbl1, add1, final, lin_a, lin_b, lin_c
+constexpr int CE_NUM_PARTS = 9; // launches of the fused evaluation: rounds, dbl0, add0, dbl1, add1, final, lin_a, lin_b, lin_c (split form: the one
+                                // linear pass is timed as lin_a, lin_b = 0, lin_c = the extension and the recombination)
 hipError_t launch_eval_constraints(const CeParams &p, unsigned nk, hipStream_t stream, hipEvent_t *part_events = nullptr);
 // Split evaluation of the Rescue windows (m = 1, all 8 cosets, k0 = 0; constraints.hip): setup of the per-proof tables; the four
 // low-degree polynomials on the even cosets, d_even = [4][4][n]; recombination over all cosets from d_even and their extension to
@@ -117,9 +118,7 @@ hipError_t launch_rounds_split(const CeParams &p, uint64_t *d_even, hipStream_t 
 // addition family d_even_linear (after part 2 wrote it)
 hipError_t launch_ec_split(const CeParams &p, int part, uint64_t *d_even_family, uint64_t *d_even_linear, hipStream_t stream);
 constexpr int CE_SPLIT_TABLES = 13, CE_SPLIT_FAM0 = 4, CE_SPLIT_FINAL = 11; // first family (Rescue windows + linear groups): four polynomials; doubling 3 | addition 2 | addition x bit 2 | final addition 2
-// split evaluation of a linear group (part 6, 7, 8): adds to the first family, d_even_family0 = [4][4][n]
-hipError_t launch_lin_split(const CeParams &p, int part, uint64_t *d_even_family0, hipStream_t stream);
-// the three linear groups in one pass over the frame (k_lin_all); same four polynomials as the three launch_lin_split parts
+// split evaluation of the three linear groups in one pass over the frame (k_lin_all): adds to the first family, d_even_family0 = [4][4][n]
 hipError_t launch_lin_all(const CeParams &p, uint64_t *d_even_family0, hipStream_t stream);
 // one rank of a proof sharded by LDE coset (p.k0 even, p.nkc = 1 or 2 even cosets, m = 1): rows [p.nkc + 4][n] = its even cosets'
 // complete values, then its share of the four odd cosets (constraints.hip, k_split_finish_shard); d_bit37_all = register 37 on all cosets

@@ -407,15 +407,6 @@ constexpr int FNT = 256;
 #ifndef CS_EC_CALL
 #define CS_EC_CALL false // true: F_p6 products of the fused EC parts as calls (smaller code): measured slower, 2.57 vs 2.15 ms per part
 #endif
-#ifndef CS_LINS_UNROLL_A
-#define CS_LINS_UNROLL_A 1
-#endif
-#ifndef CS_LINS_UNROLL_B
-#define CS_LINS_UNROLL_B 7 // split linear groups, measured: A rolled 0.57 ms (unrolled 1.26); B with both loops unrolled 0.95 ms (rolled 1.14)
-#endif
-#ifndef CS_LINS_UNROLL_BLK
-#define CS_LINS_UNROLL_BLK 2
-#endif
 #ifndef CS_ROUNDS_INV_UNROLL
 #define CS_ROUNDS_INV_UNROLL 1
 #endif
@@ -1047,7 +1038,7 @@ __device__ __forceinline__ void fused_final_addition(A &acc, const Frame &f, fp 
 // multiplied by the flag at every point in k_split_finish.  (The addition of the public key and the final addition reach degree
 // 5 (n - 1) and stay on all eight cosets.)  Accumulator with the interface of Fused: slots of the curve registers are in groups 0..2.
 // The two bit registers (slots 18 and 37, the only curve slots of group 2) are left out here: their terms are quadratic at most and
-// join the flags-inside family in lin_c_split, which keeps the curve families at three (alpha, beta of groups 0, 1) / two tables.
+// join the flags-inside family of the linear groups (lin_all_split), which keeps the curve families at three (alpha, beta of groups 0, 1) / two tables.
 template <int M>
 struct SplitAcc {
     const CS_CONST fp *coefs; // M blocks of CE_COEF_WORDS: alpha[115] | beta[115] | ...
@@ -1402,8 +1393,7 @@ __device__ __forceinline__ void fused_linear_c(Fused<M> &acc, const Frame &f) {
 }
 
 // ---- split evaluation of the linear groups (flags inside: every term has degree < 4n, see the degree table in DESIGN.md) ---------
-// Section accumulator for slots of any degree group: alpha-weighted sum and one beta-weighted sum per group.  The slot may be a
-// run-time value (rolled loops): its group is then a uniform condition.
+// Section accumulator for slots of any degree group: alpha-weighted sum and one beta-weighted sum per group.
 constexpr unsigned G0 = 1, G1 = 2, G2 = 4, G3 = 8, G4 = 16;
 // GM: the groups this section's slots can be in -- only those get a beta accumulator (four registers each) and a test in term().
 template <unsigned GM>
@@ -1453,174 +1443,16 @@ struct SectionAccT {
             }
     }
 };
-using SectionAcc = SectionAccT<31u>;
 
-// setup + value-copy constraints: every slot is in group 4
-__device__ __forceinline__ void lin_a_split(const CS_CONST fp *coefs, const Frame &f, fp (&tot)[6]) {
-    const fp setup = f.pv(P_SETUP), copy_values = f.pv(P_VALUE_COPY);
-    SectionAcc s_set, s_cp;
-    s_set.coefs = s_cp.coefs = coefs;
-    s_set.begin(); s_cp.begin();
-#pragma unroll CS_LINS_UNROLL_A
-    for (int i = 0; i < 12; i++) {
-        const fp si = f.cur(S_INIT + i), su = f.cur(S_UPD + i), ri = f.cur(R_INIT + i), ru = f.cur(R_UPD + i);
-        const fp skn = f.next(S_KEY + i), skc = f.cur(S_KEY + i), rkn = f.next(R_KEY + i), rkc = f.cur(R_KEY + i);
-        s_set.term(VALUE_RES + i, fp_sub(si, su));
-        s_set.term(VALUE_RES + 12 + i, fp_sub(ri, ru));
-        s_set.term(S_KEY_RES + i, fp_sub(skn, si));
-        s_set.term(R_KEY_RES + i, fp_sub(rkn, ri));
-        s_cp.term(S_KEY_RES + i, fp_sub(skn, skc));
-        s_cp.term(R_KEY_RES + i, fp_sub(rkn, rkc));
-    }
-    const fp s_spent = fp_sub(f.cur(S_INIT + 12), f.cur(S_UPD + 12));
-    const fp nd = f.next(DELTA_COPY), ns = f.next(SIGMA_COPY), nn = f.next(NONCE_COPY);
-    s_set.term(VALUE_RES + 24, fp_sub(f.cur(R_INIT + 13), f.cur(R_UPD + 13)));
-    s_set.term(BALANCE_RES, fp_sub(s_spent, fp_sub(f.cur(R_UPD + 12), f.cur(R_INIT + 12))));
-    s_set.term(NONCE_UPD_RES, fp_sub(f.cur(S_UPD + 13), fp_add(f.cur(S_INIT + 13), FP_ONE)));
-    s_set.term(DELTA_COPY_RES, fp_sub(nd, s_spent));
-    s_set.term(SIGMA_COPY_RES, fp_sub(ns, f.cur(S_UPD + 12)));
-    s_set.term(NONCE_COPY_RES, fp_sub(nn, f.cur(S_INIT + 13)));
-    s_cp.term(DELTA_COPY_RES, fp_sub(nd, f.cur(DELTA_COPY)));
-    s_cp.term(SIGMA_COPY_RES, fp_sub(ns, f.cur(SIGMA_COPY)));
-    s_cp.term(NONCE_COPY_RES, fp_sub(nn, f.cur(NONCE_COPY)));
-    s_set.flush<G4>(setup, tot);
-    s_cp.flush<G4>(copy_values, tot);
-}
-// merkle::update without its rounds
-__device__ __forceinline__ void lin_b_split(const CS_CONST fp *coefs, const Frame &f, fp (&tot)[6]) {
-    const fp tx_hash = f.pv(P_MERKLE), hash_input = f.pv(P_HASH_INPUT), finish = f.pv(P_FINISH), hash_flag = f.pv(P_HASH);
-    const fp hash_copy = fp_mul(tx_hash, c_not(fp_add(hash_flag, hash_input)));
-    const fp hash_init = fp_mul(tx_hash, hash_input);
-    SectionAcc sa, sb;
-    sa.coefs = sb.coefs = coefs;
-#pragma unroll CS_LINS_UNROLL_BLK
-    for (int blk = 0; blk < 2; blk++) {
-        const int base = blk == 0 ? S_INIT : R_INIT;
-        const fp bit = f.next(base + 14), not_bit = c_not(bit);
-        sa.begin();
-        sa.term(base + 14, c_is_binary(bit));
-        sa.flush<G1 | G2>(tx_hash, tot); // slot 14: group 1, slot 43: group 2
-        sa.begin(); sb.begin();
-#pragma unroll CS_LINS_UNROLL_B
-        for (int i = 0; i < 7; i++) {
-            const fp ca = f.cur(base + i), na0 = f.next(base + i), cb = f.cur(base + 15 + i), nb0 = f.next(base + 15 + i);
-            const fp na7 = f.next(base + 7 + i), nb7 = f.next(base + 22 + i);
-            const fp da = fp_sub(ca, na0), db = fp_sub(cb, nb0);
-            sa.term(base + i, da);
-            sa.term(base + 15 + i, db);
-            sb.term(base + i, fp_add(fp_mul(not_bit, da), fp_mul(bit, fp_sub(nb0, na0))));
-            sb.term(base + 7 + i, fp_add(fp_mul(bit, fp_sub(ca, na7)), fp_mul(not_bit, fp_sub(nb7, na7))));
-            sb.term(base + 15 + i, fp_mul(not_bit, db));
-            sb.term(base + 22 + i, fp_mul(bit, fp_sub(cb, nb7)));
-        }
-        sa.flush<G0 | G1 | G2>(hash_copy, tot);
-        sb.flush<G0 | G1 | G2>(hash_init, tot);
-    }
-    sa.begin(); sb.begin();
-#pragma unroll CS_LINS_UNROLL_B
-    for (int i = 0; i < 7; i++) {
-        const fp nr = f.next(PREV_ROOT + i), cr = f.cur(PREV_ROOT + i);
-        sa.term(PREV_ROOT + i, fp_sub(nr, cr));
-        sb.term(PREV_ROOT + i, fp_sub(nr, f.next(R_UPD + i)));
-        sb.term(INT_ROOT_RES + i, fp_sub(f.cur(S_UPD + i), f.cur(R_INIT + i)));
-        sb.term(PREV_MATCH_RES + i, fp_sub(f.next(S_INIT + i), cr));
-    }
-    sa.flush<G4>(c_not(finish), tot);
-    sb.flush<G3 | G4>(finish, tot);
-}
-// schnorr linear parts, hash copy, range proofs (the boundary terms are added in k_split_finish)
-__device__ __forceinline__ void lin_c_split(const CS_CONST fp *coefs, const Frame &f, fp (&tot)[6]) {
-    const fp schnorr_mask = f.pv(P_SCHNORR), scalar_mult = f.pv(P_SCALAR_MULT), doubling = f.pv(P_DOUBLING), schnorr_hash = f.pv(P_SCHNORR_HASH);
-    const fp range_flag = f.pv(P_RANGE_STEP), range_finish = f.pv(P_RANGE_FINISH);
-    const fp copy_hash = fp_mul(c_not(schnorr_hash), schnorr_mask);
-    const fp final_add = fp_mul(c_not(scalar_mult), schnorr_mask);
-    const fp addition = fp_mul(c_not(doubling), scalar_mult);
-    SectionAcc s;
-    s.coefs = coefs;
-    s.begin(); // flags are part of the values here
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const fp dflag = f.pv(P_DIGEST + i);
-        const fp c = f.cur(41 - i), nx = f.next(41 - i);
-        s.term(41 - i, fp_add(fp_mul(fp_mul(dflag, doubling), fp_sub(nx, fp_add(fp_dbl(c), f.next(37)))), fp_mul(fp_mul(c_not(dflag), doubling), fp_sub(c, nx))));
-        s.term(38 + i, fp_add(fp_mul(addition, fp_sub(f.cur(38 + i), f.next(38 + i))), fp_mul(final_add, fp_sub(f.cur(38 + i), f.cur(42 + i)))));
-    }
-    // the bit registers of the curve gadgets (slots 18, 37: group 2), left out of the curve families: binary under `doubling`
-    // (ecc.rs:96), copied under `addition` (ecc.rs:136)
-    {
-        const fp b18 = f.cur(18), b37 = f.cur(37);
-        s.term(18, fp_add(fp_mul(doubling, c_is_binary(b18)), fp_mul(addition, fp_sub(b18, f.next(18)))));
-        s.term(37, fp_add(fp_mul(doubling, c_is_binary(b37)), fp_mul(addition, fp_sub(b37, f.next(37)))));
-    }
-    s.flush<G2>(FP_ONE, tot);
-    s.begin();
-#pragma unroll
-    for (int i = 0; i < 7; i++) {
-        s.term(42 + i, fp_sub(f.cur(42 + i), f.next(42 + i)));
-        fp inp = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int m = k * 7 + i;
-            const fp cell = m < 12 ? f.next(S_KEY + m) : m < 24 ? f.next(R_KEY + m - 12) : m == 24 ? f.next(DELTA_COPY) : m == 25 ? f.next(NONCE_COPY) : 0;
-            inp = fp_add(inp, fp_mul(f.pv(P_HASH_INTERNAL + k), cell));
-        }
-        s.term(49 + i, fp_sub(f.next(49 + i), inp));
-    }
-    s.flush<G2>(copy_hash, tot);
-    const fp db = f.next(DELTA_BIT), sbit = f.next(SIGMA_BIT);
-    s.begin();
-    s.term(DELTA_ACC, fp_sub(f.next(DELTA_ACC), fp_add(fp_dbl(f.cur(DELTA_ACC)), db)));
-    s.term(DELTA_BIT, c_is_binary(db));
-    s.term(SIGMA_ACC, fp_sub(f.next(SIGMA_ACC), fp_add(fp_dbl(f.cur(SIGMA_ACC)), sbit)));
-    s.term(SIGMA_BIT, c_is_binary(sbit));
-    s.flush<G2 | G3 | G4>(range_flag, tot);
-    const fp dr = fp_sub(f.next(DELTA_ACC), f.next(DELTA_COPY));
-    s.begin();
-    s.term(DELTA_RANGE_RES, dr);
-    s.term(SIGMA_RANGE_RES, dr);
-    s.flush<G4>(range_finish, tot);
-}
-// adds to the six polynomials of the first family (alpha, beta of groups 0..4): out = [6][4 even cosets][n].  grid = (n / FNT, 4)
-// (extension proofs: one launch per coefficient set `set`; these groups are cheap and bandwidth-bound, nothing is worth sharing)
-template <int PART>
-#ifndef CS_LIN_B_SPLIT_WAVES
-#define CS_LIN_B_SPLIT_WAVES 3 // measured 1.05 (4, 77 spilled registers) / 0.90 (3) / 0.99 ms (2)
-#endif
-#ifndef CS_LIN_C_SPLIT_WAVES
-#define CS_LIN_C_SPLIT_WAVES 2 // 3 (32 spilled registers) and 4 measured: no gain
-#endif
-__global__ __launch_bounds__(FNT, PART == PART_LIN_C ? CS_LIN_C_SPLIT_WAVES : PART == PART_LIN_B ? CS_LIN_B_SPLIT_WAVES : 4) void k_lin_split(CeParams p, fp *__restrict__ out, unsigned set) {
-    const size_t n = (size_t)1 << p.log_n;
-    const size_t j = blockIdx.x * (size_t)FNT + threadIdx.x;
-    const unsigned kc = (p.k0 >> 1) + blockIdx.y; // (k_rounds_split)
-    const Frame f = make_frame(p, 2 * blockIdx.y, j);
-    out += (size_t)set * SPLIT_TABLES * 4 * n;
-    const CS_CONST fp *coefs = as_const(p.coef + (size_t)set * CE_COEF_WORDS);
-    fp tot[6] = {0, 0, 0, 0, 0, 0};
-    if (PART == PART_LIN_A) lin_a_split(coefs, f, tot);
-    if (PART == PART_LIN_B) lin_b_split(coefs, f, tot);
-    if (PART == PART_LIN_C) lin_c_split(coefs, f, tot);
-    const fp xd1 = split_lift(p, 2 * kc, j);
-    // beta of groups 2, 3, 4 in one table: S_2 + x^(n-1) S_3 + x^(2n-2) S_4 (LIN_A only has alpha and group 4)
-    tot[3] = PART == PART_LIN_A ? fp_mul(fp_mul(xd1, xd1), tot[5]) : fp_add(tot[3], fp_mul(xd1, fp_add(tot[4], fp_mul(xd1, tot[5]))));
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const bool touched = PART == PART_LIN_A ? (q == 0 || q == 3) : true;
-        if (touched) {
-            fp *o = out + ((size_t)q * 4 + kc) * n + j;
-            *o = fp_add(*o, tot[q]);
-        }
-    }
-}
-
-// ---- the three linear groups in ONE pass over the frame (round 3) -------------------------------------------------------------------
-// k_lin_split<LIN_A>, <LIN_B>, <LIN_C> each walk the Merkle registers 0..57 (LIN_A their current rows for the setup constraints,
-// LIN_B current and next rows), LIN_A and LIN_C both read the next rows of the key / amount / nonce copies, and each launch does a
-// read-modify-write of the same four tables: 9.2 GB of counter traffic for 3.1 GB of distinct cells, at 3.4-5.4 TB/s (profiles/r02_v13).
-// Here every cell is loaded once where the groups overlap: the Merkle loop of LIN_B also feeds LIN_A's setup / copy sections (their
-// slots are all in degree group 4: two accumulators each) and the hash-input sums of LIN_C; the rest of LIN_B and LIN_C follows.  Same
-// terms, same coefficients, same flags -- the sums are exact, so the four polynomials are bit-identical (split == direct at 2^23 points,
-// proof bytes: tests/test_gpu_full_size.py).
+// ---- the three linear groups in ONE pass over the frame -----------------------------------------------------------------------------
+// The groups (LIN_A: setup and value copies, LIN_B: merkle::update without its rounds, LIN_C: Schnorr linear parts, hash copy, range
+// proofs; fused_linear_a / _b / _c above state them one by one) overlap in what they read: all three walk the Merkle registers 0..57 (LIN_A
+// their current rows, LIN_B current and next rows), LIN_A and LIN_C both read the next rows of the key / amount / nonce copies.  One
+// launch per group was 9.2 GB of counter traffic for 3.1 GB of distinct cells and three read-modify-writes of the same four tables
+// (profiles/r02_v13).  Here every cell is loaded once: the Merkle loop of LIN_B also feeds LIN_A's setup / copy sections (their slots
+// are all in degree group 4: two accumulators each) and the hash-input sums of LIN_C; the rest of LIN_B and LIN_C follows.  The sums are
+// exact, so the four polynomials equal the direct evaluation bit for bit (split == direct at 2^23 points, proof bytes:
+// tests/test_gpu_full_size.py).
 #ifndef CS_LIN_ALL_WAVES
 #define CS_LIN_ALL_WAVES 3
 #endif
@@ -2753,18 +2585,6 @@ hipError_t launch_lin_all(const CeParams &p, uint64_t *d_even_family0, hipStream
     for (unsigned set = 0; set < m; set++) {
         if (buf) hipLaunchKernelGGL(k_lin_all<true>, grid, block, 0, stream, p, d_even_family0, set);
         else hipLaunchKernelGGL(k_lin_all<false>, grid, block, 0, stream, p, d_even_family0, set);
-    }
-    return hipGetLastError();
-}
-hipError_t launch_lin_split(const CeParams &p, int part, uint64_t *d_even_family0, hipStream_t stream) {
-    const size_t n = (size_t)1 << p.log_n;
-    const dim3 grid((unsigned)(n / FNT), p.nkc ? p.nkc : 4), block(FNT);
-    const unsigned m = p.m ? p.m : 1;
-    for (unsigned set = 0; set < m; set++) {
-        if (part == PART_LIN_A) hipLaunchKernelGGL(k_lin_split<PART_LIN_A>, grid, block, 0, stream, p, d_even_family0, set);
-        else if (part == PART_LIN_B) hipLaunchKernelGGL(k_lin_split<PART_LIN_B>, grid, block, 0, stream, p, d_even_family0, set);
-        else if (part == PART_LIN_C) hipLaunchKernelGGL(k_lin_split<PART_LIN_C>, grid, block, 0, stream, p, d_even_family0, set);
-        else return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

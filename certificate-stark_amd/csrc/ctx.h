@@ -97,7 +97,7 @@ struct AssertInverseTable {
     uint64_t m, zc;
     uint64_t *tab;
 };
-// what cstark_air_combine needs of an AIR that does not change from proof to proof (capi.hip, air_combine_impl): keyed by
+// what cstark_air_combine needs of an AIR that does not change from proof to proof (capi.hip, get_air_static): keyed by
 // (AIR, items, trace length, blowup)
 struct AirCombineStatic {
     int air;
@@ -105,6 +105,33 @@ struct AirCombineStatic {
     AirCombineParams p;          // groups, coset powers, device pointers of the static tables; the per-call fields are patched in
     std::vector<uint32_t> t_grp; // degree group of every transition constraint (host copy)
     uint64_t *d_static;          // device: shifts[b] | a_reg | a_seq | a_grp | t_grp
+};
+// One request to the sub-AIR constraint stage (capi.hip, air_stage): the merged evaluations sum_i (alpha_i + beta_i x^adj_i) C_i(x) / Z(x)
+// plus the boundary terms of cosets [k0, k0 + nk) of the LDE domain into d_out [nk][n].  Filled by the stage's public entry points and by
+// the prover (prove.hip); all d_ pointers are device memory.
+enum class AirTransitions {
+    Materialised, // d_evals = [nk][n_constraints][n], what cstark_air_evaluate_transitions / cstark_schnorr_evaluate_transitions wrote
+    MerkleFused,  // MerkleAir's evaluator, Merkle depth merkle_depth
+    SchnorrFused, // SchnorrAir's evaluator over d_aux_lde, the extended public-input columns [nk][19][n]
+};
+struct AirStageRequest {
+    int air = 0;          // cstark_air_id
+    uint32_t n_items = 0; // SchnorrAir: signatures
+    uint32_t log_n = 0, log_blowup = 0, k0 = 0, nk = 0;
+    const uint64_t *d_lde = nullptr; // [nk][width][n]
+    uint64_t *d_out = nullptr;
+    AirTransitions source = AirTransitions::Materialised;
+    const uint64_t *d_evals = nullptr;
+    uint32_t merkle_depth = 0;
+    const uint64_t *d_aux_lde = nullptr;
+    bool own_extension = false; // SchnorrFused: d_lde and d_aux_lde extend columns of degree < n, which the degree-split form relies on
+    // the coefficients, one of two forms.  Host: four arrays ([n_constraints] x 2, [n_assertions] x 2) and the assertion values (null for an
+    // AIR with built-in constants).  Device (d_coefs != null, drawn there by the device-side channel): alpha[115] | beta[115] |
+    // b_alpha[na] | b_beta[na], and d_avalues (null: the built-in constants)
+    const uint64_t *t_alpha = nullptr, *t_beta = nullptr, *b_alpha = nullptr, *b_beta = nullptr, *assertion_values = nullptr;
+    const uint64_t *d_coefs = nullptr, *d_avalues = nullptr;
+    const uint64_t *d_avals_lde = nullptr; // [nk][n_avals][n]: extended value polynomials of the sequence assertions (SchnorrAir)
+    uint32_t n_avals = 0;
 };
 struct ProveArena; // prove.hip
 void prove_arena_free(ProveArena *a);
@@ -180,10 +207,8 @@ int tx_evaluate_constraints_sets(cstark_ctx *c, const uint64_t *d_lde, const cst
                                  uint64_t *const *d_outs, uint32_t merkle_depth, uint32_t log_n, uint32_t log_blowup, uint32_t k0, uint32_t nk,
                                  bool input_is_lde, const uint64_t *d_pub = nullptr);
 int tx_coef_device_block(cstark_ctx *c, uint64_t **d_coef);
-// internal (capi.hip): cstark_air_combine / the fused sub-AIR evaluators with coefficients (and assertion values) on the device
-int air_combine_dev(cstark_ctx *c, int air, uint32_t n_items, int mode, uint32_t merkle_depth, const uint64_t *d_lde, const uint64_t *d_evals,
-                    const uint64_t *d_aux_lde, const uint64_t *d_coefs, const uint64_t *d_avalues, const uint64_t *d_avals_lde, uint32_t n_avals, uint64_t *d_out,
-                    uint32_t log_n, uint32_t log_blowup, uint32_t nk);
+// internal (capi.hip): the sub-AIR constraint stage behind cstark_air_combine and the fused sub-AIR evaluators
+int air_stage(cstark_ctx *c, const cs::AirStageRequest &rq);
 // internal (capi.hip): one rank's share of the degree-split evaluation of a proof sharded by LDE coset.  d_lde: the rank's cosets
 // [k0, k0 + nk) (k0 even, nk = 2 or 4) of its own extension; d_coeffs: the 94 coefficient columns (register 37 is extended to all
 // cosets here: the recombination reads it on cosets the rank does not hold).  d_out [nk / 2 + 4][n]: merged evaluations of the rank's

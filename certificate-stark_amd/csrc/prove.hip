@@ -1069,24 +1069,38 @@ int tx_combine_sets(cstark_ctx *c, ProveArena *a, AirJob &job, unsigned m, const
 }
 // The sub-AIRs are evaluated on their constraint-evaluation domain -- blowup 2^log_ce: MerkleAir 4, RangeProofAir 2 -- which is block 0 of
 // the trace table whatever the blowup factor of the proof: a plain [ce][width][n] extension with the domain offset.
+// The request to the sub-AIR stage (ctx.h) for this proof's table, with the coefficients where the channel drew them: on the device
+// (job.d_coefs, job.d_avalues) or the host's four arrays and the AIR's assertion values.  The caller adds the source of the transition sum.
+cs::AirStageRequest air_request(ProveArena *a, const AirJob &job, const uint64_t *ta, const uint64_t *tb, const uint64_t *ba, const uint64_t *bb,
+                                const uint64_t *assertion_values, uint64_t *out) {
+    cs::AirStageRequest rq;
+    rq.air = job.air; rq.n_items = job.air == CSTARK_AIR_SCHNORR ? job.item : 0;
+    rq.log_n = job.log_n; rq.log_blowup = job.log_ce; rq.k0 = 0; rq.nk = 1u << job.log_ce;
+    rq.d_lde = a->lde; rq.d_out = out;
+    // (job.d_avalues is null for SchnorrAir, whose assertion constants are built in: prove_core_dev sets it beside job.d_coefs)
+    if (job.d_coefs) { rq.d_coefs = job.d_coefs; rq.d_avalues = job.d_avalues; }
+    else { rq.t_alpha = ta; rq.t_beta = tb; rq.b_alpha = ba; rq.b_beta = bb; rq.assertion_values = assertion_values; }
+    return rq;
+}
+// RangeProofAir and RescueAir: the transition values are materialised once per proof (an extension proof merges them with each of its m
+// coefficient sets), then merged
+int materialise_and_merge(cstark_ctx *c, ProveArena *a, AirJob &job, cs::AirStageRequest rq) {
+    uint64_t *evals;
+    RC_TRY(arena_extra(c, a, 0, &evals, ((size_t)rq.nk * job.n_constraints << job.log_n) * 8));
+    if (!job.evals_ready) RC_TRY(cstark_air_evaluate_transitions(c, job.air, a->lde, evals, 0, job.log_n, rq.log_blowup, 0, rq.nk));
+    job.evals_ready = true;
+    rq.source = cs::AirTransitions::Materialised; rq.d_evals = evals;
+    return air_stage(c, rq);
+}
 // ---- MerkleAir (src/merkle/update) ---------------------------------------------------------------------------------------------
 int merkle_build(cstark_ctx *c, ProveArena *a, AirJob &job) {
     RC_TRY(cstark_merkle_build_trace(c, a->trace));
     return gather_roots(c, a, job);
 }
 int merkle_combine(cstark_ctx *c, ProveArena *a, AirJob &job, const uint64_t *ta, const uint64_t *tb, const uint64_t *ba, const uint64_t *bb, uint64_t *out) {
-    const size_t n = (size_t)1 << job.log_n;
-    const uint32_t log_ce = job.log_ce, ce = 1u << log_ce;
-    // CSTARK_MERKLE_FUSED=0 (tuning / debugging): materialise the 106 transition values and merge them generically
-    static const bool fused = [] { const char *e = getenv("CSTARK_MERKLE_FUSED"); return !e || atoi(e) != 0; }();
-    if (fused && job.d_coefs) return air_combine_dev(c, CSTARK_AIR_MERKLE_UPDATE, 0, 1, job.item, a->lde, nullptr, nullptr, job.d_coefs, job.d_avalues, nullptr, 0, out, job.log_n, log_ce, ce);
-    if (fused) return cstark_merkle_evaluate_constraints(c, job.item, a->lde, ta, tb, ba, bb, job.pub.data(), out, job.log_n, log_ce, 0, ce);
-    uint64_t *evals;
-    RC_TRY(arena_extra(c, a, 0, &evals, (size_t)ce * job.n_constraints * n * 8));
-    if (!job.evals_ready) RC_TRY(cstark_air_evaluate_transitions(c, CSTARK_AIR_MERKLE_UPDATE, a->lde, evals, job.item, job.log_n, log_ce, 0, ce));
-    job.evals_ready = true;
-    if (job.d_coefs) return air_combine_dev(c, CSTARK_AIR_MERKLE_UPDATE, 0, 0, 0, a->lde, evals, nullptr, job.d_coefs, job.d_avalues, nullptr, 0, out, job.log_n, log_ce, ce);
-    return cstark_air_combine(c, CSTARK_AIR_MERKLE_UPDATE, 0, a->lde, evals, ta, tb, ba, bb, job.pub.data(), nullptr, 0, out, job.log_n, log_ce, 0, ce);
+    cs::AirStageRequest rq = air_request(a, job, ta, tb, ba, bb, job.pub.data(), out);
+    rq.source = cs::AirTransitions::MerkleFused; rq.merkle_depth = job.item;
+    return air_stage(c, rq);
 }
 // ---- RangeProofAir (src/range) -------------------------------------------------------------------------------------------------------
 int range_build(cstark_ctx *c, ProveArena *a, AirJob &job) {
@@ -1098,15 +1112,8 @@ int range_build(cstark_ctx *c, ProveArena *a, AirJob &job) {
     return cstark_range_build_trace(c, job.number, a->trace);
 }
 int range_combine(cstark_ctx *c, ProveArena *a, AirJob &job, const uint64_t *ta, const uint64_t *tb, const uint64_t *ba, const uint64_t *bb, uint64_t *out) {
-    const size_t n = (size_t)1 << job.log_n;
-    const uint32_t log_ce = job.log_ce, ce = 1u << log_ce;
-    uint64_t *evals;
-    RC_TRY(arena_extra(c, a, 0, &evals, (size_t)ce * job.n_constraints * n * 8));
-    if (!job.evals_ready) RC_TRY(cstark_air_evaluate_transitions(c, CSTARK_AIR_RANGE, a->lde, evals, job.item, job.log_n, log_ce, 0, ce));
-    job.evals_ready = true;
-    if (job.d_coefs) return air_combine_dev(c, CSTARK_AIR_RANGE, 0, 0, 0, a->lde, evals, nullptr, job.d_coefs, job.d_avalues, nullptr, 0, out, job.log_n, log_ce, ce);
     const uint64_t vals[2] = {0, job.number}; // get_assertions, src/range/air.rs:79-86
-    return cstark_air_combine(c, CSTARK_AIR_RANGE, 0, a->lde, evals, ta, tb, ba, bb, vals, nullptr, 0, out, job.log_n, log_ce, 0, ce);
+    return materialise_and_merge(c, a, job, air_request(a, job, ta, tb, ba, bb, vals, out));
 }
 // ---- RescueAir (benches/rescue.rs:145-356) ---------------------------------------------------------------------------------------------
 int rescue_build(cstark_ctx *c, ProveArena *a, AirJob &job) {
@@ -1114,14 +1121,7 @@ int rescue_build(cstark_ctx *c, ProveArena *a, AirJob &job) {
     return gather_roots(c, a, job, 0); // get_pub_inputs :331-354: seed and result are the first / last row of registers 0..6
 }
 int rescue_combine(cstark_ctx *c, ProveArena *a, AirJob &job, const uint64_t *ta, const uint64_t *tb, const uint64_t *ba, const uint64_t *bb, uint64_t *out) {
-    const size_t n = (size_t)1 << job.log_n;
-    const uint32_t log_ce = job.log_ce, ce = 1u << log_ce;
-    uint64_t *evals;
-    RC_TRY(arena_extra(c, a, 0, &evals, (size_t)ce * job.n_constraints * n * 8));
-    if (!job.evals_ready) RC_TRY(cstark_air_evaluate_transitions(c, CSTARK_AIR_RESCUE_CHAIN, a->lde, evals, 0, job.log_n, log_ce, 0, ce));
-    job.evals_ready = true;
-    if (job.d_coefs) return air_combine_dev(c, CSTARK_AIR_RESCUE_CHAIN, 0, 0, 0, a->lde, evals, nullptr, job.d_coefs, job.d_avalues, nullptr, 0, out, job.log_n, log_ce, ce);
-    return cstark_air_combine(c, CSTARK_AIR_RESCUE_CHAIN, 0, a->lde, evals, ta, tb, ba, bb, job.pub.data(), nullptr, 0, out, job.log_n, log_ce, 0, ce);
+    return materialise_and_merge(c, a, job, air_request(a, job, ta, tb, ba, bb, job.pub.data(), out));
 }
 // ---- SchnorrAir (src/schnorr) ---------------------------------------------------------------------------------------------------------
 // the public-input columns (src/schnorr/air.rs:228-290; not committed: both sides derive them from the messages) and the sequence
@@ -1161,21 +1161,13 @@ int schnorr_build(cstark_ctx *c, ProveArena *a, AirJob &job) {
     return CSTARK_OK;
 }
 int schnorr_combine(cstark_ctx *c, ProveArena *a, AirJob &job, const uint64_t *ta, const uint64_t *tb, const uint64_t *ba, const uint64_t *bb, uint64_t *out) {
-    const size_t n = (size_t)1 << job.log_n;
-    // CSTARK_SCHNORR_FUSED=0 (tuning / debugging): materialise the 56 transition values and merge them generically
-    static const bool fused = [] { const char *e = getenv("CSTARK_SCHNORR_FUSED"); return !e || atoi(e) != 0; }();
-    uint64_t *evals = nullptr, *aux_lde, *av_lde;
-    if (!fused) RC_TRY(arena_extra(c, a, 0, &evals, 8 * (size_t)job.n_constraints * n * 8));
+    uint64_t *aux_lde, *av_lde;
     RC_TRY(schnorr_public_columns(c, a, job, &aux_lde, &av_lde, !job.public_ready)); // once per proof, in schnorr_build when it overlaps
     job.public_ready = true;
-    if (!job.evals_ready) { // once per proof (extension proofs merge with m coefficient sets)
-        if (!fused) RC_TRY(cstark_schnorr_evaluate_transitions(c, a->lde, aux_lde, evals, job.log_n, 3, 0, 8));
-        job.evals_ready = true;
-    }
-    if (fused && job.d_coefs) return air_combine_dev(c, CSTARK_AIR_SCHNORR, job.item, 2, 0, a->lde, nullptr, aux_lde, job.d_coefs, nullptr, av_lde, 12, out, job.log_n, 3, 8);
-    if (fused) return cstark_schnorr_evaluate_constraints_lde(c, job.item, a->lde, aux_lde, ta, tb, ba, bb, av_lde, 12, out, job.log_n); // own extensions: split form
-    if (job.d_coefs) return air_combine_dev(c, CSTARK_AIR_SCHNORR, job.item, 0, 0, a->lde, evals, nullptr, job.d_coefs, nullptr, av_lde, 12, out, job.log_n, 3, 8);
-    return cstark_air_combine(c, CSTARK_AIR_SCHNORR, job.item, a->lde, evals, ta, tb, ba, bb, nullptr, av_lde, 12, out, job.log_n, 3, 0, 8);
+    cs::AirStageRequest rq = air_request(a, job, ta, tb, ba, bb, nullptr, out); // (built-in assertion constants)
+    rq.source = cs::AirTransitions::SchnorrFused; rq.d_aux_lde = aux_lde; rq.own_extension = true; // own extensions: split form
+    rq.d_avals_lde = av_lde; rq.n_avals = 12;
+    return air_stage(c, rq);
 }
 
 // one proof on this GPU, on the channel its options allow

@@ -73,7 +73,7 @@ def test_state_transition_2_20_end_to_end(oracle, backend):
     cf = oracle.make_coeffs(2024)
     pub = np.concatenate([w.initial_roots[0][:2], w.final_root[:2]])
     comb = backend.evaluate_constraints(lde, cf, pub, w.depth)                       # [8][n], coset-major
-    # the degree-split evaluation the prover and the benchmark use (k_rounds_split / k_ec_split / k_lin_split / k_split_finish):
+    # the degree-split evaluation the prover and the benchmark use (k_rounds_split / k_ec_split / k_lin_all / k_split_finish):
     # on this table -- a genuine extension -- it must give the direct evaluator's values bit for bit, at all 2^23 points
     comb_split = backend.evaluate_constraints(lde, cf, pub, w.depth, input_is_lde=True)
     assert torch.equal(comb, comb_split)

@@ -104,6 +104,17 @@ def test_writer_and_parser_share_one_layout(golden, tmp_path):
     assert out.returncode == 0 and out.stdout.startswith("ok") and "golden proof rewritten byte for byte" in out.stdout, out.stdout + out.stderr
 
 
+def test_air_groups_match_the_shapes(tmp_path):
+    """csrc/air_groups.h alone (g++, host code only): the degree and divisor groups and the per-coset powers that the generic merge of
+    the sub-AIRs works from, against each AIR's shape stated directly; shapes with too many groups are refused
+    (tests/cpp/air_groups_check.cpp)."""
+    import subprocess
+    exe = str(tmp_path / "air_groups_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-o", exe, os.path.join(ROOT, "tests", "cpp", "air_groups_check.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("ok: 18 groupings checked"), out.stdout + out.stderr
+
+
 @pytest.fixture(scope="module")
 def transcript_check(tmp_path_factory):
     """tests/cpp/transcript_check.cpp: csrc/transcript.h and csrc/proof_layout.h alone under g++ (host code only)"""
