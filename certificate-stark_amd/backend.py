@@ -534,6 +534,13 @@ class Backend:
         check(self.lib.cstark_prove_stage_ms(self.ctx, ms))
         return dict(zip(self.PROVE_STAGES, [float(v) for v in ms]))
 
+    def prove_channel(self):
+        """cstark_prove_channel: "device" when the Fiat-Shamir channel of the last proof ran on the GPU (the host waited once), "host" when
+        the host absorbed and drew between the stages (Sha3 coin, proof of work, sharded proofs, CSTARK_HOST_CHANNEL=1)"""
+        ch = C.c_uint32(0)
+        check(self.lib.cstark_prove_channel(self.ctx, C.byref(ch)))
+        return ("host", "device")[ch.value]
+
     # ---- verification (cstark_tx_verify) ---------------------------------------------------------------------------------------
     def tx_verify(self, proofs, initial_roots, final_roots, options=None):
         """TransactionExample::verify for a list of proofs (bytes) or a ProofBatch, in one call.  initial_roots / final_roots: [count][7]

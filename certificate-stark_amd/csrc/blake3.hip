@@ -220,6 +220,46 @@ __global__ __launch_bounds__(64) void k_fri_coin(uint32_t *__restrict__ seed, co
     }
     if (quad == 0) { seed[c] = s_lo; seed[4 + c] = s_hi; }
 }
+// The same coin for a folding point of the degree-m extension (m = 2, 3): after the reseed, the first m accepted candidates in counter
+// order are the components alpha_out[0 .. m).  One wave, sixteen counters a pass; an accepted candidate's place is its rank among the
+// pass's accepted ones behind those of the earlier passes.
+__global__ __launch_bounds__(64) void k_fri_coin_ext(uint32_t *__restrict__ seed, const uint8_t *__restrict__ root, uint64_t *__restrict__ alpha_out,
+                                                     uint32_t *__restrict__ root_out, uint32_t m) {
+    __shared__ uint32_t msg[16][16];
+    const unsigned tid = threadIdx.x, quad = tid >> 2, c = tid & 3;
+    uint32_t sched[7];
+#pragma unroll
+    for (int r = 0; r < 7; r++) sched[r] = c_quad_sched[c][r];
+    const uint32_t *rw = reinterpret_cast<const uint32_t *>(root);
+    const uint32_t r_lo = rw[c], r_hi = rw[4 + c];
+    if (quad == 0) { root_out[c] = r_lo; root_out[4 + c] = r_hi; }
+    uint32_t *mb = msg[quad];
+    mb[c] = seed[c]; mb[4 + c] = seed[4 + c]; mb[8 + c] = r_lo; mb[12 + c] = r_hi;
+    __builtin_amdgcn_wave_barrier();
+    uint32_t s_lo, s_hi;
+    quad_hash64(mb, sched, c, s_lo, s_hi);
+    __builtin_amdgcn_wave_barrier();
+    uint64_t counter = CSTARK_CONV_COIN_FIRST_COUNTER;
+    uint32_t got = 0; // uniform: accepted so far
+    for (int pass = 0; pass < 1024 && got < m; pass++) {
+        const uint64_t ctr = counter + quad;
+        mb[c] = s_lo; mb[4 + c] = s_hi;
+        mb[8 + c] = c == 0 ? (uint32_t)ctr : c == 1 ? (uint32_t)(ctr >> 32) : 0u;
+        mb[12 + c] = 0;
+        __builtin_amdgcn_wave_barrier();
+        uint32_t lo, hi;
+        quad_hash_block(mb, sched, c, 40u, lo, hi);
+        __builtin_amdgcn_wave_barrier();
+        const uint64_t v = (uint64_t)__shfl(lo, (int)(quad * 4)) | (uint64_t)__shfl(lo, (int)(quad * 4 + 1)) << 32;
+        const bool ok = (!CSTARK_CONV_COIN_REJECT_ABOVE_P || v < FP_P) && c == 0;
+        const uint64_t votes = __ballot(ok);
+        const uint32_t at = got + (uint32_t)__popcll(votes & ((1ull << tid) - 1));
+        if (ok && at < m) alpha_out[at] = fp_from_u64(v);
+        got += (uint32_t)__popcll(votes);
+        counter += 16;
+    }
+    if (quad == 0) { seed[c] = s_lo; seed[4 + c] = s_hi; }
+}
 // Workgroup w reduces the parents [cnt + P0 w, cnt + P0 (w + 1)), P0 = min(cnt, 256), through `levels` levels (P0 >> (levels - 1) >= 1).
 // cnt: a power of two; grid = cnt / P0.
 __global__ __launch_bounds__(1024) void k_merkle_quad(uint8_t *__restrict__ nodes, size_t cnt, int levels) {
@@ -363,6 +403,11 @@ hipError_t grind_batch_chunk(const uint32_t *d_seeds, unsigned batch, uint64_t b
 }
 hipError_t fri_coin(uint32_t *d_seed, const uint8_t *d_root, uint64_t *d_alpha, uint32_t *d_root_out, hipStream_t stream) {
     hipLaunchKernelGGL(k_fri_coin, dim3(1), dim3(64), 0, stream, d_seed, d_root, d_alpha, d_root_out);
+    return hipGetLastError();
+}
+hipError_t fri_coin_ext(uint32_t *d_seed, const uint8_t *d_root, uint64_t *d_alpha, uint32_t *d_root_out, unsigned m, hipStream_t stream) {
+    if (m != 2 && m != 3) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_fri_coin_ext, dim3(1), dim3(64), 0, stream, d_seed, d_root, d_alpha, d_root_out, m);
     return hipGetLastError();
 }
 hipError_t merkle_build(uint8_t *d_nodes, unsigned log_leaves, hipStream_t stream) {

@@ -690,15 +690,22 @@ int cstark_evaluate_polys_at_ext(cstark_ctx *c, const uint64_t *d_coeffs, uint32
 }
 } // extern "C"
 
-// internal (ctx.h): one FRI layer's coin on the device (Blake3 coin: reseed with the layer root at d_root, draw the folding point) and the
-// fold with that point; d_state = [seed: 8 words][alpha: one element per layer][roots: 8 words per layer]
+// internal (ctx.h): one FRI layer's coin on the device (Blake3 coin: reseed with the layer root at d_root, draw the folding point: m words
+// at d_alpha) and the fold with that point; d_evals: [m][2^log_n] component-major
 int fri_coin_fold_dev(cstark_ctx *c, uint32_t *d_seed, const uint8_t *d_root, uint64_t *d_alpha, uint32_t *d_root_out, const uint64_t *d_evals,
-                      uint64_t *d_out, uint32_t log_n, uint32_t log_f, uint64_t domain_offset) {
+                      uint64_t *d_out, uint32_t log_n, uint32_t log_f, uint64_t domain_offset, uint32_t m) {
     if (log_n < cs::NTT_MIN_LOG_N || log_n > cs::NTT_MAX_LOG_N) return fail(CSTARK_ERR_UNSUPPORTED, "layer size must be 2^6 .. 2^24");
+    if (m < 1 || m > 3) return fail(CSTARK_ERR_INVALID_ARG, "fri_coin_fold_dev: bad extension degree");
     const NttPlan *p;
     RC_TRY(get_plan(c, log_n, &p));
-    HIP_TRY(cs::fri_coin(d_seed, d_root, d_alpha, d_root_out, c->stream));
-    HIP_TRY(cs::fri_fold(d_evals, d_out, log_n, log_f, p->winv, cs::host::inv(domain_offset), 0, cs::host::inv(cs::host::from_u64(1ull << log_f)), c->stream, d_alpha));
+    const uint64_t offset_inv = cs::host::inv(domain_offset), inv_f = cs::host::inv(cs::host::from_u64(1ull << log_f));
+    if (m == 1) {
+        HIP_TRY(cs::fri_coin(d_seed, d_root, d_alpha, d_root_out, c->stream));
+        HIP_TRY(cs::fri_fold(d_evals, d_out, log_n, log_f, p->winv, offset_inv, 0, inv_f, c->stream, d_alpha));
+    } else {
+        HIP_TRY(cs::fri_coin_ext(d_seed, d_root, d_alpha, d_root_out, m, c->stream));
+        HIP_TRY(cs::fri_fold_ext(d_evals, d_out, log_n, log_f, p->winv, offset_inv, nullptr, m, inv_f, c->stream, d_alpha));
+    }
     return CSTARK_OK;
 }
 // internal (ctx.h): row hashes of a whole table whose cosets are in block order (blake3.h, lde_coset_slot): leaf b j + k = row j of LDE coset k
@@ -753,6 +760,63 @@ int ood_frames_dev(cstark_ctx *c, const uint64_t *d_coeffs, uint32_t width, cons
     uint64_t *d_scr = (uint64_t *)c->desc_buf;
     HIP_TRY(cs::poly_eval(d_coeffs, width, log_n, d_pts, 2, d_out, d_scr, c->stream));
     HIP_TRY(cs::poly_eval(d_ccoef, n_comp, log_n, d_pts + 2, 1, d_out + 2 * (size_t)width, d_scr + scr_t, c->stream));
+    return CSTARK_OK;
+}
+// internal (ctx.h): the context's device scratch block (c->desc_buf) with room for `bytes`.  A prover that must not allocate between
+// its launches reserves the largest request of its stages first (ood_frames_dev_scratch_bytes).
+int desc_reserve(cstark_ctx *c, size_t bytes) {
+    if (bytes <= c->desc_bytes) return CSTARK_OK;
+    if (c->desc_buf) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->desc_buf)); c->desc_buf = nullptr; c->desc_bytes = 0; }
+    HIP_TRY(hipMalloc(&c->desc_buf, bytes));
+    c->desc_bytes = bytes;
+    return CSTARK_OK;
+}
+// scratch of ood_frames_dev (m = 1) / ood_frames_dev_ext (m = 2, 3): the segment sums of the three evaluations, and the raw values of
+// the m n_comp component columns (m-tuples) for m > 1
+static size_t ood_scratch_words(uint32_t width, uint32_t n_comp, uint32_t log_n, uint32_t m, size_t *scr_t, size_t *scr_c) {
+    if (m == 1) { *scr_t = cs::poly_eval_scratch_words(width, log_n, 2); *scr_c = cs::poly_eval_scratch_words(n_comp, log_n, 1); return *scr_t + *scr_c; }
+    *scr_t = cs::poly_eval_ext_scratch_words(width, log_n, m); *scr_c = cs::poly_eval_ext_scratch_words(m * n_comp, log_n, m);
+    return 2 * *scr_t + *scr_c + (size_t)m * m * n_comp;
+}
+size_t ood_frames_dev_scratch_bytes(uint32_t width, uint32_t n_comp, uint32_t log_n, uint32_t m) {
+    size_t scr_t, scr_c;
+    return ood_scratch_words(width, n_comp, log_n, m, &scr_t, &scr_c) * 8;
+}
+// internal (ctx.h): the frame of an extension-field proof with the point and the values staying on the device.  d_pts = z | z w | z^b
+// (m-tuples, where channel.hip wrote them); d_out = T(z)[width] | T(z w)[width] | H_i(z^b)[n_comp], m-tuples: what the host channel
+// computes with three cstark_evaluate_polys_at_ext calls and a recombination of the composition columns' components on the host.
+int ood_frames_dev_ext(cstark_ctx *c, const uint64_t *d_coeffs, uint32_t width, const uint64_t *d_ccoef, uint32_t n_comp, uint32_t log_n, uint32_t m,
+                       const uint64_t *d_pts, uint64_t *d_out) {
+    if (!c || !d_coeffs || !d_ccoef || !d_pts || !d_out || width == 0 || n_comp == 0 || (m != 2 && m != 3)) return fail(CSTARK_ERR_INVALID_ARG, "ood_frames_dev_ext: bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    size_t scr_t, scr_c;
+    RC_TRY(desc_reserve(c, ood_scratch_words(width, n_comp, log_n, m, &scr_t, &scr_c) * 8));
+    uint64_t *d_scr = (uint64_t *)c->desc_buf, *d_raw = d_scr + 2 * scr_t + scr_c;
+    const size_t mw = (size_t)m * width;
+    HIP_TRY(cs::poly_eval_ext(d_coeffs, width, log_n, nullptr, m, d_out, d_scr, c->stream, d_pts));
+    HIP_TRY(cs::poly_eval_ext(d_coeffs, width, log_n, nullptr, m, d_out + mw, d_scr + scr_t, c->stream, d_pts + m));
+    HIP_TRY(cs::poly_eval_ext(d_ccoef, m * n_comp, log_n, nullptr, m, d_raw, d_scr + 2 * scr_t, c->stream, d_pts + 2 * m));
+    HIP_TRY(cs::ood_recombine_ext(d_raw, d_out + 2 * mw, n_comp, m, c->stream));
+    return CSTARK_OK;
+}
+// internal (ctx.h): the quotient sums of an extension-field proof on the first nk cosets, d_out = [m][nk][n], from values that never
+// left the device: d_coef = alpha[width] | beta[width] | delta[n_comp], d_ood = the frame, d_scal = z | z w | z^b | deg_a | deg_b (5 m of
+// its 8 m words; the three constants k1, k2, k3 are computed into the rest here), d_shifts = the coset offsets.  No upload, no wait.
+int deep_composition_ext_dev(cstark_ctx *c, const uint64_t *d_trace_lde, const uint64_t *d_comp_lde, uint32_t width, uint32_t n_comp, uint32_t m,
+                             const uint64_t *d_coef, const uint64_t *d_ood, uint64_t *d_scal, const uint64_t *d_shifts, uint64_t *d_out, uint32_t log_n,
+                             uint32_t log_blowup, uint32_t nk) {
+    if (!c || !d_trace_lde || !d_comp_lde || !d_coef || !d_ood || !d_scal || !d_shifts || !d_out || width == 0 || n_comp == 0 || (m != 2 && m != 3))
+        return fail(CSTARK_ERR_INVALID_ARG, "deep_composition_ext_dev: bad argument");
+    if (log_n < cs::NTT_MIN_LOG_N || log_n > cs::NTT_MAX_LOG_N || log_blowup > 6 || nk == 0 || nk > (1u << log_blowup)) return fail(CSTARK_ERR_INVALID_ARG, "bad domain parameters");
+    HIP_TRY(hipSetDevice(c->device));
+    const NttPlan *plan;
+    RC_TRY(get_plan(c, log_n, &plan));
+    HIP_TRY(cs::deep_ext_consts(d_coef, d_ood, d_scal, width, n_comp, m, c->stream));
+    cs::DeepExtParams p{};
+    p.trace_lde = d_trace_lde; p.comp_lde = d_comp_lde; p.w = plan->w; p.coef = d_coef; p.shifts = d_shifts; p.out = d_out; p.scal = d_scal;
+    p.width = width; p.nb = n_comp; p.log_n = log_n; p.log_b = log_blowup; p.m = m;
+    p.nk = nk == (1u << log_blowup) ? 0 : nk;
+    HIP_TRY(cs::deep_composition_ext(p, c->stream));
     return CSTARK_OK;
 }
 // internal (ctx.h): the first nk cosets only, d_out = [m][nk][n]
@@ -911,8 +975,8 @@ static int ensure_coef_buf(cstark_ctx *c) {
     if (!c->coef_buf) HIP_TRY(hipMalloc((void **)&c->coef_buf, (TX_COEF_WORDS + (size_t)cs::CE_MAX_SETS * cs::CE_RTAB_WORDS) * 8));
     return CSTARK_OK;
 }
-// internal (ctx.h): the context's device block of composition coefficients (cstark_tx_coeffs layout, one set): the device-side channel
-// draws them there, tx_evaluate_constraints_sets(coeffs = null) reads them
+// internal (ctx.h): the context's device block of composition coefficients (cstark_tx_coeffs layout, CE_MAX_SETS sets CE_COEF_WORDS words
+// apart): the device-side channel draws them there, tx_evaluate_constraints_sets(coeffs = null) reads them
 int tx_coef_device_block(cstark_ctx *c, uint64_t **d_coef) {
     HIP_TRY(hipSetDevice(c->device));
     RC_TRY(ensure_coef_buf(c));
@@ -1077,16 +1141,16 @@ int tx_even_cosets(const cs::CeParams &p, uint64_t *even, size_t n, hipStream_t 
 int tx_evaluate_constraints_sets(cstark_ctx *c, const uint64_t *d_lde, const cstark_tx_coeffs *coeffs, uint32_t m, const uint64_t pub_inputs[4],
                                  uint64_t *const *d_outs, uint32_t merkle_depth, uint32_t log_n, uint32_t log_blowup, uint32_t k0, uint32_t nk,
                                  bool input_is_lde, const uint64_t *d_pub) {
-    // coeffs == null: one coefficient set already in the context's device block (tx_coef_device_block); d_pub != null: the 14 public
-    // inputs on the device instead of pub_inputs (both: the device-side channel of prove.hip)
-    if ((!coeffs && m != 1) || (!pub_inputs && !d_pub) || !d_outs) return fail(CSTARK_ERR_INVALID_ARG, "cstark_tx_evaluate_constraints: null argument");
+    // coeffs == null: the m coefficient sets are already in the context's device block (tx_coef_device_block: set q at CE_COEF_WORDS q);
+    // d_pub != null: the 14 public inputs on the device instead of pub_inputs (both: the device-side channel of prove.hip)
+    if ((!pub_inputs && !d_pub) || !d_outs) return fail(CSTARK_ERR_INVALID_ARG, "cstark_tx_evaluate_constraints: null argument");
     if (m < 1 || m > (uint32_t)cs::CE_MAX_SETS) return fail(CSTARK_ERR_INVALID_ARG, "cstark_tx_evaluate_constraints: 1..3 coefficient sets");
     for (uint32_t q = 1; q < m; q++)
         if (!d_outs[q]) return fail(CSTARK_ERR_INVALID_ARG, "cstark_tx_evaluate_constraints: null output");
     cs::CeParams p;
     RC_TRY(ce_params(c, d_lde, d_outs[0], merkle_depth, log_n, log_blowup, k0, nk, &p));
     if (coeffs) RC_TRY(upload_coeffs(c, coeffs, m, p));
-    else { RC_TRY(ensure_coef_buf(c)); p.coef = c->coef_buf; p.rtab = c->coef_buf + TX_COEF_WORDS; p.m = 1; }
+    else { RC_TRY(ensure_coef_buf(c)); p.coef = c->coef_buf; p.rtab = c->coef_buf + TX_COEF_WORDS; p.m = m; }
     for (uint32_t q = 1; q < m; q++) p.out_ext[q - 1] = d_outs[q];
     for (int i = 0; i < 4; i++) p.pub[i] = pub_inputs ? pub_inputs[i] : 0;
     p.pubd = d_pub;

@@ -18,13 +18,15 @@ enum ChanAbsorb : uint32_t {
 };
 enum ChanDraw : uint32_t {
     CHAN_DRAW_NONE = 0,
-    // field elements in memory form.  Where draw i goes:
-    CHAN_DRAW_LINEAR = 1,  // out[i]
+    // field elements in memory form.  An element is m consecutive draws (ChanStep::m words: 1 base field, 2 quadratic, 3 cubic
+    // extension); `count` counts elements.  Where component q of element i goes (m = 1: q = 0):
+    CHAN_DRAW_LINEAR = 1,  // out[m i + q]
     CHAN_DRAW_COEFFS = 2,  // (alpha, beta) pairs of a transition constraints then b assertions -> alpha[i] at out[i], beta[i] at
-                           // out[stride + i], assertion alphas at out[2 stride + i], betas at out[2 stride + b + i]  (cstark_tx_coeffs)
+                           // out[stride + i], assertion alphas at out[2 stride + i], betas at out[2 stride + b + i]  (cstark_tx_coeffs);
+                           // component q: the same places of coefficient set q, out + q set_stride
     CHAN_DRAW_DEEP = 3,    // per register `per` draws (alpha, beta, unused...), then b composition columns, then two: alpha[a] | beta[a] |
-                           // delta[b] at out, the two degree-adjustment coefficients at out2[3], out2[4]
-    CHAN_DRAW_POINT = 4,   // one draw z -> out[0] = z, out[1] = z w, out[2] = z^e (w, e below); also out2[0..3) = the same (DEEP scalars)
+                           // delta[b] at out (m-tuples), the two degree-adjustment coefficients at out2[3 m .. 5 m)
+    CHAN_DRAW_POINT = 4,   // one element z -> out = z | z w | z^e (w, e below; m-tuples); also out2[0 .. 3 m) = the same (DEEP scalars)
     CHAN_DRAW_QUERIES = 5  // `count` distinct integers below 2^log_domain -> positions; then their folded positions layer by layer
 };
 
@@ -36,6 +38,7 @@ struct ChanStep {
     const uint64_t *pub;
     struct { uint32_t kind, count; const void *ptr; uint64_t value; uint8_t *copy_out; } absorb[3]; // in order; copy_out: the 32-byte digest absorbed (or null)
     uint32_t draw, count, a, b, stride, per;
+    uint32_t m, set_stride;    // words per drawn element, 1..3; CHAN_DRAW_COEFFS: words between two coefficient sets
     uint64_t *out, *out2;
     uint64_t w;                // CHAN_DRAW_POINT: w_n (memory form); e = b
     // CHAN_DRAW_QUERIES: positions -> pos[0..count); layer l < n_layers: the distinct values of (previous list mod 2^(log_domain - (l + 1) log_f)), first
@@ -43,7 +46,9 @@ struct ChanStep {
     uint32_t log_domain, log_f, n_layers, slot;
     uint32_t *pos, *cnt;
 };
-// one workgroup of 1024 threads
+// one workgroup of 1024 threads.  hipErrorInvalidValue (nothing launched) for a step the kernel's fixed tables cannot hold: a prefix
+// over 32 bytes, an element list over 64 chunks, m outside 1..3, more than 128 positions, more layers than the domain has or than the
+// 64-word count block holds.
 hipError_t channel_step(const ChanStep &s, hipStream_t stream);
 
 } // namespace cs

@@ -1,7 +1,9 @@
 // The Fiat-Shamir channel on the device: the engine's public coin (ProverChannel / RandomCoin inside Prover::prove,
 // /root/reference/src/lib.rs:140 [UPSTREAM-RECALL winterfell v0.3, parity unpinned]) as ONE workgroup per channel step, so that the host
 // enqueues a whole proof without reading a root, a frame or a remainder back in between.  The bytes are those of prove.hip's host Coin
-// (which stays the reference implementation: CSTARK_HOST_CHANNEL=1, every Sha3 / extension / sub-AIR proof).
+// (which stays the reference implementation: CSTARK_HOST_CHANNEL=1, every Sha3, proof-of-work and sharded proof).  Base-field and
+// extension-field proofs alike: a drawn element is m consecutive draws (transcript.h), stored as the m-tuple or component by component
+// where the step's consumer wants them (store_draw).
 //
 // Four lanes share a BLAKE3 compression (blake3_quad.cuh): a reseed is one compression of quad 0; the candidates of a draw are hashed
 // 256 counters per pass by the 256 quads of the workgroup (a candidate is a field element with probability 0.256) and compacted in
@@ -10,6 +12,7 @@
 #include "blake3_quad.cuh"
 #include "fp.cuh"
 #include "../../include/cstark_conventions.h"
+#include "ext.cuh"
 
 namespace cs {
 namespace {
@@ -23,7 +26,7 @@ struct Shared {
     uint32_t cvs[MAX_CHUNKS][8];
     uint32_t wave_cnt[CT / 64];
     uint32_t total, ncand;
-    uint64_t drawn;           // CHAN_DRAW_POINT
+    uint64_t drawn[3];        // CHAN_DRAW_POINT
     uint32_t cand[MAX_CAND];
     uint32_t cur[MAX_POS], nxt[MAX_POS];
     uint8_t prefix[32];
@@ -74,26 +77,41 @@ __device__ __forceinline__ uint32_t compact_position(Shared &S, bool flag) {
     return pos;
 }
 
+// draw i = component q of element e (transcript.h: draw_coefficients, draw_deep)
 __device__ __forceinline__ void store_draw(const ChanStep &s, Shared &S, uint32_t i, fp val) {
+    const uint32_t m = s.m, e = m == 1 ? i : i / m, q = i - e * m;
     switch (s.draw) {
     case CHAN_DRAW_LINEAR: s.out[i] = val; break;
-    case CHAN_DRAW_COEFFS:
-        if (i < 2 * s.a) s.out[(i & 1) * s.stride + (i >> 1)] = val;
-        else { const uint32_t r = i - 2 * s.a; s.out[2 * s.stride + (r & 1) * s.b + (r >> 1)] = val; }
+    case CHAN_DRAW_COEFFS: {
+        uint64_t *o = s.out + (size_t)q * s.set_stride;
+        if (e < 2 * s.a) o[(e & 1) * s.stride + (e >> 1)] = val;
+        else { const uint32_t r = e - 2 * s.a; o[2 * s.stride + (r & 1) * s.b + (r >> 1)] = val; }
         break;
+    }
     case CHAN_DRAW_DEEP:
-        if (i < s.per * s.a) {
-            const uint32_t reg = i / s.per, k = i % s.per;
-            if (k == 0) s.out[reg] = val;
-            else if (k == 1) s.out[s.a + reg] = val;
+        if (e < s.per * s.a) {
+            const uint32_t reg = e / s.per, k = e % s.per;
+            if (k == 0) s.out[m * reg + q] = val;
+            else if (k == 1) s.out[m * (s.a + reg) + q] = val;
         } else {
-            const uint32_t r = i - s.per * s.a;
-            if (r < s.b) s.out[2 * s.a + r] = val;
-            else s.out2[3 + (r - s.b)] = val;
+            const uint32_t r = e - s.per * s.a;
+            if (r < s.b) s.out[m * (2 * s.a + r) + q] = val;
+            else s.out2[m * (3 + (r - s.b)) + q] = val;
         }
         break;
-    case CHAN_DRAW_POINT: S.drawn = val; break;
+    case CHAN_DRAW_POINT: S.drawn[q] = val; break;
     default: break;
+    }
+}
+// CHAN_DRAW_POINT over the degree-M extension: z | z w | z^e as M-tuples (one thread)
+template <int M>
+__device__ __forceinline__ void store_point(const ChanStep &s, const Shared &S) {
+    Ext<M> z;
+    for (int q = 0; q < M; q++) z.c[q] = S.drawn[q];
+    const Ext<M> zw = x_scale(z, s.w), ze = x_pow(z, s.b);
+    for (int q = 0; q < M; q++) {
+        s.out[q] = z.c[q]; s.out[M + q] = zw.c[q]; s.out[2 * M + q] = ze.c[q];
+        if (s.out2) { s.out2[q] = z.c[q]; s.out2[M + q] = zw.c[q]; s.out2[2 * M + q] = ze.c[q]; }
     }
 }
 
@@ -227,7 +245,8 @@ __global__ __launch_bounds__(CT) void k_chan_step(ChanStep s) {
     const unsigned lane = tid & 63;
     if (s.draw >= CHAN_DRAW_LINEAR && s.draw <= CHAN_DRAW_POINT) {
         uint64_t base = CSTARK_CONV_COIN_FIRST_COUNTER;
-        for (int pass = 0; pass < 4096 && S.total < s.count; pass++) { // (uniform: S.total is read after a barrier)
+        const uint32_t ndraw = s.count * s.m; // m draws per element
+        for (int pass = 0; pass < 4096 && S.total < ndraw; pass++) { // (uniform: S.total is read after a barrier)
             // quad q takes counters base + 2 q and base + 2 q + 1: lane 0 flags the first, lane 2 the second -- lane order = counter order
             uint32_t lo, hi, lo2, hi2;
             hash_seed_int(S, m, sched, c, base + 2 * quad, lo, hi);
@@ -238,14 +257,17 @@ __global__ __launch_bounds__(CT) void k_chan_step(ChanStep s) {
             const uint64_t v = c == 0 ? v1 : v2;
             const bool ok = (c == 0 || c == 2) && (!CSTARK_CONV_COIN_REJECT_ABOVE_P || v < FP_P);
             const uint32_t pos = compact_position(S, ok);
-            if (ok && pos < s.count) store_draw(s, S, pos, fp_from_u64(v));
+            if (ok && pos < ndraw) store_draw(s, S, pos, fp_from_u64(v));
             base += PER_PASS;
         }
         __syncthreads();
         if (s.draw == CHAN_DRAW_POINT && tid == 0) {
-            const fp z = S.drawn, zw = fp_mul(z, s.w), ze = fp_pow(z, s.b);
-            s.out[0] = z; s.out[1] = zw; s.out[2] = ze;
-            if (s.out2) { s.out2[0] = z; s.out2[1] = zw; s.out2[2] = ze; }
+            if (s.m == 1) {
+                const fp z = S.drawn[0], zw = fp_mul(z, s.w), ze = fp_pow(z, s.b);
+                s.out[0] = z; s.out[1] = zw; s.out[2] = ze;
+                if (s.out2) { s.out2[0] = z; s.out2[1] = zw; s.out2[2] = ze; }
+            } else if (s.m == 2) store_point<2>(s, S);
+            else store_point<3>(s, S);
         }
     } else if (s.draw == CHAN_DRAW_QUERIES) {
         const uint32_t mask = (1u << s.log_domain) - 1;
@@ -309,11 +331,15 @@ __global__ __launch_bounds__(CT) void k_chan_step(ChanStep s) {
 } // namespace
 
 hipError_t channel_step(const ChanStep &s, hipStream_t stream) {
-    if (!s.seed) return hipErrorInvalidValue;
+    if (!s.seed || s.m < 1 || s.m > 3) return hipErrorInvalidValue;
+    if (s.prefix_len > sizeof s.prefix) return hipErrorInvalidValue; // (Shared::prefix)
     if (s.init && s.prefix_len + 8 * s.npub > 1024) return hipErrorInvalidValue;
     for (int k = 0; k < 3; k++)
         if (s.absorb[k].kind == CHAN_ELEMS && (size_t)s.absorb[k].count * 8 > (size_t)MAX_CHUNKS * 1024) return hipErrorInvalidValue;
     if (s.draw == CHAN_DRAW_QUERIES && (s.count == 0 || s.count > MAX_POS || s.log_domain > 31 || s.slot < s.count)) return hipErrorInvalidValue;
+    // the folded positions: every layer takes log_f bits of the domain, and cnt holds 1 + n_layers words of a 64-word block
+    if (s.draw == CHAN_DRAW_QUERIES && ((uint64_t)s.n_layers * s.log_f > s.log_domain || s.n_layers + 1 > 64)) return hipErrorInvalidValue;
+    if (s.draw == CHAN_DRAW_POINT && s.count != 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_chan_step, dim3(1), dim3(CT), 0, stream, s);
     return hipGetLastError();
 }

@@ -191,9 +191,9 @@ struct cstark_ctx {
     void *rb_dev = nullptr, *rb_host = nullptr; // cstark_range_prove_batch: one device block and one pinned host block, carved per call
     size_t rb_dev_bytes = 0, rb_host_bytes = 0;
 };
-// internal (capi.hip): the coin of one FRI layer on the device followed by the fold with the drawn point (prove.hip)
+// internal (capi.hip): the coin of one FRI layer on the device followed by the fold with the drawn point, m words at d_alpha (prove.hip)
 int fri_coin_fold_dev(cstark_ctx *c, uint32_t *d_seed, const uint8_t *d_root, uint64_t *d_alpha, uint32_t *d_root_out, const uint64_t *d_evals,
-                      uint64_t *d_out, uint32_t log_n, uint32_t log_f, uint64_t domain_offset);
+                      uint64_t *d_out, uint32_t log_n, uint32_t log_f, uint64_t domain_offset, uint32_t m);
 // internal (capi.hip): row hashes of a whole table whose cosets are in block order (blake3.h): leaf b j + k = row j of LDE coset k
 int hash_rows_slots(cstark_ctx *c, uint32_t hash_fn, const uint64_t *d_lde, uint8_t *d_leaves, uint32_t width, uint32_t log_n, uint32_t log_blowup, uint32_t log_s);
 // internal (capi.hip): the cached twiddle tables of a 2^log_n-point domain: powers of w and of its inverse (device, n entries each)
@@ -231,6 +231,15 @@ int evaluate_ood_frames(cstark_ctx *c, const uint64_t *d_coeffs, uint32_t width,
                         const uint64_t zpts[2], uint64_t zb, uint64_t *out_trace, uint64_t *out_comp);
 int ood_frames_dev(cstark_ctx *c, const uint64_t *d_coeffs, uint32_t width, const uint64_t *d_ccoef, uint32_t n_comp, uint32_t log_n, const uint64_t *d_pts,
                    uint64_t *d_out);
+// internal (capi.hip): the device-channel forms of the extension-field frame and DEEP stage (m = 2, 3), and the context scratch they and
+// ood_frames_dev use, reserved ahead of a proof's first launch
+int desc_reserve(cstark_ctx *c, size_t bytes);
+size_t ood_frames_dev_scratch_bytes(uint32_t width, uint32_t n_comp, uint32_t log_n, uint32_t m);
+int ood_frames_dev_ext(cstark_ctx *c, const uint64_t *d_coeffs, uint32_t width, const uint64_t *d_ccoef, uint32_t n_comp, uint32_t log_n, uint32_t m,
+                       const uint64_t *d_pts, uint64_t *d_out);
+int deep_composition_ext_dev(cstark_ctx *c, const uint64_t *d_trace_lde, const uint64_t *d_comp_lde, uint32_t width, uint32_t n_comp, uint32_t m,
+                             const uint64_t *d_coef, const uint64_t *d_ood, uint64_t *d_scal, const uint64_t *d_shifts, uint64_t *d_out, uint32_t log_n,
+                             uint32_t log_blowup, uint32_t nk);
 int deep_composition_ext_cosets(cstark_ctx *c, const uint64_t *d_trace_lde, const uint64_t *d_comp_lde, uint32_t width, uint32_t n_comp, uint32_t m,
                                 const uint64_t *z, const uint64_t *ood_trace, const uint64_t *ood_comp, const uint64_t *alpha, const uint64_t *beta,
                                 const uint64_t *delta, const uint64_t *deg_a, const uint64_t *deg_b, uint64_t *d_out, uint32_t log_n, uint32_t log_blowup,

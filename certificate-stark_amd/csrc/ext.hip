@@ -17,7 +17,9 @@ constexpr int PE_SEG = 16384;
 // are the same for every lane -- tabulated once per workgroup in LDS, M lazily accumulated base products per coefficient instead
 // of an extension multiplication (9 base products for M = 3).  The lane's sum is then moved into place by z^t and z^(segment start).
 template <int M>
-__global__ __launch_bounds__(256) void k_poly_eval_ext_partial(const fp *__restrict__ coeffs, size_t n, Ext<M> z, fp *__restrict__ partial, unsigned seg_len) {
+__global__ __launch_bounds__(256) void k_poly_eval_ext_partial(const fp *__restrict__ coeffs, size_t n, Ext<M> z, fp *__restrict__ partial, unsigned seg_len,
+                                                               const fp *__restrict__ z_dev) {
+    if (z_dev) z = x_load<M>(z_dev); // the point was drawn on the device (channel.hip)
     __shared__ Ext<M> part[256];
     __shared__ fp pk[M][PE_SEG / 256];
     __shared__ Ext<M> zseg;
@@ -74,8 +76,16 @@ __global__ __launch_bounds__(256) void k_deep_ext(DeepExtParams p) {
     if (j >= n) return;
     const unsigned k = blockIdx.y, b = p.nk ? p.nk : 1u << p.log_b; // b: cosets in the output
     const fp x = fp_mul(p.shifts[k], p.w[j]);
+    // the points and constants: the by-value fields, or M-tuples drawn and computed on the device (p.scal: z | z w | z^nb | deg_a | deg_b | k1 | k2 | k3)
+    uint64_t pz[M], pzw[M], pzb[M], dga[M], dgb[M], k1[M], k2[M], k3[M];
+#pragma unroll
+    for (int q = 0; q < M; q++) {
+        pz[q] = p.scal ? p.scal[q] : p.z[q]; pzw[q] = p.scal ? p.scal[M + q] : p.zw[q]; pzb[q] = p.scal ? p.scal[2 * M + q] : p.zb[q];
+        dga[q] = p.scal ? p.scal[3 * M + q] : p.deg_a[q]; dgb[q] = p.scal ? p.scal[4 * M + q] : p.deg_b[q];
+        k1[q] = p.scal ? p.scal[5 * M + q] : p.k1[q]; k2[q] = p.scal ? p.scal[6 * M + q] : p.k2[q]; k3[q] = p.scal ? p.scal[7 * M + q] : p.k3[q];
+    }
     // the three divisors with one base-field inversion
-    const XInv<M> q1 = x_inv_parts(x, p.z, (Ext<M> *)nullptr), q2 = x_inv_parts(x, p.zw, (Ext<M> *)nullptr), q3 = x_inv_parts(x, p.zb, (Ext<M> *)nullptr);
+    const XInv<M> q1 = x_inv_parts(x, pz, (Ext<M> *)nullptr), q2 = x_inv_parts(x, pzw, (Ext<M> *)nullptr), q3 = x_inv_parts(x, pzb, (Ext<M> *)nullptr);
     const fp n12 = fp_mul(q1.norm, q2.norm);
     const fp inv = fp_inv(fp_mul(n12, q3.norm));
     const Ext<M> i1 = x_scale(q1.adj, fp_mul(inv, fp_mul(q2.norm, q3.norm))), i2 = x_scale(q2.adj, fp_mul(inv, fp_mul(q1.norm, q3.norm))),
@@ -99,8 +109,8 @@ __global__ __launch_bounds__(256) void k_deep_ext(DeepExtParams p) {
 #pragma unroll
     for (int q = 0; q < M; q++) {
         acc_fold(s1[q]); acc_fold(s2[q]);
-        e1.c[q] = fp_sub(acc_reduce(s1[q]), p.k1[q]);
-        e2.c[q] = fp_sub(acc_reduce(s2[q]), p.k2[q]);
+        e1.c[q] = fp_sub(acc_reduce(s1[q]), k1[q]);
+        e2.c[q] = fp_sub(acc_reduce(s2[q]), k2[q]);
     }
     Ext<M> e3 = x_zero<M>();
     const fp *h = p.comp_lde + (size_t)k * M * p.nb * n + j;
@@ -110,18 +120,19 @@ __global__ __launch_bounds__(256) void k_deep_ext(DeepExtParams p) {
         for (int q = 0; q < M; q++) hv.c[q] = h[(size_t)(M * i + q) * n];
         e3 = x_add(e3, x_mul(x_load<M>(de + M * i), hv));
     }
-    e3 = x_sub(e3, x_load<M>(p.k3));
+    e3 = x_sub(e3, x_load<M>(k3));
     Ext<M> acc = x_add(x_add(x_mul(e1, i1), x_mul(e2, i2)), x_mul(e3, i3));
-    acc = x_mul(acc, x_add(x_load<M>(p.deg_a), x_scale(x_load<M>(p.deg_b), x)));
+    acc = x_mul(acc, x_add(x_load<M>(dga), x_scale(x_load<M>(dgb), x)));
 #pragma unroll
     for (int q = 0; q < M; q++) p.out[((size_t)q * b + k) * n + j] = acc.c[q];
 }
 
 template <int M>
 __global__ __launch_bounds__(256) void k_fri_fold4_ext(const fp *__restrict__ evals, fp *__restrict__ out, size_t q, const fp *__restrict__ winv,
-                                                       fp offset_inv, Ext<M> alpha, fp inv4) {
+                                                       fp offset_inv, Ext<M> alpha, fp inv4, const fp *__restrict__ alpha_dev) {
     const size_t i = blockIdx.x * (size_t)256 + threadIdx.x;
     if (i >= q) return;
+    if (alpha_dev) alpha = x_load<M>(alpha_dev); // drawn by the device-side coin (blake3.hip, k_fri_coin_ext)
     const size_t N = 4 * q;
     const fp zi = winv[q]; // zeta^-1
     Ext<M> s[4];
@@ -144,10 +155,11 @@ __global__ __launch_bounds__(256) void k_fri_fold4_ext(const fp *__restrict__ ev
 // per component -- and the Horner steps in alpha / x_i are extension products)
 template <int M, int LOG_F>
 __global__ __launch_bounds__(256) void k_fri_fold_ext(const fp *__restrict__ evals, fp *__restrict__ out, size_t q, const fp *__restrict__ winv,
-                                                      fp offset_inv, Ext<M> alpha, fp inv_f) {
+                                                      fp offset_inv, Ext<M> alpha, fp inv_f, const fp *__restrict__ alpha_dev) {
     constexpr int F = 1 << LOG_F;
     const size_t i = blockIdx.x * (size_t)256 + threadIdx.x;
     if (i >= q) return;
+    if (alpha_dev) alpha = x_load<M>(alpha_dev);
     const size_t N = (size_t)F * q;
     Ext<M> s[F];
 #pragma unroll
@@ -186,6 +198,46 @@ __global__ __launch_bounds__(256) void k_fri_fold_ext(const fp *__restrict__ eva
     for (int comp = 0; comp < M; comp++) out[comp * q + i] = acc.c[comp];
 }
 
+// The composition half of the out-of-domain frame from the raw values: the composition table holds the components of column i as m
+// base-field columns H_i,q, so H_i(z^ce) = sum_q root^q H_i,q(z^ce) with `root` the adjoined root (0, 1, 0).  raw = [ce][M] M-tuples
+// (column M i + q at the point), out = [ce] M-tuples.  One thread per column.
+template <int M>
+__global__ void k_ood_recombine(const fp *__restrict__ raw, fp *__restrict__ out, unsigned ce) {
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ce) return;
+    Ext<M> gen = x_zero<M>(), gq = x_one<M>(), h = x_zero<M>();
+    gen.c[1] = FP_ONE;
+#pragma unroll
+    for (int q = 0; q < M; q++) {
+        h = x_add(h, x_mul(gq, x_load<M>(raw + M * (M * i + q))));
+        gq = x_mul(gq, gen);
+    }
+#pragma unroll
+    for (int q = 0; q < M; q++) out[M * i + q] = h.c[q];
+}
+// The constants of k_deep_ext from the frame and the DEEP coefficients where the channel left them: k1 = sum_c alpha_c T_c(z),
+// k2 = sum_c beta_c T_c(z w), k3 = sum_i delta_i H_i(z^nb) -> scal[5 M .. 8 M).  coef = alpha[width] | beta[width] | delta[nb],
+// ood = T(z)[width] | T(z w)[width] | H[nb], all M-tuples: three dot products of 2 width + nb terms.  One workgroup of 256.
+template <int M>
+__global__ __launch_bounds__(256) void k_deep_ext_consts(const fp *__restrict__ coef, const fp *__restrict__ ood, fp *__restrict__ scal, unsigned width, unsigned nb) {
+    __shared__ Ext<M> part[3][256];
+    const unsigned t = threadIdx.x;
+    const unsigned first[4] = {0, width, 2 * width, 2 * width + nb};
+#pragma unroll
+    for (int w = 0; w < 3; w++) {
+        Ext<M> k = x_zero<M>();
+        for (unsigned e = first[w] + t; e < first[w + 1]; e += 256) k = x_add(k, x_mul(x_load<M>(coef + (size_t)M * e), x_load<M>(ood + (size_t)M * e)));
+        part[w][t] = k;
+    }
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)t < s)
+            for (int w = 0; w < 3; w++) part[w][t] = x_add(part[w][t], part[w][t + s]);
+        __syncthreads();
+    }
+    if (t < 3 * M) scal[5 * M + t] = part[t / M][0].c[t % M];
+}
+
 } // namespace
 
 size_t poly_eval_ext_scratch_words(unsigned width, unsigned log_n, unsigned m) {
@@ -193,13 +245,28 @@ size_t poly_eval_ext_scratch_words(unsigned width, unsigned log_n, unsigned m) {
     return (size_t)m * width * (n / seg);
 }
 hipError_t poly_eval_ext(const uint64_t *d_coeffs, unsigned width, unsigned log_n, const uint64_t *z, unsigned m, uint64_t *d_out, uint64_t *d_scratch,
-                         hipStream_t stream) {
+                         hipStream_t stream, const uint64_t *d_z) {
     const size_t n = (size_t)1 << log_n;
     const unsigned seg_len = (unsigned)(n < (size_t)PE_SEG ? n : (size_t)PE_SEG), segs = (unsigned)(n / seg_len);
-    if (m == 2) hipLaunchKernelGGL(k_poly_eval_ext_partial<2>, dim3(segs, width), dim3(256), 0, stream, d_coeffs, n, Ext<2>{{z[0], z[1]}}, d_scratch, seg_len);
-    else if (m == 3) hipLaunchKernelGGL(k_poly_eval_ext_partial<3>, dim3(segs, width), dim3(256), 0, stream, d_coeffs, n, Ext<3>{{z[0], z[1], z[2]}}, d_scratch, seg_len);
+    if ((!z && !d_z) || width == 0) return hipErrorInvalidValue;
+    const uint64_t none[3] = {0, 0, 0};
+    if (d_z) z = none;
+    if (m == 2) hipLaunchKernelGGL(k_poly_eval_ext_partial<2>, dim3(segs, width), dim3(256), 0, stream, d_coeffs, n, Ext<2>{{z[0], z[1]}}, d_scratch, seg_len, d_z);
+    else if (m == 3) hipLaunchKernelGGL(k_poly_eval_ext_partial<3>, dim3(segs, width), dim3(256), 0, stream, d_coeffs, n, Ext<3>{{z[0], z[1], z[2]}}, d_scratch, seg_len, d_z);
     else return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_poly_eval_ext_sum, dim3((m * width + 255) / 256), dim3(256), 0, stream, d_scratch, d_out, width, segs, m);
+    return hipGetLastError();
+}
+hipError_t ood_recombine_ext(const uint64_t *d_raw, uint64_t *d_out, unsigned n_comp, unsigned m, hipStream_t stream) {
+    if (m == 2) hipLaunchKernelGGL(k_ood_recombine<2>, dim3((n_comp + 63) / 64), dim3(64), 0, stream, d_raw, d_out, n_comp);
+    else if (m == 3) hipLaunchKernelGGL(k_ood_recombine<3>, dim3((n_comp + 63) / 64), dim3(64), 0, stream, d_raw, d_out, n_comp);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+hipError_t deep_ext_consts(const uint64_t *d_coef, const uint64_t *d_ood, uint64_t *d_scal, unsigned width, unsigned n_comp, unsigned m, hipStream_t stream) {
+    if (m == 2) hipLaunchKernelGGL(k_deep_ext_consts<2>, dim3(1), dim3(256), 0, stream, d_coef, d_ood, d_scal, width, n_comp);
+    else if (m == 3) hipLaunchKernelGGL(k_deep_ext_consts<3>, dim3(1), dim3(256), 0, stream, d_coef, d_ood, d_scal, width, n_comp);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 hipError_t deep_composition_ext(const DeepExtParams &p, hipStream_t stream) {
@@ -211,25 +278,30 @@ hipError_t deep_composition_ext(const DeepExtParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 hipError_t fri_fold4_ext(const uint64_t *d_evals, uint64_t *d_out, unsigned log_n, const uint64_t *d_winv, uint64_t offset_inv, const uint64_t *alpha,
-                         unsigned m, uint64_t inv4, hipStream_t stream) {
+                         unsigned m, uint64_t inv4, hipStream_t stream, const uint64_t *d_alpha) {
     const size_t q = ((size_t)1 << log_n) / 4;
     const dim3 grid((unsigned)((q + 255) / 256));
-    if (m == 2) hipLaunchKernelGGL(k_fri_fold4_ext<2>, grid, dim3(256), 0, stream, d_evals, d_out, q, d_winv, offset_inv, Ext<2>{{alpha[0], alpha[1]}}, inv4);
-    else if (m == 3) hipLaunchKernelGGL(k_fri_fold4_ext<3>, grid, dim3(256), 0, stream, d_evals, d_out, q, d_winv, offset_inv, Ext<3>{{alpha[0], alpha[1], alpha[2]}}, inv4);
+    const uint64_t none[3] = {0, 0, 0};
+    if (!alpha && !d_alpha) return hipErrorInvalidValue;
+    if (d_alpha) alpha = none;
+    if (m == 2) hipLaunchKernelGGL(k_fri_fold4_ext<2>, grid, dim3(256), 0, stream, d_evals, d_out, q, d_winv, offset_inv, Ext<2>{{alpha[0], alpha[1]}}, inv4, d_alpha);
+    else if (m == 3) hipLaunchKernelGGL(k_fri_fold4_ext<3>, grid, dim3(256), 0, stream, d_evals, d_out, q, d_winv, offset_inv, Ext<3>{{alpha[0], alpha[1], alpha[2]}}, inv4, d_alpha);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
 hipError_t fri_fold_ext(const uint64_t *d_evals, uint64_t *d_out, unsigned log_n, unsigned log_f, const uint64_t *d_winv, uint64_t offset_inv,
-                        const uint64_t *alpha, unsigned m, uint64_t inv_f, hipStream_t stream) {
-    if (log_f == 2) return fri_fold4_ext(d_evals, d_out, log_n, d_winv, offset_inv, alpha, m, inv_f, stream);
-    if ((log_f != 3 && log_f != 4) || log_n < log_f || (m != 2 && m != 3)) return hipErrorInvalidValue;
+                        const uint64_t *alpha, unsigned m, uint64_t inv_f, hipStream_t stream, const uint64_t *d_alpha) {
+    if (log_f == 2) return fri_fold4_ext(d_evals, d_out, log_n, d_winv, offset_inv, alpha, m, inv_f, stream, d_alpha);
+    if ((log_f != 3 && log_f != 4) || log_n < log_f || (m != 2 && m != 3) || (!alpha && !d_alpha)) return hipErrorInvalidValue;
     const size_t q = ((size_t)1 << log_n) >> log_f;
     const dim3 grid((unsigned)((q + 255) / 256));
-    if (m == 2 && log_f == 3) hipLaunchKernelGGL((k_fri_fold_ext<2, 3>), grid, dim3(256), 0, stream, d_evals, d_out, q, d_winv, offset_inv, Ext<2>{{alpha[0], alpha[1]}}, inv_f);
-    else if (m == 2) hipLaunchKernelGGL((k_fri_fold_ext<2, 4>), grid, dim3(256), 0, stream, d_evals, d_out, q, d_winv, offset_inv, Ext<2>{{alpha[0], alpha[1]}}, inv_f);
-    else if (log_f == 3) hipLaunchKernelGGL((k_fri_fold_ext<3, 3>), grid, dim3(256), 0, stream, d_evals, d_out, q, d_winv, offset_inv, Ext<3>{{alpha[0], alpha[1], alpha[2]}}, inv_f);
-    else hipLaunchKernelGGL((k_fri_fold_ext<3, 4>), grid, dim3(256), 0, stream, d_evals, d_out, q, d_winv, offset_inv, Ext<3>{{alpha[0], alpha[1], alpha[2]}}, inv_f);
+    const uint64_t none[3] = {0, 0, 0};
+    if (d_alpha) alpha = none;
+    if (m == 2 && log_f == 3) hipLaunchKernelGGL((k_fri_fold_ext<2, 3>), grid, dim3(256), 0, stream, d_evals, d_out, q, d_winv, offset_inv, Ext<2>{{alpha[0], alpha[1]}}, inv_f, d_alpha);
+    else if (m == 2) hipLaunchKernelGGL((k_fri_fold_ext<2, 4>), grid, dim3(256), 0, stream, d_evals, d_out, q, d_winv, offset_inv, Ext<2>{{alpha[0], alpha[1]}}, inv_f, d_alpha);
+    else if (log_f == 3) hipLaunchKernelGGL((k_fri_fold_ext<3, 3>), grid, dim3(256), 0, stream, d_evals, d_out, q, d_winv, offset_inv, Ext<3>{{alpha[0], alpha[1], alpha[2]}}, inv_f, d_alpha);
+    else hipLaunchKernelGGL((k_fri_fold_ext<3, 4>), grid, dim3(256), 0, stream, d_evals, d_out, q, d_winv, offset_inv, Ext<3>{{alpha[0], alpha[1], alpha[2]}}, inv_f, d_alpha);
     return hipGetLastError();
 }
 

@@ -62,6 +62,7 @@ struct ProveArena {
     size_t open_bytes = 0;
     hipEvent_t ev[PROVE_EVENTS] = {};
     bool timed = false;
+    uint32_t channel = CSTARK_CHANNEL_HOST; // which Fiat-Shamir channel the last proof used (valid with `timed`: cstark_prove_channel)
     std::vector<void *> owned;
     struct ProofRun *run = nullptr; // a proof in progress between the phases of the sharded entry points (cstark_tx_shard_*)
 };
@@ -605,9 +606,9 @@ int deep_extend(cstark_ctx *c, ProofRun &R, uint64_t *sums, uint64_t *dcoef) {
 
 // FRI commit phase: per layer the row hashes, the tree, and the fold at the point the coin draws after the layer's root.  `last`: where
 // the last fold lands (the remainder).  The coin is the run's:
-//   d_fri != null  a coin block on the device, [seed 8 words][alpha: 2 words per layer x 32]: k_fri_coin reseeds with the layer's root,
-//                  draws the folding point and copies the root to d_roots + 8 l, so all layers are enqueued at once and nothing waits
-//                  (base field, Blake3);
+//   d_fri != null  a coin block on the device, [seed 8 words][alpha: m elements (2 m words) per layer x 32]: k_fri_coin / k_fri_coin_ext
+//                  reseeds with the layer's root, draws the folding point and copies the root to d_roots + 8 l, so all layers are
+//                  enqueued at once and nothing waits (Blake3);
 //   d_fri == null  the host coin R.coin: one wait per layer for the root (-> R.layer_roots), the point drawn between two launches.
 int fri_commit(cstark_ctx *c, ProveArena *a, ProofRun &R, uint32_t *d_fri, uint32_t *d_roots, uint64_t *last) {
     const unsigned m = R.m, log_f = R.log_f;
@@ -620,7 +621,7 @@ int fri_commit(cstark_ctx *c, ProveArena *a, ProofRun &R, uint32_t *d_fri, uint3
         RC_TRY(cstark_hash_rows_fn(c, hf, R.layer[l], a->lnodes[l] + 32 * rows, fold * m, lg - log_f, 0, 0, 1));
         RC_TRY(cstark_merkle_build_fn(c, hf, a->lnodes[l], lg - log_f));
         if (d_fri) {
-            RC_TRY(fri_coin_fold_dev(c, d_fri, a->lnodes[l] + 32, (uint64_t *)(d_fri + 8) + l, d_roots + 8 * l, R.layer[l], next, lg, log_f, offset));
+            RC_TRY(fri_coin_fold_dev(c, d_fri, a->lnodes[l] + 32, (uint64_t *)(d_fri + 8) + m * l, d_roots + 8 * l, R.layer[l], next, lg, log_f, offset, m));
         } else {
             HIP_TRY(hipMemcpyAsync(&R.layer_roots[32 * l], a->lnodes[l] + 32, 32, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(cs::stream_wait(c->stream));
@@ -813,7 +814,7 @@ int phase_open(cstark_ctx *c, ProveArena *a, ProofRun &R, const uint64_t *d_trac
     RC_TRY(open_stage(c, a, S, {R.clde, R.layer.data(), R.log_s(), R.q.counts, nullptr, d_trace_rows, ceil_log2(R.job.nk)}, R.d_open, O));
     STAGE();
     HIP_TRY(cs::stream_wait(c->stream));
-    a->timed = true;
+    a->timed = true; a->channel = CSTARK_CHANNEL_HOST;
 
     ProofParts p{};
     p.trace_root = R.trace_root; p.cons_root = R.cons_root; p.layer_roots = R.layer_roots.data(); p.rem_commit = R.rem_commit;
@@ -832,12 +833,17 @@ int prove_core(cstark_ctx *c, const cstark_options *opt, AirJob &job, uint8_t *p
     return phase_open(c, a, R, nullptr, proof, capacity, proof_len);
 }
 // ---- the same proof with the Fiat-Shamir channel on the device (channel.hip) ---------------------------------------------------------
-// Any of the AIRs, base field, Blake3 coin, no proof of work: every channel step -- seed, reseeds, the 238 coefficient draws, the
-// out-of-domain point, the DEEP coefficients, the FRI layers' folding points (k_fri_coin), the remainder commitment, the query positions
-// and their folded forms -- is a launch on the context's stream, the kernels read what was drawn from device memory, and the host waits
-// ONCE, for the block that holds everything the proof bytes are written from.  Same bytes as prove_core (the tests compare both with the
-// CPU prover); CSTARK_HOST_CHANNEL=1 keeps the host channel for the A/B.  One-at-a-time proving on the host channel leaves the GPU idle
-// for 0.6 ms of a 28.4 ms proof, 0.39 ms of it in the five waits (profiles/r04_timeline_host_channel.txt).
+// Any of the AIRs, any field extension, Blake3 coin, no proof of work, one GPU: every channel step -- seed, reseeds, the 238 coefficient
+// draws, the out-of-domain point, the DEEP coefficients, the FRI layers' folding points (k_fri_coin), the remainder commitment, the query
+// positions and their folded forms -- is a launch on the context's stream, the kernels read what was drawn from device memory, and the
+// host waits ONCE, for the block that holds everything the proof bytes are written from.  Every buffer is sized before the first launch:
+// nothing is allocated, freed or uploaded in between.  The Sha3 coin, proof of work and sharded proofs take the host channel (prove_core /
+// the cstark_tx_shard_* phases).  Same bytes as prove_core (the tests compare both with the CPU prover); CSTARK_HOST_CHANNEL=1 keeps the
+// host channel for the A/B.  One-at-a-time proving on the host channel leaves the GPU idle for 0.6 ms of a 28.4 ms base-field proof,
+// 0.39 ms of it in the five waits (profiles/r04_timeline_host_channel.txt); an extension-field proof waits more often (three frame
+// evaluations, an upload before the DEEP stage, every FRI layer) and recombines the frame on the host.
+// Extension fields (m = 2, 3 words per drawn element): the channel draws m-tuples (ChanStep::m); the m coefficient sets lie one block
+// apart; the frame, the DEEP constants and the folds read their points where the channel wrote them (ext.hip).
 // The stages between the four channel steps are the host steps above.
 int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8_t *proof, size_t capacity, size_t *proof_len) {
     const auto hp0 = std::chrono::steady_clock::now();
@@ -846,9 +852,9 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
     job0.dev_channel = true;
     RC_TRY(run_setup(c, opt, job0, R, &a));
     AirJob &job = R.job;
-    const unsigned log_n = job.log_n, log_b = R.log_b, log_N = log_n + log_b, n_layers = R.n_layers;
+    const unsigned m = R.m, log_n = job.log_n, log_b = R.log_b, log_N = log_n + log_b, n_layers = R.n_layers;
     const size_t n = (size_t)1 << log_n, W = job.width, ce = (size_t)1 << job.log_ce, nq = opt->num_queries;
-    const size_t rem_len = (size_t)1 << (log_N - n_layers * R.log_f), n_ood = 2 * W + ce;
+    const size_t rem_len = (size_t)m << (log_N - n_layers * R.log_f), n_ood = m * (2 * W + ce); // words
     hipStream_t st = c->stream;
     // ---- the result block: everything the proof bytes are written from, one copy to the host at the end ------------------------------------
     size_t off = 0;
@@ -859,22 +865,33 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
     const OpenBlock O = open_block(S, nullptr, off, 256); // the openings: the tail of the block, nq slots in every layer
     off = O.bytes;
     uint8_t *d_res;
-    uint32_t *d_fri;   // [seed 8 words][alpha: 2 words per layer x 32]: the coin and the layers' folding points
-    uint64_t *d_chan;  // [pts 4][scal 8][deep coefficients 2 W + ce]
-    uint64_t *dcoef;
+    uint32_t *d_fri;   // [seed 8 words][alpha: m elements per layer x 32]: the coin and the layers' folding points
+    uint64_t *d_chan;  // [pts 4 m][scal 8 m][deep coefficients m (2 W + ce)]: m-tuples
+    uint64_t *sums, *dcoef; // the quotient sums on coset 0 [m][n] and their coefficients (deep_extend)
     RC_TRY(arena_extra(c, a, 44, &d_res, off));
-    RC_TRY(arena_extra(c, a, 41, &d_fri, (size_t)(8 + 10 * 32) * 4));
-    RC_TRY(arena_extra(c, a, 43, &d_chan, (12 + n_ood) * 8));
-    RC_TRY(arena_extra(c, a, 40, &dcoef, n * 8));
-    uint64_t *d_pts = d_chan, *d_scal = d_chan + 4, *d_deepc = d_chan + 12, *d_ood = (uint64_t *)(d_res + o_ood);
+    RC_TRY(arena_extra(c, a, 43, &d_chan, 12 * m * 8 + n_ood * 8));
+    // (slots 40, 41 also serve the host channel: dcoef and the coin block for m = 1, sums and dcoef otherwise; an extension proof on
+    // this channel keeps its own, so a context that alternates between the channels never replaces a slot back and forth)
+    if (m == 1) {
+        RC_TRY(arena_extra(c, a, 41, &d_fri, (size_t)(8 + 10 * 32) * 4));
+        RC_TRY(arena_extra(c, a, 40, &dcoef, n * 8));
+        sums = R.deep;
+    } else {
+        RC_TRY(arena_extra(c, a, 47, &d_fri, (size_t)(8 + 2 * 3 * 32) * 4));
+        RC_TRY(arena_extra(c, a, 48, &sums, 3 * n * 8));
+        RC_TRY(arena_extra(c, a, 49, &dcoef, 3 * n * 8));
+    }
+    uint64_t *d_pts = d_chan, *d_scal = d_chan + 4 * m, *d_deepc = d_chan + 12 * m, *d_ood = (uint64_t *)(d_res + o_ood);
     uint32_t *d_cnt = (uint32_t *)(d_res + o_cnt);
     RC_TRY(host_open_block(a, off)); // before the first launch: replacing a pinned block waits for the device
-    // the coefficient block the channel draws into: TransactionAir's evaluator reads the context's cstark_tx_coeffs block; the sub-AIRs'
-    // merge takes alpha[115] | beta[115] | b_alpha[na] | b_beta[na]
+    RC_TRY(desc_reserve(c, ood_frames_dev_scratch_bytes((uint32_t)W, (uint32_t)ce, log_n, m))); // the frame's scratch, likewise
+    // the coefficient blocks the channel draws into, one per component: TransactionAir's evaluator reads the context's cstark_tx_coeffs
+    // blocks; the sub-AIRs' merge takes alpha[115] | beta[115] | b_alpha[na] | b_beta[na]
     uint64_t *d_coef_block;
     const bool is_tx = job.air == CSTARK_AIR_STATE_TRANSITION;
+    const size_t coef_stride = is_tx ? (size_t)CE_COEF_WORDS : 230 + 2 * (size_t)job.n_assertions;
     if (is_tx) RC_TRY(tx_coef_device_block(c, &d_coef_block));
-    else RC_TRY(arena_extra(c, a, 46, &d_coef_block, (230 + 2 * (size_t)job.n_assertions) * 8));
+    else RC_TRY(arena_extra(c, a, 46, &d_coef_block, m * coef_stride * 8));
     const uint64_t *pw, *pwinv;
     RC_TRY(plan_tables(c, log_n, &pw, &pwinv));
 
@@ -883,7 +900,7 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
     STAGE();
     {   // the coin: context || public inputs (read from the trace, on the device), the trace root, the coefficient pairs
         ChanStep s{};
-        s.seed = d_fri;
+        s.seed = d_fri; s.m = m;
         const std::vector<uint8_t> prefix = channel_seed(job.width, log_n, *opt, log_b, R.log_rem); // the seed up to the public inputs
         if (job.air == CSTARK_AIR_SCHNORR) {
             // SchnorrAir's public inputs -- every message, R.x and s half: 304 bytes per signature -- are host data: the seed is hashed
@@ -902,44 +919,50 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
         memcpy(s.prefix, prefix.data(), SEED_PREFIX); s.prefix_len = SEED_PREFIX;
         s.absorb[0].kind = CHAN_DIGEST; s.absorb[0].ptr = a->tnodes + 32; s.absorb[0].copy_out = d_res + o_troot;
         s.draw = CHAN_DRAW_COEFFS; s.a = job.n_constraints; s.b = job.n_assertions; s.stride = CSTARK_TX_NUM_CONSTRAINTS;
+        s.set_stride = (uint32_t)coef_stride;
         s.count = (uint32_t)transcript::coefficient_draws(job.n_constraints, job.n_assertions); s.out = d_coef_block;
         HIP_TRY(channel_step(s, st));
     }
     if (is_tx) {
-        RC_TRY(tx_evaluate_constraints_sets(c, a->lde, nullptr, 1, nullptr, R.comb, job.item, log_n, 3, 0, 8, true, a->d_pub));
+        RC_TRY(tx_evaluate_constraints_sets(c, a->lde, nullptr, m, nullptr, R.comb, job.item, log_n, 3, 0, 8, true, a->d_pub));
     } else { // the sub-AIRs: the assertion values are the public inputs (MerkleAir, RescueAir), (0, number) (RangeProofAir) or built in (SchnorrAir)
-        job.d_coefs = d_coef_block;
         job.d_avalues = job.air == CSTARK_AIR_RANGE ? a->d_pub + 1 : job.air == CSTARK_AIR_SCHNORR ? nullptr : a->d_pub;
-        RC_TRY(job.combine(c, a, job, nullptr, nullptr, nullptr, nullptr, R.comb[0]));
+        for (unsigned q = 0; q < m; q++) { // one merge per component's coefficient set
+            job.d_coefs = d_coef_block + q * coef_stride;
+            RC_TRY(job.combine(c, a, job, nullptr, nullptr, nullptr, nullptr, R.comb[q]));
+        }
     }
     STAGE();
     RC_TRY(commit_composition(c, a, R));
     STAGE();
     {   // the constraint root -> the out-of-domain point z; z w and z^ce beside it
         ChanStep s{};
-        s.seed = d_fri;
+        s.seed = d_fri; s.m = m;
         s.absorb[0].kind = CHAN_DIGEST; s.absorb[0].ptr = a->cnodes + 32; s.absorb[0].copy_out = d_res + o_croot;
         s.draw = CHAN_DRAW_POINT; s.count = 1; s.b = (uint32_t)ce; s.w = host::root_of_unity(log_n); s.out = d_pts; s.out2 = d_scal;
         HIP_TRY(channel_step(s, st));
     }
-    RC_TRY(ood_frames_dev(c, a->coeffs, (uint32_t)W, R.ccoefs, (uint32_t)ce, log_n, d_pts, d_ood));
+    if (m == 1) RC_TRY(ood_frames_dev(c, a->coeffs, (uint32_t)W, R.ccoefs, (uint32_t)ce, log_n, d_pts, d_ood));
+    else RC_TRY(ood_frames_dev_ext(c, a->coeffs, (uint32_t)W, R.ccoefs, (uint32_t)ce, log_n, m, d_pts, d_ood));
     STAGE();
     {   // the two halves of the frame -> the DEEP coefficients
         ChanStep s{};
-        s.seed = d_fri;
-        s.absorb[0].kind = CHAN_ELEMS; s.absorb[0].ptr = d_ood; s.absorb[0].count = (uint32_t)(2 * W);
-        s.absorb[1].kind = CHAN_ELEMS; s.absorb[1].ptr = d_ood + 2 * W; s.absorb[1].count = (uint32_t)ce;
+        s.seed = d_fri; s.m = m;
+        s.absorb[0].kind = CHAN_ELEMS; s.absorb[0].ptr = d_ood; s.absorb[0].count = (uint32_t)(2 * m * W);
+        s.absorb[1].kind = CHAN_ELEMS; s.absorb[1].ptr = d_ood + 2 * m * W; s.absorb[1].count = (uint32_t)(m * ce);
         s.draw = CHAN_DRAW_DEEP; s.a = (uint32_t)W; s.b = (uint32_t)ce; s.per = CSTARK_CONV_DEEP_DRAWS_PER_REGISTER;
         s.count = (uint32_t)transcript::deep_draws(W, ce); s.out = d_deepc; s.out2 = d_scal;
         HIP_TRY(channel_step(s, st));
     }
-    {   // the quotient sums on coset 0, read from the channel's blocks
+    if (m == 1) { // the quotient sums on coset 0, read from the channel's blocks
         cs::DeepParams p{};
-        p.trace_lde = a->lde; p.comp_lde = R.clde; p.w = pw; p.coef = d_deepc; p.ood = d_ood; p.shifts = a->d_shifts; p.out = R.deep;
+        p.trace_lde = a->lde; p.comp_lde = R.clde; p.w = pw; p.coef = d_deepc; p.ood = d_ood; p.shifts = a->d_shifts; p.out = sums;
         p.width = (uint32_t)W; p.nb = (uint32_t)ce; p.log_n = log_n; p.k0 = 0; p.scal = d_scal;
         HIP_TRY(cs::deep_composition(p, 1, st));
+    } else {
+        RC_TRY(deep_composition_ext_dev(c, a->lde, R.clde, (uint32_t)W, (uint32_t)ce, m, d_deepc, d_ood, d_scal, a->d_shifts, sums, log_n, log_b, 1));
     }
-    RC_TRY(deep_extend(c, R, R.deep, dcoef));
+    RC_TRY(deep_extend(c, R, sums, dcoef));
     const hipEvent_t deep_done = a->ev[R.evi]; // the end of the DEEP stage: what the tail wait below sleeps on
     STAGE();
     // the layers' roots and the remainder land in the result block
@@ -947,7 +970,7 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
     STAGE();
     {   // remainder commitment, proof of work (none: nonce 1), query positions and their folded forms
         ChanStep s{};
-        s.seed = d_fri;
+        s.seed = d_fri; s.m = m;
         s.absorb[0].kind = CHAN_ELEMS; s.absorb[0].ptr = d_res + o_remainder; s.absorb[0].count = (uint32_t)rem_len; s.absorb[0].copy_out = d_res + o_rem;
         s.absorb[1].kind = CHAN_INT; s.absorb[1].value = 1;
         s.draw = CHAN_DRAW_QUERIES; s.count = (uint32_t)nq; s.log_domain = log_N; s.log_f = R.log_f; s.n_layers = n_layers; s.slot = 256;
@@ -961,7 +984,7 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
     const auto hp1 = std::chrono::steady_clock::now();
     HIP_TRY(cs::stream_wait_tail(st, deep_done)); // the only wait of the proof: sleep until the DEEP stage is done, poll through the FRI tail
     const auto hp2 = std::chrono::steady_clock::now();
-    a->timed = true;
+    a->timed = true; a->channel = CSTARK_CHANNEL_DEVICE;
     const uint8_t *h = a->h_open;
     const uint32_t *cnt = (const uint32_t *)(h + o_cnt);
     if (cnt[0] != nq) return fail(CSTARK_ERR_HIP, "device channel: the query positions could not be drawn");
@@ -984,7 +1007,7 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
 bool use_dev_channel(const cstark_options *opt, const AirJob &job) {
     static const bool host_env = [] { const char *e = getenv("CSTARK_HOST_CHANNEL"); return e && atoi(e) != 0; }();
     if (host_env || job.sharded || job.n_constraints > CSTARK_TX_NUM_CONSTRAINTS) return false;
-    if (opt->hash_fn != 0 || opt->field_extension != 0 || opt->grinding_factor != 0) return false;
+    if (opt->hash_fn != 0 || opt->field_extension > 2 || opt->grinding_factor != 0) return false;
     uint32_t lb = 0, lf = 0, lr = 0;
     while ((1u << lb) < opt->blowup_factor && lb < 8) lb++;
     while ((1u << lf) < opt->fri_folding_factor && lf < 8) lf++;
@@ -1684,6 +1707,13 @@ size_t cstark_tx_proof_size_bound(uint32_t n_tx, const cstark_options *opt) {
     const size_t nq = opt->num_queries, layers = log_N / log_f + 1, em = opt->field_extension + 1; // em: words per drawn-field element
     return 4096 + 32 * layers + (2 * 94 + 8) * 8 * em + nq * (94 * 8 + 8 * 8 * em + 2 * log_N * 32) +
            layers * (4 + nq * (((size_t)8 << log_f) * em + log_N * 32)) + 8 * em * (size_t)opt->fri_max_remainder;
+}
+
+int cstark_prove_channel(cstark_ctx *c, uint32_t *channel) {
+    if (!c || !channel) return fail(CSTARK_ERR_INVALID_ARG, "null argument");
+    if (!c->arena || !c->arena->timed) return fail(CSTARK_ERR_INVALID_ARG, "no proof has been generated on this context");
+    *channel = c->arena->channel;
+    return CSTARK_OK;
 }
 
 int cstark_prove_stage_ms(cstark_ctx *c, float *ms /* [CSTARK_PROVE_NUM_STAGES] */) {

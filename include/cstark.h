@@ -320,6 +320,15 @@ int cstark_tx_shard_finish(cstark_ctx *ctx, const uint64_t *d_rows, uint8_t *pro
  * stream; interpolate = registers 37..93 interpolated and extended, the wait for the ladders, registers 0..36 interpolated;
  * LDE = extension of registers 0..36.  Their sum is the time from the start of the proof to the complete extended trace. */
 int cstark_prove_stage_ms(cstark_ctx *ctx, float *ms /* [CSTARK_PROVE_NUM_STAGES] */);
+/* Which Fiat-Shamir channel the last proof of the generic prover on this context used (cstark_tx_prove, cstark_air_prove and the
+ * other single-proof entry points; the phases of a sharded proof count as CSTARK_CHANNEL_HOST).  DEVICE: every channel step ran as a
+ * kernel on the context's stream and the host waited once, for the finished proof -- Blake3 coin, grinding_factor 0, any field
+ * extension, at least one FRI layer.  HOST: the host absorbed every commitment and drew between the stages -- Sha3 coin, proof of work,
+ * sharded proofs, or CSTARK_HOST_CHANNEL=1 in the environment.  The proof bytes are the same either way.  Fails like
+ * cstark_prove_stage_ms when no proof has been generated on the context. */
+#define CSTARK_CHANNEL_HOST   0
+#define CSTARK_CHANNEL_DEVICE 1
+int cstark_prove_channel(cstark_ctx *ctx, uint32_t *channel);
 
 /* ---- standalone sub-AIRs (reference src/merkle/update, src/range; BASELINE configs 1-2) ---------- */
 /* MerkleProver::build_trace (src/merkle/update/prover.rs:28-80): 65 x (512*n_tx) from the uploaded witness. */

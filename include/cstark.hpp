@@ -74,6 +74,12 @@ class Context {
         check(cstark_prove_stage_ms(ctx_, ms.data()));
         return ms;
     }
+    // CSTARK_CHANNEL_HOST / CSTARK_CHANNEL_DEVICE: the Fiat-Shamir channel of the last proof on this context
+    uint32_t prove_channel() const {
+        uint32_t channel = CSTARK_CHANNEL_HOST;
+        check(cstark_prove_channel(ctx_, &channel));
+        return channel;
+    }
 
   private:
     cstark_ctx *ctx_ = nullptr;
