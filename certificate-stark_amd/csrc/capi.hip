@@ -53,8 +53,8 @@ int get_plan(cstark_ctx *c, unsigned log_n, const NttPlan **out) {
     HIP_TRY(cs::ntt_power_table(p.w, n, w, c->stream));
     HIP_TRY(cs::ntt_power_table(p.winv, n, cs::host::inv(w), c->stream));
     p.n_inv = cs::host::inv(cs::host::from_u64(n));
-    cs::NttV4Shape shape;
-    if (cs::ntt_v4_shape(log_n, &shape)) {
+    cs::NttThreeStepShape shape;
+    if (cs::ntt_three_step_shape(log_n, &shape)) { // here and in get_coset_table: the dense tables ntt_columns requires at exactly these sizes
         const size_t words = cs::ntt_aux_plan_words(shape);
         HIP_TRY(g.alloc(&p.aux_w, words * 8));
         HIP_TRY(g.alloc(&p.aux_winv, words * 8));
@@ -80,8 +80,8 @@ int get_coset_table(cstark_ctx *c, unsigned log_n, unsigned log_b, uint64_t offs
         HIP_TRY(cs::ntt_power_table(t.s + k * n, n, shift, c->stream));
         shift = cs::host::mul(shift, wbn);
     }
-    cs::NttV4Shape shape;
-    if (cs::ntt_v4_shape(log_n, &shape)) {
+    cs::NttThreeStepShape shape;
+    if (cs::ntt_three_step_shape(log_n, &shape)) {
         const NttPlan *p;
         RC_TRY(get_plan(c, log_n, &p));
         t.aux_words = cs::ntt_aux_coset_words(shape);
@@ -153,7 +153,6 @@ const size_t LDE_BATCH_WS_BYTES = [] {
     const long long mb = atoll(e);
     return mb <= 0 ? (size_t)0 : mb > (64ll << 10) ? (size_t)64 << 30 : (size_t)mb << 20;
 }();
-constexpr uint32_t LDE_COLUMN_GROUP = 1u << 30; // columns per group of the LDE (see lde_impl); 2^30 = all columns at once
 int lde_impl_inner(cstark_ctx *c, const uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols, uint32_t log_n,
                    uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk);
 int lde_impl(cstark_ctx *c, const uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols, uint32_t log_n, uint32_t log_blowup,
@@ -182,47 +181,34 @@ int lde_impl_inner(cstark_ctx *c, const uint64_t *d_coeffs, uint64_t *d_lde, uin
     RC_TRY(get_coset_table(c, log_n, log_blowup, domain_offset, &t));
     const size_t n = (size_t)1 << log_n;
     RC_TRY(ensure_ws(c, (size_t)width * n * 8));
-    // Optional column groups with the cosets inside (CSTARK_NTT_GROUP, tuning): the group's coefficients and the intermediate of
-    // the two-pass transform would then stay within the 256 MB Infinity Cache.  Measured on MI355X at 2^20 x 94 x 8: all columns
-    // at once 10.33 ms, groups of 32 / 16 / 8 / 4 columns 10.49 / 10.80 / 11.13 / 12.17 ms -- the transform is bound by its field
-    // multiplications (11 per element for 20 butterfly levels), not by HBM, so the default stays one launch pair per coset.
-    static const uint32_t group_env = [] { const char *e = getenv("CSTARK_NTT_GROUP"); return e ? (uint32_t)atoi(e) : 0u; }();
-    const uint32_t group = group_env ? group_env : LDE_COLUMN_GROUP;
-    // narrow tables (composition columns, periodic columns): all cosets in one launch pair -- the grid's batch dimension -- when the
-    // intermediate of every coset fits the workspace budget; 2 launches of nk x the workgroups instead of 2 nk small ones
-    if (nk > 1 && (size_t)nk * (group < ncols ? group : ncols) * n * 8 <= LDE_BATCH_WS_BYTES) {
-        // (with CSTARK_NTT_GROUP: column groups, all cosets of a group in one launch pair -- the group's intermediate, nk x group x n
-        // words, is then written and read back within a short window)
-        bool batched_ok = true;
-        for (uint32_t g0 = col0; g0 < col0 + ncols; g0 += group) {
-            const uint32_t gw = col0 + ncols - g0 < group ? col0 + ncols - g0 : group;
-            if (ensure_ws(c, (size_t)nk * gw * n * 8) != CSTARK_OK) { // no room for the batched intermediate: coset by coset below
-                (void)hipGetLastError();
-                if (g0 != col0) return fail(CSTARK_ERR_OOM, "workspace allocation failed in the middle of an extension");
-                batched_ok = false;
-                break;
-            }
-            cs::NttArgs a{};
-            a.in = d_coeffs + (size_t)g0 * n; a.scratch = (uint64_t *)c->ws; a.out = d_lde + (size_t)g0 * n;
-            a.width = gw; a.batch = nk; a.log_n = log_n;
-            a.w = p->w; a.prescale = t->s + (size_t)k0 * n; a.prescale_batch_stride = n; a.do_scale = false;
-            a.aux = p->aux_w; a.aux_ps = t->aux ? t->aux + (size_t)k0 * t->aux_words : nullptr; a.aux_ps_batch_stride = t->aux_words;
-            a.in_batch_stride = 0; a.scratch_batch_stride = (size_t)gw * n; a.out_batch_stride = (size_t)width * n;
+    // Measured on MI355X at 2^20 x 94 x 8 and dropped: column groups with the cosets inside, so that a group's coefficients and the
+    // intermediate of the two-pass transform stay within the 256 MB Infinity Cache -- all columns at once 10.33 ms, groups of 32 / 16 /
+    // 8 / 4 columns 10.49 / 10.80 / 11.13 / 12.17 ms: the transform is bound by its field multiplications, not by HBM.
+    cs::NttArgs a{};
+    a.in = d_coeffs + (size_t)col0 * n; a.scratch = (uint64_t *)c->ws;
+    a.width = ncols; a.log_n = log_n;
+    a.w = p->w; a.do_scale = false; a.aux = p->aux_w;
+    // all cosets in one launch pair -- the grid's batch dimension -- when the intermediate of every coset fits the workspace budget:
+    // 2 launches of nk x the workgroups instead of 2 nk small ones
+    if (nk > 1 && (size_t)nk * ncols * n * 8 <= LDE_BATCH_WS_BYTES) {
+        if (ensure_ws(c, (size_t)nk * ncols * n * 8) == CSTARK_OK) {
+            a.scratch = (uint64_t *)c->ws; a.out = d_lde + (size_t)col0 * n; a.batch = nk;
+            a.prescale = t->s + (size_t)k0 * n; a.prescale_batch_stride = n;
+            a.aux_ps = t->aux ? t->aux + (size_t)k0 * t->aux_words : nullptr; a.aux_ps_batch_stride = t->aux_words;
+            a.in_batch_stride = 0; a.scratch_batch_stride = (size_t)ncols * n; a.out_batch_stride = (size_t)width * n;
             HIP_TRY(cs::ntt_columns(a, c->stream));
+            return CSTARK_OK;
         }
-        if (batched_ok) return CSTARK_OK;
+        (void)hipGetLastError(); // no room for the batched intermediate: coset by coset
         RC_TRY(ensure_ws(c, (size_t)width * n * 8));
+        a.scratch = (uint64_t *)c->ws;
     }
-    for (uint32_t g0 = col0; g0 < col0 + ncols; g0 += group) {
-        const uint32_t gw = col0 + ncols - g0 < group ? col0 + ncols - g0 : group;
-        for (uint32_t k = k0; k < k0 + nk; k++) {
-            cs::NttArgs a{};
-            a.in = d_coeffs + (size_t)g0 * n; a.scratch = (uint64_t *)c->ws; a.out = d_lde + ((size_t)(k - k0) * width + g0) * n;
-            a.width = gw; a.batch = 1; a.log_n = log_n;
-            a.w = p->w; a.prescale = t->s + (size_t)k * n; a.do_scale = false;
-            a.aux = p->aux_w; a.aux_ps = t->aux ? t->aux + (size_t)k * t->aux_words : nullptr;
-            HIP_TRY(cs::ntt_columns(a, c->stream));
-        }
+    a.batch = 1;
+    for (uint32_t k = k0; k < k0 + nk; k++) {
+        a.out = d_lde + ((size_t)(k - k0) * width + col0) * n;
+        a.prescale = t->s + (size_t)k * n;
+        a.aux_ps = t->aux ? t->aux + (size_t)k * t->aux_words : nullptr;
+        HIP_TRY(cs::ntt_columns(a, c->stream));
     }
     return CSTARK_OK;
 }

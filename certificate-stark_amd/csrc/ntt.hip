@@ -16,7 +16,6 @@
 #include "fp.cuh"
 #include "hostfield.h"
 #include "../../include/cstark_conventions.h"
-#include <stdlib.h>
 #ifdef CS_NTT_NOMATH // measurement build (tools/build_variant_fast.py): the kernels' memory / LDS traffic without their field arithmetic
 #define fp_mul(a, b) ((a) ^ (b))
 #define fp_add(a, b) ((a) + (b))
@@ -128,9 +127,21 @@ __global__ __launch_bounds__(NT) void k_ntt_rows(const fp *__restrict__ in, fp *
 }
 
 // =====================================================================================================
-// v2 kernels for sub-transform sizes M = 2^(LA+LB) with LA, LB <= 5: every thread runs 2^LA- and 2^LB-point
-// transforms entirely in registers (compile-time twiddles, fully unrolled), with ONE exchange through LDS in
-// between.  L = 16 adjacent columns / rows per workgroup make every global access a 128-byte segment.
+// Register kernels for the three product sizes 2^16, 2^18 and 2^20 (three_step_size below): the same two passes with every
+// 2^LOGM-point sub-transform in THREE register steps of 2^LA, 2^LB and 2^LC points (LA >= LB >= LC; compile-time twiddles, fully
+// unrolled) and an exchange through LDS between two steps.  L2 = 8 adjacent columns / rows per workgroup make every global access a
+// 64-byte segment.  A thread holds 2^LA <= 16 elements, and a CU holds four waves per SIMD or more: the two-step kernels these replaced
+// (32 elements per thread, two waves per SIMD) spent half of their wave cycles waiting (rocprofv3: SQ_WAIT_ANY 22-39 %,
+// SQ_WAIT_INST_ANY 16-30 % of SQ_WAVE_CYCLES) because two waves per SIMD cannot cover global-load latency, LDS round trips and the
+// issue gaps of dependent v_mad_u64_u32 chains.
+//
+// Index algebra (w = w_M, M = 2^LOGM, T = 2^(LB+LC)):  r = r1 T + r2 2^LC + r3,  k = k1 + 2^LA k2 + 2^(LA+LB) k3
+//   step 1  (r2, r3) fixed: Y[k1]  = sum_r1 x[r] w_{2^LA}^(r1 k1),  then  * w^((r2 2^LC + r3) k1)
+//   step 2  (k1, r3) fixed: Z[k2]  = sum_r2 Y[k1; r2, r3] w_{2^LB}^(r2 k2),  then  * w^(2^LA r3 k2)
+//   step 3  (k1, k2) fixed: X[k3]  = sum_r3 Z[k1, k2; r3] w_{2^LC}^(r3 k3)
+// LDS tile: element (k1, q, l) at (k1 T + q) L2 + l (columns kernel) resp. ((k1 L2 + l)(T + 4) + q) (rows kernel), q = r2 2^LC + r3
+// after step 1; step 2 works in place and stores Z[k2] of task (k1, r3) at q = k2 2^LC + (r3 ^ (k2 mod 2^LC)) so that step 3's
+// reads (fixed r3, lanes over k2) fall into distinct banks.
 // -----------------------------------------------------------------------------------------------------
 // compile-time field arithmetic for the small twiddle tables
 __host__ __device__ constexpr uint64_t cx_mul(uint64_t a, uint64_t b) {
@@ -186,153 +197,12 @@ __host__ __device__ constexpr unsigned cx_brev(unsigned x, int bits) {
     return r;
 }
 
-#ifndef CS_NTT_L
-#define CS_NTT_L 8
-#endif
-constexpr int L2 = CS_NTT_L; // columns / rows per workgroup in the v2 kernels
+constexpr int L2 = 8; // columns / rows per workgroup of the register kernels: 64-byte global segments, and the tile of the largest size fits 64 KB of LDS
 // Workgroups are dealt to the 8 XCDs round-robin by linear id, and each XCD has its own L2.  With 64-byte tiles two
 // neighbouring tiles share every 128-byte line, so neighbours are given ids 8 apart: same XCD, dispatched back to back.
-// (The tile counts of the v2 sizes are multiples of 16.)
-__device__ __forceinline__ unsigned xcd_pair_tile(unsigned y) {
-    return L2 >= 16 ? y : ((y & ~15u) | ((y & 7u) << 1) | ((y >> 3) & 1u));
-}
+// (The tile counts of the three-step sizes are multiples of 16.)
+__device__ __forceinline__ unsigned xcd_pair_tile(unsigned y) { return (y & ~15u) | ((y & 7u) << 1) | ((y >> 3) & 1u); }
 
-// grid = (batch, C / L2, width): batch (coset) is the fastest grid dimension so that the workgroups re-reading the
-// same coefficient tile for different cosets run close in time (the re-reads are served by L2 / Infinity Cache).
-template <int LA, int LB, bool INV>
-__global__ __launch_bounds__(L2 << (LA > LB ? LA : LB)) void k_ntt_cols_v2(const fp *__restrict__ in, fp *__restrict__ out, unsigned log_n,
-                                                                          const fp *__restrict__ w, const fp *__restrict__ prescale,
-                                                                          size_t in_batch_stride, size_t out_batch_stride,
-                                                                          size_t prescale_batch_stride) {
-    constexpr int A = 1 << LA, B = 1 << LB, M = A * B, LOGM = LA + LB;
-    extern __shared__ __attribute__((aligned(16))) fp smem[];
-    fp *tile = smem;                           // [A][B + 1][L2]
-    fp *tw = smem + (size_t)A * (B + 1) * L2;  // [M] powers of w_M
-    const unsigned log_c = log_n - LOGM;
-    const size_t n = (size_t)1 << log_n;
-    const unsigned c0 = xcd_pair_tile(blockIdx.y) * L2;
-    const fp *src = in + blockIdx.x * in_batch_stride + (size_t)blockIdx.z * n;
-    fp *dst = out + blockIdx.x * out_batch_stride + (size_t)blockIdx.z * n;
-    const fp *ps = prescale ? prescale + blockIdx.x * prescale_batch_stride : nullptr;
-    const unsigned l = threadIdx.x % L2, t = threadIdx.x / L2;
-
-    for (unsigned e = threadIdx.x; e < M; e += blockDim.x) tw[e] = w[(size_t)e << log_c];
-    if (t < B) { // step 1: A-point transforms over r1 for fixed r2 = t (rows r = r1 * B + r2)
-        fp a[A];
-#pragma unroll
-        for (int r1 = 0; r1 < A; r1++) {
-            const size_t m = ((size_t)(r1 * B + t) << log_c) + c0 + l;
-            a[r1] = src[m];
-        }
-        if (ps) {
-            // coset scaling shift^m, m = r * C + c: the row part shift^(r*C) here (M-entry slice of the power table,
-            // cache resident); the column part shift^c commutes with the transform over r and is folded into the
-            // output factor below
-#pragma unroll
-            for (int r1 = 0; r1 < A; r1++) a[r1] = fp_mul(a[r1], ps[(size_t)(r1 * B + t) << log_c]);
-        }
-        reg_ntt_dif<LA, INV>(a);
-        __syncthreads(); // tw[] ready
-#pragma unroll
-        for (int p = 0; p < A; p++) {
-            const unsigned k1 = cx_brev(p, LA);
-            const fp v = (k1 == 0) ? a[p] : fp_mul(a[p], tw[k1 * t]);
-            tile[((size_t)k1 * (B + 1) + t) * L2 + l] = v;
-        }
-    } else {
-        __syncthreads();
-    }
-    __syncthreads();
-    if (t < A) { // step 2: B-point transforms over r2 for fixed k1 = t; output row k = k1 + A * k2
-        fp b[B];
-#pragma unroll
-        for (int r2 = 0; r2 < B; r2++) b[r2] = tile[((size_t)t * (B + 1) + r2) * L2 + l];
-        reg_ntt_dif<LB, INV>(b);
-        const unsigned c = c0 + l;
-        // output factor shift^c * w_n^(k*c), k = t + A*k2: a geometric sequence in k2 with ratio w_n^(A*c), generated
-        // in registers instead of gathering 8-byte entries of the 8 MB twiddle table
-        fp g = w[(size_t)t * c];
-        if (ps) g = fp_mul(g, ps[c]);
-        const fp ratio = w[(size_t)A * c];
-#pragma unroll
-        for (int k2 = 0; k2 < B; k2++) { // b[] holds the outputs in bit-reversed positions
-            dst[((size_t)(t + A * k2) << log_c) + c] = fp_mul(b[cx_brev(k2, LB)], g);
-            if (k2 + 1 < B) g = fp_mul(g, ratio);
-        }
-    }
-}
-
-// grid = (batch, R / L2, width).  in: rows [k1][c] (each row M contiguous); out: natural order k = k1 + R * k2.
-template <int LA, int LB, bool INV>
-__global__ __launch_bounds__(L2 << (LA > LB ? LA : LB)) void k_ntt_rows_v2(const fp *__restrict__ in, fp *__restrict__ out, unsigned log_n,
-                                                                          const fp *__restrict__ w, fp post_scale, int do_scale,
-                                                                          size_t in_batch_stride, size_t out_batch_stride) {
-    constexpr int A = 1 << LA, B = 1 << LB, M = A * B, LOGM = LA + LB;
-    extern __shared__ __attribute__((aligned(16))) fp smem[];
-    fp *tile = smem;                     // [L2][A][B] with the B index XOR-swizzled
-    fp *tw = smem + (size_t)L2 * A * B;  // [M]
-    const unsigned log_r = log_n - LOGM;
-    const size_t n = (size_t)1 << log_n;
-    const unsigned k10 = xcd_pair_tile(blockIdx.y) * L2;
-    const fp *src = in + blockIdx.x * in_batch_stride + (size_t)blockIdx.z * n;
-    fp *dst = out + blockIdx.x * out_batch_stride + (size_t)blockIdx.z * n;
-
-    for (unsigned e = threadIdx.x; e < M; e += blockDim.x) tw[e] = w[(size_t)e << log_r];
-    {   // step 1: task (l, c2) with c2 fastest across lanes (coalesced row reads): A-point transforms over c1
-        const unsigned c2 = threadIdx.x % B, l = threadIdx.x / B;
-        if (l < L2) {
-            fp a[A];
-#pragma unroll
-            for (int c1 = 0; c1 < A; c1++) a[c1] = src[((size_t)(k10 + l) << LOGM) + c1 * B + c2];
-            reg_ntt_dif<LA, INV>(a);
-            __syncthreads();
-#pragma unroll
-            for (int p = 0; p < A; p++) {
-                const unsigned j1 = cx_brev(p, LA);
-                const fp v = (j1 == 0) ? a[p] : fp_mul(a[p], tw[j1 * c2]);
-                const unsigned sw = (l | ((j1 % (32 / L2)) * L2)) & (B - 1);
-                tile[((size_t)l * A + j1) * B + (c2 ^ sw)] = v;
-            }
-        } else {
-            __syncthreads();
-        }
-    }
-    __syncthreads();
-    {   // step 2: task (j1, l) with l fastest across lanes (128-byte transposed stores): B-point transforms over c2
-        const unsigned l = threadIdx.x % L2, j1 = threadIdx.x / L2;
-        if (j1 < A) {
-            fp b[B];
-            const unsigned sw = (l | ((j1 % (32 / L2)) * L2)) & (B - 1);
-#pragma unroll
-            for (int c2 = 0; c2 < B; c2++) b[c2] = tile[((size_t)l * A + j1) * B + (c2 ^ sw)];
-            reg_ntt_dif<LB, INV>(b);
-#pragma unroll
-            for (int p = 0; p < B; p++) {
-                const unsigned k2 = j1 + A * cx_brev(p, LB);
-                fp v = b[p];
-                if (do_scale) v = fp_mul(v, post_scale);
-                dst[((size_t)k2 << log_r) + k10 + l] = v;
-            }
-        }
-    }
-}
-
-// =====================================================================================================
-// v4 kernels: the same two passes with every 2^LOGM-point sub-transform in THREE register steps (2^LA, 2^LB, 2^LC points,
-// LA >= LB >= LC) instead of two.  A thread then holds 2^LA = 16 elements instead of 32, a workgroup of the same tile
-// (L2 columns x 2^LOGM points, 64 KB of LDS) has twice the threads, and a CU holds four waves per SIMD instead of two:
-// the v2 kernels spent half of their wave cycles waiting (rocprofv3: SQ_WAIT_ANY 22-39 %, SQ_WAIT_INST_ANY 16-30 % of
-// SQ_WAVE_CYCLES) because two waves per SIMD cannot cover global-load latency, LDS round trips and the issue gaps of
-// dependent v_mad_u64_u32 chains.
-//
-// Index algebra (w = w_M, M = 2^LOGM, T = 2^(LB+LC)):  r = r1 T + r2 2^LC + r3,  k = k1 + 2^LA k2 + 2^(LA+LB) k3
-//   step 1  (r2, r3) fixed: Y[k1]  = sum_r1 x[r] w_{2^LA}^(r1 k1),  then  * w^((r2 2^LC + r3) k1)
-//   step 2  (k1, r3) fixed: Z[k2]  = sum_r2 Y[k1; r2, r3] w_{2^LB}^(r2 k2),  then  * w^(2^LA r3 k2)
-//   step 3  (k1, k2) fixed: X[k3]  = sum_r3 Z[k1, k2; r3] w_{2^LC}^(r3 k3)
-// LDS tile: element (k1, q, l) at (k1 T + q) L2 + l (columns kernel) resp. ((k1 L2 + l)(T + 4) + q) (rows kernel), q = r2 2^LC + r3
-// after step 1; step 2 works in place and stores Z[k2] of task (k1, r3) at q = k2 2^LC + (r3 ^ (k2 mod 2^LC)) so that step 3's
-// reads (fixed r3, lanes over k2) fall into distinct banks.
-// -----------------------------------------------------------------------------------------------------
 template <int LA, int LB, int LC>
 struct V4 {
     static constexpr int A = 1 << LA, Bn = 1 << LB, Cn = 1 << LC, T = Bn * Cn, M = A * T, LOGM = LA + LB + LC;
@@ -341,20 +211,99 @@ struct V4 {
     static constexpr int J3 = A / Cn;       // step-3 tasks (k1, k2) per thread
     static_assert(LA >= LB && LB >= LC && LC >= 1, "step sizes must not increase");
 };
-
-#ifndef CS_NTT_TILES
-#define CS_NTT_TILES 1
-#endif
-// Tiles per workgroup; with more than one the next tile's global loads are issued before the current tile's arithmetic.  Measured on
-// MI355X (2^20 x 94 x 8): the register prefetch pushes hipcc past the 128 VGPRs that four waves per SIMD allow (15-34 spilled
-// registers even behind scheduling barriers) and the extension takes 11.2 instead of 8.6 ms; the default stays 1.  Also measured and
-// dropped: steps 2 and 3 task by task inside one wave (the 64 lanes of a wave are the L2 columns x the 8 tasks of one k1, so no
-// workgroup barrier is needed after step 1) -- 9.2 ms: the per-task LDS round trips serialise; all cosets of a tile in one
+// One workgroup works on ONE tile.  Measured on MI355X (2^20 x 94 x 8) and dropped: several tiles per workgroup with the next tile's
+// global loads issued before the current tile's arithmetic -- the register prefetch pushes hipcc past the 128 VGPRs that four waves
+// per SIMD allow (15-34 spilled registers even behind scheduling barriers) and the extension takes 11.2 instead of 8.6 ms.  Also
+// measured and dropped: steps 2 and 3 task by task inside one wave (the 64 lanes of a wave are the L2 columns x the 8 tasks of one
+// k1, so no workgroup barrier is needed after step 1) -- 9.2 ms: the per-task LDS round trips serialise; all cosets of a tile in one
 // workgroup with the coefficients kept in registers -- 83 spilled registers.
-constexpr int V4_TILES = CS_NTT_TILES;
+
+// ---- the parts of a three-step pass, written as helpers.  Only the v5 kernels use them: the v4 kernels keep copies of their own, see their note
+// tw[e] = w_M^e, e < M, from the dense table of the pass (NttAux); all threads of the workgroup take part
+template <int LA, int LB, int LC>
+__device__ __forceinline__ void fill_twiddles(fp *tw, const fp *__restrict__ tab) {
+    using G = V4<LA, LB, LC>;
+    if (MB_NO_TWIDDLE_FILL) { for (unsigned e = threadIdx.x; e < G::M; e += G::NT) tw[e] = e; }
+    else for (unsigned e = threadIdx.x; e < G::M; e += G::NT) tw[e] = tab[e];
+}
+
+// The dense side tables of the column pass (ntt_build_aux_*), M = 2^log_r points per sub-transform, C = 2^log_c columns:
+//   aux               = [M] twiddles of this pass | [C] twiddles of the row pass | [C] ratios w_n^(A Bn c) | [A Bn][C] output factors w_n^(kb c)
+//   aux_ps (per coset) = [M] row part shift^(r C) of the prescale | [A Bn][C] output factors times the column part shift^c
+// aux_ps == nullptr: a transform without prescale.
+struct ColsTables { const fp *ps_row, *outf, *ratio; };
+template <int LA, int LB, int LC>
+__device__ __forceinline__ ColsTables cols_tables(const fp *__restrict__ aux, const fp *__restrict__ aux_ps, size_t aux_ps_batch_stride, unsigned bz,
+                                                  unsigned log_c) {
+    constexpr int M = V4<LA, LB, LC>::M;
+    ColsTables tb;
+    tb.ps_row = aux_ps ? aux_ps + bz * aux_ps_batch_stride : nullptr;
+    tb.outf = tb.ps_row ? tb.ps_row + M : aux + M + ((size_t)2 << log_c);
+    tb.ratio = aux + M + ((size_t)1 << log_c);
+    return tb;
+}
+
+// Step 1's inputs of the column pass: rows r = r1 T + t of column c, times the row part shift^(r C) of the coset power (the column
+// part shift^c is folded into the output factor)
+template <int LA, int LB, int LC>
+__device__ __forceinline__ void cols_load_prescaled(fp (&a)[1 << LA], const fp *__restrict__ src, const fp *__restrict__ ps_row, unsigned log_c, unsigned t,
+                                                    unsigned c) {
+    constexpr int A = V4<LA, LB, LC>::A, T = V4<LA, LB, LC>::T;
+    const unsigned lane_off = (t << log_c) + c; // uniform row base + 32-bit lane offset: one address register for all loads
+#pragma unroll
+    for (int r1 = 0; r1 < A; r1++) a[r1] = mb_load(src + ((size_t)(r1 * T) << log_c), lane_off, lane_off + r1);
+    if (!MB_NO_PRESCALE && ps_row) {
+#pragma unroll
+        for (int r1 = 0; r1 < A; r1++) a[r1] = fp_mul(a[r1], ps_row[r1 * T + t]);
+    }
+}
+
+// The column pass's epilogue for one step-3 task (kb = k1 + A k2, column c): x[] holds X[k3] in bit-reversed positions; output rows
+// k = kb + A Bn k3 take the factor shift^c w_n^(k c), a geometric sequence in k3 with ratio w_n^(A Bn c).  First factor and ratio come
+// from the dense tables: one 64-byte segment per (kb, tile) instead of 8 scattered sectors of the n-entry table.
+template <int LA, int LB, int LC>
+__device__ __forceinline__ void cols_store_task(const fp (&x)[1 << LC], unsigned kb, unsigned c, unsigned log_c, const ColsTables &tb, fp *__restrict__ dst) {
+    constexpr int A = V4<LA, LB, LC>::A, Bn = V4<LA, LB, LC>::Bn, Cn = V4<LA, LB, LC>::Cn;
+    fp g, ratio;
+    if (MB_NO_OUTPUT_FACTOR) { g = kb + c; ratio = c; }
+    else { g = tb.outf[((size_t)kb << log_c) + c]; ratio = tb.ratio[c]; }
+    const unsigned lane_off = (kb << log_c) + c; // uniform row base + 32-bit lane offset: one address register for all stores
+#pragma unroll
+    for (int k3 = 0; k3 < Cn; k3++) {
+        fp *row = dst + ((size_t)(A * Bn * k3) << log_c);
+        const fp val = fp_mul(x[cx_brev(k3, LC)], g);
+        mb_store(row, lane_off, val);
+        if (k3 + 1 < Cn) g = fp_mul(g, ratio);
+    }
+}
+
+// The row pass's step-3 stores for one task (kb = j1 + A j2, row l of the tile at dst_tile): x[p] = X[j3 = brev(p)] goes to output
+// frequency k2 = kb + A Bn j3, the transposition back to natural order
+template <int LA, int LB, int LC>
+__device__ __forceinline__ void rows_store_task(const fp (&x)[1 << LC], unsigned kb, unsigned l, unsigned log_r, fp post_scale, int do_scale,
+                                                fp *__restrict__ dst_tile) {
+    constexpr int A = V4<LA, LB, LC>::A, Bn = V4<LA, LB, LC>::Bn, Cn = V4<LA, LB, LC>::Cn;
+    const unsigned out_lane = (kb << log_r) + l;
+#pragma unroll
+    for (int p = 0; p < Cn; p++) {
+        fp val = x[p];
+        if (do_scale) val = fp_mul(val, post_scale);
+        mb_store(dst_tile + ((size_t)(A * Bn * cx_brev(p, LC)) << log_r), out_lane, val);
+    }
+}
+
+// ---- v4: whole-tile exchanges ------------------------------------------------------------------------------------------------------
+// k_ntt_cols_v4, k_ntt_rows_v4 and cols_v4_finish below still carry what the v5 kernels have shed: the table-less fallbacks behind
+// `aux == nullptr` (no caller reaches them: launch_three_step refuses a size without its tables) and the shape of the multi-tile
+// prefetch loop, run for one tile.  Rewritten onto the helpers above they compute the same and time the same alone, but SchnorrAir's
+// 2^18 proof, which runs narrow transforms next to the trace kernels of a second stream, measured 0.2 ms slower, and neither the
+// barrier positions nor the loop's scheduling barrier explained it (profiles/ntt_generations_ab.txt).  Until the cause is known they
+// keep this text.
+constexpr int V4_TILES = 1;
+
 
 // Steps 2 and 3 of the column pass on the tile in LDS (after step 1 stored Y * twiddle), including the output factor and the
-// stores.  t, l: this thread's position; kb-dependent factors from w / ps as in the v2 kernel.
+// stores.  t, l: this thread's position; kb-dependent factors from w / ps where the dense tables are absent.
 template <int LA, int LB, int LC, bool INV>
 __device__ __forceinline__ void cols_v4_finish(fp *tile, const fp *tw, const fp *__restrict__ w, const fp *__restrict__ ps, fp *__restrict__ dst,
                                                unsigned log_c, unsigned c, unsigned t, unsigned l, const fp *__restrict__ outf,
@@ -580,23 +529,16 @@ __global__ __launch_bounds__((V4<LA, LB, LC>::NT), 4) void k_ntt_rows_v4(const f
 // alone 5.55 ms, with its memory traffic alone 5.74 ms, together 8.0 ms for 94 columns x 8 cosets: two resident workgroups
 // overlap too little.)  Register need after the cheaper field product: 62 (rows) / 95 (columns) VGPRs.
 // -----------------------------------------------------------------------------------------------------
-#ifndef CS_NTT_V5_COLS_WAVES
-#define CS_NTT_V5_COLS_WAVES 5 // 95 VGPRs, no spills, two workgroups per CU; 6 (80 VGPRs, 8 spilled -> 30 % more HBM writes): LDE 7.80 vs 7.58 ms
-#endif
-#ifndef CS_NTT_V5_ROWS_WAVES
-#define CS_NTT_V5_ROWS_WAVES 6
-#endif
-#ifndef CS_NTT_V5_ROWS_TILES
-#define CS_NTT_V5_ROWS_TILES 1
-#endif
-// Tiles per workgroup of the row pass; > 1: the next tile's loads are issued once the first exchange has freed the data registers and
-// fly behind steps 2 and 3.  Measured (94 columns x 8 cosets): 1 tile, three workgroups per CU 7.85 ms; 4 tiles at four waves per
-// SIMD (128 VGPRs, 2 spilled) 8.27 ms; 2 tiles (16 spilled) 8.77 ms -- more resident workgroups beat the software prefetch again.
-constexpr int V5_ROWS_TILES = CS_NTT_V5_ROWS_TILES;
+constexpr int V5_COLS_WAVES = 5; // 95 VGPRs, no spills, two workgroups per CU; 6 (80 VGPRs, 8 spilled -> 30 % more HBM writes): LDE 7.80 vs 7.58 ms
+constexpr int V5_ROWS_WAVES = 6; // 62 VGPRs fit: three workgroups per CU
+// The row pass, too, takes one tile per workgroup.  Measured (94 columns x 8 cosets) and dropped: the next tile's loads issued once the
+// first exchange has freed the data registers -- 1 tile, three workgroups per CU 7.85 ms; 4 tiles at four waves per SIMD (128 VGPRs,
+// 2 spilled) 8.27 ms; 2 tiles (16 spilled) 8.77 ms: more resident workgroups beat the software prefetch again.
 template <int LA, int LB, int LC, bool INV>
-__global__ __launch_bounds__((V4<LA, LB, LC>::NT), CS_NTT_V5_COLS_WAVES) void k_ntt_cols_v5(
-    const fp *__restrict__ in, fp *__restrict__ out, unsigned log_n, const fp *__restrict__ w, const fp *__restrict__ prescale, size_t in_batch_stride,
-    size_t out_batch_stride, size_t prescale_batch_stride, const fp *__restrict__ aux, const fp *__restrict__ aux_ps, size_t aux_ps_batch_stride) {
+__global__ __launch_bounds__((V4<LA, LB, LC>::NT), V5_COLS_WAVES) void k_ntt_cols_v5(const fp *__restrict__ in, fp *__restrict__ out, unsigned log_n,
+                                                                                    size_t in_batch_stride, size_t out_batch_stride,
+                                                                                    const fp *__restrict__ aux, const fp *__restrict__ aux_ps,
+                                                                                    size_t aux_ps_batch_stride) {
     using G = V4<LA, LB, LC>;
     constexpr int A = G::A, Bn = G::Bn, Cn = G::Cn, T = G::T, M = G::M, LOGM = G::LOGM, AH = A / 2;
     static_assert(G::J2 == 2 && G::J3 == 2 && Bn == AH && Cn == AH, "two tasks per thread and step, one per half");
@@ -612,31 +554,13 @@ __global__ __launch_bounds__((V4<LA, LB, LC>::NT), CS_NTT_V5_COLS_WAVES) void k_
     const unsigned bz = blockIdx.y;
     const fp *src = in + bz * in_batch_stride + (size_t)blockIdx.z * n;
     fp *dst = out + bz * out_batch_stride + (size_t)blockIdx.z * n;
-    const fp *ps = prescale ? prescale + bz * prescale_batch_stride : nullptr;
     const unsigned l = threadIdx.x % L2, t = threadIdx.x / L2;
-    const fp *ps_row = (ps && aux_ps) ? aux_ps + bz * aux_ps_batch_stride : nullptr; // tables as in the v4 kernel
-    const fp *outf = !aux ? nullptr : ps ? (ps_row ? ps_row + M : nullptr) : aux + M + ((size_t)2 << log_c);
-    const fp *ratio_tab = aux ? aux + M + ((size_t)1 << log_c) : nullptr;
+    const ColsTables tb = cols_tables<LA, LB, LC>(aux, aux_ps, aux_ps_batch_stride, bz, log_c);
     const unsigned c = xcd_pair_tile(blockIdx.x) * L2 + l;
 
-    if (MB_NO_TWIDDLE_FILL) { for (unsigned e = threadIdx.x; e < M; e += G::NT) tw[e] = e; }
-    else if (aux) for (unsigned e = threadIdx.x; e < M; e += G::NT) tw[e] = aux[e];
-    else for (unsigned e = threadIdx.x; e < M; e += G::NT) tw[e] = w[(size_t)e << log_c];
+    fill_twiddles<LA, LB, LC>(tw, aux);
     fp a[A];
-    {
-        const unsigned lane_off = (t << log_c) + c;
-#pragma unroll
-        for (int r1 = 0; r1 < A; r1++) a[r1] = mb_load(src + ((size_t)(r1 * T) << log_c), lane_off, lane_off + r1);
-    }
-    if (MB_NO_PRESCALE) {
-    } else if (ps_row) { // row part shift^(r C) of the coset power; the column part shift^c is folded into the output factor
-#pragma unroll
-        for (int r1 = 0; r1 < A; r1++) a[r1] = fp_mul(a[r1], ps_row[r1 * T + t]);
-    } else if (ps) {
-        const unsigned ps_off = t << log_c;
-#pragma unroll
-        for (int r1 = 0; r1 < A; r1++) a[r1] = fp_mul(a[r1], (ps + ((size_t)(r1 * T) << log_c))[ps_off]);
-    }
+    cols_load_prescaled<LA, LB, LC>(a, src, tb.ps_row, log_c, t, c);
     reg_ntt_dif<LA, INV>(a); // step 1: rows r = r1 T + t; a[p] = Y[k1 = brev(p)]
     __syncthreads(); // tw[] ready
     const unsigned kh = t / Cn, r3 = t % Cn; // task h of this thread in step 2: k1 = kh + AH h, r3
@@ -669,36 +593,17 @@ __global__ __launch_bounds__((V4<LA, LB, LC>::NT), CS_NTT_V5_COLS_WAVES) void k_
         for (int q = 0; q < Cn; q++) x[q] = tile[((size_t)k1s * T + k2 * Cn + (q ^ (k2 % Cn))) * L2 + l];
         if (h == 0) __syncthreads(); // the half is rewritten by task 1
         reg_ntt_dif<LC, INV>(x);
-        // output factor shift^c w_n^(k c), k = (k1 + A k2) + A Bn k3: a geometric sequence in k3 with ratio w_n^(A Bn c)
-        const unsigned kb = (k1s + AH * h) + A * k2;
-        fp g, ratio;
-        if (MB_NO_OUTPUT_FACTOR) { g = kb + c; ratio = c; }
-        else if (outf) {
-            g = outf[((size_t)kb << log_c) + c];
-            ratio = ratio_tab[c];
-        } else {
-            g = w[(size_t)kb * c];
-            if (ps) g = fp_mul(g, ps[c]);
-            ratio = w[(size_t)(A * Bn) * c];
-        }
-        const unsigned lane_off = (kb << log_c) + c;
-#pragma unroll
-        for (int k3 = 0; k3 < Cn; k3++) {
-            fp *row = dst + ((size_t)(A * Bn * k3) << log_c);
-            const fp val = fp_mul(x[cx_brev(k3, LC)], g);
-            mb_store(row, lane_off, val);
-            if (k3 + 1 < Cn) g = fp_mul(g, ratio);
-        }
+        cols_store_task<LA, LB, LC>(x, (k1s + AH * h) + A * k2, c, log_c, tb, dst);
     }
 }
 
+// grid = (batch, R / L2, width), as k_ntt_rows_v4
 template <int LA, int LB, int LC, bool INV>
-__global__ __launch_bounds__((V4<LA, LB, LC>::NT), CS_NTT_V5_ROWS_WAVES) void k_ntt_rows_v5(const fp *__restrict__ in, fp *__restrict__ out, unsigned log_n,
-                                                                                           const fp *__restrict__ w, fp post_scale, int do_scale,
-                                                                                           size_t in_batch_stride, size_t out_batch_stride,
-                                                                                           const fp *__restrict__ aux_tw) {
+__global__ __launch_bounds__((V4<LA, LB, LC>::NT), V5_ROWS_WAVES) void k_ntt_rows_v5(const fp *__restrict__ in, fp *__restrict__ out, unsigned log_n,
+                                                                                    fp post_scale, int do_scale, size_t in_batch_stride,
+                                                                                    size_t out_batch_stride, const fp *__restrict__ aux_tw) {
     using G = V4<LA, LB, LC>;
-    constexpr int A = G::A, Bn = G::Bn, Cn = G::Cn, T = G::T, M = G::M, LOGM = G::LOGM, AH = A / 2;
+    constexpr int A = G::A, Bn = G::Bn, Cn = G::Cn, T = G::T, LOGM = G::LOGM, AH = A / 2;
     static_assert(G::J2 == 2 && G::J3 == 2 && Bn == AH && Cn == AH, "two tasks per thread and step, one per half");
     constexpr int TP = T + 4; // padded run of q per (j1, l), as in the v4 kernel
     extern __shared__ __attribute__((aligned(16))) fp smem[];
@@ -710,118 +615,93 @@ __global__ __launch_bounds__((V4<LA, LB, LC>::NT), CS_NTT_V5_ROWS_WAVES) void k_
     fp *dst = out + blockIdx.x * out_batch_stride + (size_t)blockIdx.z * n;
     const unsigned s1 = threadIdx.x % T, l1 = threadIdx.x / T; // step 1: s = c2 Cn + c3 fastest across lanes (coalesced row reads)
     const unsigned l = threadIdx.x % L2, t = threadIdx.x / L2; // steps 2 and 3: l fastest across lanes (64-byte transposed stores)
-    if (MB_NO_TWIDDLE_FILL) { for (unsigned e = threadIdx.x; e < M; e += G::NT) tw[e] = e; }
-    else if (aux_tw) for (unsigned e = threadIdx.x; e < M; e += G::NT) tw[e] = aux_tw[e];
-    else for (unsigned e = threadIdx.x; e < M; e += G::NT) tw[e] = w[(size_t)e << log_r];
+    const unsigned k10 = xcd_pair_tile(blockIdx.y) * L2;
     fp a[A];
     const unsigned in_lane = (l1 << LOGM) + s1;
-    {
-        const unsigned k10 = xcd_pair_tile(blockIdx.y * V5_ROWS_TILES) * L2;
 #pragma unroll
-        for (int c1 = 0; c1 < A; c1++) a[c1] = mb_load(src + ((size_t)k10 << LOGM) + c1 * T, in_lane, in_lane + c1);
-    }
+    for (int c1 = 0; c1 < A; c1++) a[c1] = mb_load(src + ((size_t)k10 << LOGM) + c1 * T, in_lane, in_lane + c1);
+    fill_twiddles<LA, LB, LC>(tw, aux_tw); // after the tile loads: with the fill first hipcc spills 2 of the 80 VGPRs six waves per SIMD allow
     const unsigned jh = t / Cn, c3 = t % Cn;
     const unsigned j1s = t / Bn, j2s = t % Bn;
-#pragma unroll 1
-    for (int it = 0; it < V5_ROWS_TILES; it++) {
-        const unsigned k10 = xcd_pair_tile(blockIdx.y * V5_ROWS_TILES + it) * L2;
-        reg_ntt_dif<LA, INV>(a); // step 1: columns c = c1 T + s
-        __syncthreads(); // tw[] ready / the previous tile's last reads are done
-        fp z[2][Bn];
+    reg_ntt_dif<LA, INV>(a); // step 1: columns c = c1 T + s
+    __syncthreads(); // tw[] ready
+    fp z[2][Bn];
 #pragma unroll
-        for (int h = 0; h < 2; h++) {
+    for (int h = 0; h < 2; h++) {
 #pragma unroll
-            for (int p = 0; p < A; p++) {
-                const unsigned j1 = cx_brev(p, LA);
-                if ((int)(j1 / AH) == h) tile[((size_t)(j1 % AH) * L2 + l1) * TP + s1] = (j1 == 0) ? a[p] : fp_mul(a[p], tw[j1 * s1]);
-            }
-            __syncthreads();
-#pragma unroll
-            for (int c2 = 0; c2 < Bn; c2++) z[h][c2] = tile[((size_t)jh * L2 + l) * TP + c2 * Cn + c3];
-            __syncthreads();
+        for (int p = 0; p < A; p++) {
+            const unsigned j1 = cx_brev(p, LA);
+            if ((int)(j1 / AH) == h) tile[((size_t)(j1 % AH) * L2 + l1) * TP + s1] = (j1 == 0) ? a[p] : fp_mul(a[p], tw[j1 * s1]);
         }
-        if (it + 1 < V5_ROWS_TILES) { // a[] is dead: the next tile's loads fly behind steps 2 and 3 of this one
-            const unsigned k11 = xcd_pair_tile(blockIdx.y * V5_ROWS_TILES + it + 1) * L2;
+        __syncthreads();
 #pragma unroll
-            for (int c1 = 0; c1 < A; c1++) a[c1] = (src + ((size_t)k11 << LOGM) + c1 * T)[in_lane];
+        for (int c2 = 0; c2 < Bn; c2++) z[h][c2] = tile[((size_t)jh * L2 + l) * TP + c2 * Cn + c3];
+        __syncthreads();
+    }
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        reg_ntt_dif<LB, INV>(z[h]);
+#pragma unroll
+        for (int p = 0; p < Bn; p++) {
+            const unsigned j2 = cx_brev(p, LB);
+            const fp v = (j2 == 0) ? z[h][p] : fp_mul(z[h][p], tw[(A * j2) * c3]);
+            tile[((size_t)jh * L2 + l) * TP + j2 * Cn + (c3 ^ (j2 % Cn))] = v;
         }
+        __syncthreads();
+        fp x[Cn];
 #pragma unroll
-        for (int h = 0; h < 2; h++) {
-            reg_ntt_dif<LB, INV>(z[h]);
-#pragma unroll
-            for (int p = 0; p < Bn; p++) {
-                const unsigned j2 = cx_brev(p, LB);
-                const fp v = (j2 == 0) ? z[h][p] : fp_mul(z[h][p], tw[(A * j2) * c3]);
-                tile[((size_t)jh * L2 + l) * TP + j2 * Cn + (c3 ^ (j2 % Cn))] = v;
-            }
-            __syncthreads();
-            fp x[Cn];
-#pragma unroll
-            for (int q = 0; q < Cn; q++) x[q] = tile[((size_t)j1s * L2 + l) * TP + j2s * Cn + (q ^ (j2s % Cn))];
-            if (h == 0) __syncthreads();
-            reg_ntt_dif<LC, INV>(x);
-            const unsigned out_lane = (((j1s + AH * h) + A * j2s) << log_r) + l; // output frequency k2 = j1 + A j2 + A Bn j3
-#pragma unroll
-            for (int p = 0; p < Cn; p++) {
-                fp val = x[p];
-                if (do_scale) val = fp_mul(val, post_scale);
-                mb_store(dst + ((size_t)(A * Bn * cx_brev(p, LC)) << log_r) + k10, out_lane, val);
-            }
-        }
+        for (int q = 0; q < Cn; q++) x[q] = tile[((size_t)j1s * L2 + l) * TP + j2s * Cn + (q ^ (j2s % Cn))];
+        if (h == 0) __syncthreads();
+        reg_ntt_dif<LC, INV>(x);
+        rows_store_task<LA, LB, LC>(x, (j1s + AH * h) + A * j2s, l, log_r, post_scale, do_scale, dst + k10);
     }
 }
 
-template <int RA, int RB, int RC, int CA, int CB, int CC, bool INV>
-hipError_t launch_v5(const NttArgs &a, hipStream_t stream) {
-    using GR = V4<RA, RB, RC>;
-    using GC = V4<CA, CB, CC>;
-    const size_t lds_a = ((size_t)GR::M / 2 * L2 + GR::M) * sizeof(fp);
-    const size_t lds_b = ((size_t)GC::A / 2 * L2 * (GC::T + 4) + GC::M) * sizeof(fp);
-    hipError_t e;
-    if ((e = hipFuncSetAttribute((const void *)k_ntt_rows_v5<CA, CB, CC, INV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_ntt_cols_v5<RA, RB, RC, INV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a)) != hipSuccess) return e;
-    hipLaunchKernelGGL((k_ntt_cols_v5<RA, RB, RC, INV>), dim3((unsigned)GC::M / L2, a.batch, a.width), dim3(GR::NT), lds_a, stream, a.in, a.scratch, a.log_n,
-                       a.w, a.prescale, a.in_batch_stride, a.scratch_batch_stride, a.prescale_batch_stride, a.aux, a.prescale ? a.aux_ps : nullptr,
-                       a.aux_ps_batch_stride);
-    static_assert((GR::M / L2) % V5_ROWS_TILES == 0, "tiles per workgroup");
-    hipLaunchKernelGGL((k_ntt_rows_v5<CA, CB, CC, INV>), dim3(a.batch, (unsigned)GR::M / L2 / V5_ROWS_TILES, a.width), dim3(GC::NT), lds_b, stream, (const fp *)a.scratch,
-                       a.out, a.log_n, a.w, a.post_scale, a.do_scale ? 1 : 0, a.scratch_batch_stride, a.out_batch_stride,
-                       a.aux ? a.aux + GR::M : nullptr);
-    return hipGetLastError();
+// The sizes served by the three-step kernels -- the ONE list: both passes of n = 2^(2 LOGM) points split LOGM = LA + LB + LC, with
+// whole-tile (v4) or half-tile (v5) exchanges.  ntt_three_step_shape and ntt_columns both read it.
+template <int LA_, int LB_, int LC_, bool HALF_TILE_>
+struct ThreeStep { static constexpr int LA = LA_, LB = LB_, LC = LC_; static constexpr bool HALF_TILE = HALF_TILE_; };
+template <class F>
+bool three_step_size(unsigned log_n, F &&f) {
+    switch (log_n) {
+    case 20: f(ThreeStep<4, 3, 3, true>{}); return true;
+    case 18: f(ThreeStep<3, 3, 3, false>{}); return true;
+    case 16: f(ThreeStep<3, 3, 2, false>{}); return true;
+    default: return false;
+    }
 }
 
-template <int RA, int RB, int RC, int CA, int CB, int CC, bool INV>
-hipError_t launch_v4(const NttArgs &a, hipStream_t stream) {
-    using GR = V4<RA, RB, RC>;
-    using GC = V4<CA, CB, CC>;
-    const size_t lds_a = ((size_t)GR::M * L2 + GR::M) * sizeof(fp);
-    const size_t lds_b = ((size_t)GC::A * L2 * (GC::T + 4) + GC::M) * sizeof(fp);
-    static_assert((GC::M / L2) % V4_TILES == 0 && (GR::M / L2) % V4_TILES == 0, "tiles per workgroup");
+// Both passes of one three-step size.  The dense tables are not optional: get_plan / get_coset_table (capi.hip) build them for
+// exactly the sizes of three_step_size, and a caller that comes without them is refused -- there is no slower table-less path.
+template <class S, bool INV>
+hipError_t launch_three_step(const NttArgs &a, hipStream_t stream) {
+    using G = V4<S::LA, S::LB, S::LC>;
+    if (!a.aux || (a.prescale && !a.aux_ps)) return hipErrorInvalidValue;
+    constexpr int HALVES = S::HALF_TILE ? 2 : 1; // the tile in LDS holds all or half of the 2^LA k1 classes
+    const size_t lds_cols = ((size_t)G::M / HALVES * L2 + G::M) * sizeof(fp);
+    const size_t lds_rows = ((size_t)G::A / HALVES * L2 * (G::T + 4) + G::M) * sizeof(fp);
+    const dim3 grid_cols((unsigned)G::M / L2, a.batch, a.width), grid_rows(a.batch, (unsigned)G::M / L2, a.width);
+    const fp *aux_ps = a.prescale ? a.aux_ps : nullptr;
     hipError_t e;
-    if ((e = hipFuncSetAttribute((const void *)k_ntt_rows_v4<CA, CB, CC, INV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_ntt_cols_v4<RA, RB, RC, INV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a)) != hipSuccess) return e;
-    hipLaunchKernelGGL((k_ntt_cols_v4<RA, RB, RC, INV>), dim3((unsigned)GC::M / L2 / V4_TILES, a.batch, a.width), dim3(GR::NT), lds_a, stream, a.in,
-                       a.scratch, a.log_n, a.w, a.prescale, a.in_batch_stride, a.scratch_batch_stride, a.prescale_batch_stride, a.aux,
-                       a.prescale ? a.aux_ps : nullptr, a.aux_ps_batch_stride);
-    hipLaunchKernelGGL((k_ntt_rows_v4<CA, CB, CC, INV>), dim3(a.batch, (unsigned)GR::M / L2 / V4_TILES, a.width), dim3(GC::NT), lds_b, stream,
-                       (const fp *)a.scratch, a.out, a.log_n, a.w, a.post_scale, a.do_scale ? 1 : 0, a.scratch_batch_stride, a.out_batch_stride,
-                       a.aux ? a.aux + GR::M : nullptr);
-    return hipGetLastError();
-}
-
-template <int LRA, int LRB, int LCA, int LCB, bool INV>
-hipError_t launch_v2(const NttArgs &a, hipStream_t stream) {
-    constexpr int LOG_R = LRA + LRB, LOG_C = LCA + LCB;
-    constexpr int TA = L2 << (LRA > LRB ? LRA : LRB), TB = L2 << (LCA > LCB ? LCA : LCB);
-    const size_t lds_a = ((size_t)(1 << LRA) * ((1 << LRB) + 1) * L2 + (1 << LOG_R)) * sizeof(fp);
-    const size_t lds_b = ((size_t)L2 * (1 << LOG_C) + (1 << LOG_C)) * sizeof(fp);
-    hipError_t e;
-    if ((e = hipFuncSetAttribute((const void *)k_ntt_cols_v2<LRA, LRB, INV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void *)k_ntt_rows_v2<LCA, LCB, INV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b)) != hipSuccess) return e;
-    hipLaunchKernelGGL((k_ntt_cols_v2<LRA, LRB, INV>), dim3(a.batch, (1u << LOG_C) / L2, a.width), dim3(TA), lds_a, stream, a.in, a.scratch, a.log_n,
-                       a.w, a.prescale, a.in_batch_stride, a.scratch_batch_stride, a.prescale_batch_stride);
-    hipLaunchKernelGGL((k_ntt_rows_v2<LCA, LCB, INV>), dim3(a.batch, (1u << LOG_R) / L2, a.width), dim3(TB), lds_b, stream,
-                       (const fp *)a.scratch, a.out, a.log_n, a.w, a.post_scale, a.do_scale ? 1 : 0, a.scratch_batch_stride, a.out_batch_stride);
+    if constexpr (S::HALF_TILE) {
+        const auto k_cols = k_ntt_cols_v5<S::LA, S::LB, S::LC, INV>;
+        const auto k_rows = k_ntt_rows_v5<S::LA, S::LB, S::LC, INV>;
+        if ((e = hipFuncSetAttribute((const void *)k_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows)) != hipSuccess) return e;
+        if ((e = hipFuncSetAttribute((const void *)k_cols, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cols)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_cols, grid_cols, dim3(G::NT), lds_cols, stream, a.in, a.scratch, a.log_n, a.in_batch_stride, a.scratch_batch_stride, a.aux,
+                           aux_ps, a.aux_ps_batch_stride);
+        hipLaunchKernelGGL(k_rows, grid_rows, dim3(G::NT), lds_rows, stream, (const fp *)a.scratch, a.out, a.log_n, a.post_scale, a.do_scale ? 1 : 0,
+                           a.scratch_batch_stride, a.out_batch_stride, a.aux + G::M);
+    } else {
+        const auto k_cols = k_ntt_cols_v4<S::LA, S::LB, S::LC, INV>;
+        const auto k_rows = k_ntt_rows_v4<S::LA, S::LB, S::LC, INV>;
+        if ((e = hipFuncSetAttribute((const void *)k_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows)) != hipSuccess) return e;
+        if ((e = hipFuncSetAttribute((const void *)k_cols, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cols)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_cols, grid_cols, dim3(G::NT), lds_cols, stream, a.in, a.scratch, a.log_n, a.w, a.prescale, a.in_batch_stride,
+                           a.scratch_batch_stride, a.prescale_batch_stride, a.aux, aux_ps, a.aux_ps_batch_stride);
+        hipLaunchKernelGGL(k_rows, grid_rows, dim3(G::NT), lds_rows, stream, (const fp *)a.scratch, a.out, a.log_n, a.w, a.post_scale, a.do_scale ? 1 : 0,
+                           a.scratch_batch_stride, a.out_batch_stride, a.aux + G::M);
+    }
     return hipGetLastError();
 }
 
@@ -835,20 +715,19 @@ __global__ void k_power_table(fp *table, size_t n, fp base) {
     for (int i = 0; i < CHUNK && e0 + i < n; i++) { table[e0 + i] = x; x = fp_mul(x, base); }
 }
 
+// The generic pass pair with L columns / rows per workgroup
 template <int L>
-hipError_t launch(const fp *in, fp *scratch, fp *out, unsigned width, unsigned batch, unsigned log_n, const fp *w, const fp *prescale,
-                  size_t prescale_batch_stride, fp post_scale, bool do_scale, size_t in_batch_stride, size_t scratch_batch_stride,
-                  size_t out_batch_stride, hipStream_t stream) {
-    const unsigned log_r = (log_n + 1) / 2, log_c = log_n - log_r;
+hipError_t launch(const NttArgs &a, hipStream_t stream) {
+    const unsigned log_r = (a.log_n + 1) / 2, log_c = a.log_n - log_r;
     const unsigned R = 1u << log_r, C = 1u << log_c;
     const size_t lds_a = ((size_t)R * L + R / 2) * sizeof(fp), lds_b = ((size_t)C * L + C / 2) * sizeof(fp);
     hipError_t e;
     if ((e = hipFuncSetAttribute((const void *)k_ntt_cols<L>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void *)k_ntt_rows<L>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ntt_cols<L>, dim3(C / L, width, batch), dim3(NT), lds_a, stream, in, scratch, log_n, log_r, w, prescale,
-                       in_batch_stride, scratch_batch_stride, prescale_batch_stride);
-    hipLaunchKernelGGL(k_ntt_rows<L>, dim3(R / L, width, batch), dim3(NT), lds_b, stream, (const fp *)scratch, out, log_n, log_r, w,
-                       post_scale, do_scale ? 1 : 0, scratch_batch_stride, out_batch_stride);
+    hipLaunchKernelGGL(k_ntt_cols<L>, dim3(C / L, a.width, a.batch), dim3(NT), lds_a, stream, a.in, a.scratch, a.log_n, log_r, a.w, a.prescale,
+                       a.in_batch_stride, a.scratch_batch_stride, a.prescale_batch_stride);
+    hipLaunchKernelGGL(k_ntt_rows<L>, dim3(R / L, a.width, a.batch), dim3(NT), lds_b, stream, (const fp *)a.scratch, a.out, a.log_n, log_r, a.w,
+                       a.post_scale, a.do_scale ? 1 : 0, a.scratch_batch_stride, a.out_batch_stride);
     return hipGetLastError();
 }
 
@@ -1034,18 +913,16 @@ hipError_t coset_combine(const fp *d_b, fp *d_h, unsigned log_n, unsigned log_b,
     return hipGetLastError();
 }
 
-// ---- compact tables of the v4 kernels --------------------------------------------------------------------------------
+// ---- compact tables of the three-step kernels ------------------------------------------------------------------------
 // The twiddles of a sub-transform, the row part of a coset's prescale and the output factors of the column pass are strided or
 // scattered entries of the n-entry tables (w[e << log_c], s[r << log_c], w[kb c]): 8 useful bytes per 64-byte sector and, for the
 // output factors, one sector per lane.  Gathered once per table into dense arrays, a workgroup reads them as a handful of
 // contiguous lines: 2.3 k instead of 5 k sector requests per column-pass workgroup.
-bool ntt_v4_shape(unsigned log_n, NttV4Shape *s) {
-    static const bool v2_env = [] { const char *e = getenv("CSTARK_NTT_V2"); return e && atoi(e) != 0; }();
-    if (v2_env) return false;
-    if (log_n == 20) { *s = {10, 10, 7}; return true; }
-    if (log_n == 18) { *s = {9, 9, 6}; return true; }
-    if (log_n == 16) { *s = {8, 8, 6}; return true; }
-    return false;
+bool ntt_three_step_shape(unsigned log_n, NttThreeStepShape *s) {
+    return three_step_size(log_n, [s](auto split) {
+        using S = decltype(split);
+        *s = {S::LA + S::LB + S::LC, S::LA + S::LB + S::LC, S::LA + S::LB}; // both passes over 2^LOGM points; kb = k1 + 2^LA k2
+    });
 }
 namespace {
 // plan block: [R] w^(e C) | [C] w^(e R) | [C] w^(KB c) | [KB][C] w^(kb c)
@@ -1071,13 +948,13 @@ __global__ void k_aux_coset(fp *aux, const fp *__restrict__ w, const fp *__restr
     }
 }
 } // namespace
-size_t ntt_aux_plan_words(const NttV4Shape &s) { return ((size_t)1 << s.log_r) + ((size_t)2 << s.log_c) + ((size_t)1 << (s.log_c + s.log_kb)); }
-size_t ntt_aux_coset_words(const NttV4Shape &s) { return ((size_t)1 << s.log_r) + ((size_t)1 << (s.log_c + s.log_kb)); }
-hipError_t ntt_build_aux_plan(fp *d_aux, const fp *d_w, const NttV4Shape &s, hipStream_t stream) {
+size_t ntt_aux_plan_words(const NttThreeStepShape &s) { return ((size_t)1 << s.log_r) + ((size_t)2 << s.log_c) + ((size_t)1 << (s.log_c + s.log_kb)); }
+size_t ntt_aux_coset_words(const NttThreeStepShape &s) { return ((size_t)1 << s.log_r) + ((size_t)1 << (s.log_c + s.log_kb)); }
+hipError_t ntt_build_aux_plan(fp *d_aux, const fp *d_w, const NttThreeStepShape &s, hipStream_t stream) {
     hipLaunchKernelGGL(k_aux_plan, dim3(256), dim3(256), 0, stream, d_aux, d_w, s.log_r, s.log_c, s.log_kb);
     return hipGetLastError();
 }
-hipError_t ntt_build_aux_coset(fp *d_aux, const fp *d_w, const fp *d_s, const NttV4Shape &s, hipStream_t stream) {
+hipError_t ntt_build_aux_coset(fp *d_aux, const fp *d_w, const fp *d_s, const NttThreeStepShape &s, hipStream_t stream) {
     hipLaunchKernelGGL(k_aux_coset, dim3(256), dim3(256), 0, stream, d_aux, d_w, d_s, s.log_r, s.log_c, s.log_kb);
     return hipGetLastError();
 }
@@ -1090,23 +967,15 @@ hipError_t ntt_power_table(fp *d_table, size_t n, fp base, hipStream_t stream) {
 
 hipError_t ntt_columns(const NttArgs &a, hipStream_t stream) {
     if (a.log_n < NTT_MIN_LOG_N || a.log_n > NTT_MAX_LOG_N) return hipErrorInvalidValue;
-    // register-tiled kernels for the production sizes; `inverse` selects the compile-time small twiddles
-    static const bool v2_env = [] { const char *e = getenv("CSTARK_NTT_V2"); return e && atoi(e) != 0; }(); // tuning / debugging: two-step kernels
-    static const bool v4_env = [] { const char *e = getenv("CSTARK_NTT_V4"); return e && atoi(e) != 0; }(); // tuning / debugging: whole-tile exchanges
-    if (a.log_n == 20 && !v2_env && !v4_env) return a.inverse ? launch_v5<4, 3, 3, 4, 3, 3, true>(a, stream) : launch_v5<4, 3, 3, 4, 3, 3, false>(a, stream);
-    if (a.log_n == 20 && !v2_env) return a.inverse ? launch_v4<4, 3, 3, 4, 3, 3, true>(a, stream) : launch_v4<4, 3, 3, 4, 3, 3, false>(a, stream);
-    if (a.log_n == 20) return a.inverse ? launch_v2<5, 5, 5, 5, true>(a, stream) : launch_v2<5, 5, 5, 5, false>(a, stream);
-    if (a.log_n == 18 && !v2_env) return a.inverse ? launch_v4<3, 3, 3, 3, 3, 3, true>(a, stream) : launch_v4<3, 3, 3, 3, 3, 3, false>(a, stream);
-    if (a.log_n == 16 && !v2_env) return a.inverse ? launch_v4<3, 3, 2, 3, 3, 2, true>(a, stream) : launch_v4<3, 3, 2, 3, 3, 2, false>(a, stream);
-    if (a.log_n == 18) return a.inverse ? launch_v2<5, 4, 5, 4, true>(a, stream) : launch_v2<5, 4, 5, 4, false>(a, stream);
-    if (a.log_n == 16) return a.inverse ? launch_v2<4, 4, 4, 4, true>(a, stream) : launch_v2<4, 4, 4, 4, false>(a, stream);
-    // L = 8 keeps global segments at 64 bytes; sub-transforms above 2^11 points need the narrower tile to fit LDS
-    const unsigned log_r = (a.log_n + 1) / 2;
-    if (log_r <= 11)
-        return launch<8>(a.in, a.scratch, a.out, a.width, a.batch, a.log_n, a.w, a.prescale, a.prescale_batch_stride, a.post_scale,
-                         a.do_scale, a.in_batch_stride, a.scratch_batch_stride, a.out_batch_stride, stream);
-    return launch<4>(a.in, a.scratch, a.out, a.width, a.batch, a.log_n, a.w, a.prescale, a.prescale_batch_stride, a.post_scale, a.do_scale,
-                     a.in_batch_stride, a.scratch_batch_stride, a.out_batch_stride, stream);
+    // register kernels for the product sizes; `inverse` selects the compile-time small twiddles
+    hipError_t e = hipSuccess;
+    if (three_step_size(a.log_n, [&](auto split) {
+            using S = decltype(split);
+            e = a.inverse ? launch_three_step<S, true>(a, stream) : launch_three_step<S, false>(a, stream);
+        }))
+        return e;
+    // every other size: L = 8 keeps global segments at 64 bytes; sub-transforms above 2^11 points need the narrower tile to fit LDS
+    return (a.log_n + 1) / 2 <= 11 ? launch<8>(a, stream) : launch<4>(a, stream);
 }
 
 } // namespace cs

@@ -67,6 +67,21 @@ def test_product_does_not_reference_the_oracle():
                 assert not pat.search(txt), (dirpath, f)
 
 
+def test_retired_transform_switches_are_named_nowhere():
+    """The transforms have one kernel family per size: the switches that selected older generations (and the column groups of the
+    extension) are gone from the package sources and from the documentation.  profiles/history/ is history and keeps them."""
+    gone = re.compile(r"CSTARK_NTT_(V2|V4|GROUP)")
+    files = []
+    for top in ("certificate-stark_amd", "include", "tools"):
+        for dirpath, _, names in os.walk(os.path.join(ROOT, top)):
+            files += [os.path.join(dirpath, f) for f in names if f.endswith((".py", ".hip", ".h", ".cuh", ".cpp", ".sh"))]
+    files += [os.path.join(ROOT, f) for f in os.listdir(ROOT) if f.endswith(".md")]
+    files.append(os.path.join(ROOT, "profiles", "README.md"))
+    assert len(files) > 40 and any(f.endswith("ntt.hip") for f in files) and any(f.endswith("DESIGN.md") for f in files)
+    named = [os.path.relpath(f, ROOT) for f in files if gone.search(open(f, errors="replace").read())]
+    assert not named, named
+
+
 def test_host_air_description_matches_oracle(oracle):
     lib = _lib()
     base, cyc = oracle.tx_constraint_degrees()

@@ -65,3 +65,18 @@ def test_full_size_roundtrip_2_20(oracle, backend):
     assert (to_numpy_u64(co[0]) == co_ref[0]).all()
     ref = oracle.lde_columns(co_ref, 3, k0=3, nk=1)
     assert (lde0[0, 0] == ref[0, 0]).all()
+
+
+def test_both_columns_every_point_2_20(oracle, backend):
+    """The 2^20 size has kernels of its own (half-tile exchanges).  Two random columns, every point of both compared with the oracle:
+    the inverse transform (its own dense tables), then cosets 5 and 6 of the blowup-8 extension in one launch pair -- the batched grid
+    dimension, the per-coset stride of the prescale tables and a non-zero first coset."""
+    from certificate_stark_amd.backend import to_numpy_u64
+    ev = _rand(oracle, (2, 1 << 20), 2021)
+    co_ref = oracle.interpolate_columns(ev)
+    co = backend.interpolate_columns(backend.from_numpy_u64(ev))
+    assert (to_numpy_u64(co) == co_ref).all()
+    part_ref = oracle.lde_columns(co_ref, 3, k0=5, nk=2)
+    part = backend.lde_columns(co, 3, k0=5, nk=2)
+    assert part_ref.shape == (2, 2, 1 << 20)
+    assert (to_numpy_u64(part) == part_ref).all()
