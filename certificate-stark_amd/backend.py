@@ -213,7 +213,7 @@ class Backend:
         return out
 
     # ---- standalone sub-AIRs (MerkleAir, RangeProofAir) ----
-    AIR_MERKLE, AIR_SCHNORR, AIR_RANGE, AIR_RESCUE_CHAIN = 1, 2, 3, 4
+    AIR_TRANSACTION, AIR_MERKLE, AIR_SCHNORR, AIR_RANGE, AIR_RESCUE_CHAIN = 0, 1, 2, 3, 4
 
     def rescue_chain_build_trace(self, seed, chain_length):
         """cstark_rescue_chain_build_trace: 14 x 8 * chain_length (benches/rescue.rs:277-322); seed: 7 elements, memory form"""
@@ -572,8 +572,42 @@ class Backend:
         del keep
         return verdicts
 
+    def air_verify(self, proofs, airs, public_inputs=None, options=None, numbers=None):
+        """cstark_air_verify: proofs of TransactionAir, MerkleAir, RangeProofAir and RescueAir (bytes, any mix) in one call.  airs: the AIR
+        each proof is expected to be (Backend.AIR_*; one value for all, or one per proof).  public_inputs: [count][14] words (or [14] for
+        every proof), memory form -- initial root | final root, seed | result, or the range number in word 0.  numbers (instead of
+        public_inputs, RangeProofAir only): one number for all proofs or [count] numbers.  options: as for tx_verify.  Returns the verdicts, int32 [count]; SchnorrAir proofs are UNSUPPORTED."""
+        count = len(proofs)
+        verdicts = np.zeros(count, np.int32)
+        if count == 0:
+            return verdicts
+        keep = [bytes(p) for p in proofs]
+        ptrs = (C.POINTER(C.c_uint8) * count)()
+        lens = (C.c_size_t * count)()
+        for i, p in enumerate(keep):
+            ptrs[i] = C.cast(C.c_char_p(p), C.POINTER(C.c_uint8))
+            lens[i] = len(p)
+        ids = np.ascontiguousarray(np.broadcast_to(np.asarray(airs, np.int32).reshape(-1), (count,)))
+        if (numbers is None) == (public_inputs is None):
+            raise ValueError("give public_inputs ([count][14] or [14]) or numbers (RangeProofAir), not both")
+        if numbers is not None:
+            if (ids != self.AIR_RANGE).any():
+                raise ValueError("numbers= states RangeProofAir proofs only")
+            pub = np.zeros((count, 14), np.uint64)
+            pub[:, 0] = np.broadcast_to(np.asarray(numbers, np.uint64).reshape(-1), (count,))
+        else:
+            pub = np.asarray(public_inputs, np.uint64)
+            if pub.ndim not in (1, 2) or pub.shape[-1] != 14:
+                raise ValueError("public_inputs must be [count][14] or [14]")
+            pub = np.ascontiguousarray(np.broadcast_to(pub.reshape(-1, 14), (count, 14)))
+        o = None if options is None else C.byref(self._options_struct(options))
+        check(self.lib.cstark_air_verify(self.ctx, C.c_uint32(count), ptrs, lens, ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         pub.ctypes.data_as(u64p), o, verdicts.ctypes.data_as(C.POINTER(C.c_int32))))
+        del keep
+        return verdicts
+
     def verify_h2d_bytes(self):
-        """bytes the last tx_verify copied host -> device: proof bytes, descriptors and opening records"""
+        """bytes the last tx_verify / air_verify copied host -> device: proof bytes, descriptors and opening records"""
         n = C.c_uint64(0)
         check(self.lib.cstark_verify_h2d_bytes(self.ctx, C.byref(n)))
         return int(n.value)

@@ -1817,7 +1817,7 @@ __device__ __forceinline__ void merkle_transitions(Acc &acc, const Frame &f) {
     // periodic layout: setup, hash(tx), hash_input, finish, hash_mask, ark[28]; the gadget templates read the round
     // constants at P_ARK + i relative to per_p, so give them a view shifted by (5 - P_ARK) columns
     Frame fr = f;
-    fr.per_p = f.per_p - (size_t)(P_ARK - 5) * 512;
+    fr.per_p = f.per_p - (size_t)(P_ARK - 5) * f.pcycle;
     const fp setup = f.pv(0), tx_hash = f.pv(1), hash_input = f.pv(2), finish = f.pv(3), hash_flag = f.pv(4);
 #pragma unroll 1
     for (int i = 0; i < 12; i++) {
@@ -2293,16 +2293,32 @@ __global__ __launch_bounds__(FNT, 3) void k_merkle_rounds(AirCombineParams p, co
 }
 
 // RangeProofAir::evaluate_transition  src/range/air.rs:60-98 (enforce_double_and_add_step with flag ONE)
+template <class Acc>
+__device__ __forceinline__ void range_transitions(Acc &acc, const Frame &f) {
+    const fp nb = f.next(0);
+    acc.add(1, FP_ONE, fp_sub(f.next(1), fp_add(fp_dbl(f.cur(1)), nb))); // result[1]: accumulator
+    acc.add(0, FP_ONE, c_is_binary(nb));                                 // result[0]: bit
+}
+// every slot is written once, under the flag ONE: a plain store, no zero-filled output
+struct AccSet {
+    fp *out;
+    size_t n;
+    __device__ __forceinline__ void add(int i, fp, fp val) { out[(size_t)i * n] = val; }
+};
 __global__ void k_eval_transitions_range(const fp *lde, fp *out, unsigned log_n) {
     const size_t n = (size_t)1 << log_n;
     const size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (j >= n) return;
     const unsigned kk = blockIdx.y;
     const fp *base = lde + (size_t)kk * 2 * n;
-    const size_t jn = (j + 1) & (n - 1);
-    const fp nb = base[jn];
-    out[((size_t)kk * 2 + 1) * n + j] = fp_sub(base[n + jn], fp_add(fp_dbl(base[n + j]), nb)); // result[1]: accumulator
-    out[((size_t)kk * 2 + 0) * n + j] = c_is_binary(nb);                                         // result[0]: bit
+    Frame f;
+    f.n = n;
+    f.cur_p = base + j;
+    f.next_p = base + ((j + 1) & (n - 1));
+    f.per_p = nullptr;
+    f.pcycle = 0;
+    AccSet acc{out + (size_t)kk * 2 * n + j, n};
+    range_transitions(acc, f);
 }
 
 struct AssertShifts { fp s[8]; };
@@ -2478,6 +2494,17 @@ hipError_t launch_merkle_fused(const AirCombineParams &p, const uint64_t *ptab, 
 }
 // RescueAir::evaluate_transition, benches/rescue.rs:200-222 (+ enforce_hash_copy :254-264): the round gadget under the cycle mask, the
 // copy of the rate half / reset of the capacity half under its complement.  ptab: [b][29][8] (mask, 28 round constants)
+template <class Acc>
+__device__ __forceinline__ void rescue_transitions(Acc &acc, const Frame &f) {
+    const fp hash_flag = f.pv(0), copy_flag = c_not(hash_flag);
+    Frame fr = f; // the gadget reads the round constants at P_ARK + i relative to per_p: a view shifted by (1 - P_ARK) columns
+    fr.per_p = f.per_p - (size_t)(P_ARK - 1) * f.pcycle;
+    enforce_round(acc, fr, 0, 0, hash_flag, 0, 0, false);
+    for (int i = 0; i < 7; i++) {
+        acc.add(i, copy_flag, fp_sub(f.cur(i), f.next(i)));
+        acc.add(7 + i, copy_flag, f.next(7 + i));
+    }
+}
 __global__ __launch_bounds__(NT) void k_eval_transitions_rescue(const fp *lde, const fp *ptab, fp *out, unsigned log_n, unsigned k0) {
     const size_t n = (size_t)1 << log_n;
     const size_t j = blockIdx.x * (size_t)NT + threadIdx.x;
@@ -2491,14 +2518,37 @@ __global__ __launch_bounds__(NT) void k_eval_transitions_rescue(const fp *lde, c
     f.per_p = ptab + (size_t)(k0 + kk) * 29 * 8 + (j & 7);
     f.pcycle = 8;
     AccAll acc{out + (size_t)kk * 14 * n + j, n};
-    const fp hash_flag = f.pv(0), copy_flag = c_not(hash_flag);
-    Frame fr = f; // the gadget reads the round constants at P_ARK + i relative to per_p: a view shifted by (1 - P_ARK) columns
-    fr.per_p = f.per_p - (size_t)(P_ARK - 1) * 8;
-    enforce_round(acc, fr, 0, 0, hash_flag, 0, 0, false);
-    for (int i = 0; i < 7; i++) {
-        acc.add(i, copy_flag, fp_sub(f.cur(i), f.next(i)));
-        acc.add(7 + i, copy_flag, f.next(7 + i));
-    }
+    rescue_transitions(acc, f);
+}
+// The sub-AIRs' evaluators on free-standing frames, as k_eval_frames for TransactionAir: frame j is cur[c * nf + j], next[c * nf + j],
+// per[c * nf + j]; the AIR's NC slots out[i * nf + j] are zeroed here, then accumulated.  One lane per frame.
+template <int AIR, int NC>
+__global__ __launch_bounds__(NT) void k_eval_frames_sub(const fp *__restrict__ cur, const fp *__restrict__ next, const fp *__restrict__ per,
+                                                        fp *__restrict__ out, unsigned nf) {
+    const unsigned j = blockIdx.x * NT + threadIdx.x;
+    if (j >= nf) return;
+    Frame f;
+    f.n = nf;
+    f.cur_p = cur + j;
+    f.next_p = next + j;
+    f.per_p = per + j;
+    f.pcycle = nf;
+#pragma unroll 1
+    for (int i = 0; i < NC; i++) out[(size_t)i * nf + j] = 0;
+    AccAll acc{out + j, nf};
+    if (AIR == 1) merkle_transitions(acc, f);
+    else if (AIR == 3) range_transitions(acc, f);
+    else rescue_transitions(acc, f);
+}
+hipError_t launch_eval_frames_air(int air, const uint64_t *cur, const uint64_t *next, const uint64_t *per, uint64_t *out, unsigned nf, hipStream_t stream) {
+    if (nf == 0) return hipSuccess;
+    const dim3 grid((nf + NT - 1) / NT), block(NT);
+    if (air == 0) hipLaunchKernelGGL(k_eval_frames, grid, block, 0, stream, cur, next, per, out, nf);
+    else if (air == 1) hipLaunchKernelGGL((k_eval_frames_sub<1, 106>), grid, block, 0, stream, cur, next, per, out, nf);
+    else if (air == 3) hipLaunchKernelGGL((k_eval_frames_sub<3, 2>), grid, block, 0, stream, cur, next, per, out, nf);
+    else if (air == 4) hipLaunchKernelGGL((k_eval_frames_sub<4, 14>), grid, block, 0, stream, cur, next, per, out, nf);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
 }
 hipError_t launch_eval_transitions_rescue(const uint64_t *lde, const uint64_t *ptab, uint64_t *out, unsigned log_n, unsigned k0, unsigned nk,
                                           hipStream_t stream) {

@@ -1,11 +1,13 @@
-// TransactionExample::verify (src/lib.rs:144-150) for proofs in this library's own layout (include/cstark.h, "Proof
-// layout"), many proofs per call.  Pipeline of one chunk of proofs:
+// TransactionExample::verify (src/lib.rs:144-150) and the sub-AIR examples' verify (MerkleAir, RangeProofAir, RescueAir) for proofs in this
+// library's own layout (include/cstark.h, "Proof layout"), many proofs per call, any mix of AIRs: what differs between the AIRs is the
+// VAir record of each proof's descriptor, the constraint bodies (constraints.hip) and the cached periodic coefficients.  SchnorrAir is
+// not verified (UNSUPPORTED).  Pipeline of one chunk of proofs:
 //   host    parse (structure only: every count against the stated options) and the per-proof constants of the domains; the raw
 //           proof bytes and one descriptor per proof go to one pinned staging block -> ONE host-to-device copy
 //   device  transcript replay, one workgroup per proof (Blake3 or Sha3 coin, vhash.cuh): coefficients, z, DEEP coefficients, layer
 //           alphas, remainder commitment, proof of work, query positions and their folded positions and slots
-//           per extension degree m present: out-of-domain frames (periodic columns at z^(n/1024) from cached coefficients, the frame
-//           sampled along t -> e(t) for m > 1) -> the 115 constraints on every frame (constraints.hip, launch_eval_frames) -> merge
+//           per (AIR, extension degree m) present: out-of-domain frames (periodic columns at z^(n/cycle) from cached coefficients, the frame
+//           sampled along t -> e(t) for m > 1) -> the AIR's constraints on every frame (constraints.hip, launch_eval_frames_air) -> merge
 //           and compare with sum_i H_i z^i; DEEP + FRI, one lane per (proof, query)
 //           all proofs: Merkle openings, one lane per opened row (leaf hash + path walk, Blake3 or Sha3); remainder degree (exact,
 //           one workgroup per component); reduction to one verdict per proof -> ONE device-to-host copy
@@ -13,7 +15,9 @@
 // reduction takes the smallest.  The number of launches per chunk does not depend on the number of proofs.
 #include <hip/hip_runtime.h>
 #include <string.h>
+#include <assert.h>
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <vector>
 #include "../../include/cstark.h"
@@ -37,19 +41,27 @@ enum : uint32_t {
     RK_REMAINDER_FOLDING = 2000, RK_REMAINDER_DEGREE = 2001,
     RK_NONE = 0xffffffffu
 };
-constexpr uint32_t TX_W = 94, TX_CE = 8, TX_NC = 115, TX_NA = 4;
 
 // ---- what the device reads --------------------------------------------------------------------------------------------------------
-// Offsets (in words) of the replayed transcript block of a proof (device memory, written by k_vfy_transcript): z | t_alpha, t_beta [115] | b_alpha, b_beta [4] | DEEP alpha, beta [94]
-// | delta [8] | deg_a | deg_b | layer alphas [L] (all m words each) | constants | positions [nq] | slots [L][nq] | folded positions [L][nq]
+// What the pipeline knows of an AIR (host: air_desc; every proof's descriptor carries a copy): trace width | composition columns =
+// constraint-evaluation blowup | transition constraints | single-row assertions | public words in the channel seed | periodic columns
+// and the binary logarithm of their cycle | the first asserted register.  Assertion a < na / 2 is on register areg + a at row 0,
+// assertion na / 2 + a on the same register at row n - 1; their values are the descriptor's K_PUB words, in that order.
+struct VAir { uint32_t air, w, ce, nc, na, npub, nper, log_cycle, areg; };
+constexpr uint32_t VMAX_NC = 115, VMAX_NPER = 48, VMAX_GROUPS = 8;
+// the degree-adjustment group of every constraint of one AIR (k_vfy_ood_check's argument; the exponents are K_ADJ of the proof)
+struct VGroups { uint8_t n, g[VMAX_NC]; };
+
+// Offsets (in words) of the replayed transcript block of a proof (device memory, written by k_vfy_transcript): z | t_alpha, t_beta [nc] | b_alpha, b_beta [na] | DEEP alpha, beta [w]
+// | delta [ce] | deg_a | deg_b | layer alphas [L] (all m words each) | constants | positions [nq] | slots [L][nq] | folded positions [L][nq]
 struct TOff { uint32_t z, ta, tb, ba, bb, da, db, dd, dga, dgb, alpha, k, pos, slot, lpos, st, words; };
-enum { K_WN, K_WNN, K_WLAST, K_G, K_ADJ /* 5 */, K_BADJ = K_ADJ + 5, K_INVF, K_ZETA_INV, K_WRINV, K_PUB /* 4 */, K_WL = K_PUB + 4 /* [L] */, K_WORDS = K_WL + VMAX_LAYERS };
-__host__ __device__ inline TOff toff(uint32_t m, uint32_t L, uint32_t nq) {
+enum { K_WN, K_WNN, K_WLAST, K_G, K_ADJ /* [VMAX_GROUPS] */, K_BADJ = K_ADJ + 8, K_INVF, K_ZETA_INV, K_WRINV, K_PUB /* [14] */, K_WL = K_PUB + 14 /* [L] */, K_WORDS = K_WL + VMAX_LAYERS };
+__host__ __device__ inline TOff toff(const VAir &a, uint32_t m, uint32_t L, uint32_t nq) {
     TOff t;
     uint32_t o = 0;
     t.z = o; o += m;
-    t.ta = o; o += TX_NC * m; t.tb = o; o += TX_NC * m; t.ba = o; o += TX_NA * m; t.bb = o; o += TX_NA * m;
-    t.da = o; o += TX_W * m; t.db = o; o += TX_W * m; t.dd = o; o += TX_CE * m; t.dga = o; o += m; t.dgb = o; o += m;
+    t.ta = o; o += a.nc * m; t.tb = o; o += a.nc * m; t.ba = o; o += a.na * m; t.bb = o; o += a.na * m;
+    t.da = o; o += a.w * m; t.db = o; o += a.w * m; t.dd = o; o += a.ce * m; t.dga = o; o += m; t.dgb = o; o += m;
     t.alpha = o; o += L * m;
     t.k = o; o += K_WORDS;
     t.pos = o; o += nq; t.slot = o; o += L * nq; t.lpos = o; o += L * nq;
@@ -62,13 +74,16 @@ struct VDesc {
     uint64_t base;   // byte offset of the proof in the chunk's block (8-aligned)
     uint64_t tb;     // word offset of its transcript block in the device region
     uint64_t k[K_WORDS];  // constants of its domains (host; copied to the transcript block)
-    uint64_t pub[14];     // initial root | final root, memory form
+    uint64_t pub[14];     // the public words of the channel seed, memory form (a.npub of them)
+    uint64_t pcoef;       // word offset of the AIR's periodic coefficients [a.nper][2^a.log_cycle] in the cache
+    VAir a;
     uint32_t ood, trows, tpaths, crows, cpaths, rem;                 // byte offsets inside the proof
     uint32_t lrows[VMAX_LAYERS];
-    uint32_t log_n, log_N, nq, log_f, n_layers, m, R, log_b, depth_slot, hash, grinding, log_rem, npos[VMAX_LAYERS];
+    uint32_t log_n, log_N, nq, log_f, n_layers, m, R, log_b, hash, grinding, log_rem, npos[VMAX_LAYERS];
     uint32_t slot0;     // result slots: [0] out-of-domain, then openings, then nq queries, then m remainder components
-    uint32_t n_open, frame0;
+    uint32_t n_open;
 };
+__device__ __forceinline__ TOff toff(const VDesc &d) { return toff(d.a, d.m, d.n_layers, d.nq); }
 struct VOpen {
     uint32_t proof, row, path, root; // row / path / root: byte offsets inside the proof
     uint32_t words, depth, layer, t, rank, slot, hash; // layer = VNO_LAYER: trace / composition row of query t; else row t of that layer
@@ -154,7 +169,7 @@ __global__ __launch_bounds__(128) void k_vfy_openings(const uint8_t *__restrict_
     const VDesc &d = desc[o.proof];
     const uint8_t *pb = buf + d.base;
     const uint64_t *tb = tbase + d.tb;
-    const TOff to = toff(d.m, d.n_layers, d.nq);
+    const TOff to = toff(d);
     bool canonical = true, match = true;
     uint32_t idx = 0, rank = o.rank;
     if (o.layer == VNO_LAYER) idx = (uint32_t)tb[to.pos + o.t];
@@ -206,40 +221,42 @@ __global__ __launch_bounds__(128) void k_vfy_openings(const uint8_t *__restrict_
     slots[o.slot] = !canonical ? (uint32_t)RK_MALFORMED : match ? (uint32_t)RK_NONE : rank;
 }
 
-// Out-of-domain frames of the proofs gp[0..G) (one workgroup each): periodic values at z^(n/1024) from the coefficient table of the
-// proof's Merkle depth, then K frames t = 0..K-1 whose entries are e(t) = sum_q e_q t^q (K = 1 for m = 1); frame j of the group at
+// Out-of-domain frames of the proofs gp[0..G) of one AIR (one workgroup each): periodic values at z^(n / cycle) from the proof's
+// coefficient table in the cache (none for an AIR without periodic columns), then K frames t = 0..K-1 whose entries are e(t) = sum_q e_q t^q (K = 1 for m = 1); frame j of the group at
 // column stride F.  bad[g] = 1 if an out-of-domain word is not below p.
 template <int M>
 __global__ __launch_bounds__(128) void k_vfy_ood_frames(const uint8_t *__restrict__ buf, const VDesc *__restrict__ desc, const uint32_t *__restrict__ gp,
                                                         const uint64_t *__restrict__ tbase, const uint64_t *__restrict__ pcoef, uint32_t K, uint32_t F, fp *__restrict__ cur,
                                                         fp *__restrict__ nxt, fp *__restrict__ per, uint32_t *__restrict__ bad) {
-    __shared__ Ext<M> pv[48];
+    __shared__ Ext<M> pv[VMAX_NPER];
     const VDesc &d = desc[gp[blockIdx.x]];
     const uint8_t *pb = buf + d.base;
     const uint64_t *tb = tbase + d.tb;
-    const TOff to = toff(d.m, d.n_layers, d.nq);
+    const TOff to = toff(d);
     const uint32_t tid = threadIdx.x;
     bool ok = true;
-    for (uint32_t i = tid; i < (2 * TX_W + TX_CE) * M; i += 128) ok &= ld64(pb + d.ood + 8 * i) < FP_P;
+    const uint32_t W = d.a.w, NP = d.a.nper;
+    for (uint32_t i = tid; i < (2 * W + d.a.ce) * M; i += 128) ok &= ld64(pb + d.ood + 8 * i) < FP_P;
     const int any_bad = __syncthreads_or(!ok);
-    if (tid < 48) {
+    if (tid < NP) {
         Ext<M> zp = x_load<M>(tb + to.z);
-        for (uint32_t s = 10; s < d.log_n; s++) zp = x_mul(zp, zp);
-        const uint64_t *co = pcoef + ((size_t)d.depth_slot * 48 + tid) * 1024;
+        for (uint32_t s = d.a.log_cycle; s < d.log_n; s++) zp = x_mul(zp, zp);
+        const uint32_t cycle = 1u << d.a.log_cycle;
+        const uint64_t *co = pcoef + d.pcoef + (size_t)tid * cycle;
         Ext<M> acc = x_zero<M>();
-        for (int i = 1023; i >= 0; i--) { acc = x_mul(acc, zp); acc.c[0] = fp_add(acc.c[0], co[i]); }
+        for (int i = (int)cycle - 1; i >= 0; i--) { acc = x_mul(acc, zp); acc.c[0] = fp_add(acc.c[0], co[i]); }
         pv[tid] = acc;
     }
     __syncthreads();
     if (tid == 0) bad[blockIdx.x] = any_bad ? 1u : 0u;
     const uint32_t f0 = blockIdx.x * K;
-    for (uint32_t e = tid; e < K * (2 * TX_W + 48); e += 128) {
-        const uint32_t t = e / (2 * TX_W + 48), c = e % (2 * TX_W + 48);
+    for (uint32_t e = tid; e < K * (2 * W + NP); e += 128) {
+        const uint32_t t = e / (2 * W + NP), c = e % (2 * W + NP);
         Ext<M> v;
         fp *dst;
-        if (c < TX_W) { v = ld_ext<M>(pb + d.ood + 8 * M * c); dst = cur + (size_t)c * F; }
-        else if (c < 2 * TX_W) { v = ld_ext<M>(pb + d.ood + 8 * M * c); dst = nxt + (size_t)(c - TX_W) * F; }
-        else { v = pv[c - 2 * TX_W]; dst = per + (size_t)(c - 2 * TX_W) * F; }
+        if (c < W) { v = ld_ext<M>(pb + d.ood + 8 * M * c); dst = cur + (size_t)c * F; }
+        else if (c < 2 * W) { v = ld_ext<M>(pb + d.ood + 8 * M * c); dst = nxt + (size_t)(c - W) * F; }
+        else { v = pv[c - 2 * W]; dst = per + (size_t)(c - 2 * W) * F; }
         const fp tt = fp_from_u64(t);
         fp r = v.c[M - 1];
         for (int q = M - 2; q >= 0; q--) r = fp_add(fp_mul(r, tt), v.c[q]);
@@ -249,28 +266,28 @@ __global__ __launch_bounds__(128) void k_vfy_ood_frames(const uint8_t *__restric
 
 template <int M> struct Lagrange { uint64_t w[18][M]; };
 
-// One lane per proof of the group: recombine the sampled constraint values, merge (transition divisor, degree adjustments, the four
-// boundary terms) and compare with sum_i H_i z^i.
+// One lane per proof of the group (one AIR, one extension degree): recombine the sampled constraint values, merge (transition divisor,
+// degree adjustments, the AIR's single-row assertions) and compare with sum_i H_i z^i over the AIR's ce columns.
 template <int M>
 __global__ __launch_bounds__(64) void k_vfy_ood_check(const uint8_t *__restrict__ buf, const VDesc *__restrict__ desc, const uint32_t *__restrict__ gp,
                                                       uint32_t G, uint32_t K, uint32_t F, const fp *__restrict__ cvals, const uint32_t *__restrict__ bad,
-                                                      Lagrange<M> lag, const uint64_t *__restrict__ tbase, uint32_t *__restrict__ slots) {
+                                                      Lagrange<M> lag, VGroups grps, const uint64_t *__restrict__ tbase, uint32_t *__restrict__ slots) {
     const uint32_t g = blockIdx.x * 64 + threadIdx.x;
     if (g >= G) return;
     const VDesc &d = desc[gp[g]];
     const uint8_t *pb = buf + d.base;
     const uint64_t *tb = tbase + d.tb;
-    const TOff to = toff(d.m, d.n_layers, d.nq);
+    const TOff to = toff(d);
     const uint64_t *k = tb + to.k;
     const Ext<M> z = x_load<M>(tb + to.z);
-    // constraint i's merge coefficient alpha_i + beta_i z^adj: the five degree groups one after the other (z^adj in registers)
+    // constraint i's merge coefficient alpha_i + beta_i z^adj: the AIR's degree groups one after the other (z^adj in registers)
     Ext<M> acc = x_zero<M>();
 #pragma unroll 1
-    for (int grp = 0; grp < 5; grp++) {
+    for (uint32_t grp = 0; grp < grps.n; grp++) {
         const Ext<M> za = x_pow(z, k[K_ADJ + grp]);
 #pragma unroll 1
-        for (uint32_t i = 0; i < TX_NC; i++) {
-            if (tx_degree_group(i) != grp) continue;
+        for (uint32_t i = 0; i < d.a.nc; i++) {
+            if (grps.g[i] != grp) continue;
             Ext<M> cv = x_zero<M>();
             for (uint32_t j = 0; j < K; j++) cv = x_add(cv, x_scale(x_load<M>(lag.w[j]), cvals[(size_t)i * F + g * K + j]));
             const Ext<M> coef = x_add(x_load<M>(tb + to.ta + M * i), x_mul(x_load<M>(tb + to.tb + M * i), za));
@@ -284,23 +301,25 @@ __global__ __launch_bounds__(64) void k_vfy_ood_check(const uint8_t *__restrict_
     acc = x_mul(acc, x_mul(x_sub(z, x_base<M>(w_last)), x_inv(x_sub(zn, one))));
     const Ext<M> xb = x_pow(z, k[K_BADJ]);
     Ext<M> first = x_zero<M>(), last = x_zero<M>();
-    for (int a = 0; a < 2; a++) {
-        const Ext<M> c = ld_ext<M>(pb + d.ood + 8 * M * (58 + a));
+    const uint32_t hn = d.a.na / 2;
+#pragma unroll 1
+    for (uint32_t a = 0; a < hn; a++) {
+        const Ext<M> c = ld_ext<M>(pb + d.ood + 8 * M * (d.a.areg + a));
         first = x_add(first, x_mul(x_sub(c, x_base<M>(k[K_PUB + a])), x_add(x_load<M>(tb + to.ba + M * a), x_mul(x_load<M>(tb + to.bb + M * a), xb))));
-        last = x_add(last, x_mul(x_sub(c, x_base<M>(k[K_PUB + 2 + a])),
-                                 x_add(x_load<M>(tb + to.ba + M * (2 + a)), x_mul(x_load<M>(tb + to.bb + M * (2 + a)), xb))));
+        last = x_add(last, x_mul(x_sub(c, x_base<M>(k[K_PUB + hn + a])),
+                                 x_add(x_load<M>(tb + to.ba + M * (hn + a)), x_mul(x_load<M>(tb + to.bb + M * (hn + a)), xb))));
     }
     const Ext<M> lhs = x_add(acc, x_add(x_mul(first, x_inv(x_sub(z, one))), x_mul(last, x_inv(x_sub(z, x_base<M>(w_last))))));
     Ext<M> rhs = x_zero<M>(), zi = one;
-    for (uint32_t i = 0; i < TX_CE; i++) {
-        rhs = x_add(rhs, x_mul(ld_ext<M>(pb + d.ood + 8 * M * (2 * TX_W + i)), zi));
+    for (uint32_t i = 0; i < d.a.ce; i++) {
+        rhs = x_add(rhs, x_mul(ld_ext<M>(pb + d.ood + 8 * M * (2 * d.a.w + i)), zi));
         zi = x_mul(zi, z);
     }
     slots[d.slot0] = bad[g] ? (uint32_t)RK_MALFORMED : x_eq(lhs, rhs) ? (uint32_t)RK_NONE : (uint32_t)RK_OOD;
 }
 
 // One lane per (proof, query): DEEP value at x = g w_N^pos, then every layer -- the value against the opened row, the fold of the row
-// -- and finally the remainder.  Slots and positions come from the host's replay and were checked against the layer's row count.
+// -- and finally the remainder (a proof without a layer: the DEEP value against the remainder directly).  Slots and positions come from the host's replay and were checked against the layer's row count.
 template <int M>
 __global__ __launch_bounds__(128) void k_vfy_fri(const uint8_t *__restrict__ buf, const VDesc *__restrict__ desc, const uint32_t *__restrict__ gp,
                                                  const uint64_t *__restrict__ tbase, uint32_t *__restrict__ slots) {
@@ -309,7 +328,7 @@ __global__ __launch_bounds__(128) void k_vfy_fri(const uint8_t *__restrict__ buf
     if (q >= d.nq) return;
     const uint8_t *pb = buf + d.base;
     const uint64_t *tb = tbase + d.tb;
-    const TOff to = toff(d.m, d.n_layers, d.nq);
+    const TOff to = toff(d);
     const uint64_t *k = tb + to.k;
     uint32_t pos = (uint32_t)tb[to.pos + q];
     const fp g = k[K_G];
@@ -317,17 +336,18 @@ __global__ __launch_bounds__(128) void k_vfy_fri(const uint8_t *__restrict__ buf
     const Ext<M> z = x_load<M>(tb + to.z);
     const Ext<M> zw = x_scale(z, k[K_WN]);
     Ext<M> zb = z;
-    for (int s = 0; s < 3; s++) zb = x_mul(zb, zb); // z^8: the composition columns of TransactionAir
+    for (uint32_t s = 1; s < d.a.ce; s <<= 1) zb = x_mul(zb, zb); // z^ce: the composition columns
+    const uint32_t W = d.a.w, CE = d.a.ce;
     Ext<M> s1 = x_zero<M>(), s2 = x_zero<M>(), s3 = x_zero<M>();
-    const uint8_t *row = pb + d.trows + 8 * (size_t)q * TX_W;
-    for (uint32_t c = 0; c < TX_W; c++) {
+    const uint8_t *row = pb + d.trows + 8 * (size_t)q * W;
+    for (uint32_t c = 0; c < W; c++) {
         const Ext<M> rv = x_base<M>(ld64(row + 8 * c));
         s1 = x_add(s1, x_mul(x_load<M>(tb + to.da + M * c), x_sub(rv, ld_ext<M>(pb + d.ood + 8 * M * c))));
-        s2 = x_add(s2, x_mul(x_load<M>(tb + to.db + M * c), x_sub(rv, ld_ext<M>(pb + d.ood + 8 * M * (TX_W + c)))));
+        s2 = x_add(s2, x_mul(x_load<M>(tb + to.db + M * c), x_sub(rv, ld_ext<M>(pb + d.ood + 8 * M * (W + c)))));
     }
-    const uint8_t *crow = pb + d.crows + 8 * (size_t)q * TX_CE * M;
-    for (uint32_t i = 0; i < TX_CE; i++)
-        s3 = x_add(s3, x_mul(x_load<M>(tb + to.dd + M * i), x_sub(ld_ext<M>(crow + 8 * M * i), ld_ext<M>(pb + d.ood + 8 * M * (2 * TX_W + i)))));
+    const uint8_t *crow = pb + d.crows + 8 * (size_t)q * CE * M;
+    for (uint32_t i = 0; i < CE; i++)
+        s3 = x_add(s3, x_mul(x_load<M>(tb + to.dd + M * i), x_sub(ld_ext<M>(crow + 8 * M * i), ld_ext<M>(pb + d.ood + 8 * M * (2 * W + i)))));
     const Ext<M> bx = x_base<M>(x);
     const Ext<M> t = x_add(x_add(x_mul(s1, x_inv(x_sub(bx, z))), x_mul(s2, x_inv(x_sub(bx, zw)))), x_mul(s3, x_inv(x_sub(bx, zb))));
     Ext<M> val = x_mul(t, x_add(x_load<M>(tb + to.dga), x_scale(x_load<M>(tb + to.dgb), x)));
@@ -384,7 +404,7 @@ __global__ __launch_bounds__(256) void k_vfy_remainder(const uint8_t *__restrict
     if (comp >= d.m) return;
     const uint8_t *pb = buf + d.base;
     const uint64_t *tb = tbase + d.tb;
-    const TOff to = toff(d.m, d.n_layers, d.nq);
+    const TOff to = toff(d);
     const fp wrinv = tb[to.k + K_WRINV];
     const uint32_t R = d.R;
     bool ok = true;
@@ -423,7 +443,7 @@ __global__ __launch_bounds__(256) void k_vfy_reduce(const VDesc *__restrict__ de
     __shared__ uint32_t red[256];
     const VDesc &d = desc[blockIdx.x];
     const uint32_t n = 1 + d.n_open + d.nq + d.m;
-    uint32_t r = threadIdx.x == 0 ? (uint32_t)tbase[d.tb + toff(d.m, d.n_layers, d.nq).st + 1] : RK_NONE;
+    uint32_t r = threadIdx.x == 0 ? (uint32_t)tbase[d.tb + toff(d).st + 1] : RK_NONE;
     for (uint32_t i = threadIdx.x; i < n; i += 256) r = min(r, slots[d.slot0 + i]);
     red[threadIdx.x] = r;
     __syncthreads();
@@ -563,16 +583,17 @@ __global__ __launch_bounds__(VT) void k_vfy_transcript(const uint8_t *__restrict
     const uint8_t *pb = buf + d.base;
     uint64_t *T = tbase + d.tb;
     const uint32_t m = d.m, nq = d.nq, nl = d.n_layers, hash = d.hash, tid = threadIdx.x;
-    const TOff to = toff(m, nl, nq);
+    const uint32_t W = d.a.w, CE = d.a.ce, NC = d.a.nc, NA = d.a.na;
+    const TOff to = toff(d);
     for (uint32_t i = tid; i < K_WORDS; i += VT) T[to.k + i] = d.k[i];
     if (tid == 0) {
-        // seed = H(width, log n | p | nq, log b, grinding, hash, extension, folding, log remainder | 14 public inputs, canonical)
+        // seed = H(width, log n | p | nq, log b, grinding, hash, extension, folding, log remainder | the AIR's public inputs, canonical)
         uint32_t o = 0;
-        sh.msg[o++] = (uint8_t)TX_W; sh.msg[o++] = (uint8_t)d.log_n;
+        sh.msg[o++] = (uint8_t)W; sh.msg[o++] = (uint8_t)d.log_n;
         for (int i = 0; i < 8; i++) sh.msg[o++] = (uint8_t)(FP_P >> (8 * i));
         const uint32_t ob[7] = {nq, d.log_b, d.grinding, hash, m - 1, 1u << d.log_f, d.log_rem};
         for (int i = 0; i < 7; i++) sh.msg[o++] = (uint8_t)ob[i];
-        for (int i = 0; i < 14; i++) {
+        for (uint32_t i = 0; i < d.a.npub; i++) {
             const uint64_t v = fp_to_u64(d.pub[i]);
             for (int k = 0; k < 8; k++) sh.msg[o++] = (uint8_t)(v >> (8 * k));
         }
@@ -590,31 +611,31 @@ __global__ __launch_bounds__(VT) void k_vfy_transcript(const uint8_t *__restrict
     }
     __syncthreads();
     // (alpha, beta) per constraint, then per assertion: elements of E (m draws each)
-    draws(hash, sh, 2 * (TX_NC + TX_NA) * m, [&](uint32_t i, uint64_t v) {
+    draws(hash, sh, 2 * (NC + NA) * m, [&](uint32_t i, uint64_t v) {
         const uint32_t e = i / m, q = i % m, pair = e / 2, which = e % 2;
-        if (pair < TX_NC) T[(which ? to.tb : to.ta) + m * pair + q] = v;
-        else T[(which ? to.bb : to.ba) + m * (pair - TX_NC) + q] = v;
+        if (pair < NC) T[(which ? to.tb : to.ta) + m * pair + q] = v;
+        else T[(which ? to.bb : to.ba) + m * (pair - NC) + q] = v;
     });
     if (tid == 0) reseed(hash, sh, w32(pb + 84)); // constraint root
     __syncthreads();
     draws(hash, sh, m, [&](uint32_t i, uint64_t v) { T[to.z + i] = v; });
-    block_digest(hash, pb + d.ood, 8 * 2 * TX_W * m, sh);
+    block_digest(hash, pb + d.ood, 8 * 2 * W * m, sh);
     if (tid == 0) reseed(hash, sh, sh.dig);
     __syncthreads();
-    block_digest(hash, pb + d.ood + 8 * 2 * TX_W * m, 8 * TX_CE * m, sh);
+    block_digest(hash, pb + d.ood + 8 * 2 * W * m, 8 * CE * m, sh);
     if (tid == 0) reseed(hash, sh, sh.dig);
     __syncthreads();
     constexpr uint32_t PER = CSTARK_CONV_DEEP_DRAWS_PER_REGISTER;
-    draws(hash, sh, (TX_W * PER + TX_CE + 2) * m, [&](uint32_t i, uint64_t v) {
+    draws(hash, sh, (W * PER + CE + 2) * m, [&](uint32_t i, uint64_t v) {
         const uint32_t e = i / m, q = i % m;
-        if (e < TX_W * PER) {
+        if (e < W * PER) {
             const uint32_t c = e / PER, k = e % PER;
             if (k == 0) T[to.da + m * c + q] = v;
             else if (k == 1) T[to.db + m * c + q] = v;
         } else {
-            const uint32_t e2 = e - TX_W * PER;
-            if (e2 < TX_CE) T[to.dd + m * e2 + q] = v;
-            else if (e2 == TX_CE) T[to.dga + q] = v;
+            const uint32_t e2 = e - W * PER;
+            if (e2 < CE) T[to.dd + m * e2 + q] = v;
+            else if (e2 == CE) T[to.dga + q] = v;
             else T[to.dgb + q] = v;
         }
     });
@@ -631,7 +652,7 @@ __global__ __launch_bounds__(VT) void k_vfy_transcript(const uint8_t *__restrict
         for (int i = 0; i < 8; i++) same &= sh.dig[i] == rc[i];
         if (!same) sh.rank = RK_REMAINDER_COMMITMENT;
         reseed(hash, sh, rc);
-        const uint32_t *nw = w32(pb + d.ood + 8 * (2 * TX_W + TX_CE) * m);
+        const uint32_t *nw = w32(pb + d.ood + 8 * (2 * W + CE) * m);
         const uint64_t nonce = (uint64_t)nw[0] | ((uint64_t)nw[1] << 32);
         uint32_t h[8];
         with_int(hash, sh.seed, nonce, h);
@@ -701,11 +722,15 @@ struct VerifyArena {
     size_t scratch_bytes = 0;
     int32_t *h_verdicts = nullptr;
     size_t verdict_cap = 0;
-    uint64_t *d_pcoef = nullptr;           // periodic coefficients [depth slot][48][1024], depth = 2^(slot+1) - 1
-    bool pcoef_ready[6] = {};
+    // periodic coefficients per (AIR, header word): TransactionAir [depth slot][48][1024], depth = 2^(slot+1) - 1 | MerkleAir
+    // [depth slot][33][512] | RescueAir [29][8]
+    uint64_t *d_pcoef = nullptr;
+    bool pcoef_ready[13] = {};
+    struct Adj { uint32_t air, log_n; uint64_t adj[VMAX_GROUPS], badj; };
+    std::vector<Adj> adj;                  // degree adjustments per (AIR, log_n): the constraint-evaluation domain is n * ce
     hipEvent_t ev[VFY_EVENTS] = {};
     float ms[CSTARK_VERIFY_NUM_STAGES] = {};
-    uint64_t h2d_bytes = 0;              // bytes copied host -> device by the last cstark_tx_verify
+    uint64_t h2d_bytes = 0;              // bytes copied host -> device by the last verify call
     bool timed = false;
 };
 
@@ -727,27 +752,107 @@ struct Staged {
     const uint8_t *bytes;
     Layout L;
     VDesc d;
+    uint32_t D;         // the AIR's largest constraint degree (AirInfo)
+};
+// the proofs of one (AIR, extension degree) of a chunk: their list, the frames sampled for them (K each) and the constraint values
+struct Group {
+    uint32_t start = 0, count = 0, K = 0, frames = 0;
+    fp *cur, *nxt, *per, *val;
+    uint32_t *bad;
 };
 
-// what the device needs besides the proof bytes: the domain constants and the public inputs (the transcript itself is replayed on the
-// device, k_vfy_transcript)
-void describe(const Layout &L, const uint64_t *iroot, const uint64_t *froot, VDesc &d) {
+// The AIRs the pipeline verifies, as data, built once per process.  D: the largest total degree of a constraint in the frame's entries
+// (trace registers and periodic values), the sum of cstark_air_constraint_degree's two answers.  groups: constraints of one degree
+// (base; cycles) share an adjustment exponent at every trace length, so the grouping is the AIR's own; rep[g] = a constraint of group g.
+struct AirInfo { bool ok = false; VAir a{}; uint32_t D = 0; VGroups groups{}; uint32_t rep[VMAX_GROUPS] = {}; host::AirShape shape; };
+const AirInfo &air_info(uint32_t air) {
+    static const std::array<AirInfo, 5> table = [] {
+        std::array<AirInfo, 5> t;
+        for (uint32_t id = 0; id < 5; id++) {
+            AirInfo &I = t[id];
+            if (id == CSTARK_AIR_STATE_TRANSITION) {
+                I.ok = true;
+                I.a = {id, AIR_WIDTH[id], AIR_CE[id], 115, 4, 14, host::TX_NUM_PERIODIC, 10, 58};
+                I.D = 7;
+                I.groups.n = 5;
+                for (uint32_t i = 0; i < I.a.nc; i++) I.groups.g[i] = (uint8_t)tx_degree_group((int)i);
+                continue;
+            }
+            host::AirShape &s = I.shape;
+            if (id == CSTARK_AIR_SCHNORR || !host::air_shape((int)id, s)) continue; // SchnorrAir: no verifier
+            I.ok = true;
+            I.a = {id, s.width, 1u << s.log_ce_blowup(), s.n_constraints, (uint32_t)s.a_reg.size(), id == CSTARK_AIR_RANGE ? 1u : 14u, s.n_periodic,
+                   s.cycle_len ? ilog2(s.cycle_len) : 0, s.a_reg[0]};
+            for (uint32_t i = 0; i < s.n_constraints; i++) {
+                I.D = std::max(I.D, s.base[i] + (s.cycle_len ? s.cycles[i] : 0));
+                uint32_t g = 0;
+                while (g < I.groups.n && !(s.base[I.rep[g]] == s.base[i] && s.cycles[I.rep[g]] == s.cycles[i])) g++;
+                if (g == I.groups.n) { assert(g < VMAX_GROUPS); I.rep[I.groups.n++] = i; }
+                I.groups.g[i] = (uint8_t)g;
+            }
+        }
+        return t;
+    }();
+    return table[air];
+}
+// header values no prover of this library writes (cstark_tx_witness_upload, cstark_air_prove, cstark_range_prove_bits,
+// cstark_rescue_prove, prove.hip): checked before anything is sized or cached from them
+bool header_ok(const Layout &L) {
+    if (L.nq > (1u << L.log_N) / 2) return false;
+    switch (L.air) {
+    case CSTARK_AIR_STATE_TRANSITION: return L.log_n >= 10 && tx_depth_ok(L.word);
+    case CSTARK_AIR_MERKLE_UPDATE: return L.log_n >= 9 && tx_depth_ok(L.word);
+    case CSTARK_AIR_RANGE: return L.word == 0; // log_n in 6 .. 21: parse_layout
+    case CSTARK_AIR_RESCUE_CHAIN: return L.word == 1u << (L.log_n - 3); // the chain length; log_n in 6 .. 21: parse_layout
+    }
+    return false;
+}
+
+// degree adjustments of (AIR, log_n), one per constraint group: TransactionAir's own five (air_tx_host.h), the sub-AIRs' from air_groups.h
+const VerifyArena::Adj &adjustments(VerifyArena *a, const AirInfo &I, uint32_t log_n) {
+    for (const VerifyArena::Adj &e : a->adj)
+        if (e.air == I.a.air && e.log_n == log_n) return e;
+    using namespace host;
+    const uint64_t n = 1ull << log_n;
+    VerifyArena::Adj e{I.a.air, log_n, {}, 0};
+    if (I.a.air == CSTARK_AIR_STATE_TRANSITION) {
+        for (int g = 0; g < 5; g++) e.adj[g] = tx_group_adjustment(g, n, n * I.a.ce);
+        e.badj = tx_boundary_adjustment(n, n * I.a.ce);
+    } else {
+        AirGroups q;
+        const AirGroupsResult r = air_groups(I.shape, log_n, 0, q); // at most as many distinct exponents as degrees: air_info's bound
+        assert(r == AIR_GROUPS_OK);
+        (void)r;
+        for (uint32_t g = 0; g < I.groups.n; g++) e.adj[g] = q.tgrp_adj[q.t_grp[I.rep[g]]];
+        e.badj = q.agrp_badj[0]; // single-row assertions only: one adjustment
+    }
+    a->adj.push_back(e);
+    return a->adj.back();
+}
+
+// what the device needs besides the proof bytes: the AIR, the domain constants and the public inputs (the transcript itself is replayed
+// on the device, k_vfy_transcript).  pub: the caller's 14 words (RangeProofAir: word 0 = number).
+void describe(const Layout &L, const AirInfo &I, const VerifyArena::Adj &adj, const uint64_t *pub, VDesc &d) {
     using namespace host;
     const uint64_t n = 1ull << L.log_n;
     uint64_t *K = d.k;
+    d.a = I.a;
     K[K_WN] = root_of_unity(L.log_n);
     K[K_WNN] = root_of_unity(L.log_N);
     K[K_WLAST] = pow(K[K_WN], n - 1);
     K[K_G] = lde_offset();
-    for (int g = 0; g < 5; g++) K[K_ADJ + g] = tx_group_adjustment(g, n, n * TX_CE);
-    K[K_BADJ] = tx_boundary_adjustment(n, n * TX_CE);
+    for (uint32_t g = 0; g < VMAX_GROUPS; g++) K[K_ADJ + g] = adj.adj[g];
+    K[K_BADJ] = adj.badj;
     K[K_INVF] = inv(from_u64(L.f));
     K[K_ZETA_INV] = inv(root_of_unity(L.log_f));
     K[K_WRINV] = inv(root_of_unity(ilog2(L.R)));
-    K[K_PUB] = iroot[0]; K[K_PUB + 1] = iroot[1]; K[K_PUB + 2] = froot[0]; K[K_PUB + 3] = froot[1];
+    // asserted values: the first na / 2 at row 0, the others at row n - 1
+    if (L.air == CSTARK_AIR_STATE_TRANSITION) { K[K_PUB] = pub[0]; K[K_PUB + 1] = pub[1]; K[K_PUB + 2] = pub[7]; K[K_PUB + 3] = pub[8]; }
+    else if (L.air == CSTARK_AIR_RANGE) { K[K_PUB] = 0; K[K_PUB + 1] = pub[0]; }
+    else for (int i = 0; i < 14; i++) K[K_PUB + i] = pub[i];
     unsigned lg = L.log_N;
     for (uint32_t l = 0; l < L.n_layers; l++) { K[K_WL + l] = root_of_unity(lg); lg -= L.log_f; }
-    for (int i = 0; i < 7; i++) { d.pub[i] = iroot[i]; d.pub[7 + i] = froot[i]; }
+    for (uint32_t i = 0; i < I.a.npub; i++) d.pub[i] = pub[i];
     d.hash = L.opt[3]; d.grinding = L.opt[2]; d.log_rem = ilog2(L.opt[6]);
     for (uint32_t l = 0; l < VMAX_LAYERS; l++) d.npos[l] = l < L.n_layers ? L.npos[l] : 0;
 }
@@ -774,14 +879,30 @@ template <int M> Lagrange<M> lagrange_weights(uint32_t K) {
     return L;
 }
 
-int ensure_pcoef(cstark_ctx *c, VerifyArena *a, uint32_t depth, uint32_t &slot) {
-    slot = ilog2(depth + 1) - 1;
-    if (!a->d_pcoef) HIP_TRY(hipMalloc(&a->d_pcoef, 6 * 48 * 1024 * 8));
+// the cached coefficients of the proof's periodic columns (header_ok has passed); off = their word offset in the cache
+int ensure_pcoef(cstark_ctx *c, VerifyArena *a, const Layout &L, uint64_t &off) {
+    constexpr size_t TX_WORDS = 48 * 1024, MK_WORDS = 33 * 512, RS_WORDS = 29 * 8;
+    off = 0;
+    if (L.air == CSTARK_AIR_RANGE) return CSTARK_OK;
+    const uint32_t dslot = L.air == CSTARK_AIR_RESCUE_CHAIN ? 0 : ilog2(L.word + 1) - 1;
+    const uint32_t slot = L.air == CSTARK_AIR_STATE_TRANSITION ? dslot : L.air == CSTARK_AIR_MERKLE_UPDATE ? 6 + dslot : 12;
+    off = L.air == CSTARK_AIR_STATE_TRANSITION ? dslot * TX_WORDS : L.air == CSTARK_AIR_MERKLE_UPDATE ? 6 * TX_WORDS + dslot * MK_WORDS : 6 * (TX_WORDS + MK_WORDS);
+    if (!a->d_pcoef) HIP_TRY(hipMalloc(&a->d_pcoef, (6 * (TX_WORDS + MK_WORDS) + RS_WORDS) * 8));
     if (a->pcoef_ready[slot]) return CSTARK_OK;
     std::vector<uint64_t> cols;
-    if (!host::tx_periodic_columns(depth, cols)) return fail(CSTARK_ERR_INVALID_ARG, "unsupported Merkle depth");
-    for (int col = 0; col < 48; col++) host::intt_small(cols.data() + (size_t)col * 1024, 10);
-    HIP_TRY(hipMemcpyAsync(a->d_pcoef + (size_t)slot * 48 * 1024, cols.data(), cols.size() * 8, hipMemcpyHostToDevice, c->stream));
+    uint32_t ncols, log_cycle;
+    if (L.air == CSTARK_AIR_STATE_TRANSITION) {
+        if (!host::tx_periodic_columns(L.word, cols)) return fail(CSTARK_ERR_INVALID_ARG, "unsupported Merkle depth");
+        ncols = 48; log_cycle = 10;
+    } else if (L.air == CSTARK_AIR_MERKLE_UPDATE) {
+        if (!host::merkle_periodic_columns(L.word, cols)) return fail(CSTARK_ERR_INVALID_ARG, "unsupported Merkle depth");
+        ncols = 33; log_cycle = 9;
+    } else {
+        host::rescue_chain_periodic_columns(cols);
+        ncols = 29; log_cycle = 3;
+    }
+    for (uint32_t col = 0; col < ncols; col++) host::intt_small(cols.data() + ((size_t)col << log_cycle), log_cycle);
+    HIP_TRY(hipMemcpyAsync(a->d_pcoef + off, cols.data(), cols.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     a->pcoef_ready[slot] = true;
     return CSTARK_OK;
@@ -805,7 +926,7 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
     for (uint32_t i = 0; i < P; i++) {
         const Layout &L = st[i].L;
         off = (off + 15) & ~(size_t)15; pofs[i] = off; off += L.rem + 8 * (size_t)L.R * L.m;
-        tofs[i] = t_words; t_words += (toff(L.m, L.n_layers, L.nq).words + 1) & ~(size_t)1;
+        tofs[i] = t_words; t_words += (toff(st[i].d.a, L.m, L.n_layers, L.nq).words + 1) & ~(size_t)1;
         uint32_t no = 2 * L.nq;
         for (uint32_t l = 0; l < L.n_layers; l++) no += L.npos[l];
         st[i].d.n_open = no;
@@ -816,7 +937,7 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
     const size_t desc_off = (off + 15) & ~(size_t)15;
     const size_t open_off = (desc_off + P * sizeof(VDesc) + 15) & ~(size_t)15;
     const size_t grp_off = (open_off + n_open * sizeof(VOpen) + 15) & ~(size_t)15;
-    const size_t total = grp_off + 3 * (size_t)P * 4 + 16;
+    const size_t total = grp_off + (size_t)P * 4 + 16;
     if (total > a->stage_bytes) {
         HIP_TRY(hipStreamSynchronize(s));
         if (a->h_stage) { HIP_TRY(hipHostFree(a->h_stage)); a->h_stage = nullptr; }
@@ -830,9 +951,15 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
     uint8_t *H = a->h_stage;
     VDesc *hd = reinterpret_cast<VDesc *>(H + desc_off);
     VOpen *ho = reinterpret_cast<VOpen *>(H + open_off);
-    uint32_t *hg = reinterpret_cast<uint32_t *>(H + grp_off); // [3][P]: proofs of each extension degree
-    uint32_t gcount[3] = {0, 0, 0}, frames[3] = {0, 0, 0};
-    const uint32_t KM[3] = {1, 7 * 1 + 4, 7 * 2 + 4}; // samples per frame: degree <= 7 (m - 1) along t
+    uint32_t *hg = reinterpret_cast<uint32_t *>(H + grp_off); // [P]: the proofs of each (AIR, extension degree), group after group
+    // samples per frame: a constraint of degree <= D in the frame has degree <= D (m - 1) along t; any K above that is exact
+    Group grp[5 * 3];
+    for (uint32_t i = 0; i < P; i++) {
+        Group &g = grp[st[i].L.air * 3 + st[i].L.m - 1];
+        g.count++;
+        g.K = st[i].L.m == 1 ? 1 : st[i].D * (st[i].L.m - 1) + 4;
+    }
+    for (uint32_t g = 0, o = 0; g < 15; g++) { grp[g].start = o; o += grp[g].count; grp[g].frames = grp[g].count * grp[g].K; grp[g].count = 0; }
     std::vector<VOpen> opens;
     opens.reserve(n_open);
     for (uint32_t i = 0; i < P; i++) {
@@ -845,18 +972,17 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
         d.cpaths = (uint32_t)L.cpaths; d.rem = (uint32_t)L.rem;
         for (uint32_t l = 0; l < VMAX_LAYERS; l++) d.lrows[l] = (uint32_t)L.lrows[l];
         d.log_n = L.log_n; d.log_N = L.log_N; d.nq = L.nq; d.log_f = L.log_f; d.n_layers = L.n_layers; d.m = L.m; d.R = L.R; d.log_b = L.log_b;
-        const uint32_t mi = L.m - 1;
-        d.frame0 = frames[mi];
-        frames[mi] += KM[mi];
-        hg[mi * P + gcount[mi]++] = i;
+        Group &g = grp[L.air * 3 + L.m - 1];
+        hg[g.start + g.count++] = i;
         hd[i] = d;
+        const uint32_t TW = d.a.w, TCE = d.a.ce;
         const uint32_t hash = L.opt[3];
         uint32_t sl = d.slot0 + 1;
         for (uint32_t q = 0; q < L.nq; q++) {
-            opens.push_back(VOpen{i, (uint32_t)(L.trows + 8 * (size_t)q * TX_W), (uint32_t)(L.tpaths + 32 * (size_t)q * L.log_N), 52u, TX_W, L.log_N,
+            opens.push_back(VOpen{i, (uint32_t)(L.trows + 8 * (size_t)q * TW), (uint32_t)(L.tpaths + 32 * (size_t)q * L.log_N), 52u, TW, L.log_N,
                                   VNO_LAYER, q, RK_OPENING0 + 2 * q, sl++, hash});
-            opens.push_back(VOpen{i, (uint32_t)(L.crows + 8 * (size_t)q * TX_CE * L.m), (uint32_t)(L.cpaths + 32 * (size_t)q * L.log_N), 84u,
-                                  TX_CE * L.m, L.log_N, VNO_LAYER, q, RK_OPENING0 + 2 * q + 1, sl++, hash});
+            opens.push_back(VOpen{i, (uint32_t)(L.crows + 8 * (size_t)q * TCE * L.m), (uint32_t)(L.cpaths + 32 * (size_t)q * L.log_N), 84u,
+                                  TCE * L.m, L.log_N, VNO_LAYER, q, RK_OPENING0 + 2 * q + 1, sl++, hash});
         }
         unsigned lg = L.log_N;
         // every layer's rows: from the first layer whose count differs (LAYER_COUNT, found by the replay) there are no positions to
@@ -877,11 +1003,15 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
     const auto t1 = std::chrono::steady_clock::now();
     host_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
 
-    // ---- device scratch: transcript blocks | slots | verdicts | per degree: frames cur, next, per, values | bad flags
+    // ---- device scratch: transcript blocks | slots | verdicts | per group: frames cur, next, per, values | bad flags
     size_t need = 8 * t_words + 16;
     need += 4 * n_slots + 16;
     need += 4 * (size_t)P + 16;
-    for (int g = 0; g < 3; g++) need += 8 * (size_t)frames[g] * (2 * TX_W + 48 + TX_NC) + 4 * (size_t)gcount[g] + 64;
+    for (uint32_t g = 0; g < 15; g++)
+        if (grp[g].count) {
+            const VAir &A = air_info(g / 3).a;
+            need += 8 * (size_t)grp[g].frames * (2 * A.w + A.nper + A.nc) + 4 * (size_t)grp[g].count + 5 * 16;
+        }
     if (need > a->scratch_bytes) {
         HIP_TRY(hipStreamSynchronize(s));
         if (a->d_scratch) { HIP_TRY(hipFree(a->d_scratch)); a->d_scratch = nullptr; }
@@ -900,14 +1030,14 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
     uint64_t *d_tb = carve<uint64_t>(D, so, t_words);
     uint32_t *d_slots = carve<uint32_t>(D, so, n_slots);
     int32_t *d_verd = carve<int32_t>(D, so, P);
-    fp *f_cur[3], *f_nxt[3], *f_per[3], *f_val[3];
-    uint32_t *f_bad[3];
-    for (int g = 0; g < 3; g++) {
-        f_cur[g] = carve<fp>(D, so, (size_t)frames[g] * TX_W);
-        f_nxt[g] = carve<fp>(D, so, (size_t)frames[g] * TX_W);
-        f_per[g] = carve<fp>(D, so, (size_t)frames[g] * 48);
-        f_val[g] = carve<fp>(D, so, (size_t)frames[g] * TX_NC);
-        f_bad[g] = carve<uint32_t>(D, so, gcount[g]);
+    for (uint32_t g = 0; g < 15; g++) {
+        if (!grp[g].count) continue;
+        const VAir &A = air_info(g / 3).a;
+        grp[g].cur = carve<fp>(D, so, (size_t)grp[g].frames * A.w);
+        grp[g].nxt = carve<fp>(D, so, (size_t)grp[g].frames * A.w);
+        grp[g].per = carve<fp>(D, so, (size_t)grp[g].frames * A.nper);
+        grp[g].val = carve<fp>(D, so, (size_t)grp[g].frames * A.nc);
+        grp[g].bad = carve<uint32_t>(D, so, grp[g].count);
     }
     const uint8_t *dbuf = a->d_stage;
     const VDesc *d_desc = reinterpret_cast<const VDesc *>(dbuf + desc_off);
@@ -917,31 +1047,33 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
     for (int e = 0; e < VFY_EVENTS; e++)
         if (!a->ev[e]) HIP_TRY(hipEventCreate(&a->ev[e]));
     HIP_TRY(hipEventRecord(a->ev[0], s));
-    const size_t copy_bytes = grp_off + 3 * (size_t)P * 4;
+    const size_t copy_bytes = grp_off + (size_t)P * 4;
     HIP_TRY(hipMemcpyAsync(a->d_stage, H, copy_bytes, hipMemcpyHostToDevice, s));
     a->h2d_bytes += copy_bytes;
     HIP_TRY(hipEventRecord(a->ev[1], s));
     hipLaunchKernelGGL(k_vfy_transcript, dim3(P), dim3(VT), 0, s, dbuf, d_desc, d_tb);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(a->ev[2], s));
-    for (int g = 0; g < 3; g++) {
-        const uint32_t G = gcount[g];
+    for (uint32_t g = 0; g < 15; g++) {
+        const Group &Gr = grp[g];
+        const uint32_t G = Gr.count, mi = g % 3, air = g / 3;
         if (!G) continue;
-        const uint32_t F = frames[g], K = KM[g];
-        const uint32_t *gp = d_grp + g * P;
-        if (g == 0) {
-            hipLaunchKernelGGL(k_vfy_ood_frames<1>, dim3(G), dim3(128), 0, s, dbuf, d_desc, gp, d_tb, a->d_pcoef, K, F, f_cur[g], f_nxt[g], f_per[g], f_bad[g]);
-        } else if (g == 1) {
-            hipLaunchKernelGGL(k_vfy_ood_frames<2>, dim3(G), dim3(128), 0, s, dbuf, d_desc, gp, d_tb, a->d_pcoef, K, F, f_cur[g], f_nxt[g], f_per[g], f_bad[g]);
+        const uint32_t F = Gr.frames, K = Gr.K;
+        const uint32_t *gp = d_grp + Gr.start;
+        if (mi == 0) {
+            hipLaunchKernelGGL(k_vfy_ood_frames<1>, dim3(G), dim3(128), 0, s, dbuf, d_desc, gp, d_tb, a->d_pcoef, K, F, Gr.cur, Gr.nxt, Gr.per, Gr.bad);
+        } else if (mi == 1) {
+            hipLaunchKernelGGL(k_vfy_ood_frames<2>, dim3(G), dim3(128), 0, s, dbuf, d_desc, gp, d_tb, a->d_pcoef, K, F, Gr.cur, Gr.nxt, Gr.per, Gr.bad);
         } else {
-            hipLaunchKernelGGL(k_vfy_ood_frames<3>, dim3(G), dim3(128), 0, s, dbuf, d_desc, gp, d_tb, a->d_pcoef, K, F, f_cur[g], f_nxt[g], f_per[g], f_bad[g]);
+            hipLaunchKernelGGL(k_vfy_ood_frames<3>, dim3(G), dim3(128), 0, s, dbuf, d_desc, gp, d_tb, a->d_pcoef, K, F, Gr.cur, Gr.nxt, Gr.per, Gr.bad);
         }
         HIP_TRY(hipGetLastError());
-        HIP_TRY(launch_eval_frames(f_cur[g], f_nxt[g], f_per[g], f_val[g], F, s));
+        HIP_TRY(launch_eval_frames_air((int)air, Gr.cur, Gr.nxt, Gr.per, Gr.val, F, s));
         const dim3 cg((G + 63) / 64);
-        if (g == 0) hipLaunchKernelGGL(k_vfy_ood_check<1>, cg, dim3(64), 0, s, dbuf, d_desc, gp, G, K, F, f_val[g], f_bad[g], lagrange_weights<1>(K), d_tb, d_slots);
-        else if (g == 1) hipLaunchKernelGGL(k_vfy_ood_check<2>, cg, dim3(64), 0, s, dbuf, d_desc, gp, G, K, F, f_val[g], f_bad[g], lagrange_weights<2>(K), d_tb, d_slots);
-        else hipLaunchKernelGGL(k_vfy_ood_check<3>, cg, dim3(64), 0, s, dbuf, d_desc, gp, G, K, F, f_val[g], f_bad[g], lagrange_weights<3>(K), d_tb, d_slots);
+        const VGroups &vg = air_info(air).groups;
+        if (mi == 0) hipLaunchKernelGGL(k_vfy_ood_check<1>, cg, dim3(64), 0, s, dbuf, d_desc, gp, G, K, F, Gr.val, Gr.bad, lagrange_weights<1>(K), vg, d_tb, d_slots);
+        else if (mi == 1) hipLaunchKernelGGL(k_vfy_ood_check<2>, cg, dim3(64), 0, s, dbuf, d_desc, gp, G, K, F, Gr.val, Gr.bad, lagrange_weights<2>(K), vg, d_tb, d_slots);
+        else hipLaunchKernelGGL(k_vfy_ood_check<3>, cg, dim3(64), 0, s, dbuf, d_desc, gp, G, K, F, Gr.val, Gr.bad, lagrange_weights<3>(K), vg, d_tb, d_slots);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(a->ev[3], s));
@@ -950,13 +1082,13 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(a->ev[4], s));
-    for (int g = 0; g < 3; g++) {
-        const uint32_t G = gcount[g];
+    for (uint32_t g = 0; g < 15; g++) {
+        const uint32_t G = grp[g].count, mi = g % 3;
         if (!G) continue;
         const dim3 grid(1, G); // num_queries <= 128: one workgroup per proof
-        if (g == 0) hipLaunchKernelGGL(k_vfy_fri<1>, grid, dim3(128), 0, s, dbuf, d_desc, d_grp + g * P, d_tb, d_slots);
-        else if (g == 1) hipLaunchKernelGGL(k_vfy_fri<2>, grid, dim3(128), 0, s, dbuf, d_desc, d_grp + g * P, d_tb, d_slots);
-        else hipLaunchKernelGGL(k_vfy_fri<3>, grid, dim3(128), 0, s, dbuf, d_desc, d_grp + g * P, d_tb, d_slots);
+        if (mi == 0) hipLaunchKernelGGL(k_vfy_fri<1>, grid, dim3(128), 0, s, dbuf, d_desc, d_grp + grp[g].start, d_tb, d_slots);
+        else if (mi == 1) hipLaunchKernelGGL(k_vfy_fri<2>, grid, dim3(128), 0, s, dbuf, d_desc, d_grp + grp[g].start, d_tb, d_slots);
+        else hipLaunchKernelGGL(k_vfy_fri<3>, grid, dim3(128), 0, s, dbuf, d_desc, d_grp + grp[g].start, d_tb, d_slots);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(a->ev[5], s));
@@ -995,16 +1127,22 @@ int cstark_proof_inspect(const uint8_t *proof, size_t len, cstark_proof_info *in
     return CSTARK_OK;
 }
 
-int cstark_tx_verify(cstark_ctx *c, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens, const uint64_t *initial_roots,
-                     const uint64_t *final_roots, const cstark_options *expected, int32_t *verdicts) {
-    if (!c) return fail(CSTARK_ERR_INVALID_ARG, "cstark_tx_verify: null context");
+// Both verify calls.  airs: the AIR the caller states for each proof (null: all TransactionAir); the 14 public words of proof i are
+// pub_lo[i * stride .. +7) | pub_hi[i * stride .. +7).
+static int verify_batch(const char *who, cstark_ctx *c, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens, const int32_t *airs,
+                        const uint64_t *pub_lo, const uint64_t *pub_hi, size_t stride, const cstark_options *expected, int32_t *verdicts) {
+    if (!c) return fail(CSTARK_ERR_INVALID_ARG, "%s: null context", who);
     if (count == 0) return CSTARK_OK;
-    if (!proofs || !proof_lens || !initial_roots || !final_roots || !verdicts) return fail(CSTARK_ERR_INVALID_ARG, "cstark_tx_verify: null argument");
-    for (size_t i = 0; i < 14 * (size_t)count; i++)
-        if ((i % 14 < 7 ? initial_roots[(i / 14) * 7 + i % 14] : final_roots[(i / 14) * 7 + i % 14 - 7]) >= host::P)
-            return fail(CSTARK_ERR_INVALID_ARG, "cstark_tx_verify: a root word is not a field element");
-    for (uint32_t i = 0; i < count; i++)
-        if (!proofs[i] && proof_lens[i]) return fail(CSTARK_ERR_INVALID_ARG, "cstark_tx_verify: null proof");
+    if (!proofs || !proof_lens || !pub_lo || !pub_hi || !verdicts) return fail(CSTARK_ERR_INVALID_ARG, "%s: null argument", who);
+    for (uint32_t i = 0; i < count; i++) {
+        const int32_t air = airs ? airs[i] : (int32_t)CSTARK_AIR_STATE_TRANSITION;
+        if (air < 0 || air > 4) return fail(CSTARK_ERR_INVALID_ARG, "%s: unknown AIR id", who);
+        const uint32_t used = air == CSTARK_AIR_SCHNORR ? 0 : air == CSTARK_AIR_RANGE ? 1 : 14; // SchnorrAir: never verified, nothing read
+        for (uint32_t k = 0; k < used; k++)
+            if ((k < 7 ? pub_lo[i * stride + k] : pub_hi[i * stride + k - 7]) >= host::P)
+                return fail(CSTARK_ERR_INVALID_ARG, "%s: a public input word is not a field element", who);
+        if (!proofs[i] && proof_lens[i]) return fail(CSTARK_ERR_INVALID_ARG, "%s: null proof", who);
+    }
     HIP_TRY(hipSetDevice(c->device));
     if (!c->verify) c->verify = new VerifyArena();
     VerifyArena *a = c->verify;
@@ -1017,20 +1155,27 @@ int cstark_tx_verify(cstark_ctx *c, uint32_t count, const uint8_t *const *proofs
     auto t0 = std::chrono::steady_clock::now();
     for (uint32_t i = 0; i < count; i++) {
         const uint8_t *b = proofs[i];
+        const uint32_t air = airs ? (uint32_t)airs[i] : (uint32_t)CSTARK_AIR_STATE_TRANSITION;
         Staged S;
         S.index = i;
         S.bytes = b;
         int v = b ? parse_layout(b, proof_lens[i], S.L) : CSTARK_PROOF_MALFORMED;
-        // another AIR's proof: no kernel reads it, so its elements are scanned here (a word >= p is MALFORMED before UNSUPPORTED)
-        if (v == CSTARK_PROOF_OK && S.L.air != CSTARK_AIR_STATE_TRANSITION) v = elements_canonical(b, S.L) ? CSTARK_PROOF_UNSUPPORTED : CSTARK_PROOF_MALFORMED;
+        // a proof of another AIR than the caller states, or of SchnorrAir: no kernel reads it, so its elements are scanned here (a word
+        // >= p is MALFORMED before UNSUPPORTED)
+        const AirInfo &I = air_info(air);
+        if (v == CSTARK_PROOF_OK && (S.L.air != air || !I.ok)) v = elements_canonical(b, S.L) ? CSTARK_PROOF_UNSUPPORTED : CSTARK_PROOF_MALFORMED;
+        if (v == CSTARK_PROOF_OK && !header_ok(S.L)) v = CSTARK_PROOF_MALFORMED;
         if (v == CSTARK_PROOF_OK && expected) {
             const uint32_t *e = &expected->num_queries;
             if (memcmp(e, S.L.opt, sizeof S.L.opt) != 0) v = elements_canonical(b, S.L) ? CSTARK_PROOF_OPTIONS_MISMATCH : CSTARK_PROOF_MALFORMED;
         }
         if (v != CSTARK_PROOF_OK) { verdicts[i] = v; continue; }
         memset(&S.d, 0, sizeof S.d);
-        RC_TRY(ensure_pcoef(c, a, S.L.word, S.d.depth_slot));
-        describe(S.L, initial_roots + 7 * (size_t)i, final_roots + 7 * (size_t)i, S.d);
+        S.D = I.D;
+        RC_TRY(ensure_pcoef(c, a, S.L, S.d.pcoef));
+        uint64_t pub[14];
+        for (int k = 0; k < 7; k++) { pub[k] = pub_lo[i * stride + k]; pub[7 + k] = pub_hi[i * stride + k]; }
+        describe(S.L, I, adjustments(a, I, S.L.log_n), pub, S.d);
         const size_t bytes = proof_lens[i] + sizeof(VDesc) + sizeof(VOpen) * (2 + S.L.nq * (size_t)(2 + S.L.n_layers)) + 256;
         if (!st.empty() && chunk_bytes + bytes > VFY_CHUNK_BYTES) {
             host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1046,6 +1191,17 @@ int cstark_tx_verify(cstark_ctx *c, uint32_t count, const uint8_t *const *proofs
     else a->ms[0] += (float)host_ms;
     a->timed = true;
     return CSTARK_OK;
+}
+
+int cstark_tx_verify(cstark_ctx *c, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens, const uint64_t *initial_roots,
+                     const uint64_t *final_roots, const cstark_options *expected, int32_t *verdicts) {
+    return verify_batch("cstark_tx_verify", c, count, proofs, proof_lens, nullptr, initial_roots, final_roots, 7, expected, verdicts);
+}
+
+int cstark_air_verify(cstark_ctx *c, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens, const int32_t *airs,
+                      const uint64_t *public_inputs, const cstark_options *expected, int32_t *verdicts) {
+    if (c && count && (!airs || !public_inputs)) return fail(CSTARK_ERR_INVALID_ARG, "cstark_air_verify: null argument");
+    return verify_batch("cstark_air_verify", c, count, proofs, proof_lens, airs, public_inputs, public_inputs ? public_inputs + 7 : nullptr, 14, expected, verdicts);
 }
 
 int cstark_verify_stage_ms(cstark_ctx *c, float *ms) {

@@ -195,6 +195,14 @@ class TransactionExample:
 
 
 # ---- the standalone examples of the reference: same prove() surface over cstark_air_prove ---------------------------------------
+def _air_verify_or_raise(backend, proof, air, public_inputs=None, numbers=None):
+    """winterfell::verify::<Air>(proof, pub_inputs) through cstark_air_verify: the proof's own options are accepted"""
+    from .verify import VerifierError
+    v = int(backend.air_verify([proof], air, public_inputs, numbers=numbers)[0])
+    if v != 0:
+        raise VerifierError(v)
+
+
 class _ResidentWitness:
     """An example's witness is uploaded by its first prove() and stays in device memory (any other upload on the same backend replaces
     it).  While it is resident the host arrays it was uploaded from are READ-ONLY (numpy refuses writes), so a changed witness can never
@@ -243,6 +251,10 @@ class MerkleExample(_ResidentWitness):
     def pub_inputs(self):
         return self.tx_metadata.initial_roots[0], self.tx_metadata.final_root
 
+    def verify(self, proof):
+        """src/merkle/update/mod.rs:109-127; raises VerifierError on rejection, like TransactionExample.verify"""
+        _air_verify_or_raise(self.backend, proof, Backend.AIR_MERKLE, np.concatenate(self.pub_inputs()))
+
 
 class SchnorrExample(_ResidentWitness):
     """schnorr::SchnorrExample (src/schnorr/mod.rs:52-186): messages [n][28] (public key || 16 elements) with signatures."""
@@ -284,6 +296,18 @@ class RescueExample:
     def prove(self):
         return self.backend.rescue_prove(self.options, self.seed, self.chain_length)
 
+    def pub_inputs(self):
+        """seed and result; the result is the rate half of the chain's last row (RescueProver::get_pub_inputs, benches/rescue.rs:331-354),
+        read from a trace built on the device the first time it is asked for"""
+        if getattr(self, "_result", None) is None:
+            trace = self.backend.rescue_chain_build_trace(self.seed, self.chain_length)
+            self._result = to_numpy_u64(trace[:7, -1])
+        return self.seed, self._result
+
+    def verify(self, proof):
+        """benches/rescue.rs:88-94; raises VerifierError on rejection"""
+        _air_verify_or_raise(self.backend, proof, Backend.AIR_RESCUE_CHAIN, np.concatenate(self.pub_inputs()))
+
 
 class RangeProofExample:
     """range::RangeProofExample (src/range/mod.rs:28-110): `number` is a field element in memory form whose canonical value is
@@ -295,3 +319,7 @@ class RangeProofExample:
 
     def prove(self):
         return self.backend.air_prove(Backend.AIR_RANGE, self.options, self.number)
+
+    def verify(self, proof):
+        """src/range/mod.rs:103-110; raises VerifierError on rejection"""
+        _air_verify_or_raise(self.backend, proof, Backend.AIR_RANGE, numbers=self.number)

@@ -431,7 +431,7 @@ int cstark_schnorr_witness_generate(uint32_t n_sig, uint64_t seed, uint64_t *mes
 typedef enum cstark_verdict {
     CSTARK_PROOF_OK = 0,                 /* verify: accepted;  inspect: well-formed */
     CSTARK_PROOF_MALFORMED = 1,          /* layout, counts, lengths, non-canonical field element, trailing bytes */
-    CSTARK_PROOF_UNSUPPORTED = 2,        /* well-formed proof of another AIR (MerkleAir, SchnorrAir, RangeProofAir, RescueAir) */
+    CSTARK_PROOF_UNSUPPORTED = 2,        /* well-formed proof of another AIR than the call verifies or the caller states; SchnorrAir always */
     CSTARK_PROOF_OPTIONS_MISMATCH = 3,   /* differs from `expected` */
     CSTARK_PROOF_OOD = 4,                /* out-of-domain constraint evaluations inconsistent (also: wrong public inputs) */
     CSTARK_PROOF_REMAINDER_COMMITMENT = 5,
@@ -464,12 +464,21 @@ int cstark_proof_inspect(const uint8_t *proof, size_t len, cstark_proof_info *in
 int cstark_tx_verify(cstark_ctx *ctx, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens,
                      const uint64_t *initial_roots, const uint64_t *final_roots, const cstark_options *expected,
                      int32_t *verdicts);
-/* Stage times of the last cstark_tx_verify on this context, like cstark_prove_stage_ms (milliseconds, summed over its chunks):
+/* The same for TransactionAir, MerkleAir, RangeProofAir and RescueAir proofs, `count` of them in one call; a batch may mix AIRs, sizes,
+ * hashes and extensions (one pipeline, cstark_tx_verify is its all-TransactionAir call).  airs[i]: the AIR the caller expects proof i to be
+ * (CSTARK_AIR_*).  public_inputs: [count][14] words, memory form -- TransactionAir / MerkleAir: initial root | final root; RescueAir: seed
+ * | result; RangeProofAir: word 0 = number, words 1..13 ignored.  A well-formed proof whose header states another AIR than airs[i] is
+ * UNSUPPORTED, and so is every proof with airs[i] == CSTARK_AIR_SCHNORR (its statement is O(n) public data: no verifier yet); header
+ * values no prover of this library writes (a Merkle depth or a trace length the AIR does not have) are MALFORMED.  Negative status only
+ * for null pointers, an airs[i] that is no CSTARK_AIR_* id, a used public word >= p, or a HIP failure. */
+int cstark_air_verify(cstark_ctx *ctx, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens, const int32_t *airs,
+                      const uint64_t *public_inputs, const cstark_options *expected, int32_t *verdicts);
+/* Stage times of the last cstark_tx_verify / cstark_air_verify on this context, like cstark_prove_stage_ms (milliseconds, summed over its chunks):
  * host parse + staging, host-to-device copy, transcript replay (on the device), out-of-domain check, Merkle openings, DEEP + FRI,
  * remainder + reduction + device-to-host copy.  cstark_verify_h2d_bytes: the bytes the same call copied host -> device (proof bytes,
  * descriptors, opening records). */
 #define CSTARK_VERIFY_NUM_STAGES 7
-/* Batches of any size: cstark_tx_verify stages proofs (their bytes, descriptors and opening records) for the device in chunks of at
+/* Batches of any size: both verify calls stage proofs (their bytes, descriptors and opening records) for the device in chunks of at
  * most this many bytes and verifies one chunk after the other, so a large count never sizes its buffers beyond one chunk (a single
  * larger proof is a chunk of its own).  Verdicts do not depend on where the chunks divide. */
 #define CSTARK_VERIFY_CHUNK_BYTES 67108864 /* 64 MiB */

@@ -277,6 +277,14 @@ inline TransactionExample get_example(size_t num_transactions, Context &ctx) { /
 }
 
 namespace detail {
+// cstark_air_verify for one proof of `air` against its 14 public words: throws VerifierError on rejection
+inline void air_verify(Context &ctx, int32_t air, const std::vector<uint8_t> &proof, const uint64_t (&pub)[14]) {
+    const uint8_t *ptr = proof.data();
+    const size_t len = proof.size();
+    int32_t v = -1;
+    check(cstark_air_verify(ctx.raw(), 1, &ptr, &len, &air, pub, nullptr, &v));
+    if (v != CSTARK_PROOF_OK) throw VerifierError(v);
+}
 inline std::vector<uint8_t> air_prove(Context &ctx, int air, const ProofOptions &options, uint64_t number, size_t rows) {
     const cstark_options o = options.raw();
     std::vector<uint8_t> proof(2 * cstark_tx_proof_size_bound((uint32_t)((rows + 1023) / 1024), &o));
@@ -297,6 +305,13 @@ class MerkleExample {
         return detail::air_prove(ctx_, CSTARK_AIR_MERKLE_UPDATE, options_, 0, m_.len() * 512);
     }
     PublicInputs pub_inputs() const { return {m_.initial_roots.at(0), m_.final_root}; }
+    // src/merkle/update/mod.rs:109-127: throws VerifierError on rejection
+    void verify(const std::vector<uint8_t> &proof) const {
+        const PublicInputs p = pub_inputs();
+        uint64_t pub[14];
+        for (int k = 0; k < 7; k++) { pub[k] = p.initial_root[k]; pub[7 + k] = p.final_root[k]; }
+        detail::air_verify(ctx_, CSTARK_AIR_MERKLE_UPDATE, proof, pub);
+    }
 
   private:
     ProofOptions options_;
@@ -308,6 +323,11 @@ class RangeProofExample {
   public:
     RangeProofExample(const ProofOptions &options, BaseElement number, Context &ctx) : options_(options), number_(number), ctx_(ctx) {}
     std::vector<uint8_t> prove() { return detail::air_prove(ctx_, CSTARK_AIR_RANGE, options_, number_, 64); }
+    // src/range/mod.rs:103-110: throws VerifierError on rejection
+    void verify(const std::vector<uint8_t> &proof) const {
+        const uint64_t pub[14] = {number_};
+        detail::air_verify(ctx_, CSTARK_AIR_RANGE, proof, pub);
+    }
 
   private:
     ProofOptions options_;
@@ -343,11 +363,36 @@ class RescueExample {
         proof.resize(len);
         return proof;
     }
+    // the chain's result: the rate half of the last row of its trace (RescueProver::get_pub_inputs :331-354), built on the device the
+    // first time it is asked for
+    std::array<BaseElement, 7> result() const {
+        if (have_result_) return result_;
+        const size_t n = 8 * chain_length_;
+        void *d_trace = nullptr;
+        check(cstark_malloc(ctx_.raw(), 14 * n * 8, &d_trace));
+        std::array<BaseElement, 7> r{};
+        int rc = cstark_rescue_chain_build_trace(ctx_.raw(), seed, (uint32_t)chain_length_, (uint64_t *)d_trace);
+        for (int i = 0; i < 7 && rc == CSTARK_OK; i++) rc = cstark_memcpy_d2h(ctx_.raw(), &r[i], (const uint64_t *)d_trace + (size_t)i * n + n - 1, 8);
+        cstark_free(ctx_.raw(), d_trace);
+        check(rc);
+        result_ = r;
+        have_result_ = true;
+        return r;
+    }
+    // benches/rescue.rs:88-94: throws VerifierError on rejection
+    void verify(const std::vector<uint8_t> &proof) const {
+        const std::array<BaseElement, 7> r = result();
+        uint64_t pub[14];
+        for (int k = 0; k < 7; k++) { pub[k] = seed[k]; pub[7 + k] = r[k]; }
+        detail::air_verify(ctx_, CSTARK_AIR_RESCUE_CHAIN, proof, pub);
+    }
     BaseElement seed[7];
 
   private:
     ProofOptions options_;
     size_t chain_length_;
+    mutable std::array<BaseElement, 7> result_{};
+    mutable bool have_result_ = false;
     Context &ctx_;
 };
 // schnorr::SchnorrExample (src/schnorr/mod.rs:52-186)

@@ -2,9 +2,12 @@
 remainder 256): single-proof latency, proofs/s at batch sizes 16, 64 and 256, bytes copied per call (proof bytes and the whole copy)
 and the achieved host-to-device rate of the whole copy, and cstark_verify_stage_ms.  Prints one JSON line.  Run on a GPU box.
 
-    python tools/bench_verify.py [--counts 1,64] [--min-seconds 1.0]
+    python tools/bench_verify.py [--counts 1,64] [--min-seconds 1.0] [--air transaction|merkle|range]
 
-cstark_tx_verify is synchronous (verdicts are on the host when it returns), so wall time around the call is the latency; every
+--air merkle: a MerkleAir proof of 512 transfers (2^18 rows, depth 15, 96 queries); --air range: the reference's 64-row range proof
+(42 queries); both through cstark_air_verify.
+
+The verify calls are synchronous (verdicts are on the host when they return), so wall time around the call is the latency; every
 configuration is warmed up first and timed over at least --min-seconds of calls."""
 import argparse
 import json
@@ -16,7 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
 from certificate_stark_amd.backend import Backend  # noqa: E402
-from certificate_stark_amd.prover import ProofOptions, TransactionExample, TransactionMetadata  # noqa: E402
+from certificate_stark_amd.prover import MerkleExample, ProofOptions, RangeProofExample, TransactionExample, TransactionMetadata  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PCIE_GEN5_X16_GBPS = 63.0  # per direction, MI355X spec
@@ -26,23 +29,46 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--counts", default="1,16,64,256")
     ap.add_argument("--min-seconds", type=float, default=1.0)
+    ap.add_argument("--air", default="transaction", choices=("transaction", "merkle", "range"))
     args = ap.parse_args()
     b = Backend()
     meta = TransactionMetadata.load(os.path.join(ROOT, "tests", "golden", "witness_1024_d15.npz"))
-    opt = ProofOptions(96, 8, 0, ProofOptions.BLAKE3_256, ProofOptions.EXT_NONE, 4, 256)
-    tx = TransactionExample(opt, meta, b)
-    proof = tx.prove()
-    r0, r1 = tx.pub_inputs()
-    out = {"config": "state_transition 1024 tx (2^20 rows), depth 15, options (96, 8, 0, Blake3, None, 4, 256)",
-           "proof_bytes": len(proof), "device": "MI355X", "results": {}}
+    if args.air == "transaction":
+        opt = ProofOptions(96, 8, 0, ProofOptions.BLAKE3_256, ProofOptions.EXT_NONE, 4, 256)
+        tx = TransactionExample(opt, meta, b)
+        proof = tx.prove()
+        r0, r1 = tx.pub_inputs()
+        config = "state_transition 1024 tx (2^20 rows), depth 15, options (96, 8, 0, Blake3, None, 4, 256)"
+
+        def verify(proofs):
+            return b.tx_verify(proofs, r0, r1, opt)
+    elif args.air == "merkle":
+        opt = ProofOptions(96, 8, 0, ProofOptions.BLAKE3_256, ProofOptions.EXT_NONE, 4, 256)
+        half = TransactionMetadata(*[getattr(meta, f) if f == "final_root" else getattr(meta, f)[:512] for f in TransactionMetadata.FIELDS])
+        proof = MerkleExample(opt, half, b).prove()
+        pub = np.concatenate([meta.initial_roots[0], meta.initial_roots[512]])  # the tree's root before and after the first 512 transfers
+        config = "merkle_update 512 tx (2^18 rows), depth 15, options (96, 8, 0, Blake3, None, 4, 256)"
+
+        def verify(proofs):
+            return b.air_verify(proofs, Backend.AIR_MERKLE, pub, opt)
+    else:
+        opt = ProofOptions(42, 8, 0, ProofOptions.BLAKE3_256, ProofOptions.EXT_NONE, 4, 256)
+        p = (1 << 62) + (1 << 56) + (1 << 55) + 1
+        number = 12345678901234567 * pow(2, 64, p) % p   # memory form
+        proof = RangeProofExample(opt, number, b).prove()
+        config = "range 64 rows, options (42, 8, 0, Blake3, None, 4, 256)"
+
+        def verify(proofs):
+            return b.air_verify(proofs, Backend.AIR_RANGE, options=opt, numbers=number)
+    out = {"config": config, "proof_bytes": len(proof), "device": "MI355X", "results": {}}
     for count in [int(c) for c in args.counts.split(",")]:
         proofs = [proof] * count
         for _ in range(3):  # warm-up: staging buffers, periodic coefficients, code objects
-            v = b.tx_verify(proofs, r0, r1, opt)
+            v = verify(proofs)
         assert not v.any(), v
         calls, t0 = 0, time.perf_counter()
         while True:
-            b.tx_verify(proofs, r0, r1, opt)
+            verify(proofs)
             calls += 1
             dt = time.perf_counter() - t0
             if dt >= args.min_seconds:
