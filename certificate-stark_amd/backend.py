@@ -414,6 +414,34 @@ class Backend:
                                                C.c_uint32(k0), C.c_uint32(nk)))
         return out
 
+    def evaluate_polys_at_ext(self, coeffs, z):
+        """cstark_evaluate_polys_at_ext: base-field coefficient columns at one point of the degree-m extension (z: m memory-form
+        words); returns a host [width][m] array"""
+        width, n = coeffs.shape
+        m = len(z)
+        zp = (C.c_uint64 * m)(*[int(v) for v in z])
+        out = np.zeros((width, m), np.uint64)
+        check(self.lib.cstark_evaluate_polys_at_ext(self.ctx, self._ptr(coeffs), C.c_uint32(width), C.c_uint32(n.bit_length() - 1), C.c_uint32(m),
+                                                    zp, out.ctypes.data_as(u64p)))
+        return out
+
+    def deep_composition_ext(self, trace_lde, comp_lde, z, ood_trace, ood_comp, alpha, beta, delta, deg_a, deg_b, log_blowup, out=None):
+        """cstark_deep_composition_ext: trace_lde [b][width][n], comp_lde [b][m nb][n] (column m i + q = component q of composition
+        column i); z, deg_a, deg_b: m words; ood_trace [2][width][m], ood_comp [nb][m], alpha, beta [width][m], delta [nb][m].
+        Returns [m][b][n], component-major."""
+        b, width, n = trace_lde.shape
+        m = len(z)
+        nb = comp_lde.shape[1] // m
+        assert b == 1 << log_blowup and comp_lde.shape[0] == b and comp_lde.shape[1] == m * nb
+        if out is None:
+            out = self.empty_u64(m, b, n)
+        arrs = [_np_u64(a) for a in (z, ood_trace, ood_comp, alpha, beta, delta, deg_a, deg_b)]
+        assert [a.size for a in arrs] == [m, 2 * width * m, nb * m, width * m, width * m, nb * m, m, m]
+        check(self.lib.cstark_deep_composition_ext(self.ctx, self._ptr(trace_lde), self._ptr(comp_lde), C.c_uint32(width), C.c_uint32(nb), C.c_uint32(m),
+                                                   *[a.ctypes.data_as(u64p) for a in arrs], self._ptr(out), C.c_uint32(n.bit_length() - 1),
+                                                   C.c_uint32(log_blowup)))
+        return out
+
     # ---- FRI ----
     def interleave_cosets(self, coset_major):
         b, n = coset_major.shape

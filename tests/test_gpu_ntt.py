@@ -80,3 +80,37 @@ def test_both_columns_every_point_2_20(oracle, backend):
     part = backend.lde_columns(co, 3, k0=5, nk=2)
     assert part_ref.shape == (2, 2, 1 << 20)
     assert (to_numpy_u64(part) == part_ref).all()
+
+
+@pytest.mark.parametrize("log_n", [15, 17, 19])
+def test_generic_sizes_with_sub_transforms_of_a_workgroup_or_more(oracle, backend, log_n):
+    """The sizes between the register kernels' own: sub-transforms of 256 to 1024 points, where every thread of the workgroup owns one
+    butterfly or several.  Interpolation, then cosets 5 and 6 of the blowup-8 extension, every point against the oracle."""
+    from certificate_stark_amd.backend import to_numpy_u64
+    ev = _rand(oracle, (2, 1 << log_n), 3000 + log_n)
+    co_ref = oracle.interpolate_columns(ev)
+    co = backend.interpolate_columns(backend.from_numpy_u64(ev))
+    assert (to_numpy_u64(co) == co_ref).all()
+    part = backend.lde_columns(co, 3, k0=5, nk=2)
+    assert (to_numpy_u64(part) == oracle.lde_columns(co_ref, 3, k0=5, nk=2)).all()
+
+
+@pytest.mark.parametrize("log_n", [22, 23, 24])
+def test_largest_sizes_every_point(oracle, backend, log_n):
+    """2^22 (sub-transforms of 2048 points) and 2^23, 2^24 (4096 points: the narrower tile, which no smaller size reaches): one column --
+    at 2^23 a second one of all p - 1 -- interpolated, extended to coset 1 of blowup 2, every point against the oracle; and evaluating
+    the interpolant on the trace domain returns the input."""
+    import torch
+    from certificate_stark_amd.backend import to_numpy_u64
+    n = 1 << log_n
+    ev = _rand(oracle, (1, n), 4000 + log_n)
+    if log_n == 23:
+        ev = np.concatenate([ev, np.full((1, n), P - 1, np.uint64)])
+    d_ev = backend.from_numpy_u64(ev)
+    co_ref = oracle.interpolate_columns(ev)
+    co = backend.interpolate_columns(d_ev.clone())
+    assert (to_numpy_u64(co) == co_ref).all()
+    part = backend.lde_columns(co, 1, k0=1, nk=1)
+    assert (to_numpy_u64(part) == oracle.lde_columns(co_ref, 1, k0=1, nk=1)).all()
+    back = backend.lde_columns(co, 0, offset=int(oracle.to_mont([1])[0]))
+    assert torch.equal(back[0], d_ev)
