@@ -155,18 +155,23 @@ const size_t LDE_BATCH_WS_BYTES = [] {
 }();
 int lde_impl_inner(cstark_ctx *c, const uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols, uint32_t log_n,
                    uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk);
-int lde_impl(cstark_ctx *c, const uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols, uint32_t log_n, uint32_t log_blowup,
-             uint64_t domain_offset, uint32_t k0, uint32_t nk) {
+// one extension of `units` elements between an event pair of the part timing
+template <class F>
+int lde_timed(cstark_ctx *c, uint64_t units, F &&run) {
     // events come in pairs: without room for both, or if the first cannot be recorded, the extension simply is not timed
     bool timed = c && c->part_timing && c->lde_ev_used + 2 <= LDE_EVENT_CAP;
     const size_t mark = timed ? c->lde_ev_used : 0;
     if (timed && lde_mark(c) != CSTARK_OK) { c->lde_ev_used = mark; timed = false; }
-    const int rc = lde_impl_inner(c, d_coeffs, d_lde, width, col0, ncols, log_n, log_blowup, domain_offset, k0, nk);
+    const int rc = run();
     if (timed) {
-        if (rc == CSTARK_OK && lde_mark(c) == CSTARK_OK) c->lde_units += (uint64_t)ncols * nk << log_n;
+        if (rc == CSTARK_OK && lde_mark(c) == CSTARK_OK) c->lde_units += units;
         else c->lde_ev_used = mark; // never leave an unpaired event behind
     }
     return rc;
+}
+int lde_impl(cstark_ctx *c, const uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols, uint32_t log_n, uint32_t log_blowup,
+             uint64_t domain_offset, uint32_t k0, uint32_t nk) {
+    return lde_timed(c, (uint64_t)ncols * nk << log_n, [&] { return lde_impl_inner(c, d_coeffs, d_lde, width, col0, ncols, log_n, log_blowup, domain_offset, k0, nk); });
 }
 int lde_impl_inner(cstark_ctx *c, const uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols, uint32_t log_n,
                    uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk) {
@@ -211,6 +216,66 @@ int lde_impl_inner(cstark_ctx *c, const uint64_t *d_coeffs, uint64_t *d_lde, uin
         HIP_TRY(cs::ntt_columns(a, c->stream));
     }
     return CSTARK_OK;
+}
+
+// Step columns (ntt.h): the constants of one (trace length, blowup, offset, block length) -- D and, per coset, the column pass of D.
+// Built on first use on the context's stream, freed with the context; 8 (1 + b) n bytes: 72 MB at 2^20 rows and blowup 8.
+int get_step_table(cstark_ctx *c, unsigned log_n, unsigned log_b, uint64_t offset, unsigned log_block, const cs::StepTable **out) {
+    for (const cs::StepTable &t : c->steps)
+        if (t.log_n == log_n && t.log_b == log_b && t.offset == offset && t.log_block == log_block) { *out = &t; return CSTARK_OK; }
+    const NttPlan *p;
+    const CosetTable *ct;
+    RC_TRY(get_plan(c, log_n, &p));
+    RC_TRY(get_coset_table(c, log_n, log_b, offset, &ct));
+    const size_t n = (size_t)1 << log_n, b = (size_t)1 << log_b;
+    cs::StepTable t{log_n, log_b, offset, log_block, nullptr, nullptr};
+    DevGuard g;
+    HIP_TRY(g.alloc(&t.d, n * 8));
+    HIP_TRY(g.alloc(&t.w, b * n * 8));
+    cs::NttArgs a{};
+    a.in = t.d; a.scratch = t.w; a.width = 1; a.batch = (unsigned)b; a.log_n = log_n;
+    a.w = p->w; a.aux = p->aux_w;
+    a.prescale = ct->s; a.prescale_batch_stride = n;
+    a.aux_ps = ct->aux; a.aux_ps_batch_stride = ct->aux_words;
+    a.in_batch_stride = 0; a.scratch_batch_stride = n;
+    HIP_TRY(cs::ntt_step_build_tables(t.d, log_block, p->winv, a, c->stream));
+    c->steps.push_back(t);
+    g.release();
+    *out = &c->steps.back();
+    return CSTARK_OK;
+}
+// Coefficients and extension of columns [col0, col0 + ncols) that are constant over blocks of block_len rows.  Where the transform serves
+// the shape (cs::ntt_step_shape) only the first row of every block is read and d_evals stays intact; everywhere else the columns take
+// interpolate_impl (which destroys them) and lde_impl.
+int step_impl(cstark_ctx *c, uint64_t *d_evals, uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols, uint32_t log_n,
+              uint32_t block_len, uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk) {
+    if (!c || !d_evals || !d_coeffs || !d_lde || width == 0 || ncols == 0 || (uint64_t)col0 + ncols > width)
+        return fail(CSTARK_ERR_INVALID_ARG, "cstark_step_columns: bad argument");
+    if (log_n < cs::NTT_MIN_LOG_N || log_n > cs::NTT_MAX_LOG_N || log_blowup > 6) return fail(CSTARK_ERR_UNSUPPORTED, "unsupported domain size");
+    if (block_len == 0 || (block_len & (block_len - 1)) || block_len > (1u << log_n)) return fail(CSTARK_ERR_INVALID_ARG, "the block length must be a power of two up to the trace length");
+    if (domain_offset == 0 || domain_offset >= cs::host::P) return fail(CSTARK_ERR_INVALID_ARG, "domain offset must be a nonzero field element");
+    if ((uint64_t)k0 + nk > (1ull << log_blowup)) return fail(CSTARK_ERR_INVALID_ARG, "coset range exceeds the blowup factor");
+    const size_t n = (size_t)1 << log_n;
+    const unsigned log_block = (unsigned)__builtin_ctz(block_len);
+    if (!cs::ntt_step_shape(log_n, log_block)) {
+        RC_TRY(interpolate_impl(c, d_evals + (size_t)col0 * n, d_coeffs + (size_t)col0 * n, ncols, log_n));
+        return lde_impl(c, d_coeffs, d_lde, width, col0, ncols, log_n, log_blowup, domain_offset, k0, nk);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const NttPlan *p;
+    const cs::StepTable *t;
+    RC_TRY(get_plan(c, log_n, &p));
+    RC_TRY(get_step_table(c, log_n, log_blowup, domain_offset, log_block, &t));
+    RC_TRY(ensure_ws(c, ((size_t)ncols << (log_n - log_block)) * 8)); // the factors A [ncols][T]
+    uint64_t *fac = (uint64_t *)c->ws;
+    HIP_TRY(cs::ntt_step_coefficients(d_evals + (size_t)col0 * n, fac, d_coeffs + (size_t)col0 * n, t->d, ncols, log_n, log_block, p->winv, p->n_inv, c->stream));
+    return lde_timed(c, (uint64_t)ncols * nk << log_n, [&] {
+        cs::NttArgs a{};
+        a.out = d_lde + (size_t)col0 * n; a.width = ncols; a.batch = nk; a.log_n = log_n;
+        a.out_batch_stride = (size_t)width * n; a.aux = p->aux_w;
+        HIP_TRY(cs::ntt_step_rows(a, t->w + (size_t)k0 * n, fac, log_block, c->stream));
+        return (int)CSTARK_OK;
+    });
 }
 
 // Periodic columns over the LDE domain: host columns [ncols][2^log_cycle] -> *d_tab = [b][ncols][cycle], an allocation of `keep`.  A
@@ -406,6 +471,7 @@ void cstark_ctx_destroy(cstark_ctx *c) {
     if (c->coef_ev) (void)hipEventDestroy(c->coef_ev);
     for (NttPlan &p : c->plans) { (void)hipFree(p.w); (void)hipFree(p.winv); (void)hipFree(p.aux_w); (void)hipFree(p.aux_winv); }
     for (CosetTable &t : c->cosets) { (void)hipFree(t.s); (void)hipFree(t.aux); }
+    for (cs::StepTable &t : c->steps) { (void)hipFree(t.d); (void)hipFree(t.w); }
     for (PeriodicTable &t : c->periodic) { (void)hipFree(t.tab); (void)hipFree(t.coset); (void)hipFree(t.binv); }
     for (PeriodicTable &t : c->small_periodic) (void)hipFree(t.tab);
     for (cs::AssertInverseTable &t : c->assert_inv) (void)hipFree(t.tab);
@@ -523,6 +589,10 @@ int cstark_interpolate_columns(cstark_ctx *c, uint64_t *d_evals, uint64_t *d_coe
 int cstark_lde_columns(cstark_ctx *c, const uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t log_n, uint32_t log_blowup,
                        uint64_t domain_offset, uint32_t k0, uint32_t nk) {
     return lde_impl(c, d_coeffs, d_lde, width, 0, width, log_n, log_blowup, domain_offset, k0, nk);
+}
+int cstark_step_columns(cstark_ctx *c, uint64_t *d_evals, uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols,
+                        uint32_t log_n, uint32_t block_len, uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk) {
+    return step_impl(c, d_evals, d_coeffs, d_lde, width, col0, ncols, log_n, block_len, log_blowup, domain_offset, k0, nk);
 }
 
 // ---- composition polynomial (first "next" row: engine into_poly + column split) -----------------------------------
@@ -944,6 +1014,10 @@ int cstark_tx_evaluate_transitions(cstark_ctx *c, const uint64_t *d_lde, uint64_
 int lde_column_range(cstark_ctx *c, const uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols, uint32_t log_n,
                      uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk) {
     return lde_impl(c, d_coeffs, d_lde, width, col0, ncols, log_n, log_blowup, domain_offset, k0, nk);
+}
+int step_column_range(cstark_ctx *c, uint64_t *d_evals, uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols, uint32_t log_n,
+                      uint32_t block_len, uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk) {
+    return step_impl(c, d_evals, d_coeffs, d_lde, width, col0, ncols, log_n, block_len, log_blowup, domain_offset, k0, nk);
 }
 int tx_build_trace_split(cstark_ctx *c, uint64_t *d_trace) {
     if (!c || !d_trace) return fail(CSTARK_ERR_INVALID_ARG, "tx_build_trace_split: null argument");

@@ -84,6 +84,14 @@ struct CosetTable {
     uint64_t *aux = nullptr; // [b][aux_words]: compact prescale / output-factor tables per coset (ntt.h), null for other sizes
     size_t aux_words = 0;
 };
+// the constants of the step-column transform (ntt.h): columns constant over blocks of 2^log_block rows
+struct StepTable {
+    unsigned log_n, log_b;
+    uint64_t offset;
+    unsigned log_block;
+    uint64_t *d; // [n]: the fixed vector D of (log_n, log_block)
+    uint64_t *w; // [b][n]: the forward column pass of D under each coset of (log_b, offset)
+};
 struct PeriodicTable {
     unsigned depth, log_n, log_b;
     uint64_t *tab;   // [b][48][1024]
@@ -153,6 +161,7 @@ struct cstark_ctx {
     // cached tables (deque: references stay valid as entries are added) and workspace
     std::deque<cs::NttPlan> plans;
     std::deque<cs::CosetTable> cosets;
+    std::deque<cs::StepTable> steps;
     std::deque<cs::PeriodicTable> periodic;
     uint64_t *coef_buf = nullptr; // device copy of the composition coefficients
     void *coef_stage = nullptr;   // pinned host staging of the same block: the upload is asynchronous, no wait for the caller's struct
@@ -222,10 +231,14 @@ int tx_shard_combine(cstark_ctx *c, const uint64_t *d_parts, uint64_t *d_out, ui
 // after ev_join and ev_mid, registers [0, TX_LATE_COLS) after ev_join2 as well.
 constexpr uint32_t TX_LATE_COLS = 37; // registers 0..36: the two curve points and the s-bit register between them
 constexpr uint32_t TX_COPY_COLS = 65; // registers 65..93: key / amount copies and the sigma range accumulator
+constexpr uint32_t TX_STEP_COLS = 27; // of these, registers 65..91 are constant over the 1024 rows of a transaction (the copies and the nonce)
 int tx_build_trace_split(cstark_ctx *c, uint64_t *d_trace);
 // LDE of columns [col0, col0 + ncols) of a table of `width` columns (same layout and arguments as cstark_lde_columns)
 int lde_column_range(cstark_ctx *c, const uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols, uint32_t log_n,
                      uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk);
+// cstark_step_columns for the prover: coefficients and extension of trace columns that are constant over blocks of block_len rows
+int step_column_range(cstark_ctx *c, uint64_t *d_evals, uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols, uint32_t log_n,
+                      uint32_t block_len, uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk);
 // internal (capi.hip): cstark_deep_composition_ext restricted to the first nk cosets, d_out = [m][nk][n]
 int evaluate_ood_frames(cstark_ctx *c, const uint64_t *d_coeffs, uint32_t width, const uint64_t *d_ccoef, uint32_t n_comp, uint32_t log_n,
                         const uint64_t zpts[2], uint64_t zb, uint64_t *out_trace, uint64_t *out_comp);

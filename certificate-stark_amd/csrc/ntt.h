@@ -38,6 +38,21 @@ hipError_t ntt_build_aux_plan(uint64_t *d_aux, const uint64_t *d_w, const NttThr
 hipError_t ntt_build_aux_coset(uint64_t *d_aux, const uint64_t *d_w, const uint64_t *d_s, const NttThreeStepShape &s, hipStream_t stream);
 
 hipError_t ntt_columns(const NttArgs &a, hipStream_t stream);
+
+// Step columns: constant over blocks of 2^log_block rows, f[i] = g[i >> log_block] (ntt.hip, "step columns").  Served at the three-step
+// sizes whose row length holds a whole number of periods T = n >> log_block; every other (log_n, log_block) takes ntt_columns.
+bool ntt_step_shape(unsigned log_n, unsigned log_block);
+// The constants of one (log_n, log_block, coset set), everything in Montgomery form: d_d [n] = the fixed vector D, and the forward column pass
+// of D under each coset of `a` -- a forward NttArgs with in = d_d, width = 1, its batch / prescale / aux fields as for ntt_columns --
+// written to a.scratch [batch][n] (a.out is not used).  d_winv: the n powers of w_n^-1.
+hipError_t ntt_step_build_tables(uint64_t *d_d, unsigned log_block, const uint64_t *d_winv, const NttArgs &a, hipStream_t stream);
+// d_evals [ncols][n] (only the first row of every block is read) -> d_fac [ncols][T], the per-column factors A, and d_coeffs [ncols][n],
+// the interpolants c_k = A[k mod T] D[k]
+hipError_t ntt_step_coefficients(const uint64_t *d_evals, uint64_t *d_fac, uint64_t *d_coeffs, const uint64_t *d_d, unsigned ncols, unsigned log_n,
+                                 unsigned log_block, const uint64_t *d_winv, uint64_t n_inv, hipStream_t stream);
+// The extension: the row pass alone, its input formed as d_wtab[batch][k1][c] * d_fac[column][c mod T] at the load.  Of `a`: out, width,
+// batch, log_n, out_batch_stride, aux.
+hipError_t ntt_step_rows(const NttArgs &a, const uint64_t *d_wtab, const uint64_t *d_fac, unsigned log_block, hipStream_t stream);
 // table[e] = base^e, e < n
 hipError_t ntt_power_table(uint64_t *d_table, size_t n, uint64_t base, hipStream_t stream);
 

@@ -224,7 +224,8 @@ struct AirJob {
     // Optional: the order in which the trace columns become complete when build() returns with parts of the trace still being
     // written on internal streams (TransactionAir).  The prover interpolates and extends batch after batch, waiting for a batch's
     // events first; empty = all columns at once.
-    struct ColumnBatch { uint32_t col0, ncols; hipEvent_t wait[2]; };
+    // block != 0: a step batch -- every column is constant over blocks of `block` rows (taken to cstark_step_columns where the proof's shape allows)
+    struct ColumnBatch { uint32_t col0, ncols; hipEvent_t wait[2]; uint32_t block = 0; };
     std::vector<ColumnBatch> batches;
     const uint64_t *pub_staging = nullptr; // pinned host copy of the public inputs, valid once every batch has been waited for
     bool public_ready = false;      // SchnorrAir: the extended public-input columns of this proof are in the arena
@@ -426,9 +427,12 @@ int commit_columns(cstark_ctx *c, ProveArena *a, AirJob &job, hipStream_t st, in
         const AirJob::ColumnBatch &cb = job.batches[i];
         for (hipEvent_t e : cb.wait)
             if (e) HIP_TRY(hipStreamWaitEvent(st, e, 0));
-        RC_TRY(cstark_interpolate_columns(c, a->trace + (size_t)cb.col0 * n, a->coeffs + (size_t)cb.col0 * n, cb.ncols, log_n));
+        // a step batch of an unsharded proof whose extension is the single-offset form: coefficients and cosets without full-length transforms
+        const bool step = cb.block != 0 && !job.sharded && job.log_b <= job.log_ce;
+        if (!step) RC_TRY(cstark_interpolate_columns(c, a->trace + (size_t)cb.col0 * n, a->coeffs + (size_t)cb.col0 * n, cb.ncols, log_n));
         if (i + 1 == job.batches.size()) HIP_TRY(hipEventRecord(a->ev[evi++], st));
-        RC_TRY(lde_trace(c, a, job, cb.col0, cb.ncols));
+        if (step) RC_TRY(step_column_range(c, a->trace, a->coeffs, a->lde, W, cb.col0, cb.ncols, log_n, cb.block, job.log_b, host::lde_offset(), job.k0, job.nk));
+        else RC_TRY(lde_trace(c, a, job, cb.col0, cb.ncols));
     }
     HIP_TRY(hipEventRecord(a->ev[evi++], st));
     return CSTARK_OK;
@@ -1062,7 +1066,9 @@ int tx_build(cstark_ctx *c, ProveArena *a, AirJob &job) {
     if (mode == 3) // two batches: everything but the curve registers once the Merkle recurrence and the message hash are done
         job.batches = {{TX_LATE_COLS, job.width - TX_LATE_COLS, {c->ev_join, c->ev_mid}}, {0, TX_LATE_COLS, {c->ev_join2, nullptr}}};
     else
-        job.batches = {{TX_COPY_COLS, job.width - TX_COPY_COLS, {nullptr, nullptr}},
+        // registers 65..91 are constant over a transaction (k_trace_aux): a step batch; the sigma range accumulator behind them is not
+        job.batches = {{TX_COPY_COLS, TX_STEP_COLS, {nullptr, nullptr}, 1024},
+                       {TX_COPY_COLS + TX_STEP_COLS, job.width - TX_COPY_COLS - TX_STEP_COLS, {nullptr, nullptr}},
                        {TX_LATE_COLS, TX_COPY_COLS - TX_LATE_COLS, {c->ev_join, c->ev_mid}},
                        {0, TX_LATE_COLS, {c->ev_join2, nullptr}}};
     return CSTARK_OK;

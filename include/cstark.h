@@ -131,6 +131,13 @@ int cstark_interpolate_columns(cstark_ctx *ctx, uint64_t *d_evals, uint64_t *d_c
  * Sharding by coset is what distributes one proof over several GPUs. */
 int cstark_lde_columns(cstark_ctx *ctx, const uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t log_n,
                        uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk);
+/* Both stages for columns [col0, col0 + ncols) of a table of `width` columns whose values are constant over blocks of block_len rows
+ * (a power of two): d_coeffs and d_lde receive what cstark_interpolate_columns and cstark_lde_columns write for these columns, other
+ * columns are not touched.  At trace lengths 2^16, 2^18 and 2^20 with block_len >= the square root of the length only the first row of
+ * every block is read, d_evals stays intact and no full-length transform of the column is run; at every other shape the columns go
+ * through the two calls above (and their part of d_evals is destroyed). */
+int cstark_step_columns(cstark_ctx *ctx, uint64_t *d_evals, uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols,
+                        uint32_t log_n, uint32_t block_len, uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk);
 
 /* FieldExtension::Quadratic / Cubic: the same three stages over the degree-m extension, m = 2: F_p[u]/(u^2 - 2u - 2), m = 3:
  * F_p[v]/(v^3 + v + 1) [assumption: the two polynomials of the reference's own curve tower, src/utils/ecc.rs:407-648; the fork's
