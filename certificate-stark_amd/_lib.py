@@ -38,6 +38,10 @@ class OptionsStruct(C.Structure):
                                            "field_extension", "fri_folding_factor", "fri_max_remainder")]
 
 
+class SchnorrStatementStruct(C.Structure):
+    _fields_ = [("n_sig", C.c_uint32), ("messages", u64p), ("sig_rx", u64p), ("sig_s", u8p)]
+
+
 _lib = None
 
 

@@ -621,7 +621,7 @@ class Backend:
         """cstark_air_verify: proofs of TransactionAir, MerkleAir, RangeProofAir and RescueAir (bytes, any mix) in one call.  airs: the AIR
         each proof is expected to be (Backend.AIR_*; one value for all, or one per proof).  public_inputs: [count][14] words (or [14] for
         every proof), memory form -- initial root | final root, seed | result, or the range number in word 0.  numbers (instead of
-        public_inputs, RangeProofAir only): one number for all proofs or [count] numbers.  options: as for tx_verify.  Returns the verdicts, int32 [count]; SchnorrAir proofs are UNSUPPORTED."""
+        public_inputs, RangeProofAir only): one number for all proofs or [count] numbers.  options: as for tx_verify.  Returns the verdicts, int32 [count]; SchnorrAir proofs are UNSUPPORTED here (schnorr_verify takes their statement)."""
         count = len(proofs)
         verdicts = np.zeros(count, np.int32)
         if count == 0:
@@ -651,8 +651,55 @@ class Backend:
         del keep
         return verdicts
 
+    def schnorr_verify(self, proofs, statements, options=None):
+        """cstark_schnorr_verify: SchnorrAir proofs (bytes) against their statements in one call.  statements: one (messages [n][28],
+        sig_rx [n][6], sig_s [n][32]) triple per proof -- or an object with those attributes, such as a SchnorrExample -- memory form;
+        the batch may mix numbers of signatures, hashes, extensions and options.  options: as for tx_verify.  Returns the verdicts, int32 [count]."""
+        count = len(proofs)
+        verdicts = np.zeros(count, np.int32)
+        vp = verdicts.ctypes.data_as(C.POINTER(C.c_int32))
+        if count == 0:
+            check(self.lib.cstark_schnorr_verify(self.ctx, C.c_uint32(0), None, None, None, None, vp))
+            return verdicts
+        if len(statements) != count:
+            raise ValueError("one statement per proof")
+        keep = [bytes(p) for p in proofs]
+        ptrs = (C.POINTER(C.c_uint8) * count)()
+        lens = (C.c_size_t * count)()
+        stm = (_lib.SchnorrStatementStruct * count)()
+        arrays = []
+        for i, (p, st) in enumerate(zip(keep, statements)):
+            ptrs[i] = C.cast(C.c_char_p(p), C.POINTER(C.c_uint8))
+            lens[i] = len(p)
+            msg, rx, s = (st.messages, st.sig_rx, st.sig_s) if hasattr(st, "messages") else st
+            msg = np.ascontiguousarray(np.asarray(msg, np.uint64).reshape(-1, 28))
+            rx = np.ascontiguousarray(np.asarray(rx, np.uint64).reshape(-1, 6))
+            s = np.ascontiguousarray(np.asarray(s, np.uint8).reshape(-1, 32))
+            if not (msg.shape[0] == rx.shape[0] == s.shape[0]):
+                raise ValueError("messages, sig_rx and sig_s state different numbers of signatures")
+            arrays.append((msg, rx, s))
+            stm[i].n_sig = msg.shape[0]
+            stm[i].messages, stm[i].sig_rx, stm[i].sig_s = msg.ctypes.data_as(u64p), rx.ctypes.data_as(u64p), s.ctypes.data_as(_lib.u8p)
+        o = None if options is None else C.byref(self._options_struct(options))
+        check(self.lib.cstark_schnorr_verify(self.ctx, C.c_uint32(count), ptrs, lens, stm, o, vp))
+        del keep, arrays
+        return verdicts
+
+    def schnorr_public_at(self, messages, sig_rx, z):
+        """cstark_schnorr_public_at: the 19 public-input columns and the 12 sequence-value polynomials of the statement at z (m words,
+        memory form, m = 1, 2 or 3) -> uint64 [31][m]"""
+        msg = np.ascontiguousarray(np.asarray(messages, np.uint64).reshape(-1, 28))
+        rx = np.ascontiguousarray(np.asarray(sig_rx, np.uint64).reshape(-1, 6))
+        if msg.shape[0] != rx.shape[0]:
+            raise ValueError("messages and sig_rx state different numbers of signatures")
+        zz = np.ascontiguousarray(np.asarray(z, np.uint64).reshape(-1))
+        out = np.zeros((31, zz.size), np.uint64)
+        check(self.lib.cstark_schnorr_public_at(self.ctx, C.c_uint32(msg.shape[0]), msg.ctypes.data_as(u64p), rx.ctypes.data_as(u64p),
+                                                zz.ctypes.data_as(u64p), C.c_uint32(zz.size), out.ctypes.data_as(u64p)))
+        return out
+
     def verify_h2d_bytes(self):
-        """bytes the last tx_verify / air_verify copied host -> device: proof bytes, descriptors and opening records"""
+        """bytes the last tx_verify / air_verify / schnorr_verify copied host -> device: proof bytes, descriptors and opening records"""
         n = C.c_uint64(0)
         check(self.lib.cstark_verify_h2d_bytes(self.ctx, C.byref(n)))
         return int(n.value)

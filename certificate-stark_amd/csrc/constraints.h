@@ -105,7 +105,8 @@ hipError_t launch_eval_transitions(const CeParams &p, unsigned nk, hipStream_t s
 // cur[c * nf + j] (c < 94), next[c * nf + j] and the periodic values per[c * nf + j] (c < 48); out[i * nf + j], i < 115 (device memory)
 hipError_t launch_eval_frames(const uint64_t *cur, const uint64_t *next, const uint64_t *per, uint64_t *out, unsigned nf, hipStream_t stream);
 // The same for any AIR the verifier knows (CSTARK_AIR_STATE_TRANSITION: launch_eval_frames; MerkleAir 65 / 33 periodic / 106 slots,
-// RangeProofAir 2 / 0 / 2, RescueAir 14 / 29 / 14), through the bodies the table kernels run
+// RangeProofAir 2 / 0 / 2, RescueAir 14 / 29 / 14, SchnorrAir 56 / 36 + the 19 public-input values of the frame's point / 56, in the four
+// parts of its table kernel), through the bodies the table kernels run
 hipError_t launch_eval_frames_air(int air, const uint64_t *cur, const uint64_t *next, const uint64_t *per, uint64_t *out, unsigned nf, hipStream_t stream);
 constexpr int CE_NUM_PARTS = 9; // launches of the fused evaluation: rounds, dbl0, add0, dbl1, add1, final, lin_a, lin_b, lin_c (split form: the one
                                 // linear pass is timed as lin_a, lin_b = 0, lin_c = the extension and the recombination)

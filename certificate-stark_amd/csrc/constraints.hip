@@ -1867,22 +1867,10 @@ __global__ __launch_bounds__(NT) void k_eval_transitions_merkle(const fp *lde, c
 // PART: 0 = double-and-add step of s*G (slots 0..18), 1 = of h*P (19..37), 2 = limb accumulators, Rescue round, hash copies, 3 = final
 // addition.  One kernel for everything needs 450 VGPRs (one wave per SIMD); the parts accumulate into the zero-filled output one after
 // the other on the stream.
-template <int PART>
-__global__ __launch_bounds__(NT) void k_eval_transitions_schnorr(const fp *lde, const fp *aux, const fp *ptab, fp *out, unsigned log_n, unsigned k0) {
-    const size_t n = (size_t)1 << log_n;
-    const size_t j = blockIdx.x * (size_t)NT + threadIdx.x;
-    const unsigned kk = blockIdx.y;
-    const fp *base = lde + (size_t)kk * 56 * n;
-    Frame f;
-    f.n = n;
-    f.cur_p = base + j;
-    f.next_p = base + ((j + 1) & (n - 1));
-    f.per_p = ptab + (size_t)(k0 + kk) * 36 * 512 + (j & 511);
-    f.pcycle = 512;
-    Frame fr = f; // view whose column P_ARK is the first round-constant column (index 8 here)
-    fr.per_p = f.per_p - (size_t)(P_ARK - 8) * 512;
-    const fp *ax = aux + (size_t)kk * 19 * n + j;
-    AccAll acc{out + (size_t)kk * 56 * n + j, n};
+// The body, shared by the table kernel and the free-standing-frame kernel: ax = element 0 of the 19 public-input values of the point,
+// value c at ax[c * astride]; fr = f with column P_ARK at the first round-constant column (index 8 here).
+template <int PART, class Acc>
+__device__ __forceinline__ void schnorr_transitions(Acc &acc, const Frame &f, const Frame &fr, const fp *ax, size_t astride) {
     const fp global_mask = f.pv(0), scalar_mult = f.pv(1), doubling = f.pv(2), hash_flag = f.pv(7);
     const fp copy_hash = fp_mul(c_not(hash_flag), global_mask);
     const fp final_add = fp_mul(c_not(scalar_mult), global_mask);
@@ -1892,7 +1880,7 @@ __global__ __launch_bounds__(NT) void k_eval_transitions_schnorr(const fp *lde, 
         enforce_scalar_mult_step(acc, f, 0, gx, gy, doubling, addition);
     }
     if constexpr (PART == 1) {
-        const Fp6 px = fp6_load_strided(ax, n), py = fp6_load_strided(ax + 6 * n, n); // periodic pkey columns
+        const Fp6 px = fp6_load_strided(ax, astride), py = fp6_load_strided(ax + 6 * astride, astride); // periodic pkey columns
         enforce_scalar_mult_step(acc, f, 19, px, py, doubling, addition);
     }
     if constexpr (PART == 2) {
@@ -1909,7 +1897,7 @@ __global__ __launch_bounds__(NT) void k_eval_transitions_schnorr(const fp *lde, 
 #pragma unroll 1
         for (int i = 0; i < 7; i++) {
             acc.add(42 + i, copy_hash, fp_sub(f.cur(42 + i), f.next(42 + i)));
-            acc.add(49 + i, copy_hash, fp_sub(f.next(49 + i), ax[(size_t)(12 + i) * n]));
+            acc.add(49 + i, copy_hash, fp_sub(f.next(49 + i), ax[(size_t)(12 + i) * astride]));
         }
     }
     if constexpr (PART == 3) {
@@ -1924,6 +1912,46 @@ __global__ __launch_bounds__(NT) void k_eval_transitions_schnorr(const fp *lde, 
             acc.add(12 + i, final_add, fp_sub(f.next(12 + i), r.z.c[i]));
         }
     }
+}
+template <int PART>
+__global__ __launch_bounds__(NT) void k_eval_transitions_schnorr(const fp *lde, const fp *aux, const fp *ptab, fp *out, unsigned log_n, unsigned k0) {
+    const size_t n = (size_t)1 << log_n;
+    const size_t j = blockIdx.x * (size_t)NT + threadIdx.x;
+    const unsigned kk = blockIdx.y;
+    const fp *base = lde + (size_t)kk * 56 * n;
+    Frame f;
+    f.n = n;
+    f.cur_p = base + j;
+    f.next_p = base + ((j + 1) & (n - 1));
+    f.per_p = ptab + (size_t)(k0 + kk) * 36 * 512 + (j & 511);
+    f.pcycle = 512;
+    Frame fr = f; // view whose column P_ARK is the first round-constant column (index 8 here)
+    fr.per_p = f.per_p - (size_t)(P_ARK - 8) * 512;
+    AccAll acc{out + (size_t)kk * 56 * n + j, n};
+    schnorr_transitions<PART>(acc, f, fr, aux + (size_t)kk * 19 * n + j, n);
+}
+// The same on free-standing frames (the verifier's out-of-domain check): frame j is cur[c * nf + j], next[c * nf + j] and per[c * nf + j],
+// c < 36 the periodic values, 36 <= c < 55 the 19 public-input values of the frame's point; the 56 slots out[i * nf + j] are zeroed by
+// part 0, then accumulated by the parts in stream order.
+template <int PART>
+__global__ __launch_bounds__(NT) void k_eval_frames_schnorr(const fp *__restrict__ cur, const fp *__restrict__ next, const fp *__restrict__ per,
+                                                            fp *__restrict__ out, unsigned nf) {
+    const unsigned j = blockIdx.x * NT + threadIdx.x;
+    if (j >= nf) return;
+    Frame f;
+    f.n = nf;
+    f.cur_p = cur + j;
+    f.next_p = next + j;
+    f.per_p = per + j;
+    f.pcycle = nf;
+    Frame fr = f;
+    fr.per_p = f.per_p - (size_t)(P_ARK - 8) * nf;
+    if constexpr (PART == 0) {
+#pragma unroll 1
+        for (int i = 0; i < 56; i++) out[(size_t)i * nf + j] = 0;
+    }
+    AccAll acc{out + j, nf};
+    schnorr_transitions<PART>(acc, f, fr, per + (size_t)36 * nf + j, nf);
 }
 // ---- SchnorrAir, fused: the merged transition sum  sum_i (alpha_i + beta_i x^adj_i) C_i(x)  without the 56 materialised values -------
 // The same gadget templates as the TransactionAir evaluator (lazy F_p6 arithmetic, one 128-bit accumulation per section) behind an
@@ -2547,7 +2575,12 @@ hipError_t launch_eval_frames_air(int air, const uint64_t *cur, const uint64_t *
     else if (air == 1) hipLaunchKernelGGL((k_eval_frames_sub<1, 106>), grid, block, 0, stream, cur, next, per, out, nf);
     else if (air == 3) hipLaunchKernelGGL((k_eval_frames_sub<3, 2>), grid, block, 0, stream, cur, next, per, out, nf);
     else if (air == 4) hipLaunchKernelGGL((k_eval_frames_sub<4, 14>), grid, block, 0, stream, cur, next, per, out, nf);
-    else return hipErrorInvalidValue;
+    else if (air == 2) {
+        hipLaunchKernelGGL(k_eval_frames_schnorr<0>, grid, block, 0, stream, cur, next, per, out, nf);
+        hipLaunchKernelGGL(k_eval_frames_schnorr<1>, grid, block, 0, stream, cur, next, per, out, nf);
+        hipLaunchKernelGGL(k_eval_frames_schnorr<2>, grid, block, 0, stream, cur, next, per, out, nf);
+        hipLaunchKernelGGL(k_eval_frames_schnorr<3>, grid, block, 0, stream, cur, next, per, out, nf);
+    } else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 hipError_t launch_eval_transitions_rescue(const uint64_t *lde, const uint64_t *ptab, uint64_t *out, unsigned log_n, unsigned k0, unsigned nk,

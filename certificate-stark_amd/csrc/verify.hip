@@ -1,12 +1,14 @@
 // TransactionExample::verify (src/lib.rs:144-150) and the sub-AIR examples' verify (MerkleAir, RangeProofAir, RescueAir) for proofs in this
 // library's own layout (include/cstark.h, "Proof layout"), many proofs per call, any mix of AIRs: what differs between the AIRs is the
-// VAir record of each proof's descriptor, the constraint bodies (constraints.hip) and the cached periodic coefficients.  SchnorrAir is
-// not verified (UNSUPPORTED).  Pipeline of one chunk of proofs:
+// VAir record of each proof's descriptor, the constraint bodies (constraints.hip) and the cached periodic coefficients.  SchnorrAir
+// (cstark_schnorr_verify) has an O(n) statement: it is staged behind the proof bytes, its channel seed is hashed on the host, and the 31
+// statement-dependent values of the out-of-domain check -- the 19 public-input columns and the 12 sequence-assertion polynomials at z --
+// are barycentric sums over the trace domain, formed in one pass by k_vfy_schnorr_public.  Pipeline of one chunk of proofs:
 //   host    parse (structure only: every count against the stated options) and the per-proof constants of the domains; the raw
 //           proof bytes and one descriptor per proof go to one pinned staging block -> ONE host-to-device copy
 //   device  transcript replay, one workgroup per proof (Blake3 or Sha3 coin, vhash.cuh): coefficients, z, DEEP coefficients, layer
 //           alphas, remainder commitment, proof of work, query positions and their folded positions and slots
-//           per (AIR, extension degree m) present: out-of-domain frames (periodic columns at z^(n/cycle) from cached coefficients, the frame
+//           per (AIR, extension degree m) present: (SchnorrAir: the statement's 31 values at z) -> out-of-domain frames (periodic columns at z^(n/cycle) from cached coefficients, the frame
 //           sampled along t -> e(t) for m > 1) -> the AIR's constraints on every frame (constraints.hip, launch_eval_frames_air) -> merge
 //           and compare with sum_i H_i z^i; DEEP + FRI, one lane per (proof, query)
 //           all proofs: Merkle openings, one lane per opened row (leaf hash + path walk, Blake3 or Sha3); remainder degree (exact,
@@ -18,6 +20,7 @@
 #include <assert.h>
 #include <algorithm>
 #include <array>
+#include <type_traits>
 #include <chrono>
 #include <vector>
 #include "../../include/cstark.h"
@@ -26,6 +29,7 @@
 #include "air_tx_host.h"
 #include "coin.h"
 #include "proof_layout.h"
+#include "transcript.h"
 #include "blake3_compress.cuh"
 #include "ext.cuh"
 #include "keccak.cuh"
@@ -47,8 +51,13 @@ enum : uint32_t {
 // constraint-evaluation blowup | transition constraints | single-row assertions | public words in the channel seed | periodic columns
 // and the binary logarithm of their cycle | the first asserted register.  Assertion a < na / 2 is on register areg + a at row 0,
 // assertion na / 2 + a on the same register at row n - 1; their values are the descriptor's K_PUB words, in that order.
-struct VAir { uint32_t air, w, ce, nc, na, npub, nper, log_cycle, areg; };
-constexpr uint32_t VMAX_NC = 115, VMAX_NPER = 48, VMAX_GROUPS = 8;
+// naux: frame entries beyond the periodic ones that depend on the statement (SchnorrAir's 19 public-input columns at z).
+struct VAir { uint32_t air, w, ce, nc, na, npub, nper, log_cycle, areg, naux; };
+constexpr uint32_t VMAX_NC = 115, VMAX_NPER = 56, VMAX_GROUPS = 8;
+// SchnorrAir's assertions (air_groups.h, air_shape(2)) as the merge reads them: register, divisor group (0: step 0, 1: step 511 of every
+// 512-row block) and value (0, 1: the constants zero and one; 2 + q: sequence value q of the statement)
+constexpr uint32_t VMAX_NA = 61, SCH_PUBLIC = 31, SCH_AUX = 19, SCH_TILE = 4; // SCH_TILE signatures (waves) per workgroup of k_vfy_schnorr_public
+struct VAsserts { uint8_t n, reg[VMAX_NA], div[VMAX_NA], val[VMAX_NA]; };
 // the degree-adjustment group of every constraint of one AIR (k_vfy_ood_check's argument; the exponents are K_ADJ of the proof)
 struct VGroups { uint8_t n, g[VMAX_NC]; };
 
@@ -76,6 +85,10 @@ struct VDesc {
     uint64_t k[K_WORDS];  // constants of its domains (host; copied to the transcript block)
     uint64_t pub[14];     // the public words of the channel seed, memory form (a.npub of them)
     uint64_t pcoef;       // word offset of the AIR's periodic coefficients [a.nper][2^a.log_cycle] in the cache
+    uint64_t stmt;        // SchnorrAir: byte offset of the statement in the chunk's block, messages [n_sig][28] | R.x [n_sig][6] | s [n_sig][32]
+    uint64_t sp;          // ... word offset of its public values in the device region: partials [tiles][31][m], then the values [31][m]
+    uint32_t seed[8];     // ... the channel seed's digest (host: transcript.h, channel_seed)
+    uint32_t n_sig;
     VAir a;
     uint32_t ood, trows, tpaths, crows, cpaths, rem;                 // byte offsets inside the proof
     uint32_t lrows[VMAX_LAYERS];
@@ -221,13 +234,135 @@ __global__ __launch_bounds__(128) void k_vfy_openings(const uint8_t *__restrict_
     slots[o.slot] = !canonical ? (uint32_t)RK_MALFORMED : match ? (uint32_t)RK_NONE : rank;
 }
 
+template <int R, class F> __device__ __forceinline__ void static_down(F &&f) {
+    f(std::integral_constant<int, R>{});
+    if constexpr (R > 0) static_down<R - 1>(f);
+}
+__host__ __device__ inline uint32_t schnorr_tiles(uint32_t n_sig) { return (n_sig + SCH_TILE - 1) / SCH_TILE; }
+
+// SchnorrAir's statement at z.  With w = w_n, n = 512 T, and term_i = w^i / (z - w^i), every column that is non-zero on rows R only has
+// the value (z^n - 1) / n * sum_{i in R} v_i term_i at z, and a sequence polynomial (degree < T, values on the coset w^first <w^512>)
+// the value (z^T w^(-first T) - 1) / T * sum_t v_t term_{512 t + first}.  This kernel forms the sums: grid (tiles, proofs of the group),
+// one wave per signature (512 rows), lane l rows 8 l .. 8 l + 7: one inversion per lane (prefix products), the block sum S_t through
+// shared memory, the six single terms (rows 0, 7, 15, 23, 31, 511) beside it, then lanes 0..30 form the signature's 31 contributions:
+//   0..11   public key word j: msg[t][j] S_t                  12..18  hash input j: sum_{i<4} msg[t][j + 7 i] term_{512 t + 8 i + 7}
+//   19..24  R.x word k at step 0: rx[t][k] term_{512 t}       25..30  at step 511: rx[t][k] term_{512 t + 511}
+// The workgroup's SCH_TILE signatures are added in shared memory; its partial [31][M] goes out with plain stores (no atomics on field
+// elements) and k_vfy_schnorr_public_sum adds the tiles and applies the two factors.  Every bound is the descriptor's n_sig, which the
+// host took from the validated header.
+template <int M>
+__global__ __launch_bounds__(64 * SCH_TILE) void k_vfy_schnorr_public(const uint8_t *__restrict__ buf, const VDesc *__restrict__ desc,
+                                                                      const uint32_t *__restrict__ gp, const uint64_t *__restrict__ tbase,
+                                                                      uint64_t *__restrict__ spub) {
+    __shared__ Ext<M> red[SCH_TILE][64];
+    __shared__ Ext<M> spec[SCH_TILE][7];        // term of row 0, 7, 15, 23, 31, 511 of the block | S_t
+    __shared__ Ext<M> contrib[SCH_TILE][32];
+    const VDesc &d = desc[gp[blockIdx.y]];
+    const uint32_t T = d.n_sig;
+    if (blockIdx.x >= schnorr_tiles(T)) return; // the grid is sized for the group's largest statement (uniform per workgroup)
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t t = blockIdx.x * SCH_TILE + wave;
+    const bool live = t < T;
+    const Ext<M> z = x_load<M>(tbase + d.tb + toff(d).z);
+    const fp wn = d.k[K_WN];
+    Ext<M> sum = x_zero<M>();
+    if (live) {
+        fp w[8];
+        Ext<M> dif[8], pre[8];
+        // w_n^(512 t + 8 lane), row < 2^21: every lane takes the same 21 steps (a loop that ends with the lane's exponent would leave
+        // lane 0 of the first signature, whose exponent is 0, out of whatever the compiler places around it)
+        const uint32_t row0 = 512 * t + 8 * lane;
+        w[0] = FP_ONE;
+#pragma unroll 1
+        for (int b = 20; b >= 0; b--) {
+            w[0] = fp_sqr(w[0]);
+            const fp ww = fp_mul(w[0], wn);
+            w[0] = (row0 >> b) & 1 ? ww : w[0];
+        }
+#pragma unroll
+        for (int r = 1; r < 8; r++) w[r] = fp_mul(w[r - 1], wn);
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            dif[r] = x_sub(z, x_base<M>(w[r]));
+            pre[r] = r ? x_mul(pre[r - 1], dif[r]) : dif[0];
+        }
+        Ext<M> inv = x_inv(pre[7]);
+        static_down<7>([&](auto rc) { // indices known at compile time: the arrays stay in registers
+            constexpr int r = decltype(rc)::value;
+            Ext<M> term;
+            if constexpr (r > 0) term = x_scale(x_mul(inv, pre[r - 1]), w[r]);
+            else term = x_scale(inv, w[0]);
+            inv = x_mul(inv, dif[r]);
+            sum = x_add(sum, term);
+            if (r == 0 && lane == 0) spec[wave][0] = term;
+            if (r == 7 && lane < 4) spec[wave][1 + lane] = term;
+            if (r == 7 && lane == 63) spec[wave][5] = term;
+        });
+    }
+    red[wave][lane] = sum;
+    __syncthreads();
+    for (uint32_t s = 32; s > 0; s >>= 1) {
+        if (lane < s) red[wave][lane] = x_add(red[wave][lane], red[wave][lane + s]);
+        __syncthreads();
+    }
+    if (lane == 0) spec[wave][6] = red[wave][0];
+    __syncthreads();
+    if (lane < SCH_PUBLIC) {
+        Ext<M> c = x_zero<M>();
+        if (live) {
+            const uint8_t *msg = buf + d.stmt + 8 * 28 * (size_t)t, *rx = buf + d.stmt + 8 * (28 * (size_t)T + 6 * (size_t)t);
+            if (lane < 12) c = x_scale(spec[wave][6], ld64(msg + 8 * lane));
+            else if (lane < 19) {
+                for (uint32_t i = 0; i < 4; i++) c = x_add(c, x_scale(spec[wave][1 + i], ld64(msg + 8 * (lane - 12 + 7 * i))));
+            } else if (lane < 25) c = x_scale(spec[wave][0], ld64(rx + 8 * (lane - 19)));
+            else c = x_scale(spec[wave][5], ld64(rx + 8 * (lane - 25)));
+        }
+        contrib[wave][lane] = c;
+    }
+    __syncthreads();
+    if (wave == 0 && lane < SCH_PUBLIC) {
+        Ext<M> c = contrib[0][lane];
+        for (uint32_t v = 1; v < SCH_TILE; v++) c = x_add(c, contrib[v][lane]);
+        uint64_t *o = spub + d.sp + (size_t)M * (SCH_PUBLIC * blockIdx.x + lane);
+        for (int q = 0; q < M; q++) o[q] = c.c[q];
+    }
+}
+// One workgroup per proof of the group, lane v < 31: the tiles' partials added, times (z^n - 1) / n (v < 19) or
+// (z^T w_512^(0 | 1) - 1) / T (the sequence values at step 0 | 511: w^(-511 T) = w_512) -> the values [31][M] behind the partials.
+template <int M>
+__global__ __launch_bounds__(64) void k_vfy_schnorr_public_sum(const VDesc *__restrict__ desc, const uint32_t *__restrict__ gp,
+                                                               const uint64_t *__restrict__ tbase, uint64_t *__restrict__ spub) {
+    const VDesc &d = desc[gp[blockIdx.x]];
+    const uint32_t v = threadIdx.x, tiles = schnorr_tiles(d.n_sig);
+    if (v >= SCH_PUBLIC) return;
+    Ext<M> acc = x_zero<M>();
+    for (uint32_t i = 0; i < tiles; i++) acc = x_add(acc, x_load<M>(spub + d.sp + (size_t)M * (SCH_PUBLIC * i + v)));
+    Ext<M> zt = x_load<M>(tbase + d.tb + toff(d).z); // z^T, T = n / 512
+    for (uint32_t s = 9; s < d.log_n; s++) zt = x_mul(zt, zt);
+    Ext<M> f;
+    uint64_t count;
+    if (v < SCH_AUX) {
+        f = zt;
+        for (uint32_t s = 0; s < 9; s++) f = x_mul(f, f);
+        count = 1ull << d.log_n;
+    } else {
+        f = v < SCH_AUX + 6 ? zt : x_scale(zt, fp_pow(d.k[K_WN], d.n_sig));
+        count = d.n_sig;
+    }
+    f = x_scale(x_sub(f, x_one<M>()), fp_inv(fp_from_u64(count)));
+    acc = x_mul(acc, f);
+    uint64_t *o = spub + d.sp + (size_t)M * (SCH_PUBLIC * tiles + v);
+    for (int q = 0; q < M; q++) o[q] = acc.c[q];
+}
+
 // Out-of-domain frames of the proofs gp[0..G) of one AIR (one workgroup each): periodic values at z^(n / cycle) from the proof's
 // coefficient table in the cache (none for an AIR without periodic columns), then K frames t = 0..K-1 whose entries are e(t) = sum_q e_q t^q (K = 1 for m = 1); frame j of the group at
 // column stride F.  bad[g] = 1 if an out-of-domain word is not below p.
 template <int M>
 __global__ __launch_bounds__(128) void k_vfy_ood_frames(const uint8_t *__restrict__ buf, const VDesc *__restrict__ desc, const uint32_t *__restrict__ gp,
-                                                        const uint64_t *__restrict__ tbase, const uint64_t *__restrict__ pcoef, uint32_t K, uint32_t F, fp *__restrict__ cur,
-                                                        fp *__restrict__ nxt, fp *__restrict__ per, uint32_t *__restrict__ bad) {
+                                                        const uint64_t *__restrict__ tbase, const uint64_t *__restrict__ pcoef, const uint64_t *__restrict__ spub,
+                                                        uint32_t K, uint32_t F, fp *__restrict__ cur, fp *__restrict__ nxt, fp *__restrict__ per,
+                                                        uint32_t *__restrict__ bad) {
     __shared__ Ext<M> pv[VMAX_NPER];
     const VDesc &d = desc[gp[blockIdx.x]];
     const uint8_t *pb = buf + d.base;
@@ -235,10 +370,12 @@ __global__ __launch_bounds__(128) void k_vfy_ood_frames(const uint8_t *__restric
     const TOff to = toff(d);
     const uint32_t tid = threadIdx.x;
     bool ok = true;
-    const uint32_t W = d.a.w, NP = d.a.nper;
+    const uint32_t W = d.a.w, NP = d.a.nper + d.a.naux;
     for (uint32_t i = tid; i < (2 * W + d.a.ce) * M; i += 128) ok &= ld64(pb + d.ood + 8 * i) < FP_P;
     const int any_bad = __syncthreads_or(!ok);
-    if (tid < NP) {
+    if (tid >= d.a.nper && tid < NP) // the statement's values at z (k_vfy_schnorr_public_sum)
+        pv[tid] = x_load<M>(spub + d.sp + (size_t)M * (SCH_PUBLIC * schnorr_tiles(d.n_sig) + tid - d.a.nper));
+    if (tid < d.a.nper) {
         Ext<M> zp = x_load<M>(tb + to.z);
         for (uint32_t s = d.a.log_cycle; s < d.log_n; s++) zp = x_mul(zp, zp);
         const uint32_t cycle = 1u << d.a.log_cycle;
@@ -271,7 +408,8 @@ template <int M> struct Lagrange { uint64_t w[18][M]; };
 template <int M>
 __global__ __launch_bounds__(64) void k_vfy_ood_check(const uint8_t *__restrict__ buf, const VDesc *__restrict__ desc, const uint32_t *__restrict__ gp,
                                                       uint32_t G, uint32_t K, uint32_t F, const fp *__restrict__ cvals, const uint32_t *__restrict__ bad,
-                                                      Lagrange<M> lag, VGroups grps, const uint64_t *__restrict__ tbase, uint32_t *__restrict__ slots) {
+                                                      Lagrange<M> lag, VGroups grps, VAsserts asr, const uint64_t *__restrict__ spub,
+                                                      const uint64_t *__restrict__ tbase, uint32_t *__restrict__ slots) {
     const uint32_t g = blockIdx.x * 64 + threadIdx.x;
     if (g >= G) return;
     const VDesc &d = desc[gp[g]];
@@ -301,7 +439,26 @@ __global__ __launch_bounds__(64) void k_vfy_ood_check(const uint8_t *__restrict_
     acc = x_mul(acc, x_mul(x_sub(z, x_base<M>(w_last)), x_inv(x_sub(zn, one))));
     const Ext<M> xb = x_pow(z, k[K_BADJ]);
     Ext<M> first = x_zero<M>(), last = x_zero<M>();
-    const uint32_t hn = d.a.na / 2;
+    Ext<M> d_first = x_sub(z, one), d_last = x_sub(z, x_base<M>(w_last));
+    if (d.a.air == CSTARK_AIR_SCHNORR) {
+        // 61 assertions on every 512th row from row 0 or row 511: divisors z^T - K_PUB[0 | 1] (= w_n^(first T)), values constant or the
+        // statement's sequence values at z
+        Ext<M> zt = z;
+        for (uint32_t s = 9; s < d.log_n; s++) zt = x_mul(zt, zt);
+        d_first = x_sub(zt, x_base<M>(k[K_PUB]));
+        d_last = x_sub(zt, x_base<M>(k[K_PUB + 1]));
+        const uint64_t *sv = spub + d.sp + (size_t)M * (SCH_PUBLIC * schnorr_tiles(d.n_sig) + SCH_AUX);
+#pragma unroll 1
+        for (uint32_t a = 0; a < asr.n; a++) {
+            const Ext<M> c = ld_ext<M>(pb + d.ood + 8 * M * asr.reg[a]);
+            const uint32_t vk = asr.val[a];
+            const Ext<M> val = vk >= 2 ? x_load<M>(sv + M * (vk - 2)) : vk ? one : x_zero<M>();
+            const Ext<M> term = x_mul(x_sub(c, val), x_add(x_load<M>(tb + to.ba + M * a), x_mul(x_load<M>(tb + to.bb + M * a), xb)));
+            if (asr.div[a]) last = x_add(last, term);
+            else first = x_add(first, term);
+        }
+    }
+    const uint32_t hn = d.a.air == CSTARK_AIR_SCHNORR ? 0 : d.a.na / 2;
 #pragma unroll 1
     for (uint32_t a = 0; a < hn; a++) {
         const Ext<M> c = ld_ext<M>(pb + d.ood + 8 * M * (d.a.areg + a));
@@ -309,7 +466,7 @@ __global__ __launch_bounds__(64) void k_vfy_ood_check(const uint8_t *__restrict_
         last = x_add(last, x_mul(x_sub(c, x_base<M>(k[K_PUB + hn + a])),
                                  x_add(x_load<M>(tb + to.ba + M * (hn + a)), x_mul(x_load<M>(tb + to.bb + M * (hn + a)), xb))));
     }
-    const Ext<M> lhs = x_add(acc, x_add(x_mul(first, x_inv(x_sub(z, one))), x_mul(last, x_inv(x_sub(z, x_base<M>(w_last))))));
+    const Ext<M> lhs = x_add(acc, x_add(x_mul(first, x_inv(d_first)), x_mul(last, x_inv(d_last))));
     Ext<M> rhs = x_zero<M>(), zi = one;
     for (uint32_t i = 0; i < d.a.ce; i++) {
         rhs = x_add(rhs, x_mul(ld_ext<M>(pb + d.ood + 8 * M * (2 * d.a.w + i)), zi));
@@ -597,7 +754,9 @@ __global__ __launch_bounds__(VT) void k_vfy_transcript(const uint8_t *__restrict
             const uint64_t v = fp_to_u64(d.pub[i]);
             for (int k = 0; k < 8; k++) sh.msg[o++] = (uint8_t)(v >> (8 * k));
         }
-        if (hash == 1) {
+        if (d.a.npub == 0) { // a statement too long for sh.msg (SchnorrAir): the host hashed the seed message
+            for (int i = 0; i < 8; i++) sh.seed[i] = d.seed[i];
+        } else if (hash == 1) {
             uint64_t h[4];
             nsha3(sh.msg, o, h);
             for (int i = 0; i < 4; i++) { sh.seed[2 * i] = (uint32_t)h[i]; sh.seed[2 * i + 1] = (uint32_t)(h[i] >> 32); }
@@ -713,6 +872,7 @@ __global__ __launch_bounds__(VT) void k_vfy_transcript(const uint8_t *__restrict
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 constexpr size_t VFY_CHUNK_BYTES = CSTARK_VERIFY_CHUNK_BYTES; // staging budget of one chunk (cstark.h)
+constexpr size_t SCH_STATEMENT_BYTES = 8 * 34 + 32;          // one signature of SchnorrAir's statement: message, R.x, s
 enum { VFY_EVENTS = CSTARK_VERIFY_NUM_STAGES };
 
 struct VerifyArena {
@@ -723,11 +883,12 @@ struct VerifyArena {
     int32_t *h_verdicts = nullptr;
     size_t verdict_cap = 0;
     // periodic coefficients per (AIR, header word): TransactionAir [depth slot][48][1024], depth = 2^(slot+1) - 1 | MerkleAir
-    // [depth slot][33][512] | RescueAir [29][8]
+    // [depth slot][33][512] | RescueAir [29][8] | SchnorrAir [36][512]
     uint64_t *d_pcoef = nullptr;
-    bool pcoef_ready[13] = {};
-    struct Adj { uint32_t air, log_n; uint64_t adj[VMAX_GROUPS], badj; };
-    std::vector<Adj> adj;                  // degree adjustments per (AIR, log_n): the constraint-evaluation domain is n * ce
+    bool pcoef_ready[14] = {};
+    struct Adj { uint32_t air, log_n; uint64_t adj[VMAX_GROUPS], badj, zc[2]; }; // zc: SchnorrAir's two assertion divisors x^(n / 512) - zc
+    std::vector<Adj> adj;                  // degree adjustments per (AIR, log_n): the constraint-evaluation domain is n * ce (SchnorrAir:
+                                           // log_n == 9 is the one-signature shape, whose bit constraints have a lower degree)
     hipEvent_t ev[VFY_EVENTS] = {};
     float ms[CSTARK_VERIFY_NUM_STAGES] = {};
     uint64_t h2d_bytes = 0;              // bytes copied host -> device by the last verify call
@@ -750,13 +911,14 @@ namespace {
 struct Staged {
     uint32_t index;     // position in the caller's arrays
     const uint8_t *bytes;
+    const cstark_schnorr_statement *stm = nullptr; // SchnorrAir: the caller's statement (n_sig equals the header's)
     Layout L;
     VDesc d;
     uint32_t D;         // the AIR's largest constraint degree (AirInfo)
 };
 // the proofs of one (AIR, extension degree) of a chunk: their list, the frames sampled for them (K each) and the constraint values
 struct Group {
-    uint32_t start = 0, count = 0, K = 0, frames = 0;
+    uint32_t start = 0, count = 0, K = 0, frames = 0, tiles = 0; // tiles: SchnorrAir, those of the group's largest statement
     fp *cur, *nxt, *per, *val;
     uint32_t *bad;
 };
@@ -764,7 +926,12 @@ struct Group {
 // The AIRs the pipeline verifies, as data, built once per process.  D: the largest total degree of a constraint in the frame's entries
 // (trace registers and periodic values), the sum of cstark_air_constraint_degree's two answers.  groups: constraints of one degree
 // (base; cycles) share an adjustment exponent at every trace length, so the grouping is the AIR's own; rep[g] = a constraint of group g.
-struct AirInfo { bool ok = false; VAir a{}; uint32_t D = 0; VGroups groups{}; uint32_t rep[VMAX_GROUPS] = {}; host::AirShape shape; };
+// SchnorrAir: `shape` is the one-signature shape, whose grouping is the finer one (the bit constraints 19..36 are a group of their own;
+// from two signatures on they have the degree of constraints 0..5, and the two groups then carry the same exponent), shape_many the
+// shape from two signatures on; asserts lists its 61 assertions.
+struct AirInfo {
+    bool ok = false; VAir a{}; uint32_t D = 0; VGroups groups{}; uint32_t rep[VMAX_GROUPS] = {}; host::AirShape shape, shape_many; VAsserts asserts{};
+};
 const AirInfo &air_info(uint32_t air) {
     static const std::array<AirInfo, 5> table = [] {
         std::array<AirInfo, 5> t;
@@ -779,12 +946,24 @@ const AirInfo &air_info(uint32_t air) {
                 continue;
             }
             host::AirShape &s = I.shape;
-            if (id == CSTARK_AIR_SCHNORR || !host::air_shape((int)id, s)) continue; // SchnorrAir: no verifier
+            if (!host::air_shape((int)id, s, 1)) continue;
             I.ok = true;
-            I.a = {id, s.width, 1u << s.log_ce_blowup(), s.n_constraints, (uint32_t)s.a_reg.size(), id == CSTARK_AIR_RANGE ? 1u : 14u, s.n_periodic,
-                   s.cycle_len ? ilog2(s.cycle_len) : 0, s.a_reg[0]};
+            I.a = {id, s.width, 1u << s.log_ce_blowup(), s.n_constraints, (uint32_t)s.a_reg.size(),
+                   id == CSTARK_AIR_RANGE ? 1u : id == CSTARK_AIR_SCHNORR ? 0u : 14u, s.n_periodic, s.cycle_len ? ilog2(s.cycle_len) : 0, s.a_reg[0], 0};
+            if (id == CSTARK_AIR_SCHNORR) {
+                host::air_shape((int)id, I.shape_many, 2);
+                I.a.naux = SCH_AUX;
+                assert(s.a_reg.size() == VMAX_NA);
+                I.asserts.n = (uint8_t)s.a_reg.size();
+                for (size_t a = 0; a < s.a_reg.size(); a++) {
+                    assert(s.a_stride[a] == 512 && (s.a_first[a] == 0 || s.a_first[a] == 511) && (s.a_const[a] == 0 || s.a_const[a] == host::ONE));
+                    I.asserts.reg[a] = (uint8_t)s.a_reg[a];
+                    I.asserts.div[a] = s.a_first[a] ? 1 : 0;
+                    I.asserts.val[a] = s.a_seq[a] >= 0 ? (uint8_t)(2 + s.a_seq[a]) : s.a_const[a] ? 1 : 0;
+                }
+            }
             for (uint32_t i = 0; i < s.n_constraints; i++) {
-                I.D = std::max(I.D, s.base[i] + (s.cycle_len ? s.cycles[i] : 0));
+                I.D = std::max(I.D, s.base[i] + (s.cycle_len ? s.cycles[i] : 0)); // (SchnorrAir: 7 in either shape)
                 uint32_t g = 0;
                 while (g < I.groups.n && !(s.base[I.rep[g]] == s.base[i] && s.cycles[I.rep[g]] == s.cycles[i])) g++;
                 if (g == I.groups.n) { assert(g < VMAX_GROUPS); I.rep[I.groups.n++] = i; }
@@ -804,6 +983,7 @@ bool header_ok(const Layout &L) {
     case CSTARK_AIR_MERKLE_UPDATE: return L.log_n >= 9 && tx_depth_ok(L.word);
     case CSTARK_AIR_RANGE: return L.word == 0; // log_n in 6 .. 21: parse_layout
     case CSTARK_AIR_RESCUE_CHAIN: return L.word == 1u << (L.log_n - 3); // the chain length; log_n in 6 .. 21: parse_layout
+    case CSTARK_AIR_SCHNORR: return L.log_n >= 9 && L.word == 1u << (L.log_n - 9); // the number of signatures, 512 rows each
     }
     return false;
 }
@@ -814,17 +994,19 @@ const VerifyArena::Adj &adjustments(VerifyArena *a, const AirInfo &I, uint32_t l
         if (e.air == I.a.air && e.log_n == log_n) return e;
     using namespace host;
     const uint64_t n = 1ull << log_n;
-    VerifyArena::Adj e{I.a.air, log_n, {}, 0};
+    VerifyArena::Adj e{I.a.air, log_n, {}, 0, {}};
     if (I.a.air == CSTARK_AIR_STATE_TRANSITION) {
         for (int g = 0; g < 5; g++) e.adj[g] = tx_group_adjustment(g, n, n * I.a.ce);
         e.badj = tx_boundary_adjustment(n, n * I.a.ce);
     } else {
         AirGroups q;
-        const AirGroupsResult r = air_groups(I.shape, log_n, 0, q); // at most as many distinct exponents as degrees: air_info's bound
+        const AirShape &shape = I.a.air == CSTARK_AIR_SCHNORR && log_n > 9 ? I.shape_many : I.shape;
+        const AirGroupsResult r = air_groups(shape, log_n, 0, q); // at most as many distinct exponents as degrees: air_info's bound
         assert(r == AIR_GROUPS_OK);
         (void)r;
         for (uint32_t g = 0; g < I.groups.n; g++) e.adj[g] = q.tgrp_adj[q.t_grp[I.rep[g]]];
-        e.badj = q.agrp_badj[0]; // single-row assertions only: one adjustment
+        e.badj = q.agrp_badj[0]; // single-row assertions only: one adjustment (SchnorrAir: both divisors have n / 512 steps)
+        if (I.a.air == CSTARK_AIR_SCHNORR) { assert(q.n_agrp == 2 && q.agrp_badj[1] == e.badj); e.zc[0] = q.agrp_zc[0]; e.zc[1] = q.agrp_zc[1]; }
     }
     a->adj.push_back(e);
     return a->adj.back();
@@ -849,6 +1031,7 @@ void describe(const Layout &L, const AirInfo &I, const VerifyArena::Adj &adj, co
     // asserted values: the first na / 2 at row 0, the others at row n - 1
     if (L.air == CSTARK_AIR_STATE_TRANSITION) { K[K_PUB] = pub[0]; K[K_PUB + 1] = pub[1]; K[K_PUB + 2] = pub[7]; K[K_PUB + 3] = pub[8]; }
     else if (L.air == CSTARK_AIR_RANGE) { K[K_PUB] = 0; K[K_PUB + 1] = pub[0]; }
+    else if (L.air == CSTARK_AIR_SCHNORR) { K[K_PUB] = adj.zc[0]; K[K_PUB + 1] = adj.zc[1]; d.n_sig = L.word; }
     else for (int i = 0; i < 14; i++) K[K_PUB + i] = pub[i];
     unsigned lg = L.log_N;
     for (uint32_t l = 0; l < L.n_layers; l++) { K[K_WL + l] = root_of_unity(lg); lg -= L.log_f; }
@@ -881,13 +1064,15 @@ template <int M> Lagrange<M> lagrange_weights(uint32_t K) {
 
 // the cached coefficients of the proof's periodic columns (header_ok has passed); off = their word offset in the cache
 int ensure_pcoef(cstark_ctx *c, VerifyArena *a, const Layout &L, uint64_t &off) {
-    constexpr size_t TX_WORDS = 48 * 1024, MK_WORDS = 33 * 512, RS_WORDS = 29 * 8;
+    constexpr size_t TX_WORDS = 48 * 1024, MK_WORDS = 33 * 512, RS_WORDS = 29 * 8, SC_WORDS = 36 * 512;
     off = 0;
     if (L.air == CSTARK_AIR_RANGE) return CSTARK_OK;
-    const uint32_t dslot = L.air == CSTARK_AIR_RESCUE_CHAIN ? 0 : ilog2(L.word + 1) - 1;
-    const uint32_t slot = L.air == CSTARK_AIR_STATE_TRANSITION ? dslot : L.air == CSTARK_AIR_MERKLE_UPDATE ? 6 + dslot : 12;
-    off = L.air == CSTARK_AIR_STATE_TRANSITION ? dslot * TX_WORDS : L.air == CSTARK_AIR_MERKLE_UPDATE ? 6 * TX_WORDS + dslot * MK_WORDS : 6 * (TX_WORDS + MK_WORDS);
-    if (!a->d_pcoef) HIP_TRY(hipMalloc(&a->d_pcoef, (6 * (TX_WORDS + MK_WORDS) + RS_WORDS) * 8));
+    const bool by_depth = L.air == CSTARK_AIR_STATE_TRANSITION || L.air == CSTARK_AIR_MERKLE_UPDATE;
+    const uint32_t dslot = by_depth ? ilog2(L.word + 1) - 1 : 0;
+    const uint32_t slot = L.air == CSTARK_AIR_STATE_TRANSITION ? dslot : L.air == CSTARK_AIR_MERKLE_UPDATE ? 6 + dslot : L.air == CSTARK_AIR_RESCUE_CHAIN ? 12 : 13;
+    off = L.air == CSTARK_AIR_STATE_TRANSITION ? dslot * TX_WORDS : L.air == CSTARK_AIR_MERKLE_UPDATE ? 6 * TX_WORDS + dslot * MK_WORDS
+          : 6 * (TX_WORDS + MK_WORDS) + (L.air == CSTARK_AIR_SCHNORR ? RS_WORDS : 0);
+    if (!a->d_pcoef) HIP_TRY(hipMalloc(&a->d_pcoef, (6 * (TX_WORDS + MK_WORDS) + RS_WORDS + SC_WORDS) * 8));
     if (a->pcoef_ready[slot]) return CSTARK_OK;
     std::vector<uint64_t> cols;
     uint32_t ncols, log_cycle;
@@ -897,6 +1082,9 @@ int ensure_pcoef(cstark_ctx *c, VerifyArena *a, const Layout &L, uint64_t &off) 
     } else if (L.air == CSTARK_AIR_MERKLE_UPDATE) {
         if (!host::merkle_periodic_columns(L.word, cols)) return fail(CSTARK_ERR_INVALID_ARG, "unsupported Merkle depth");
         ncols = 33; log_cycle = 9;
+    } else if (L.air == CSTARK_AIR_SCHNORR) {
+        host::schnorr_mask_columns(cols);
+        ncols = 36; log_cycle = 9;
     } else {
         host::rescue_chain_periodic_columns(cols);
         ncols = 29; log_cycle = 3;
@@ -905,6 +1093,24 @@ int ensure_pcoef(cstark_ctx *c, VerifyArena *a, const Layout &L, uint64_t &off) 
     HIP_TRY(hipMemcpyAsync(a->d_pcoef + off, cols.data(), cols.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     a->pcoef_ready[slot] = true;
+    return CSTARK_OK;
+}
+
+// the two launches that leave the statements' 31 values at z in the device region (m = extension degree, tiles = those of the largest statement)
+int launch_schnorr_public(uint32_t m, uint32_t tiles, uint32_t G, const uint8_t *buf, const VDesc *desc, const uint32_t *gp, const uint64_t *tb, uint64_t *sp,
+                          hipStream_t s) {
+    const dim3 grid(tiles, G), block(64 * SCH_TILE);
+    if (m == 1) {
+        hipLaunchKernelGGL(k_vfy_schnorr_public<1>, grid, block, 0, s, buf, desc, gp, tb, sp);
+        hipLaunchKernelGGL(k_vfy_schnorr_public_sum<1>, dim3(G), dim3(64), 0, s, desc, gp, tb, sp);
+    } else if (m == 2) {
+        hipLaunchKernelGGL(k_vfy_schnorr_public<2>, grid, block, 0, s, buf, desc, gp, tb, sp);
+        hipLaunchKernelGGL(k_vfy_schnorr_public_sum<2>, dim3(G), dim3(64), 0, s, desc, gp, tb, sp);
+    } else {
+        hipLaunchKernelGGL(k_vfy_schnorr_public<3>, grid, block, 0, s, buf, desc, gp, tb, sp);
+        hipLaunchKernelGGL(k_vfy_schnorr_public_sum<3>, dim3(G), dim3(64), 0, s, desc, gp, tb, sp);
+    }
+    HIP_TRY(hipGetLastError());
     return CSTARK_OK;
 }
 
@@ -919,13 +1125,18 @@ template <class T> T *carve(uint8_t *base, size_t &off, size_t count) {
 int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *out, double host_ms) {
     const hipStream_t s = c->stream;
     const uint32_t P = (uint32_t)st.size();
-    // ---- staging block: proofs | descriptors | openings | group lists; the transcript blocks live on the device only
-    size_t off = 0, t_words = 0;
+    // ---- staging block: proofs (a SchnorrAir proof is followed by its statement) | descriptors | openings | group lists; the transcript
+    // blocks and the statements' values at z live on the device only
+    size_t off = 0, t_words = 0, sp_words = 0;
     std::vector<size_t> pofs(P), tofs(P);
     size_t n_open = 0, n_slots = 0;
     for (uint32_t i = 0; i < P; i++) {
         const Layout &L = st[i].L;
         off = (off + 15) & ~(size_t)15; pofs[i] = off; off += L.rem + 8 * (size_t)L.R * L.m;
+        if (st[i].stm) {
+            off = (off + 7) & ~(size_t)7; st[i].d.stmt = off; off += SCH_STATEMENT_BYTES * (size_t)L.word;
+            st[i].d.sp = sp_words; sp_words += (size_t)SCH_PUBLIC * L.m * (schnorr_tiles(L.word) + 1);
+        }
         tofs[i] = t_words; t_words += (toff(st[i].d.a, L.m, L.n_layers, L.nq).words + 1) & ~(size_t)1;
         uint32_t no = 2 * L.nq;
         for (uint32_t l = 0; l < L.n_layers; l++) no += L.npos[l];
@@ -958,6 +1169,7 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
         Group &g = grp[st[i].L.air * 3 + st[i].L.m - 1];
         g.count++;
         g.K = st[i].L.m == 1 ? 1 : st[i].D * (st[i].L.m - 1) + 4;
+        if (st[i].stm) g.tiles = std::max(g.tiles, schnorr_tiles(st[i].L.word));
     }
     for (uint32_t g = 0, o = 0; g < 15; g++) { grp[g].start = o; o += grp[g].count; grp[g].frames = grp[g].count * grp[g].K; grp[g].count = 0; }
     std::vector<VOpen> opens;
@@ -967,6 +1179,20 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
         const Layout &L = S.L;
         memcpy(H + pofs[i], S.bytes, L.rem + 8 * (size_t)L.R * L.m);
         VDesc &d = S.d;
+        if (S.stm) {
+            // the statement in the order of the channel seed: messages, R.x (canonical words there), the s halves; the seed message is
+            // up to 155 KB and SHA3 is sequential, so its digest is taken here, by the prover's own statement of it
+            const size_t ns = L.word;
+            uint8_t *sm = H + d.stmt;
+            memcpy(sm, S.stm->messages, 8 * 28 * ns); memcpy(sm + 8 * 28 * ns, S.stm->sig_rx, 8 * 6 * ns); memcpy(sm + 8 * 34 * ns, S.stm->sig_s, 32 * ns);
+            cstark_options o;
+            memcpy(&o.num_queries, L.opt, sizeof L.opt);
+            const std::vector<uint8_t> seed = transcript::channel_seed(L.width, L.log_n, o, L.log_b, ilog2(L.opt[6]), reinterpret_cast<const uint64_t *>(sm),
+                                                                       34 * ns, sm + 8 * 34 * ns, 32 * ns);
+            uint8_t dg[32];
+            digest(L.opt[3], seed.data(), seed.size(), dg);
+            memcpy(d.seed, dg, 32);
+        }
         d.base = pofs[i]; d.tb = tofs[i];
         d.ood = (uint32_t)L.ood; d.trows = (uint32_t)L.trows; d.tpaths = (uint32_t)L.tpaths; d.crows = (uint32_t)L.crows;
         d.cpaths = (uint32_t)L.cpaths; d.rem = (uint32_t)L.rem;
@@ -1005,12 +1231,13 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
 
     // ---- device scratch: transcript blocks | slots | verdicts | per group: frames cur, next, per, values | bad flags
     size_t need = 8 * t_words + 16;
+    need += 8 * sp_words + 16;
     need += 4 * n_slots + 16;
     need += 4 * (size_t)P + 16;
     for (uint32_t g = 0; g < 15; g++)
         if (grp[g].count) {
             const VAir &A = air_info(g / 3).a;
-            need += 8 * (size_t)grp[g].frames * (2 * A.w + A.nper + A.nc) + 4 * (size_t)grp[g].count + 5 * 16;
+            need += 8 * (size_t)grp[g].frames * (2 * A.w + A.nper + A.naux + A.nc) + 4 * (size_t)grp[g].count + 5 * 16;
         }
     if (need > a->scratch_bytes) {
         HIP_TRY(hipStreamSynchronize(s));
@@ -1028,6 +1255,7 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
     uint8_t *D = (uint8_t *)a->d_scratch;
     size_t so = 0;
     uint64_t *d_tb = carve<uint64_t>(D, so, t_words);
+    uint64_t *d_sp = carve<uint64_t>(D, so, sp_words);
     uint32_t *d_slots = carve<uint32_t>(D, so, n_slots);
     int32_t *d_verd = carve<int32_t>(D, so, P);
     for (uint32_t g = 0; g < 15; g++) {
@@ -1035,7 +1263,7 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
         const VAir &A = air_info(g / 3).a;
         grp[g].cur = carve<fp>(D, so, (size_t)grp[g].frames * A.w);
         grp[g].nxt = carve<fp>(D, so, (size_t)grp[g].frames * A.w);
-        grp[g].per = carve<fp>(D, so, (size_t)grp[g].frames * A.nper);
+        grp[g].per = carve<fp>(D, so, (size_t)grp[g].frames * (A.nper + A.naux));
         grp[g].val = carve<fp>(D, so, (size_t)grp[g].frames * A.nc);
         grp[g].bad = carve<uint32_t>(D, so, grp[g].count);
     }
@@ -1060,20 +1288,22 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
         if (!G) continue;
         const uint32_t F = Gr.frames, K = Gr.K;
         const uint32_t *gp = d_grp + Gr.start;
+        if (air == CSTARK_AIR_SCHNORR) RC_TRY(launch_schnorr_public(mi + 1, Gr.tiles, G, dbuf, d_desc, gp, d_tb, d_sp, s));
         if (mi == 0) {
-            hipLaunchKernelGGL(k_vfy_ood_frames<1>, dim3(G), dim3(128), 0, s, dbuf, d_desc, gp, d_tb, a->d_pcoef, K, F, Gr.cur, Gr.nxt, Gr.per, Gr.bad);
+            hipLaunchKernelGGL(k_vfy_ood_frames<1>, dim3(G), dim3(128), 0, s, dbuf, d_desc, gp, d_tb, a->d_pcoef, d_sp, K, F, Gr.cur, Gr.nxt, Gr.per, Gr.bad);
         } else if (mi == 1) {
-            hipLaunchKernelGGL(k_vfy_ood_frames<2>, dim3(G), dim3(128), 0, s, dbuf, d_desc, gp, d_tb, a->d_pcoef, K, F, Gr.cur, Gr.nxt, Gr.per, Gr.bad);
+            hipLaunchKernelGGL(k_vfy_ood_frames<2>, dim3(G), dim3(128), 0, s, dbuf, d_desc, gp, d_tb, a->d_pcoef, d_sp, K, F, Gr.cur, Gr.nxt, Gr.per, Gr.bad);
         } else {
-            hipLaunchKernelGGL(k_vfy_ood_frames<3>, dim3(G), dim3(128), 0, s, dbuf, d_desc, gp, d_tb, a->d_pcoef, K, F, Gr.cur, Gr.nxt, Gr.per, Gr.bad);
+            hipLaunchKernelGGL(k_vfy_ood_frames<3>, dim3(G), dim3(128), 0, s, dbuf, d_desc, gp, d_tb, a->d_pcoef, d_sp, K, F, Gr.cur, Gr.nxt, Gr.per, Gr.bad);
         }
         HIP_TRY(hipGetLastError());
         HIP_TRY(launch_eval_frames_air((int)air, Gr.cur, Gr.nxt, Gr.per, Gr.val, F, s));
         const dim3 cg((G + 63) / 64);
         const VGroups &vg = air_info(air).groups;
-        if (mi == 0) hipLaunchKernelGGL(k_vfy_ood_check<1>, cg, dim3(64), 0, s, dbuf, d_desc, gp, G, K, F, Gr.val, Gr.bad, lagrange_weights<1>(K), vg, d_tb, d_slots);
-        else if (mi == 1) hipLaunchKernelGGL(k_vfy_ood_check<2>, cg, dim3(64), 0, s, dbuf, d_desc, gp, G, K, F, Gr.val, Gr.bad, lagrange_weights<2>(K), vg, d_tb, d_slots);
-        else hipLaunchKernelGGL(k_vfy_ood_check<3>, cg, dim3(64), 0, s, dbuf, d_desc, gp, G, K, F, Gr.val, Gr.bad, lagrange_weights<3>(K), vg, d_tb, d_slots);
+        const VAsserts &va = air_info(air).asserts;
+        if (mi == 0) hipLaunchKernelGGL(k_vfy_ood_check<1>, cg, dim3(64), 0, s, dbuf, d_desc, gp, G, K, F, Gr.val, Gr.bad, lagrange_weights<1>(K), vg, va, d_sp, d_tb, d_slots);
+        else if (mi == 1) hipLaunchKernelGGL(k_vfy_ood_check<2>, cg, dim3(64), 0, s, dbuf, d_desc, gp, G, K, F, Gr.val, Gr.bad, lagrange_weights<2>(K), vg, va, d_sp, d_tb, d_slots);
+        else hipLaunchKernelGGL(k_vfy_ood_check<3>, cg, dim3(64), 0, s, dbuf, d_desc, gp, G, K, F, Gr.val, Gr.bad, lagrange_weights<3>(K), vg, va, d_sp, d_tb, d_slots);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(a->ev[3], s));
@@ -1127,14 +1357,26 @@ int cstark_proof_inspect(const uint8_t *proof, size_t len, cstark_proof_info *in
     return CSTARK_OK;
 }
 
-// Both verify calls.  airs: the AIR the caller states for each proof (null: all TransactionAir); the 14 public words of proof i are
-// pub_lo[i * stride .. +7) | pub_hi[i * stride .. +7).
+// All verify calls.  airs: the AIR the caller states for each proof (null: all TransactionAir); the 14 public words of proof i are
+// pub_lo[i * stride .. +7) | pub_hi[i * stride .. +7).  stm (cstark_schnorr_verify; then airs and the public words are null): every proof is
+// stated to be SchnorrAir's, with statement stm[i].
 static int verify_batch(const char *who, cstark_ctx *c, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens, const int32_t *airs,
-                        const uint64_t *pub_lo, const uint64_t *pub_hi, size_t stride, const cstark_options *expected, int32_t *verdicts) {
+                        const uint64_t *pub_lo, const uint64_t *pub_hi, size_t stride, const cstark_schnorr_statement *stm,
+                        const cstark_options *expected, int32_t *verdicts) {
     if (!c) return fail(CSTARK_ERR_INVALID_ARG, "%s: null context", who);
     if (count == 0) return CSTARK_OK;
-    if (!proofs || !proof_lens || !pub_lo || !pub_hi || !verdicts) return fail(CSTARK_ERR_INVALID_ARG, "%s: null argument", who);
-    for (uint32_t i = 0; i < count; i++) {
+    if (!proofs || !proof_lens || (!stm && (!pub_lo || !pub_hi)) || !verdicts) return fail(CSTARK_ERR_INVALID_ARG, "%s: null argument", who);
+    for (uint32_t i = 0; stm && i < count; i++) {
+        const cstark_schnorr_statement &S = stm[i];
+        if (!S.messages || !S.sig_rx || !S.sig_s) return fail(CSTARK_ERR_INVALID_ARG, "%s: null statement array", who);
+        if (S.n_sig == 0) return fail(CSTARK_ERR_INVALID_ARG, "%s: a statement without signatures", who);
+        for (size_t k = 0; k < 28 * (size_t)S.n_sig; k++)
+            if (S.messages[k] >= host::P) return fail(CSTARK_ERR_INVALID_ARG, "%s: a message word is not a field element", who);
+        for (size_t k = 0; k < 6 * (size_t)S.n_sig; k++)
+            if (S.sig_rx[k] >= host::P) return fail(CSTARK_ERR_INVALID_ARG, "%s: an R.x word is not a field element", who);
+        if (!proofs[i] && proof_lens[i]) return fail(CSTARK_ERR_INVALID_ARG, "%s: null proof", who);
+    }
+    for (uint32_t i = 0; !stm && i < count; i++) {
         const int32_t air = airs ? airs[i] : (int32_t)CSTARK_AIR_STATE_TRANSITION;
         if (air < 0 || air > 4) return fail(CSTARK_ERR_INVALID_ARG, "%s: unknown AIR id", who);
         const uint32_t used = air == CSTARK_AIR_SCHNORR ? 0 : air == CSTARK_AIR_RANGE ? 1 : 14; // SchnorrAir: never verified, nothing read
@@ -1155,28 +1397,34 @@ static int verify_batch(const char *who, cstark_ctx *c, uint32_t count, const ui
     auto t0 = std::chrono::steady_clock::now();
     for (uint32_t i = 0; i < count; i++) {
         const uint8_t *b = proofs[i];
-        const uint32_t air = airs ? (uint32_t)airs[i] : (uint32_t)CSTARK_AIR_STATE_TRANSITION;
+        const uint32_t air = stm ? (uint32_t)CSTARK_AIR_SCHNORR : airs ? (uint32_t)airs[i] : (uint32_t)CSTARK_AIR_STATE_TRANSITION;
         Staged S;
         S.index = i;
         S.bytes = b;
         int v = b ? parse_layout(b, proof_lens[i], S.L) : CSTARK_PROOF_MALFORMED;
-        // a proof of another AIR than the caller states, or of SchnorrAir: no kernel reads it, so its elements are scanned here (a word
-        // >= p is MALFORMED before UNSUPPORTED)
+        // a proof of another AIR than the caller states, or of SchnorrAir through a call that carries no statement for it: no kernel reads
+        // it, so its elements are scanned here (a word >= p is MALFORMED before UNSUPPORTED)
         const AirInfo &I = air_info(air);
-        if (v == CSTARK_PROOF_OK && (S.L.air != air || !I.ok)) v = elements_canonical(b, S.L) ? CSTARK_PROOF_UNSUPPORTED : CSTARK_PROOF_MALFORMED;
+        if (v == CSTARK_PROOF_OK && (S.L.air != air || !I.ok || (air == CSTARK_AIR_SCHNORR && !stm)))
+            v = elements_canonical(b, S.L) ? CSTARK_PROOF_UNSUPPORTED : CSTARK_PROOF_MALFORMED;
         if (v == CSTARK_PROOF_OK && !header_ok(S.L)) v = CSTARK_PROOF_MALFORMED;
         if (v == CSTARK_PROOF_OK && expected) {
             const uint32_t *e = &expected->num_queries;
             if (memcmp(e, S.L.opt, sizeof S.L.opt) != 0) v = elements_canonical(b, S.L) ? CSTARK_PROOF_OPTIONS_MISMATCH : CSTARK_PROOF_MALFORMED;
         }
+        // a statement of another number of signatures than the header's: its seed and its values at z are not the proof's, decided
+        // here so that nothing on the device is sized by the difference (the restated verifier: "proof is for a different number of signatures")
+        if (v == CSTARK_PROOF_OK && stm && stm[i].n_sig != S.L.word) v = elements_canonical(b, S.L) ? CSTARK_PROOF_OOD : CSTARK_PROOF_MALFORMED;
         if (v != CSTARK_PROOF_OK) { verdicts[i] = v; continue; }
+        if (stm) S.stm = &stm[i];
         memset(&S.d, 0, sizeof S.d);
         S.D = I.D;
         RC_TRY(ensure_pcoef(c, a, S.L, S.d.pcoef));
-        uint64_t pub[14];
-        for (int k = 0; k < 7; k++) { pub[k] = pub_lo[i * stride + k]; pub[7 + k] = pub_hi[i * stride + k]; }
+        uint64_t pub[14] = {};
+        for (int k = 0; !stm && k < 7; k++) { pub[k] = pub_lo[i * stride + k]; pub[7 + k] = pub_hi[i * stride + k]; }
         describe(S.L, I, adjustments(a, I, S.L.log_n), pub, S.d);
-        const size_t bytes = proof_lens[i] + sizeof(VDesc) + sizeof(VOpen) * (2 + S.L.nq * (size_t)(2 + S.L.n_layers)) + 256;
+        const size_t bytes = proof_lens[i] + (stm ? SCH_STATEMENT_BYTES * (size_t)S.L.word : 0) + sizeof(VDesc) +
+                             sizeof(VOpen) * (2 + S.L.nq * (size_t)(2 + S.L.n_layers)) + 256;
         if (!st.empty() && chunk_bytes + bytes > VFY_CHUNK_BYTES) {
             host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             RC_TRY(run_chunk(c, a, st, verdicts, host_ms));
@@ -1195,13 +1443,62 @@ static int verify_batch(const char *who, cstark_ctx *c, uint32_t count, const ui
 
 int cstark_tx_verify(cstark_ctx *c, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens, const uint64_t *initial_roots,
                      const uint64_t *final_roots, const cstark_options *expected, int32_t *verdicts) {
-    return verify_batch("cstark_tx_verify", c, count, proofs, proof_lens, nullptr, initial_roots, final_roots, 7, expected, verdicts);
+    return verify_batch("cstark_tx_verify", c, count, proofs, proof_lens, nullptr, initial_roots, final_roots, 7, nullptr, expected, verdicts);
 }
 
 int cstark_air_verify(cstark_ctx *c, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens, const int32_t *airs,
                       const uint64_t *public_inputs, const cstark_options *expected, int32_t *verdicts) {
     if (c && count && (!airs || !public_inputs)) return fail(CSTARK_ERR_INVALID_ARG, "cstark_air_verify: null argument");
-    return verify_batch("cstark_air_verify", c, count, proofs, proof_lens, airs, public_inputs, public_inputs ? public_inputs + 7 : nullptr, 14, expected, verdicts);
+    return verify_batch("cstark_air_verify", c, count, proofs, proof_lens, airs, public_inputs, public_inputs ? public_inputs + 7 : nullptr, 14, nullptr, expected, verdicts);
+}
+
+int cstark_schnorr_verify(cstark_ctx *c, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens, const cstark_schnorr_statement *statements,
+                          const cstark_options *expected, int32_t *verdicts) {
+    if (c && count && !statements) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_verify: null argument");
+    return verify_batch("cstark_schnorr_verify", c, count, proofs, proof_lens, nullptr, nullptr, nullptr, 0, statements, expected, verdicts);
+}
+
+// k_vfy_schnorr_public + k_vfy_schnorr_public_sum for one statement and the caller's z, through a descriptor that holds what the two read
+int cstark_schnorr_public_at(cstark_ctx *c, uint32_t n_sig, const uint64_t *messages, const uint64_t *sig_rx, const uint64_t *z, uint32_t m, uint64_t *out) {
+    using namespace host;
+    if (!c || !messages || !sig_rx || !z || !out) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_public_at: null argument");
+    if (m < 1 || m > 3) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_public_at: m must be 1, 2 or 3");
+    if (n_sig == 0 || (n_sig & (n_sig - 1)) || n_sig > (1u << 12)) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_public_at: n_sig must be a power of two, at most 4096");
+    for (size_t k = 0; k < 28 * (size_t)n_sig; k++) if (messages[k] >= P) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_public_at: a message word is not a field element");
+    for (size_t k = 0; k < 6 * (size_t)n_sig; k++) if (sig_rx[k] >= P) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_public_at: an R.x word is not a field element");
+    for (uint32_t q = 0; q < m; q++) if (z[q] >= P) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_public_at: z is not a field element");
+    const uint32_t log_n = 9 + ilog2(n_sig);
+    EX zn = ex_load(z, m);
+    for (uint32_t s = 0; s < log_n; s++) zn = ex_mul(zn, zn, m);
+    if (zn.c[0] == ONE && zn.c[1] == 0 && zn.c[2] == 0) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_public_at: z lies on the trace domain");
+    HIP_TRY(hipSetDevice(c->device));
+    // one block: descriptor | group list | statement | z | partials and values
+    const uint32_t tiles = schnorr_tiles(n_sig);
+    const size_t o_gp = sizeof(VDesc), o_stmt = (o_gp + 4 + 15) & ~(size_t)15, o_z = o_stmt + 8 * 34 * (size_t)n_sig, o_sp = o_z + 8 * m,
+                 total = o_sp + 8 * (size_t)SCH_PUBLIC * m * (tiles + 1);
+    std::vector<uint8_t> h(o_sp, 0);
+    VDesc *d = reinterpret_cast<VDesc *>(h.data());
+    d->a = air_info(CSTARK_AIR_SCHNORR).a;
+    d->k[K_WN] = root_of_unity(log_n);
+    d->stmt = o_stmt; d->sp = 0; d->tb = 0; d->n_sig = n_sig; d->log_n = log_n; d->m = m;
+    memcpy(h.data() + o_stmt, messages, 8 * 28 * (size_t)n_sig);
+    memcpy(h.data() + o_stmt + 8 * 28 * (size_t)n_sig, sig_rx, 8 * 6 * (size_t)n_sig);
+    memcpy(h.data() + o_z, z, 8 * m);
+    uint8_t *dev = nullptr;
+    HIP_TRY(hipMalloc(&dev, total));
+    int rc = CSTARK_OK;
+    hipError_t e = hipMemcpyAsync(dev, h.data(), o_sp, hipMemcpyHostToDevice, c->stream);
+    uint64_t *d_sp = reinterpret_cast<uint64_t *>(dev + o_sp);
+    if (e == hipSuccess)
+        rc = launch_schnorr_public(m, tiles, 1, dev, reinterpret_cast<const VDesc *>(dev), reinterpret_cast<const uint32_t *>(dev + o_gp),
+                                   reinterpret_cast<const uint64_t *>(dev + o_z), d_sp, c->stream);
+    if (e == hipSuccess && rc == CSTARK_OK)
+        e = hipMemcpyAsync(out, d_sp + (size_t)SCH_PUBLIC * m * tiles, 8 * (size_t)SCH_PUBLIC * m, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(dev);
+    if (rc != CSTARK_OK) return rc;
+    HIP_TRY(e);
+    return CSTARK_OK;
 }
 
 int cstark_verify_stage_ms(cstark_ctx *c, float *ms) {

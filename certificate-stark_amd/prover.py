@@ -280,6 +280,14 @@ class SchnorrExample(_ResidentWitness):
         self._ensure_resident(lambda: self.backend.upload_schnorr_witness(self.messages, self.sig_rx, self.sig_s))
         return self.backend.air_prove(Backend.AIR_SCHNORR, self.options)
 
+    def verify(self, proof):
+        """src/schnorr/mod.rs:175-186 through cstark_schnorr_verify: the statement is every message and signature of this example; the
+        proof's own options are accepted.  Raises VerifierError on rejection"""
+        from .verify import VerifierError
+        v = int(self.backend.schnorr_verify([proof], [self])[0])
+        if v != 0:
+            raise VerifierError(v)
+
 
 class RescueExample:
     """RescueExample of benches/rescue.rs:25-102: a chain of `chain_length` Rescue hashes from the bench's seed 42..48 (held in memory

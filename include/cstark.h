@@ -438,7 +438,7 @@ int cstark_schnorr_witness_generate(uint32_t n_sig, uint64_t seed, uint64_t *mes
 typedef enum cstark_verdict {
     CSTARK_PROOF_OK = 0,                 /* verify: accepted;  inspect: well-formed */
     CSTARK_PROOF_MALFORMED = 1,          /* layout, counts, lengths, non-canonical field element, trailing bytes */
-    CSTARK_PROOF_UNSUPPORTED = 2,        /* well-formed proof of another AIR than the call verifies or the caller states; SchnorrAir always */
+    CSTARK_PROOF_UNSUPPORTED = 2,        /* well-formed proof of another AIR than the call verifies or the caller states */
     CSTARK_PROOF_OPTIONS_MISMATCH = 3,   /* differs from `expected` */
     CSTARK_PROOF_OOD = 4,                /* out-of-domain constraint evaluations inconsistent (also: wrong public inputs) */
     CSTARK_PROOF_REMAINDER_COMMITMENT = 5,
@@ -475,17 +475,39 @@ int cstark_tx_verify(cstark_ctx *ctx, uint32_t count, const uint8_t *const *proo
  * hashes and extensions (one pipeline, cstark_tx_verify is its all-TransactionAir call).  airs[i]: the AIR the caller expects proof i to be
  * (CSTARK_AIR_*).  public_inputs: [count][14] words, memory form -- TransactionAir / MerkleAir: initial root | final root; RescueAir: seed
  * | result; RangeProofAir: word 0 = number, words 1..13 ignored.  A well-formed proof whose header states another AIR than airs[i] is
- * UNSUPPORTED, and so is every proof with airs[i] == CSTARK_AIR_SCHNORR (its statement is O(n) public data: no verifier yet); header
+ * UNSUPPORTED, and so is every proof with airs[i] == CSTARK_AIR_SCHNORR (its statement is O(n) public data, which the 14 words cannot
+ * carry: cstark_schnorr_verify); header
  * values no prover of this library writes (a Merkle depth or a trace length the AIR does not have) are MALFORMED.  Negative status only
  * for null pointers, an airs[i] that is no CSTARK_AIR_* id, a used public word >= p, or a HIP failure. */
 int cstark_air_verify(cstark_ctx *ctx, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens, const int32_t *airs,
                       const uint64_t *public_inputs, const cstark_options *expected, int32_t *verdicts);
-/* Stage times of the last cstark_tx_verify / cstark_air_verify on this context, like cstark_prove_stage_ms (milliseconds, summed over its chunks):
+/* SchnorrExample::verify (src/schnorr/mod.rs:175-186) for `count` SchnorrAir proofs in one call: the pipeline, the verdict order and the
+ * chunking of cstark_air_verify; a batch may mix numbers of signatures, hashes, extensions and options, and a verdict does not depend on the
+ * rest of the batch.  statements[i]: everything the proof is about -- the messages (public key || 16 elements), R.x and s of every
+ * signature; its bytes are staged with the proof (and count towards a chunk), its channel seed is hashed on the host, and the values the
+ * out-of-domain check needs of it (19 public-input columns, 12 sequence polynomials, at z) are formed on the device in one pass
+ * (cstark_schnorr_public_at is that stage alone).  A well-formed proof of another AIR is UNSUPPORTED.  A statement whose n_sig differs from
+ * the proof's header word -- any n_sig that is not a power of two among them -- gives CSTARK_PROOF_OOD, after MALFORMED, UNSUPPORTED and
+ * OPTIONS_MISMATCH.  Negative status only for null pointers with count > 0, n_sig == 0, a messages / sig_rx word >= p, or a HIP failure. */
+typedef struct cstark_schnorr_statement {
+    uint32_t n_sig;
+    const uint64_t *messages;   /* [n_sig][28], memory form */
+    const uint64_t *sig_rx;     /* [n_sig][6],  memory form */
+    const uint8_t  *sig_s;      /* [n_sig][32] */
+} cstark_schnorr_statement;
+int cstark_schnorr_verify(cstark_ctx *ctx, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens,
+                          const cstark_schnorr_statement *statements, const cstark_options *expected, int32_t *verdicts);
+/* Stage entry point, like the other stages: the 19 public-input columns (12 public-key words, 7 hash-input words) and the 12
+ * sequence-value polynomials (R.x at step 0, at step 511) of a statement at one point z of the degree-m extension, m in {1, 2, 3};
+ * out [31][m], memory form, host memory.  CSTARK_ERR_INVALID_ARG if z^n = 1 (n = 512 n_sig) or n_sig is not a power of two (at most 4096). */
+int cstark_schnorr_public_at(cstark_ctx *ctx, uint32_t n_sig, const uint64_t *messages, const uint64_t *sig_rx, const uint64_t *z,
+                             uint32_t m, uint64_t *out);
+/* Stage times of the last cstark_tx_verify / cstark_air_verify / cstark_schnorr_verify on this context, like cstark_prove_stage_ms (milliseconds, summed over its chunks):
  * host parse + staging, host-to-device copy, transcript replay (on the device), out-of-domain check, Merkle openings, DEEP + FRI,
  * remainder + reduction + device-to-host copy.  cstark_verify_h2d_bytes: the bytes the same call copied host -> device (proof bytes,
  * descriptors, opening records). */
 #define CSTARK_VERIFY_NUM_STAGES 7
-/* Batches of any size: both verify calls stage proofs (their bytes, descriptors and opening records) for the device in chunks of at
+/* Batches of any size: the verify calls stage proofs (their bytes, descriptors and opening records) for the device in chunks of at
  * most this many bytes and verifies one chunk after the other, so a large count never sizes its buffers beyond one chunk (a single
  * larger proof is a chunk of its own).  Verdicts do not depend on where the chunks divide. */
 #define CSTARK_VERIFY_CHUNK_BYTES 67108864 /* 64 MiB */

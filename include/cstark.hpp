@@ -407,6 +407,16 @@ class SchnorrExample {
         check(cstark_schnorr_witness_upload(ctx_.raw(), n, messages.data(), sig_rx.data(), sig_s.data()));
         return detail::air_prove(ctx_, CSTARK_AIR_SCHNORR, options_, 0, (size_t)n * 512);
     }
+    // src/schnorr/mod.rs:175-186 through cstark_schnorr_verify: the statement is every message and signature held here; throws
+    // VerifierError on rejection
+    void verify(const std::vector<uint8_t> &proof) const {
+        const cstark_schnorr_statement st{(uint32_t)(messages.size() / 28), messages.data(), sig_rx.data(), sig_s.data()};
+        const uint8_t *ptr = proof.data();
+        const size_t len = proof.size();
+        int32_t v = -1;
+        check(cstark_schnorr_verify(ctx_.raw(), 1, &ptr, &len, &st, nullptr, &v));
+        if (v != CSTARK_PROOF_OK) throw VerifierError(v);
+    }
     ProofOptions options_;
     std::vector<BaseElement> messages, sig_rx;
     std::vector<uint8_t> sig_s;

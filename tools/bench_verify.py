@@ -2,10 +2,11 @@
 remainder 256): single-proof latency, proofs/s at batch sizes 16, 64 and 256, bytes copied per call (proof bytes and the whole copy)
 and the achieved host-to-device rate of the whole copy, and cstark_verify_stage_ms.  Prints one JSON line.  Run on a GPU box.
 
-    python tools/bench_verify.py [--counts 1,64] [--min-seconds 1.0] [--air transaction|merkle|range]
+    python tools/bench_verify.py [--counts 1,64] [--min-seconds 1.0] [--air transaction|merkle|range|schnorr] [--signatures 1]
 
 --air merkle: a MerkleAir proof of 512 transfers (2^18 rows, depth 15, 96 queries); --air range: the reference's 64-row range proof
-(42 queries); both through cstark_air_verify.
+(42 queries); both through cstark_air_verify.  --air schnorr: a SchnorrAir proof of --signatures signatures (1: 2^9 rows, counts 1, 64, 1024;
+512: 2^18 rows, count 1; 42 queries) through cstark_schnorr_verify; its statement (304 bytes per signature) is part of the copy.
 
 The verify calls are synchronous (verdicts are on the host when they return), so wall time around the call is the latency; every
 configuration is warmed up first and timed over at least --min-seconds of calls."""
@@ -19,7 +20,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
 from certificate_stark_amd.backend import Backend  # noqa: E402
-from certificate_stark_amd.prover import MerkleExample, ProofOptions, RangeProofExample, TransactionExample, TransactionMetadata  # noqa: E402
+from certificate_stark_amd.prover import (MerkleExample, ProofOptions, RangeProofExample, SchnorrExample, TransactionExample,  # noqa: E402
+                                           TransactionMetadata)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PCIE_GEN5_X16_GBPS = 63.0  # per direction, MI355X spec
@@ -29,10 +31,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--counts", default="1,16,64,256")
     ap.add_argument("--min-seconds", type=float, default=1.0)
-    ap.add_argument("--air", default="transaction", choices=("transaction", "merkle", "range"))
+    ap.add_argument("--air", default="transaction", choices=("transaction", "merkle", "range", "schnorr"))
+    ap.add_argument("--signatures", type=int, default=1)
     args = ap.parse_args()
     b = Backend()
-    meta = TransactionMetadata.load(os.path.join(ROOT, "tests", "golden", "witness_1024_d15.npz"))
+    meta = None if args.air in ("range", "schnorr") else TransactionMetadata.load(os.path.join(ROOT, "tests", "golden", "witness_1024_d15.npz"))
     if args.air == "transaction":
         opt = ProofOptions(96, 8, 0, ProofOptions.BLAKE3_256, ProofOptions.EXT_NONE, 4, 256)
         tx = TransactionExample(opt, meta, b)
@@ -51,6 +54,14 @@ def main():
 
         def verify(proofs):
             return b.air_verify(proofs, Backend.AIR_MERKLE, pub, opt)
+    elif args.air == "schnorr":
+        opt = ProofOptions(42, 8, 0, ProofOptions.BLAKE3_256, ProofOptions.EXT_NONE, 4, 256)
+        ex = SchnorrExample.build_random(opt, args.signatures, backend=b)
+        proof = ex.prove()
+        config = "schnorr %d signatures (%d rows), options (42, 8, 0, Blake3, None, 4, 256)" % (args.signatures, 512 * args.signatures)
+
+        def verify(proofs):
+            return b.schnorr_verify(proofs, [ex] * len(proofs), opt)
     else:
         opt = ProofOptions(42, 8, 0, ProofOptions.BLAKE3_256, ProofOptions.EXT_NONE, 4, 256)
         p = (1 << 62) + (1 << 56) + (1 << 55) + 1
