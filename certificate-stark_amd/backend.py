@@ -110,6 +110,65 @@ class Backend:
         check(self.lib.cstark_tx_build_trace(self.ctx, self._ptr(out)))
         return out
 
+    # ---- account ledger (cstark_ledger_*): the witness from accounts and transfers ----
+    def ledger_create(self, depth):
+        led = C.c_void_p()
+        check(self.lib.cstark_ledger_create(self.ctx, C.c_uint32(depth), C.byref(led)))
+        return led
+
+    def ledger_destroy(self, led):
+        self.lib.cstark_ledger_destroy(led)
+
+    def ledger_set_accounts(self, led, indices, values):
+        idx = _np_u64(indices).reshape(-1)
+        val = _np_u64(values).reshape(-1, 14)
+        if val.shape[0] != idx.size:
+            raise ValueError("one 14-element value per index")
+        check(self.lib.cstark_ledger_set_accounts(self.ctx, led, C.c_uint32(idx.size), self._hptr(idx), self._hptr(val)))
+
+    def ledger_get_accounts(self, led, indices):
+        """-> (values uint64 [count][14], present bool [count])"""
+        idx = _np_u64(indices).reshape(-1)
+        val, present = np.zeros((idx.size, 14), np.uint64), np.zeros(idx.size, np.uint8)
+        check(self.lib.cstark_ledger_get_accounts(self.ctx, led, C.c_uint32(idx.size), self._hptr(idx), self._hptr(val), self._hptr(present, u8p)))
+        return val, present.astype(bool)
+
+    def ledger_root(self, led):
+        root = np.zeros(7, np.uint64)
+        check(self.lib.cstark_ledger_root(self.ctx, led, self._hptr(root)))
+        return root
+
+    def ledger_apply(self, led, depth, s_indices, r_indices, deltas, sig_rx, sig_s, want_witness=True):
+        """cstark_ledger_apply: -> (refused_at, reason, arrays).  Applied (refused_at == -1): the batch's witness is resident in this
+        backend (build_trace / prove / air_prove follow without an upload) and arrays is the dict of its eleven fields (None with
+        want_witness=False).  Refused: nothing changed, arrays is None."""
+        s, r, dl = _np_u64(s_indices).reshape(-1), _np_u64(r_indices).reshape(-1), _np_u64(deltas).reshape(-1)
+        n = s.size
+        rx = _np_u64(sig_rx).reshape(-1, 6)
+        ss = np.ascontiguousarray(sig_s, np.uint8).reshape(-1, 32)
+        if not (r.size == dl.size == rx.shape[0] == ss.shape[0] == n):
+            raise ValueError("the transfer arrays state different numbers of transfers")
+        arrays, out = None, None
+        if want_witness:
+            arrays = dict(initial_roots=np.zeros((n, 7), np.uint64), final_root=np.zeros(7, np.uint64),
+                          s_old_values=np.zeros((n, 14), np.uint64), r_old_values=np.zeros((n, 14), np.uint64),
+                          s_indices=np.zeros(n, np.uint64), r_indices=np.zeros(n, np.uint64),
+                          s_paths=np.zeros((n, depth + 1, 7), np.uint64), r_paths=np.zeros((n, depth + 1, 7), np.uint64),
+                          deltas=np.zeros(n, np.uint64), sig_rx=np.zeros((n, 6), np.uint64), sig_s=np.zeros((n, 32), np.uint8))
+            st = _lib.TxWitnessStruct()
+            st.n_tx, st.merkle_depth = n, depth
+            for f, a in arrays.items():
+                setattr(st, f, a.ctypes.data_as(u8p if f == "sig_s" else u64p))
+            out = C.byref(st)
+        at, reason = C.c_int32(-1), C.c_int32(0)
+        check(self.lib.cstark_ledger_apply(self.ctx, led, C.c_uint32(n), self._hptr(s), self._hptr(r), self._hptr(dl), self._hptr(rx), self._hptr(ss, u8p),
+                                           out, C.byref(at), C.byref(reason)))
+        if at.value >= 0:
+            return at.value, reason.value, None
+        self.resident = None   # an example that believed its own witness resident uploads again
+        self.n_tx, self.depth = n, depth
+        return -1, 0, arrays
+
     # ---- K2 / K3 ----
     def field_generator(self):
         self.lib.cstark_field_generator.restype = C.c_uint64

@@ -409,6 +409,37 @@ int ce_params(cstark_ctx *c, const uint64_t *d_lde, uint64_t *d_out, uint32_t me
 
 } // namespace
 
+// the resident witness allocation of n transfers at depth d (witness_layout.h: one allocation, 8-byte fields first), grown when needed
+int tx_witness_reserve(cstark_ctx *c, size_t n, size_t d, size_t *sz, size_t *off) {
+    cs::witness_segments(n, d, sz, off);
+    const size_t total = off[cs::WIT_NUM_SEGMENTS];
+    if (total > c->wit_bytes) {
+        if (c->wit_buf) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->wit_buf)); c->wit_buf = nullptr; c->wit_bytes = 0; }
+        HIP_TRY(hipMalloc(&c->wit_buf, total));
+        c->wit_bytes = total;
+    }
+    return CSTARK_OK;
+}
+// ... and the context's view of it, once its segments are written (or enqueued on the context's stream)
+void tx_witness_bind(cstark_ctx *c, size_t n, size_t d, const size_t *off) {
+    char *base = (char *)c->wit_buf;
+    cs::TxWitnessDev &dv = c->wit;
+    dv.n_tx = (uint32_t)n;
+    dv.depth = (uint32_t)d;
+    dv.initial_roots = (const uint64_t *)(base + off[cs::WIT_INITIAL_ROOTS]);
+    dv.s_old = (const uint64_t *)(base + off[cs::WIT_S_OLD]);
+    dv.r_old = (const uint64_t *)(base + off[cs::WIT_R_OLD]);
+    dv.s_idx = (const uint64_t *)(base + off[cs::WIT_S_IDX]);
+    dv.r_idx = (const uint64_t *)(base + off[cs::WIT_R_IDX]);
+    dv.s_paths = (const uint64_t *)(base + off[cs::WIT_S_PATHS]);
+    dv.r_paths = (const uint64_t *)(base + off[cs::WIT_R_PATHS]);
+    dv.deltas = (const uint64_t *)(base + off[cs::WIT_DELTAS]);
+    dv.sig_rx = (const uint64_t *)(base + off[cs::WIT_SIG_RX]);
+    dv.h_limbs = (uint64_t *)(base + off[cs::WIT_H_LIMBS]);
+    dv.sig_s = (const uint8_t *)(base + off[cs::WIT_SIG_S]);
+    dv.msg_tail = nullptr;
+}
+
 extern "C" {
 
 const char *cstark_last_error(void) { return g_err; }
@@ -538,35 +569,14 @@ int cstark_tx_witness_upload(cstark_ctx *c, const cstark_tx_witness *w) {
         !w->deltas || !w->sig_rx || !w->sig_s)
         return fail(CSTARK_ERR_INVALID_ARG, "witness array pointer is null");
     HIP_TRY(hipSetDevice(c->device));
-    // one allocation, 8-byte fields first
-    const size_t sz[] = {n * 7 * 8, n * 14 * 8, n * 14 * 8, n * 8, n * 8, n * (d + 1) * 7 * 8, n * (d + 1) * 7 * 8, n * 8, n * 6 * 8, n * 4 * 8, n * 32};
     const void *src[] = {w->initial_roots, w->s_old_values, w->r_old_values, w->s_indices, w->r_indices, w->s_paths, w->r_paths, w->deltas, w->sig_rx, nullptr, w->sig_s};
-    size_t off[12] = {0};
-    for (int i = 0; i < 11; i++) off[i + 1] = off[i] + ((sz[i] + 255) & ~(size_t)255);
-    if (off[11] > c->wit_bytes) {
-        if (c->wit_buf) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->wit_buf)); c->wit_buf = nullptr; c->wit_bytes = 0; }
-        HIP_TRY(hipMalloc(&c->wit_buf, off[11]));
-        c->wit_bytes = off[11];
-    }
+    size_t sz[cs::WIT_NUM_SEGMENTS], off[cs::WIT_NUM_SEGMENTS + 1];
+    RC_TRY(tx_witness_reserve(c, n, d, sz, off));
     char *base = (char *)c->wit_buf;
-    for (int i = 0; i < 11; i++)
+    for (int i = 0; i < cs::WIT_NUM_SEGMENTS; i++)
         if (src[i]) HIP_TRY(hipMemcpyAsync(base + off[i], src[i], sz[i], hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream)); // the caller may free its host arrays on return
-    cs::TxWitnessDev &dv = c->wit;
-    dv.n_tx = (uint32_t)n;
-    dv.depth = (uint32_t)d;
-    dv.initial_roots = (const uint64_t *)(base + off[0]);
-    dv.s_old = (const uint64_t *)(base + off[1]);
-    dv.r_old = (const uint64_t *)(base + off[2]);
-    dv.s_idx = (const uint64_t *)(base + off[3]);
-    dv.r_idx = (const uint64_t *)(base + off[4]);
-    dv.s_paths = (const uint64_t *)(base + off[5]);
-    dv.r_paths = (const uint64_t *)(base + off[6]);
-    dv.deltas = (const uint64_t *)(base + off[7]);
-    dv.sig_rx = (const uint64_t *)(base + off[8]);
-    dv.h_limbs = (uint64_t *)(base + off[9]);
-    dv.sig_s = (const uint8_t *)(base + off[10]);
-    dv.msg_tail = nullptr;
+    tx_witness_bind(c, n, d, off);
     return CSTARK_OK;
 }
 

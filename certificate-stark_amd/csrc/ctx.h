@@ -9,6 +9,7 @@
 #include "../../include/cstark.h"
 #include "constraints.h"
 #include "trace_gen.h"
+#include "witness_layout.h"
 
 // The prover waits for a root, a frame or an upload a dozen times per proof with the GPU idle until the host answers: poll the stream
 // instead of blocking in hipStreamSynchronize (whose wake-up costs tens of microseconds; FRI stage 0.69 -> 0.58 ms).  The poll is
@@ -200,6 +201,10 @@ struct cstark_ctx {
     void *rb_dev = nullptr, *rb_host = nullptr; // cstark_range_prove_batch: one device block and one pinned host block, carved per call
     size_t rb_dev_bytes = 0, rb_host_bytes = 0;
 };
+// internal (capi.hip): the resident witness of n transfers at depth d, for cstark_tx_witness_upload and cstark_ledger_apply.  reserve: the
+// allocation (grown when needed; sz / off as witness_segments fills them); bind: the context's view, once the segments are written
+int tx_witness_reserve(cstark_ctx *c, size_t n, size_t d, size_t *sz, size_t *off);
+void tx_witness_bind(cstark_ctx *c, size_t n, size_t d, const size_t *off);
 // internal (capi.hip): the coin of one FRI layer on the device followed by the fold with the drawn point, m words at d_alpha (prove.hip)
 int fri_coin_fold_dev(cstark_ctx *c, uint32_t *d_seed, const uint8_t *d_root, uint64_t *d_alpha, uint32_t *d_root_out, const uint64_t *d_evals,
                       uint64_t *d_out, uint32_t log_n, uint32_t log_f, uint64_t domain_offset, uint32_t m);

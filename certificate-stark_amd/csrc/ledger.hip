@@ -1,0 +1,291 @@
+// The account ledger on gfx950: the Merkle work of the reference's transfer loop (TransactionMetadata::build_random,
+// /root/reference/src/lib.rs:341-422) as depth + 1 dependent launches of independent Rescue merges, planned on the host
+// (ledger_plan.h: balance walk, predecessor map, slot numbering) and run over one device pool of digests.
+//   k_ledger_merge    one list of merge jobs (left slot, right slot, output slot): 14 lanes per hash, four hashes per wave, the
+//                     lane-per-state-element permutation of the trace kernels (rescue_lane.cuh)
+//   k_ledger_gather   one emit list (pool slot -> word offset): paths, roots and old values into the resident witness; the touched
+//                     nodes' last versions into the stored nodes
+// One launch per level, ordered by the stream: every input of a launch was written by an earlier launch or by the upload, so no
+// workgroup ever waits for another one.
+#include <string.h>
+#include <new>
+#include "../../include/cstark.h"
+#include "ctx.h"
+#include "ledger_plan.h"
+#include "rescue_lane.cuh"
+
+namespace cs {
+namespace {
+
+// out = Rescue63::merge(left, right) for jobs [0, n_jobs): lanes 0..55 = (hash s, state element e), lanes 56..63 and the hashes of a
+// partial last group only take part in the barriers.  A slot outside the pool (the plan never emits one) makes its hash inactive.
+__global__ __launch_bounds__(64) void k_ledger_merge(fp *pool, const ledger::Job *__restrict__ jobs, uint32_t n_jobs, uint32_t pool_slots) {
+    __shared__ fp st[4][14];
+    const int lane = threadIdx.x;
+    const bool is_state = lane < 56;
+    const int s = is_state ? lane / 14 : 0, e = is_state ? lane % 14 : 0;
+    const uint32_t j = 4 * blockIdx.x + s;
+    bool active = is_state && j < n_jobs;
+    fp mrow[14];
+#pragma unroll
+    for (int k = 0; k < 14; k++) mrow[k] = c_mds[e * 14 + k];
+    uint32_t left = 0, right = 0, out = 0;
+    if (active) {
+        left = jobs[j].left; right = jobs[j].right; out = jobs[j].out;
+        active = left < pool_slots && right < pool_slots && out < pool_slots;
+    }
+    fp v = 0;
+    if (active) v = e < 7 ? pool[(size_t)7 * left + e] : pool[(size_t)7 * right + e - 7];
+    for (int cyc = 0; cyc < 7; cyc++) v = rescue_round_lane(v, st[s], mrow, e, cyc, active);
+    if (active && e < 7) pool[(size_t)7 * out + e] = v;
+}
+
+// dst[word .. word + 7) = pool slot, for emits [0, n): one thread per word
+__global__ __launch_bounds__(256) void k_ledger_gather(const fp *pool, const ledger::Emit *__restrict__ list, uint32_t n, uint32_t pool_slots,
+                                                       fp *dst, size_t dst_words) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const uint32_t m = (uint32_t)(i / 7), k = (uint32_t)(i % 7);
+    if (m >= n) return;
+    const uint32_t slot = list[m].slot;
+    const size_t word = (size_t)list[m].word + k;
+    if (slot < pool_slots && word < dst_words) dst[word] = pool[(size_t)7 * slot + k];
+}
+
+} // namespace
+} // namespace cs
+
+struct cstark_ledger {
+    cstark_ctx *ctx;
+    cs::ledger::Index index;
+    uint64_t *pool = nullptr;    // device: EMPTY_SLOTS | stored nodes (capacity) | scratch of the call in flight
+    uint32_t capacity = 0;       // stored-node slots reserved
+    uint64_t pool_slots = 0;
+    bool broken = false;         // a HIP call failed inside a ledger call: the pool's content is unknown
+    cstark_ledger(cstark_ctx *c, uint32_t depth) : ctx(c), index(depth) {}
+};
+
+namespace {
+using namespace cs::ledger;
+using cs::fail;
+
+// room for `new_nodes` more stored nodes and `scratch` slots behind them; *scratch_base = the first scratch slot
+int reserve_pool(cstark_ledger *L, uint64_t new_nodes, uint64_t scratch, uint32_t *scratch_base) {
+    cstark_ctx *c = L->ctx;
+    const uint64_t need_nodes = (uint64_t)L->index.n_stored + new_nodes;
+    uint64_t cap = L->capacity;
+    if (need_nodes > cap) {
+        cap = cap ? cap : 1024;
+        while (cap < need_nodes) cap *= 2;
+    }
+    const uint64_t slots = EMPTY_SLOTS + cap + scratch;
+    if (slots > MAX_POOL_SLOTS) return fail(CSTARK_ERR_UNSUPPORTED, "ledger: the batch needs more than 2^28 digest slots");
+    if (cap != L->capacity || slots > L->pool_slots) {
+        uint64_t *fresh = nullptr;
+        HIP_TRY(hipMalloc(&fresh, slots * 56));
+        if (L->pool) {
+            hipError_t e = hipMemcpyAsync(fresh, L->pool, ((size_t)EMPTY_SLOTS + L->index.n_stored) * 56, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) { (void)hipFree(fresh); HIP_TRY(e); }
+            HIP_TRY(hipFree(L->pool));
+        } else {
+            hipError_t e = hipMemsetAsync(fresh, 0, (size_t)EMPTY_SLOTS * 56, c->stream);
+            if (e != hipSuccess) { (void)hipFree(fresh); HIP_TRY(e); }
+        }
+        L->pool = fresh;
+        L->capacity = (uint32_t)cap;
+        L->pool_slots = slots;
+    }
+    *scratch_base = EMPTY_SLOTS + L->capacity;
+    return CSTARK_OK;
+}
+
+// upload block, merge launches, then the emit lists: `witness` into dst_witness (may be empty), `commit` back into the pool
+int run_plan(cstark_ledger *L, const Plan &p, uint64_t *dst_witness, size_t witness_words) {
+    cstark_ctx *c = L->ctx;
+    if (p.pool_slots > L->pool_slots) return fail(CSTARK_ERR_INVALID_ARG, "ledger: plan exceeds the reserved pool");
+    uint64_t *block = L->pool + (size_t)7 * p.upload_slot;
+    HIP_TRY(hipMemcpyAsync(block, p.upload.data(), p.upload.size() * 8, hipMemcpyHostToDevice, c->stream));
+    const uint32_t slots = (uint32_t)L->pool_slots;
+    const Job *d_jobs = (const Job *)(block + p.jobs_word);
+    for (size_t k = 0; k + 1 < p.launch.size(); k++) {
+        const uint32_t n = p.launch[k + 1] - p.launch[k];
+        if (n == 0) continue;
+        hipLaunchKernelGGL(cs::k_ledger_merge, dim3((n + 3) / 4), dim3(64), 0, c->stream, L->pool, d_jobs + p.launch[k], n, slots);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!p.witness.empty()) {
+        const uint32_t n = (uint32_t)p.witness.size();
+        hipLaunchKernelGGL(cs::k_ledger_gather, dim3((uint32_t)(((size_t)7 * n + 255) / 256)), dim3(256), 0, c->stream, L->pool,
+                           (const Emit *)(block + p.witness_word), n, slots, dst_witness, witness_words);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!p.commit.empty()) {
+        const uint32_t n = (uint32_t)p.commit.size();
+        hipLaunchKernelGGL(cs::k_ledger_gather, dim3((uint32_t)(((size_t)7 * n + 255) / 256)), dim3(256), 0, c->stream, L->pool,
+                           (const Emit *)(block + p.commit_word), n, slots, L->pool, (size_t)7 * (EMPTY_SLOTS + L->capacity));
+        HIP_TRY(hipGetLastError());
+    }
+    return CSTARK_OK;
+}
+
+int create_impl(cstark_ledger *L) {
+    cstark_ctx *c = L->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    uint32_t scratch_base;
+    Plan p;
+    plan_empty_digests(L->index.depth, 0, p); // sizes only
+    RC_TRY(reserve_pool(L, 0, (p.upload.size() + 6) / 7, &scratch_base));
+    Plan q;
+    plan_empty_digests(L->index.depth, scratch_base, q);
+    RC_TRY(run_plan(L, q, nullptr, 0));
+    HIP_TRY(cs::stream_wait(c->stream)); // the plan's host block is read by the copy
+    return CSTARK_OK;
+}
+
+int set_accounts_impl(cstark_ledger *L, uint32_t count, const uint64_t *indices, const uint64_t *values) {
+    cstark_ctx *c = L->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint32_t d = L->index.depth;
+    // values (2 slots each), at most depth + 1 jobs per account (2 words each): an upper bound on the upload block
+    const uint64_t scratch = 2ull * count + ((uint64_t)count * (d + 1) * 2 + 6) / 7 + 1;
+    uint32_t scratch_base;
+    RC_TRY(reserve_pool(L, max_new_nodes(d, count), scratch, &scratch_base));
+    Plan p;
+    if (!plan_set_accounts(L->index, scratch_base, count, indices, values, p))
+        return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_set_accounts: an index is out of range or given twice, or a value word is not reduced");
+    RC_TRY(run_plan(L, p, nullptr, 0));
+    commit(L->index, p);
+    HIP_TRY(cs::stream_wait(c->stream));
+    return CSTARK_OK;
+}
+
+int root_impl(cstark_ledger *L, uint64_t *root) {
+    cstark_ctx *c = L->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(root, L->pool + (size_t)7 * L->index.root_slot(), 56, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(cs::stream_wait(c->stream));
+    return CSTARK_OK;
+}
+
+int apply_impl(cstark_ledger *L, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices, const uint64_t *deltas, const uint64_t *sig_rx,
+               const uint8_t *sig_s, cstark_tx_witness *out, int32_t *refused_at, int32_t *reason) {
+    cstark_ctx *c = L->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint32_t d = L->index.depth, ne = 2 * n_tx;
+    // the host plan first: a refused batch touches neither the pool nor the resident witness
+    const uint64_t new_nodes = max_new_nodes(d, ne);
+    uint64_t cap = L->capacity ? L->capacity : 1024;
+    while (cap < (uint64_t)L->index.n_stored + new_nodes) cap *= 2;
+    if (EMPTY_SLOTS + cap > MAX_POOL_SLOTS) return fail(CSTARK_ERR_UNSUPPORTED, "ledger: the batch needs more than 2^28 digest slots");
+    Plan p;
+    if (!plan_apply(L->index, (uint32_t)(EMPTY_SLOTS + cap), n_tx, s_indices, r_indices, deltas, p))
+        return fail(CSTARK_ERR_UNSUPPORTED, "cstark_ledger_apply: the batch is too large to plan");
+    *refused_at = p.refused_at;
+    *reason = p.reason;
+    if (p.refused_at >= 0) return CSTARK_OK;
+    uint32_t scratch_base;
+    RC_TRY(reserve_pool(L, new_nodes, p.pool_slots - (EMPTY_SLOTS + cap), &scratch_base));
+    if (scratch_base != EMPTY_SLOTS + cap) return fail(CSTARK_ERR_INVALID_ARG, "ledger: pool layout differs from the plan's");
+    size_t sz[cs::WIT_NUM_SEGMENTS], off[cs::WIT_NUM_SEGMENTS + 1];
+    RC_TRY(tx_witness_reserve(c, n_tx, d, sz, off));
+    char *base = (char *)c->wit_buf;
+    const void *src[cs::WIT_NUM_SEGMENTS] = {};
+    src[cs::WIT_S_IDX] = s_indices; src[cs::WIT_R_IDX] = r_indices; src[cs::WIT_DELTAS] = deltas; src[cs::WIT_SIG_RX] = sig_rx; src[cs::WIT_SIG_S] = sig_s;
+    for (int i = 0; i < cs::WIT_NUM_SEGMENTS; i++)
+        if (src[i]) HIP_TRY(hipMemcpyAsync(base + off[i], src[i], sz[i], hipMemcpyHostToDevice, c->stream));
+    RC_TRY(run_plan(L, p, (uint64_t *)base, off[cs::WIT_NUM_SEGMENTS] / 8));
+    tx_witness_bind(c, n_tx, d, off);
+    commit(L->index, p);
+    if (out) {
+        const int segs[] = {cs::WIT_INITIAL_ROOTS, cs::WIT_S_OLD, cs::WIT_R_OLD, cs::WIT_S_PATHS, cs::WIT_R_PATHS};
+        void *dst[] = {(void *)out->initial_roots, (void *)out->s_old_values, (void *)out->r_old_values, (void *)out->s_paths, (void *)out->r_paths};
+        for (int i = 0; i < 5; i++) HIP_TRY(hipMemcpyAsync(dst[i], base + off[segs[i]], sz[segs[i]], hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync((void *)out->final_root, L->pool + (size_t)7 * L->index.root_slot(), 56, hipMemcpyDeviceToHost, c->stream));
+        memcpy((void *)out->s_indices, s_indices, sz[cs::WIT_S_IDX]);
+        memcpy((void *)out->r_indices, r_indices, sz[cs::WIT_R_IDX]);
+        memcpy((void *)out->deltas, deltas, sz[cs::WIT_DELTAS]);
+        memcpy((void *)out->sig_rx, sig_rx, sz[cs::WIT_SIG_RX]);
+        memcpy((void *)out->sig_s, sig_s, sz[cs::WIT_SIG_S]);
+    }
+    HIP_TRY(cs::stream_wait(c->stream)); // the caller's arrays and the plan's host block are read by the copies
+    return CSTARK_OK;
+}
+
+// a HIP failure inside a ledger call leaves the pool in an unknown state: every later call fails
+int guard(cstark_ledger *L, int rc) {
+    if (rc == CSTARK_ERR_HIP || rc == CSTARK_ERR_OOM) L->broken = true;
+    return rc;
+}
+int usable(cstark_ctx *c, cstark_ledger *L, const char *who) {
+    if (!c || !L) return fail(CSTARK_ERR_INVALID_ARG, "%s: null argument", who);
+    if (L->ctx != c) return fail(CSTARK_ERR_INVALID_ARG, "%s: the ledger belongs to another context", who);
+    if (L->broken) return fail(CSTARK_ERR_HIP, "%s: an earlier HIP failure left this ledger unusable", who);
+    return CSTARK_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int cstark_ledger_create(cstark_ctx *c, uint32_t merkle_depth, cstark_ledger **out) {
+    if (!c || !out) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_create: null argument");
+    *out = nullptr;
+    const uint32_t d = merkle_depth;
+    if (d == 0 || ((d + 1) & d) != 0 || d > MAX_DEPTH) return fail(CSTARK_ERR_INVALID_ARG, "tree depth must be one less than a power of 2 and at most 31");
+    cstark_ledger *L = new (std::nothrow) cstark_ledger(c, d);
+    if (!L) return fail(CSTARK_ERR_OOM, "cstark_ledger_create: out of host memory");
+    const int rc = create_impl(L);
+    if (rc) { cstark_ledger_destroy(L); return rc; }
+    *out = L;
+    return CSTARK_OK;
+}
+
+void cstark_ledger_destroy(cstark_ledger *L) {
+    if (!L) return;
+    (void)hipSetDevice(L->ctx->device);
+    (void)hipStreamSynchronize(L->ctx->stream);
+    if (L->pool) (void)hipFree(L->pool);
+    delete L;
+}
+
+int cstark_ledger_set_accounts(cstark_ctx *c, cstark_ledger *L, uint32_t count, const uint64_t *indices, const uint64_t *values) {
+    RC_TRY(usable(c, L, "cstark_ledger_set_accounts"));
+    if (count == 0 || count > MAX_TRANSFERS || !indices || !values) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_set_accounts: bad argument");
+    return guard(L, set_accounts_impl(L, count, indices, values));
+}
+
+int cstark_ledger_get_accounts(cstark_ctx *c, cstark_ledger *L, uint32_t count, const uint64_t *indices, uint64_t *values_out, uint8_t *present_out) {
+    RC_TRY(usable(c, L, "cstark_ledger_get_accounts"));
+    if (count && (!indices || !values_out || !present_out)) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_get_accounts: null argument");
+    for (uint32_t i = 0; i < count; i++) {
+        const auto it = L->index.accounts.find(indices[i]);
+        present_out[i] = it != L->index.accounts.end();
+        if (present_out[i]) memcpy(values_out + (size_t)14 * i, it->second.data(), 112);
+        else memset(values_out + (size_t)14 * i, 0, 112);
+    }
+    return CSTARK_OK;
+}
+
+int cstark_ledger_root(cstark_ctx *c, cstark_ledger *L, uint64_t root[7]) {
+    RC_TRY(usable(c, L, "cstark_ledger_root"));
+    if (!root) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_root: null argument");
+    return guard(L, root_impl(L, root));
+}
+
+int cstark_ledger_apply(cstark_ctx *c, cstark_ledger *L, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices, const uint64_t *deltas,
+                        const uint64_t *sig_rx, const uint8_t *sig_s, cstark_tx_witness *out, int32_t *refused_at, int32_t *reason) {
+    RC_TRY(usable(c, L, "cstark_ledger_apply"));
+    if (n_tx == 0 || n_tx > MAX_TRANSFERS || !s_indices || !r_indices || !deltas || !sig_rx || !sig_s || !refused_at || !reason)
+        return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_apply: bad argument");
+    if (out) {
+        if (out->n_tx != n_tx || out->merkle_depth != L->index.depth) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_apply: the output witness has another shape");
+        if (!out->initial_roots || !out->final_root || !out->s_old_values || !out->r_old_values || !out->s_indices || !out->r_indices || !out->s_paths ||
+            !out->r_paths || !out->deltas || !out->sig_rx || !out->sig_s)
+            return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_apply: output witness array pointer is null (the caller allocates every array)");
+    }
+    for (uint32_t t = 0; t < n_tx; t++)
+        if (deltas[t] >= cs::host::P) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_apply: a delta is not a reduced field element");
+    return guard(L, apply_impl(L, n_tx, s_indices, r_indices, deltas, sig_rx, sig_s, out, refused_at, reason));
+}
+
+} // extern "C"

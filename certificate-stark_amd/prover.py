@@ -100,6 +100,61 @@ class TransactionMetadata:
         np.savez_compressed(path, **{f: getattr(self, f) for f in self.FIELDS})
 
 
+class TransferRefused(Exception):
+    """Ledger.apply refused the batch at transfer `index`; nothing changed.  reason: one of Ledger.REASONS (cstark_ledger_reason)."""
+
+    def __init__(self, index, reason):
+        super().__init__("transfer %d refused: %s" % (index, Ledger.REASONS.get(reason, reason)))
+        self.index, self.reason = index, reason
+
+
+class Ledger:
+    """The account tree an operator holds, resident on the GPU (cstark_ledger_*): set_accounts, then apply(transfers) per batch -- the
+    counterpart of the sequential loop of TransactionMetadata::build_random (src/lib.rs:341-422) on real accounts and transfers.
+    apply() leaves the batch's witness resident in the backend: backend.prove(options) follows without an upload."""
+    INDEX_RANGE, SELF_TRANSFER, ABSENT, BALANCE = 1, 2, 3, 4
+    REASONS = {1: "index out of range", 2: "sender equals receiver", 3: "account absent", 4: "delta above the sender's balance"}
+
+    def __init__(self, depth=15, backend=None):
+        self.backend = backend or Backend()
+        self.depth = int(depth)
+        self._led = self.backend.ledger_create(self.depth)
+
+    def close(self):
+        if getattr(self, "_led", None) and getattr(self.backend, "ctx", None):
+            self.backend.ledger_destroy(self._led)
+        self._led = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_accounts(self, indices, values):
+        """bulk insert or overwrite: distinct leaf indices, values [count][14] (pk.x pk.y balance nonce, memory form)"""
+        self.backend.ledger_set_accounts(self._led, indices, values)
+
+    def root(self):
+        return self.backend.ledger_root(self._led)
+
+    def accounts(self, indices):
+        """-> (values [count][14], present [count])"""
+        return self.backend.ledger_get_accounts(self._led, indices)
+
+    def apply(self, transfers, want_witness=True):
+        """transfers: (s_indices, r_indices, deltas, sig_rx, sig_s) or an object with these attributes (a TransactionMetadata, say).
+        Applies them in order and returns the batch's TransactionMetadata (None with want_witness=False: the witness stays on the
+        device only); raises TransferRefused, with ledger and resident witness unchanged, at the first transfer that cannot be applied.
+        Signatures are copied through, not checked."""
+        if hasattr(transfers, "s_indices"):
+            transfers = tuple(getattr(transfers, f) for f in ("s_indices", "r_indices", "deltas", "sig_rx", "sig_s"))
+        at, reason, arrays = self.backend.ledger_apply(self._led, self.depth, *transfers, want_witness=want_witness)
+        if at >= 0:
+            raise TransferRefused(at, reason)
+        return None if arrays is None else TransactionMetadata(*[arrays[f] for f in TransactionMetadata.FIELDS])
+
+
 class TransactionProver:
     """MI355X counterpart of src/prover.rs::TransactionProver plus the hot half of Prover::prove."""
 

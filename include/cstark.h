@@ -429,6 +429,47 @@ int cstark_tx_witness_generate(cstark_tx_witness *w, uint64_t seed);
 /* n_sig messages [n][28] (public key || 16 elements) with their signatures (R.x [n][6], s [n][32]). */
 int cstark_schnorr_witness_generate(uint32_t n_sig, uint64_t seed, uint64_t *messages, uint64_t *sig_rx, uint8_t *sig_s);
 
+/* ---- account ledger: the witness from what an operator holds (replaces the sequential loop of TransactionMetadata::build_random,
+ * src/lib.rs:341-422: record the root and the sender's path, apply the transfer, re-hash two leaf-to-root paths, record the receiver's
+ * path) ------------------------------------------------------------------------------------------------------------------------------
+ * A ledger is a sparse Rescue `merge` tree of accounts (leaf = merge(value[0..7], value[7..14]); empty leaves are the all-zero digest,
+ * as in cstark_tx_witness_generate) whose digests live in device memory of its context: storage grows with the touched nodes, so depth 31
+ * with indices above 2^24 works.  The host keeps which nodes exist and the account values (the balance checks need them).  A batch is
+ * hashed as depth + 1 dependent launches of 2 n_tx independent merges, not as 2 n_tx (depth + 1) dependent merges.
+ * Every call is synchronous and takes the ledger's own context.  Misuse (null pointers, count or n_tx == 0, a ledger of another
+ * context, a word that is no reduced field element) is CSTARK_ERR_INVALID_ARG.  After a HIP failure inside a ledger call the ledger is
+ * unusable: every later call on it returns CSTARK_ERR_HIP. */
+typedef struct cstark_ledger cstark_ledger;
+/* why cstark_ledger_apply refused a batch; the first matching reason in this order */
+typedef enum cstark_ledger_reason {
+    CSTARK_LEDGER_APPLIED = 0,
+    CSTARK_LEDGER_INDEX_RANGE = 1,  /* an index >= 2^merkle_depth */
+    CSTARK_LEDGER_SELF_TRANSFER = 2, /* sender equals receiver */
+    CSTARK_LEDGER_ABSENT = 3,       /* sender or receiver has no account */
+    CSTARK_LEDGER_BALANCE = 4       /* delta above the sender's balance, both as canonical integers */
+} cstark_ledger_reason;
+/* An empty tree of depth 1, 3, 7, 15 or 31 (the depths cstark_tx_witness_upload accepts).  Destroy it before its context. */
+int cstark_ledger_create(cstark_ctx *ctx, uint32_t merkle_depth, cstark_ledger **out);
+void cstark_ledger_destroy(cstark_ledger *ledger);
+/* Bulk insert or overwrite: indices[count] distinct within the call, values[count][14] (pk.x pk.y balance nonce).  The leaves and then
+ * the unique parents of every level are hashed in parallel, one launch per level. */
+int cstark_ledger_set_accounts(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t count, const uint64_t *indices, const uint64_t *values);
+/* values_out[count][14] and present_out[count] (1 = the account exists; absent accounts read as zeros) */
+int cstark_ledger_get_accounts(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t count, const uint64_t *indices, uint64_t *values_out,
+                               uint8_t *present_out);
+int cstark_ledger_root(cstark_ctx *ctx, cstark_ledger *ledger, uint64_t root[7]);
+/* Applies n_tx transfers in order with the reference's arithmetic (sender balance - delta, sender nonce + 1, receiver balance + delta:
+ * field operations, src/lib.rs:373-375), advances the ledger and leaves the batch's witness RESIDENT in the context exactly as
+ * cstark_tx_witness_upload would: cstark_tx_build_trace / cstark_tx_prove / cstark_air_prove follow without an upload.  Roots, paths
+ * and old values are written on the device; indices, deltas and signatures (sig_rx [n_tx][6], sig_s [n_tx][32]) are copied through --
+ * signatures are NOT checked here, a wrong one yields a proof the verifier rejects.  out (optional): a witness whose arrays the caller
+ * allocated for (n_tx, merkle_depth), filled with all eleven fields.
+ * Refusal is not a failure: the status is CSTARK_OK, *refused_at = the first offending transfer (-1: none) and *reason its
+ * cstark_ledger_reason; a refused batch changes neither the ledger nor the resident witness (and `out` is not written). */
+int cstark_ledger_apply(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices,
+                        const uint64_t *deltas, const uint64_t *sig_rx, const uint8_t *sig_s, cstark_tx_witness *out,
+                        int32_t *refused_at, int32_t *reason);
+
 /* ---- verification (TransactionExample::verify, src/lib.rs:144-150: winterfell::verify over this library's own proof layout) -------
  * The call's status (cstark_status) is kept apart from the proof's verdict.  A verdict names the FIRST check that fails, in this
  * order: layout (MALFORMED, then UNSUPPORTED) | OPTIONS_MISMATCH | OOD | REMAINDER_COMMITMENT | POW | per query q = 0..nq-1:

@@ -159,6 +159,15 @@ class TransactionProver {
         proof.resize(len);
         return proof;
     }
+    // proves the witness that is resident in the context: the batch Ledger::apply just left there (n_tx: its number of transfers)
+    std::vector<uint8_t> prove_resident(size_t n_tx) {
+        const cstark_options o = options_.raw();
+        std::vector<uint8_t> proof(cstark_tx_proof_size_bound((uint32_t)n_tx, &o));
+        size_t len = 0;
+        check(cstark_tx_prove(ctx_.raw(), &o, proof.data(), proof.size(), &len));
+        proof.resize(len);
+        return proof;
+    }
     // src/prover.rs:106-129 (from the metadata: the first initial root and the final root)
     static PublicInputs get_pub_inputs(const TransactionMetadata &m) { return {m.initial_roots.at(0), m.final_root}; }
 
@@ -166,6 +175,67 @@ class TransactionProver {
     ProofOptions options_;
     Context &ctx_;
     size_t n_tx_ = 0;
+};
+
+// Ledger::apply refused the batch at transfer `index` (reason: cstark_ledger_reason); ledger and resident witness are unchanged
+struct TransferRefused : std::runtime_error {
+    int32_t index, reason;
+    TransferRefused(int32_t i, int32_t r) : std::runtime_error("transfer " + std::to_string(i) + " refused (reason " + std::to_string(r) + ")"), index(i), reason(r) {}
+};
+// A batch of signed transfers as an operator receives them
+struct Transfers {
+    std::vector<uint64_t> s_indices, r_indices;
+    std::vector<BaseElement> deltas;
+    std::vector<std::array<BaseElement, 6>> sig_rx;
+    std::vector<std::array<uint8_t, 32>> sig_s;
+};
+// The account tree an operator holds, resident on the GPU (cstark_ledger_*): what replaces the sequential loop of
+// TransactionMetadata::build_random (src/lib.rs:341-422) on real accounts.  apply() leaves the batch's witness resident in the context:
+// TransactionProver::prove_resident follows without an upload.
+class Ledger {
+  public:
+    Ledger(Context &ctx, unsigned depth = 15) : ctx_(ctx), depth_(depth) { check(cstark_ledger_create(ctx.raw(), depth, &led_)); }
+    ~Ledger() { cstark_ledger_destroy(led_); }
+    Ledger(const Ledger &) = delete;
+    Ledger &operator=(const Ledger &) = delete;
+    void set_accounts(const std::vector<uint64_t> &indices, const std::vector<std::array<BaseElement, 14>> &values) {
+        if (indices.size() != values.size() || indices.empty()) throw Error(CSTARK_ERR_INVALID_ARG, "one value per account index");
+        check(cstark_ledger_set_accounts(ctx_.raw(), led_, (uint32_t)indices.size(), indices.data(), values[0].data()));
+    }
+    Hash root() const {
+        Hash r{};
+        check(cstark_ledger_root(ctx_.raw(), led_, r.data()));
+        return r;
+    }
+    // values of the given accounts; present[i] = 0 where there is none (its value reads as zeros)
+    std::vector<std::array<BaseElement, 14>> accounts(const std::vector<uint64_t> &indices, std::vector<uint8_t> *present = nullptr) const {
+        std::vector<std::array<BaseElement, 14>> values(indices.size());
+        std::vector<uint8_t> have(indices.size());
+        if (!indices.empty()) check(cstark_ledger_get_accounts(ctx_.raw(), led_, (uint32_t)indices.size(), indices.data(), values[0].data(), have.data()));
+        if (present) *present = have;
+        return values;
+    }
+    // applies the transfers in order; throws TransferRefused (nothing changed) at the first one that cannot be applied
+    TransactionMetadata apply(const Transfers &t) {
+        const size_t n = t.s_indices.size();
+        if (n == 0 || t.r_indices.size() != n || t.deltas.size() != n || t.sig_rx.size() != n || t.sig_s.size() != n)
+            throw Error(CSTARK_ERR_INVALID_ARG, "transfer vectors are not of equal length");
+        TransactionMetadata m;
+        m.merkle_depth = depth_;
+        m.initial_roots.resize(n); m.s_old_values.resize(n); m.r_old_values.resize(n); m.s_indices.resize(n); m.r_indices.resize(n);
+        m.s_paths.resize(n * (depth_ + 1) * 7); m.r_paths.resize(n * (depth_ + 1) * 7); m.deltas.resize(n); m.sig_rx.resize(n); m.sig_s.resize(n);
+        cstark_tx_witness w = m.view();
+        int32_t at = -1, reason = 0;
+        check(cstark_ledger_apply(ctx_.raw(), led_, (uint32_t)n, t.s_indices.data(), t.r_indices.data(), t.deltas.data(), t.sig_rx[0].data(),
+                                  t.sig_s[0].data(), &w, &at, &reason));
+        if (at >= 0) throw TransferRefused(at, reason);
+        return m;
+    }
+
+  private:
+    Context &ctx_;
+    unsigned depth_;
+    cstark_ledger *led_ = nullptr;
 };
 
 // Several proofs in flight on ONE GPU.  A proof is a chain of launches with a dozen host round trips (the Fiat-Shamir channel) during
