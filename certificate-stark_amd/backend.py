@@ -215,6 +215,22 @@ class Backend:
                                            C.c_uint32(block_len), C.c_uint32(log_blowup), C.c_uint64(off), C.c_uint32(k0), C.c_uint32(nk)))
         return coeffs, lde
 
+    def step2_columns(self, evals, block_len, split, log_blowup, col0=0, ncols=None, offset=None, k0=0, nk=None, coeffs=None, lde=None):
+        """step_columns for columns that hold one value on rows [0, split) of every block of block_len rows and another on rows
+        [split, block_len), 0 < split < block_len."""
+        width, n = evals.shape
+        ncols = width - col0 if ncols is None else ncols
+        nk = (1 << log_blowup) - k0 if nk is None else nk
+        if coeffs is None:
+            coeffs = self.empty_u64(width, n)
+        if lde is None:
+            lde = self.empty_u64(nk, width, n)
+        off = self.field_lde_offset() if offset is None else int(offset)
+        check(self.lib.cstark_step2_columns(self.ctx, self._ptr(evals), self._ptr(coeffs), self._ptr(lde), C.c_uint32(width),
+                                            C.c_uint32(col0), C.c_uint32(ncols), C.c_uint32(n.bit_length() - 1), C.c_uint32(block_len),
+                                            C.c_uint32(split), C.c_uint32(log_blowup), C.c_uint64(off), C.c_uint32(k0), C.c_uint32(nk)))
+        return coeffs, lde
+
     # ---- K4 / K5 ----
     def empty_u8(self, *shape):
         return torch.empty(shape, dtype=torch.uint8, device=self.device)

@@ -220,15 +220,16 @@ int lde_impl_inner(cstark_ctx *c, const uint64_t *d_coeffs, uint64_t *d_lde, uin
 
 // Step columns (ntt.h): the constants of one (trace length, blowup, offset, block length) -- D and, per coset, the column pass of D.
 // Built on first use on the context's stream, freed with the context; 8 (1 + b) n bytes: 72 MB at 2^20 rows and blowup 8.
-int get_step_table(cstark_ctx *c, unsigned log_n, unsigned log_b, uint64_t offset, unsigned log_block, const cs::StepTable **out) {
+// split = R > 0: the same for D_R, the second pair of tables of the two-level columns.
+int get_step_table(cstark_ctx *c, unsigned log_n, unsigned log_b, uint64_t offset, unsigned log_block, unsigned split, const cs::StepTable **out) {
     for (const cs::StepTable &t : c->steps)
-        if (t.log_n == log_n && t.log_b == log_b && t.offset == offset && t.log_block == log_block) { *out = &t; return CSTARK_OK; }
+        if (t.log_n == log_n && t.log_b == log_b && t.offset == offset && t.log_block == log_block && t.split == split) { *out = &t; return CSTARK_OK; }
     const NttPlan *p;
     const CosetTable *ct;
     RC_TRY(get_plan(c, log_n, &p));
     RC_TRY(get_coset_table(c, log_n, log_b, offset, &ct));
     const size_t n = (size_t)1 << log_n, b = (size_t)1 << log_b;
-    cs::StepTable t{log_n, log_b, offset, log_block, nullptr, nullptr};
+    cs::StepTable t{log_n, log_b, offset, log_block, split, nullptr, nullptr};
     DevGuard g;
     HIP_TRY(g.alloc(&t.d, n * 8));
     HIP_TRY(g.alloc(&t.w, b * n * 8));
@@ -238,7 +239,7 @@ int get_step_table(cstark_ctx *c, unsigned log_n, unsigned log_b, uint64_t offse
     a.prescale = ct->s; a.prescale_batch_stride = n;
     a.aux_ps = ct->aux; a.aux_ps_batch_stride = ct->aux_words;
     a.in_batch_stride = 0; a.scratch_batch_stride = n;
-    HIP_TRY(cs::ntt_step_build_tables(t.d, log_block, p->winv, a, c->stream));
+    HIP_TRY(cs::ntt_step_build_tables(t.d, log_block, split, p->winv, a, c->stream));
     c->steps.push_back(t);
     g.release();
     *out = &c->steps.back();
@@ -247,12 +248,14 @@ int get_step_table(cstark_ctx *c, unsigned log_n, unsigned log_b, uint64_t offse
 // Coefficients and extension of columns [col0, col0 + ncols) that are constant over blocks of block_len rows.  Where the transform serves
 // the shape (cs::ntt_step_shape) only the first row of every block is read and d_evals stays intact; everywhere else the columns take
 // interpolate_impl (which destroys them) and lde_impl.
+// split = R > 0: two-level columns, one value on rows [0, R) of every block and another on rows [R, block_len); rows 0 and R are read.
 int step_impl(cstark_ctx *c, uint64_t *d_evals, uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols, uint32_t log_n,
-              uint32_t block_len, uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk) {
+              uint32_t block_len, uint32_t split, uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk) {
     if (!c || !d_evals || !d_coeffs || !d_lde || width == 0 || ncols == 0 || (uint64_t)col0 + ncols > width)
         return fail(CSTARK_ERR_INVALID_ARG, "cstark_step_columns: bad argument");
     if (log_n < cs::NTT_MIN_LOG_N || log_n > cs::NTT_MAX_LOG_N || log_blowup > 6) return fail(CSTARK_ERR_UNSUPPORTED, "unsupported domain size");
     if (block_len == 0 || (block_len & (block_len - 1)) || block_len > (1u << log_n)) return fail(CSTARK_ERR_INVALID_ARG, "the block length must be a power of two up to the trace length");
+    if (split >= block_len) return fail(CSTARK_ERR_INVALID_ARG, "the split row must lie inside the block");
     if (domain_offset == 0 || domain_offset >= cs::host::P) return fail(CSTARK_ERR_INVALID_ARG, "domain offset must be a nonzero field element");
     if ((uint64_t)k0 + nk > (1ull << log_blowup)) return fail(CSTARK_ERR_INVALID_ARG, "coset range exceeds the blowup factor");
     const size_t n = (size_t)1 << log_n;
@@ -265,15 +268,21 @@ int step_impl(cstark_ctx *c, uint64_t *d_evals, uint64_t *d_coeffs, uint64_t *d_
     const NttPlan *p;
     const cs::StepTable *t;
     RC_TRY(get_plan(c, log_n, &p));
-    RC_TRY(get_step_table(c, log_n, log_blowup, domain_offset, log_block, &t));
-    RC_TRY(ensure_ws(c, ((size_t)ncols << (log_n - log_block)) * 8)); // the factors A [ncols][T]
+    const cs::StepTable *tr = nullptr;
+    RC_TRY(get_step_table(c, log_n, log_blowup, domain_offset, log_block, 0, &t));
+    if (split) RC_TRY(get_step_table(c, log_n, log_blowup, domain_offset, log_block, split, &tr));
+    RC_TRY(ensure_ws(c, ((size_t)ncols << (log_n - log_block)) * (split ? 16 : 8))); // the factors A [ncols][T], or A1 | A2 [ncols][2][T]
     uint64_t *fac = (uint64_t *)c->ws;
-    HIP_TRY(cs::ntt_step_coefficients(d_evals + (size_t)col0 * n, fac, d_coeffs + (size_t)col0 * n, t->d, ncols, log_n, log_block, p->winv, p->n_inv, c->stream));
+    if (split)
+        HIP_TRY(cs::ntt_step2_coefficients(d_evals + (size_t)col0 * n, fac, d_coeffs + (size_t)col0 * n, t->d, tr->d, ncols, log_n, log_block, split, p->winv,
+                                           p->n_inv, c->stream));
+    else
+        HIP_TRY(cs::ntt_step_coefficients(d_evals + (size_t)col0 * n, fac, d_coeffs + (size_t)col0 * n, t->d, ncols, log_n, log_block, p->winv, p->n_inv, c->stream));
     return lde_timed(c, (uint64_t)ncols * nk << log_n, [&] {
         cs::NttArgs a{};
         a.out = d_lde + (size_t)col0 * n; a.width = ncols; a.batch = nk; a.log_n = log_n;
         a.out_batch_stride = (size_t)width * n; a.aux = p->aux_w;
-        HIP_TRY(cs::ntt_step_rows(a, t->w + (size_t)k0 * n, fac, log_block, c->stream));
+        HIP_TRY(cs::ntt_step_rows(a, t->w + (size_t)k0 * n, tr ? tr->w + (size_t)k0 * n : nullptr, fac, log_block, c->stream));
         return (int)CSTARK_OK;
     });
 }
@@ -602,7 +611,12 @@ int cstark_lde_columns(cstark_ctx *c, const uint64_t *d_coeffs, uint64_t *d_lde,
 }
 int cstark_step_columns(cstark_ctx *c, uint64_t *d_evals, uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols,
                         uint32_t log_n, uint32_t block_len, uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk) {
-    return step_impl(c, d_evals, d_coeffs, d_lde, width, col0, ncols, log_n, block_len, log_blowup, domain_offset, k0, nk);
+    return step_impl(c, d_evals, d_coeffs, d_lde, width, col0, ncols, log_n, block_len, 0, log_blowup, domain_offset, k0, nk);
+}
+int cstark_step2_columns(cstark_ctx *c, uint64_t *d_evals, uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols,
+                         uint32_t log_n, uint32_t block_len, uint32_t split, uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk) {
+    if (split == 0) return fail(CSTARK_ERR_INVALID_ARG, "the split row must lie inside the block");
+    return step_impl(c, d_evals, d_coeffs, d_lde, width, col0, ncols, log_n, block_len, split, log_blowup, domain_offset, k0, nk);
 }
 
 // ---- composition polynomial (first "next" row: engine into_poly + column split) -----------------------------------
@@ -1026,8 +1040,8 @@ int lde_column_range(cstark_ctx *c, const uint64_t *d_coeffs, uint64_t *d_lde, u
     return lde_impl(c, d_coeffs, d_lde, width, col0, ncols, log_n, log_blowup, domain_offset, k0, nk);
 }
 int step_column_range(cstark_ctx *c, uint64_t *d_evals, uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols, uint32_t log_n,
-                      uint32_t block_len, uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk) {
-    return step_impl(c, d_evals, d_coeffs, d_lde, width, col0, ncols, log_n, block_len, log_blowup, domain_offset, k0, nk);
+                      uint32_t block_len, uint32_t split, uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk) {
+    return step_impl(c, d_evals, d_coeffs, d_lde, width, col0, ncols, log_n, block_len, split, log_blowup, domain_offset, k0, nk);
 }
 int tx_build_trace_split(cstark_ctx *c, uint64_t *d_trace) {
     if (!c || !d_trace) return fail(CSTARK_ERR_INVALID_ARG, "tx_build_trace_split: null argument");

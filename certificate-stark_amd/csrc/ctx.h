@@ -90,8 +90,9 @@ struct StepTable {
     unsigned log_n, log_b;
     uint64_t offset;
     unsigned log_block;
-    uint64_t *d; // [n]: the fixed vector D of (log_n, log_block)
-    uint64_t *w; // [b][n]: the forward column pass of D under each coset of (log_b, offset)
+    unsigned split; // 0: D of the whole block; R > 0: D_R of the first R rows of every block (two-level columns)
+    uint64_t *d; // [n]: the fixed vector D (or D_R) of (log_n, log_block)
+    uint64_t *w; // [b][n]: the forward column pass of d under each coset of (log_b, offset)
 };
 struct PeriodicTable {
     unsigned depth, log_n, log_b;
@@ -235,15 +236,17 @@ int tx_shard_combine(cstark_ctx *c, const uint64_t *d_parts, uint64_t *d_out, ui
 // (c->ev_mid behind it), then the curve ladders (c->ev_join2 behind them).  Registers [TX_LATE_COLS, TX_COPY_COLS) are complete
 // after ev_join and ev_mid, registers [0, TX_LATE_COLS) after ev_join2 as well.
 constexpr uint32_t TX_LATE_COLS = 37; // registers 0..36: the two curve points and the s-bit register between them
+constexpr uint32_t TX_ROOT_COLS = 58; // registers 58..64: the tree roots, two values per transaction (before / behind the Merkle recurrence's root copy)
 constexpr uint32_t TX_COPY_COLS = 65; // registers 65..93: key / amount copies and the sigma range accumulator
 constexpr uint32_t TX_STEP_COLS = 27; // of these, registers 65..91 are constant over the 1024 rows of a transaction (the copies and the nonce)
 int tx_build_trace_split(cstark_ctx *c, uint64_t *d_trace);
 // LDE of columns [col0, col0 + ncols) of a table of `width` columns (same layout and arguments as cstark_lde_columns)
 int lde_column_range(cstark_ctx *c, const uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols, uint32_t log_n,
                      uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk);
-// cstark_step_columns for the prover: coefficients and extension of trace columns that are constant over blocks of block_len rows
+// cstark_step_columns / cstark_step2_columns for the prover: coefficients and extension of trace columns that are constant over blocks of
+// block_len rows (split = 0), or over rows [0, split) and [split, block_len) of every block
 int step_column_range(cstark_ctx *c, uint64_t *d_evals, uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols, uint32_t log_n,
-                      uint32_t block_len, uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk);
+                      uint32_t block_len, uint32_t split, uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk);
 // internal (capi.hip): cstark_deep_composition_ext restricted to the first nk cosets, d_out = [m][nk][n]
 int evaluate_ood_frames(cstark_ctx *c, const uint64_t *d_coeffs, uint32_t width, const uint64_t *d_ccoef, uint32_t n_comp, uint32_t log_n,
                         const uint64_t zpts[2], uint64_t zb, uint64_t *out_trace, uint64_t *out_comp);

@@ -45,14 +45,20 @@ bool ntt_step_shape(unsigned log_n, unsigned log_block);
 // The constants of one (log_n, log_block, coset set), everything in Montgomery form: d_d [n] = the fixed vector D, and the forward column pass
 // of D under each coset of `a` -- a forward NttArgs with in = d_d, width = 1, its batch / prescale / aux fields as for ntt_columns --
 // written to a.scratch [batch][n] (a.out is not used).  d_winv: the n powers of w_n^-1.
-hipError_t ntt_step_build_tables(uint64_t *d_d, unsigned log_block, const uint64_t *d_winv, const NttArgs &a, hipStream_t stream);
+// split = R, 0 < R < 2^log_block: the same for D_R, the fixed vector of the first R rows of every block (two-level columns: one value
+// on rows [0, R) of a block and another on [R, 2^log_block))
+hipError_t ntt_step_build_tables(uint64_t *d_d, unsigned log_block, unsigned split, const uint64_t *d_winv, const NttArgs &a, hipStream_t stream);
 // d_evals [ncols][n] (only the first row of every block is read) -> d_fac [ncols][T], the per-column factors A, and d_coeffs [ncols][n],
 // the interpolants c_k = A[k mod T] D[k]
 hipError_t ntt_step_coefficients(const uint64_t *d_evals, uint64_t *d_fac, uint64_t *d_coeffs, const uint64_t *d_d, unsigned ncols, unsigned log_n,
                                  unsigned log_block, const uint64_t *d_winv, uint64_t n_inv, hipStream_t stream);
+// Two-level columns: rows 0 and `split` of every block are read -> d_fac [ncols][2][T], the factors A1 (of the value on rows >= split)
+// and A2 (of the difference), and d_coeffs, the interpolants c_k = A1[k mod T] D[k] + A2[k mod T] D_R[k]
+hipError_t ntt_step2_coefficients(const uint64_t *d_evals, uint64_t *d_fac, uint64_t *d_coeffs, const uint64_t *d_d, const uint64_t *d_dr, unsigned ncols,
+                                  unsigned log_n, unsigned log_block, unsigned split, const uint64_t *d_winv, uint64_t n_inv, hipStream_t stream);
 // The extension: the row pass alone, its input formed as d_wtab[batch][k1][c] * d_fac[column][c mod T] at the load.  Of `a`: out, width,
-// batch, log_n, out_batch_stride, aux.
-hipError_t ntt_step_rows(const NttArgs &a, const uint64_t *d_wtab, const uint64_t *d_fac, unsigned log_block, hipStream_t stream);
+// batch, log_n, out_batch_stride, aux.  d_wtab_r (or null): the tables of D_R -- two-level columns, d_fac as ntt_step2_coefficients writes it.
+hipError_t ntt_step_rows(const NttArgs &a, const uint64_t *d_wtab, const uint64_t *d_wtab_r, const uint64_t *d_fac, unsigned log_block, hipStream_t stream);
 // table[e] = base^e, e < n
 hipError_t ntt_power_table(uint64_t *d_table, size_t n, uint64_t base, hipStream_t stream);
 

@@ -304,6 +304,25 @@ __device__ __forceinline__ void rows_load_step(fp (&a)[1 << LA], const fp *__res
 #pragma unroll
     for (int c1 = 0; c1 < A; c1++) a[c1] = fp_mul(a[c1], fac[(c1 * T + s1) & fac_mask]);
 }
+// The same for a TWO-LEVEL column (see "two-level columns" below): the sum of two such products, rows * fac + rows_r * fac_r, with the
+// thread's row of the second table W_R and the column's second factors A2
+template <int LA, int LB, int LC>
+__device__ __forceinline__ void rows_load_step2(fp (&a)[1 << LA], const fp *__restrict__ rows, const fp *__restrict__ rows_r, unsigned in_lane, unsigned s1,
+                                                const fp *__restrict__ fac, const fp *__restrict__ fac_r, unsigned fac_mask) {
+    constexpr int A = V4<LA, LB, LC>::A, T = V4<LA, LB, LC>::T;
+    // One entry at a time: left to the scheduler, all 2^(LA+2) loads of a thread are issued first and the 2^20 kernel spills (80 VGPRs at six
+    // waves per SIMD; 60 dwords of scratch, and still 18 with two entries at a time).  The tables are read-only memory, whose loads no fence holds
+    // back, so the next entry's offsets are made to depend on this entry's sum.  64 VGPRs, no scratch; the waves of the other workgroups of a
+    // CU cover the serial round trips.
+    unsigned off = in_lane, sv = s1;
+#pragma unroll
+    for (int c1 = 0; c1 < A; c1++) {
+        const fp w = mb_load(rows + c1 * T, off, off + c1), wr = mb_load(rows_r + c1 * T, off, off + c1);
+        const unsigned j = (c1 * T + sv) & fac_mask;
+        a[c1] = fp_add(fp_mul(w, fac[j]), fp_mul(wr, fac_r[j]));
+        if (c1 + 1 < A) asm volatile("" : "+v"(off), "+v"(sv) : "v"((unsigned)a[c1]));
+    }
+}
 
 // ---- v4: whole-tile exchanges ------------------------------------------------------------------------------------------------------
 // k_ntt_cols_v4, k_ntt_rows_v4 and cols_v4_finish below still carry what the v5 kernels have shed: the table-less fallbacks behind
@@ -593,6 +612,69 @@ __global__ __launch_bounds__((V4<LA, LB, LC>::NT), 4) void k_ntt_rows_step_v4(co
     }
 }
 
+// k_ntt_rows_step_v4 for two-level columns (rows_load_step2): wtab_r [b][n] is the second table, fac [z][2][2^log_t] the factors A1 | A2.  Its own
+// text for the reason above: a load selected by a template parameter would be a shared body again.
+template <int LA, int LB, int LC>
+__global__ __launch_bounds__((V4<LA, LB, LC>::NT), 4) void k_ntt_rows_step2_v4(const fp *__restrict__ wtab, const fp *__restrict__ wtab_r, const fp *__restrict__ fac,
+                                                                              fp *__restrict__ out, unsigned log_n, unsigned log_t, size_t out_batch_stride,
+                                                                              const fp *__restrict__ aux_tw) {
+    using G = V4<LA, LB, LC>;
+    constexpr int A = G::A, Bn = G::Bn, Cn = G::Cn, T = G::T, LOGM = G::LOGM;
+    constexpr int TP = T + 4;
+    extern __shared__ __attribute__((aligned(16))) fp smem[];
+    fp *tile = smem;                              // [A][L2][TP]
+    fp *tw = smem + (size_t)A * L2 * TP;          // [M]
+    const unsigned log_r = log_n - LOGM;
+    const size_t n = (size_t)1 << log_n;
+    const fp *src = wtab + blockIdx.x * n;
+    const fp *src_r = wtab_r + blockIdx.x * n;
+    const fp *fac_z = fac + ((size_t)blockIdx.z << (log_t + 1)); // A1 [T] | A2 [T]
+    fp *dst = out + blockIdx.x * out_batch_stride + (size_t)blockIdx.z * n;
+    const unsigned s1 = threadIdx.x % T, l1 = threadIdx.x / T;
+    const unsigned l = threadIdx.x % L2, t = threadIdx.x / L2;
+    const unsigned k10 = xcd_pair_tile(blockIdx.y) * L2;
+    fp a[A];
+    rows_load_step2<LA, LB, LC>(a, src + ((size_t)k10 << LOGM), src_r + ((size_t)k10 << LOGM), (l1 << LOGM) + s1, s1, fac_z, fac_z + ((size_t)1 << log_t),
+                                (1u << log_t) - 1);
+    fill_twiddles<LA, LB, LC>(tw, aux_tw);
+    reg_ntt_dif<LA, false>(a); // step 1: columns c = c1 T + s
+    __syncthreads(); // tw[] ready
+#pragma unroll
+    for (int p = 0; p < A; p++) {
+        const unsigned j1 = cx_brev(p, LA);
+        tile[((size_t)j1 * L2 + l1) * TP + s1] = (j1 == 0) ? a[p] : fp_mul(a[p], tw[j1 * s1]);
+    }
+    __syncthreads();
+    fp z[G::J2][Bn];
+#pragma unroll
+    for (int j = 0; j < G::J2; j++) { // step 2: task u = t + T j = j1 Cn + c3
+        const unsigned u = t + T * j, j1 = u / Cn, c3 = u % Cn;
+#pragma unroll
+        for (int c2 = 0; c2 < Bn; c2++) z[j][c2] = tile[((size_t)j1 * L2 + l) * TP + c2 * Cn + c3];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < G::J2; j++) {
+        const unsigned u = t + T * j, j1 = u / Cn, c3 = u % Cn;
+        reg_ntt_dif<LB, false>(z[j]);
+#pragma unroll
+        for (int p = 0; p < Bn; p++) {
+            const unsigned j2 = cx_brev(p, LB);
+            tile[((size_t)j1 * L2 + l) * TP + j2 * Cn + (c3 ^ (j2 % Cn))] = (j2 == 0) ? z[j][p] : fp_mul(z[j][p], tw[(A * j2) * c3]);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < G::J3; j++) { // step 3: task v = t + T j = j1 Bn + j2
+        const unsigned v = t + T * j, j1 = v / Bn, j2 = v % Bn;
+        fp x[Cn];
+#pragma unroll
+        for (int c3 = 0; c3 < Cn; c3++) x[c3] = tile[((size_t)j1 * L2 + l) * TP + j2 * Cn + (c3 ^ (j2 % Cn))];
+        reg_ntt_dif<LC, false>(x);
+        rows_store_task<LA, LB, LC>(x, j1 + A * j2, l, log_r, 0, 0, dst + k10);
+    }
+}
+
 // =====================================================================================================
 // v5 kernels: the v4 passes for shapes with two step-2 and two step-3 tasks per thread (2^LA = 2 * 2^LB = 2 * 2^LC: the
 // 16 * 8 * 8 split of 1024 points), with each of the two exchanges done in TWO HALVES through a tile of half the size.  The tasks
@@ -792,6 +874,69 @@ __global__ __launch_bounds__((V4<LA, LB, LC>::NT), V5_ROWS_WAVES) void k_ntt_row
     }
 }
 
+// k_ntt_rows_step_v5 for two-level columns, as k_ntt_rows_step2_v4.
+template <int LA, int LB, int LC>
+__global__ __launch_bounds__((V4<LA, LB, LC>::NT), V5_ROWS_WAVES) void k_ntt_rows_step2_v5(const fp *__restrict__ wtab, const fp *__restrict__ wtab_r,
+                                                                                          const fp *__restrict__ fac, fp *__restrict__ out, unsigned log_n,
+                                                                                          unsigned log_t, size_t out_batch_stride,
+                                                                                          const fp *__restrict__ aux_tw) {
+    constexpr bool INV = false;
+    using G = V4<LA, LB, LC>;
+    constexpr int A = G::A, Bn = G::Bn, Cn = G::Cn, T = G::T, LOGM = G::LOGM, AH = A / 2;
+    static_assert(G::J2 == 2 && G::J3 == 2 && Bn == AH && Cn == AH, "two tasks per thread and step, one per half");
+    constexpr int TP = T + 4; // padded run of q per (j1, l), as in the v4 kernel
+    extern __shared__ __attribute__((aligned(16))) fp smem[];
+    fp *tile = smem;                              // [A / 2][L2][TP]
+    fp *tw = smem + (size_t)AH * L2 * TP;         // [M]
+    const unsigned log_r = log_n - LOGM;
+    const size_t n = (size_t)1 << log_n;
+    const fp *src = wtab + blockIdx.x * n;
+    const fp *src_r = wtab_r + blockIdx.x * n;
+    const fp *fac_z = fac + ((size_t)blockIdx.z << (log_t + 1)); // A1 [T] | A2 [T]
+    fp *dst = out + blockIdx.x * out_batch_stride + (size_t)blockIdx.z * n;
+    const unsigned s1 = threadIdx.x % T, l1 = threadIdx.x / T; // step 1: s = c2 Cn + c3 fastest across lanes (coalesced row reads)
+    const unsigned l = threadIdx.x % L2, t = threadIdx.x / L2; // steps 2 and 3: l fastest across lanes (64-byte transposed stores)
+    const unsigned k10 = xcd_pair_tile(blockIdx.y) * L2;
+    fp a[A];
+    rows_load_step2<LA, LB, LC>(a, src + ((size_t)k10 << LOGM), src_r + ((size_t)k10 << LOGM), (l1 << LOGM) + s1, s1, fac_z, fac_z + ((size_t)1 << log_t),
+                                (1u << log_t) - 1);
+    fill_twiddles<LA, LB, LC>(tw, aux_tw); // after the tile loads: with the fill first hipcc spills 2 of the 80 VGPRs six waves per SIMD allow
+    const unsigned jh = t / Cn, c3 = t % Cn;
+    const unsigned j1s = t / Bn, j2s = t % Bn;
+    reg_ntt_dif<LA, INV>(a); // step 1: columns c = c1 T + s
+    __syncthreads(); // tw[] ready
+    fp z[2][Bn];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+#pragma unroll
+        for (int p = 0; p < A; p++) {
+            const unsigned j1 = cx_brev(p, LA);
+            if ((int)(j1 / AH) == h) tile[((size_t)(j1 % AH) * L2 + l1) * TP + s1] = (j1 == 0) ? a[p] : fp_mul(a[p], tw[j1 * s1]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int c2 = 0; c2 < Bn; c2++) z[h][c2] = tile[((size_t)jh * L2 + l) * TP + c2 * Cn + c3];
+        __syncthreads();
+    }
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        reg_ntt_dif<LB, INV>(z[h]);
+#pragma unroll
+        for (int p = 0; p < Bn; p++) {
+            const unsigned j2 = cx_brev(p, LB);
+            const fp v = (j2 == 0) ? z[h][p] : fp_mul(z[h][p], tw[(A * j2) * c3]);
+            tile[((size_t)jh * L2 + l) * TP + j2 * Cn + (c3 ^ (j2 % Cn))] = v;
+        }
+        __syncthreads();
+        fp x[Cn];
+#pragma unroll
+        for (int q = 0; q < Cn; q++) x[q] = tile[((size_t)j1s * L2 + l) * TP + j2s * Cn + (q ^ (j2s % Cn))];
+        if (h == 0) __syncthreads();
+        reg_ntt_dif<LC, INV>(x);
+        rows_store_task<LA, LB, LC>(x, (j1s + AH * h) + A * j2s, l, log_r, 0, 0, dst + k10);
+    }
+}
+
 // The sizes served by the three-step kernels -- the ONE list: both passes of n = 2^(2 LOGM) points split LOGM = LA + LB + LC, with
 // whole-tile (v4) or half-tile (v5) exchanges.  ntt_three_step_shape and ntt_columns both read it.
 template <int LA_, int LB_, int LC_, bool HALF_TILE_>
@@ -809,8 +954,9 @@ bool three_step_size(unsigned log_n, F &&f) {
 // Both passes of one three-step size.  The dense tables are not optional: get_plan / get_coset_table (capi.hip) build them for
 // exactly the sizes of three_step_size, and a caller that comes without them is refused -- there is no slower table-less path.
 // `step` (forward only): instead of the pair, either the column pass alone (step->wtab == nullptr: a.scratch receives it -- how the
-// step-column tables are built) or the row pass of step columns alone (reads step->wtab and step->fac, no scratch)
-struct StepPass { const fp *wtab, *fac; unsigned log_t; };
+// step-column tables are built) or the row pass of step columns alone (reads step->wtab and step->fac, no scratch; with step->wtab_r
+// the row pass of two-level columns, fac holding both sets of factors)
+struct StepPass { const fp *wtab, *fac; unsigned log_t; const fp *wtab_r = nullptr; };
 template <class S, bool INV>
 hipError_t launch_three_step(const NttArgs &a, hipStream_t stream, const StepPass *step = nullptr) {
     using G = V4<S::LA, S::LB, S::LC>;
@@ -836,9 +982,15 @@ hipError_t launch_three_step(const NttArgs &a, hipStream_t stream, const StepPas
         if constexpr (!INV) {
             if (step && step->wtab) {
                 const auto k_step = k_ntt_rows_step_v5<S::LA, S::LB, S::LC>;
+                const auto k_step2 = k_ntt_rows_step2_v5<S::LA, S::LB, S::LC>;
                 if ((e = hipFuncSetAttribute((const void *)k_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows)) != hipSuccess) return e;
-                hipLaunchKernelGGL(k_step, grid_rows, dim3(G::NT), lds_rows, stream, step->wtab, step->fac, a.out, a.log_n, step->log_t, a.out_batch_stride,
-                                   a.aux + G::M);
+                if ((e = hipFuncSetAttribute((const void *)k_step2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows)) != hipSuccess) return e;
+                if (step->wtab_r)
+                    hipLaunchKernelGGL(k_step2, grid_rows, dim3(G::NT), lds_rows, stream, step->wtab, step->wtab_r, step->fac, a.out, a.log_n, step->log_t,
+                                       a.out_batch_stride, a.aux + G::M);
+                else
+                    hipLaunchKernelGGL(k_step, grid_rows, dim3(G::NT), lds_rows, stream, step->wtab, step->fac, a.out, a.log_n, step->log_t,
+                                       a.out_batch_stride, a.aux + G::M);
             }
         }
     } else {
@@ -855,9 +1007,15 @@ hipError_t launch_three_step(const NttArgs &a, hipStream_t stream, const StepPas
         if constexpr (!INV) {
             if (step && step->wtab) {
                 const auto k_step = k_ntt_rows_step_v4<S::LA, S::LB, S::LC>;
+                const auto k_step2 = k_ntt_rows_step2_v4<S::LA, S::LB, S::LC>;
                 if ((e = hipFuncSetAttribute((const void *)k_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows)) != hipSuccess) return e;
-                hipLaunchKernelGGL(k_step, grid_rows, dim3(G::NT), lds_rows, stream, step->wtab, step->fac, a.out, a.log_n, step->log_t, a.out_batch_stride,
-                                   a.aux + G::M);
+                if ((e = hipFuncSetAttribute((const void *)k_step2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows)) != hipSuccess) return e;
+                if (step->wtab_r)
+                    hipLaunchKernelGGL(k_step2, grid_rows, dim3(G::NT), lds_rows, stream, step->wtab, step->wtab_r, step->fac, a.out, a.log_n, step->log_t,
+                                       a.out_batch_stride, a.aux + G::M);
+                else
+                    hipLaunchKernelGGL(k_step, grid_rows, dim3(G::NT), lds_rows, stream, step->wtab, step->fac, a.out, a.log_n, step->log_t,
+                                       a.out_batch_stride, a.aux + G::M);
             }
         }
     }
@@ -1126,6 +1284,12 @@ hipError_t ntt_build_aux_coset(fp *d_aux, const fp *d_w, const fp *d_s, const Nt
 // on (n, B) alone.  The column pass of the three-step transform works on every column class c = k mod C by itself and linearly, so
 // for T | C it sends c_k to A[c mod T] W[k1][c], W = the column pass of D: a table per coset, built once.  A step column then costs a
 // T-point transform, the pointwise coefficient table and, per coset, the row pass alone with W A formed at its loads.
+//
+// Two-level columns: f[t B + r] = u[t] for r < R, v[t] for r >= R (0 < R < B) is the step column of v plus (u - v) on the first R
+// rows of every block, so with A1 = the factors A of v and Delta^[j] = sum_t (u - v)[t] z^(-t j)
+//   c_k = A1[k mod T] D[k] + A2[k mod T] D_R[k],   A2[j] = Delta^[j] / n,   D_R[k] = sum_{r<R} w_n^(-r k):
+//   D_R[0] = R,  D_R[k] = (w_n^(-R k) - 1) / (w_n^(-k) - 1) otherwise
+// D_R depends on (n, R) alone, its column pass W_R is a second table per coset, and the row pass takes W A1 + W_R A2 at its loads.
 bool ntt_step_shape(unsigned log_n, unsigned log_block) {
     NttThreeStepShape s;
     return log_block < log_n && ntt_three_step_shape(log_n, &s) && log_n - log_block <= s.log_c;
@@ -1135,6 +1299,12 @@ __global__ __launch_bounds__(256) void k_step_d(fp *__restrict__ d, const fp *__
     const size_t k = blockIdx.x * (size_t)256 + threadIdx.x;
     if (k >= n) return;
     d[k] = k == 0 ? FP_ONE : (k & (((size_t)1 << log_t) - 1)) == 0 ? 0 : fp_inv(fp_sub(winv[k], FP_ONE));
+}
+// D_R [n] of the two-level columns: r_mont = R in Montgomery form; w_n^(-R k) is winv[R k mod n]
+__global__ __launch_bounds__(256) void k_step_dr(fp *__restrict__ d, const fp *__restrict__ winv, size_t n, unsigned split, fp r_mont) {
+    const size_t k = blockIdx.x * (size_t)256 + threadIdx.x;
+    if (k >= n) return;
+    d[k] = k == 0 ? r_mont : fp_mul(fp_sub(winv[(k * split) & (n - 1)], FP_ONE), fp_inv(fp_sub(winv[k], FP_ONE)));
 }
 // grid = columns: one workgroup gathers the T block values of its column (the first row of every block), transforms them in LDS and
 // writes the T factors A
@@ -1153,6 +1323,36 @@ __global__ __launch_bounds__(NT) void k_step_factors(const fp *__restrict__ eval
         fac[((size_t)blockIdx.x << log_t) + j] = j == 0 ? fp_mul(g, t_inv) : fp_mul(fp_mul(g, n_inv), fp_sub(winv[(size_t)j << log_block], FP_ONE));
     }
 }
+// The same for a two-level column: rows `split` (v) and 0 (u) of every block; fac [column][2][T] = A1 (of v) | A2 (of u - v)
+__global__ __launch_bounds__(NT) void k_step2_factors(const fp *__restrict__ evals, fp *__restrict__ fac, unsigned log_n, unsigned log_t, unsigned split,
+                                                      const fp *__restrict__ winv, fp n_inv, fp t_inv) {
+    extern __shared__ __attribute__((aligned(16))) fp smem[];
+    const unsigned T = 1u << log_t, log_block = log_n - log_t;
+    fp *tile = smem, *tile_d = smem + T, *tw = smem + 2 * T;
+    const fp *col = evals + ((size_t)blockIdx.x << log_n);
+    for (unsigned t = threadIdx.x; t < T; t += NT) {
+        const fp v = col[((size_t)t << log_block) + split];
+        tile[t] = v;
+        tile_d[t] = fp_sub(col[(size_t)t << log_block], v);
+    }
+    for (unsigned e = threadIdx.x; e < T / 2; e += NT) tw[e] = winv[(size_t)e << log_block];
+    __syncthreads();
+    lds_ntt_dif<1>(tile, log_t, tw);
+    lds_ntt_dif<1>(tile_d, log_t, tw);
+    fp *out = fac + ((size_t)blockIdx.x << (log_t + 1));
+    for (unsigned j = threadIdx.x; j < T; j += NT) {
+        const fp g = tile[bitrev(j, log_t)];
+        out[j] = j == 0 ? fp_mul(g, t_inv) : fp_mul(fp_mul(g, n_inv), fp_sub(winv[(size_t)j << log_block], FP_ONE));
+        out[T + j] = fp_mul(tile_d[bitrev(j, log_t)], n_inv);
+    }
+}
+// grid = (n / 256, columns)
+__global__ __launch_bounds__(256) void k_step2_coeffs(const fp *__restrict__ fac, const fp *__restrict__ d, const fp *__restrict__ dr, fp *__restrict__ coeffs,
+                                                      unsigned log_n, unsigned log_t) {
+    const size_t k = blockIdx.x * (size_t)256 + threadIdx.x, j = k & (((size_t)1 << log_t) - 1);
+    const fp *f = fac + ((size_t)blockIdx.y << (log_t + 1));
+    coeffs[((size_t)blockIdx.y << log_n) + k] = fp_add(fp_mul(f[j], d[k]), fp_mul(f[((size_t)1 << log_t) + j], dr[k]));
+}
 // grid = (n / 256, columns)
 __global__ __launch_bounds__(256) void k_step_coeffs(const fp *__restrict__ fac, const fp *__restrict__ d, fp *__restrict__ coeffs, unsigned log_n,
                                                      unsigned log_t) {
@@ -1160,10 +1360,11 @@ __global__ __launch_bounds__(256) void k_step_coeffs(const fp *__restrict__ fac,
     coeffs[((size_t)blockIdx.y << log_n) + k] = fp_mul(fac[((size_t)blockIdx.y << log_t) + (k & (((size_t)1 << log_t) - 1))], d[k]);
 }
 } // namespace
-hipError_t ntt_step_build_tables(uint64_t *d_d, unsigned log_block, const uint64_t *d_winv, const NttArgs &a, hipStream_t stream) {
-    if (!ntt_step_shape(a.log_n, log_block) || a.inverse || a.width != 1 || a.in != d_d) return hipErrorInvalidValue;
+hipError_t ntt_step_build_tables(uint64_t *d_d, unsigned log_block, unsigned split, const uint64_t *d_winv, const NttArgs &a, hipStream_t stream) {
+    if (!ntt_step_shape(a.log_n, log_block) || a.inverse || a.width != 1 || a.in != d_d || split >= (1u << log_block)) return hipErrorInvalidValue;
     const size_t n = (size_t)1 << a.log_n;
-    hipLaunchKernelGGL(k_step_d, dim3((unsigned)(n / 256)), dim3(256), 0, stream, d_d, d_winv, n, a.log_n - log_block);
+    if (split == 0) hipLaunchKernelGGL(k_step_d, dim3((unsigned)(n / 256)), dim3(256), 0, stream, d_d, d_winv, n, a.log_n - log_block);
+    else hipLaunchKernelGGL(k_step_dr, dim3((unsigned)(n / 256)), dim3(256), 0, stream, d_d, d_winv, n, split, host::from_u64(split));
     const StepPass columns_only{nullptr, nullptr, 0};
     hipError_t e = hipErrorInvalidValue;
     three_step_size(a.log_n, [&](auto split) { e = launch_three_step<decltype(split), false>(a, stream, &columns_only); });
@@ -1179,9 +1380,19 @@ hipError_t ntt_step_coefficients(const uint64_t *d_evals, uint64_t *d_fac, uint6
                        log_t);
     return hipGetLastError();
 }
-hipError_t ntt_step_rows(const NttArgs &a, const uint64_t *d_wtab, const uint64_t *d_fac, unsigned log_block, hipStream_t stream) {
+hipError_t ntt_step2_coefficients(const uint64_t *d_evals, uint64_t *d_fac, uint64_t *d_coeffs, const uint64_t *d_d, const uint64_t *d_dr, unsigned ncols,
+                                  unsigned log_n, unsigned log_block, unsigned split, const uint64_t *d_winv, uint64_t n_inv, hipStream_t stream) {
+    if (!ntt_step_shape(log_n, log_block) || ncols == 0 || ncols > 65535 || split == 0 || split >= (1u << log_block)) return hipErrorInvalidValue;
+    const unsigned log_t = log_n - log_block;
+    const uint64_t t_inv = host::inv(host::from_u64((uint64_t)1 << log_t));
+    hipLaunchKernelGGL(k_step2_factors, dim3(ncols), dim3(NT), (size_t)5 * 8 << (log_t - 1), stream, d_evals, d_fac, log_n, log_t, split, d_winv, n_inv, t_inv);
+    hipLaunchKernelGGL(k_step2_coeffs, dim3((unsigned)(((size_t)1 << log_n) / 256), ncols), dim3(256), 0, stream, (const fp *)d_fac, d_d, d_dr, d_coeffs,
+                       log_n, log_t);
+    return hipGetLastError();
+}
+hipError_t ntt_step_rows(const NttArgs &a, const uint64_t *d_wtab, const uint64_t *d_wtab_r, const uint64_t *d_fac, unsigned log_block, hipStream_t stream) {
     if (!ntt_step_shape(a.log_n, log_block) || a.inverse || !d_wtab || !d_fac) return hipErrorInvalidValue;
-    const StepPass rows{d_wtab, d_fac, a.log_n - log_block};
+    const StepPass rows{d_wtab, d_fac, a.log_n - log_block, d_wtab_r};
     hipError_t e = hipErrorInvalidValue;
     three_step_size(a.log_n, [&](auto split) { e = launch_three_step<decltype(split), false>(a, stream, &rows); });
     return e;

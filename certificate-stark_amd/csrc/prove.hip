@@ -224,8 +224,9 @@ struct AirJob {
     // Optional: the order in which the trace columns become complete when build() returns with parts of the trace still being
     // written on internal streams (TransactionAir).  The prover interpolates and extends batch after batch, waiting for a batch's
     // events first; empty = all columns at once.
-    // block != 0: a step batch -- every column is constant over blocks of `block` rows (taken to cstark_step_columns where the proof's shape allows)
-    struct ColumnBatch { uint32_t col0, ncols; hipEvent_t wait[2]; uint32_t block = 0; };
+    // block != 0: a step batch -- every column is constant over blocks of `block` rows (taken to cstark_step_columns where the proof's shape allows),
+    // or, with split != 0, over rows [0, split) and [split, block) of every block (cstark_step2_columns)
+    struct ColumnBatch { uint32_t col0, ncols; hipEvent_t wait[2]; uint32_t block = 0, split = 0; };
     std::vector<ColumnBatch> batches;
     const uint64_t *pub_staging = nullptr; // pinned host copy of the public inputs, valid once every batch has been waited for
     bool public_ready = false;      // SchnorrAir: the extended public-input columns of this proof are in the arena
@@ -431,7 +432,7 @@ int commit_columns(cstark_ctx *c, ProveArena *a, AirJob &job, hipStream_t st, in
         const bool step = cb.block != 0 && !job.sharded && job.log_b <= job.log_ce;
         if (!step) RC_TRY(cstark_interpolate_columns(c, a->trace + (size_t)cb.col0 * n, a->coeffs + (size_t)cb.col0 * n, cb.ncols, log_n));
         if (i + 1 == job.batches.size()) HIP_TRY(hipEventRecord(a->ev[evi++], st));
-        if (step) RC_TRY(step_column_range(c, a->trace, a->coeffs, a->lde, W, cb.col0, cb.ncols, log_n, cb.block, job.log_b, host::lde_offset(), job.k0, job.nk));
+        if (step) RC_TRY(step_column_range(c, a->trace, a->coeffs, a->lde, W, cb.col0, cb.ncols, log_n, cb.block, cb.split, job.log_b, host::lde_offset(), job.k0, job.nk));
         else RC_TRY(lde_trace(c, a, job, cb.col0, cb.ncols));
     }
     HIP_TRY(hipEventRecord(a->ev[evi++], st));
@@ -1069,7 +1070,10 @@ int tx_build(cstark_ctx *c, ProveArena *a, AirJob &job) {
         // registers 65..91 are constant over a transaction (k_trace_aux): a step batch; the sigma range accumulator behind them is not
         job.batches = {{TX_COPY_COLS, TX_STEP_COLS, {nullptr, nullptr}, 1024},
                        {TX_COPY_COLS + TX_STEP_COLS, job.width - TX_COPY_COLS - TX_STEP_COLS, {nullptr, nullptr}},
-                       {TX_LATE_COLS, TX_COPY_COLS - TX_LATE_COLS, {c->ev_join, c->ev_mid}},
+                       {TX_LATE_COLS, TX_ROOT_COLS - TX_LATE_COLS, {c->ev_join, c->ev_mid}},
+                       // the tree roots 58..64 hold one value up to the root copy of the Merkle recurrence (row 8 depth + 7 of a
+                       // transaction) and another behind it: a two-level step batch
+                       {TX_ROOT_COLS, TX_COPY_COLS - TX_ROOT_COLS, {c->ev_join, c->ev_mid}, 1024, 8 * job.item + 7},
                        {0, TX_LATE_COLS, {c->ev_join2, nullptr}}};
     return CSTARK_OK;
 }

@@ -182,66 +182,90 @@ __global__ __launch_bounds__(64) void k_trace_schnorr_hash(TxWitnessDev w, fp *_
 
 // ---------------------------------------------------------------------------------------------------
 // Curve ladders.  A point operation is a short program of F_p6 products whose operands are small
-// integer combinations of LDS-resident F_p6 "slots"; each product is done by one lane.
+// integer combinations of LDS-resident F_p6 "slots"; each product is done by six lanes.
 struct Term { int8_t slot, coef; };
-struct Instr { int8_t out; Term a[3]; Term b[3]; }; // out < 0: no-op; b[0].coef == 0: linear (no product)
+struct Instr { int8_t out; Term a[4]; Term b; }; // out < 0: no-op; product: a[0] * b; linear: a[0] + a[1] + a[2] + a[3]
 
-enum { SX = 0, SY = 1, SZ = 2, SB3 = 3, SPX = 4, SPY = 5, QX = 27, QY = 28, QZ = 29, NSLOT = 30 };
-enum { OP_DOUBLE = 0, OP_ADD_MIXED = 1, OP_ADD_FULL = 2, NPHASE = 6, NROLE = 6 };
-#define NOP {-1, {{0, 0}, {0, 0}, {0, 0}}, {{0, 0}, {0, 0}, {0, 0}}}
-#define T1(s, c) {{s, c}, {0, 0}, {0, 0}}
-#define T2(s, c, s2, c2) {{s, c}, {s2, c2}, {0, 0}}
-#define T3(s, c, s2, c2, s3, c3) {{s, c}, {s2, c2}, {s3, c3}}
-#define NONE {{0, 0}, {0, 0}, {0, 0}}
-#define NOPS6 {NOP, NOP, NOP, NOP, NOP, NOP}
-// Product phases take single-slot operands (optionally scaled by a small integer); every other operand is
-// materialised by a preceding linear phase, so that no lane recomputes a combination another lane also needs.
+// slots 6..26 are scratch of the programs; QX..QZ: the second point of the complete addition (k_trace_schnorr_final);
+// SW, SK, SK2: the ladders' fourth coordinate W = b3*Z and the per-ladder constants b3*qx, b3*qy
+enum { SX = 0, SY = 1, SZ = 2, SB3 = 3, SPX = 4, SPY = 5, QX = 27, QY = 28, QZ = 29, SW = 30, SK = 31, SK2 = 32, NSLOT = 33 };
+enum { OP_DOUBLE = 0, OP_ADD_MIXED = 1 };
+enum { LPHASE = 4, LROLE = 10 }; // the two ladder programs: product, linear, product, linear; up to ten products per phase
+enum { FPHASE = 6, FROLE = 6 };  // the complete addition of the final row: three product phases of up to six products
+#define NOP {-1, {{0, 0}, {0, 0}, {0, 0}, {0, 0}}, {0, 0}}
+#define P(out, sa, ca, sb, cb) {out, {{sa, ca}, {0, 0}, {0, 0}, {0, 0}}, {sb, cb}}
+#define L2(out, s, c, s2, c2) {out, {{s, c}, {s2, c2}, {0, 0}, {0, 0}}, {0, 0}}
+#define L3(out, s, c, s2, c2, s3, c3) {out, {{s, c}, {s2, c2}, {s3, c3}, {0, 0}}, {0, 0}}
+#define L4(out, s, c, s2, c2, s3, c3, s4, c4) {out, {{s, c}, {s2, c2}, {s3, c3}, {s4, c4}}, {0, 0}}
+// Product phases take single-slot operands (optionally doubled); every other operand is materialised by a preceding linear
+// phase, so that no lane recomputes a combination another lane also needs.  A phase costs the same whether 6 or 60 lanes work
+// in it, so the ladder programs carry W = b3*Z as a fourth coordinate: every product by the constant b3 of the reference's
+// formulas (b3*Z^2, b3*2XZ; b3*(qx*Z + X), and b3*Z' for the next W) becomes a product by W, or by K = b3*qx, K2 = b3*qy,
+// beside the others, and an operation is two product phases instead of three.  The values are the reference's by
+// distributivity (the arithmetic is exact and every slot holds a reduced element).  Multiples are written as repeated unit
+// terms or doubled operands: a linear phase whose coefficients are all 0, +1, -1 has no multiplication (lincomb2).
 // (the tables exist twice: in constant memory for the kernels, and as constexpr twins from which the linear phases take their
 // compile-time shape -- how many terms a phase uses and which of them only carry coefficients 0, +1, -1)
-#define CS_EC_PROG { \
-    /* OP_DOUBLE: X3 = 2XY(Y^2-2XZ-3bZ^2) - 2YZ(X^2+6bXZ-Z^2), ... (complete doubling, ecc.rs:177-242) */ \
-    {{{6, T1(0, 1), T1(0, 1)}, {7, T1(1, 1), T1(1, 1)}, {8, T1(2, 1), T1(2, 1)}, {9, T1(0, 1), T1(1, 1)}, {10, T1(0, 1), T1(2, 1)}, {11, T1(1, 1), T1(2, 1)}}, \
-     {{12, T1(3, 1), T1(8, 1)}, {13, T1(3, 1), T1(10, 2)}, NOP, NOP, NOP, NOP}, \
-     {{19, T3(7, 1, 10, -2, 12, -1), NONE}, {20, T3(7, 1, 10, 2, 12, 1), NONE}, {21, T3(6, 1, 8, -1, 13, 1), NONE}, {22, T2(6, 3, 8, 1), NONE}, NOP, NOP}, \
-     {{14, T1(19, 1), T1(20, 1)}, {15, T1(9, 2), T1(19, 1)}, {16, T1(22, 1), T1(21, 1)}, {17, T1(11, 2), T1(21, 1)}, {18, T1(11, 2), T1(7, 1)}, NOP}, \
-     {{0, T2(15, 1, 17, -1), NONE}, {1, T2(14, 1, 16, 1), NONE}, {2, T1(18, 4), NONE}, NOP, NOP, NOP}, \
-     NOPS6}, \
-    /* OP_ADD_MIXED with the affine point in slots 4,5 (complete mixed addition, ecc.rs:330-404) */ \
-    {{{6, T1(0, 1), T1(4, 1)}, {7, T1(1, 1), T1(5, 1)}, {8, T1(26, 1), T1(25, 1)}, {9, T1(4, 1), T1(2, 1)}, {10, T1(5, 1), T1(2, 1)}, {11, T1(2, 1), T1(3, 1)}}, \
-     {{19, T2(9, 1, 0, 1), NONE}, NOP, NOP, NOP, NOP, NOP}, \
-     {{12, T1(19, 1), T1(3, 1)}, NOP, NOP, NOP, NOP, NOP}, \
-     {{20, T3(7, 1, 11, -1, 19, -1), NONE}, {21, T3(7, 1, 11, 1, 19, 1), NONE}, {22, T2(6, 3, 2, 1), NONE}, {23, T3(12, 1, 6, 1, 2, -1), NONE}, \
-      {24, T2(10, 1, 1, 1), NONE}, {25, T3(8, 1, 6, -1, 7, -1), NONE}}, \
-     {{13, T1(20, 1), T1(21, 1)}, {14, T1(22, 1), T1(23, 1)}, {15, T1(24, 1), T1(23, 1)}, {16, T1(25, 1), T1(20, 1)}, {17, T1(25, 1), T1(22, 1)}, {18, T1(24, 1), T1(21, 1)}}, \
-     {{0, T2(16, 1, 15, -1), NONE}, {1, T2(13, 1, 14, 1), NONE}, {2, T2(18, 1, 17, 1), NONE}, NOP, NOP, NOP}}, \
-    /* OP_ADD_FULL with the projective point in slots 27..29 (complete addition, ecc.rs:244-328) */ \
-    {{{6, T1(0, 1), T1(27, 1)}, {7, T1(1, 1), T1(28, 1)}, {8, T1(2, 1), T1(29, 1)}, {9, T1(20, 1), T1(21, 1)}, {10, T1(22, 1), T1(23, 1)}, {11, T1(24, 1), T1(25, 1)}}, \
-     {{19, T3(10, 1, 6, -1, 8, -1), NONE}, NOP, NOP, NOP, NOP, NOP}, \
-     {{12, T1(3, 1), T1(8, 1)}, {13, T1(3, 1), T1(19, 1)}, NOP, NOP, NOP, NOP}, \
-     {{20, T3(7, 1, 12, -1, 19, -1), NONE}, {21, T3(7, 1, 12, 1, 19, 1), NONE}, {22, T2(6, 3, 8, 1), NONE}, {23, T3(13, 1, 6, 1, 8, -1), NONE}, \
-      {24, T3(9, 1, 6, -1, 7, -1), NONE}, {25, T3(11, 1, 7, -1, 8, -1), NONE}}, \
-     {{14, T1(20, 1), T1(21, 1)}, {15, T1(22, 1), T1(23, 1)}, {16, T1(25, 1), T1(23, 1)}, {17, T1(24, 1), T1(20, 1)}, {18, T1(24, 1), T1(22, 1)}, {26, T1(25, 1), T1(21, 1)}}, \
-     {{0, T2(17, 1, 16, -1), NONE}, {1, T2(14, 1, 15, 1), NONE}, {2, T2(26, 1, 18, 1), NONE}, NOP, NOP, NOP}}, \
+#define CS_LADDER_PROG { \
+    /* OP_DOUBLE (complete doubling, ecc.rs:177-242): 6..14 = X^2 Y^2 Z^2 XY 2XZ YZ WZ 2XW YW; */ \
+    /* a = Y^2-2XZ-WZ, b = Y^2+2XZ+WZ, c = X^2-Z^2+2XW, d = 3X^2+Z^2; */ \
+    /* X' = 2XY a - 2YZ c, Y' = ab + dc, Z' = 2 (2YZ)(2Y^2), W' = 2 (2YW)(2Y^2) */ \
+    {{P(6, 0, 1, 0, 1), P(7, 1, 1, 1, 1), P(8, 2, 1, 2, 1), P(9, 0, 1, 1, 1), P(10, 0, 2, 2, 1), P(11, 1, 1, 2, 1), P(12, SW, 1, 2, 1), \
+      P(13, 0, 2, SW, 1), P(14, 1, 1, SW, 1), NOP}, \
+     {L3(19, 7, 1, 10, -1, 12, -1), L3(20, 7, 1, 10, 1, 12, 1), L3(21, 6, 1, 8, -1, 13, 1), L4(22, 6, 1, 6, 1, 6, 1, 8, 1), NOP, NOP, NOP, NOP, NOP, NOP}, \
+     {P(15, 19, 1, 20, 1), P(16, 9, 2, 19, 1), P(17, 22, 1, 21, 1), P(18, 11, 2, 21, 1), P(23, 11, 2, 7, 2), P(24, 14, 2, 7, 2), NOP, NOP, NOP, NOP}, \
+     {L2(0, 16, 1, 18, -1), L2(1, 15, 1, 17, 1), L2(2, 23, 1, 23, 1), L2(SW, 24, 1, 24, 1), NOP, NOP, NOP, NOP, NOP, NOP}}, \
+    /* OP_ADD_MIXED with the affine point (qx, qy) in slots 4, 5 (complete mixed addition, ecc.rs:330-404): */ \
+    /* 6..15 = t0 = X qx, t1 = Y qy, (qx+qy)(X+Y), qx Z, qy Z, K Z, b3 X, K2 Z, b3 Y, K X; */ \
+    /* 19 x3 = t1-W-qxZ-X, 20 z3 = t1+W+qxZ+X, 21 t1' = 3t0+Z, 22 t4' = KZ+b3X+t0-Z, 23 t5 = qyZ+Y, 24 t3, 16 u = b3 t5, 17 v = b3 t1'; */ \
+    /* X' = t3 x3 - t5 t4', Y' = x3 z3 + t1' t4', Z' = t5 z3 + t3 t1', W' = u z3 + t3 v */ \
+    {{P(6, 0, 1, 4, 1), P(7, 1, 1, 5, 1), P(8, 26, 1, 25, 1), P(9, 4, 1, 2, 1), P(10, 5, 1, 2, 1), P(11, SK, 1, 2, 1), P(12, 3, 1, 0, 1), \
+      P(13, SK2, 1, 2, 1), P(14, 3, 1, 1, 1), P(15, SK, 1, 0, 1)}, \
+     {L4(19, 7, 1, SW, -1, 9, -1, 0, -1), L4(20, 7, 1, SW, 1, 9, 1, 0, 1), L4(21, 6, 1, 6, 1, 6, 1, 2, 1), L4(22, 11, 1, 12, 1, 6, 1, 2, -1), \
+      L2(23, 10, 1, 1, 1), L3(24, 8, 1, 6, -1, 7, -1), L2(16, 13, 1, 14, 1), L4(17, 15, 1, 15, 1, 15, 1, SW, 1), NOP, NOP}, \
+     {P(6, 19, 1, 20, 1), P(7, 21, 1, 22, 1), P(8, 23, 1, 22, 1), P(9, 24, 1, 19, 1), P(10, 24, 1, 21, 1), P(11, 23, 1, 20, 1), P(12, 16, 1, 20, 1), \
+      P(13, 24, 1, 17, 1), NOP, NOP}, \
+     {L2(0, 9, 1, 8, -1), L2(1, 6, 1, 7, 1), L2(2, 11, 1, 10, 1), L2(SW, 12, 1, 13, 1), NOP, NOP, NOP, NOP, NOP, NOP}}, \
 }
-// operand sums that feed the first product phase of the additions (a "phase -1" run before the program):
-//   mixed: 26 = x2 + y2 (constant per ladder, set once), 25 = X + Y;  full: 20..25 = X1+Y1, X2+Y2, X1+Z1, X2+Z2, Y1+Z1, Y2+Z2
-#define CS_EC_PRE { \
-    NOPS6, \
-    {{25, T2(0, 1, 1, 1), NONE}, NOP, NOP, NOP, NOP, NOP}, \
-    {{20, T2(0, 1, 1, 1), NONE}, {21, T2(27, 1, 28, 1), NONE}, {22, T2(0, 1, 2, 1), NONE}, {23, T2(27, 1, 29, 1), NONE}, {24, T2(1, 1, 2, 1), NONE}, {25, T2(28, 1, 29, 1), NONE}}, \
+// operand sum that feeds the first product phase of the mixed addition (a "phase -1" run before the program): 25 = X + Y
+// (26 = qx + qy is constant per ladder and set once)
+#define CS_LADDER_PRE {L2(25, 0, 1, 1, 1)}
+// The complete addition with the projective point in slots 27..29 (ecc.rs:244-328), one per transaction in k_trace_schnorr_final:
+// X3 = ..., with the two products by b3 in a phase of their own.  "Phase -1": 20..25 = X1+Y1, X2+Y2, X1+Z1, X2+Z2, Y1+Z1, Y2+Z2
+#define CS_FULL_PROG { \
+    {P(6, 0, 1, 27, 1), P(7, 1, 1, 28, 1), P(8, 2, 1, 29, 1), P(9, 20, 1, 21, 1), P(10, 22, 1, 23, 1), P(11, 24, 1, 25, 1)}, \
+    {L3(19, 10, 1, 6, -1, 8, -1), NOP, NOP, NOP, NOP, NOP}, \
+    {P(12, 3, 1, 8, 1), P(13, 3, 1, 19, 1), NOP, NOP, NOP, NOP}, \
+    {L3(20, 7, 1, 12, -1, 19, -1), L3(21, 7, 1, 12, 1, 19, 1), L2(22, 6, 3, 8, 1), L3(23, 13, 1, 6, 1, 8, -1), L3(24, 9, 1, 6, -1, 7, -1), \
+     L3(25, 11, 1, 7, -1, 8, -1)}, \
+    {P(14, 20, 1, 21, 1), P(15, 22, 1, 23, 1), P(16, 25, 1, 23, 1), P(17, 24, 1, 20, 1), P(18, 24, 1, 22, 1), P(26, 25, 1, 21, 1)}, \
+    {L2(0, 17, 1, 16, -1), L2(1, 14, 1, 15, 1), L2(2, 26, 1, 18, 1), NOP, NOP, NOP}, \
 }
-__constant__ Instr c_prog[3][NPHASE][NROLE] = CS_EC_PROG;
-__constant__ Instr c_pre[3][NROLE] = CS_EC_PRE;
-constexpr Instr k_prog[3][NPHASE][NROLE] = CS_EC_PROG;
-constexpr Instr k_pre[3][NROLE] = CS_EC_PRE;
-#undef CS_EC_PROG
-#undef CS_EC_PRE
+#define CS_FULL_PRE {L2(20, 0, 1, 1, 1), L2(21, 27, 1, 28, 1), L2(22, 0, 1, 2, 1), L2(23, 27, 1, 29, 1), L2(24, 1, 1, 2, 1), L2(25, 28, 1, 29, 1)}
+__constant__ Instr c_lprog[2][LPHASE][LROLE] = CS_LADDER_PROG;
+__constant__ Instr c_lpre[1] = CS_LADDER_PRE;
+__constant__ Instr c_fprog[FPHASE][FROLE] = CS_FULL_PROG;
+__constant__ Instr c_fpre[FROLE] = CS_FULL_PRE;
+constexpr Instr k_lprog[2][LPHASE][LROLE] = CS_LADDER_PROG;
+constexpr Instr k_lpre[1] = CS_LADDER_PRE;
+constexpr Instr k_fprog[FPHASE][FROLE] = CS_FULL_PROG;
+constexpr Instr k_fpre[FROLE] = CS_FULL_PRE;
+#undef CS_LADDER_PROG
+#undef CS_LADDER_PRE
+#undef CS_FULL_PROG
+#undef CS_FULL_PRE
+#undef NOP
+#undef P
+#undef L2
+#undef L3
+#undef L4
 // shape of a linear phase: (number of leading terms any instruction uses) | (bit 4 + k set: term k only has coefficients 0, 1, -1)
-constexpr int lin_shape(const Instr (&ph)[NROLE]) {
-    int nt = 0, unit = 7;
-    for (int m = 0; m < NROLE; m++) {
+template <int NR>
+constexpr int lin_shape(const Instr (&ph)[NR]) {
+    int nt = 0, unit = 15;
+    for (int m = 0; m < NR; m++) {
         if (ph[m].out < 0) continue;
-        for (int k = 0; k < 3; k++) {
+        for (int k = 0; k < 4; k++) {
             const int c = ph[m].a[k].coef;
             if (c != 0 && k + 1 > nt) nt = k + 1;
             if (c < -1 || c > 1) unit &= ~(1 << k);
@@ -249,25 +273,26 @@ constexpr int lin_shape(const Instr (&ph)[NROLE]) {
     }
     return nt | (unit << 4);
 }
-#undef NOP
-#undef T1
-#undef T2
-#undef T3
-#undef NONE
-#undef NOPS6
+constexpr bool lin_shape_unit(int shape) { return (shape >> 4) == 15; }
 
-// phase kinds of the three programs, known at compile time: 1 product phase, 0 linear phase, -1 end
-constexpr int8_t PHASE_KIND[3][NPHASE] = {{1, 1, 0, 1, 0, -1}, {1, 0, 1, 0, 1, 0}, {1, 0, 1, 0, 1, 0}};
-// the programs live in LDS while a ladder runs: every lane fetches its own instruction each phase, and a divergent read
-// of __constant__ memory is a vector load with global-memory latency.  small[c + 4] = the field element c for |c| <= 4:
-// integer coefficients are applied as one multiplication, the same code for every lane (a switch over the coefficient
-// would run all of its cases serially in a wave whose lanes hold different instructions).
-struct ProgLds { Instr prog[3][NPHASE][NROLE]; Instr pre[3][NROLE]; fp small[9]; };
-__device__ __forceinline__ void load_programs(ProgLds &p, int tid, int nthreads) {
-    Instr *dst = &p.prog[0][0][0];
-    const Instr *src = &c_prog[0][0][0];
-    for (int i = tid; i < 3 * NPHASE * NROLE; i += nthreads) dst[i] = src[i];
-    for (int i = tid; i < 3 * NROLE; i += nthreads) (&p.pre[0][0])[i] = (&c_pre[0][0])[i];
+// The programs live in LDS while a kernel runs: every lane fetches its own instruction each phase, and a divergent read
+// of __constant__ memory is a vector load with global-memory latency.  A ladder holds its two programs only (0.9 KB: eight
+// ladders share a CU's LDS with the transform workgroups), the final row's kernel the complete addition.
+// small[c + 4] = the field element c for |c| <= 4: integer coefficients other than 0, +1, -1 are applied as one multiplication,
+// the same code for every lane (a switch over the coefficient would run all of its cases serially in a wave whose lanes hold
+// different instructions).  Only the complete addition has such a coefficient.
+struct LadderLds { Instr prog[2][LPHASE][LROLE]; Instr pre[1]; };
+struct FullLds { Instr prog[FPHASE][FROLE]; Instr pre[FROLE]; fp small[9]; };
+__device__ __forceinline__ void copy_program(Instr *dst, const Instr *src, int count, int tid, int nthreads) {
+    for (int i = tid; i < count; i += nthreads) dst[i] = src[i];
+}
+__device__ __forceinline__ void load_programs(LadderLds &p, int tid, int nthreads) {
+    copy_program(&p.prog[0][0][0], &c_lprog[0][0][0], 2 * LPHASE * LROLE, tid, nthreads);
+    copy_program(p.pre, c_lpre, 1, tid, nthreads);
+}
+__device__ __forceinline__ void load_programs(FullLds &p, int tid, int nthreads) {
+    copy_program(&p.prog[0][0], &c_fprog[0][0], FPHASE * FROLE, tid, nthreads);
+    copy_program(p.pre, c_fpre, FROLE, tid, nthreads);
     if (tid < 9) {
         const int c = tid - 4;
         const fp m = fp_mul((uint64_t)(c < 0 ? -c : c), FP_R2); // |c| in Montgomery form
@@ -278,9 +303,9 @@ __device__ __forceinline__ void load_programs(ProgLds &p, int tid, int nthreads)
 // F_p2 component `comp` (0..2) of an integer combination of slots.  SHAPE (lin_shape): only the terms the phase uses are walked, and a
 // term whose coefficients are all 0 / +1 / -1 is a conditional negation instead of a product (a product by a small constant costs 52
 // issue cycles per component, the negation and selects about 20); other coefficients are applied as one multiplication, the same
-// code for every lane.
+// code for every lane (`small` is not read by a phase whose terms are all of the first kind).
 template <int SHAPE>
-__device__ __forceinline__ Fp2 lincomb2(const fp (*slot)[6], const Term (&t)[3], int comp, const fp *small) {
+__device__ __forceinline__ Fp2 lincomb2(const fp (*slot)[6], const Term (&t)[4], int comp, const fp *small) {
     Fp2 r = {0, 0};
 #pragma unroll
     for (int k = 0; k < (SHAPE & 15); k++) { // unused terms have coefficient 0 (and slot 0): they add 0
@@ -309,17 +334,18 @@ __device__ __forceinline__ Fp2 operand2(const fp (*slot)[6], const Term t, int c
     return v;
 }
 
-// Runs program `op` on the slots of one point with the 64 lanes of one wave:
+// One phase of a program of NR instructions on the slots of one point, with the 64 lanes of one wave:
 //   product phase  lane (m, q), q < 6: the q-th Karatsuba F_p2 product of instruction m  (3 base products per lane)
 //   recombination  lane (m, r), r < 3: F_p2 coefficient r of the F_p6 result of instruction m
 //   linear phase   lane (m, r): coefficient r of an integer combination of slots
-// Called by all lanes of the workgroup (barriers inside).  prod = this point's [6][6] F_p2 scratch.
-template <int SHAPE>
-__device__ __forceinline__ void run_linear_phase(const Instr (&prog)[NROLE], const fp *small, fp (*slot)[6], int lane, bool enabled) {
+// Called by all lanes of the workgroup (barriers inside).  prod = this point's [NR][6] F_p2 scratch.
+template <int NR, int SHAPE>
+__device__ __forceinline__ void run_linear_phase(const Instr *prog, const fp *small, fp (*slot)[6], int lane) {
+    static_assert(3 * NR <= 64, "one lane per F_p2 coefficient");
     const int m = lane / 3, r = lane % 3;
     Fp2 c = {0, 0};
     int out = -1;
-    if (enabled && m < NROLE) {
+    if (m < NR) {
         const Instr ins = prog[m];
         out = ins.out;
         if (out >= 0) c = lincomb2<SHAPE>(slot, ins.a, r, small);
@@ -329,57 +355,79 @@ __device__ __forceinline__ void run_linear_phase(const Instr (&prog)[NROLE], con
     __syncthreads();
 }
 
-template <int OP, int PH>
-__device__ __forceinline__ void run_phases(const ProgLds &pg, fp (*slot)[6], Fp2 (*prod)[6], int lane, bool enabled) {
-    if constexpr (PH < NPHASE) {
-        if constexpr (PHASE_KIND[OP][PH] >= 0) {
-            if constexpr (PHASE_KIND[OP][PH] == 1) {
-                const int m = lane / 6, q = lane % 6;
-                if (enabled && m < NROLE) {
-                    const Instr ins = pg.prog[OP][PH][m];
-                    if (ins.out >= 0) {
-                        const int c1 = q < 3 ? q : (q == 5 ? 1 : 0), c2 = q < 3 ? -1 : (q == 3 ? 1 : 2);
-                        prod[m][q] = fp2_mul(operand2(slot, ins.a[0], c1, c2), operand2(slot, ins.b[0], c1, c2));
-                    }
-                }
-                __syncthreads();
-                const int m2 = lane / 3, r = lane % 3;
-                if (enabled && m2 < NROLE) {
-                    const int out = pg.prog[OP][PH][m2].out;
-                    if (out >= 0) {
-                        // r = 0: d0 + d1 + d2 - e12;  r = 1: e01 - e12 - d0;  r = 2: e02 + d1 - d0 - 2 d2.  One five-term form
-                        // t1 + t2 + t3 - t4 - t5 with the operands selected per lane: the three cases as branches would run one after
-                        // the other in the wave (nine F_p2 additions instead of six).
-                        const Fp2 zero = {0, 0};
-                        const Fp2 d0 = prod[m2][0], d1 = prod[m2][1], d2 = prod[m2][2];
-                        const Fp2 t1 = r == 0 ? d0 : prod[m2][r + 2];        // d0 | e01 | e02
-                        const Fp2 t2 = r == 1 ? zero : d1;
-                        const Fp2 t3 = r == 0 ? d2 : zero;
-                        const Fp2 t4 = r == 2 ? d0 : prod[m2][5];            // e12 | e12 | d0
-                        const Fp2 t5 = r == 0 ? zero : (r == 1 ? d0 : fp2_dbl(d2));
-                        const Fp2 c = fp2_sub(fp2_sub(fp2_add(fp2_add(t1, t2), t3), t4), t5);
-                        slot[out][2 * r] = c.a;
-                        slot[out][2 * r + 1] = c.b;
-                    }
-                }
-                __syncthreads();
-            } else {
-                run_linear_phase<lin_shape(k_prog[OP][PH])>(pg.prog[OP][PH], pg.small, slot, lane, enabled);
-            }
-            run_phases<OP, PH + 1>(pg, slot, prod, lane, enabled);
+template <int NR>
+__device__ __forceinline__ void run_product_phase(const Instr *prog, fp (*slot)[6], Fp2 (*prod)[6], int lane) {
+    static_assert(6 * NR <= 64, "one lane per F_p2 product");
+    const int m = lane / 6, q = lane % 6;
+    if (m < NR) {
+        const Instr ins = prog[m];
+        if (ins.out >= 0) {
+            const int c1 = q < 3 ? q : (q == 5 ? 1 : 0), c2 = q < 3 ? -1 : (q == 3 ? 1 : 2);
+            prod[m][q] = fp2_mul(operand2(slot, ins.a[0], c1, c2), operand2(slot, ins.b, c1, c2));
         }
+    }
+    __syncthreads();
+    const int m2 = lane / 3, r = lane % 3;
+    if (m2 < NR) {
+        const int out = prog[m2].out;
+        if (out >= 0) {
+            // r = 0: d0 + d1 + d2 - e12;  r = 1: e01 - e12 - d0;  r = 2: e02 + d1 - d0 - 2 d2.  One five-term form
+            // t1 + t2 + t3 - t4 - t5 with the operands selected per lane: the three cases as branches would run one after
+            // the other in the wave (nine F_p2 additions instead of six).
+            const Fp2 zero = {0, 0};
+            const Fp2 d0 = prod[m2][0], d1 = prod[m2][1], d2 = prod[m2][2];
+            const Fp2 t1 = r == 0 ? d0 : prod[m2][r + 2];        // d0 | e01 | e02
+            const Fp2 t2 = r == 1 ? zero : d1;
+            const Fp2 t3 = r == 0 ? d2 : zero;
+            const Fp2 t4 = r == 2 ? d0 : prod[m2][5];            // e12 | e12 | d0
+            const Fp2 t5 = r == 0 ? zero : (r == 1 ? d0 : fp2_dbl(d2));
+            const Fp2 c = fp2_sub(fp2_sub(fp2_add(fp2_add(t1, t2), t3), t4), t5);
+            slot[out][2 * r] = c.a;
+            slot[out][2 * r + 1] = c.b;
+        }
+    }
+    __syncthreads();
+}
+
+// even phases of a program are product phases, odd ones linear
+template <int OP, int PH = 0>
+__device__ __forceinline__ void run_ladder_phases(const LadderLds &pg, fp (*slot)[6], Fp2 (*prod)[6], int lane) {
+    if constexpr (PH < LPHASE) {
+        if constexpr ((PH & 1) == 0) {
+            run_product_phase<LROLE>(pg.prog[OP][PH], slot, prod, lane);
+        } else {
+            constexpr int shape = lin_shape(k_lprog[OP][PH]);
+            static_assert(lin_shape_unit(shape), "the ladder programs carry no table of small multiples");
+            run_linear_phase<LROLE, shape>(pg.prog[OP][PH], nullptr, slot, lane);
+        }
+        run_ladder_phases<OP, PH + 1>(pg, slot, prod, lane);
     }
 }
 template <int OP>
-__device__ __forceinline__ void run_point_op(const ProgLds &pg, fp (*slot)[6], Fp2 (*prod)[6], int lane, bool enabled) {
-    if constexpr (OP != OP_DOUBLE) run_linear_phase<lin_shape(k_pre[OP])>(pg.pre[OP], pg.small, slot, lane, enabled);
-    run_phases<OP, 0>(pg, slot, prod, lane, enabled);
+__device__ __forceinline__ void run_ladder_op(const LadderLds &pg, fp (*slot)[6], Fp2 (*prod)[6], int lane) {
+    if constexpr (OP == OP_ADD_MIXED) {
+        static_assert(lin_shape_unit(lin_shape(k_lpre)), "the ladder programs carry no table of small multiples");
+        run_linear_phase<1, lin_shape(k_lpre)>(pg.pre, nullptr, slot, lane);
+    }
+    run_ladder_phases<OP>(pg, slot, prod, lane);
+}
+template <int PH = 0>
+__device__ __forceinline__ void run_full_phases(const FullLds &pg, fp (*slot)[6], Fp2 (*prod)[6], int lane) {
+    if constexpr (PH < FPHASE) {
+        if constexpr ((PH & 1) == 0) run_product_phase<FROLE>(pg.prog[PH], slot, prod, lane);
+        else run_linear_phase<FROLE, lin_shape(k_fprog[PH])>(pg.prog[PH], pg.small, slot, lane);
+        run_full_phases<PH + 1>(pg, slot, prod, lane);
+    }
+}
+__device__ __forceinline__ void run_full_add(const FullLds &pg, fp (*slot)[6], Fp2 (*prod)[6], int lane) {
+    run_linear_phase<FROLE, lin_shape(k_fpre)>(pg.pre, pg.small, slot, lane);
+    run_full_phases(pg, slot, prod, lane);
 }
 
 __device__ __forceinline__ int bit_le(const uint8_t *bytes, int i) { return (bytes[i >> 3] >> (i & 7)) & 1; }
 
 // grid = 2 * n_tx workgroups of ONE wave: workgroup 2t is the ladder s*G of transaction t (registers 0..17), 2t+1 the ladder
-// h*P (registers 19..36).  With a single wave per workgroup the phase barriers of run_point_op cost nothing and the two
+// h*P (registers 19..36).  With a single wave per workgroup the phase barriers of run_ladder_op cost nothing and the two
 // ladders of a transaction never wait for each other; 2 * n_tx independent waves keep every SIMD busy with two of them.
 // The last step (S += h*P, X <- X/Z) needs both ladders: k_trace_schnorr_final, below.
 // TR = rows of the staging tile (rows per flush).  64 is the fastest alone (3.99 ms of trace generation against 5.77 ms with 16);
@@ -391,9 +439,9 @@ __global__ __launch_bounds__(64) void k_trace_schnorr_ec(TxWitnessDev w, fp *__r
     constexpr int TG = 64 / TR; // column groups of a flush
     __shared__ fp tile[TR][19];
     __shared__ fp slots[NSLOT][6];
-    __shared__ Fp2 prods[6][6];
+    __shared__ Fp2 prods[LROLE][6];
     __shared__ uint8_t sbytes[32];
-    __shared__ ProgLds pg;
+    __shared__ LadderLds pg;
     const int t = blockIdx.x >> 1, g = blockIdx.x & 1, lane = threadIdx.x;
     fp(*slot)[6] = slots;
     load_programs(pg, lane, 64);
@@ -409,7 +457,11 @@ __global__ __launch_bounds__(64) void k_trace_schnorr_ec(TxWitnessDev w, fp *__r
         slot[SPX][lane] = g == 0 ? c_generator[lane] : w.s_old[14 * (size_t)t + lane];
         slot[SPY][lane] = g == 0 ? c_generator[6 + lane] : w.s_old[14 * (size_t)t + 6 + lane];
         slot[26][lane] = fp_add(slot[SPX][lane], slot[SPY][lane]); // x2 + y2, operand of the mixed addition
+        slot[SW][lane] = 0;                                        // W = b3 * Z
     }
+    __syncthreads();
+    // K = b3 * qx, K2 = b3 * qy: once per ladder
+    if (lane < 2) fp6_store(slot[SK + lane], fp6_mul(fp6_load(slot[SB3]), fp6_load(slot[SPX + lane])));
     __syncthreads();
     if (lane < 18) tile[0][lane] = slot[lane / 6][lane % 6];
     const size_t gbase = STANDALONE ? (size_t)t * MERKLE_LEN : (size_t)t * TXC + MERKLE_LEN;
@@ -417,10 +469,10 @@ __global__ __launch_bounds__(64) void k_trace_schnorr_ec(TxWitnessDev w, fp *__r
     for (int step = 0; step < MERKLE_LEN - 1; step++) {
         if (step < SCALAR_MUL_LEN) {
             if ((step & 1) == 0) {
-                run_point_op<OP_DOUBLE>(pg, slot, prods, lane, true);
+                run_ladder_op<OP_DOUBLE>(pg, slot, prods, lane);
             } else {
                 const int bit = bit_le(sbytes, 254 - (step >> 1)); // MSB first, src/schnorr/trace.rs:79-82
-                if (bit) run_point_op<OP_ADD_MIXED>(pg, slot, prods, lane, true); // uniform over the wave
+                if (bit) run_ladder_op<OP_ADD_MIXED>(pg, slot, prods, lane); // uniform over the wave
             }
         } // step == SCALAR_MUL_LEN: the row is a copy here; k_trace_schnorr_final rewrites registers 0..17 of it
         const int r = (step + 1) & (TR - 1);
@@ -436,9 +488,9 @@ __global__ __launch_bounds__(64) void k_trace_schnorr_ec(TxWitnessDev w, fp *__r
 // One wave per transaction; reads both ladders' results from the row before.
 template <bool STANDALONE>
 __global__ __launch_bounds__(64) void k_trace_schnorr_final(fp *__restrict__ trace, size_t n) {
-    __shared__ fp slots[NSLOT][6];
-    __shared__ Fp2 prods[6][6];
-    __shared__ ProgLds pg;
+    __shared__ fp slots[QZ + 1][6];
+    __shared__ Fp2 prods[FROLE][6];
+    __shared__ FullLds pg;
     const int t = blockIdx.x, lane = threadIdx.x;
     load_programs(pg, lane, 64);
     const size_t last = (STANDALONE ? (size_t)t * MERKLE_LEN : (size_t)t * TXC + MERKLE_LEN) + MERKLE_LEN - 1;
@@ -448,7 +500,7 @@ __global__ __launch_bounds__(64) void k_trace_schnorr_final(fp *__restrict__ tra
     }
     if (lane < 6) slots[SB3][lane] = c_b3[lane];
     __syncthreads();
-    run_point_op<OP_ADD_FULL>(pg, slots, prods, lane, true);
+    run_full_add(pg, slots, prods, lane);
     if (lane == 0) fp6_store(slots[SX], fp6_mul(fp6_load(slots[SX]), fp6_inv(fp6_load(slots[SZ]))));
     __syncthreads();
     if (lane < 18) trace[(size_t)lane * n + last] = slots[lane / 6][lane % 6];

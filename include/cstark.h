@@ -138,6 +138,10 @@ int cstark_lde_columns(cstark_ctx *ctx, const uint64_t *d_coeffs, uint64_t *d_ld
  * through the two calls above (and their part of d_evals is destroyed). */
 int cstark_step_columns(cstark_ctx *ctx, uint64_t *d_evals, uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols,
                         uint32_t log_n, uint32_t block_len, uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk);
+/* The same for columns with two values per block: one on rows [0, split) of every block and another on rows [split, block_len),
+ * 0 < split < block_len.  On the shapes named above rows 0 and split of every block are read. */
+int cstark_step2_columns(cstark_ctx *ctx, uint64_t *d_evals, uint64_t *d_coeffs, uint64_t *d_lde, uint32_t width, uint32_t col0, uint32_t ncols,
+                         uint32_t log_n, uint32_t block_len, uint32_t split, uint32_t log_blowup, uint64_t domain_offset, uint32_t k0, uint32_t nk);
 
 /* FieldExtension::Quadratic / Cubic: the same three stages over the degree-m extension, m = 2: F_p[u]/(u^2 - 2u - 2), m = 3:
  * F_p[v]/(v^3 + v + 1) [assumption: the two polynomials of the reference's own curve tower, src/utils/ecc.rs:407-648; the fork's
