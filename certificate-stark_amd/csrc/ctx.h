@@ -72,6 +72,11 @@ inline int fail(int code, const char *fmt, const char *detail = "") {
         if (rc_) return rc_;    \
     } while (0)
 
+// internal (prove.hip): the proof-of-work search on the device, chunks [1 + k chunk, 1 + (k + 1) chunk) in increasing k until one holds
+// a nonce whose digest with `seed` (host memory) has `bits` low zero bits; the smallest such nonce -> *nonce_out.  d_found: 5 device
+// words (the minimum, then the seed for the Sha3 coin).  The prover's grind_nonce calls it with chunks of 2^22.
+int grind_search(hipStream_t stream, unsigned long long *d_found, const uint8_t seed[32], uint32_t hash_fn, unsigned bits, uint64_t chunk, uint64_t *nonce_out);
+
 struct NttPlan {
     unsigned log_n;
     uint64_t *w, *winv; // [n] each: powers of w_n and of its inverse

@@ -453,17 +453,21 @@ int grind_nonce(cstark_ctx *c, ProveArena *a, const Coin &coin, unsigned bits, u
     }
     unsigned long long *d_found; // [found | seed (Sha3 coin: read from device memory)]
     RC_TRY(arena_extra(c, a, 42, &d_found, 64));
-    constexpr uint64_t CHUNK = (uint64_t)1 << 22;
-    if (coin.hash_fn == 1) {
-        HIP_TRY(hipMemcpyAsync(d_found + 1, coin.seed, 32, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemsetAsync(d_found, 0xFF, 8, c->stream));
+    return grind_search(c->stream, d_found, coin.seed, coin.hash_fn, bits, (uint64_t)1 << 22, nonce_out);
+}
+// the device search of grind_nonce: chunks of `chunk` nonces from 1 on until one holds a hit (ctx.h)
+int grind_search(hipStream_t stream, unsigned long long *d_found, const uint8_t seed[32], uint32_t hash_fn, unsigned bits, uint64_t chunk, uint64_t *nonce_out) {
+    if (chunk == 0) return fail(CSTARK_ERR_INVALID_ARG, "proof of work: empty chunk");
+    if (hash_fn == 1) {
+        HIP_TRY(hipMemcpyAsync(d_found + 1, seed, 32, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemsetAsync(d_found, 0xFF, 8, stream));
     }
-    for (uint64_t base = 1;; base += CHUNK) {
-        if (coin.hash_fn == 1) HIP_TRY(cs::grind_batch_chunk_sha3((const uint64_t *)(d_found + 1), 1, base, CHUNK, bits, d_found, c->stream));
-        else HIP_TRY(cs::grind_chunk(coin.seed, base, CHUNK, bits, d_found, c->stream));
+    for (uint64_t base = 1;; base += chunk) {
+        if (hash_fn == 1) HIP_TRY(cs::grind_batch_chunk_sha3((const uint64_t *)(d_found + 1), 1, base, chunk, bits, d_found, stream));
+        else HIP_TRY(cs::grind_chunk(seed, base, chunk, bits, d_found, stream));
         unsigned long long found = 0;
-        HIP_TRY(hipMemcpyAsync(&found, d_found, 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(cs::stream_wait(c->stream));
+        HIP_TRY(hipMemcpyAsync(&found, d_found, 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(cs::stream_wait(stream));
         if (found != ~0ull) { *nonce_out = found; return CSTARK_OK; }
         if (base > ((uint64_t)1 << 44)) return fail(CSTARK_ERR_HIP, "proof of work: no nonce found"); // 2^-(2^12) to get here at 32 bits
     }
