@@ -444,7 +444,10 @@ int cstark_schnorr_witness_generate(uint32_t n_sig, uint64_t seed, uint64_t *mes
  * context, a word that is no reduced field element) is CSTARK_ERR_INVALID_ARG.  After a HIP failure inside a ledger call the ledger is
  * unusable: every later call on it returns CSTARK_ERR_HIP. */
 typedef struct cstark_ledger cstark_ledger;
-/* why cstark_ledger_apply refused a batch; the first matching reason in this order */
+/* why cstark_ledger_apply refused a batch.  Transfers are examined in transfer order, each against the accounts as the transfers before
+ * it in the same batch leave them; the batch is refused at the first transfer that matches a reason, with the first reason in this
+ * order that this transfer matches: either index out of range, then sender equals receiver, then either account absent, then the
+ * balance. */
 typedef enum cstark_ledger_reason {
     CSTARK_LEDGER_APPLIED = 0,
     CSTARK_LEDGER_INDEX_RANGE = 1,  /* an index >= 2^merkle_depth */

@@ -1,7 +1,8 @@
 // csrc/ledger_plan.h alone under g++ (host code only): the plans of the account ledger are executed here with the host `merge`
 // (hostgadgets.h) over a host pool, exactly as the device executes them -- upload block, one pass per launch, emit lists -- and every
-// witness array is compared with a case written by tests/test_ledger_cpu.py (flat little-endian 64-bit words, see read_case).
-//   ledger_plan_check CASE          all checks
+// witness array is compared with a case written by tests/ledger_cases.py (flat little-endian 64-bit words, see read_case).
+//   ledger_plan_check CASE          all checks; a case that ends in the pair (refused_at, reason) is a batch the plan must refuse there
+//                                   (expect_refused_batch), any other case a batch it must apply
 //   ledger_plan_check CASE --time   additionally: seconds the job lists of the whole batch take on this CPU (tools/bench_ledger.py)
 #include <stdio.h>
 #include <stdlib.h>
@@ -30,6 +31,9 @@ struct Case {
     uint32_t depth, n_acc, n_tx;
     uint64_t absent; // an index without an account, UINT64_MAX when every leaf has one
     Words acc_idx, acc_val, final_val, initial_roots, final_root, s_old, r_old, s_idx, r_idx, s_paths, r_paths, deltas;
+    bool refusal = false; // the case ends in a pair of words: the plan must refuse the batch at transfer `refused_at` for `reason`
+    uint32_t refused_at = 0;
+    int32_t reason = REASON_NONE;
 };
 
 static bool read_case(const char *path, Case &c) {
@@ -47,8 +51,11 @@ static bool read_case(const char *path, Case &c) {
         p.w->resize(p.len);
         if (p.len && fread(p.w->data(), 8, p.len, f) != p.len) ok = false;
     }
-    uint64_t extra;
-    if (fread(&extra, 8, 1, f) != 0) ok = false; // trailing words
+    uint64_t extra[3];
+    const size_t trailing = fread(extra, 8, 3, f); // none, or the expected refusal
+    if (trailing == 2 && extra[0] < c.n_tx && extra[1] >= REASON_INDEX && extra[1] <= REASON_BALANCE) {
+        c.refusal = true; c.refused_at = (uint32_t)extra[0]; c.reason = (int32_t)extra[1];
+    } else if (trailing != 0) ok = false;
     fclose(f);
     return ok;
 }
@@ -148,11 +155,37 @@ static void expect_refusal(const Ledger &L, const Case &c, uint32_t at, Words s,
     CHECK(p.jobs.empty() && p.witness.empty() && p.commit.empty() && p.new_nodes.empty() && p.new_values.empty(), "%s: a refused plan carries work", what);
 }
 
+// A case with an expected refusal: the arrays describe transfers [0, refused_at) only (initial_roots[refused_at] is the root they
+// leave, final_val the accounts they leave).  The whole batch must be refused at that transfer for that reason without a change to the
+// index; the ledger then applies the valid prefix.
+static int expect_refused_batch(const Case &c) {
+    const uint32_t d = c.depth, n = c.n_tx, na = c.n_acc, at = c.refused_at;
+    Ledger L(d, (na + 4 * n) * (d + 1) + 16);
+    CHECK(L.set_accounts(na, c.acc_idx.data(), c.acc_val.data()), "set_accounts");
+    CHECK(same(L.root(), c.initial_roots.data(), 7), "the root after set_accounts is not initial_roots[0]");
+    const Index before = L.ix;
+    const Words pool_before = L.pool;
+    expect_refusal(L, c, at, c.s_idx, c.r_idx, c.deltas, c.reason, "the steered batch");
+    CHECK(L.ix.depth == before.depth && L.ix.n_stored == before.n_stored && L.ix.node == before.node && L.ix.accounts == before.accounts,
+          "a refused plan changed the index");
+    CHECK(L.pool == pool_before, "a refused plan changed the pool");
+    size_t merges = 0;
+    if (at > 0) merges = apply_and_compare(L, c, 0, at, "the valid prefix");
+    for (uint32_t i = 0; i < na; i++) {
+        const auto it = L.ix.accounts.find(c.acc_idx[i]);
+        CHECK(it != L.ix.accounts.end() && same(it->second.data(), &c.final_val[(size_t)14 * i], 14), "account %u: value after the valid prefix differs", i);
+    }
+    if (failures) { printf("%d checks failed\n", failures); return 1; }
+    printf("ok: depth %u, %u accounts, refused at %u of %u (reason %d), %zu merges in the valid prefix\n", d, na, at, n, c.reason, merges);
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { printf("usage: ledger_plan_check CASE [--time]\n"); return 2; }
     const bool timing = argc > 2 && std::string(argv[2]) == "--time";
     Case c;
     if (!read_case(argv[1], c)) { printf("cannot read %s\n", argv[1]); return 2; }
+    if (c.refusal) return expect_refused_batch(c);
     const uint32_t d = c.depth, n = c.n_tx, na = c.n_acc;
     const uint32_t reserve = (na + 4 * n) * (d + 1) + 16;
 

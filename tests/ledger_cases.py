@@ -72,13 +72,22 @@ def absent_index(w, indices):
     return None
 
 
-def write_case(path, w):
-    """the case as flat little-endian 64-bit words, as tests/cpp/ledger_plan_check.cpp reads it"""
-    indices, values = initial_accounts(w)
+def write_case(path, w, accounts=None, refusal=None):
+    """The case as flat little-endian 64-bit words, as tests/cpp/ledger_plan_check.cpp reads it.
+    accounts: (indices, values, final_values) where the accounts are not those the witness names (bystanders that no transfer touches).
+    refusal: (refused_at, reason) that the plan must answer to the whole batch; w then holds the arrays of transfers [0, refused_at),
+    the root they leave in initial_roots[refused_at], and final_values the accounts they leave."""
+    if accounts is None:
+        indices, values = initial_accounts(w)
+        final = final_accounts(w, indices)
+    else:
+        indices, values, final = (np.asarray(a, np.uint64) for a in accounts)
     absent = absent_index(w, indices)
     head = np.array([w.depth, len(indices), w.n_tx, 2**64 - 1 if absent is None else absent], np.uint64)
-    parts = [head, indices, values, final_accounts(w, indices), w.initial_roots, w.final_root, w.s_old_values, w.r_old_values, w.s_indices,
+    parts = [head, indices, values, final, w.initial_roots, w.final_root, w.s_old_values, w.r_old_values, w.s_indices,
              w.r_indices, w.s_paths, w.r_paths, w.deltas]
+    if refusal is not None:
+        parts.append(np.array(refusal, np.uint64))
     with open(path, "wb") as f:
         for a in parts:
             f.write(np.ascontiguousarray(a, "<u8").tobytes())
