@@ -216,6 +216,18 @@ int fri_coin_fold_dev(cstark_ctx *c, uint32_t *d_seed, const uint8_t *d_root, ui
                       uint64_t *d_out, uint32_t log_n, uint32_t log_f, uint64_t domain_offset, uint32_t m);
 // internal (capi.hip): row hashes of a whole table whose cosets are in block order (blake3.h): leaf b j + k = row j of LDE coset k
 int hash_rows_slots(cstark_ctx *c, uint32_t hash_fn, const uint64_t *d_lde, uint8_t *d_leaves, uint32_t width, uint32_t log_n, uint32_t log_blowup, uint32_t log_s);
+// internal (prove.hip): opening gathers of the caller's choice through the prover's own job list (GatherList: rows, paths, one
+// k_gather_batch launch on the context's stream, nothing waited for) -- what csrc/debug/debug_commit.hip calls.  paths = 0: row
+// d_pos[q] of the coset-major table src (a = width; log_s: block order, blake3.h); paths = 1: levels [lvl0, a) of the authentication
+// path of leaf d_pos[q] in the node array src (a = log2 of the leaf count).  d_count != null: the number of positions is read there
+// (at most count).  All pointers are device memory and the CALLER has checked every position: nothing is validated here but n_jobs.
+struct cstark_gather_desc {
+    const void *src;
+    void *out;
+    const uint32_t *d_pos, *d_count;
+    uint32_t paths, a, log_n, log_b, log_s, count, lvl0;
+};
+int gather_jobs_launch(cstark_ctx *c, const cstark_gather_desc *jobs, uint32_t n_jobs);
 // internal (capi.hip): the cached twiddle tables of a 2^log_n-point domain: powers of w and of its inverse (device, n entries each)
 int plan_tables(cstark_ctx *c, unsigned log_n, const uint64_t **w, const uint64_t **winv);
 

@@ -1473,6 +1473,18 @@ struct RangeBatch {
 
 using namespace cs;
 
+int gather_jobs_launch(cstark_ctx *c, const cstark_gather_desc *jobs, uint32_t n_jobs) {
+    if (!c || !jobs || n_jobs == 0 || n_jobs > (uint32_t)MAX_GATHER_JOBS) return fail(CSTARK_ERR_INVALID_ARG, "gather_jobs_launch: 1 .. 32 jobs");
+    GatherList gl;
+    for (uint32_t i = 0; i < n_jobs; i++) {
+        const cstark_gather_desc &j = jobs[i];
+        if (j.paths) gl.paths((const uint8_t *)j.src, j.a, j.d_pos, j.out, j.count, j.d_count, j.lvl0);
+        else gl.rows((const uint64_t *)j.src, j.a, j.log_n, j.log_b, j.d_pos, j.out, j.count, j.log_s, j.d_count);
+    }
+    HIP_TRY(gl.launch(c->stream));
+    return CSTARK_OK;
+}
+
 extern "C" {
 
 int cstark_tx_prove(cstark_ctx *c, const cstark_options *opt, uint8_t *proof, size_t capacity, size_t *proof_len) {
