@@ -15,6 +15,7 @@
 #include "constraints.h"
 #include "deep.h"
 #include "ext.h"
+#include "generator_fold.h"
 #include "hostfield.h"
 #include "ntt.h"
 #include "trace_gen.h"
@@ -394,6 +395,26 @@ int get_small_periodic(cstark_ctx *c, int air, unsigned depth, unsigned log_n, u
     return CSTARK_OK;
 }
 
+// The matrix of the generator addition on the doubling's six products (generator_fold.h), derived on the host and uploaded once per
+// context: a constant of the curve, read by the per-proof fold of the composition coefficients (constraints.hip)
+int generator_fold_table(cstark_ctx *c, const uint64_t **d_j) {
+    static_assert(cs::hostg::GF_COMPONENTS == cs::CE_GFOLD_COMPONENTS && cs::hostg::GF_LAMBDA_WORDS == cs::CE_GFOLD_WORDS &&
+                  cs::hostg::GF_OUTPUTS * cs::hostg::GF_COMPONENTS == cs::CE_GFOLD_J_WORDS, "generator fold layout");
+    if (!c->gfold_j) {
+        std::vector<uint64_t> j(cs::CE_GFOLD_J_WORDS);
+        cs::hostg::generator_fold_matrix(j.data());
+        DevGuard keep;
+        uint64_t *d = nullptr;
+        HIP_TRY(keep.alloc(&d, j.size() * 8));
+        HIP_TRY(hipMemcpyAsync(d, j.data(), j.size() * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        keep.release();
+        c->gfold_j = d;
+    }
+    *d_j = c->gfold_j;
+    return CSTARK_OK;
+}
+
 int ce_params(cstark_ctx *c, const uint64_t *d_lde, uint64_t *d_out, uint32_t merkle_depth, uint32_t log_n, uint32_t log_blowup, uint32_t k0,
               uint32_t nk, cs::CeParams *p) {
     if (!c || !d_lde || !d_out) return fail(CSTARK_ERR_INVALID_ARG, "constraint evaluation: null argument");
@@ -413,6 +434,7 @@ int ce_params(cstark_ctx *c, const uint64_t *d_lde, uint64_t *d_out, uint32_t me
     for (int g = 0; g < 5; g++) p->adj_mod_n[g] = (uint32_t)(cs::host::tx_group_adjustment(g, n, ce) & (n - 1));
     p->badj_mod_n = (uint32_t)(cs::host::tx_boundary_adjustment(n, ce) & (n - 1));
     p->log_n = log_n; p->log_b = log_blowup; p->k0 = k0;
+    RC_TRY(generator_fold_table(c, &p->gfold_j));
     return CSTARK_OK;
 }
 
@@ -507,6 +529,7 @@ void cstark_ctx_destroy(cstark_ctx *c) {
     if (c->wit_buf) (void)hipFree(c->wit_buf);
     if (c->ws) (void)hipFree(c->ws);
     if (c->coef_buf) (void)hipFree(c->coef_buf);
+    if (c->gfold_j) (void)hipFree(c->gfold_j);
     if (c->coef_stage) (void)hipHostFree(c->coef_stage);
     if (c->coef_ev) (void)hipEventDestroy(c->coef_ev);
     for (NttPlan &p : c->plans) { (void)hipFree(p.w); (void)hipFree(p.winv); (void)hipFree(p.aux_w); (void)hipFree(p.aux_winv); }
@@ -1203,10 +1226,9 @@ int tx_even_cosets(const cs::CeParams &p, uint64_t *even, size_t n, hipStream_t 
     HIP_TRY(cs::launch_rounds_split(p, even, stream));
     if (pev) HIP_TRY(hipEventRecord(pev[1], stream));
     uint64_t *fam_dbl = even + (size_t)cs::CE_SPLIT_FAM0 * 4 * n, *fam_add = fam_dbl + 12 * n, *fam_addbit = fam_add + 8 * n; // 3 | 2 | 2 tables
-    HIP_TRY(cs::launch_ec_split(p, 1, fam_dbl, nullptr, stream));
+    HIP_TRY(cs::launch_ec_split(p, 1, fam_dbl, fam_add, stream)); // the doubling of s*G and the addition of G to the same point
     if (pev) HIP_TRY(hipEventRecord(pev[2], stream));
-    HIP_TRY(cs::launch_ec_split(p, 2, fam_add, nullptr, stream));
-    if (pev) HIP_TRY(hipEventRecord(pev[3], stream));
+    if (pev) HIP_TRY(hipEventRecord(pev[3], stream)); // (add0: inside the launch before; the event positions stay)
     HIP_TRY(cs::launch_ec_split(p, 3, fam_dbl, nullptr, stream));
     if (pev) HIP_TRY(hipEventRecord(pev[4], stream));
     HIP_TRY(cs::launch_ec_split(p, 4, fam_addbit, fam_add, stream));
@@ -1734,7 +1756,9 @@ int schnorr_transition_sum(cstark_ctx *c, const AirStageRequest &rq, const cs::A
     const size_t n = st.n, region = (size_t)T * 4 * n, hcol = (size_t)3 * n; // hcol: the final addition's three sums, one n-point table each
     SplitWs w;
     RC_TRY(split_ws_unmerged(c, region, hcol, &w));
-    HIP_TRY(cs::launch_schnorr_ec_split(p, rq.d_aux_lde, d_txl, w.even, c->stream));
+    const uint64_t *d_gfold_j;
+    RC_TRY(generator_fold_table(c, &d_gfold_j));
+    HIP_TRY(cs::launch_schnorr_ec_split(p, rq.d_aux_lde, d_txl, w.even, d_gfold_j, d_rtab + cs::MERKLE_RTAB_LAMBDA, c->stream));
     if (final5) HIP_TRY(cs::launch_schnorr_final_split(p, d_txl, w.even + (size_t)cs::SCHNORR_SPLIT_EC_TABLES * 4 * n, -1, c->stream));
     RC_TRY(inverse_columns(st, w.even, w.sa, w.sb, 4 * T));
     RC_TRY(even_to_odd(st, w.sb, w.sa, T));

@@ -20,6 +20,9 @@ constexpr int CE_RTAB_WORDS = 12288;
 constexpr int CE_COEF_WORDS = 115 * 2 + 8; // one coefficient set: alpha[115] | beta[115] | b_alpha[4] | b_beta[4]
 constexpr int CE_MAX_SETS = 3;             // coefficient sets merged in one pass (the components of an extension proof)
 constexpr int CE_COSET_CONSTS = 10; // per coset: shift, 1/(shift^n - 1), shift^adj[0..5), shift^badj, shift^(n-1), unused
+// The generator addition as a functional on the doubling's six products (generator_fold.h): 36 monomial components; per coefficient
+// set three functionals (alpha | beta of x | beta of y, z); the constant matrix J[18][36] they are folded from
+constexpr int CE_GFOLD_COMPONENTS = 36, CE_GFOLD_WORDS = 3 * CE_GFOLD_COMPONENTS, CE_GFOLD_J_WORDS = 18 * CE_GFOLD_COMPONENTS;
 
 struct CeParams {
     const uint64_t *lde;   // cosets [k0, k0+nk), coset-major [kk][94][n]
@@ -29,6 +32,7 @@ struct CeParams {
     const uint64_t *coef;  // m sets of CE_COEF_WORDS: alpha[115] | beta[115] | b_alpha[4] | b_beta[4]   (device)
     const uint64_t *binv;  // [b][2][n]: 1/(x-1), 1/(x-w^(n-1)) over the evaluation domain
     uint64_t *rtab;        // [m][CE_RTAB_WORDS] scratch: per-proof folded coefficients of the Rescue windows (k_rounds_setup)
+    const uint64_t *gfold_j; // [CE_GFOLD_J_WORDS] the matrix of the generator addition (device; constant, uploaded once per context)
     uint64_t *out;         // merged evaluations of coefficient set 0
     uint64_t *out_ext[CE_MAX_SETS - 1]; // ... of sets 1, 2 (m > 1)
     uint32_t m;            // number of coefficient sets (0 reads as 1)
@@ -79,6 +83,7 @@ hipError_t launch_eval_transitions_schnorr(const uint64_t *lde, const uint64_t *
 // d_rtab != null (MERKLE_RTAB_WORDS device words, scratch): the four Rescue round gadgets through their folded form (k_merkle_rounds; blowup
 // at most 8), round_group = p.t_grp of the round slots; null: every constraint through the generic frame evaluator
 constexpr int MERKLE_RTAB_WORDS = 2048;
+constexpr int MERKLE_RTAB_LAMBDA = MERKLE_RTAB_WORDS - CE_GFOLD_WORDS; // its last words: d_lambda of launch_schnorr_ec_split
 hipError_t launch_merkle_fused(const AirCombineParams &p, const uint64_t *ptab, unsigned nk, hipStream_t stream, uint64_t *d_rtab = nullptr,
                                unsigned round_group = 0);
 hipError_t launch_schnorr_fused(const AirCombineParams &p, const uint64_t *aux, const uint64_t *ptab, unsigned nk, hipStream_t stream);
@@ -86,7 +91,10 @@ hipError_t launch_schnorr_fused(const AirCombineParams &p, const uint64_t *aux, 
 // cosets, d_even = [8][4][n] (d_coefs_tx_layout: alpha[i] at word i, beta[i] at word 115 + i, device); after their extension to the odd
 // cosets (d_odd = [4][8][n]) the recombination into p.out, to which the final addition and the remaining constraints are then added
 constexpr int SCHNORR_SPLIT_EC_TABLES = 8, SCHNORR_SPLIT_TABLES = 11; // without / with the final addition's three sums (tables 8..10)
-hipError_t launch_schnorr_ec_split(const AirCombineParams &p, const uint64_t *aux, const uint64_t *d_coefs_tx_layout, uint64_t *d_even, hipStream_t stream);
+// d_gfold_j = the matrix of the generator addition, d_lambda = CE_GFOLD_WORDS words of per-proof scratch: the addition of G is folded into
+// the doubling of the same point (k_generator_fold, then three launches)
+hipError_t launch_schnorr_ec_split(const AirCombineParams &p, const uint64_t *aux, const uint64_t *d_coefs_tx_layout, uint64_t *d_even, const uint64_t *d_gfold_j,
+                                   uint64_t *d_lambda, hipStream_t stream);
 hipError_t launch_schnorr_split_finish(const AirCombineParams &p, const uint64_t *aux, const uint64_t *ptab, const uint64_t *d_even, const uint64_t *d_odd,
                                        unsigned g0, unsigned g1, hipStream_t stream, uint64_t *d_rtab = nullptr, unsigned round_group = 0,
                                        const uint64_t *d_hi = nullptr);
@@ -116,10 +124,12 @@ hipError_t launch_eval_constraints(const CeParams &p, unsigned nk, hipStream_t s
 // the odd cosets d_odd = [4 cosets][4][n] (writes p.out, like the first part of launch_eval_constraints).
 hipError_t launch_rounds_setup(const CeParams &p, hipStream_t stream);
 hipError_t launch_rounds_split(const CeParams &p, uint64_t *d_even, hipStream_t stream);
-// split evaluation of a curve gadget (part 1 = doubling of s*G, 2 = addition of G, 3 = doubling of h*P; 1 and 2 write their family's
-// four polynomials, 3 adds to the doubling family): d_even_family = [4][4][n]
+// split evaluation of a curve gadget (part 1 = doubling of s*G AND addition of G to the same point, 3 = doubling of h*P; 1 writes the
+// doubling family's three polynomials into d_even_family and the addition family's two into d_even_linear -- the addition of the
+// constant G is a functional on the doubling's six products, folded per proof by launch_rounds_setup, which must precede it; 3 adds
+// to the doubling family): d_even_family = [3][4][n]
 // part 4 = addition of the public key: its quartic half is a family of its own (d_even_family), its linear half is ADDED to the
-// addition family d_even_linear (after part 2 wrote it)
+// addition family d_even_linear (after part 1 wrote it)
 hipError_t launch_ec_split(const CeParams &p, int part, uint64_t *d_even_family, uint64_t *d_even_linear, hipStream_t stream);
 constexpr int CE_SPLIT_TABLES = 13, CE_SPLIT_FAM0 = 4, CE_SPLIT_FINAL = 11; // first family (Rescue windows + linear groups): four polynomials; doubling 3 | addition 2 | addition x bit 2 | final addition 2
 // split evaluation of the three linear groups in one pass over the frame (k_lin_all): adds to the first family, d_even_family0 = [4][4][n]

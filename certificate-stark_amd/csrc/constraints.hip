@@ -510,9 +510,24 @@ constexpr size_t ROUNDS_DYN_LDS = 0;
 // With c_i = alpha_i + beta_i x^adj_g(i) this is one 14-term dot product per (alpha | beta restricted to a degree group) instead of
 // one per result slot.  k_rounds_setup folds the coefficients of one proof through MDS (U) and through the round constants, whose
 // extension has period 8 in j on every coset (A[k][j & 7]).  Exact arithmetic: the merged value is unchanged.
-__global__ void k_rounds_setup(const fp *__restrict__ coef, const fp *__restrict__ ptab, fp *__restrict__ rtab) {
+// The LAST block folds the same coefficients through the matrix of the generator addition (gfold_j = J[18][CE_GFOLD_COMPONENTS],
+// generator_fold.h) into RT_LAM, the three functionals that k_ec_split<PART_DBL0> applies to the doubling's six products.
+// Entry e = 36 q + t of one coefficient set (alpha[i] at word i, beta[i] at word 115 + i): q = 0 alpha over the 18 outputs, q = 1 beta
+// over x (outputs 0..5, degree group 0), q = 2 beta over y, z (outputs 6..17, group 1).
+__device__ __forceinline__ fp generator_fold_entry(const fp *__restrict__ coef, const fp *__restrict__ gfold_j, int e) {
+    const int q = e / CE_GFOLD_COMPONENTS, t = e % CE_GFOLD_COMPONENTS;
+    const int first = q == 2 ? 6 : 0, last = q == 1 ? 6 : 18;
+    fp s = 0;
+    for (int i = first; i < last; i++) s = fp_add(s, fp_mul(coef[(q ? 115 : 0) + i], gfold_j[i * CE_GFOLD_COMPONENTS + t]));
+    return s;
+}
+__global__ void k_rounds_setup(const fp *__restrict__ coef, const fp *__restrict__ ptab, fp *__restrict__ rtab, const fp *__restrict__ gfold_j) {
     coef += (size_t)blockIdx.y * CE_COEF_WORDS; // grid.y = coefficient set
     rtab += (size_t)blockIdx.y * CE_RTAB_WORDS;
+    if (blockIdx.x == gridDim.x - 1) {
+        for (int e = threadIdx.x; e < CE_GFOLD_WORDS; e += blockDim.x) rtab[RT_LAM + e] = generator_fold_entry(coef, gfold_j, e);
+        return;
+    }
     if (blockIdx.x >= RT_SECTIONS) { // the constant matrix of the inverse half as a matrix-core table (region zero-filled by the launcher)
         if (threadIdx.x < 16) mdsmfma::build_table_entry((uint8_t *)(rtab + RT_MT), c_inv_mds, 14, blockIdx.x - RT_SECTIONS, threadIdx.x);
         return;
@@ -1078,6 +1093,125 @@ struct SplitAcc {
         return acc_reduce(a);
     }
 };
+// ---- the addition of the generator, folded into the doubling of the same point ----------------------------------------------------
+// add(cur, G) for the CONSTANT G is a quadratic map of (X, Y, Z): each of its 18 components is a fixed F_p-linear combination of the
+// 36 components of mono = (X^2, Y^2, Z^2, XY, XZ, YZ) (generator_fold.h: the matrix J) -- and these six products are the first six
+// of the complete doubling.  A sum over the 18 outputs with per-proof coefficients is therefore ONE functional on the monomial
+// components, Lambda = coef^T J, folded once per proof (k_rounds_setup / k_generator_fold) for the three sums of SplitAcc: alpha,
+// beta of group 0 (x), beta of group 1 (y, z); lam = [3][CE_GFOLD_COMPONENTS] per coefficient set, `stride` words apart.
+// With N = sum coef_i next_i, C = sum coef_i cur_i, DD = sum coef_i double(cur)_i, QA = Lambda . mono, bit = cur(18):
+//     doubling:  sum coef_i (next_i - double(cur)_i)                            =  N - DD
+//     addition:  sum coef_i ((next_i - cur_i) - bit (add(cur, G)_i - cur_i))    =  (N - C) - bit (QA - C)
+// Exact arithmetic and fully reduced sums: the values are those of fused_doubling / fused_addition under SplitAcc.
+template <int M>
+struct MonoAcc {
+    const CS_CONST fp *lam;
+    int stride;
+    Acc128 s[M][3];
+    int cnt;
+    __device__ __forceinline__ void begin() {
+        cnt = 0;
+#pragma unroll
+        for (int c = 0; c < M; c++) s[c][0] = s[c][1] = s[c][2] = acc_zero();
+    }
+    __device__ __forceinline__ void feed(int m, const Fp6 &v) { // monomial m as soon as it exists: its 18 M multiply-accumulates
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            const bool fold = ++cnt == 7;
+#pragma unroll
+            for (int c = 0; c < M; c++)
+#pragma unroll
+                for (int q = 0; q < 3; q++) {
+                    acc_mad(s[c][q], lam[c * stride + q * CE_GFOLD_COMPONENTS + 6 * m + k], v.c[k]);
+                    if (fold) acc_fold(s[c][q]);
+                }
+            if (fold) cnt = 0;
+        }
+    }
+    __device__ __forceinline__ fp result(int c, int q) {
+        acc_fold(s[c][q]);
+        return acc_reduce(s[c][q]);
+    }
+};
+// the complete doubling (ec_double above) continued from its six products
+template <bool CALL>
+__device__ __forceinline__ Point ec_double_from_monomials(const Fp6 &xx, const Fp6 &yy, const Fp6 &zz, const Fp6 &xy, const Fp6 &xz, const Fp6 &yz) {
+#define mul6 MUL6_SEL<CALL>
+    const Fp6 b3 = const6(c_b3);
+    Fp6 t0 = xx, t1 = yy, t2 = zz;
+    Fp6 t3 = fp6_dbl(xy);
+    Fp6 z3 = fp6_dbl(xz);
+    Fp6 y3 = fp6_add(z3, mul6(b3, t2));
+    Fp6 x3 = fp6_sub(t1, y3);
+    y3 = fp6_add(t1, y3);
+    y3 = mul6(x3, y3);
+    x3 = mul6(t3, x3);
+    z3 = mul6(b3, z3);
+    t3 = fp6_add(fp6_sub(t0, t2), z3);
+    t0 = fp6_add(fp6_add(fp6_dbl(t0), t0), t2);
+    y3 = fp6_add(y3, mul6(t0, t3));
+    t2 = fp6_dbl(yz);
+    x3 = fp6_sub(x3, mul6(t2, t3));
+    z3 = fp6_dbl(fp6_dbl(mul6(t2, t1)));
+    return {x3, y3, z3};
+#undef mul6
+}
+// dbl[c][q], add[c][q]: the three sums (SplitAcc::result order) of the doubling and of the generator addition for the point at
+// registers 0..17, bit register 18.  `next` is read once, before the curve arithmetic; nothing but the sums stays live across it.
+template <int M>
+__device__ __forceinline__ void split_doubling_with_generator(SplitAcc<M> &acc, MonoAcc<M> &qa, const Frame &f, fp (&dbl)[M][3], fp (&add)[M][3]) {
+    fp nx[M][3], cu[M][3];
+    acc.begin();
+#pragma unroll
+    for (int i = 0; i < 18; i++) acc.term(i, f.next(i));
+#pragma unroll
+    for (int c = 0; c < M; c++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) nx[c][q] = acc.result(c, q);
+    const Point p = {load6(f, 0, false), load6(f, 6, false), load6(f, 12, false)};
+    acc.begin();
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        acc.term(i, p.x.c[i]);
+        acc.term(6 + i, p.y.c[i]);
+        acc.term(12 + i, p.z.c[i]);
+    }
+#pragma unroll
+    for (int c = 0; c < M; c++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) cu[c][q] = acc.result(c, q);
+    qa.begin();
+    const Fp6 xx = MUL6_SEL<CS_EC_CALL>(p.x, p.x);
+    qa.feed(0, xx);
+    const Fp6 yy = MUL6_SEL<CS_EC_CALL>(p.y, p.y);
+    qa.feed(1, yy);
+    const Fp6 zz = MUL6_SEL<CS_EC_CALL>(p.z, p.z);
+    qa.feed(2, zz);
+    const Fp6 xy = MUL6_SEL<CS_EC_CALL>(p.x, p.y);
+    qa.feed(3, xy);
+    const Fp6 xz = MUL6_SEL<CS_EC_CALL>(p.x, p.z);
+    qa.feed(4, xz);
+    const Fp6 yz = MUL6_SEL<CS_EC_CALL>(p.y, p.z);
+    qa.feed(5, yz);
+    const fp bit = f.cur(18);
+#pragma unroll
+    for (int c = 0; c < M; c++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) add[c][q] = fp_sub(fp_sub(nx[c][q], cu[c][q]), fp_mul(bit, fp_sub(qa.result(c, q), cu[c][q])));
+    const Point d = ec_double_from_monomials<CS_EC_CALL>(xx, yy, zz, xy, xz, yz);
+    acc.begin();
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        acc.term(i, d.x.c[i]);
+        acc.term(6 + i, d.y.c[i]);
+        acc.term(12 + i, d.z.c[i]);
+    }
+#pragma unroll
+    for (int c = 0; c < M; c++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) dbl[c][q] = fp_sub(nx[c][q], acc.result(c, q));
+}
+
 // The addition of the public key (a variable point: add(cur, P) is quartic, bit * add quintic) splits once more:
 //     (next - cur) - bit (add(cur, P) - cur)  =  L - bit * Q,   L = next - cur (degree n - 1),  Q = add(cur, P) - cur (degree 4 (n - 1)):
 // sum coef_i L_i joins the addition family, sum coef_i Q_i is a family of its own whose "flag" is -addition(x) * bit(x), the bit
@@ -1096,9 +1230,23 @@ __global__ __launch_bounds__(FNT, CS_EC_WAVES) void k_ec_split(CeParams p, fp *_
     SplitAcc<M> acc;
     acc.coefs = as_const(p.coef);
     constexpr size_t SET = (size_t)SPLIT_TABLES * 4; // tables (x n words) between the blocks of two coefficient sets
-    if (PART == PART_DBL0) fused_doubling(acc, f, 0, (fp)0);
+    if constexpr (PART == PART_DBL0) { // + the addition of the generator to the same point: out_linear = the addition family, written here
+        MonoAcc<M> qa;
+        qa.lam = as_const((const fp *)(p.rtab + RT_LAM));
+        qa.stride = CE_RTAB_WORDS;
+        fp dbl[M][3], add[M][3];
+        split_doubling_with_generator(acc, qa, f, dbl, add);
+        const fp xd1 = split_lift(p, 2 * kc, j);
+#pragma unroll
+        for (int c = 0; c < M; c++) {
+#pragma unroll
+            for (int q = 0; q < 3; q++) out[(c * SET + (size_t)q * 4 + kc) * n + j] = dbl[c][q];
+            out_linear[(c * SET + kc) * n + j] = add[c][0];
+            out_linear[(c * SET + 4 + kc) * n + j] = fp_add(add[c][1], fp_mul(xd1, add[c][2]));
+        }
+        return;
+    }
     if (PART == PART_DBL1) fused_doubling(acc, f, 19, (fp)0);
-    if (PART == PART_ADD0) fused_addition(acc, f, 0, const6(c_generator), const6(c_generator + 6), (fp)0);
     if (PART == PART_ADD1) {
         acc.begin(); // the linear half first: its four sums leave the registers before the curve arithmetic starts
 #pragma unroll
@@ -1121,16 +1269,14 @@ __global__ __launch_bounds__(FNT, CS_EC_WAVES) void k_ec_split(CeParams p, fp *_
         }
     }
     // the h*P registers 19..36 are all in group 0 (PART_DBL1 adds zero for group 1); the addition family keeps beta of groups 0, 1 in ONE
-    // table, group 1 lifted by x^(n-1) (cubic terms: the sum stays below degree 4n)
-    constexpr int NQ = (PART == PART_ADD1 || PART == PART_ADD0) ? 2 : 3;
-    const fp xd1 = PART == PART_ADD0 ? split_lift(p, 2 * kc, j) : 0;
+    // table, group 1 lifted by x^(n-1) (cubic terms: the sum stays below degree 4n): PART_DBL0 above merges them when it writes
+    constexpr int NQ = PART == PART_ADD1 ? 2 : 3;
 #pragma unroll
     for (int c = 0; c < M; c++)
 #pragma unroll
         for (int q = 0; q < NQ; q++) {
             fp *o = out + (c * SET + (size_t)q * 4 + kc) * n + j;
-            fp v = acc.result(c, q);
-            if (PART == PART_ADD0 && q == 1) v = fp_add(v, fp_mul(xd1, acc.result(c, 2)));
+            const fp v = acc.result(c, q);
             *o = ACCUMULATE ? fp_add(*o, v) : v;
         }
 }
@@ -2045,12 +2191,17 @@ __global__ __launch_bounds__(FNT, PART == SF_REST ? 2 : CS_EC_WAVES) void k_schn
 // groups those of SchnorrAir (slots 0..5 and 19..36: first group, 6..17: second -- the same partition of the curve slots as in
 // TransactionAir, so SplitAcc applies with the coefficients laid out alpha[i] | beta[115 + i]).
 // Eight polynomials per proof on the even cosets, out = [8][4][n]: doubling alpha, beta_0, beta_1 | addition alpha, beta_0, beta_1 |
-// addition x bit alpha, beta_0.  PART: 1 = doubling of s*G (writes the doubling family), 3 = doubling of h*P (adds to it), 2 = addition of
-// G (writes the addition family), 4 = addition of P (adds its linear half to the addition family, writes the third family).
+// addition x bit alpha, beta_0.  PART: 1 = doubling of s*G and addition of G to the same point (writes the doubling and the addition
+// family: the addition of the constant G from the doubling's six products, through lam = the three functionals that k_generator_fold
+// folds from this proof's coefficients), 3 = doubling of h*P (adds to the doubling family), 4 = addition of P (adds its linear half to
+// the addition family, writes the third family).
 constexpr int SCH_SPLIT_EC_TABLES = 8, SCH_SPLIT_TABLES = 11; // the doubling / addition families | + the final addition's three sums
+__global__ void k_generator_fold(const fp *__restrict__ coefs_tx_layout, const fp *__restrict__ gfold_j, fp *__restrict__ lam) {
+    for (int e = threadIdx.x; e < CE_GFOLD_WORDS; e += blockDim.x) lam[e] = generator_fold_entry(coefs_tx_layout, gfold_j, e);
+}
 template <int PART>
 __global__ __launch_bounds__(FNT, CS_EC_WAVES) void k_schnorr_ec_split(const fp *__restrict__ lde, const fp *__restrict__ aux, const fp *__restrict__ coefs_tx_layout,
-                                                                      fp *__restrict__ out, unsigned log_n) {
+                                                                      fp *__restrict__ out, unsigned log_n, const fp *__restrict__ lam) {
     const size_t n = (size_t)1 << log_n;
     const size_t j = blockIdx.x * (size_t)FNT + threadIdx.x;
     const unsigned kc = blockIdx.y, kk = 2 * kc;
@@ -2064,9 +2215,20 @@ __global__ __launch_bounds__(FNT, CS_EC_WAVES) void k_schnorr_ec_split(const fp 
     SplitAcc<1> acc;
     acc.coefs = as_const(coefs_tx_layout);
     fp *fam = out + (size_t)(PART == PART_DBL0 || PART == PART_DBL1 ? 0 : 3) * 4 * n;
-    if (PART == PART_DBL0) fused_doubling(acc, f, 0, (fp)0);
+    if constexpr (PART == PART_DBL0) { // both families of the point s*G from the doubling's six products (split_doubling_with_generator)
+        MonoAcc<1> qa;
+        qa.lam = as_const(lam);
+        qa.stride = 0;
+        fp dbl[1][3], add[1][3];
+        split_doubling_with_generator(acc, qa, f, dbl, add);
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            fam[((size_t)q * 4 + kc) * n + j] = dbl[0][q];
+            fam[((size_t)(3 + q) * 4 + kc) * n + j] = add[0][q];
+        }
+        return;
+    }
     if (PART == PART_DBL1) fused_doubling(acc, f, 19, (fp)0);
-    if (PART == PART_ADD0) fused_addition(acc, f, 0, const6(c_generator), const6(c_generator + 6), (fp)0);
     if (PART == PART_ADD1) {
         acc.begin(); // the linear half: next - cur of registers 19..36 (all in the first group)
 #pragma unroll
@@ -2463,14 +2625,16 @@ hipError_t launch_schnorr_fused(const AirCombineParams &p, const uint64_t *aux, 
 // SchnorrAir's curve gadgets in the degree-split form (all eight cosets, k0 = 0).  1: launch_schnorr_ec_split -- the eight polynomials on
 // the even cosets, d_even = [8][4][n]; the caller interpolates them per coset, carries them to the odd cosets (ntt.h: coset_even_to_odd)
 // and extends them, d_odd = [4][8][n]; 2: launch_schnorr_split_finish -- recombination into p.out, then the remaining parts add to it.
-hipError_t launch_schnorr_ec_split(const AirCombineParams &p, const uint64_t *aux, const uint64_t *d_coefs_tx_layout, uint64_t *d_even, hipStream_t stream) {
+// d_gfold_j: the matrix of the generator addition (generator_fold.h); d_lambda: CE_GFOLD_WORDS words of per-proof scratch for its fold.
+hipError_t launch_schnorr_ec_split(const AirCombineParams &p, const uint64_t *aux, const uint64_t *d_coefs_tx_layout, uint64_t *d_even, const uint64_t *d_gfold_j,
+                                   uint64_t *d_lambda, hipStream_t stream) {
     const size_t n = (size_t)1 << p.log_n;
-    if (n % FNT) return hipErrorInvalidValue;
+    if (n % FNT || !d_gfold_j || !d_lambda) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(n / FNT), 4), block(FNT);
-    hipLaunchKernelGGL(k_schnorr_ec_split<PART_DBL0>, grid, block, 0, stream, p.lde, aux, d_coefs_tx_layout, d_even, p.log_n);
-    hipLaunchKernelGGL(k_schnorr_ec_split<PART_DBL1>, grid, block, 0, stream, p.lde, aux, d_coefs_tx_layout, d_even, p.log_n);
-    hipLaunchKernelGGL(k_schnorr_ec_split<PART_ADD0>, grid, block, 0, stream, p.lde, aux, d_coefs_tx_layout, d_even, p.log_n);
-    hipLaunchKernelGGL(k_schnorr_ec_split<PART_ADD1>, grid, block, 0, stream, p.lde, aux, d_coefs_tx_layout, d_even, p.log_n);
+    hipLaunchKernelGGL(k_generator_fold, dim3(1), dim3(128), 0, stream, d_coefs_tx_layout, d_gfold_j, d_lambda);
+    hipLaunchKernelGGL(k_schnorr_ec_split<PART_DBL0>, grid, block, 0, stream, p.lde, aux, d_coefs_tx_layout, d_even, p.log_n, (const fp *)d_lambda);
+    hipLaunchKernelGGL(k_schnorr_ec_split<PART_DBL1>, grid, block, 0, stream, p.lde, aux, d_coefs_tx_layout, d_even, p.log_n, (const fp *)d_lambda);
+    hipLaunchKernelGGL(k_schnorr_ec_split<PART_ADD1>, grid, block, 0, stream, p.lde, aux, d_coefs_tx_layout, d_even, p.log_n, (const fp *)d_lambda);
     return hipGetLastError();
 }
 hipError_t launch_schnorr_final_split(const AirCombineParams &p, const uint64_t *d_coefs_tx_layout, uint64_t *d_out, int coset, hipStream_t stream) {
@@ -2630,12 +2794,12 @@ static hipError_t with_sets(unsigned m, Fn fn) {
 
 hipError_t launch_rounds_setup(const CeParams &p, hipStream_t stream) {
     const unsigned m = p.m ? p.m : 1;
-    if (m > 3) return hipErrorInvalidValue;
+    if (m > 3 || !p.gfold_j) return hipErrorInvalidValue;
 #ifdef CS_ROUNDS_MFMA // the matrix-core table of the inverse matrix: 14 more blocks and a zero-fill, only for the opt-in variant
     (void)hipMemsetAsync(p.rtab + RT_MT, 0, MT_BYTES, stream);
-    hipLaunchKernelGGL(k_rounds_setup, dim3(RT_SECTIONS + 14, m), dim3(64), 0, stream, p.coef, p.ptab, p.rtab);
+    hipLaunchKernelGGL(k_rounds_setup, dim3(RT_SECTIONS + 14 + 1, m), dim3(64), 0, stream, p.coef, p.ptab, p.rtab, p.gfold_j);
 #else
-    hipLaunchKernelGGL(k_rounds_setup, dim3(RT_SECTIONS, m), dim3(64), 0, stream, p.coef, p.ptab, p.rtab);
+    hipLaunchKernelGGL(k_rounds_setup, dim3(RT_SECTIONS + 1, m), dim3(64), 0, stream, p.coef, p.ptab, p.rtab, p.gfold_j); // + the generator fold
 #endif
     return hipGetLastError();
 }
@@ -2652,11 +2816,11 @@ hipError_t launch_ec_split(const CeParams &p, int part, uint64_t *d_even_family,
     const size_t n = (size_t)1 << p.log_n;
     const dim3 grid((unsigned)(n / FNT), p.nkc ? p.nkc : 4), block(FNT);
     const unsigned m = p.m ? p.m : 1;
-    if (part != PART_DBL0 && part != PART_DBL1 && part != PART_ADD0 && part != PART_ADD1) return hipErrorInvalidValue;
+    if (part != PART_DBL0 && part != PART_DBL1 && part != PART_ADD1) return hipErrorInvalidValue;
+    if (part != PART_DBL1 && !d_even_linear) return hipErrorInvalidValue;
     return with_sets(m, [&](auto M) {
         if (part == PART_DBL0) hipLaunchKernelGGL((k_ec_split<PART_DBL0, false, M>), grid, block, 0, stream, p, d_even_family, d_even_linear);
         else if (part == PART_DBL1) hipLaunchKernelGGL((k_ec_split<PART_DBL1, true, M>), grid, block, 0, stream, p, d_even_family, d_even_linear);
-        else if (part == PART_ADD0) hipLaunchKernelGGL((k_ec_split<PART_ADD0, false, M>), grid, block, 0, stream, p, d_even_family, d_even_linear);
         else hipLaunchKernelGGL((k_ec_split<PART_ADD1, false, M>), grid, block, 0, stream, p, d_even_family, d_even_linear);
     });
 }

@@ -171,6 +171,7 @@ struct cstark_ctx {
     std::deque<cs::StepTable> steps;
     std::deque<cs::PeriodicTable> periodic;
     uint64_t *coef_buf = nullptr; // device copy of the composition coefficients
+    uint64_t *gfold_j = nullptr;  // the matrix of the generator addition (generator_fold.h), uploaded on first use
     void *coef_stage = nullptr;   // pinned host staging of the same block: the upload is asynchronous, no wait for the caller's struct
     hipEvent_t coef_ev = nullptr; // recorded behind the upload; waited on before the staging block is rewritten
     std::deque<cs::AssertInverseTable> assert_inv;  // k_air_combine's divisor inverses, keyed by (m, zc, log_n, log_b)

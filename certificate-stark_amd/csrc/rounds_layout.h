@@ -16,7 +16,8 @@ struct RoundWindow { int reg, res_a, flag_a, res_b, flag_b; }; // dwords: sub-dw
 
 constexpr int RT_SECTIONS = 5 * 2 * 4; // (window, flag set, {alpha, beta of up to 3 groups})
 // CeParams::rtab (u64 words): A[sections][64] | limbs of U[sections][14] (4 dwords each) | limbs of INV_MDS | byte-Toeplitz table of
-// INV_MDS (the opt-in -DCS_ROUNDS_MFMA variant of the vector-ALU kernels) | the sections' coefficient vectors | tables of k_rounds_mfma
+// INV_MDS (the opt-in -DCS_ROUNDS_MFMA variant of the vector-ALU kernels) | the sections' coefficient vectors | tables of k_rounds_mfma |
+// the generator addition's functionals (RT_LAM: read by k_ec_split<PART_DBL0>)
 constexpr int RT_A = 0, RT_UL = RT_SECTIONS * 64, RT_ML = RT_UL + RT_SECTIONS * 14 * 2, RT_MT = RT_ML + 14 * 14 * 2;
 constexpr size_t MT_BYTES = (mdsmfma::table_bytes(14) + 15) & ~(size_t)15;
 constexpr int RT_G = RT_MT + (int)(MT_BYTES / 8); // the sections' coefficient vectors themselves (split evaluation)
@@ -34,7 +35,8 @@ constexpr int MF_INV_D = RT_MF;                                  // [7][2 g][2 h
 constexpr int MF_SEC_D = MF_INV_D + MF_TILES_INV * 4 * 8;        // [13][2 g][2 h][16 m]
 constexpr int MF_K = MF_SEC_D + MF_TILES_SEC * 4 * 16;           // [14 + 26][4]: the 32-bit words of the 128-bit row constants, one per u64
 constexpr int RT_SIZE = MF_K + (14 + 2 * MF_TILES_SEC) * 4;
-static_assert(RT_SIZE <= CE_RTAB_WORDS, "rtab size");
+constexpr int RT_LAM = RT_SIZE; // [3][CE_GFOLD_COMPONENTS]: the generator addition's three functionals (k_rounds_setup's last block)
+static_assert(RT_LAM + CE_GFOLD_WORDS <= CE_RTAB_WORDS, "rtab size");
 // section tile t -> (window, flag set, pair); window w owns the tiles [mf_tile_base(w), mf_tile_base(w + 1))
 __host__ __device__ constexpr int mf_tile_base(int w) { return w == 0 ? 0 : w == 1 ? 2 : w == 2 ? 6 : w == 3 ? 10 : w == 4 ? 12 : 13; }
 __host__ __device__ constexpr int mf_tile_window(int t) { return t < 2 ? 0 : t < 6 ? 1 : t < 10 ? 2 : t < 12 ? 3 : 4; }
@@ -48,7 +50,7 @@ constexpr int MRF_INV_D = MR_G + MR_SECTIONS * 14;          // [7][2][2][8]
 constexpr int MRF_SEC_D = MRF_INV_D + MF_TILES_INV * 32;   // [4 windows][2][2][16]
 constexpr int MRF_K = MRF_SEC_D + 4 * 64;                  // [14 + 8][4]
 constexpr int MR_SIZE = MRF_K + (14 + 8) * 4;
-static_assert(MR_SIZE <= MERKLE_RTAB_WORDS, "MerkleAir rounds table");
+static_assert(MR_SIZE <= MERKLE_RTAB_LAMBDA, "MerkleAir rounds table"); // (the scratch's last words: SchnorrAir's generator fold)
 
 hipError_t launch_merkle_rounds_mfma(const AirCombineParams &p, const uint64_t *ptab, uint64_t *d_rtab, unsigned nk, unsigned round_group, int which,
                                      hipStream_t stream); // rounds_mfma.hip; after k_merkle_rounds_setup
