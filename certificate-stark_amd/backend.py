@@ -138,10 +138,11 @@ class Backend:
         check(self.lib.cstark_ledger_root(self.ctx, led, self._hptr(root)))
         return root
 
-    def ledger_apply(self, led, depth, s_indices, r_indices, deltas, sig_rx, sig_s, want_witness=True):
+    def ledger_apply(self, led, depth, s_indices, r_indices, deltas, sig_rx, sig_s, want_witness=True, check_signatures=False):
         """cstark_ledger_apply: -> (refused_at, reason, arrays).  Applied (refused_at == -1): the batch's witness is resident in this
         backend (build_trace / prove / air_prove follow without an upload) and arrays is the dict of its eleven fields (None with
-        want_witness=False).  Refused: nothing changed, arrays is None."""
+        want_witness=False).  Refused: nothing changed, arrays is None.  check_signatures: cstark_ledger_apply_checked -- every
+        transfer's signature is checked on the device before anything is applied (reason 5 at the first bad one)."""
         s, r, dl = _np_u64(s_indices).reshape(-1), _np_u64(r_indices).reshape(-1), _np_u64(deltas).reshape(-1)
         n = s.size
         rx = _np_u64(sig_rx).reshape(-1, 6)
@@ -161,8 +162,9 @@ class Backend:
                 setattr(st, f, a.ctypes.data_as(u8p if f == "sig_s" else u64p))
             out = C.byref(st)
         at, reason = C.c_int32(-1), C.c_int32(0)
-        check(self.lib.cstark_ledger_apply(self.ctx, led, C.c_uint32(n), self._hptr(s), self._hptr(r), self._hptr(dl), self._hptr(rx), self._hptr(ss, u8p),
-                                           out, C.byref(at), C.byref(reason)))
+        apply = self.lib.cstark_ledger_apply_checked if check_signatures else self.lib.cstark_ledger_apply
+        check(apply(self.ctx, led, C.c_uint32(n), self._hptr(s), self._hptr(r), self._hptr(dl), self._hptr(rx), self._hptr(ss, u8p),
+                    out, C.byref(at), C.byref(reason)))
         if at.value >= 0:
             return at.value, reason.value, None
         self.resident = None   # an example that believed its own witness resident uploads again
@@ -436,6 +438,23 @@ class Backend:
         check(self.lib.cstark_schnorr_witness_upload(self.ctx, C.c_uint32(n_sig), m.ctypes.data_as(u64p), rx.ctypes.data_as(u64p),
                                                      s.ctypes.data_as(u8p)))
         self.n_tx = n_sig
+
+    SIG_VALID, SIG_MISMATCH, SIG_KEY_NOT_ON_CURVE, SIG_SCALAR_RANGE = 0, 1, 2, 3   # cstark_sig_verdict
+
+    def schnorr_check(self, messages, sig_rx, sig_s, want_rx=False):
+        """cstark_schnorr_check_signatures: verify_signature for every (message [28], R.x [6], s [32]) on the device -> verdicts
+        uint8[count] (cstark_sig_verdict); with want_rx also the affine x of s*G + h*P, uint64 [count][6].  The resident witness is
+        not touched."""
+        m, rx = _np_u64(messages).reshape(-1, 28), _np_u64(sig_rx).reshape(-1, 6)
+        s = np.ascontiguousarray(sig_s, np.uint8).reshape(-1, 32)
+        n = m.shape[0]
+        if not (rx.shape[0] == s.shape[0] == n):
+            raise ValueError("the signature arrays state different numbers of signatures")
+        verdicts = np.zeros(n, np.uint8)
+        x = np.zeros((n, 6), np.uint64) if want_rx else None
+        check(self.lib.cstark_schnorr_check_signatures(self.ctx, C.c_uint32(n), self._hptr(m), self._hptr(rx), self._hptr(s, u8p),
+                                                       self._hptr(verdicts, u8p), self._hptr(x) if want_rx else None))
+        return (verdicts, x) if want_rx else verdicts
 
     def schnorr_build_trace(self):
         out = self.empty_u64(56, self.n_tx * 512)

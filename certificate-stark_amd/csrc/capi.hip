@@ -550,6 +550,7 @@ void cstark_ctx_destroy(cstark_ctx *c) {
     if (c->shard_bit37) (void)hipFree(c->shard_bit37);
     if (c->rb_host) (void)hipHostFree(c->rb_host);
     if (c->tail_buf) (void)hipFree(c->tail_buf);
+    if (c->sig_buf) (void)hipFree(c->sig_buf);
     if (c->arena) cs::prove_arena_free(c->arena);
     if (c->verify) cs::verify_arena_free(c->verify);
     for (hipEvent_t e : c->part_ev) if (e) (void)hipEventDestroy(e);
@@ -1360,6 +1361,44 @@ int tx_shard_combine(cstark_ctx *c, const uint64_t *d_parts, uint64_t *d_out, ui
     return CSTARK_OK;
 }
 
+// cstark_schnorr_check_signatures behind its null / count checks.  One device block of the context, grown when needed:
+//   messages [count][28] | sig_rx [count][6] | h limbs [count][4] | ladder points [2 count][18] | x [count][6] | sig_s [count][32] | verdicts [count]
+// Nothing of the resident witness (c->wit, c->wit_buf, c->tail_buf, the Schnorr statement caches) is read or written.
+static_assert(cs::SIG_VALID == CSTARK_SIG_VALID && cs::SIG_MISMATCH == CSTARK_SIG_MISMATCH && cs::SIG_KEY_NOT_ON_CURVE == CSTARK_SIG_KEY_NOT_ON_CURVE &&
+                  cs::SIG_SCALAR_RANGE == CSTARK_SIG_SCALAR_RANGE,
+              "k_sig_final writes the values of cstark_sig_verdict");
+int signature_check(cstark_ctx *c, const char *who, uint32_t count, const uint64_t *messages, const uint64_t *sig_rx, const uint8_t *sig_s,
+                    uint8_t *verdicts, uint64_t *rx_out) {
+    char where[96];
+    for (size_t i = 0; i < (size_t)28 * count; i++)
+        if (messages[i] >= cs::host::P) {
+            snprintf(where, sizeof where, "%s: messages[%zu][%zu]", who, i / 28, i % 28);
+            return fail(CSTARK_ERR_INVALID_ARG, "%s is not a reduced field element", where);
+        }
+    for (size_t i = 0; i < (size_t)6 * count; i++)
+        if (sig_rx[i] >= cs::host::P) {
+            snprintf(where, sizeof where, "%s: sig_rx[%zu][%zu]", who, i / 6, i % 6);
+            return fail(CSTARK_ERR_INVALID_ARG, "%s is not a reduced field element", where);
+        }
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = count, bytes = n * (80 * 8 + 32 + 1);
+    if (c->sig_bytes < bytes) {
+        if (c->sig_buf) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->sig_buf)); c->sig_buf = nullptr; c->sig_bytes = 0; }
+        HIP_TRY(hipMalloc(&c->sig_buf, bytes));
+        c->sig_bytes = bytes;
+    }
+    uint64_t *d_msg = (uint64_t *)c->sig_buf, *d_rx = d_msg + 28 * n, *d_h = d_rx + 6 * n, *d_pts = d_h + 4 * n, *d_x = d_pts + 36 * n;
+    uint8_t *d_s = (uint8_t *)(d_x + 6 * n), *d_verdicts = d_s + 32 * n;
+    HIP_TRY(hipMemcpyAsync(d_msg, messages, n * 28 * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_rx, sig_rx, n * 6 * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_s, sig_s, n * 32, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(cs::launch_signature_check(d_msg, d_rx, d_s, d_h, d_pts, d_verdicts, d_x, count, c->stream));
+    HIP_TRY(hipMemcpyAsync(verdicts, d_verdicts, n, hipMemcpyDeviceToHost, c->stream));
+    if (rx_out) HIP_TRY(hipMemcpyAsync(rx_out, d_x, n * 6 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream)); // synchronous: the verdicts are on the host, the caller's arrays are free again
+    return CSTARK_OK;
+}
+
 extern "C" {
 
 int cstark_tx_evaluate_constraints(cstark_ctx *c, const uint64_t *d_lde, const cstark_tx_coeffs *coeffs, const uint64_t pub_inputs[4],
@@ -1478,6 +1517,12 @@ int cstark_schnorr_aux_columns(cstark_ctx *c, uint64_t *d_out) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(cs::launch_schnorr_aux_columns(c->wit, d_out, c->stream));
     return CSTARK_OK;
+}
+int cstark_schnorr_check_signatures(cstark_ctx *c, uint32_t count, const uint64_t *messages, const uint64_t *sig_rx, const uint8_t *sig_s,
+                                    uint8_t *verdicts, uint64_t *rx_out) {
+    if (!c || !messages || !sig_rx || !sig_s || !verdicts) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_check_signatures: null argument");
+    if (count == 0 || count > (1u << 20)) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_check_signatures: count must be 1 .. 2^20");
+    return signature_check(c, "cstark_schnorr_check_signatures", count, messages, sig_rx, sig_s, verdicts, rx_out);
 }
 int cstark_schnorr_mask_columns(uint64_t *out /* [36][512] host */) {
     if (!out) return fail(CSTARK_ERR_INVALID_ARG, "null argument");

@@ -207,7 +207,13 @@ struct cstark_ctx {
     size_t shard_bit37_words = 0;
     void *rb_dev = nullptr, *rb_host = nullptr; // cstark_range_prove_batch: one device block and one pinned host block, carved per call
     size_t rb_dev_bytes = 0, rb_host_bytes = 0;
+    void *sig_buf = nullptr; // cstark_schnorr_check_signatures: its inputs, scratch and outputs on the device (never the resident witness)
+    size_t sig_bytes = 0;
 };
+// internal (capi.hip): cstark_schnorr_check_signatures behind its null / count checks (cstark_ledger_apply_checked calls it with the
+// messages of ledger_plan.h).  `who` names the public call in the error text.
+int signature_check(cstark_ctx *c, const char *who, uint32_t count, const uint64_t *messages, const uint64_t *sig_rx, const uint8_t *sig_s,
+                    uint8_t *verdicts, uint64_t *rx_out);
 // internal (capi.hip): the resident witness of n transfers at depth d, for cstark_tx_witness_upload and cstark_ledger_apply.  reserve: the
 // allocation (grown when needed; sz / off as witness_segments fills them); bind: the context's view, once the segments are written
 int tx_witness_reserve(cstark_ctx *c, size_t n, size_t d, size_t *sz, size_t *off);

@@ -7,6 +7,8 @@
 //                     nodes' last versions into the stored nodes
 // One launch per level, ordered by the stream: every input of a launch was written by an earlier launch or by the upload, so no
 // workgroup ever waits for another one.
+// cstark_ledger_apply_checked puts the signature check (trace_gen.hip, launch_signature_check) between the host plan and the first
+// change: the plan's balance walk builds the message every transfer signs, the check runs in scratch of the context.
 #include <string.h>
 #include <new>
 #include "../../include/cstark.h"
@@ -168,7 +170,7 @@ int root_impl(cstark_ledger *L, uint64_t *root) {
 }
 
 int apply_impl(cstark_ledger *L, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices, const uint64_t *deltas, const uint64_t *sig_rx,
-               const uint8_t *sig_s, cstark_tx_witness *out, int32_t *refused_at, int32_t *reason) {
+               const uint8_t *sig_s, cstark_tx_witness *out, int32_t *refused_at, int32_t *reason, bool check_signatures) {
     cstark_ctx *c = L->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t d = L->index.depth, ne = 2 * n_tx;
@@ -178,8 +180,22 @@ int apply_impl(cstark_ledger *L, uint32_t n_tx, const uint64_t *s_indices, const
     while (cap < (uint64_t)L->index.n_stored + new_nodes) cap *= 2;
     if (EMPTY_SLOTS + cap > MAX_POOL_SLOTS) return fail(CSTARK_ERR_UNSUPPORTED, "ledger: the batch needs more than 2^28 digest slots");
     Plan p;
-    if (!plan_apply(L->index, (uint32_t)(EMPTY_SLOTS + cap), n_tx, s_indices, r_indices, deltas, p))
+    std::vector<uint64_t> messages;
+    if (!plan_apply(L->index, (uint32_t)(EMPTY_SLOTS + cap), n_tx, s_indices, r_indices, deltas, p, check_signatures ? &messages : nullptr))
         return fail(CSTARK_ERR_UNSUPPORTED, "cstark_ledger_apply: the batch is too large to plan");
+    // cstark_ledger_apply_checked: the signatures of the transfers the plan accepted, all of them or those before its refusal, in the
+    // context's own scratch and ahead of every change; the first bad one refuses the batch
+    const uint32_t n_signed = (uint32_t)(messages.size() / 28);
+    if (n_signed) {
+        std::vector<uint8_t> verdicts(n_signed);
+        RC_TRY(signature_check(c, "cstark_ledger_apply_checked", n_signed, messages.data(), sig_rx, sig_s, verdicts.data(), nullptr));
+        for (uint32_t t = 0; t < n_signed; t++)
+            if (verdicts[t] != CSTARK_SIG_VALID) {
+                *refused_at = (int32_t)t;
+                *reason = REASON_SIGNATURE;
+                return CSTARK_OK;
+            }
+    }
     *refused_at = p.refused_at;
     *reason = p.reason;
     if (p.refused_at >= 0) return CSTARK_OK;
@@ -272,8 +288,9 @@ int cstark_ledger_root(cstark_ctx *c, cstark_ledger *L, uint64_t root[7]) {
     return guard(L, root_impl(L, root));
 }
 
-int cstark_ledger_apply(cstark_ctx *c, cstark_ledger *L, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices, const uint64_t *deltas,
-                        const uint64_t *sig_rx, const uint8_t *sig_s, cstark_tx_witness *out, int32_t *refused_at, int32_t *reason) {
+// cstark_ledger_apply and cstark_ledger_apply_checked: one argument contract
+static int apply_entry(cstark_ctx *c, cstark_ledger *L, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices, const uint64_t *deltas,
+                       const uint64_t *sig_rx, const uint8_t *sig_s, cstark_tx_witness *out, int32_t *refused_at, int32_t *reason, bool check_signatures) {
     RC_TRY(usable(c, L, "cstark_ledger_apply"));
     if (n_tx == 0 || n_tx > MAX_TRANSFERS || !s_indices || !r_indices || !deltas || !sig_rx || !sig_s || !refused_at || !reason)
         return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_apply: bad argument");
@@ -285,7 +302,17 @@ int cstark_ledger_apply(cstark_ctx *c, cstark_ledger *L, uint32_t n_tx, const ui
     }
     for (uint32_t t = 0; t < n_tx; t++)
         if (deltas[t] >= cs::host::P) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_apply: a delta is not a reduced field element");
-    return guard(L, apply_impl(L, n_tx, s_indices, r_indices, deltas, sig_rx, sig_s, out, refused_at, reason));
+    return guard(L, apply_impl(L, n_tx, s_indices, r_indices, deltas, sig_rx, sig_s, out, refused_at, reason, check_signatures));
+}
+
+int cstark_ledger_apply(cstark_ctx *c, cstark_ledger *L, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices, const uint64_t *deltas,
+                        const uint64_t *sig_rx, const uint8_t *sig_s, cstark_tx_witness *out, int32_t *refused_at, int32_t *reason) {
+    return apply_entry(c, L, n_tx, s_indices, r_indices, deltas, sig_rx, sig_s, out, refused_at, reason, false);
+}
+
+int cstark_ledger_apply_checked(cstark_ctx *c, cstark_ledger *L, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices, const uint64_t *deltas,
+                                const uint64_t *sig_rx, const uint8_t *sig_s, cstark_tx_witness *out, int32_t *refused_at, int32_t *reason) {
+    return apply_entry(c, L, n_tx, s_indices, r_indices, deltas, sig_rx, sig_s, out, refused_at, reason, true);
 }
 
 } // extern "C"

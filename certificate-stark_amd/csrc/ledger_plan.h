@@ -40,7 +40,7 @@ struct Emit { uint32_t slot, word; };
 static_assert(sizeof(Job) == 16 && sizeof(Emit) == 8, "lists are copied to the device as they are");
 
 // cstark_ledger_reason (include/cstark.h)
-enum Reason : int32_t { REASON_NONE = 0, REASON_INDEX = 1, REASON_SELF = 2, REASON_ABSENT = 3, REASON_BALANCE = 4 };
+enum Reason : int32_t { REASON_NONE = 0, REASON_INDEX = 1, REASON_SELF = 2, REASON_ABSENT = 3, REASON_BALANCE = 4, REASON_SIGNATURE = 5 };
 
 typedef std::array<uint64_t, 14> Value; // pk.x(6) pk.y(6) balance nonce, memory form
 
@@ -144,7 +144,12 @@ inline bool plan_set_accounts(const Index &ix, uint32_t scratch_base, uint32_t c
 // cstark_ledger_apply: the balance walk with its refusals, the per-level predecessor map, the jobs of the depth + 1 launches and the
 // two emit lists.  A refusal sets refused_at / reason and nothing else.  false: the batch is too large to plan.
 // Deltas are reduced field elements (the caller checks).  Witness word offsets are those of witness_segments(n_tx, depth).
-inline bool plan_apply(const Index &ix, uint32_t scratch_base, uint32_t n_tx, const uint64_t *s_idx, const uint64_t *r_idx, const uint64_t *deltas, Plan &p) {
+// messages (optional, cstark_ledger_apply_checked): the message every transfer signs, 28 words each (build_tx_message, src/lib.rs:467-481:
+// sender's key, receiver's key, delta, sender's nonce, two zeros), keys and nonce as the walk holds them BEFORE the transfer, that is as
+// the transfers before it in the same batch leave them.  One message per transfer that passed the four refusal tests: all n_tx of an
+// applied batch, the transfers [0, refused_at) of a refused one.
+inline bool plan_apply(const Index &ix, uint32_t scratch_base, uint32_t n_tx, const uint64_t *s_idx, const uint64_t *r_idx, const uint64_t *deltas, Plan &p,
+                       std::vector<uint64_t> *messages = nullptr) {
     using namespace cs::host;
     const uint32_t d = ix.depth, ne = 2 * n_tx;
     const uint64_t size = (uint64_t)1 << d;
@@ -176,6 +181,12 @@ inline bool plan_apply(const Index &ix, uint32_t scratch_base, uint32_t n_tx, co
         Value *sv = value_of(si), *rv = value_of(ri);
         if (!sv || !rv) return refuse(t, REASON_ABSENT);
         if (to_u64(delta) > to_u64((*sv)[12])) return refuse(t, REASON_BALANCE);
+        if (messages) {
+            messages->insert(messages->end(), sv->begin(), sv->begin() + 12);
+            messages->insert(messages->end(), rv->begin(), rv->begin() + 12);
+            const uint64_t tail[4] = {delta, (*sv)[13], 0, 0};
+            messages->insert(messages->end(), tail, tail + 4);
+        }
         for (int k = 0; k < 2; k++) {
             const uint32_t e = 2 * t + k;
             const uint64_t a = k ? ri : si;

@@ -39,4 +39,12 @@ hipError_t launch_schnorr_trace_split(const TxWitnessDev &w, uint64_t *d_trace, 
 // the 19 public-input columns of SchnorrAir (pkey x12, message chunks x7; src/schnorr/air.rs:228-290): 19 x 512*n
 hipError_t launch_schnorr_aux_columns(const TxWitnessDev &w, uint64_t *d_out, hipStream_t stream);
 
+// verify_signature (src/schnorr/mod.rs:220-245) for `count` signatures, the trace's own programs run for their verdict: message hash
+// (four per wave) -> d_h_limbs [count][4]; 2 * count single-wave ladders -> d_points [2 * count][18]; complete addition, affine x and
+// verdict -> d_verdicts [count] (the values of cstark_sig_verdict, below), d_rx_out [count][6] (may be null).  d_messages [count][28],
+// d_sig_rx [count][6], d_sig_s [count][32]; every pointer is device memory and nothing of a TxWitnessDev is read or written.
+enum : uint8_t { SIG_VALID = 0, SIG_MISMATCH = 1, SIG_KEY_NOT_ON_CURVE = 2, SIG_SCALAR_RANGE = 3 };
+hipError_t launch_signature_check(const uint64_t *d_messages, const uint64_t *d_sig_rx, const uint8_t *d_sig_s, uint64_t *d_h_limbs, uint64_t *d_points,
+                                  uint8_t *d_verdicts, uint64_t *d_rx_out, uint32_t count, hipStream_t stream);
+
 } // namespace cs

@@ -795,4 +795,118 @@ hipError_t launch_range_trace_bits(const uint64_t *d_words, fp *d_prefix, fp *d_
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Signature check (cstark_schnorr_check_signatures): verify_signature (src/schnorr/mod.rs:220-245) for `count` signatures.  The
+// programs of the SchnorrAir trace run for their verdict: the same message hash, the same two ladders (run_ladder_op) and the same
+// complete addition and affine x (run_full_add, fp6_inv) as k_trace_schnorr_hash / _ec / _final, without a staging tile and without a
+// trace store.  The values are therefore the trace's: the x that k_sig_final compares is registers 0..5 of row 511.
+namespace {
+
+// h = hash_message(R.x, message) as four canonical limbs.  14 lanes carry a hash: FOUR hashes per wave, as in k_ledger_merge (lanes
+// 0..55 = (hash s, state element e); lanes 56..63 and the hashes of a partial last group only take part in the barriers).
+__global__ __launch_bounds__(64) void k_sig_hash(const fp *__restrict__ messages, const fp *__restrict__ sig_rx, uint64_t *__restrict__ h_limbs,
+                                                 uint32_t count) {
+    __shared__ fp st[4][14];
+    const int lane = threadIdx.x;
+    const bool is_state = lane < 56;
+    const int s = is_state ? lane / 14 : 0, e = is_state ? lane % 14 : 0;
+    const uint32_t t = 4 * blockIdx.x + s;
+    const bool active = is_state && t < count;
+    fp mrow[14];
+#pragma unroll
+    for (int j = 0; j < 14; j++) mrow[j] = c_mds[e * 14 + j];
+    const fp *msg = messages + 28 * (size_t)(active ? t : 0);
+    fp v = (active && e < 6) ? sig_rx[6 * (size_t)t + e] : 0; // init_sig_verification_state, src/schnorr/trace.rs:18-30
+    for (int step = 0; step < 39; step++) {                   // the steps of k_trace_schnorr_hash up to the one that yields h
+        const int cyc = step & 7;
+        if (cyc < 7) v = rescue_round_lane(v, st[s], mrow, e, cyc, active);
+        else if (active && e >= 7) v = msg[7 * (step >> 3) + e - 7]; // message chunk, src/lib.rs:467-481 layout
+    }
+    if (active && e < 4) h_limbs[4 * (size_t)t + e] = fp_to_u64(v);
+}
+
+// grid = 2 * count workgroups of ONE wave, as k_trace_schnorr_ec: workgroup 2t is the ladder s*G of signature t, 2t + 1 the ladder
+// h*P with P = message[0..12].  Each leaves its final (X, Y, Z) in points[2t + g][18]: what the trace holds in row 510.
+__global__ __launch_bounds__(64) void k_sig_ladder(const fp *__restrict__ messages, const uint8_t *__restrict__ sig_s, const uint64_t *__restrict__ h_limbs,
+                                                   fp *__restrict__ points, uint32_t count) {
+    if (blockIdx.x >= 2 * count) return; // uniform over the workgroup, ahead of every barrier
+    __shared__ fp slots[NSLOT][6];
+    __shared__ Fp2 prods[LROLE][6];
+    __shared__ uint8_t sbytes[32];
+    __shared__ LadderLds pg;
+    const uint32_t t = blockIdx.x >> 1;
+    const int g = blockIdx.x & 1, lane = threadIdx.x;
+    fp(*slot)[6] = slots;
+    load_programs(pg, lane, 64);
+    const fp *key = messages + 28 * (size_t)t;
+    if (lane < 32) sbytes[lane] = g == 0 ? sig_s[32 * (size_t)t + lane] : (uint8_t)(h_limbs[4 * (size_t)t + (lane >> 3)] >> (8 * (lane & 7)));
+    if (lane < 6) {
+        slot[SX][lane] = 0;
+        slot[SY][lane] = lane == 0 ? FP_ONE : 0;
+        slot[SZ][lane] = 0;
+        slot[SB3][lane] = c_b3[lane];
+        slot[SPX][lane] = g == 0 ? c_generator[lane] : key[lane];
+        slot[SPY][lane] = g == 0 ? c_generator[6 + lane] : key[6 + lane];
+        slot[26][lane] = fp_add(slot[SPX][lane], slot[SPY][lane]);
+        slot[SW][lane] = 0;
+    }
+    __syncthreads();
+    if (lane < 2) fp6_store(slot[SK + lane], fp6_mul(fp6_load(slot[SB3]), fp6_load(slot[SPX + lane])));
+    __syncthreads();
+    for (int i = 254; i >= 0; i--) { // bits 254..0, MSB first (src/schnorr/trace.rs:79-82): bit 255 is never read
+        run_ladder_op<OP_DOUBLE>(pg, slot, prods, lane);
+        if (bit_le(sbytes, i)) run_ladder_op<OP_ADD_MIXED>(pg, slot, prods, lane); // uniform over the wave
+    }
+    if (lane < 18) points[18 * (size_t)blockIdx.x + lane] = slot[lane / 6][lane % 6];
+}
+
+// One wave per signature: S = s*G + h*P by the complete addition, x = X / Z (what k_trace_schnorr_final writes to row 511), then the
+// verdict (cstark_sig_verdict): bit 255 of s, the curve equation of the key as 3 (y^2 - x^3 - x) = 3B, x against R.x.  Z = 0 -- the
+// point at infinity -- is a mismatch whatever fp6_inv makes of it.  rx_out (optional) gets x for every signature.
+__global__ __launch_bounds__(64) void k_sig_final(const fp *__restrict__ messages, const fp *__restrict__ sig_rx, const uint8_t *__restrict__ sig_s,
+                                                  const fp *__restrict__ points, uint8_t *__restrict__ verdicts, fp *__restrict__ rx_out, uint32_t count) {
+    if (blockIdx.x >= count) return; // uniform over the workgroup, ahead of every barrier
+    __shared__ fp slots[QZ + 1][6];
+    __shared__ Fp2 prods[FROLE][6];
+    __shared__ FullLds pg;
+    const uint32_t t = blockIdx.x;
+    const int lane = threadIdx.x;
+    load_programs(pg, lane, 64);
+    if (lane < 18) {
+        slots[lane / 6][lane % 6] = points[36 * (size_t)t + lane];
+        slots[QX + lane / 6][lane % 6] = points[36 * (size_t)t + 18 + lane];
+    }
+    if (lane < 6) slots[SB3][lane] = c_b3[lane];
+    __syncthreads();
+    run_full_add(pg, slots, prods, lane);
+    if (lane != 0) return;
+    const Fp6 z = fp6_load(slots[SZ]);
+    bool match = false;
+#pragma unroll
+    for (int i = 0; i < 6; i++) match |= z.c[i] != 0; // infinity never matches
+    const Fp6 x = fp6_mul(fp6_load(slots[SX]), fp6_inv(z));
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        match &= x.c[i] == sig_rx[6 * (size_t)t + i];
+        if (rx_out) rx_out[6 * (size_t)t + i] = x.c[i];
+    }
+    const Fp6 kx = fp6_load(messages + 28 * (size_t)t), ky = fp6_load(messages + 28 * (size_t)t + 6);
+    const Fp6 d = fp6_sub(fp6_sub(fp6_sqr(ky), fp6_mul(fp6_sqr(kx), kx)), kx);
+    const Fp6 d3 = fp6_add(fp6_dbl(d), d);
+    bool on_curve = true;
+#pragma unroll
+    for (int i = 0; i < 6; i++) on_curve &= d3.c[i] == c_b3[i];
+    verdicts[t] = (sig_s[32 * (size_t)t + 31] >> 7) ? SIG_SCALAR_RANGE : !on_curve ? SIG_KEY_NOT_ON_CURVE : !match ? SIG_MISMATCH : SIG_VALID;
+}
+
+} // namespace
+
+hipError_t launch_signature_check(const uint64_t *d_messages, const uint64_t *d_sig_rx, const uint8_t *d_sig_s, uint64_t *d_h_limbs, uint64_t *d_points,
+                                  uint8_t *d_verdicts, uint64_t *d_rx_out, uint32_t count, hipStream_t stream) {
+    hipLaunchKernelGGL(k_sig_hash, dim3((count + 3) / 4), dim3(64), 0, stream, d_messages, d_sig_rx, d_h_limbs, count);
+    hipLaunchKernelGGL(k_sig_ladder, dim3(2 * count), dim3(64), 0, stream, d_messages, d_sig_s, (const uint64_t *)d_h_limbs, d_points, count);
+    hipLaunchKernelGGL(k_sig_final, dim3(count), dim3(64), 0, stream, d_messages, d_sig_rx, d_sig_s, (const fp *)d_points, d_verdicts, d_rx_out, count);
+    return hipGetLastError();
+}
+
 } // namespace cs

@@ -112,8 +112,9 @@ class Ledger:
     """The account tree an operator holds, resident on the GPU (cstark_ledger_*): set_accounts, then apply(transfers) per batch -- the
     counterpart of the sequential loop of TransactionMetadata::build_random (src/lib.rs:341-422) on real accounts and transfers.
     apply() leaves the batch's witness resident in the backend: backend.prove(options) follows without an upload."""
-    INDEX_RANGE, SELF_TRANSFER, ABSENT, BALANCE = 1, 2, 3, 4
-    REASONS = {1: "index out of range", 2: "sender equals receiver", 3: "account absent", 4: "delta above the sender's balance"}
+    INDEX_RANGE, SELF_TRANSFER, ABSENT, BALANCE, SIGNATURE = 1, 2, 3, 4, 5
+    REASONS = {1: "index out of range", 2: "sender equals receiver", 3: "account absent", 4: "delta above the sender's balance",
+               5: "signature does not verify"}
 
     def __init__(self, depth=15, backend=None):
         self.backend = backend or Backend()
@@ -142,14 +143,18 @@ class Ledger:
         """-> (values [count][14], present [count])"""
         return self.backend.ledger_get_accounts(self._led, indices)
 
-    def apply(self, transfers, want_witness=True):
+    def apply(self, transfers, want_witness=True, check_signatures=False):
         """transfers: (s_indices, r_indices, deltas, sig_rx, sig_s) or an object with these attributes (a TransactionMetadata, say).
         Applies them in order and returns the batch's TransactionMetadata (None with want_witness=False: the witness stays on the
         device only); raises TransferRefused, with ledger and resident witness unchanged, at the first transfer that cannot be applied.
-        Signatures are copied through, not checked."""
+        By default signatures are copied through, not checked -- and TransactionAir does not bind them either: a batch with a forged
+        signature still proves and verifies.  check_signatures=True (cstark_ledger_apply_checked) checks every transfer's signature on
+        the device first, against the message the transfer signs (sender's key, receiver's key, delta, the sender's nonce as the
+        transfers before it leave it), and refuses the batch with reason SIGNATURE at the first bad one."""
         if hasattr(transfers, "s_indices"):
             transfers = tuple(getattr(transfers, f) for f in ("s_indices", "r_indices", "deltas", "sig_rx", "sig_s"))
-        at, reason, arrays = self.backend.ledger_apply(self._led, self.depth, *transfers, want_witness=want_witness)
+        at, reason, arrays = self.backend.ledger_apply(self._led, self.depth, *transfers, want_witness=want_witness,
+                                                       check_signatures=check_signatures)
         if at >= 0:
             raise TransferRefused(at, reason)
         return None if arrays is None else TransactionMetadata(*[arrays[f] for f in TransactionMetadata.FIELDS])
@@ -334,6 +339,11 @@ class SchnorrExample(_ResidentWitness):
         """The witness is uploaded by the first call and stays resident (_ResidentWitness: read-only on the host until invalidate())."""
         self._ensure_resident(lambda: self.backend.upload_schnorr_witness(self.messages, self.sig_rx, self.sig_s))
         return self.backend.air_prove(Backend.AIR_SCHNORR, self.options)
+
+    def check(self):
+        """verify_signature (src/schnorr/mod.rs:220-245) for every signature of this example, on the device: verdicts uint8 [n]
+        (Backend.SIG_*: 0 = valid).  Runs beside a resident witness without touching it."""
+        return self.backend.schnorr_check(self.messages, self.sig_rx, self.sig_s)
 
     def verify(self, proof):
         """src/schnorr/mod.rs:175-186 through cstark_schnorr_verify: the statement is every message and signature of this example; the

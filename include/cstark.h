@@ -433,6 +433,27 @@ int cstark_tx_witness_generate(cstark_tx_witness *w, uint64_t seed);
 /* n_sig messages [n][28] (public key || 16 elements) with their signatures (R.x [n][6], s [n][32]). */
 int cstark_schnorr_witness_generate(uint32_t n_sig, uint64_t seed, uint64_t *messages, uint64_t *sig_rx, uint8_t *sig_s);
 
+/* ---- signature check: verify_signature (src/schnorr/mod.rs:220-245) on the device, for its verdict ---------------------------------
+ * Where several verdicts apply, the verdict is the first of SCALAR_RANGE, KEY_NOT_ON_CURVE, MISMATCH.  The order of the curve's scalar
+ * field is stated nowhere in the reference tree (csrc/witness_gen.hip), so s < 2^255 is the ONLY range rule: a scalar at or above the
+ * group order is not refused for that, it is used by its bits 254..0 exactly as the SchnorrAir trace uses it. */
+typedef enum cstark_sig_verdict {
+    CSTARK_SIG_VALID = 0,
+    CSTARK_SIG_MISMATCH = 1,          /* x(s*G + h*P) != R.x, or the sum is the point at infinity */
+    CSTARK_SIG_KEY_NOT_ON_CURVE = 2,  /* message[0..12] is no affine point of the curve (the reference asserts this, mod.rs:228) */
+    CSTARK_SIG_SCALAR_RANGE = 3       /* bit 255 of s set: the ladders read bits 254..0 only */
+} cstark_sig_verdict;
+/* verify_signature for `count` signatures (1 .. 2^20).  messages [count][28] (public key || 16 elements), sig_rx [count][6] (memory
+ * form), sig_s [count][32] little-endian; verdicts [count] (cstark_sig_verdict); rx_out (optional) [count][6]: the affine x of
+ * s*G + h*P as the SchnorrAir trace holds it in registers 0..5 of row 511, written for every signature whatever its verdict.  All
+ * arrays are host memory.  Null messages, sig_rx, sig_s or verdicts, count == 0, count > 2^20, or a messages / sig_rx word >= p is
+ * CSTARK_ERR_INVALID_ARG before anything is launched and with the outputs untouched; cstark_last_error names the first such word.
+ * Synchronous, on the context's stream, in device scratch of its own that the context keeps and frees: the resident witness
+ * (cstark_tx_witness_upload, cstark_schnorr_witness_upload, cstark_ledger_apply) is neither read nor written, so a proof after a check
+ * is the proof without it. */
+int cstark_schnorr_check_signatures(cstark_ctx *ctx, uint32_t count, const uint64_t *messages, const uint64_t *sig_rx,
+                                    const uint8_t *sig_s, uint8_t *verdicts, uint64_t *rx_out);
+
 /* ---- account ledger: the witness from what an operator holds (replaces the sequential loop of TransactionMetadata::build_random,
  * src/lib.rs:341-422: record the root and the sender's path, apply the transfer, re-hash two leaf-to-root paths, record the receiver's
  * path) ------------------------------------------------------------------------------------------------------------------------------
@@ -447,13 +468,14 @@ typedef struct cstark_ledger cstark_ledger;
 /* why cstark_ledger_apply refused a batch.  Transfers are examined in transfer order, each against the accounts as the transfers before
  * it in the same batch leave them; the batch is refused at the first transfer that matches a reason, with the first reason in this
  * order that this transfer matches: either index out of range, then sender equals receiver, then either account absent, then the
- * balance. */
+ * balance, then (cstark_ledger_apply_checked only) the signature. */
 typedef enum cstark_ledger_reason {
     CSTARK_LEDGER_APPLIED = 0,
     CSTARK_LEDGER_INDEX_RANGE = 1,  /* an index >= 2^merkle_depth */
     CSTARK_LEDGER_SELF_TRANSFER = 2, /* sender equals receiver */
     CSTARK_LEDGER_ABSENT = 3,       /* sender or receiver has no account */
-    CSTARK_LEDGER_BALANCE = 4       /* delta above the sender's balance, both as canonical integers */
+    CSTARK_LEDGER_BALANCE = 4,      /* delta above the sender's balance, both as canonical integers */
+    CSTARK_LEDGER_SIGNATURE = 5     /* cstark_ledger_apply_checked only: the transfer's signature has another verdict than CSTARK_SIG_VALID */
 } cstark_ledger_reason;
 /* An empty tree of depth 1, 3, 7, 15 or 31 (the depths cstark_tx_witness_upload accepts).  Destroy it before its context. */
 int cstark_ledger_create(cstark_ctx *ctx, uint32_t merkle_depth, cstark_ledger **out);
@@ -468,14 +490,28 @@ int cstark_ledger_root(cstark_ctx *ctx, cstark_ledger *ledger, uint64_t root[7])
 /* Applies n_tx transfers in order with the reference's arithmetic (sender balance - delta, sender nonce + 1, receiver balance + delta:
  * field operations, src/lib.rs:373-375), advances the ledger and leaves the batch's witness RESIDENT in the context exactly as
  * cstark_tx_witness_upload would: cstark_tx_build_trace / cstark_tx_prove / cstark_air_prove follow without an upload.  Roots, paths
- * and old values are written on the device; indices, deltas and signatures (sig_rx [n_tx][6], sig_s [n_tx][32]) are copied through --
- * signatures are NOT checked here, a wrong one yields a proof the verifier rejects.  out (optional): a witness whose arrays the caller
- * allocated for (n_tx, merkle_depth), filled with all eleven fields.
+ * and old values are written on the device; indices, deltas and signatures (sig_rx [n_tx][6], sig_s [n_tx][32]) are copied through.
+ * Signatures are NOT checked here, and nothing later checks them either: TransactionAir asserts the four root values only
+ * (src/air.rs:175-184) and a forged signature satisfies every transition constraint, so a batch with a wrong signature still proves and
+ * the proof still verifies.  An operator who must enforce signatures calls cstark_ledger_apply_checked.  out (optional): a witness whose
+ * arrays the caller allocated for (n_tx, merkle_depth), filled with all eleven fields.
  * Refusal is not a failure: the status is CSTARK_OK, *refused_at = the first offending transfer (-1: none) and *reason its
  * cstark_ledger_reason; a refused batch changes neither the ledger nor the resident witness (and `out` is not written). */
 int cstark_ledger_apply(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices,
                         const uint64_t *deltas, const uint64_t *sig_rx, const uint8_t *sig_s, cstark_tx_witness *out,
                         int32_t *refused_at, int32_t *reason);
+/* The same call with the same arguments and contract, and every transfer's signature checked before anything is applied
+ * (cstark_schnorr_check_signatures).  The message of transfer t is build_tx_message (src/lib.rs:467-481): the sender's key (12 words),
+ * the receiver's key (12 words), delta, the sender's nonce, two zeros -- keys and nonce as the transfers before t in the same batch
+ * leave the accounts.  Transfers are examined in transfer order; within a transfer the four reasons above come first, then
+ * CSTARK_LEDGER_SIGNATURE (any verdict other than CSTARK_SIG_VALID).  So a batch whose first unappliable transfer is k is refused at
+ * the first transfer below k with a bad signature, else at k with its own reason; an appliable batch is refused at its first bad
+ * signature.  A sig_rx word >= p of an examined transfer is CSTARK_ERR_INVALID_ARG.  The check runs in scratch of the context, ahead of
+ * every change: a refused batch changes neither the ledger nor the resident witness nor `out`; a batch whose signatures are all valid
+ * is applied exactly as cstark_ledger_apply applies it. */
+int cstark_ledger_apply_checked(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices,
+                                const uint64_t *deltas, const uint64_t *sig_rx, const uint8_t *sig_s, cstark_tx_witness *out,
+                                int32_t *refused_at, int32_t *reason);
 
 /* ---- verification (TransactionExample::verify, src/lib.rs:144-150: winterfell::verify over this library's own proof layout) -------
  * The call's status (cstark_status) is kept apart from the proof's verdict.  A verdict names the FIRST check that fails, in this

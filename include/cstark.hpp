@@ -215,8 +215,15 @@ class Ledger {
         if (present) *present = have;
         return values;
     }
-    // applies the transfers in order; throws TransferRefused (nothing changed) at the first one that cannot be applied
-    TransactionMetadata apply(const Transfers &t) {
+    // applies the transfers in order; throws TransferRefused (nothing changed) at the first one that cannot be applied.  Signatures are
+    // copied through unchecked, and TransactionAir does not bind them: a forged one still proves and verifies (apply_checked)
+    TransactionMetadata apply(const Transfers &t) { return apply(t, false); }
+    // the same with every transfer's signature checked on the device first (cstark_ledger_apply_checked): TransferRefused with reason
+    // CSTARK_LEDGER_SIGNATURE at the first transfer whose signature does not verify
+    TransactionMetadata apply_checked(const Transfers &t) { return apply(t, true); }
+
+  private:
+    TransactionMetadata apply(const Transfers &t, bool check_signatures) {
         const size_t n = t.s_indices.size();
         if (n == 0 || t.r_indices.size() != n || t.deltas.size() != n || t.sig_rx.size() != n || t.sig_s.size() != n)
             throw Error(CSTARK_ERR_INVALID_ARG, "transfer vectors are not of equal length");
@@ -226,13 +233,11 @@ class Ledger {
         m.s_paths.resize(n * (depth_ + 1) * 7); m.r_paths.resize(n * (depth_ + 1) * 7); m.deltas.resize(n); m.sig_rx.resize(n); m.sig_s.resize(n);
         cstark_tx_witness w = m.view();
         int32_t at = -1, reason = 0;
-        check(cstark_ledger_apply(ctx_.raw(), led_, (uint32_t)n, t.s_indices.data(), t.r_indices.data(), t.deltas.data(), t.sig_rx[0].data(),
-                                  t.sig_s[0].data(), &w, &at, &reason));
+        check((check_signatures ? cstark_ledger_apply_checked : cstark_ledger_apply)(ctx_.raw(), led_, (uint32_t)n, t.s_indices.data(), t.r_indices.data(),
+                                                                                     t.deltas.data(), t.sig_rx[0].data(), t.sig_s[0].data(), &w, &at, &reason));
         if (at >= 0) throw TransferRefused(at, reason);
         return m;
     }
-
-  private:
     Context &ctx_;
     unsigned depth_;
     cstark_ledger *led_ = nullptr;
@@ -465,6 +470,20 @@ class RescueExample {
     mutable bool have_result_ = false;
     Context &ctx_;
 };
+// verify_signature (src/schnorr/mod.rs:220-245) on the device for every signature: messages [n][28], sig_rx [n][6], sig_s [n][32] ->
+// one cstark_sig_verdict each (CSTARK_SIG_VALID = 0); rx_out (optional): the affine x of s*G + h*P, [n][6].  A resident witness is
+// not touched.
+inline std::vector<uint8_t> schnorr_check(Context &ctx, const std::vector<BaseElement> &messages, const std::vector<BaseElement> &sig_rx,
+                                          const std::vector<uint8_t> &sig_s, std::vector<BaseElement> *rx_out = nullptr) {
+    const size_t n = messages.size() / 28;
+    if (n == 0 || messages.size() != 28 * n || sig_rx.size() != 6 * n || sig_s.size() != 32 * n)
+        throw Error(CSTARK_ERR_INVALID_ARG, "signature vectors are not of equal length");
+    std::vector<uint8_t> verdicts(n);
+    if (rx_out) rx_out->resize(6 * n);
+    check(cstark_schnorr_check_signatures(ctx.raw(), (uint32_t)n, messages.data(), sig_rx.data(), sig_s.data(), verdicts.data(),
+                                          rx_out ? rx_out->data() : nullptr));
+    return verdicts;
+}
 // schnorr::SchnorrExample (src/schnorr/mod.rs:52-186)
 class SchnorrExample {
   public:
@@ -477,6 +496,8 @@ class SchnorrExample {
         check(cstark_schnorr_witness_upload(ctx_.raw(), n, messages.data(), sig_rx.data(), sig_s.data()));
         return detail::air_prove(ctx_, CSTARK_AIR_SCHNORR, options_, 0, (size_t)n * 512);
     }
+    // verify_signature for every signature held here: one cstark_sig_verdict each
+    std::vector<uint8_t> check_signatures() const { return schnorr_check(ctx_, messages, sig_rx, sig_s); }
     // src/schnorr/mod.rs:175-186 through cstark_schnorr_verify: the statement is every message and signature held here; throws
     // VerifierError on rejection
     void verify(const std::vector<uint8_t> &proof) const {
