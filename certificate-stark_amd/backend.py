@@ -138,6 +138,48 @@ class Backend:
         check(self.lib.cstark_ledger_root(self.ctx, led, self._hptr(root)))
         return root
 
+    def ledger_open_accounts(self, led, depth, indices):
+        """cstark_ledger_open_accounts: -> (values [count][14], present bool [count], paths [count][depth + 1][7], root [7]): the
+        accounts as ledger_get_accounts gives them and their authentication paths under the current root, in the witness's path form
+        (absent accounts: an all-zero leaf).  Read-only: the ledger and the resident witness are as before."""
+        idx = _np_u64(indices).reshape(-1)
+        n = idx.size
+        val, present = np.zeros((n, 14), np.uint64), np.zeros(n, np.uint8)
+        paths, root = np.zeros((n, depth + 1, 7), np.uint64), np.zeros(7, np.uint64)
+        check(self.lib.cstark_ledger_open_accounts(self.ctx, led, C.c_uint32(n), self._hptr(idx), self._hptr(val), self._hptr(present, u8p),
+                                                   self._hptr(paths), self._hptr(root)))
+        return val, present.astype(bool), paths, root
+
+    PATH_VALID, PATH_INDEX_RANGE, PATH_LEAF, PATH_ROOT = 0, 1, 2, 3   # cstark_path_verdict
+
+    def account_check_paths(self, indices, paths, roots, values=None, present=None, want_roots=False):
+        """cstark_account_check_paths: folds every path ([count][depth + 1][7], any depth 1 .. 31) to a root on the device, one launch ->
+        verdicts uint8[count] (cstark_path_verdict); with want_roots also the folded roots, uint64 [count][7], whatever the verdict.
+        roots: one root [7] for all paths or one per path [count][7].  values [count][14] (and optionally present [count]): the leaf
+        entry is checked against the account; without values the paths are paths of digests.  No ledger is needed and the resident
+        witness is not touched."""
+        idx = _np_u64(indices).reshape(-1)
+        n = idx.size
+        p = _np_u64(paths)
+        if p.ndim != 3 or p.shape[0] != n or p.shape[2] != 7 or p.shape[1] < 2:
+            raise ValueError("paths must be [count][depth + 1][7]")
+        r = _np_u64(roots).reshape(-1, 7)
+        val = None if values is None else _np_u64(values).reshape(-1, 14)
+        if val is not None and val.shape[0] != n:
+            raise ValueError("one 14-element value per path")
+        if present is not None and val is None:
+            raise ValueError("present without values")
+        pres = None if present is None else np.ascontiguousarray(present, np.uint8).reshape(-1)
+        if pres is not None and pres.size != n:
+            raise ValueError("one present flag per path")
+        verdicts = np.zeros(n, np.uint8)
+        out = np.zeros((n, 7), np.uint64) if want_roots else None
+        check(self.lib.cstark_account_check_paths(self.ctx, C.c_uint32(n), C.c_uint32(p.shape[1] - 1), self._hptr(idx),
+                                                  None if val is None else self._hptr(val), None if pres is None else self._hptr(pres, u8p),
+                                                  self._hptr(p), self._hptr(r), C.c_uint32(r.shape[0]), self._hptr(verdicts, u8p),
+                                                  self._hptr(out) if want_roots else None))
+        return (verdicts, out) if want_roots else verdicts
+
     def ledger_apply(self, led, depth, s_indices, r_indices, deltas, sig_rx, sig_s, want_witness=True, check_signatures=False):
         """cstark_ledger_apply: -> (refused_at, reason, arrays).  Applied (refused_at == -1): the batch's witness is resident in this
         backend (build_trace / prove / air_prove follow without an upload) and arrays is the dict of its eleven fields (None with

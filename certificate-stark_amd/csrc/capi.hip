@@ -551,6 +551,7 @@ void cstark_ctx_destroy(cstark_ctx *c) {
     if (c->rb_host) (void)hipHostFree(c->rb_host);
     if (c->tail_buf) (void)hipFree(c->tail_buf);
     if (c->sig_buf) (void)hipFree(c->sig_buf);
+    if (c->path_buf) (void)hipFree(c->path_buf);
     if (c->arena) cs::prove_arena_free(c->arena);
     if (c->verify) cs::verify_arena_free(c->verify);
     for (hipEvent_t e : c->part_ev) if (e) (void)hipEventDestroy(e);

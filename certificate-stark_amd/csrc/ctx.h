@@ -209,6 +209,8 @@ struct cstark_ctx {
     size_t rb_dev_bytes = 0, rb_host_bytes = 0;
     void *sig_buf = nullptr; // cstark_schnorr_check_signatures: its inputs, scratch and outputs on the device (never the resident witness)
     size_t sig_bytes = 0;
+    void *path_buf = nullptr; // cstark_account_check_paths (ledger.hip): its inputs and outputs on the device, likewise
+    size_t path_bytes = 0;
 };
 // internal (capi.hip): cstark_schnorr_check_signatures behind its null / count checks (cstark_ledger_apply_checked calls it with the
 // messages of ledger_plan.h).  `who` names the public call in the error text.

@@ -9,6 +9,10 @@
 // workgroup ever waits for another one.
 // cstark_ledger_apply_checked puts the signature check (trace_gen.hip, launch_signature_check) between the host plan and the first
 // change: the plan's balance walk builds the message every transfer signs, the check runs in scratch of the context.
+// The read side: cstark_ledger_open_accounts gathers authentication paths out of the pool (plan_open, k_ledger_gather, no hashing);
+// cstark_account_check_paths, which needs no ledger, folds paths to their roots:
+//   k_path_check      one path per 14 lanes: the leaf hash and all `depth` merges of a path in one launch
+#include <stdio.h>
 #include <string.h>
 #include <new>
 #include "../../include/cstark.h"
@@ -51,6 +55,60 @@ __global__ __launch_bounds__(256) void k_ledger_gather(const fp *pool, const led
     const uint32_t slot = list[m].slot;
     const size_t word = (size_t)list[m].word + k;
     if (slot < pool_slots && word < dst_words) dst[word] = pool[(size_t)7 * slot + k];
+}
+
+// cstark_account_check_paths: the leaf hash (with values) and the `depth` merges of one authentication path in ONE launch, in the shape
+// of k_ledger_merge: lanes 0..55 = (path s, state element e), lanes 56..63 and the paths of a partial last group only attend the
+// barriers.  After a permutation the digest sits in the lanes e < 7; the next state is (digest, sibling) or (sibling, digest) by the
+// index bit of the level, so the digest goes to the lanes e >= 7 by a cross-lane move that every lane executes and the bit selects
+// data only.  depth is uniform: every lane of the workgroup reaches every barrier.  The sibling of the next level is loaded ahead of
+// the permutation that precedes its use.  Every read is inside [0, count) paths of depth + 1 digests.
+__global__ __launch_bounds__(64) void k_path_check(const uint64_t *__restrict__ indices, const fp *__restrict__ values, const uint8_t *__restrict__ present,
+                                                   const fp *__restrict__ paths, const fp *__restrict__ roots, uint32_t n_roots, uint32_t count,
+                                                   uint32_t depth, uint8_t *__restrict__ verdicts, fp *__restrict__ roots_out) {
+    __shared__ fp st[4][14];
+    if (4 * blockIdx.x >= count) return; // the whole workgroup, ahead of its first barrier
+    const int lane = threadIdx.x;
+    const bool is_state = lane < 56;
+    const int s = is_state ? lane / 14 : 0, e = is_state ? lane % 14 : 0;
+    const bool low = e < 7;
+    const int w = low ? e : e - 7;     // the digest word this lane holds in either half
+    const int from = low ? lane : lane - 7;
+    const uint32_t i = 4 * blockIdx.x + s;
+    const bool active = is_state && i < count;
+    fp mrow[14];
+#pragma unroll
+    for (int k = 0; k < 14; k++) mrow[k] = c_mds[e * 14 + k];
+    const uint32_t bits = active ? (uint32_t)indices[i] : 0; // the fold reads bits 0 .. depth - 1 <= 30 only
+    const uint32_t at = 7 * (depth + 1) * (active ? i : 0) + w; // this lane's word of entry 0: below 2^20 * 32 * 7
+    fp cur = active ? paths[at] : 0;     // the stated leaf digest
+    fp sib = active ? paths[at + 7] : 0; // depth >= 1
+    unsigned long long leaf_bad = 0;
+    if (values) { // uniform
+        const bool have = active && (present ? present[i] != 0 : true);
+        fp v = active ? values[(size_t)14 * i + e] : 0;
+        for (int cyc = 0; cyc < 7; cyc++) v = rescue_round_lane(v, st[s], mrow, e, cyc, active);
+        leaf_bad = __ballot(active && low && cur != (have ? v : (fp)0));
+    }
+    for (uint32_t k = 0; k < depth; k++) {
+        const bool right = (bits >> k) & 1; // this node is the right child: the sibling is the left half
+        const fp moved = __shfl(cur, from, 64);
+        fp v = low == right ? sib : moved;
+        if (active && k + 1 < depth) sib = paths[at + 7 * (k + 2)];
+        for (int cyc = 0; cyc < 7; cyc++) v = rescue_round_lane(v, st[s], mrow, e, cyc, active);
+        cur = v;
+    }
+    fp stated = 0;
+    if (active && low) stated = roots[(size_t)7 * (n_roots == 1 ? 0 : i) + e];
+    const unsigned long long root_bad = __ballot(active && low && cur != stated);
+    if (active && low) roots_out[(size_t)7 * i + e] = cur;
+    if (active && e == 0) {
+        const unsigned long long mine = 0x7Full << (14 * s);
+        verdicts[i] = (indices[i] >> depth) ? CSTARK_PATH_INDEX_RANGE
+                      : (leaf_bad & mine) ? CSTARK_PATH_LEAF
+                      : (root_bad & mine) ? CSTARK_PATH_ROOT
+                                          : CSTARK_PATH_VALID;
+    }
 }
 
 } // namespace
@@ -227,6 +285,80 @@ int apply_impl(cstark_ledger *L, uint32_t n_tx, const uint64_t *s_indices, const
     return CSTARK_OK;
 }
 
+// one upload of the emit list, one gather into the staging area behind it, the paths and the root copied out: no hashing, and neither
+// the stored nodes nor the index nor the resident witness change (reserve_pool may move the pool)
+int open_impl(cstark_ledger *L, uint32_t count, const uint64_t *indices, uint64_t *values_out, uint8_t *present_out, uint64_t *paths_out, uint64_t *root_out) {
+    cstark_ctx *c = L->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint32_t d = L->index.depth;
+    uint32_t scratch_base;
+    RC_TRY(reserve_pool(L, 0, open_scratch_slots(d, count), &scratch_base));
+    Plan p;
+    if (!plan_open(L->index, scratch_base, count, indices, p) || p.pool_slots > L->pool_slots)
+        return fail(CSTARK_ERR_INVALID_ARG, "ledger: the opening exceeds the reserved pool");
+    uint64_t *block = L->pool + (size_t)7 * p.upload_slot, *stage = L->pool + (size_t)7 * p.stage_slot;
+    const uint32_t n = (uint32_t)p.witness.size();
+    HIP_TRY(hipMemcpyAsync(block, p.upload.data(), p.upload.size() * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(cs::k_ledger_gather, dim3((uint32_t)(((size_t)7 * n + 255) / 256)), dim3(256), 0, c->stream, L->pool,
+                       (const Emit *)(block + p.witness_word), n, (uint32_t)L->pool_slots, stage, (size_t)7 * n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(paths_out, stage, (size_t)56 * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(root_out, L->pool + (size_t)7 * p.final_root_slot, 56, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(cs::stream_wait(c->stream)); // the plan's host block is read by the upload
+    for (uint32_t i = 0; i < count; i++) {
+        const auto it = L->index.accounts.find(indices[i]);
+        present_out[i] = it != L->index.accounts.end();
+        if (present_out[i]) memcpy(values_out + (size_t)14 * i, it->second.data(), 112);
+        else memset(values_out + (size_t)14 * i, 0, 112);
+    }
+    return CSTARK_OK;
+}
+
+// cstark_account_check_paths behind its argument checks.  One device block of the context, grown when needed:
+//   indices [count] | values [count][14] | paths [count][depth + 1][7] | roots [n_roots][7] | roots_out [count][7] | present [count] | verdicts [count]
+// (values and present only when given).  Nothing of the resident witness, tail_buf or the statement caches is read or written.
+static_assert(sizeof(cstark_path_verdict) >= 1 && CSTARK_PATH_VALID == 0 && CSTARK_PATH_INDEX_RANGE == 1 && CSTARK_PATH_LEAF == 2 && CSTARK_PATH_ROOT == 3,
+              "k_path_check writes the values of cstark_path_verdict");
+int check_paths_impl(cstark_ctx *c, uint32_t count, uint32_t depth, const uint64_t *indices, const uint64_t *values, const uint8_t *present,
+                     const uint64_t *paths, const uint64_t *roots, uint32_t n_roots, uint8_t *verdicts, uint64_t *roots_out) {
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = count, path_words = (size_t)7 * (depth + 1) * n;
+    const size_t words = n + (values ? 14 * n : 0) + path_words + (size_t)7 * n_roots + 7 * n, bytes = words * 8 + 2 * n;
+    if (c->path_bytes < bytes) {
+        if (c->path_buf) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->path_buf)); c->path_buf = nullptr; c->path_bytes = 0; }
+        HIP_TRY(hipMalloc(&c->path_buf, bytes));
+        c->path_bytes = bytes;
+    }
+    uint64_t *d_idx = (uint64_t *)c->path_buf, *d_val = d_idx + n, *d_paths = d_val + (values ? 14 * n : 0), *d_roots = d_paths + path_words;
+    uint64_t *d_out = d_roots + (size_t)7 * n_roots;
+    uint8_t *d_present = (uint8_t *)(d_out + 7 * n), *d_verdicts = d_present + n;
+    HIP_TRY(hipMemcpyAsync(d_idx, indices, n * 8, hipMemcpyHostToDevice, c->stream));
+    if (values) HIP_TRY(hipMemcpyAsync(d_val, values, n * 112, hipMemcpyHostToDevice, c->stream));
+    if (present) HIP_TRY(hipMemcpyAsync(d_present, present, n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_paths, paths, path_words * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_roots, roots, (size_t)56 * n_roots, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(cs::k_path_check, dim3((count + 3) / 4), dim3(64), 0, c->stream, d_idx, values ? d_val : nullptr, present ? d_present : nullptr, d_paths,
+                       d_roots, n_roots, count, depth, d_verdicts, d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(verdicts, d_verdicts, n, hipMemcpyDeviceToHost, c->stream));
+    if (roots_out) HIP_TRY(hipMemcpyAsync(roots_out, d_out, n * 56, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream)); // synchronous: the verdicts are on the host, the caller's arrays are free again
+    return CSTARK_OK;
+}
+
+// the first word >= p of a [rows][per_row] array, named as `name[row][col]` (paths: `name[row][entry][word]`)
+bool reduced_words(const char *who, const char *name, const uint64_t *a, size_t rows, size_t per_row, bool entries) {
+    for (size_t i = 0; i < rows * per_row; i++)
+        if (a[i] >= cs::host::P) {
+            char where[128];
+            if (entries) snprintf(where, sizeof where, "%s: %s[%zu][%zu][%zu]", who, name, i / per_row, i % per_row / 7, i % 7);
+            else snprintf(where, sizeof where, "%s: %s[%zu][%zu]", who, name, i / per_row, i % per_row);
+            fail(CSTARK_ERR_INVALID_ARG, "%s is not a reduced field element", where);
+            return false;
+        }
+    return true;
+}
+
 // a HIP failure inside a ledger call leaves the pool in an unknown state: every later call fails
 int guard(cstark_ledger *L, int rc) {
     if (rc == CSTARK_ERR_HIP || rc == CSTARK_ERR_OOM) L->broken = true;
@@ -280,6 +412,34 @@ int cstark_ledger_get_accounts(cstark_ctx *c, cstark_ledger *L, uint32_t count, 
         else memset(values_out + (size_t)14 * i, 0, 112);
     }
     return CSTARK_OK;
+}
+
+int cstark_ledger_open_accounts(cstark_ctx *c, cstark_ledger *L, uint32_t count, const uint64_t *indices, uint64_t *values_out, uint8_t *present_out,
+                                uint64_t *paths_out, uint64_t root_out[7]) {
+    RC_TRY(usable(c, L, "cstark_ledger_open_accounts"));
+    if (count == 0 || count > MAX_TRANSFERS || !indices || !values_out || !present_out || !paths_out || !root_out)
+        return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_open_accounts: bad argument");
+    for (uint32_t i = 0; i < count; i++)
+        if (indices[i] >> L->index.depth) {
+            char where[32];
+            snprintf(where, sizeof where, "indices[%u]", i);
+            return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_open_accounts: %s is out of range", where);
+        }
+    return guard(L, open_impl(L, count, indices, values_out, present_out, paths_out, root_out));
+}
+
+int cstark_account_check_paths(cstark_ctx *c, uint32_t count, uint32_t depth, const uint64_t *indices, const uint64_t *values, const uint8_t *present,
+                               const uint64_t *paths, const uint64_t *roots, uint32_t n_roots, uint8_t *verdicts, uint64_t *roots_out) {
+    const char *who = "cstark_account_check_paths";
+    if (!c || !indices || !paths || !roots || !verdicts) return fail(CSTARK_ERR_INVALID_ARG, "%s: null argument", who);
+    if (count == 0 || count > MAX_TRANSFERS) return fail(CSTARK_ERR_INVALID_ARG, "%s: count must be 1 .. 2^20", who);
+    if (depth == 0 || depth > MAX_DEPTH) return fail(CSTARK_ERR_INVALID_ARG, "%s: depth must be 1 .. 31", who);
+    if (n_roots != 1 && n_roots != count) return fail(CSTARK_ERR_INVALID_ARG, "%s: n_roots must be 1 or count", who);
+    if (present && !values) return fail(CSTARK_ERR_INVALID_ARG, "%s: present without values", who);
+    if (values && !reduced_words(who, "values", values, count, 14, false)) return CSTARK_ERR_INVALID_ARG;
+    if (!reduced_words(who, "paths", paths, count, (size_t)7 * (depth + 1), true)) return CSTARK_ERR_INVALID_ARG;
+    if (!reduced_words(who, "roots", roots, n_roots, 7, false)) return CSTARK_ERR_INVALID_ARG;
+    return check_paths_impl(c, count, depth, indices, values, present, paths, roots, n_roots, verdicts, roots_out);
 }
 
 int cstark_ledger_root(cstark_ctx *c, cstark_ledger *L, uint64_t root[7]) {

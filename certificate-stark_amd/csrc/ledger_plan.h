@@ -70,6 +70,7 @@ struct Plan {
     std::vector<Emit> witness, commit;
     uint32_t final_root_slot = 0;    // the root after the call (a scratch slot for plan_apply)
     uint64_t pool_slots = 0;         // slots the pool must hold for this call
+    uint32_t stage_slot = 0;         // plan_open: the staging area its emit list fills
     // what commit() changes in the index
     std::vector<NewNode> new_nodes;
     std::vector<std::pair<uint64_t, Value>> new_values;
@@ -274,6 +275,33 @@ inline bool plan_apply(const Index &ix, uint32_t scratch_base, uint32_t n_tx, co
     p.final_root_slot = D(0, ne - 1);
     for (const auto &kv : cur) p.new_values.emplace_back(kv.first, kv.second);
     detail::pack_lists(p);
+    return p.pool_slots <= MAX_POOL_SLOTS;
+}
+
+// cstark_ledger_open_accounts: the authentication paths of `count` leaves of the tree as it stands, in the witness's form (path[0] = the
+// leaf, path[k + 1] = the sibling at level depth - k).  One emit list of count (depth + 1) entries, `witness`, whose word offsets count
+// from the staging area [stage_slot, stage_slot + count (depth + 1)) that follows the list in the scratch: path i starts at word
+// 7 (depth + 1) i.  An absent leaf and an untouched sibling read the level's empty-subtree slot (Index::slot).  Indices may repeat.
+// Nothing of the index changes and nothing is hashed.  false: an index is out of range, or the call is too large to plan.
+inline uint64_t open_scratch_slots(uint32_t depth, uint64_t count) { return (count * (depth + 1) + 6) / 7 + count * (depth + 1); }
+inline bool plan_open(const Index &ix, uint32_t scratch_base, uint32_t count, const uint64_t *indices, Plan &p) {
+    const uint32_t d = ix.depth;
+    const uint64_t size = (uint64_t)1 << d;
+    if (count == 0 || count > MAX_TRANSFERS || (uint64_t)scratch_base + open_scratch_slots(d, count) > MAX_POOL_SLOTS) return false;
+    for (uint32_t i = 0; i < count; i++)
+        if (indices[i] >= size) return false;
+    p.upload_slot = scratch_base;
+    p.witness.reserve((size_t)count * (d + 1));
+    for (uint32_t i = 0; i < count; i++) {
+        const uint64_t a = indices[i];
+        const uint32_t word = 7 * (d + 1) * i; // below 2^20 * 32 * 7
+        p.witness.push_back({ix.slot(d, a), word});
+        for (uint32_t k = 0; k < d; k++) p.witness.push_back({ix.slot(d - k, (a >> k) ^ 1), word + 7 * (k + 1)});
+    }
+    p.final_root_slot = ix.root_slot();
+    detail::pack_lists(p);
+    p.stage_slot = (uint32_t)p.pool_slots;
+    p.pool_slots += p.witness.size();
     return p.pool_slots <= MAX_POOL_SLOTS;
 }
 

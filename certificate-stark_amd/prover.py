@@ -108,6 +108,29 @@ class TransferRefused(Exception):
         self.index, self.reason = index, reason
 
 
+def check_account_paths(indices, paths, roots, values=None, present=None, backend=None, want_roots=False):
+    """Authentication paths from anywhere (an AccountOpening, a witness's s_paths / r_paths, a file) against the roots they state, on
+    the GPU: -> one cstark_path_verdict per path (0 = valid, Backend.PATH_*); see Backend.account_check_paths.  No ledger is needed."""
+    return (backend or Backend()).account_check_paths(indices, paths, roots, values=values, present=present, want_roots=want_roots)
+
+
+class AccountOpening:
+    """What Ledger.open returns: the accounts at `indices` (values [count][14], present [count]) with their authentication paths
+    ([count][depth + 1][7], the witness's path form; an absent account's leaf is the all-zero digest) under `root`."""
+
+    def __init__(self, indices, values, present, paths, root, backend=None):
+        self.indices, self.values, self.present, self.paths, self.root = indices, values, present, paths, root
+        self._backend = backend
+
+    @property
+    def depth(self):
+        return self.paths.shape[1] - 1
+
+    def check(self, backend=None):
+        """the verdict of every path against `root`, with the leaf test on (values, present): all zero for an honest opening"""
+        return check_account_paths(self.indices, self.paths, self.root, self.values, self.present, backend=backend or self._backend)
+
+
 class Ledger:
     """The account tree an operator holds, resident on the GPU (cstark_ledger_*): set_accounts, then apply(transfers) per batch -- the
     counterpart of the sequential loop of TransactionMetadata::build_random (src/lib.rs:341-422) on real accounts and transfers.
@@ -142,6 +165,12 @@ class Ledger:
     def accounts(self, indices):
         """-> (values [count][14], present [count])"""
         return self.backend.ledger_get_accounts(self._led, indices)
+
+    def open(self, indices):
+        """-> AccountOpening: values, presence and authentication paths of the given leaves under the current root (indices may repeat
+        and may name absent accounts: that is a proof of absence).  Read-only."""
+        idx = np.ascontiguousarray(indices, np.uint64).reshape(-1)
+        return AccountOpening(idx, *self.backend.ledger_open_accounts(self._led, self.depth, idx), backend=self.backend)
 
     def apply(self, transfers, want_witness=True, check_signatures=False):
         """transfers: (s_indices, r_indices, deltas, sig_rx, sig_s) or an object with these attributes (a TransactionMetadata, say).

@@ -487,6 +487,41 @@ int cstark_ledger_set_accounts(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t 
 int cstark_ledger_get_accounts(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t count, const uint64_t *indices, uint64_t *values_out,
                                uint8_t *present_out);
 int cstark_ledger_root(cstark_ctx *ctx, cstark_ledger *ledger, uint64_t root[7]);
+/* The authentication paths of `count` (1 .. 2^20) leaves under the CURRENT root.  indices may repeat and may name absent accounts.
+ * values_out [count][14] and present_out [count] are what cstark_ledger_get_accounts gives; paths_out [count][depth + 1][7] has the
+ * witness's path form (s_paths / r_paths of cstark_tx_witness): [leaf digest, sibling at level depth, ..., sibling at level 1]; root_out
+ * is the root every path folds to (cstark_account_check_paths states the fold).  The leaf entry of an absent account is the all-zero
+ * digest and its siblings are what the tree holds, empty-subtree digests where nothing was touched: a proof of absence.  Null pointers,
+ * count == 0, count > 2^20 or an index >= 2^depth is CSTARK_ERR_INVALID_ARG with the outputs untouched.  Synchronous and read-only: one
+ * upload of a slot list, one gather on the device, no hashing; root, stored nodes, accounts and the resident witness are unchanged. */
+int cstark_ledger_open_accounts(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t count, const uint64_t *indices,
+                                uint64_t *values_out /* [count][14] */, uint8_t *present_out /* [count] */,
+                                uint64_t *paths_out /* [count][depth + 1][7] */, uint64_t root_out[7]);
+/* ---- the verifier's side of an opening: needs no ledger --------------------------------------------------------------------------
+ * The verdict of a path is the first that applies, in the order INDEX_RANGE, LEAF, ROOT. */
+typedef enum cstark_path_verdict {
+    CSTARK_PATH_VALID = 0,
+    CSTARK_PATH_INDEX_RANGE = 1, /* index >= 2^depth */
+    CSTARK_PATH_LEAF = 2,        /* paths[i][0] is not the leaf of the stated account: merge(value[0..7], value[7..14]) if present,
+                                    all-zero if absent */
+    CSTARK_PATH_ROOT = 3         /* the path does not fold to the stated root */
+} cstark_path_verdict;
+/* Folds `count` (1 .. 2^20) paths of a tree of any depth 1 .. 31 on the device, each in one chain of depth Rescue merges inside ONE
+ * launch: cur = paths[i][0]; for k = 0 .. depth - 1: cur = bit k of indices[i] ? merge(paths[i][k + 1], cur) : merge(cur, paths[i][k + 1]).
+ * The fold reads bits 0 .. depth - 1 of the index whatever the verdict, and roots_out (optional, [count][7]) receives its result for
+ * every path whatever the verdict.  roots: n_roots = 1 (one root for all paths) or count (one each), [n_roots][7].
+ * values [count][14] given: the LEAF test runs, against merge(value[0..7], value[7..14]) where present[i] != 0 (a NULL present: all
+ * present) and against the all-zero digest where present[i] == 0.  values == NULL is digest mode: present must be NULL too, no LEAF
+ * test runs and the path is taken as a path of digests.  verdicts [count]: one cstark_path_verdict each.  All arrays are host memory.
+ * Null ctx, indices, paths, roots or verdicts, count == 0, count > 2^20, depth == 0, depth > 31, n_roots neither 1 nor count, present
+ * without values, or a word >= p in values, paths or roots is CSTARK_ERR_INVALID_ARG before anything is launched and with the outputs
+ * untouched; cstark_last_error names the first such word (values, then paths, then roots).  Synchronous, on the context's stream, in a
+ * device block of its own that the context keeps and frees: the resident witness is neither read nor written, so a proof after a check
+ * is the proof without it. */
+int cstark_account_check_paths(cstark_ctx *ctx, uint32_t count, uint32_t depth, const uint64_t *indices,
+                               const uint64_t *values /* [count][14] or NULL */, const uint8_t *present /* [count] or NULL */,
+                               const uint64_t *paths /* [count][depth + 1][7] */, const uint64_t *roots, uint32_t n_roots /* 1 or count */,
+                               uint8_t *verdicts /* [count] */, uint64_t *roots_out /* optional [count][7] */);
 /* Applies n_tx transfers in order with the reference's arithmetic (sender balance - delta, sender nonce + 1, receiver balance + delta:
  * field operations, src/lib.rs:373-375), advances the ledger and leaves the batch's witness RESIDENT in the context exactly as
  * cstark_tx_witness_upload would: cstark_tx_build_trace / cstark_tx_prove / cstark_air_prove follow without an upload.  Roots, paths

@@ -189,6 +189,31 @@ struct Transfers {
     std::vector<std::array<BaseElement, 6>> sig_rx;
     std::vector<std::array<uint8_t, 32>> sig_s;
 };
+// What Ledger::open returns: the accounts at `indices` with their authentication paths ([count][depth + 1][7] words, the witness's path
+// form; an absent account's leaf is the all-zero digest) under `root`
+struct AccountOpening {
+    unsigned depth = 0;
+    std::vector<uint64_t> indices;
+    std::vector<std::array<BaseElement, 14>> values;
+    std::vector<uint8_t> present;
+    std::vector<BaseElement> paths;
+    Hash root{};
+};
+// cstark_account_check_paths: one cstark_path_verdict per path (CSTARK_PATH_VALID = 0).  paths [count][depth + 1][7]; roots: one root or
+// one per path; values / present (optional): the leaf test, without values the paths are paths of digests; roots_out (optional): what
+// every path folds to, [count][7].  No ledger is needed and a resident witness is not touched.
+inline std::vector<uint8_t> check_account_paths(Context &ctx, unsigned depth, const std::vector<uint64_t> &indices, const std::vector<BaseElement> &paths,
+                                                const std::vector<Hash> &roots, const std::vector<std::array<BaseElement, 14>> *values = nullptr,
+                                                const std::vector<uint8_t> *present = nullptr, std::vector<BaseElement> *roots_out = nullptr) {
+    const size_t n = indices.size();
+    if (n == 0 || paths.size() != n * (depth + 1) * 7 || roots.empty() || (values && values->size() != n) || (present && present->size() != n))
+        throw Error(CSTARK_ERR_INVALID_ARG, "path vectors are not of equal length");
+    std::vector<uint8_t> verdicts(n);
+    if (roots_out) roots_out->resize(7 * n);
+    check(cstark_account_check_paths(ctx.raw(), (uint32_t)n, depth, indices.data(), values ? (*values)[0].data() : nullptr, present ? present->data() : nullptr,
+                                     paths.data(), roots[0].data(), (uint32_t)roots.size(), verdicts.data(), roots_out ? roots_out->data() : nullptr));
+    return verdicts;
+}
 // The account tree an operator holds, resident on the GPU (cstark_ledger_*): what replaces the sequential loop of
 // TransactionMetadata::build_random (src/lib.rs:341-422) on real accounts.  apply() leaves the batch's witness resident in the context:
 // TransactionProver::prove_resident follows without an upload.
@@ -214,6 +239,21 @@ class Ledger {
         if (!indices.empty()) check(cstark_ledger_get_accounts(ctx_.raw(), led_, (uint32_t)indices.size(), indices.data(), values[0].data(), have.data()));
         if (present) *present = have;
         return values;
+    }
+    // values, presence and authentication paths of the given leaves under the current root (cstark_ledger_open_accounts); indices may
+    // repeat and may name absent accounts.  Read-only.  check_account_paths(ctx, o.depth, o.indices, o.paths, {o.root}, &o.values,
+    // &o.present) is all CSTARK_PATH_VALID for what this returns
+    AccountOpening open(const std::vector<uint64_t> &indices) const {
+        if (indices.empty()) throw Error(CSTARK_ERR_INVALID_ARG, "no account index to open");
+        AccountOpening o;
+        o.depth = depth_;
+        o.indices = indices;
+        o.values.resize(indices.size());
+        o.present.resize(indices.size());
+        o.paths.resize(indices.size() * (depth_ + 1) * 7);
+        check(cstark_ledger_open_accounts(ctx_.raw(), led_, (uint32_t)indices.size(), indices.data(), o.values[0].data(), o.present.data(), o.paths.data(),
+                                          o.root.data()));
+        return o;
     }
     // applies the transfers in order; throws TransferRefused (nothing changed) at the first one that cannot be applied.  Signatures are
     // copied through unchecked, and TransactionAir does not bind them: a forged one still proves and verifies (apply_checked)
