@@ -42,6 +42,22 @@ class SchnorrStatementStruct(C.Structure):
     _fields_ = [("n_sig", C.c_uint32), ("messages", u64p), ("sig_rx", u64p), ("sig_s", u8p)]
 
 
+class TraceReportStruct(C.Structure):
+    _fields_ = [("step", C.c_int64), ("constraint", C.c_uint32), ("bad_cycles", C.c_uint32), ("boundary", C.c_int32),
+                ("boundary_register", C.c_uint32), ("boundary_step", C.c_uint64)]
+
+
+TRACE_CLEAN = 0xFFFFFFFF
+AIR_CYCLE_NAMES = ("transfer", "transfer", "signature", "trace", "link")   # per cstark_air_id: what one cycle of the trace is
+
+
+def air_trace_shape(air, log_n):
+    """cstark_air_trace_shape: (trace width, transition constraints, rows per cycle) of `air` at 2^log_n rows"""
+    w, nc, lc = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    check(load().cstark_air_trace_shape(C.c_int(air), C.c_uint32(log_n), C.byref(w), C.byref(nc), C.byref(lc)))
+    return w.value, nc.value, 1 << lc.value
+
+
 _lib = None
 
 

@@ -44,6 +44,42 @@ class ProofBatch:
         return list(self) == list(other)
 
 
+class TraceReport:
+    """What cstark_air_validate_trace found: the first violated transition constraint (step = cycle * cycle length + row_in_cycle; None
+    when every frame is clean), the number of cycles with a violated frame, and the first failing boundary entry (None: none, or not
+    checked).  cycle_codes / frame_values are numpy arrays when they were asked for (frame_values only with a violation)."""
+
+    def __init__(self, air, n, rep, cycle_codes=None, frame_values=None):
+        self.air = air
+        _, nc, cyc = _lib.air_trace_shape(air, n.bit_length() - 1)
+        self.unit = _lib.AIR_CYCLE_NAMES[air]
+        self.step = None if rep.step < 0 else int(rep.step)
+        self.constraint = None if self.step is None else int(rep.constraint)
+        self.cycle = None if self.step is None else self.step // cyc
+        self.row_in_cycle = None if self.step is None else self.step % cyc
+        self.bad_cycles = int(rep.bad_cycles)
+        self.boundary = None if rep.boundary < 0 else int(rep.boundary)
+        self.boundary_register = None if self.boundary is None else int(rep.boundary_register)
+        self.boundary_step = None if self.boundary is None else int(rep.boundary_step)
+        self.cycle_codes = cycle_codes
+        self.frame_values = frame_values if self.step is not None else None
+
+    @property
+    def ok(self):
+        return self.step is None and self.boundary is None
+
+    def __str__(self):
+        parts = []
+        if self.step is not None:
+            parts.append("%s %d, row %d, constraint %d" % (self.unit, self.cycle, self.row_in_cycle, self.constraint))
+        if self.boundary is not None:
+            parts.append("boundary entry %d: register %d at step %d" % (self.boundary, self.boundary_register, self.boundary_step))
+        return "; ".join(parts) if parts else "clean"
+
+    def __repr__(self):
+        return "TraceReport(%s)" % self
+
+
 class Backend:
     """One cstark_ctx bound to a torch device and the current torch stream."""
 
@@ -420,6 +456,28 @@ class Backend:
         w, nc, na, lce = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
         check(self.lib.cstark_air_shape(C.c_int(air), C.c_uint32(n_items), C.byref(w), C.byref(nc), C.byref(na), C.byref(lce)))
         return w.value, nc.value, na.value, lce.value
+
+    def air_validate_trace(self, air, trace, depth=0, public_inputs=None, want_cycles=False, want_frame=False):
+        """cstark_air_validate_trace: every transition constraint on every frame of the device trace [width][n] and, with public_inputs
+        (14 words, memory form; RangeProofAir: the number; SchnorrAir: anything but None), the boundary entries.  Returns a TraceReport."""
+        assert trace.dim() == 2 and trace.dtype == torch.int64
+        n = trace.shape[1]
+        assert n > 0 and n & (n - 1) == 0, "the trace length must be a power of two"
+        width, nc, cyc = _lib.air_trace_shape(air, n.bit_length() - 1)   # refuses an unknown AIR or an impossible length
+        assert trace.shape[0] == width
+        pub = None
+        if public_inputs is not None:
+            pub = np.zeros(14, np.uint64)
+            flat = _np_u64(public_inputs).reshape(-1)[:14]
+            pub[:flat.size] = flat
+        codes = np.empty(n // cyc, np.uint32) if want_cycles else None
+        frame = np.zeros(nc, np.uint64) if want_frame else None
+        rep = _lib.TraceReportStruct()
+        check(self.lib.cstark_air_validate_trace(self.ctx, C.c_int(air), self._ptr(trace), C.c_uint32(n.bit_length() - 1), C.c_uint32(depth),
+                                                 self._hptr(pub) if pub is not None else None, C.byref(rep),
+                                                 codes.ctypes.data_as(C.POINTER(C.c_uint32)) if want_cycles else None,
+                                                 self._hptr(frame) if want_frame else None))
+        return TraceReport(air, n, rep, codes, frame)
 
     def air_evaluate_transitions(self, air, lde, depth, log_blowup, k0=0):
         nk, width, n = lde.shape

@@ -552,6 +552,8 @@ void cstark_ctx_destroy(cstark_ctx *c) {
     if (c->tail_buf) (void)hipFree(c->tail_buf);
     if (c->sig_buf) (void)hipFree(c->sig_buf);
     if (c->path_buf) (void)hipFree(c->path_buf);
+    for (cs::RawPeriodic &t : c->raw_periodic) (void)hipFree(t.tab);
+    if (c->val_buf) (void)hipFree(c->val_buf);
     if (c->arena) cs::prove_arena_free(c->arena);
     if (c->verify) cs::verify_arena_free(c->verify);
     for (hipEvent_t e : c->part_ev) if (e) (void)hipEventDestroy(e);
@@ -1952,6 +1954,130 @@ int cstark_tx_periodic_columns(uint32_t merkle_depth, uint64_t *out /* [48][1024
     std::vector<uint64_t> cols;
     if (!out || !cs::host::tx_periodic_columns(merkle_depth, cols)) return fail(CSTARK_ERR_INVALID_ARG, "unsupported Merkle depth");
     memcpy(out, cols.data(), cols.size() * 8);
+    return CSTARK_OK;
+}
+
+// ---- trace validation ----------------------------------------------------------------------------------------------
+// the raw periodic columns of (air, depth) on the device, uploaded on first use and kept with the context
+static int get_raw_periodic(cstark_ctx *c, int air, unsigned depth, const cs::host::TraceCheckShape &s, const uint64_t **out) {
+    *out = nullptr;
+    if (s.n_per == 0) return CSTARK_OK;
+    for (const cs::RawPeriodic &t : c->raw_periodic)
+        if (t.air == air && t.depth == depth) { *out = t.tab; return CSTARK_OK; }
+    std::vector<uint64_t> cols;
+    bool ok = true;
+    if (air == CSTARK_AIR_STATE_TRANSITION) ok = cs::host::tx_periodic_columns(depth, cols);
+    else if (air == CSTARK_AIR_MERKLE_UPDATE) ok = cs::host::merkle_periodic_columns(depth, cols);
+    else if (air == CSTARK_AIR_SCHNORR) cs::host::schnorr_mask_columns(cols);
+    else cs::host::rescue_chain_periodic_columns(cols);
+    if (!ok || cols.size() != ((size_t)s.n_per << s.log_cycle)) return fail(CSTARK_ERR_INVALID_ARG, "cstark_air_validate_trace: unsupported Merkle depth");
+    cs::RawPeriodic t{air, depth, nullptr};
+    DevGuard g;
+    HIP_TRY(g.alloc(&t.tab, cols.size() * 8));
+    HIP_TRY(hipMemcpyAsync(t.tab, cols.data(), cols.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->raw_periodic.push_back(t);
+    g.release();
+    *out = t.tab;
+    return CSTARK_OK;
+}
+int cstark_air_trace_shape(int air, uint32_t log_n, uint32_t *width, uint32_t *n_constraints, uint32_t *log_cycle) {
+    cs::host::TraceCheckShape s;
+    if (!width || !n_constraints || !log_cycle || !cs::host::trace_check_shape(air, log_n, s))
+        return fail(CSTARK_ERR_INVALID_ARG, "cstark_air_trace_shape: not an AIR, or a trace length it cannot have");
+    *width = s.width; *n_constraints = s.nc; *log_cycle = s.log_cycle;
+    return CSTARK_OK;
+}
+int cstark_air_validate_trace(cstark_ctx *c, int air, const uint64_t *d_trace, uint32_t log_n, uint32_t item, const uint64_t *public_inputs,
+                              cstark_trace_report *report, uint32_t *cycle_codes, uint64_t *frame_values) {
+    if (!c || !d_trace || !report) return fail(CSTARK_ERR_INVALID_ARG, "cstark_air_validate_trace: null argument");
+    cs::host::TraceCheckShape s;
+    if (air < CSTARK_AIR_STATE_TRANSITION || air > CSTARK_AIR_RESCUE_CHAIN) return fail(CSTARK_ERR_INVALID_ARG, "cstark_air_validate_trace: unknown AIR");
+    if (!cs::host::trace_check_shape(air, log_n, s))
+        return fail(CSTARK_ERR_INVALID_ARG, "cstark_air_validate_trace: the AIR has no trace of this length (at least one cycle, at most 2^24 rows)");
+    const bool tree = air == CSTARK_AIR_STATE_TRANSITION || air == CSTARK_AIR_MERKLE_UPDATE;
+    if (tree && !cs::host::trace_check_depth(item)) return fail(CSTARK_ERR_INVALID_ARG, "cstark_air_validate_trace: the Merkle depth must be 1, 3, 7, 15 or 31");
+    const unsigned depth = tree ? item : 0;
+    const size_t n = (size_t)1 << log_n, n_cycles = n >> s.log_cycle;
+    const unsigned n_pub = air == CSTARK_AIR_SCHNORR ? 0 : air == CSTARK_AIR_RANGE ? 1 : 14;
+    if (public_inputs)
+        for (unsigned i = 0; i < n_pub; i++)
+            if (public_inputs[i] >= cs::host::P) return fail(CSTARK_ERR_INVALID_ARG, "cstark_air_validate_trace: a public input is not a reduced field element");
+    size_t n_sig = 0;
+    if (air == CSTARK_AIR_SCHNORR) {
+        n_sig = c->schnorr_rx.size() / 6;
+        if (n_sig == 0 || n_sig * 512 != n || c->schnorr_pub.size() < n_sig * 28)
+            return fail(CSTARK_ERR_INVALID_ARG, "cstark_air_validate_trace: no Schnorr statement uploaded for this trace length");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t *d_per;
+    RC_TRY(get_raw_periodic(c, air, depth, s, &d_per));
+    std::vector<cs::ValidateEntry> entries;
+    std::vector<uint64_t> seq;
+    if (public_inputs && !cs::host::trace_check_entries(air, log_n, public_inputs, c->schnorr_rx.data(), entries, seq))
+        return fail(CSTARK_ERR_INVALID_ARG, "cstark_air_validate_trace: no boundary list for this AIR");
+    // scratch of the call: codes [n_cycles] | summary [4] (32-bit words), then 64-bit words: messages | sequences | boundary list | one frame
+    // (cur, next, periodic values, public-input values, slot values).  At 2^24 rows: 8 MiB of codes (RescueAir), or 7 MiB + 3 MiB of statement words (SchnorrAir); below 64 MiB whatever the AIR and n.
+    const size_t code_words = (n_cycles + 4 + 1) & ~(size_t)1;
+    const size_t msg_words = n_sig * 28, ent_words = entries.size() * sizeof(cs::ValidateEntry) / 8;
+    const size_t frame_in = 2 * (size_t)s.width + s.n_per + 19, frame_words = frame_in + s.nc;
+    const size_t stage_words = msg_words + seq.size() + ent_words, bytes = code_words * 4 + (stage_words + frame_words) * 8;
+    static_assert(sizeof(cs::ValidateEntry) == 24, "boundary entries are staged as three words each");
+    if (c->val_bytes < bytes) {
+        if (c->val_buf) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->val_buf)); c->val_buf = nullptr; c->val_bytes = 0; }
+        HIP_TRY(hipMalloc(&c->val_buf, bytes));
+        c->val_bytes = bytes;
+    }
+    uint32_t *d_codes = (uint32_t *)c->val_buf, *d_summary = d_codes + n_cycles;
+    uint64_t *d_stage = (uint64_t *)(d_codes + code_words), *d_frame = d_stage + stage_words;
+    std::vector<uint64_t> stage(stage_words);
+    if (msg_words) memcpy(stage.data(), c->schnorr_pub.data(), msg_words * 8);
+    if (!seq.empty()) memcpy(stage.data() + msg_words, seq.data(), seq.size() * 8);
+    if (ent_words) memcpy(stage.data() + msg_words + seq.size(), entries.data(), ent_words * 8);
+    HIP_TRY(hipMemsetAsync(d_codes, 0xFF, (n_cycles + 2) * 4, c->stream));
+    HIP_TRY(hipMemsetAsync(d_summary + 2, 0, 8, c->stream));
+    if (stage_words) HIP_TRY(hipMemcpyAsync(d_stage, stage.data(), stage_words * 8, hipMemcpyHostToDevice, c->stream));
+    cs::ValidateParams p{};
+    p.trace = d_trace; p.per = d_per; p.messages = msg_words ? d_stage : nullptr;
+    p.codes = d_codes; p.summary = d_summary; p.log_n = log_n; p.log_cycle = s.log_cycle;
+    hipError_t e = cs::launch_validate_frames(air, p, c->stream);
+    if (e == hipSuccess && !entries.empty())
+        e = cs::launch_validate_boundary(p, (const cs::ValidateEntry *)(d_stage + msg_words + seq.size()), (unsigned)entries.size(),
+                                         seq.empty() ? nullptr : d_stage + msg_words, n_sig ? (unsigned)n_sig : 1u, c->stream);
+    uint32_t summary[4];
+    if (e == hipSuccess) e = hipMemcpyAsync(summary, d_summary, sizeof summary, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e_sync = hipStreamSynchronize(c->stream); // also: `stage` is no longer read
+    HIP_TRY(e);
+    HIP_TRY(e_sync);
+    cstark_trace_report rep{};
+    rep.step = -1; rep.constraint = CSTARK_TRACE_CLEAN; rep.bad_cycles = summary[2]; rep.boundary = -1;
+    if (summary[1] != cs::VALIDATE_CLEAN) {
+        rep.boundary = (int32_t)(summary[1] >> 24);
+        rep.boundary_register = entries[rep.boundary].reg;
+        rep.boundary_step = summary[1] & 0xFFFFFFu;
+    }
+    std::vector<uint64_t> values;
+    if (summary[0] != cs::VALIDATE_CLEAN) {
+        uint32_t code;
+        HIP_TRY(hipMemcpyAsync(&code, d_codes + summary[0], 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        const cs::host::TraceViolation v = cs::host::trace_check_decode(s, summary[0], code);
+        rep.step = (int64_t)v.step; rep.constraint = v.constraint;
+        // every slot of that one frame through the free-standing-frame kernels: the caller's frame_values, and the two evaluators' cross-check
+        HIP_TRY(cs::launch_validate_gather_frame(p, d_frame, (size_t)v.step, s.width, s.n_per, c->stream));
+        HIP_TRY(cs::launch_eval_frames_air(air, d_frame, d_frame + s.width, d_frame + 2 * s.width, d_frame + frame_in, 1, c->stream));
+        values.resize(s.nc);
+        HIP_TRY(hipMemcpyAsync(values.data(), d_frame + frame_in, (size_t)s.nc * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (values[v.constraint] == 0)
+            return fail(CSTARK_ERR_HIP, "cstark_air_validate_trace: the two evaluators disagree (the frame kernel names a constraint whose value on that frame is zero)");
+    }
+    if (cycle_codes) {
+        HIP_TRY(hipMemcpyAsync(cycle_codes, d_codes, n_cycles * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (frame_values && !values.empty()) memcpy(frame_values, values.data(), values.size() * 8);
+    *report = rep;
     return CSTARK_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "ntt.h" // CosetMergeTerm
+#include "trace_check.h" // ValidateEntry, VALIDATE_CLEAN
 
 namespace cs {
 
@@ -116,6 +117,22 @@ hipError_t launch_eval_frames(const uint64_t *cur, const uint64_t *next, const u
 // RangeProofAir 2 / 0 / 2, RescueAir 14 / 29 / 14, SchnorrAir 56 / 36 + the 19 public-input values of the frame's point / 56, in the four
 // parts of its table kernel), through the bodies the table kernels run
 hipError_t launch_eval_frames_air(int air, const uint64_t *cur, const uint64_t *next, const uint64_t *per, uint64_t *out, unsigned nf, hipStream_t stream);
+// Trace validation (cstark_air_validate_trace): every transition constraint of AIR `air` on the frames (r, r + 1) of the trace itself.
+struct ValidateParams {
+    const uint64_t *trace;    // [width][n], the layout of the build-trace entry points
+    const uint64_t *per;      // raw periodic columns [n_per][cycle_len] (null for RangeProofAir)
+    const uint64_t *messages; // SchnorrAir: the statement's messages [n / 512][28]; null otherwise
+    uint32_t *codes;          // [n / cycle_len], pre-filled with VALIDATE_CLEAN: min over the cycle's violated frames of row * NC + slot
+    uint32_t *summary;        // [0] first violated cycle, [1] boundary verdict (entry << 24 | step), both pre-filled with VALIDATE_CLEAN; [2] violated cycles, pre-filled 0
+    uint32_t log_n, log_cycle;
+};
+// the frame kernel of the AIR (one wave per 64 frames, slot sums in LDS), then the summary over the cycles
+hipError_t launch_validate_frames(int air, const ValidateParams &p, hipStream_t stream);
+// the boundary list (trace_check.h) against the trace: max_occ = the largest number of occurrences of an entry; d_seq may be null
+hipError_t launch_validate_boundary(const ValidateParams &p, const ValidateEntry *d_entries, unsigned n_entries, const uint64_t *d_seq, unsigned max_occ,
+                                    hipStream_t stream);
+// frame r as the input of launch_eval_frames_air with nf = 1: d_dst = cur[width] | next[width] | per[n_per] (| the 19 public-input values)
+hipError_t launch_validate_gather_frame(const ValidateParams &p, uint64_t *d_dst, size_t r, unsigned width, unsigned n_per, hipStream_t stream);
 constexpr int CE_NUM_PARTS = 9; // launches of the fused evaluation: rounds, dbl0, add0, dbl1, add1, final, lin_a, lin_b, lin_c (split form: the one
                                 // linear pass is timed as lin_a, lin_b = 0, lin_c = the extension and the recombination)
 hipError_t launch_eval_constraints(const CeParams &p, unsigned nk, hipStream_t stream, hipEvent_t *part_events = nullptr);

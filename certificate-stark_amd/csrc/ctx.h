@@ -106,6 +106,12 @@ struct PeriodicTable {
     uint64_t *binv;  // [b][2][n] inverses of the boundary divisors
     int air = 0;     // cstark_air_id the table belongs to
 };
+// the periodic columns of an AIR as the AIR states them, [n_periodic][cycle_len] on the device: the values on the trace domain
+struct RawPeriodic {
+    int air;
+    unsigned depth;
+    uint64_t *tab;
+};
 // 1 / (x^m - zc) over the LDE domain for one assertion divisor: [b cosets][n / m] (x^m has period n / m in the row index of a coset)
 struct AssertInverseTable {
     unsigned log_n, log_b;
@@ -211,6 +217,9 @@ struct cstark_ctx {
     size_t sig_bytes = 0;
     void *path_buf = nullptr; // cstark_account_check_paths (ledger.hip): its inputs and outputs on the device, likewise
     size_t path_bytes = 0;
+    std::deque<cs::RawPeriodic> raw_periodic; // cstark_air_validate_trace: the raw periodic columns of (AIR, depth), uploaded once
+    void *val_buf = nullptr; // ... and its scratch: per-cycle codes, summary, statement words, boundary list, one frame
+    size_t val_bytes = 0;
 };
 // internal (capi.hip): cstark_schnorr_check_signatures behind its null / count checks (cstark_ledger_apply_checked calls it with the
 // messages of ledger_plan.h).  `who` names the public call in the error text.

@@ -652,6 +652,7 @@ __global__ __launch_bounds__(256) void k_trace_schnorr_bits(TxWitnessDev w, fp *
         trace[(size_t)(41 - c) * n + g] = small_to_fp(acc);
     }
 }
+// (the same row rule, from the statement's messages and for one row: schnorr_aux_value in trace_check.hip -- keep the two in step)
 __global__ __launch_bounds__(256) void k_schnorr_aux_columns(TxWitnessDev w, fp *__restrict__ out, size_t n) {
     const int t = blockIdx.x;
     const int q = blockIdx.y * 256 + threadIdx.x;

@@ -282,6 +282,14 @@ class TransactionExample:
     def pub_inputs(self):
         return self.tx_metadata.initial_roots[0], self.tx_metadata.final_root
 
+    def validate(self, want_cycles=False, want_frame=False):
+        """Trace::validate of the reference's debug builds, on the device: builds the trace of this example's witness and checks every
+        transition constraint and the statement verify() would be given (cstark_air_validate_trace).  -> TraceReport; str(report) names
+        the first violation, e.g. "transfer 3, row 126, constraint 99"."""
+        trace = self.prover.build_trace(self.tx_metadata)
+        return self.prover.backend.air_validate_trace(Backend.AIR_TRANSACTION, trace, self.tx_metadata.depth, np.concatenate(self.pub_inputs()),
+                                                      want_cycles=want_cycles, want_frame=want_frame)
+
 
 # ---- the standalone examples of the reference: same prove() surface over cstark_air_prove ---------------------------------------
 def _air_verify_or_raise(backend, proof, air, public_inputs=None, numbers=None):
@@ -344,6 +352,12 @@ class MerkleExample(_ResidentWitness):
         """src/merkle/update/mod.rs:109-127; raises VerifierError on rejection, like TransactionExample.verify"""
         _air_verify_or_raise(self.backend, proof, Backend.AIR_MERKLE, np.concatenate(self.pub_inputs()))
 
+    def validate(self, want_cycles=False, want_frame=False):
+        """as TransactionExample.validate, for the MerkleAir trace of the witness"""
+        self._ensure_resident(lambda: self.backend.upload_witness(self.tx_metadata))
+        return self.backend.air_validate_trace(Backend.AIR_MERKLE, self.backend.merkle_build_trace(), self.tx_metadata.depth,
+                                               np.concatenate(self.pub_inputs()), want_cycles=want_cycles, want_frame=want_frame)
+
 
 class SchnorrExample(_ResidentWitness):
     """schnorr::SchnorrExample (src/schnorr/mod.rs:52-186): messages [n][28] (public key || 16 elements) with signatures."""
@@ -382,6 +396,13 @@ class SchnorrExample(_ResidentWitness):
         if v != 0:
             raise VerifierError(v)
 
+    def validate(self, want_cycles=False, want_frame=False):
+        """as TransactionExample.validate: the SchnorrAir trace against the resident statement; a forged signature shows as a failing
+        boundary entry at the last row of its block (str(report): "boundary entry 55: register 0 at step 1023")"""
+        self._ensure_resident(lambda: self.backend.upload_schnorr_witness(self.messages, self.sig_rx, self.sig_s))
+        return self.backend.air_validate_trace(Backend.AIR_SCHNORR, self.backend.schnorr_build_trace(), 0, True,
+                                               want_cycles=want_cycles, want_frame=want_frame)
+
 
 class RescueExample:
     """RescueExample of benches/rescue.rs:25-102: a chain of `chain_length` Rescue hashes from the bench's seed 42..48 (held in memory
@@ -410,6 +431,12 @@ class RescueExample:
         """benches/rescue.rs:88-94; raises VerifierError on rejection"""
         _air_verify_or_raise(self.backend, proof, Backend.AIR_RESCUE_CHAIN, np.concatenate(self.pub_inputs()))
 
+    def validate(self, want_cycles=False, want_frame=False):
+        """as TransactionExample.validate: the chain's trace against seed and result"""
+        trace = self.backend.rescue_chain_build_trace(self.seed, self.chain_length)
+        return self.backend.air_validate_trace(Backend.AIR_RESCUE_CHAIN, trace, 0, np.concatenate(self.pub_inputs()),
+                                               want_cycles=want_cycles, want_frame=want_frame)
+
 
 class RangeProofExample:
     """range::RangeProofExample (src/range/mod.rs:28-110): `number` is a field element in memory form whose canonical value is
@@ -425,3 +452,8 @@ class RangeProofExample:
     def verify(self, proof):
         """src/range/mod.rs:103-110; raises VerifierError on rejection"""
         _air_verify_or_raise(self.backend, proof, Backend.AIR_RANGE, numbers=self.number)
+
+    def validate(self, want_cycles=False, want_frame=False):
+        """as TransactionExample.validate: the 64-row accumulator trace against the number"""
+        return self.backend.air_validate_trace(Backend.AIR_RANGE, self.backend.range_build_trace(self.number), 0, [self.number],
+                                               want_cycles=want_cycles, want_frame=want_frame)

@@ -633,6 +633,45 @@ int cstark_schnorr_public_at(cstark_ctx *ctx, uint32_t n_sig, const uint64_t *me
 int cstark_verify_stage_ms(cstark_ctx *ctx, float *ms /* [CSTARK_VERIFY_NUM_STAGES] */);
 int cstark_verify_h2d_bytes(cstark_ctx *ctx, uint64_t *bytes);
 
+/* ---- trace validation: Trace::validate of the reference's debug builds, on the device ----
+ * Evaluates every transition constraint of `air` on every frame (r, r + 1), r < n - 1, of the base trace d_trace ([width][n] device memory,
+ * the layout of the cstark_*_build_trace entry points, n = 2^log_n) and, with public_inputs, every boundary entry, and names the first
+ * violation.  A constraint is violated where the SUM of its contributions is non-zero.  Cycles: 1024 rows (one transfer) for TransactionAir,
+ * 512 for MerkleAir and SchnorrAir, 8 for RescueAir, the whole trace for RangeProofAir.
+ *   item           the Merkle depth for TransactionAir and MerkleAir (1, 3, 7, 15 or 31); ignored otherwise.
+ *   public_inputs  host [14] as cstark_air_verify takes them (RangeProofAir: word 0); NULL: no boundary check (boundary = -1).  Boundary
+ *                  lists, in the order of `boundary`: TransactionAir / MerkleAir registers 58..64 at step 0 against the initial root, then
+ *                  at step n - 1 against the final root (for TransactionAir entries 0, 1, 7, 8 are the AIR's assertions, the others public
+ *                  words the channel seed binds); RescueAir registers 0..6 at the first and last row against seed | result; RangeProofAir
+ *                  register 1 = 0 at step 0, = number at step n - 1; SchnorrAir: any non-NULL pointer checks the 61 assertions of
+ *                  get_assertions (every 512 rows) against the resident statement (cstark_schnorr_witness_upload), whose messages the
+ *                  transitions always read: no resident statement of this trace length is CSTARK_ERR_INVALID_ARG.
+ *   cycle_codes    optional host [n / cycle length]: per cycle CSTARK_TRACE_CLEAN or (first violated row in the cycle) * n_constraints +
+ *                  its lowest violated constraint.
+ *   frame_values   optional host [n_constraints]: all constraint values of the first violated frame, memory form, from the free-standing
+ *                  frame evaluator; untouched when the transitions are clean.  The named constraint's value is checked to be non-zero
+ *                  there on every call that finds a violation: CSTARK_ERR_HIP if the two evaluators disagree.
+ * Synchronous, on the context's stream.  Violations are not failures: the status is CSTARK_OK.  Null ctx, d_trace or report, an unknown
+ * air, a log_n the AIR cannot have (fewer rows than one cycle, more than 2^24), a bad depth or a public word >= p is
+ * CSTARK_ERR_INVALID_ARG before anything is launched and with the outputs untouched.  Trace cells >= p are the caller's responsibility,
+ * as for every other device-table entry point.  The resident witness, the prover's buffers and the scratch of the signature and path
+ * checks are neither read nor written: a proof after a validation is the proof without it. */
+#define CSTARK_TRACE_CLEAN 0xFFFFFFFFu
+typedef struct cstark_trace_report {
+    int64_t  step;               /* first row r whose frame (r, r+1) violates a transition constraint; -1: none */
+    uint32_t constraint;         /* the lowest violated constraint index at that row (CSTARK_TRACE_CLEAN: none) */
+    uint32_t bad_cycles;         /* cycles with at least one violated frame */
+    int32_t  boundary;           /* index of the first failing boundary entry (list order above); -1: none, or not checked */
+    uint32_t boundary_register;
+    uint64_t boundary_step;
+} cstark_trace_report;
+/* The shape cstark_air_validate_trace works on (csrc/trace_check.h; host only): trace width, transition constraints and log2 of the
+ * cycle length (RangeProofAir: log_n) of `air` at 2^log_n rows.  CSTARK_ERR_INVALID_ARG for an unknown air or a log_n the AIR cannot have. */
+int cstark_air_trace_shape(int air, uint32_t log_n, uint32_t *width, uint32_t *n_constraints, uint32_t *log_cycle);
+int cstark_air_validate_trace(cstark_ctx *ctx, int air, const uint64_t *d_trace, uint32_t log_n, uint32_t item,
+                              const uint64_t *public_inputs, cstark_trace_report *report,
+                              uint32_t *cycle_codes, uint64_t *frame_values);
+
 /* ---- device memory helpers for callers without a HIP runtime of their own (the Rust shim) ---- */
 int cstark_malloc(cstark_ctx *ctx, size_t bytes, void **d_ptr);
 int cstark_free(cstark_ctx *ctx, void *d_ptr);

@@ -368,6 +368,75 @@ inline std::vector<int32_t> verify_batch(Context &ctx, const std::vector<std::ve
     return verdicts;
 }
 
+// ---- trace validation (cstark_air_validate_trace) ----
+// What the validation of a device trace found: step < 0 and boundary < 0 is a clean trace.  cycle = step / cycle length (one transfer,
+// signature or link; the whole trace for RangeProofAir), row_in_cycle = step % cycle length.
+struct TraceReport {
+    int air = 0;
+    int64_t step = -1;
+    uint64_t cycle = 0;
+    uint32_t row_in_cycle = 0, constraint = CSTARK_TRACE_CLEAN, bad_cycles = 0;
+    int32_t boundary = -1;
+    uint32_t boundary_register = 0;
+    uint64_t boundary_step = 0;
+    std::vector<uint32_t> cycle_codes;     // with want_cycles: one code per cycle (CSTARK_TRACE_CLEAN, or row * n_constraints + constraint)
+    std::vector<BaseElement> frame_values; // with want_frame and a violated frame: every constraint value of the first violated frame
+    bool ok() const { return step < 0 && boundary < 0; }
+    // "transfer 3, row 126, constraint 99", "boundary entry 8: register 59 at step 2047", both joined by "; ", or "clean"
+    std::string str() const {
+        static const char *unit[5] = {"transfer", "transfer", "signature", "trace", "link"};
+        std::string s;
+        if (step >= 0) s = std::string(unit[air]) + " " + std::to_string(cycle) + ", row " + std::to_string(row_in_cycle) + ", constraint " + std::to_string(constraint);
+        if (boundary >= 0)
+            s += std::string(s.empty() ? "" : "; ") + "boundary entry " + std::to_string(boundary) + ": register " + std::to_string(boundary_register) + " at step " +
+                 std::to_string(boundary_step);
+        return s.empty() ? "clean" : s;
+    }
+};
+// d_trace: [width][2^log_n] device memory; item: the Merkle depth (TransactionAir, MerkleAir); public_inputs: 14 words as for
+// cstark_air_verify, or null for no boundary check (SchnorrAir: any non-null pointer checks the resident statement)
+inline TraceReport validate_trace(Context &ctx, int air, const uint64_t *d_trace, uint32_t log_n, uint32_t item, const uint64_t *public_inputs,
+                                  bool want_cycles = false, bool want_frame = false) {
+    uint32_t width = 0, nc = 0, lc = 0;
+    check(cstark_air_trace_shape(air, log_n, &width, &nc, &lc)); // an unknown AIR or an impossible trace length throws here
+    TraceReport r;
+    r.air = air;
+    if (want_cycles) r.cycle_codes.assign((size_t)1 << (log_n - lc), CSTARK_TRACE_CLEAN);
+    if (want_frame) r.frame_values.assign(nc, 0);
+    cstark_trace_report rep{};
+    check(cstark_air_validate_trace(ctx.raw(), air, d_trace, log_n, item, public_inputs, &rep, r.cycle_codes.empty() ? nullptr : r.cycle_codes.data(),
+                                    want_frame ? r.frame_values.data() : nullptr));
+    r.step = rep.step; r.constraint = rep.constraint; r.bad_cycles = rep.bad_cycles;
+    r.boundary = rep.boundary; r.boundary_register = rep.boundary_register; r.boundary_step = rep.boundary_step;
+    if (rep.step >= 0) { r.cycle = (uint64_t)rep.step >> lc; r.row_in_cycle = (uint32_t)((uint64_t)rep.step & (((uint64_t)1 << lc) - 1)); }
+    else r.frame_values.clear();
+    return r;
+}
+namespace detail {
+// a device trace of width x 2^log_n filled by `build`, validated, freed
+template <class Build>
+inline TraceReport validate_built(Context &ctx, int air, uint32_t width, size_t rows, uint32_t item, const uint64_t *public_inputs, bool want_cycles,
+                                  bool want_frame, Build build) {
+    uint32_t log_n = 0;
+    while (((size_t)1 << log_n) < rows) log_n++;
+    if (((size_t)1 << log_n) != rows) throw Error(CSTARK_ERR_INVALID_ARG, "the trace length must be a power of two");
+    void *d_trace = nullptr;
+    check(cstark_malloc(ctx.raw(), (size_t)width * rows * 8, &d_trace));
+    try {
+        check(build((uint64_t *)d_trace));
+        TraceReport r = validate_trace(ctx, air, (const uint64_t *)d_trace, log_n, item, public_inputs, want_cycles, want_frame);
+        cstark_free(ctx.raw(), d_trace);
+        return r;
+    } catch (...) {
+        cstark_free(ctx.raw(), d_trace);
+        throw;
+    }
+}
+inline void root_words(const PublicInputs &p, uint64_t (&pub)[14]) {
+    for (int k = 0; k < 7; k++) { pub[k] = p.initial_root[k]; pub[7 + k] = p.final_root[k]; }
+}
+} // namespace detail
+
 // src/lib.rs:92-150
 class TransactionExample {
   public:
@@ -380,6 +449,16 @@ class TransactionExample {
     void verify(const std::vector<uint8_t> &proof) const {
         const int32_t v = verify_batch(ctx_, {proof}, {pub_inputs()})[0];
         if (v != CSTARK_PROOF_OK) throw VerifierError(v);
+    }
+    // Trace::validate of the reference's debug builds, on the device: the trace of this witness against every transition constraint and
+    // the statement verify() is given
+    TraceReport validate(bool want_cycles = false, bool want_frame = false) const {
+        uint64_t pub[14];
+        detail::root_words(pub_inputs(), pub);
+        const cstark_tx_witness w = tx_metadata_.view();
+        check(cstark_tx_witness_upload(ctx_.raw(), &w));
+        return detail::validate_built(ctx_, CSTARK_AIR_STATE_TRANSITION, 94, tx_metadata_.len() * 1024, w.merkle_depth, pub, want_cycles, want_frame,
+                                      [&](uint64_t *d) { return cstark_tx_build_trace(ctx_.raw(), d); });
     }
 
   private:
@@ -427,6 +506,14 @@ class MerkleExample {
         for (int k = 0; k < 7; k++) { pub[k] = p.initial_root[k]; pub[7 + k] = p.final_root[k]; }
         detail::air_verify(ctx_, CSTARK_AIR_MERKLE_UPDATE, proof, pub);
     }
+    TraceReport validate(bool want_cycles = false, bool want_frame = false) const {
+        uint64_t pub[14];
+        detail::root_words(pub_inputs(), pub);
+        const cstark_tx_witness w = m_.view();
+        check(cstark_tx_witness_upload(ctx_.raw(), &w));
+        return detail::validate_built(ctx_, CSTARK_AIR_MERKLE_UPDATE, 65, m_.len() * 512, w.merkle_depth, pub, want_cycles, want_frame,
+                                      [&](uint64_t *d) { return cstark_merkle_build_trace(ctx_.raw(), d); });
+    }
 
   private:
     ProofOptions options_;
@@ -442,6 +529,11 @@ class RangeProofExample {
     void verify(const std::vector<uint8_t> &proof) const {
         const uint64_t pub[14] = {number_};
         detail::air_verify(ctx_, CSTARK_AIR_RANGE, proof, pub);
+    }
+    TraceReport validate(bool want_cycles = false, bool want_frame = false) const {
+        const uint64_t pub[14] = {number_};
+        return detail::validate_built(ctx_, CSTARK_AIR_RANGE, 2, 64, 0, pub, want_cycles, want_frame,
+                                      [&](uint64_t *d) { return cstark_range_build_trace(ctx_.raw(), number_, d); });
     }
 
   private:
@@ -501,6 +593,13 @@ class RescueExample {
         for (int k = 0; k < 7; k++) { pub[k] = seed[k]; pub[7 + k] = r[k]; }
         detail::air_verify(ctx_, CSTARK_AIR_RESCUE_CHAIN, proof, pub);
     }
+    TraceReport validate(bool want_cycles = false, bool want_frame = false) const {
+        const std::array<BaseElement, 7> r = result();
+        uint64_t pub[14];
+        for (int k = 0; k < 7; k++) { pub[k] = seed[k]; pub[7 + k] = r[k]; }
+        return detail::validate_built(ctx_, CSTARK_AIR_RESCUE_CHAIN, 14, 8 * chain_length_, 0, pub, want_cycles, want_frame,
+                                      [&](uint64_t *d) { return cstark_rescue_chain_build_trace(ctx_.raw(), seed, (uint32_t)chain_length_, d); });
+    }
     BaseElement seed[7];
 
   private:
@@ -547,6 +646,14 @@ class SchnorrExample {
         int32_t v = -1;
         check(cstark_schnorr_verify(ctx_.raw(), 1, &ptr, &len, &st, nullptr, &v));
         if (v != CSTARK_PROOF_OK) throw VerifierError(v);
+    }
+    // the trace of the signatures held here against the transitions and the 61 assertions: a forged signature is the failing boundary
+    // entry at the last row of its block
+    TraceReport validate(bool want_cycles = false, bool want_frame = false) const {
+        const uint32_t n = (uint32_t)(messages.size() / 28);
+        check(cstark_schnorr_witness_upload(ctx_.raw(), n, messages.data(), sig_rx.data(), sig_s.data()));
+        return detail::validate_built(ctx_, CSTARK_AIR_SCHNORR, 56, (size_t)n * 512, 0, sig_rx.data(), want_cycles, want_frame,
+                                      [&](uint64_t *d) { return cstark_schnorr_build_trace(ctx_.raw(), d); });
     }
     ProofOptions options_;
     std::vector<BaseElement> messages, sig_rx;
