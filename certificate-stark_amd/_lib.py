@@ -47,6 +47,12 @@ class TraceReportStruct(C.Structure):
                 ("boundary_register", C.c_uint32), ("boundary_step", C.c_uint64)]
 
 
+class LedgerAuditReportStruct(C.Structure):
+    _fields_ = [("consistent", C.c_uint32), ("n_bad", C.c_uint32), ("first_kind", C.c_uint32), ("first_level", C.c_uint32),
+                ("first_index", C.c_uint64), ("n_nodes", C.c_uint64), ("slots_live", C.c_uint64), ("slots_held", C.c_uint64),
+                ("slots_free", C.c_uint64)]
+
+
 TRACE_CLEAN = 0xFFFFFFFF
 AIR_CYCLE_NAMES = ("transfer", "transfer", "signature", "trace", "link")   # per cstark_air_id: what one cycle of the trace is
 

@@ -174,17 +174,47 @@ class Backend:
         check(self.lib.cstark_ledger_root(self.ctx, led, self._hptr(root)))
         return root
 
-    def ledger_open_accounts(self, led, depth, indices):
+    def ledger_open_accounts(self, led, depth, indices, at=None):
         """cstark_ledger_open_accounts: -> (values [count][14], present bool [count], paths [count][depth + 1][7], root [7]): the
         accounts as ledger_get_accounts gives them and their authentication paths under the current root, in the witness's path form
-        (absent accounts: an all-zero leaf).  Read-only: the ledger and the resident witness are as before."""
+        (absent accounts: an all-zero leaf).  Read-only: the ledger and the resident witness are as before.
+        at: a checkpoint id -- cstark_ledger_open_accounts_at, the same under the root of that checkpoint."""
         idx = _np_u64(indices).reshape(-1)
         n = idx.size
         val, present = np.zeros((n, 14), np.uint64), np.zeros(n, np.uint8)
         paths, root = np.zeros((n, depth + 1, 7), np.uint64), np.zeros(7, np.uint64)
-        check(self.lib.cstark_ledger_open_accounts(self.ctx, led, C.c_uint32(n), self._hptr(idx), self._hptr(val), self._hptr(present, u8p),
-                                                   self._hptr(paths), self._hptr(root)))
+        out = (C.c_uint32(n), self._hptr(idx), self._hptr(val), self._hptr(present, u8p), self._hptr(paths), self._hptr(root))
+        if at is None:
+            check(self.lib.cstark_ledger_open_accounts(self.ctx, led, *out))
+        else:
+            check(self.lib.cstark_ledger_open_accounts_at(self.ctx, led, C.c_uint64(at), *out))
         return val, present.astype(bool), paths, root
+
+    # ---- ledger checkpoints: ids are plain integers, 0 = the current state ----
+    def ledger_checkpoint(self, led):
+        cp = C.c_uint64(0)
+        check(self.lib.cstark_ledger_checkpoint(self.ctx, led, C.byref(cp)))
+        return cp.value
+
+    def ledger_revert(self, led, cp):
+        check(self.lib.cstark_ledger_revert(self.ctx, led, C.c_uint64(cp)))
+
+    def ledger_release(self, led, cp):
+        check(self.lib.cstark_ledger_release(self.ctx, led, C.c_uint64(cp)))
+
+    def ledger_root_at(self, led, cp):
+        root = np.zeros(7, np.uint64)
+        check(self.lib.cstark_ledger_root_at(self.ctx, led, C.c_uint64(cp), self._hptr(root)))
+        return root
+
+    NODE_EMPTY, NODE_LEAF, NODE_INNER = 0, 1, 2   # cstark_ledger_node_kind
+
+    def ledger_audit(self, led, cp=0):
+        """cstark_ledger_audit: every stored node of the state at checkpoint cp (0: the current state) against its stored children, one
+        launch -> _lib.LedgerAuditReportStruct (consistent, n_bad, first_kind / first_level / first_index, n_nodes, slots_*)"""
+        report = _lib.LedgerAuditReportStruct()
+        check(self.lib.cstark_ledger_audit(self.ctx, led, C.c_uint64(cp), C.byref(report)))
+        return report
 
     PATH_VALID, PATH_INDEX_RANGE, PATH_LEAF, PATH_ROOT = 0, 1, 2, 3   # cstark_path_verdict
 

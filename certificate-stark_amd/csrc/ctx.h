@@ -246,6 +246,10 @@ struct cstark_gather_desc {
     uint32_t paths, a, log_n, log_b, log_s, count, lvl0;
 };
 int gather_jobs_launch(cstark_ctx *c, const cstark_gather_desc *jobs, uint32_t n_jobs);
+// internal (ledger.hip): XORs one word of a stored digest of a ledger -- what csrc/debug/debug_ledger.hip calls, so that a test can make
+// a resident tree inconsistent.  level 0xFFFFFFFF: empty-subtree slot `index`.  1: refused, nothing written.
+struct cstark_ledger;
+int ledger_xor_word(cstark_ledger *L, uint64_t id, uint32_t level, uint64_t index, uint32_t word, uint64_t mask);
 // internal (capi.hip): the cached twiddle tables of a 2^log_n-point domain: powers of w and of its inverse (device, n entries each)
 int plan_tables(cstark_ctx *c, unsigned log_n, const uint64_t **w, const uint64_t **winv);
 

@@ -12,6 +12,10 @@
 // The read side: cstark_ledger_open_accounts gathers authentication paths out of the pool (plan_open, k_ledger_gather, no hashing);
 // cstark_account_check_paths, which needs no ledger, folds paths to their roots:
 //   k_path_check      one path per 14 lanes: the leaf hash and all `depth` merges of a path in one launch
+// Checkpoints (cstark_ledger_checkpoint, _revert, _release, _root_at, _open_accounts_at) are host bookkeeping of ledger_plan.h: old states
+// are kept by not overwriting their slots, and nothing here launches for them but the gather of an opening.
+// cstark_ledger_audit tests that a state is a Merkle tree, every stored node against its STORED children, in one launch:
+//   k_ledger_audit    one list of jobs (left slot, right slot, expected slot) in the shape of k_ledger_merge; reads the pool only
 #include <stdio.h>
 #include <string.h>
 #include <new>
@@ -44,6 +48,42 @@ __global__ __launch_bounds__(64) void k_ledger_merge(fp *pool, const ledger::Job
     if (active) v = e < 7 ? pool[(size_t)7 * left + e] : pool[(size_t)7 * right + e - 7];
     for (int cyc = 0; cyc < 7; cyc++) v = rescue_round_lane(v, st[s], mrow, e, cyc, active);
     if (active && e < 7) pool[(size_t)7 * out + e] = v;
+}
+
+// cstark_ledger_audit: does merge(left, right) equal the digest stored in slot `out` (the expected slot), for jobs [0, n_jobs)?  The shape
+// of k_ledger_merge with one more load and a compare: after the permutation the lanes e < 7 hold the digest, their seven verdicts meet
+// in one wave ballot, and lane e = 0 of a failing hash reports it: result[0] = min(result[0], job), result[1] += 1 (the host pre-fills
+// 0xFFFFFFFF and 0 on the stream).  Nothing else is written, the pool never: the result does not depend on the order of the waves.  A job
+// that names a slot outside the pool fails without a load.  A workgroup without a job leaves ahead of its first barrier.
+__global__ __launch_bounds__(64) void k_ledger_audit(const fp *__restrict__ pool, const ledger::Job *__restrict__ jobs, uint32_t n_jobs, uint32_t pool_slots,
+                                                     uint32_t *__restrict__ result) {
+    __shared__ fp st[4][14];
+    if (4 * blockIdx.x >= n_jobs) return; // the whole workgroup
+    const int lane = threadIdx.x;
+    const bool is_state = lane < 56;
+    const int s = is_state ? lane / 14 : 0, e = is_state ? lane % 14 : 0;
+    const uint32_t j = 4 * blockIdx.x + s;
+    const bool active = is_state && j < n_jobs;
+    fp mrow[14];
+#pragma unroll
+    for (int k = 0; k < 14; k++) mrow[k] = c_mds[e * 14 + k];
+    uint32_t left = 0, right = 0, expected = 0;
+    bool hashing = false; // active and every slot inside the pool
+    if (active) {
+        left = jobs[j].left; right = jobs[j].right; expected = jobs[j].out;
+        hashing = left < pool_slots && right < pool_slots && expected < pool_slots;
+    }
+    fp v = 0, want = 0;
+    if (hashing) {
+        v = e < 7 ? pool[(size_t)7 * left + e] : pool[(size_t)7 * right + e - 7];
+        if (e < 7) want = pool[(size_t)7 * expected + e];
+    }
+    for (int cyc = 0; cyc < 7; cyc++) v = rescue_round_lane(v, st[s], mrow, e, cyc, hashing);
+    const unsigned long long differ = __ballot(hashing && e < 7 && v != want);
+    if (active && e == 0 && (!hashing || (differ & (0x7Full << (14 * s))))) {
+        atomicMin(&result[0], j);
+        atomicAdd(&result[1], 1u);
+    }
 }
 
 // dst[word .. word + 7) = pool slot, for emits [0, n): one thread per word
@@ -121,6 +161,7 @@ struct cstark_ledger {
     uint32_t capacity = 0;       // stored-node slots reserved
     uint64_t pool_slots = 0;
     bool broken = false;         // a HIP call failed inside a ledger call: the pool's content is unknown
+    uint32_t *audit_words = nullptr; // device: {first failing job, failing jobs} of cstark_ledger_audit, allocated by the first audit
     cstark_ledger(cstark_ctx *c, uint32_t depth) : ctx(c), index(depth) {}
 };
 
@@ -219,10 +260,10 @@ int set_accounts_impl(cstark_ledger *L, uint32_t count, const uint64_t *indices,
     return CSTARK_OK;
 }
 
-int root_impl(cstark_ledger *L, uint64_t *root) {
+int root_impl(cstark_ledger *L, uint64_t *root, size_t at = HEAD) {
     cstark_ctx *c = L->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(root, L->pool + (size_t)7 * L->index.root_slot(), 56, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(root, L->pool + (size_t)7 * L->index.slot_at(at, 0, 0), 56, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(cs::stream_wait(c->stream));
     return CSTARK_OK;
 }
@@ -286,15 +327,17 @@ int apply_impl(cstark_ledger *L, uint32_t n_tx, const uint64_t *s_indices, const
 }
 
 // one upload of the emit list, one gather into the staging area behind it, the paths and the root copied out: no hashing, and neither
-// the stored nodes nor the index nor the resident witness change (reserve_pool may move the pool)
-int open_impl(cstark_ledger *L, uint32_t count, const uint64_t *indices, uint64_t *values_out, uint8_t *present_out, uint64_t *paths_out, uint64_t *root_out) {
+// the stored nodes nor the index nor the resident witness change (reserve_pool may move the pool).  `at`: the checkpoint position whose
+// state is opened (HEAD: the current one); only the slots the list names and the values copied out differ
+int open_impl(cstark_ledger *L, uint32_t count, const uint64_t *indices, uint64_t *values_out, uint8_t *present_out, uint64_t *paths_out, uint64_t *root_out,
+              size_t at = HEAD) {
     cstark_ctx *c = L->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t d = L->index.depth;
     uint32_t scratch_base;
     RC_TRY(reserve_pool(L, 0, open_scratch_slots(d, count), &scratch_base));
     Plan p;
-    if (!plan_open(L->index, scratch_base, count, indices, p) || p.pool_slots > L->pool_slots)
+    if (!plan_open(L->index, scratch_base, count, indices, p, at) || p.pool_slots > L->pool_slots)
         return fail(CSTARK_ERR_INVALID_ARG, "ledger: the opening exceeds the reserved pool");
     uint64_t *block = L->pool + (size_t)7 * p.upload_slot, *stage = L->pool + (size_t)7 * p.stage_slot;
     const uint32_t n = (uint32_t)p.witness.size();
@@ -306,11 +349,61 @@ int open_impl(cstark_ledger *L, uint32_t count, const uint64_t *indices, uint64_
     HIP_TRY(hipMemcpyAsync(root_out, L->pool + (size_t)7 * p.final_root_slot, 56, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(cs::stream_wait(c->stream)); // the plan's host block is read by the upload
     for (uint32_t i = 0; i < count; i++) {
-        const auto it = L->index.accounts.find(indices[i]);
-        present_out[i] = it != L->index.accounts.end();
-        if (present_out[i]) memcpy(values_out + (size_t)14 * i, it->second.data(), 112);
+        const Value *v = L->index.value_at(at, indices[i]);
+        present_out[i] = v != nullptr;
+        if (v) memcpy(values_out + (size_t)14 * i, v->data(), 112);
         else memset(values_out + (size_t)14 * i, 0, 112);
     }
+    return CSTARK_OK;
+}
+
+// cstark_ledger_audit behind its argument checks: the job list of plan_audit in the scratch of the pool (one upload), the two result
+// words pre-filled on the stream, ONE k_ledger_audit, the result words and empty-subtree slot `depth` copied back.  That slot's all-zero
+// test runs here on the host; it counts as the first job of the order (kind EMPTY, level depth) when it fails.
+int audit_impl(cstark_ledger *L, size_t at, cstark_ledger_audit_report *report) {
+    cstark_ctx *c = L->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const Index &ix = L->index;
+    const uint32_t d = ix.depth;
+    const NodeMap nodes = nodes_at(ix, at);
+    uint64_t n_nodes = 0;
+    for (const auto &level : nodes) n_nodes += level.size();
+    uint32_t scratch_base;
+    RC_TRY(reserve_pool(L, 0, audit_scratch_slots(nodes[d].size(), n_nodes + d), &scratch_base));
+    Plan p;
+    if (!plan_audit(ix, at, nodes, scratch_base, p)) return fail(CSTARK_ERR_UNSUPPORTED, "cstark_ledger_audit: the state is too large to plan");
+    if (p.pool_slots > L->pool_slots) return fail(CSTARK_ERR_INVALID_ARG, "ledger: the audit exceeds the reserved pool");
+    if (!L->audit_words) HIP_TRY(hipMalloc(&L->audit_words, 8));
+    const uint32_t n = (uint32_t)p.jobs.size();
+    uint64_t *block = L->pool + (size_t)7 * p.upload_slot;
+    uint32_t words[2] = {0xFFFFFFFFu, 0};
+    uint64_t zero_slot[7];
+    HIP_TRY(hipMemcpyAsync(block, p.upload.data(), p.upload.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(L->audit_words, words, 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(cs::k_ledger_audit, dim3((n + 3) / 4), dim3(64), 0, c->stream, L->pool, (const Job *)(block + p.jobs_word), n, (uint32_t)L->pool_slots,
+                       L->audit_words);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(words, L->audit_words, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(zero_slot, L->pool + (size_t)7 * d, 56, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream)); // the words above and the plan's host block are read and written by the copies
+    bool zero_bad = false;
+    for (int k = 0; k < 7; k++) zero_bad |= zero_slot[k] != 0;
+    cstark_ledger_audit_report r = {};
+    r.n_bad = words[1] + (zero_bad ? 1 : 0);
+    r.consistent = r.n_bad == 0;
+    if (zero_bad) {
+        r.first_kind = CSTARK_LEDGER_NODE_EMPTY; r.first_level = d; r.first_index = 0;
+    } else if (words[1]) {
+        if (words[0] >= n) return fail(CSTARK_ERR_HIP, "cstark_ledger_audit: the kernel reported a job it was not given");
+        const NewNode &node = p.audited[words[0]];
+        r.first_kind = words[0] < d ? CSTARK_LEDGER_NODE_EMPTY : node.level == d ? CSTARK_LEDGER_NODE_LEAF : CSTARK_LEDGER_NODE_INNER;
+        r.first_level = node.level; r.first_index = node.x;
+    }
+    r.n_nodes = n_nodes;
+    r.slots_live = ix.live_nodes();
+    r.slots_free = ix.free_slots.size();
+    r.slots_held = ix.n_stored - r.slots_live - r.slots_free;
+    *report = r;
     return CSTARK_OK;
 }
 
@@ -371,7 +464,43 @@ int usable(cstark_ctx *c, cstark_ledger *L, const char *who) {
     return CSTARK_OK;
 }
 
+static_assert(MAX_CHECKPOINTS == CSTARK_LEDGER_MAX_CHECKPOINTS, "the documented cap is the plan's");
+// the position of checkpoint `id` (0: the current state) for the calls that take one; -1 with the error set
+ptrdiff_t checkpoint_position(cstark_ledger *L, uint64_t id, const char *who) {
+    const ptrdiff_t at = L->index.position(id);
+    if (at < 0) fail(CSTARK_ERR_INVALID_ARG, "%s: no live checkpoint of this ledger has that id (never taken, released, or dropped by a revert)", who);
+    return at;
+}
+
 } // namespace
+
+// internal, for the test-only library (include/cstark_debug_ledger.h): XORs `mask` into word `word` of the digest that the lookup at
+// checkpoint `id` finds for node (level, index), or, with level == 0xFFFFFFFF, of empty-subtree slot `index`.  One word down, one word
+// up, no launch.  1: refused (an unknown id, a node the state does not store, a word or slot out of range), nothing written.
+int ledger_xor_word(cstark_ledger *L, uint64_t id, uint32_t level, uint64_t index, uint32_t word, uint64_t mask) {
+    if (!L || L->broken || word >= 7) return 1;
+    const Index &ix = L->index;
+    const ptrdiff_t at = ix.position(id);
+    if (at < 0) return 1;
+    uint32_t slot;
+    if (level == 0xFFFFFFFFu) {
+        if (index > ix.depth) return 1;
+        slot = (uint32_t)index;
+    } else {
+        if (level > ix.depth || (index >> level)) return 1;
+        slot = ix.slot_at((size_t)at, level, index);
+        if (slot < EMPTY_SLOTS) return 1; // the state stores no such node: it reads an empty-subtree slot
+    }
+    if (slot >= L->pool_slots) return 1;
+    cstark_ctx *c = L->ctx;
+    if (hipSetDevice(c->device) != hipSuccess) return (int)hipErrorInvalidDevice;
+    uint64_t *at_word = L->pool + (size_t)7 * slot + word, w = 0;
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(&w, at_word, 8, hipMemcpyDeviceToHost);
+    w ^= mask;
+    if (e == hipSuccess) e = hipMemcpy(at_word, &w, 8, hipMemcpyHostToDevice);
+    return (int)e;
+}
 
 extern "C" {
 
@@ -393,6 +522,7 @@ void cstark_ledger_destroy(cstark_ledger *L) {
     (void)hipSetDevice(L->ctx->device);
     (void)hipStreamSynchronize(L->ctx->stream);
     if (L->pool) (void)hipFree(L->pool);
+    if (L->audit_words) (void)hipFree(L->audit_words);
     delete L;
 }
 
@@ -426,6 +556,65 @@ int cstark_ledger_open_accounts(cstark_ctx *c, cstark_ledger *L, uint32_t count,
             return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_open_accounts: %s is out of range", where);
         }
     return guard(L, open_impl(L, count, indices, values_out, present_out, paths_out, root_out));
+}
+
+int cstark_ledger_checkpoint(cstark_ctx *c, cstark_ledger *L, uint64_t *id_out) {
+    RC_TRY(usable(c, L, "cstark_ledger_checkpoint"));
+    if (!id_out) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_checkpoint: null argument");
+    const uint64_t id = checkpoint(L->index);
+    if (!id) return fail(CSTARK_ERR_UNSUPPORTED, "cstark_ledger_checkpoint: 16 checkpoints are live already (release one)");
+    *id_out = id;
+    return CSTARK_OK;
+}
+
+int cstark_ledger_revert(cstark_ctx *c, cstark_ledger *L, uint64_t id) {
+    RC_TRY(usable(c, L, "cstark_ledger_revert"));
+    if (id == 0) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_revert: id 0 is the current state");
+    const ptrdiff_t at = checkpoint_position(L, id, "cstark_ledger_revert");
+    if (at < 0) return CSTARK_ERR_INVALID_ARG;
+    revert(L->index, (size_t)at);
+    return CSTARK_OK;
+}
+
+int cstark_ledger_release(cstark_ctx *c, cstark_ledger *L, uint64_t id) {
+    RC_TRY(usable(c, L, "cstark_ledger_release"));
+    if (id == 0) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_release: id 0 is the current state");
+    const ptrdiff_t at = checkpoint_position(L, id, "cstark_ledger_release");
+    if (at < 0) return CSTARK_ERR_INVALID_ARG;
+    release(L->index, (size_t)at);
+    return CSTARK_OK;
+}
+
+int cstark_ledger_root_at(cstark_ctx *c, cstark_ledger *L, uint64_t id, uint64_t root[7]) {
+    RC_TRY(usable(c, L, "cstark_ledger_root_at"));
+    if (!root) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_root_at: null argument");
+    const ptrdiff_t at = checkpoint_position(L, id, "cstark_ledger_root_at");
+    if (at < 0) return CSTARK_ERR_INVALID_ARG;
+    return guard(L, root_impl(L, root, (size_t)at));
+}
+
+int cstark_ledger_open_accounts_at(cstark_ctx *c, cstark_ledger *L, uint64_t id, uint32_t count, const uint64_t *indices, uint64_t *values_out,
+                                   uint8_t *present_out, uint64_t *paths_out, uint64_t root_out[7]) {
+    RC_TRY(usable(c, L, "cstark_ledger_open_accounts_at"));
+    if (count == 0 || count > MAX_TRANSFERS || !indices || !values_out || !present_out || !paths_out || !root_out)
+        return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_open_accounts_at: bad argument");
+    const ptrdiff_t at = checkpoint_position(L, id, "cstark_ledger_open_accounts_at");
+    if (at < 0) return CSTARK_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < count; i++)
+        if (indices[i] >> L->index.depth) {
+            char where[32];
+            snprintf(where, sizeof where, "indices[%u]", i);
+            return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_open_accounts_at: %s is out of range", where);
+        }
+    return guard(L, open_impl(L, count, indices, values_out, present_out, paths_out, root_out, (size_t)at));
+}
+
+int cstark_ledger_audit(cstark_ctx *c, cstark_ledger *L, uint64_t id, cstark_ledger_audit_report *report) {
+    RC_TRY(usable(c, L, "cstark_ledger_audit"));
+    if (!report) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_audit: null argument");
+    const ptrdiff_t at = checkpoint_position(L, id, "cstark_ledger_audit");
+    if (at < 0) return CSTARK_ERR_INVALID_ARG;
+    return guard(L, audit_impl(L, (size_t)at, report));
 }
 
 int cstark_account_check_paths(cstark_ctx *c, uint32_t count, uint32_t depth, const uint64_t *indices, const uint64_t *values, const uint8_t *present,

@@ -16,9 +16,19 @@
 // A plan is job lists (left slot, right slot, output slot), one per launch, and emit lists (pool slot -> 64-bit word offset): one into
 // the resident witness (witness_layout.h), one back into the pool (the touched nodes' last versions become the stored nodes).
 // Values, jobs and emit lists form one contiguous block: one host-to-device copy.
+//
+// Checkpoints (cstark_ledger_checkpoint ...) keep old states by NOT overwriting them.  While a checkpoint is live, the first write of a
+// node since the newest checkpoint goes to a fresh slot, Index::node is redirected to it, and the newest checkpoint's log records
+// (level, x) -> the old slot, or ABSENT_SLOT for a node that did not exist (it reads as the level's empty-subtree slot).  Old account
+// values are logged the same way.  The log of checkpoint c_i therefore holds the state at c_i of exactly the nodes first changed in
+// [c_i, c_i+1): the state at c is found by searching the log of c, then the logs after it in order, then the index (Index::slot_at).
+// The plans only name other slots: no launch and no copy is added.  Freed slots go on Index::free_slots and are taken before the pool
+// is extended; Index::n_stored counts the slots ever allocated, the upper end of the stored nodes in the pool.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include <string.h>
+#include <algorithm>
 #include <array>
 #include <unordered_map>
 #include <unordered_set>
@@ -34,6 +44,9 @@ constexpr uint32_t EMPTY_SLOTS = 33;
 constexpr uint32_t MAX_DEPTH = 31;
 constexpr uint32_t MAX_TRANSFERS = 1u << 20;
 constexpr uint64_t MAX_POOL_SLOTS = 1ull << 28; // 15 GB of digests: far beyond any batch, keeps every slot and word offset in 32 bits
+constexpr uint32_t MAX_CHECKPOINTS = 16;        // live checkpoints of one ledger: a lookup walks at most this many logs
+constexpr uint32_t ABSENT_SLOT = 0xFFFFFFFFu;   // in a checkpoint's log: the node did not exist at the checkpoint
+constexpr size_t HEAD = ~(size_t)0;             // a checkpoint position that names the current state
 
 struct Job { uint32_t left, right, out, reserved; };
 struct Emit { uint32_t slot, word; };
@@ -44,18 +57,79 @@ enum Reason : int32_t { REASON_NONE = 0, REASON_INDEX = 1, REASON_SELF = 2, REAS
 
 typedef std::array<uint64_t, 14> Value; // pk.x(6) pk.y(6) balance nonce, memory form
 
+typedef std::vector<std::unordered_map<uint64_t, uint32_t>> NodeMap; // [depth + 1]: index within the level -> pool slot
+
+// the log of one checkpoint: what the nodes and accounts first changed since it (and before the next checkpoint) were at the checkpoint
+struct Checkpoint {
+    uint64_t id;
+    NodeMap node;                                                   // -> the old slot, or ABSENT_SLOT
+    std::unordered_map<uint64_t, std::pair<bool, Value>> accounts; // -> (present, the old value)
+    Checkpoint(uint64_t i, uint32_t depth) : id(i), node(depth + 1) {}
+};
+
 // what the host keeps of a ledger: which nodes exist (and their pool slots) and the account values the balance walk needs
 struct Index {
     uint32_t depth;
-    uint32_t n_stored = 0;
-    std::vector<std::unordered_map<uint64_t, uint32_t>> node; // [depth + 1]: index within the level -> pool slot
-    std::unordered_map<uint64_t, Value> accounts;             // by leaf index
+    uint32_t n_stored = 0;                        // slots allocated so far: stored nodes live in [EMPTY_SLOTS, EMPTY_SLOTS + n_stored)
+    NodeMap node;
+    std::unordered_map<uint64_t, Value> accounts; // by leaf index
+    std::vector<uint32_t> free_slots;             // allocated slots nothing names any more; taken (from the back) before the pool is extended
+    std::vector<Checkpoint> checkpoints;          // live ones, oldest first
+    uint64_t next_id = 1;                         // ids count from 1 and are never reused
     explicit Index(uint32_t d) : depth(d), node(d + 1) {}
     uint32_t slot(uint32_t level, uint64_t x) const {
         const auto it = node[level].find(x);
         return it == node[level].end() ? level : it->second;
     }
     uint32_t root_slot() const { return slot(0, 0); }
+    // the position of a live checkpoint in `checkpoints`; id 0 is the current state (HEAD); -1: no such live checkpoint
+    ptrdiff_t position(uint64_t id) const {
+        if (id == 0) return (ptrdiff_t)checkpoints.size();
+        for (size_t k = 0; k < checkpoints.size(); k++)
+            if (checkpoints[k].id == id) return (ptrdiff_t)k;
+        return -1;
+    }
+    // Index::slot in the state at checkpoint position `at`: the first log from `at` on that holds the node answers, else the index
+    uint32_t slot_at(size_t at, uint32_t level, uint64_t x) const {
+        for (size_t k = at; k < checkpoints.size(); k++) {
+            const auto it = checkpoints[k].node[level].find(x);
+            if (it != checkpoints[k].node[level].end()) return it->second == ABSENT_SLOT ? level : it->second;
+        }
+        return slot(level, x);
+    }
+    // the account's value in that state, nullptr where it had none
+    const Value *value_at(size_t at, uint64_t a) const {
+        for (size_t k = at; k < checkpoints.size(); k++) {
+            const auto it = checkpoints[k].accounts.find(a);
+            if (it != checkpoints[k].accounts.end()) return it->second.first ? &it->second.second : nullptr;
+        }
+        const auto it = accounts.find(a);
+        return it == accounts.end() ? nullptr : &it->second;
+    }
+    // the slot a write of this node goes to in place, or ABSENT_SLOT where it must take a fresh one: the node has none yet, or this is
+    // its first write since the newest checkpoint.  Without a live checkpoint this is the one lookup the plans always did.
+    uint32_t slot_in_place(uint32_t level, uint64_t x) const {
+        const auto it = node[level].find(x);
+        if (it == node[level].end()) return ABSENT_SLOT;
+        if (!checkpoints.empty() && !checkpoints.back().node[level].count(x)) return ABSENT_SLOT;
+        return it->second;
+    }
+    uint64_t live_nodes() const {
+        uint64_t n = 0;
+        for (const auto &level : node) n += level.size();
+        return n;
+    }
+};
+
+// the slots a plan takes: from the back of the free list first, then by extending the stored nodes; commit() makes it so
+struct SlotTaker {
+    const Index &ix;
+    uint32_t from_free = 0, extended = 0;
+    explicit SlotTaker(const Index &i) : ix(i) {}
+    uint32_t take() {
+        if (from_free < ix.free_slots.size()) return ix.free_slots[ix.free_slots.size() - 1 - from_free++];
+        return EMPTY_SLOTS + ix.n_stored + extended++;
+    }
 };
 
 struct NewNode { uint32_t level; uint64_t x; uint32_t slot; };
@@ -71,12 +145,17 @@ struct Plan {
     uint32_t final_root_slot = 0;    // the root after the call (a scratch slot for plan_apply)
     uint64_t pool_slots = 0;         // slots the pool must hold for this call
     uint32_t stage_slot = 0;         // plan_open: the staging area its emit list fills
-    // what commit() changes in the index
+    // what commit() changes in the index: nodes created or redirected to a fresh slot, the slots they took, the accounts' new values
     std::vector<NewNode> new_nodes;
+    uint32_t from_free = 0, extended = 0;
     std::vector<std::pair<uint64_t, Value>> new_values;
+    // plan_audit: the node every job tests, in job order (jobs [0, depth) test the empty-subtree slots, x = 0), and the leaf count
+    std::vector<NewNode> audited;
+    uint32_t audit_leaves = 0;
 };
 
-// slots a call may add to the stored nodes: the caller places scratch_base beyond EMPTY_SLOTS + n_stored + this bound
+// slots a call may add to the stored nodes (the number of touched nodes: under a live checkpoint every one of them may take a fresh
+// slot): the caller places scratch_base beyond EMPTY_SLOTS + n_stored + this bound
 inline uint64_t max_new_nodes(uint32_t depth, uint64_t leaves) { return leaves * (depth + 1); }
 
 namespace detail {
@@ -93,20 +172,21 @@ inline void pack_lists(Plan &p) {
 } // namespace detail
 
 // cstark_ledger_set_accounts: leaf hashes of the given accounts, then the unique parents level by level, written straight into the
-// stored nodes (every node is written once per call).  false: misuse (an index out of range or given twice, a value word >= p).
+// stored nodes (every node is written once per call; under a live checkpoint the first write since it takes a fresh slot).
+// false: misuse (an index out of range or given twice, a value word >= p).
 inline bool plan_set_accounts(const Index &ix, uint32_t scratch_base, uint32_t count, const uint64_t *indices, const uint64_t *values, Plan &p) {
     const uint32_t d = ix.depth;
     const uint64_t size = (uint64_t)1 << d;
     std::vector<std::unordered_map<uint64_t, uint32_t>> fresh(d + 1);
-    uint32_t n_stored = ix.n_stored;
+    SlotTaker slots(ix);
     auto lookup = [&](uint32_t l, uint64_t x) -> uint32_t {
         const auto it = fresh[l].find(x);
         return it != fresh[l].end() ? it->second : ix.slot(l, x);
     };
     auto stored = [&](uint32_t l, uint64_t x) -> uint32_t {
-        const auto it = ix.node[l].find(x);
-        if (it != ix.node[l].end()) return it->second;
-        const uint32_t s = EMPTY_SLOTS + n_stored++;
+        const uint32_t in_place = ix.slot_in_place(l, x);
+        if (in_place != ABSENT_SLOT) return in_place;
+        const uint32_t s = slots.take();
         fresh[l][x] = s;
         p.new_nodes.push_back({l, x, s});
         return s;
@@ -138,6 +218,8 @@ inline bool plan_set_accounts(const Index &ix, uint32_t scratch_base, uint32_t c
         touched.swap(parents);
     }
     p.final_root_slot = lookup(0, 0);
+    p.from_free = slots.from_free;
+    p.extended = slots.extended;
     detail::pack_lists(p);
     return p.pool_slots <= MAX_POOL_SLOTS;
 }
@@ -259,19 +341,20 @@ inline bool plan_apply(const Index &ix, uint32_t scratch_base, uint32_t n_tx, co
         }
     }
 
-    // the ledger advances: every touched node's last version becomes the stored node
-    uint32_t n_stored = ix.n_stored;
+    // the ledger advances: every touched node's last version becomes the stored node (in a fresh slot where the node is new or a live
+    // checkpoint still names the old one)
+    SlotTaker slots(ix);
     for (uint32_t l = 0; l <= d; l++)
         for (const auto &kv : last[l]) {
-            const auto it = ix.node[l].find(kv.first);
-            uint32_t dst;
-            if (it != ix.node[l].end()) dst = it->second;
-            else {
-                dst = EMPTY_SLOTS + n_stored++;
+            uint32_t dst = ix.slot_in_place(l, kv.first);
+            if (dst == ABSENT_SLOT) {
+                dst = slots.take();
                 p.new_nodes.push_back({l, kv.first, dst});
             }
             p.commit.push_back({D(l, kv.second), dst * 7});
         }
+    p.from_free = slots.from_free;
+    p.extended = slots.extended;
     p.final_root_slot = D(0, ne - 1);
     for (const auto &kv : cur) p.new_values.emplace_back(kv.first, kv.second);
     detail::pack_lists(p);
@@ -282,9 +365,10 @@ inline bool plan_apply(const Index &ix, uint32_t scratch_base, uint32_t n_tx, co
 // leaf, path[k + 1] = the sibling at level depth - k).  One emit list of count (depth + 1) entries, `witness`, whose word offsets count
 // from the staging area [stage_slot, stage_slot + count (depth + 1)) that follows the list in the scratch: path i starts at word
 // 7 (depth + 1) i.  An absent leaf and an untouched sibling read the level's empty-subtree slot (Index::slot).  Indices may repeat.
+// `at`: the checkpoint position whose state is opened (Index::slot_at; HEAD = the current state, the lookup is Index::slot then).
 // Nothing of the index changes and nothing is hashed.  false: an index is out of range, or the call is too large to plan.
 inline uint64_t open_scratch_slots(uint32_t depth, uint64_t count) { return (count * (depth + 1) + 6) / 7 + count * (depth + 1); }
-inline bool plan_open(const Index &ix, uint32_t scratch_base, uint32_t count, const uint64_t *indices, Plan &p) {
+inline bool plan_open(const Index &ix, uint32_t scratch_base, uint32_t count, const uint64_t *indices, Plan &p, size_t at = HEAD) {
     const uint32_t d = ix.depth;
     const uint64_t size = (uint64_t)1 << d;
     if (count == 0 || count > MAX_TRANSFERS || (uint64_t)scratch_base + open_scratch_slots(d, count) > MAX_POOL_SLOTS) return false;
@@ -295,21 +379,142 @@ inline bool plan_open(const Index &ix, uint32_t scratch_base, uint32_t count, co
     for (uint32_t i = 0; i < count; i++) {
         const uint64_t a = indices[i];
         const uint32_t word = 7 * (d + 1) * i; // below 2^20 * 32 * 7
-        p.witness.push_back({ix.slot(d, a), word});
-        for (uint32_t k = 0; k < d; k++) p.witness.push_back({ix.slot(d - k, (a >> k) ^ 1), word + 7 * (k + 1)});
+        p.witness.push_back({ix.slot_at(at, d, a), word});
+        for (uint32_t k = 0; k < d; k++) p.witness.push_back({ix.slot_at(at, d - k, (a >> k) ^ 1), word + 7 * (k + 1)});
     }
-    p.final_root_slot = ix.root_slot();
+    p.final_root_slot = ix.slot_at(at, 0, 0);
     detail::pack_lists(p);
     p.stage_slot = (uint32_t)p.pool_slots;
     p.pool_slots += p.witness.size();
     return p.pool_slots <= MAX_POOL_SLOTS;
 }
 
-// after the device work of a plan has been enqueued: the index follows
+// after the device work of a plan has been enqueued: the index follows, and the newest live checkpoint logs what it replaces
 inline void commit(Index &ix, const Plan &p) {
-    for (const NewNode &nn : p.new_nodes) ix.node[nn.level][nn.x] = nn.slot;
-    ix.n_stored += (uint32_t)p.new_nodes.size();
-    for (const auto &kv : p.new_values) ix.accounts[kv.first] = kv.second;
+    Checkpoint *log = ix.checkpoints.empty() ? nullptr : &ix.checkpoints.back();
+    for (const NewNode &nn : p.new_nodes) {
+        if (log) {
+            const auto it = ix.node[nn.level].find(nn.x);
+            log->node[nn.level].emplace(nn.x, it == ix.node[nn.level].end() ? ABSENT_SLOT : it->second);
+        }
+        ix.node[nn.level][nn.x] = nn.slot;
+    }
+    ix.free_slots.resize(ix.free_slots.size() - p.from_free);
+    ix.n_stored += p.extended;
+    for (const auto &kv : p.new_values) {
+        if (log && !log->accounts.count(kv.first)) {
+            const auto it = ix.accounts.find(kv.first);
+            log->accounts.emplace(kv.first, it == ix.accounts.end() ? std::make_pair(false, Value{}) : std::make_pair(true, it->second));
+        }
+        ix.accounts[kv.first] = kv.second;
+    }
+}
+
+// cstark_ledger_checkpoint: names the current state.  0: the cap of MAX_CHECKPOINTS live checkpoints is reached.
+inline uint64_t checkpoint(Index &ix) {
+    if (ix.checkpoints.size() >= MAX_CHECKPOINTS) return 0;
+    ix.checkpoints.emplace_back(ix.next_id, ix.depth);
+    return ix.next_id++;
+}
+
+// cstark_ledger_revert: the index goes back to the state at position `at`.  The logs are undone from the newest down to that one; the
+// slot a node holds when its log entry is undone was written after that checkpoint and is named by nothing older, so it is freed.
+// The checkpoints after `at` are dropped and `at` stays live with an empty log.  Host bookkeeping only.
+inline void revert(Index &ix, size_t at) {
+    for (size_t k = ix.checkpoints.size(); k-- > at;) {
+        Checkpoint &c = ix.checkpoints[k];
+        for (uint32_t l = 0; l <= ix.depth; l++)
+            for (const auto &kv : c.node[l]) {
+                const auto it = ix.node[l].find(kv.first);
+                ix.free_slots.push_back(it->second);
+                if (kv.second == ABSENT_SLOT) ix.node[l].erase(it);
+                else it->second = kv.second;
+            }
+        for (const auto &kv : c.accounts) {
+            if (kv.second.first) ix.accounts[kv.first] = kv.second.second;
+            else ix.accounts.erase(kv.first);
+        }
+    }
+    ix.checkpoints.erase(ix.checkpoints.begin() + at + 1, ix.checkpoints.end());
+    Checkpoint &c = ix.checkpoints[at];
+    for (auto &level : c.node) level.clear();
+    c.accounts.clear();
+}
+
+// cstark_ledger_release: the checkpoint at position `at` ends.  Its log merges into its predecessor's, where the entries the predecessor
+// already holds win (the state at the predecessor is older): the loser's slot was the node's between the two checkpoints and nothing
+// names it any more.  The oldest checkpoint has no predecessor: all its slots are freed.
+inline void release(Index &ix, size_t at) {
+    Checkpoint &c = ix.checkpoints[at];
+    Checkpoint *before = at ? &ix.checkpoints[at - 1] : nullptr;
+    for (uint32_t l = 0; l <= ix.depth; l++)
+        for (const auto &kv : c.node[l])
+            if (!(before && before->node[l].emplace(kv.first, kv.second).second) && kv.second != ABSENT_SLOT) ix.free_slots.push_back(kv.second);
+    if (before)
+        for (const auto &kv : c.accounts) before->accounts.emplace(kv.first, kv.second);
+    ix.checkpoints.erase(ix.checkpoints.begin() + at);
+}
+
+// the nodes of the state at checkpoint position `at`, all levels: the index with the logs from the newest down to `at` undone on a copy
+inline NodeMap nodes_at(const Index &ix, size_t at) {
+    NodeMap m = ix.node;
+    for (size_t k = ix.checkpoints.size(); k > at; k--)
+        for (uint32_t l = 0; l <= ix.depth; l++)
+            for (const auto &kv : ix.checkpoints[k - 1].node[l]) {
+                if (kv.second == ABSENT_SLOT) m[l].erase(kv.first);
+                else m[l][kv.first] = kv.second;
+            }
+    return m;
+}
+
+// cstark_ledger_audit: is the state at `at` a Merkle tree?  ONE list of independent jobs (left, right, expected): the job passes iff
+// merge(left, right) equals the digest STORED in slot `expected` (Job::out; nothing is written).  Every job reads stored children, never
+// recomputed ones, so one launch serves all levels.  The order is fixed, and Plan::audited names the node of every job:
+//   1. the empty-subtree slots, level depth - 1 down to 0: slot l against merge(slot l + 1, slot l + 1)        [depth jobs]
+//   2. the leaves by ascending index: the two halves of the account's value, uploaded as a slot pair           [n_leaves jobs]
+//   3. the inner nodes, level depth - 1 down to 0, ascending x within a level: the children by Index::slot_at  [n_inner jobs]
+// The all-zero test of slot `depth` is no job: the caller reads that one slot back and compares it on the host.
+// false: the state is too large to plan.
+inline uint64_t audit_scratch_slots(uint64_t leaves, uint64_t jobs) { return 2 * leaves + (2 * jobs + 6) / 7; }
+inline bool plan_audit(const Index &ix, size_t at, const NodeMap &m /* nodes_at(ix, at) */, uint32_t scratch_base, Plan &p) {
+    const uint32_t d = ix.depth;
+    uint64_t n_jobs = d;
+    for (const auto &level : m) n_jobs += level.size();
+    const uint64_t n_leaves = m[d].size();
+    if (n_jobs > 0xFFFFFFF0ull || (uint64_t)scratch_base + audit_scratch_slots(n_leaves, n_jobs) > MAX_POOL_SLOTS) return false;
+    p.upload_slot = scratch_base;
+    p.audit_leaves = (uint32_t)n_leaves;
+    p.upload.assign((size_t)14 * n_leaves, 0);
+    p.jobs.reserve(n_jobs);
+    p.audited.reserve(n_jobs);
+    for (uint32_t l = d; l-- > 0;) {
+        p.jobs.push_back({l + 1, l + 1, l, 0});
+        p.audited.push_back({l, 0, l});
+    }
+    std::vector<std::pair<uint64_t, uint32_t>> sorted;
+    for (uint32_t l = d + 1; l-- > 0;) {
+        sorted.assign(m[l].begin(), m[l].end());
+        std::sort(sorted.begin(), sorted.end());
+        for (size_t i = 0; i < sorted.size(); i++) {
+            const uint64_t x = sorted[i].first;
+            if (l == d) {
+                const Value *v = ix.value_at(at, x); // a stored leaf without an account fails its job against the zero value
+                if (v) memcpy(&p.upload[14 * i], v->data(), sizeof *v);
+                p.jobs.push_back({scratch_base + 2 * (uint32_t)i, scratch_base + 2 * (uint32_t)i + 1, sorted[i].second, 0});
+            } else {
+                auto child = [&](uint64_t y) -> uint32_t {
+                    const auto it = m[l + 1].find(y);
+                    return it == m[l + 1].end() ? l + 1 : it->second;
+                };
+                p.jobs.push_back({child(2 * x), child(2 * x + 1), sorted[i].second, 0});
+            }
+            p.audited.push_back({l, x, sorted[i].second});
+        }
+    }
+    p.launch = {0, (uint32_t)p.jobs.size()};
+    p.final_root_slot = p.audited.empty() ? 0 : ix.slot_at(at, 0, 0);
+    detail::pack_lists(p);
+    return p.pool_slots <= MAX_POOL_SLOTS;
 }
 
 // the depth launches that fill the empty-subtree digests of a new ledger (slot depth is the all-zero leaf): one job each

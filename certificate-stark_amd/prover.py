@@ -159,18 +159,40 @@ class Ledger:
         """bulk insert or overwrite: distinct leaf indices, values [count][14] (pk.x pk.y balance nonce, memory form)"""
         self.backend.ledger_set_accounts(self._led, indices, values)
 
-    def root(self):
-        return self.backend.ledger_root(self._led)
+    def root(self, at=None):
+        """the current root, or with at=checkpoint the root at that checkpoint"""
+        return self.backend.ledger_root(self._led) if at is None else self.backend.ledger_root_at(self._led, at)
 
     def accounts(self, indices):
         """-> (values [count][14], present [count])"""
         return self.backend.ledger_get_accounts(self._led, indices)
 
-    def open(self, indices):
+    def open(self, indices, at=None):
         """-> AccountOpening: values, presence and authentication paths of the given leaves under the current root (indices may repeat
-        and may name absent accounts: that is a proof of absence).  Read-only."""
+        and may name absent accounts: that is a proof of absence).  Read-only.  at=checkpoint: the same as the ledger was at that
+        checkpoint, under the root a proof of that moment binds (an account created since is absent)."""
         idx = np.ascontiguousarray(indices, np.uint64).reshape(-1)
-        return AccountOpening(idx, *self.backend.ledger_open_accounts(self._led, self.depth, idx), backend=self.backend)
+        return AccountOpening(idx, *self.backend.ledger_open_accounts(self._led, self.depth, idx, at=at), backend=self.backend)
+
+    def checkpoint(self):
+        """-> an id that names the ledger's state as it is now (an integer >= 1, never reused).  No device work; old states are kept by
+        not overwriting them, so apply() costs what it costs without one.  At most 16 are live at once (CstarkError -5 beyond)."""
+        return self.backend.ledger_checkpoint(self._led)
+
+    def revert(self, cp):
+        """the ledger goes back to checkpoint cp: root, accounts and openings of that moment; checkpoints taken after cp are dropped,
+        cp stays live.  The resident witness is left alone: it is still the last applied batch's."""
+        self.backend.ledger_revert(self._led, cp)
+
+    def release(self, cp):
+        """checkpoint cp ends; the current state and the other checkpoints are unchanged"""
+        self.backend.ledger_release(self._led, cp)
+
+    def audit(self, at=None):
+        """-> the audit report of the current state (or of checkpoint `at`): .consistent, .n_bad, the first failing node as .first_kind
+        (Backend.NODE_EMPTY / NODE_LEAF / NODE_INNER), .first_level, .first_index; .n_nodes; .slots_live / .slots_held / .slots_free of
+        the whole ledger.  Every stored node is hashed from its stored children on the GPU, in one launch.  Read-only."""
+        return self.backend.ledger_audit(self._led, 0 if at is None else at)
 
     def apply(self, transfers, want_witness=True, check_signatures=False):
         """transfers: (s_indices, r_indices, deltas, sig_rx, sig_s) or an object with these attributes (a TransactionMetadata, say).

@@ -548,6 +548,54 @@ int cstark_ledger_apply_checked(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t
                                 const uint64_t *deltas, const uint64_t *sig_rx, const uint8_t *sig_s, cstark_tx_witness *out,
                                 int32_t *refused_at, int32_t *reason);
 
+/* ---- ledger checkpoints: take a batch back, open accounts under a past root, audit the resident tree -----------------------------
+ * A checkpoint names the ledger's state at the moment it is taken.  Old states are kept by not overwriting them: while a checkpoint is
+ * live, the first change of a tree node since the newest checkpoint goes to a fresh slot of the device pool and the old slot stays as it
+ * is.  cstark_ledger_apply and cstark_ledger_set_accounts run the same launches and copies with and without live
+ * checkpoints and write the same witness; a ledger without a live checkpoint allocates what it always did.  Ids are 64-bit, count from
+ * 1 and are never reused within a ledger; 0 means "the current state" wherever an id is read (revert and release refuse it).  At most
+ * CSTARK_LEDGER_MAX_CHECKPOINTS are live at once: one more is CSTARK_ERR_UNSUPPORTED.  Misuse as for the other ledger calls: null
+ * pointers, a ledger of another context, or an id that is unknown, released or dropped by a revert give CSTARK_ERR_INVALID_ARG with the
+ * outputs untouched; a ledger broken by an earlier HIP failure gives CSTARK_ERR_HIP; every call is synchronous on the ledger's context. */
+#define CSTARK_LEDGER_MAX_CHECKPOINTS 16
+/* O(1), no device work. */
+int cstark_ledger_checkpoint(cstark_ctx *ctx, cstark_ledger *ledger, uint64_t *id_out);
+/* The ledger's state becomes the state at `id`: root, accounts and openings are those of that moment, the slots written since are free
+ * again, the checkpoints taken after `id` are dropped (their ids are invalid from now on) and `id` itself stays live, so it can be
+ * reverted to again.  Host bookkeeping only: nothing is launched or copied.  The RESIDENT WITNESS is left alone: it is still the last
+ * applied batch's, and proving it stays legal although the ledger no longer holds its final root. */
+int cstark_ledger_revert(cstark_ctx *ctx, cstark_ledger *ledger, uint64_t id);
+/* The checkpoint ends; the current state and the other checkpoints are unchanged, the slots only it kept are free again.  No device work. */
+int cstark_ledger_release(cstark_ctx *ctx, cstark_ledger *ledger, uint64_t id);
+/* cstark_ledger_root for the state at `id` (0: the current state). */
+int cstark_ledger_root_at(cstark_ctx *ctx, cstark_ledger *ledger, uint64_t id, uint64_t root[7]);
+/* cstark_ledger_open_accounts for the state at `id`, with the same arguments, outputs and refusals: values, presence, paths and root
+ * as they were at the checkpoint (an account created later is absent: an all-zero leaf under the old siblings).  One upload, one
+ * gather, no hashing.  With id 0 it is cstark_ledger_open_accounts, byte for byte. */
+int cstark_ledger_open_accounts_at(cstark_ctx *ctx, cstark_ledger *ledger, uint64_t id, uint32_t count, const uint64_t *indices,
+                                   uint64_t *values_out /* [count][14] */, uint8_t *present_out /* [count] */,
+                                   uint64_t *paths_out /* [count][depth + 1][7] */, uint64_t root_out[7]);
+/* The audit: is the state at `id` (0: the current one) a Merkle tree?  Three kinds of test, every one on digests as they are STORED:
+ *   EMPTY  empty-subtree digest l equals merge(digest l + 1, digest l + 1), and digest `depth` is all zero;
+ *   LEAF   every stored leaf equals merge(value[0..7], value[7..14]) of its account;
+ *   INNER  every stored inner node (level, x) equals merge of its children (level + 1, 2x) and (level + 1, 2x + 1), an untouched child
+ *          reading the empty-subtree digest of its level.
+ * The tests run in one launch in a fixed order: EMPTY from level depth down to 0, LEAF by ascending index, INNER from level depth - 1
+ * down to 0 (the root) and by ascending x within a level.  A wrong node fails its own test and, unless it is the root, its parent's.
+ * An inconsistency is a finding, not a failure of the call: the status is CSTARK_OK and the report says so.  Read-only: pool, index,
+ * root and resident witness are unchanged.  A state too large to plan is CSTARK_ERR_UNSUPPORTED. */
+typedef enum cstark_ledger_node_kind { CSTARK_LEDGER_NODE_EMPTY = 0, CSTARK_LEDGER_NODE_LEAF = 1, CSTARK_LEDGER_NODE_INNER = 2 } cstark_ledger_node_kind;
+typedef struct cstark_ledger_audit_report {
+    uint32_t consistent;        /* 1: every test passed */
+    uint32_t n_bad;             /* failing tests */
+    uint32_t first_kind;        /* cstark_ledger_node_kind of the first failing test in the order above (0 when consistent) */
+    uint32_t first_level;       /* its level: 0 = the root, depth = the leaves; for EMPTY the level of the digest */
+    uint64_t first_index;       /* its index within the level (0 for EMPTY) */
+    uint64_t n_nodes;           /* nodes of the audited state, all levels */
+    uint64_t slots_live, slots_held, slots_free; /* of the whole ledger: current nodes, slots only checkpoints keep, free list */
+} cstark_ledger_audit_report;
+int cstark_ledger_audit(cstark_ctx *ctx, cstark_ledger *ledger, uint64_t id, cstark_ledger_audit_report *report);
+
 /* ---- verification (TransactionExample::verify, src/lib.rs:144-150: winterfell::verify over this library's own proof layout) -------
  * The call's status (cstark_status) is kept apart from the proof's verdict.  A verdict names the FIRST check that fails, in this
  * order: layout (MALFORMED, then UNSUPPORTED) | OPTIONS_MISMATCH | OOD | REMAINDER_COMMITMENT | POW | per query q = 0..nq-1:

@@ -255,6 +255,42 @@ class Ledger {
                                           o.root.data()));
         return o;
     }
+    // ---- checkpoints (cstark_ledger_checkpoint ...): ids are integers >= 1, never reused; 0 names the current state where an id is read
+    // names the state as it is now; no device work, and apply() costs what it costs without one.  At most
+    // CSTARK_LEDGER_MAX_CHECKPOINTS are live at once (Error CSTARK_ERR_UNSUPPORTED beyond)
+    uint64_t checkpoint() {
+        uint64_t id = 0;
+        check(cstark_ledger_checkpoint(ctx_.raw(), led_, &id));
+        return id;
+    }
+    // the ledger goes back to the checkpoint: later checkpoints are dropped, this one stays live.  The resident witness is left alone
+    void revert(uint64_t id) { check(cstark_ledger_revert(ctx_.raw(), led_, id)); }
+    void release(uint64_t id) { check(cstark_ledger_release(ctx_.raw(), led_, id)); }
+    Hash root(uint64_t at) const {
+        Hash r{};
+        check(cstark_ledger_root_at(ctx_.raw(), led_, at, r.data()));
+        return r;
+    }
+    // open() as the ledger was at checkpoint `at`: under the root a proof of that moment binds
+    AccountOpening open(const std::vector<uint64_t> &indices, uint64_t at) const {
+        if (indices.empty()) throw Error(CSTARK_ERR_INVALID_ARG, "no account index to open");
+        AccountOpening o;
+        o.depth = depth_;
+        o.indices = indices;
+        o.values.resize(indices.size());
+        o.present.resize(indices.size());
+        o.paths.resize(indices.size() * (depth_ + 1) * 7);
+        check(cstark_ledger_open_accounts_at(ctx_.raw(), led_, at, (uint32_t)indices.size(), indices.data(), o.values[0].data(), o.present.data(),
+                                             o.paths.data(), o.root.data()));
+        return o;
+    }
+    // every stored node of the state at `at` (0: the current one) against its stored children, on the GPU in one launch.  Read-only; an
+    // inconsistency is reported (consistent == 0, the first failing node named), not thrown
+    cstark_ledger_audit_report audit(uint64_t at = 0) const {
+        cstark_ledger_audit_report r{};
+        check(cstark_ledger_audit(ctx_.raw(), led_, at, &r));
+        return r;
+    }
     // applies the transfers in order; throws TransferRefused (nothing changed) at the first one that cannot be applied.  Signatures are
     // copied through unchecked, and TransactionAir does not bind them: a forged one still proves and verifies (apply_checked)
     TransactionMetadata apply(const Transfers &t) { return apply(t, false); }
