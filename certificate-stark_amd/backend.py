@@ -246,6 +246,65 @@ class Backend:
                                                   self._hptr(out) if want_roots else None))
         return (verdicts, out) if want_roots else verdicts
 
+    MULTI_VALID, MULTI_INDEX, MULTI_NODE_COUNT, MULTI_ROOT = 0, 1, 2, 3   # cstark_multi_verdict
+
+    def account_multiproof_shape(self, depth, indices):
+        """cstark_account_multiproof_shape (host only): -> (n_nodes, n_merges) of the multiproof of the strictly ascending `indices`"""
+        idx = _np_u64(indices).reshape(-1)
+        n_nodes, n_merges = C.c_uint32(0), C.c_uint32(0)
+        check(self.lib.cstark_account_multiproof_shape(C.c_uint32(depth), C.c_uint32(idx.size), self._hptr(idx), C.byref(n_nodes), C.byref(n_merges)))
+        return n_nodes.value, n_merges.value
+
+    def ledger_open_multi(self, led, depth, indices, at=None):
+        """cstark_ledger_open_multi: -> (values [count][14], present bool [count], nodes [n_nodes][7], root [7]): the accounts at the
+        strictly ascending `indices` and ONE multiproof for all of them -- the de-duplicated siblings, level `depth` first and ascending
+        within a level (include/cstark.h) -- under the current root, or with at=checkpoint id under the root of that checkpoint.
+        Read-only: one gather, no hashing; the ledger and the resident witness are as before."""
+        idx = _np_u64(indices).reshape(-1)
+        n = idx.size
+        need, _ = self.account_multiproof_shape(depth, idx)
+        val, present = np.zeros((n, 14), np.uint64), np.zeros(n, np.uint8)
+        nodes, root, n_nodes = np.zeros((need, 7), np.uint64), np.zeros(7, np.uint64), C.c_uint32(0)
+        check(self.lib.cstark_ledger_open_multi(self.ctx, led, C.c_uint64(at or 0), C.c_uint32(n), self._hptr(idx), self._hptr(val),
+                                                self._hptr(present, u8p), self._hptr(nodes) if need else None, C.c_uint32(need),
+                                                C.byref(n_nodes), self._hptr(root)))
+        assert n_nodes.value == need
+        return val, present.astype(bool), nodes, root
+
+    def account_check_multiproof(self, depth, indices, nodes, root, values=None, present=None, leaves=None):
+        """cstark_account_check_multiproof: folds one multiproof (any depth 1 .. 31) on the device, the leaf hashes and then one launch
+        per level -> (verdict, at, folded root [7], n_merges).  verdict: Backend.MULTI_* (0 = valid); INDEX (at = the first position
+        whose index is out of range or not above its predecessor) and NODE_COUNT (at = the needed count) launch nothing, and the folded
+        root is None for them (n_merges too for INDEX).  Exactly one of values [count][14] (optionally with present [count]) and
+        leaves [count][7] (digest mode).  nodes: [n_nodes][7], or None for none.  No ledger is needed and the resident witness is not
+        touched."""
+        idx = _np_u64(indices).reshape(-1)
+        n = idx.size
+        val = None if values is None else _np_u64(values).reshape(-1, 14)
+        lv = None if leaves is None else _np_u64(leaves).reshape(-1, 7)
+        if (val is None) == (lv is None):
+            raise ValueError("exactly one of values and leaves")
+        if (val if lv is None else lv).shape[0] != n:
+            raise ValueError("one value or leaf per index")
+        if present is not None and val is None:
+            raise ValueError("present without values")
+        pres = None if present is None else np.ascontiguousarray(present, np.uint8).reshape(-1)
+        if pres is not None and pres.size != n:
+            raise ValueError("one present flag per index")
+        nd = None if nodes is None else _np_u64(nodes).reshape(-1, 7)
+        if nd is not None and nd.shape[0] == 0:
+            nd = None
+        r = _np_u64(root).reshape(7)
+        verdict, at, n_merges = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        out = np.zeros(7, np.uint64)
+        check(self.lib.cstark_account_check_multiproof(self.ctx, C.c_uint32(depth), C.c_uint32(n), self._hptr(idx),
+                                                       None if val is None else self._hptr(val), None if pres is None else self._hptr(pres, u8p),
+                                                       None if lv is None else self._hptr(lv), None if nd is None else self._hptr(nd),
+                                                       C.c_uint32(0 if nd is None else nd.shape[0]), self._hptr(r), C.byref(verdict), C.byref(at),
+                                                       self._hptr(out), C.byref(n_merges)))
+        launched = verdict.value in (self.MULTI_VALID, self.MULTI_ROOT)
+        return verdict.value, at.value, out if launched else None, None if verdict.value == self.MULTI_INDEX else n_merges.value
+
     def ledger_apply(self, led, depth, s_indices, r_indices, deltas, sig_rx, sig_s, want_witness=True, check_signatures=False):
         """cstark_ledger_apply: -> (refused_at, reason, arrays).  Applied (refused_at == -1): the batch's witness is resident in this
         backend (build_trace / prove / air_prove follow without an upload) and arrays is the dict of its eleven fields (None with

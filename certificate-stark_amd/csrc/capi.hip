@@ -552,6 +552,7 @@ void cstark_ctx_destroy(cstark_ctx *c) {
     if (c->tail_buf) (void)hipFree(c->tail_buf);
     if (c->sig_buf) (void)hipFree(c->sig_buf);
     if (c->path_buf) (void)hipFree(c->path_buf);
+    if (c->multi_buf) (void)hipFree(c->multi_buf);
     for (cs::RawPeriodic &t : c->raw_periodic) (void)hipFree(t.tab);
     if (c->val_buf) (void)hipFree(c->val_buf);
     if (c->arena) cs::prove_arena_free(c->arena);

@@ -217,6 +217,8 @@ struct cstark_ctx {
     size_t sig_bytes = 0;
     void *path_buf = nullptr; // cstark_account_check_paths (ledger.hip): its inputs and outputs on the device, likewise
     size_t path_bytes = 0;
+    void *multi_buf = nullptr; // cstark_account_check_multiproof (ledger.hip): its digest slots, job lists and result words, likewise
+    size_t multi_bytes = 0;
     std::deque<cs::RawPeriodic> raw_periodic; // cstark_air_validate_trace: the raw periodic columns of (AIR, depth), uploaded once
     void *val_buf = nullptr; // ... and its scratch: per-cycle codes, summary, statement words, boundary list, one frame
     size_t val_bytes = 0;

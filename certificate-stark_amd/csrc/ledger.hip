@@ -16,12 +16,17 @@
 // are kept by not overwriting their slots, and nothing here launches for them but the gather of an opening.
 // cstark_ledger_audit tests that a state is a Merkle tree, every stored node against its STORED children, in one launch:
 //   k_ledger_audit    one list of jobs (left slot, right slot, expected slot) in the shape of k_ledger_merge; reads the pool only
+// Multi-openings (multiproof_plan.h): cstark_ledger_open_multi gathers the de-duplicated sibling set of many leaves (plan_open_multi,
+// k_ledger_gather, no hashing); cstark_account_check_multiproof, which needs no ledger, folds it level by level in a block of its own:
+//   k_multi_level     one level of a multiproof's fold in the shape of k_ledger_merge: the leaf hashes, a level's job list, or the
+//                     root's one job with the compare against the stated root
 #include <stdio.h>
 #include <string.h>
 #include <new>
 #include "../../include/cstark.h"
 #include "ctx.h"
 #include "ledger_plan.h"
+#include "multiproof_plan.h"
 #include "rescue_lane.cuh"
 
 namespace cs {
@@ -83,6 +88,59 @@ __global__ __launch_bounds__(64) void k_ledger_audit(const fp *__restrict__ pool
     if (active && e == 0 && (!hashing || (differ & (0x7Full << (14 * s))))) {
         atomicMin(&result[0], j);
         atomicAdd(&result[1], 1u);
+    }
+}
+
+// cstark_account_check_multiproof: one launch of the fold of a multiproof over its block of digest slots (multiproof_plan.h), in the shape
+// of k_ledger_merge: lanes 0..55 = (hash s, state element e), lanes 56..63 and the hashes of a partial last group only attend the
+// barriers; a workgroup without a job leaves ahead of its first barrier.  Three uses, told apart by uniform arguments:
+//   values != null    the leaf launch: job j hashes values[j][0..14) into slot j, or writes the all-zero digest where present[j] == 0
+//   jobs != null      a level: slot out = merge(slot left, slot right) for jobs [0, n_jobs)
+//   result != null    with jobs, the launch of level 0 (one job): the seven words meet the stated root in one wave ballot; result word 0 =
+//                     the verdict (as 64 bits), words 1..7 = the folded root, all by plain vector stores
+// Every slot is tested against block_slots before it is read or written.  A job that names a slot outside the block is inactive and sets
+// *fault (the host clears it in the upload; every writer stores the same 1); the last launch reads it -- the stream ordered the earlier
+// launches before it -- and a set fault makes the verdict ROOT.  No launch waits for another workgroup.
+static_assert((int)CSTARK_MULTI_VALID == (int)multi::VALID && (int)CSTARK_MULTI_INDEX == (int)multi::INDEX &&
+                  (int)CSTARK_MULTI_NODE_COUNT == (int)multi::NODE_COUNT && (int)CSTARK_MULTI_ROOT == (int)multi::ROOT,
+              "k_multi_level writes the values of cstark_multi_verdict");
+__global__ __launch_bounds__(64) void k_multi_level(fp *block, uint32_t block_slots, const ledger::Job *__restrict__ jobs, const fp *__restrict__ values,
+                                                    const uint8_t *__restrict__ present, uint32_t n_jobs, uint32_t *fault, const fp *__restrict__ stated,
+                                                    fp *result) {
+    __shared__ fp st[4][14];
+    if (4 * blockIdx.x >= n_jobs) return; // the whole workgroup
+    const int lane = threadIdx.x;
+    const bool is_state = lane < 56;
+    const int s = is_state ? lane / 14 : 0, e = is_state ? lane % 14 : 0;
+    const uint32_t j = 4 * blockIdx.x + s;
+    const bool active = is_state && j < n_jobs;
+    fp mrow[14];
+#pragma unroll
+    for (int k = 0; k < 14; k++) mrow[k] = c_mds[e * 14 + k];
+    uint32_t left = 0, right = 0, out = 0;
+    bool inside = false, hashing = false; // inside: active and every slot in the block; hashing: and there is something to hash
+    fp v = 0;
+    if (values) { // uniform
+        out = j;
+        inside = active && j < block_slots;
+        hashing = inside && (present ? present[j] != 0 : true);
+        if (hashing) v = values[(size_t)14 * j + e];
+    } else {
+        if (active) {
+            left = jobs[j].left; right = jobs[j].right; out = jobs[j].out;
+            inside = left < block_slots && right < block_slots && out < block_slots;
+        }
+        hashing = inside;
+        if (hashing) v = e < 7 ? block[(size_t)7 * left + e] : block[(size_t)7 * right + e - 7];
+    }
+    for (int cyc = 0; cyc < 7; cyc++) v = rescue_round_lane(v, st[s], mrow, e, cyc, hashing);
+    if (!hashing) v = 0; // an absent leaf
+    if (inside && e < 7) block[(size_t)7 * out + e] = v;
+    if (active && !inside && e == 0) *fault = 1;
+    if (result) { // uniform: one job, hash s = 0
+        const unsigned long long differ = __ballot(inside && e < 7 && v != stated[e]);
+        if (active && e < 7) result[1 + e] = v;
+        if (active && e == 0) result[0] = (!inside || (differ & 0x7Full) || *fault != 0) ? (fp)CSTARK_MULTI_ROOT : (fp)CSTARK_MULTI_VALID;
     }
 }
 
@@ -439,6 +497,87 @@ int check_paths_impl(cstark_ctx *c, uint32_t count, uint32_t depth, const uint64
     return CSTARK_OK;
 }
 
+// cstark_ledger_open_multi behind its argument checks (the indices have a shape of n_nodes proof nodes, nodes_out holds them): one upload
+// of the emit list, one gather into the staging area behind it, the nodes and the root copied out.  No hashing; stored nodes, index and
+// resident witness are unchanged (reserve_pool may move the pool)
+int open_multi_impl(cstark_ledger *L, size_t at, uint32_t count, const uint64_t *indices, uint32_t n_nodes, uint64_t *values_out, uint8_t *present_out,
+                    uint64_t *nodes_out, uint64_t *root_out) {
+    cstark_ctx *c = L->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    uint32_t scratch_base;
+    RC_TRY(reserve_pool(L, 0, cs::multi::open_multi_scratch_slots(n_nodes), &scratch_base));
+    Plan p;
+    if (!cs::multi::plan_open_multi(L->index, at, scratch_base, count, indices, p) || p.pool_slots > L->pool_slots || p.witness.size() != (size_t)n_nodes + 1)
+        return fail(CSTARK_ERR_INVALID_ARG, "ledger: the multi-opening exceeds the reserved pool");
+    uint64_t *block = L->pool + (size_t)7 * p.upload_slot, *stage = L->pool + (size_t)7 * p.stage_slot;
+    const uint32_t n = n_nodes + 1;
+    HIP_TRY(hipMemcpyAsync(block, p.upload.data(), p.upload.size() * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(cs::k_ledger_gather, dim3((uint32_t)(((size_t)7 * n + 255) / 256)), dim3(256), 0, c->stream, L->pool,
+                       (const Emit *)(block + p.witness_word), n, (uint32_t)L->pool_slots, stage, (size_t)7 * n);
+    HIP_TRY(hipGetLastError());
+    if (n_nodes) HIP_TRY(hipMemcpyAsync(nodes_out, stage, (size_t)56 * n_nodes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(root_out, stage + (size_t)7 * n_nodes, 56, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(cs::stream_wait(c->stream)); // the plan's host block is read by the upload
+    for (uint32_t i = 0; i < count; i++) {
+        const Value *v = L->index.value_at(at, indices[i]);
+        present_out[i] = v != nullptr;
+        if (v) memcpy(values_out + (size_t)14 * i, v->data(), 112);
+        else memset(values_out + (size_t)14 * i, 0, 112);
+    }
+    return CSTARK_OK;
+}
+
+// cstark_account_check_multiproof behind its argument checks and its host verdicts (the plan exists, n_nodes is the shape's).  One
+// device block of the context, grown when needed, in 64-bit words:
+//   digest slots [p.slots][7] | values [count][14] (when given) | upload: stated root [7], fault word, jobs [n_merges][2], result [8] | present [count] bytes
+// The upload block goes up in one copy; leaves (or values and present) and nodes are the caller's arrays and go up as they are.  Then the
+// leaf launch (with values) and one launch per level, ordered by the stream.  Nothing of the resident witness, path_buf, tail_buf or the
+// statement caches is read or written.
+int check_multi_impl(cstark_ctx *c, uint32_t depth, uint32_t count, const uint64_t *values, const uint8_t *present, const uint64_t *leaves,
+                     const uint64_t *nodes, const uint64_t *root, const cs::multi::CheckPlan &p, uint32_t *verdict, uint64_t *root_out) {
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = count, n_jobs = p.jobs.size();
+    const size_t slot_words = (size_t)7 * p.slots, value_words = values ? 14 * n : 0, upload_words = 8 + 2 * n_jobs;
+    const size_t bytes = (slot_words + value_words + upload_words + 8) * 8 + n;
+    if (c->multi_bytes < bytes) {
+        if (c->multi_buf) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->multi_buf)); c->multi_buf = nullptr; c->multi_bytes = 0; }
+        HIP_TRY(hipMalloc(&c->multi_buf, bytes));
+        c->multi_bytes = bytes;
+    }
+    uint64_t *d_slots = (uint64_t *)c->multi_buf, *d_values = d_slots + slot_words, *d_upload = d_values + value_words, *d_result = d_upload + upload_words;
+    uint8_t *d_present = (uint8_t *)(d_result + 8);
+    std::vector<uint64_t> upload(upload_words + 8, 0); // word 7: the fault word, cleared; the result words behind the jobs: no verdict yet
+    std::fill(upload.end() - 8, upload.end(), ~(uint64_t)0);
+    memcpy(upload.data(), root, 56);
+    memcpy(upload.data() + 8, p.jobs.data(), 16 * n_jobs);
+    if (values) HIP_TRY(hipMemcpyAsync(d_values, values, n * 112, hipMemcpyHostToDevice, c->stream));
+    else HIP_TRY(hipMemcpyAsync(d_slots, leaves, n * 56, hipMemcpyHostToDevice, c->stream));
+    if (present) HIP_TRY(hipMemcpyAsync(d_present, present, n, hipMemcpyHostToDevice, c->stream));
+    if (p.shape.n_nodes) HIP_TRY(hipMemcpyAsync(d_slots + 7 * n, nodes, (size_t)56 * p.shape.n_nodes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_upload, upload.data(), upload.size() * 8, hipMemcpyHostToDevice, c->stream));
+    uint32_t *d_fault = (uint32_t *)(d_upload + 7);
+    const Job *d_jobs = (const Job *)(d_upload + 8);
+    if (values) {
+        hipLaunchKernelGGL(cs::k_multi_level, dim3((count + 3) / 4), dim3(64), 0, c->stream, d_slots, p.slots, (const Job *)nullptr, d_values,
+                           present ? d_present : nullptr, count, d_fault, (const uint64_t *)nullptr, (uint64_t *)nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    for (uint32_t k = 0; k < depth; k++) {
+        const uint32_t m = p.launch[k + 1] - p.launch[k];
+        const bool last = k + 1 == depth; // level 0: one job
+        hipLaunchKernelGGL(cs::k_multi_level, dim3((m + 3) / 4), dim3(64), 0, c->stream, d_slots, p.slots, d_jobs + p.launch[k], (const uint64_t *)nullptr,
+                           (const uint8_t *)nullptr, m, d_fault, last ? d_upload : nullptr, last ? d_result : nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    uint64_t result[8];
+    HIP_TRY(hipMemcpyAsync(result, d_result, 64, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream)); // synchronous: the verdict is on the host, the caller's arrays and the upload block are free again
+    if (result[0] != CSTARK_MULTI_VALID && result[0] != CSTARK_MULTI_ROOT) return fail(CSTARK_ERR_HIP, "cstark_account_check_multiproof: the kernel wrote no verdict");
+    *verdict = (uint32_t)result[0];
+    if (root_out) memcpy(root_out, result + 1, 56);
+    return CSTARK_OK;
+}
+
 // the first word >= p of a [rows][per_row] array, named as `name[row][col]` (paths: `name[row][entry][word]`)
 bool reduced_words(const char *who, const char *name, const uint64_t *a, size_t rows, size_t per_row, bool entries) {
     for (size_t i = 0; i < rows * per_row; i++)
@@ -450,6 +589,13 @@ bool reduced_words(const char *who, const char *name, const uint64_t *a, size_t 
             return false;
         }
     return true;
+}
+
+// the misuse of the multi-opening calls that take their indices on trust: indices[i] has no place in a strictly ascending list below 2^depth
+int unsorted(const char *who, uint32_t i) {
+    char where[128];
+    snprintf(where, sizeof where, "%s: indices[%u]", who, i);
+    return fail(CSTARK_ERR_INVALID_ARG, "%s is out of range or not above its predecessor (indices are strictly ascending)", where);
 }
 
 // a HIP failure inside a ledger call leaves the pool in an unknown state: every later call fails
@@ -629,6 +775,74 @@ int cstark_account_check_paths(cstark_ctx *c, uint32_t count, uint32_t depth, co
     if (!reduced_words(who, "paths", paths, count, (size_t)7 * (depth + 1), true)) return CSTARK_ERR_INVALID_ARG;
     if (!reduced_words(who, "roots", roots, n_roots, 7, false)) return CSTARK_ERR_INVALID_ARG;
     return check_paths_impl(c, count, depth, indices, values, present, paths, roots, n_roots, verdicts, roots_out);
+}
+
+int cstark_account_multiproof_shape(uint32_t depth, uint32_t count, const uint64_t *indices, uint32_t *n_nodes, uint32_t *n_merges) {
+    const char *who = "cstark_account_multiproof_shape";
+    if (!indices || !n_nodes || !n_merges) return fail(CSTARK_ERR_INVALID_ARG, "%s: null argument", who);
+    if (depth == 0 || depth > MAX_DEPTH) return fail(CSTARK_ERR_INVALID_ARG, "%s: depth must be 1 .. 31", who);
+    if (count == 0 || count > cs::multi::MAX_COUNT) return fail(CSTARK_ERR_INVALID_ARG, "%s: count must be 1 .. 2^20", who);
+    const cs::multi::Shape s = cs::multi::multiproof_shape(depth, count, indices);
+    if (!s.ok) return unsorted(who, s.bad_at);
+    *n_nodes = s.n_nodes;
+    *n_merges = s.n_merges;
+    return CSTARK_OK;
+}
+
+int cstark_ledger_open_multi(cstark_ctx *c, cstark_ledger *L, uint64_t id, uint32_t count, const uint64_t *indices, uint64_t *values_out, uint8_t *present_out,
+                             uint64_t *nodes_out, uint32_t nodes_capacity, uint32_t *n_nodes, uint64_t root_out[7]) {
+    const char *who = "cstark_ledger_open_multi";
+    RC_TRY(usable(c, L, who));
+    if (count == 0 || count > cs::multi::MAX_COUNT || !indices || !values_out || !present_out || (!nodes_out && nodes_capacity) || !n_nodes || !root_out)
+        return fail(CSTARK_ERR_INVALID_ARG, "%s: bad argument", who);
+    const ptrdiff_t at = checkpoint_position(L, id, who);
+    if (at < 0) return CSTARK_ERR_INVALID_ARG;
+    const cs::multi::Shape s = cs::multi::multiproof_shape(L->index.depth, count, indices);
+    if (!s.ok) return unsorted(who, s.bad_at);
+    if (nodes_capacity < s.n_nodes) {
+        *n_nodes = s.n_nodes;
+        char need[96];
+        snprintf(need, sizeof need, "%s: nodes_capacity %u is below the %u proof nodes of this opening", who, nodes_capacity, s.n_nodes);
+        return fail(CSTARK_ERR_INVALID_ARG, "%s", need);
+    }
+    RC_TRY(guard(L, open_multi_impl(L, (size_t)at, count, indices, s.n_nodes, values_out, present_out, nodes_out, root_out)));
+    *n_nodes = s.n_nodes;
+    return CSTARK_OK;
+}
+
+int cstark_account_check_multiproof(cstark_ctx *c, uint32_t depth, uint32_t count, const uint64_t *indices, const uint64_t *values, const uint8_t *present,
+                                    const uint64_t *leaves, const uint64_t *nodes, uint32_t n_nodes, const uint64_t root[7], uint32_t *verdict, uint32_t *at,
+                                    uint64_t *root_out, uint32_t *n_merges) {
+    const char *who = "cstark_account_check_multiproof";
+    if (!c || !indices || !root || !verdict || !at) return fail(CSTARK_ERR_INVALID_ARG, "%s: null argument", who);
+    if (depth == 0 || depth > MAX_DEPTH) return fail(CSTARK_ERR_INVALID_ARG, "%s: depth must be 1 .. 31", who);
+    if (count == 0 || count > cs::multi::MAX_COUNT) return fail(CSTARK_ERR_INVALID_ARG, "%s: count must be 1 .. 2^20", who);
+    if (!values == !leaves) return fail(CSTARK_ERR_INVALID_ARG, "%s: exactly one of values and leaves is given", who);
+    if (present && !values) return fail(CSTARK_ERR_INVALID_ARG, "%s: present without values", who);
+    if (!nodes != !n_nodes) return fail(CSTARK_ERR_INVALID_ARG, "%s: nodes is null iff n_nodes is 0", who);
+    if (n_nodes > cs::multi::MAX_COUNT * MAX_DEPTH) return fail(CSTARK_ERR_INVALID_ARG, "%s: n_nodes is beyond any multiproof", who);
+    if (values && !reduced_words(who, "values", values, count, 14, false)) return CSTARK_ERR_INVALID_ARG;
+    if (leaves && !reduced_words(who, "leaves", leaves, count, 7, false)) return CSTARK_ERR_INVALID_ARG;
+    if (nodes && !reduced_words(who, "nodes", nodes, n_nodes, 7, false)) return CSTARK_ERR_INVALID_ARG;
+    if (!reduced_words(who, "root", root, 1, 7, false)) return CSTARK_ERR_INVALID_ARG;
+    // the shape of an untrusted proof is data: these two are verdicts, and nothing is launched for them
+    cs::multi::CheckPlan p;
+    if (!cs::multi::plan_check(depth, count, indices, p)) {
+        *verdict = CSTARK_MULTI_INDEX;
+        *at = p.shape.bad_at;
+        return CSTARK_OK;
+    }
+    if (n_merges) *n_merges = p.shape.n_merges;
+    if (n_nodes != p.shape.n_nodes) {
+        *verdict = CSTARK_MULTI_NODE_COUNT;
+        *at = p.shape.n_nodes;
+        return CSTARK_OK;
+    }
+    uint32_t v = 0;
+    RC_TRY(check_multi_impl(c, depth, count, values, present, leaves, nodes, root, p, &v, root_out));
+    *verdict = v;
+    *at = 0;
+    return CSTARK_OK;
 }
 
 int cstark_ledger_root(cstark_ctx *c, cstark_ledger *L, uint64_t root[7]) {

@@ -10,6 +10,8 @@ Names and argument meaning follow the reference so tests read like its own:
         interpolate -> LDE -> Blake3 row hashes -> Merkle tree -> constraint evaluations
 All device work goes through the C ABI (include/cstark.h); there is no CPU path here.
 """
+import collections
+
 import numpy as np
 
 _P = 2**62 + 2**56 + 2**55 + 1  # the prime of f63::BaseElement
@@ -131,6 +133,35 @@ class AccountOpening:
         return check_account_paths(self.indices, self.paths, self.root, self.values, self.present, backend=backend or self._backend)
 
 
+MultiproofCheck = collections.namedtuple("MultiproofCheck", "verdict at root n_merges")
+
+
+def check_account_multiproof(depth, indices, nodes, root, values=None, present=None, leaves=None, backend=None):
+    """One Merkle multiproof from anywhere (an AccountMultiOpening, a file, a peer) against the root it states, on the GPU: ->
+    MultiproofCheck(verdict, at, root, n_merges); verdict 0 = valid, Backend.MULTI_*; see Backend.account_check_multiproof.  indices are
+    strictly ascending as given: an untrusted proof's order is data, and a wrong one is the verdict INDEX.  No ledger is needed."""
+    return MultiproofCheck(*(backend or Backend()).account_check_multiproof(depth, indices, nodes, root, values=values, present=present, leaves=leaves))
+
+
+class AccountMultiOpening:
+    """What Ledger.open_multi returns: the accounts at the ascending, distinct `indices` (values [count][14], present [count]) and ONE
+    multiproof for all of them under `root`: nodes [n_nodes][7], the siblings no opened leaf accounts for, level `depth` first and
+    ascending within a level (include/cstark.h).  inverse[k] is the position in `indices` of the k-th index the caller asked for;
+    nbytes is what travels: indices, values, presence flags, nodes and root."""
+
+    def __init__(self, depth, indices, values, present, nodes, root, inverse, backend=None):
+        self.depth, self.indices, self.values, self.present, self.nodes, self.root, self.inverse = depth, indices, values, present, nodes, root, inverse
+        self._backend = backend
+
+    @property
+    def nbytes(self):
+        return self.indices.nbytes + self.values.nbytes + self.present.size + self.nodes.nbytes + self.root.nbytes
+
+    def check(self, backend=None):
+        """-> MultiproofCheck: verdict 0 for an honest opening, .root the fold, .n_merges the merges it took"""
+        return check_account_multiproof(self.depth, self.indices, self.nodes, self.root, self.values, self.present, backend=backend or self._backend)
+
+
 class Ledger:
     """The account tree an operator holds, resident on the GPU (cstark_ledger_*): set_accounts, then apply(transfers) per batch -- the
     counterpart of the sequential loop of TransactionMetadata::build_random (src/lib.rs:341-422) on real accounts and transfers.
@@ -173,6 +204,16 @@ class Ledger:
         checkpoint, under the root a proof of that moment binds (an account created since is absent)."""
         idx = np.ascontiguousarray(indices, np.uint64).reshape(-1)
         return AccountOpening(idx, *self.backend.ledger_open_accounts(self._led, self.depth, idx, at=at), backend=self.backend)
+
+    def open_multi(self, indices, at=None):
+        """-> AccountMultiOpening: the given leaves (in any order, repeats allowed: they are sorted and de-duplicated here, and
+        .inverse maps the request back) with ONE multiproof for all of them instead of a path each: the siblings that paths under one
+        root share travel once, and those an opened leaf accounts for not at all.  Absent accounts are proven absent.  Read-only: one
+        gather on the GPU, no hashing.  at=checkpoint: under the root of that checkpoint, as open()."""
+        asked = np.ascontiguousarray(indices, np.uint64).reshape(-1)
+        idx, inverse = np.unique(asked, return_inverse=True)
+        return AccountMultiOpening(self.depth, idx, *self.backend.ledger_open_multi(self._led, self.depth, idx, at=at), inverse=inverse.reshape(-1),
+                                   backend=self.backend)
 
     def checkpoint(self):
         """-> an id that names the ledger's state as it is now (an integer >= 1, never reused).  No device work; old states are kept by

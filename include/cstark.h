@@ -596,6 +596,55 @@ typedef struct cstark_ledger_audit_report {
 } cstark_ledger_audit_report;
 int cstark_ledger_audit(cstark_ctx *ctx, cstark_ledger *ledger, uint64_t id, cstark_ledger_audit_report *report);
 
+/* ---- multi-openings: one Merkle multiproof for many accounts -------------------------------------------------------
+ * The multiproof of a tree of depth d and a STRICTLY ASCENDING list of leaf indices I:
+ *     K_d = I;  for each level l = d .. 1, every x of K_l in ascending order contributes the proof node (l, x ^ 1) iff x ^ 1 is not in
+ *     K_l;  K_{l-1} is the set of parents {x >> 1} of K_l.
+ * nodes [n_nodes][7] holds those digests in that order: level d (the leaves' level) first, ascending x within a level.  The fold takes
+ * n_merges = sum over l < d of |K_l| merges (the `count` leaf hashes are not among them).  The leaf of an opened index is
+ * merge(value[0..7], value[7..14]) when the account is present and the all-zero digest when it is absent, and an untouched sibling is the
+ * empty-subtree digest of its level, exactly as in cstark_ledger_open_accounts: absence is provable.  With all 2^d leaves opened,
+ * n_nodes = 0.
+ * Host only: n_nodes and n_merges of (depth, indices).  depth outside 1 .. 31, count outside 1 .. 2^20, null pointers, or indices that
+ * are not strictly ascending below 2^depth are CSTARK_ERR_INVALID_ARG with the outputs untouched (cstark_last_error names the first
+ * offending position). */
+int cstark_account_multiproof_shape(uint32_t depth, uint32_t count, const uint64_t *indices, uint32_t *n_nodes, uint32_t *n_merges);
+/* The multiproof of `count` (1 .. 2^20) leaves of the state at `id` (0: the current state; otherwise a live checkpoint, as in
+ * cstark_ledger_open_accounts_at).  values_out [count][14] and present_out [count] are what cstark_ledger_get_accounts gives (of that
+ * state); nodes_out receives the n_nodes proof nodes, *n_nodes their number, root_out the root they fold to.  Indices must be strictly
+ * ascending below 2^depth: if not, the call is CSTARK_ERR_INVALID_ARG with the outputs untouched, as for null pointers (nodes_out may be
+ * null only with nodes_capacity == 0), a bad count, an unknown id or a ledger of another context.  A nodes_capacity below the need is
+ * CSTARK_ERR_INVALID_ARG with *n_nodes set to the need and nothing else written (cstark_account_multiproof_shape states the need
+ * beforehand).  n_nodes == 0 is legal.  Synchronous and read-only: one upload of a slot list, one gather on the device, no hashing;
+ * root, stored nodes, accounts and the resident witness are unchanged. */
+int cstark_ledger_open_multi(cstark_ctx *ctx, cstark_ledger *ledger, uint64_t id, uint32_t count, const uint64_t *indices,
+                             uint64_t *values_out /* [count][14] */, uint8_t *present_out /* [count] */,
+                             uint64_t *nodes_out /* [nodes_capacity][7] */, uint32_t nodes_capacity, uint32_t *n_nodes, uint64_t root_out[7]);
+/* The verifier's side: needs no ledger and takes any depth 1 .. 31.  The verdict is the first that applies. */
+typedef enum cstark_multi_verdict {
+    CSTARK_MULTI_VALID = 0,
+    CSTARK_MULTI_INDEX = 1,      /* *at = the first position whose index is >= 2^depth or not above its predecessor */
+    CSTARK_MULTI_NODE_COUNT = 2, /* n_nodes differs from the shape's count; *at = the needed count */
+    CSTARK_MULTI_ROOT = 3        /* the fold differs from `root`; root_out holds the fold */
+} cstark_multi_verdict;
+/* Folds one multiproof on the device: the leaf hashes in one launch, then one launch per level.  Exactly one of `values` [count][14] and
+ * `leaves` [count][7] is given: with values the leaf of position i is merge(values[i][0..7], values[i][7..14]) where present[i] != 0 (a
+ * NULL present: all present) and the all-zero digest where present[i] == 0; with leaves (digest mode, present must be NULL) the stated
+ * digests are the leaves.  nodes [n_nodes][7] may be NULL iff n_nodes == 0.  The shape of an untrusted proof is data, so INDEX and
+ * NODE_COUNT are verdicts, not misuse: the status is CSTARK_OK, nothing is launched and root_out is untouched.  *at is 0 for VALID and
+ * ROOT.  root_out (optional) receives the fold for VALID and ROOT; n_merges (optional) receives the shape's merge count unless the
+ * verdict is INDEX.
+ * Null ctx, indices, root, verdict or at, depth outside 1 .. 31, count outside 1 .. 2^20, both or neither of values and leaves, present
+ * without values, nodes null with n_nodes != 0 or the reverse, or a word >= p in values, leaves, nodes or root is CSTARK_ERR_INVALID_ARG
+ * before anything is launched and with the outputs untouched; cstark_last_error names the first such word, in that order of the arrays.
+ * Synchronous, on the context's stream, in a device block of its own that the context keeps and frees: the resident witness and the
+ * blocks of the other checks are neither read nor written, so a proof after a check is the proof without it. */
+int cstark_account_check_multiproof(cstark_ctx *ctx, uint32_t depth, uint32_t count, const uint64_t *indices,
+                                    const uint64_t *values /* [count][14] or NULL */, const uint8_t *present /* [count] or NULL */,
+                                    const uint64_t *leaves /* [count][7] or NULL */, const uint64_t *nodes /* [n_nodes][7] */, uint32_t n_nodes,
+                                    const uint64_t root[7], uint32_t *verdict /* cstark_multi_verdict */, uint32_t *at,
+                                    uint64_t *root_out /* optional [7] */, uint32_t *n_merges /* optional */);
+
 /* ---- verification (TransactionExample::verify, src/lib.rs:144-150: winterfell::verify over this library's own proof layout) -------
  * The call's status (cstark_status) is kept apart from the proof's verdict.  A verdict names the FIRST check that fails, in this
  * order: layout (MALFORMED, then UNSUPPORTED) | OPTIONS_MISMATCH | OOD | REMAINDER_COMMITMENT | POW | per query q = 0..nq-1:

@@ -12,6 +12,7 @@
 // Failures are exceptions (cstark::Error) where the reference returns Err / panics.  Header-only; link libcstark_hip.so.
 #ifndef CSTARK_HPP
 #define CSTARK_HPP
+#include <algorithm>
 #include <array>
 #include <condition_variable>
 #include <cstdint>
@@ -214,6 +215,38 @@ inline std::vector<uint8_t> check_account_paths(Context &ctx, unsigned depth, co
                                      paths.data(), roots[0].data(), (uint32_t)roots.size(), verdicts.data(), roots_out ? roots_out->data() : nullptr));
     return verdicts;
 }
+// What Ledger::open_multi returns: the accounts at the strictly ascending `indices` and ONE multiproof for all of them under `root`:
+// nodes [n_nodes][7] words, the siblings no opened leaf accounts for, level `depth` first and ascending within a level (cstark.h)
+struct AccountMultiOpening {
+    unsigned depth = 0;
+    std::vector<uint64_t> indices;
+    std::vector<std::array<BaseElement, 14>> values;
+    std::vector<uint8_t> present;
+    std::vector<BaseElement> nodes;
+    Hash root{};
+};
+// cstark_account_check_multiproof
+struct MultiproofCheck {
+    uint32_t verdict = 0; // cstark_multi_verdict (CSTARK_MULTI_VALID = 0)
+    uint32_t at = 0;      // INDEX: the offending position; NODE_COUNT: the needed number of nodes
+    uint32_t n_merges = 0;
+    Hash root{};          // the fold, for VALID and ROOT
+};
+// One multiproof against the root it states.  Exactly one of values (with present, optional) and leaves ([count][7] words, digest mode);
+// nodes [n_nodes][7] words.  A wrong order of the indices or a wrong number of nodes is a verdict, not an Error.  No ledger is needed and
+// a resident witness is not touched.
+inline MultiproofCheck check_account_multiproof(Context &ctx, unsigned depth, const std::vector<uint64_t> &indices, const std::vector<BaseElement> &nodes,
+                                                const Hash &root, const std::vector<std::array<BaseElement, 14>> *values = nullptr,
+                                                const std::vector<uint8_t> *present = nullptr, const std::vector<BaseElement> *leaves = nullptr) {
+    const size_t n = indices.size();
+    if (n == 0 || nodes.size() % 7 || (values && values->size() != n) || (present && present->size() != n) || (leaves && leaves->size() != 7 * n))
+        throw Error(CSTARK_ERR_INVALID_ARG, "multiproof vectors are not of matching length");
+    MultiproofCheck r;
+    check(cstark_account_check_multiproof(ctx.raw(), depth, (uint32_t)n, indices.data(), values ? (*values)[0].data() : nullptr,
+                                          present ? present->data() : nullptr, leaves ? leaves->data() : nullptr, nodes.empty() ? nullptr : nodes.data(),
+                                          (uint32_t)(nodes.size() / 7), root.data(), &r.verdict, &r.at, r.root.data(), &r.n_merges));
+    return r;
+}
 // The account tree an operator holds, resident on the GPU (cstark_ledger_*): what replaces the sequential loop of
 // TransactionMetadata::build_random (src/lib.rs:341-422) on real accounts.  apply() leaves the batch's witness resident in the context:
 // TransactionProver::prove_resident follows without an upload.
@@ -282,6 +315,25 @@ class Ledger {
         o.paths.resize(indices.size() * (depth_ + 1) * 7);
         check(cstark_ledger_open_accounts_at(ctx_.raw(), led_, at, (uint32_t)indices.size(), indices.data(), o.values[0].data(), o.present.data(),
                                              o.paths.data(), o.root.data()));
+        return o;
+    }
+    // the given leaves (any order, repeats allowed: sorted and de-duplicated here) with ONE multiproof for all of them
+    // (cstark_ledger_open_multi), under the current root or the root of checkpoint `at`.  Read-only: one gather, no hashing.
+    // check_account_multiproof(ctx, o.depth, o.indices, o.nodes, o.root, &o.values, &o.present).verdict is CSTARK_MULTI_VALID
+    AccountMultiOpening open_multi(std::vector<uint64_t> indices, uint64_t at = 0) const {
+        if (indices.empty()) throw Error(CSTARK_ERR_INVALID_ARG, "no account index to open");
+        std::sort(indices.begin(), indices.end());
+        indices.erase(std::unique(indices.begin(), indices.end()), indices.end());
+        AccountMultiOpening o;
+        o.depth = depth_;
+        uint32_t n_nodes = 0, n_merges = 0;
+        check(cstark_account_multiproof_shape(depth_, (uint32_t)indices.size(), indices.data(), &n_nodes, &n_merges));
+        o.values.resize(indices.size());
+        o.present.resize(indices.size());
+        o.nodes.resize((size_t)7 * n_nodes);
+        check(cstark_ledger_open_multi(ctx_.raw(), led_, at, (uint32_t)indices.size(), indices.data(), o.values[0].data(), o.present.data(),
+                                       n_nodes ? o.nodes.data() : nullptr, n_nodes, &n_nodes, o.root.data()));
+        o.indices = std::move(indices);
         return o;
     }
     // every stored node of the state at `at` (0: the current one) against its stored children, on the GPU in one launch.  Read-only; an
