@@ -177,8 +177,12 @@ def test_unmerged_stage_for_several_coefficient_sets(oracle, stage_cases, tmp_pa
 # ---- 3. both paths write the same proof -----------------------------------------------------------------------------------------
 
 def test_merged_and_unmerged_paths_give_the_same_proof_bytes():
-    """CSTARK_SPLIT_MERGE is read once per process, hence the child process for the unmerged path."""
+    """CSTARK_SPLIT_MERGE is read once per process, hence the child process for the unmerged path.  Both digests are also the CPU
+    prover's for the same witness, so that a disagreement between the two says which side wrote the wrong proof."""
+    from oracle import oracle as O
+    from oracle import prover as OP
     from test_gpu_prove import example
+    cpu = hashlib.sha256(OP.prove(O.TxWitness.generate(1, 3, seed=505), (42, 8, 0, 0, 0, 4, 256))).hexdigest()   # example()'s witness and options
     code = ("import sys, hashlib; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
             "from test_gpu_prove import example\n"
             "print(hashlib.sha256(example(1, 3, seed=505).prove()).hexdigest())\n") % (ROOT, os.path.join(ROOT, "tests"))
@@ -186,4 +190,9 @@ def test_merged_and_unmerged_paths_give_the_same_proof_bytes():
     want = hashlib.sha256(example(1, 3, seed=505).prove()).hexdigest()
     got = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, CSTARK_SPLIT_MERGE="0"), capture_output=True, text=True, timeout=600)
     assert got.returncode == 0, got.stderr[-2000:]
-    assert got.stdout.strip().splitlines()[-1] == want
+    unmerged = got.stdout.strip().splitlines()[-1]
+    print("merged %s\nunmerged %s\ncpu %s" % (want, unmerged, cpu))
+    assert unmerged == want, "the two paths differ: the merged proof %s the CPU prover's, the unmerged one %s it" % (
+        "is" if want == cpu else "is NOT", "is" if unmerged == cpu else "is NOT")
+    assert want == cpu, "the merged path (this process) wrote another proof than the CPU prover"
+    assert unmerged == cpu, "the unmerged path (the child process) wrote another proof than the CPU prover"
