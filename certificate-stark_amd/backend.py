@@ -152,6 +152,41 @@ class Backend:
         check(self.lib.cstark_ledger_create(self.ctx, C.c_uint32(depth), C.byref(led)))
         return led
 
+    def ledger_create_partial(self, depth, indices, values, present, nodes, root):
+        """cstark_ledger_create_partial: a ledger built from a multi-opening under `root` -> (handle or None, verdict, at); verdict:
+        Backend.MULTI_* (0 = valid, the only one with a handle).  indices strictly ascending, values [count][14], present [count] or
+        None (all present), nodes [n_nodes][7] or None.  The resident witness is not touched."""
+        idx = _np_u64(indices).reshape(-1)
+        val = _np_u64(values).reshape(-1, 14)
+        if val.shape[0] != idx.size:
+            raise ValueError("one 14-element value per index")
+        pres = None if present is None else np.ascontiguousarray(present, np.uint8).reshape(-1)
+        if pres is not None and pres.size != idx.size:
+            raise ValueError("one present flag per index")
+        nd = None if nodes is None else _np_u64(nodes).reshape(-1, 7)
+        if nd is not None and nd.shape[0] == 0:
+            nd = None
+        r = _np_u64(root).reshape(7)
+        led, verdict, at = C.c_void_p(), C.c_uint32(0), C.c_uint32(0)
+        check(self.lib.cstark_ledger_create_partial(self.ctx, C.c_uint32(depth), C.c_uint32(idx.size), self._hptr(idx), self._hptr(val),
+                                                    None if pres is None else self._hptr(pres, u8p), None if nd is None else self._hptr(nd),
+                                                    C.c_uint32(0 if nd is None else nd.shape[0]), self._hptr(r), C.byref(led), C.byref(verdict),
+                                                    C.byref(at)))
+        return (led if led.value else None), verdict.value, at.value
+
+    def ledger_known(self, led, indices):
+        """cstark_ledger_known -> bool [count]: which leaves the ledger knows (a full ledger: every index below 2^depth)"""
+        idx = _np_u64(indices).reshape(-1)
+        out = np.zeros(idx.size, np.uint8)
+        check(self.lib.cstark_ledger_known(self.ctx, led, C.c_uint32(idx.size), self._hptr(idx), self._hptr(out, u8p)))
+        return out.astype(bool)
+
+    def ledger_partial_info(self, led):
+        """cstark_ledger_partial_info -> (is_partial, n_known, n_opaque)"""
+        partial, n_known, n_opaque = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        check(self.lib.cstark_ledger_partial_info(self.ctx, led, C.byref(partial), C.byref(n_known), C.byref(n_opaque)))
+        return bool(partial.value), n_known.value, n_opaque.value
+
     def ledger_destroy(self, led):
         self.lib.cstark_ledger_destroy(led)
 
@@ -304,6 +339,43 @@ class Backend:
                                                        self._hptr(out), C.byref(n_merges)))
         launched = verdict.value in (self.MULTI_VALID, self.MULTI_ROOT)
         return verdict.value, at.value, out if launched else None, None if verdict.value == self.MULTI_INDEX else n_merges.value
+
+    UPDATE_VALID, UPDATE_INDEX, UPDATE_NODE_COUNT, UPDATE_OLD_ROOT, UPDATE_NEW_ROOT = 0, 1, 2, 3, 4   # cstark_update_verdict
+
+    def account_check_update(self, depth, indices, old_values, new_values, nodes, old_root, new_root=None, old_present=None, new_present=None):
+        """cstark_account_check_update: folds one multi-opening over the old AND the new state of its accounts in one pass on the
+        device, with the launches of one account_check_multiproof -> (verdict, at, new root [7], n_changed).  verdict: Backend.UPDATE_*
+        (0 = valid); INDEX and NODE_COUNT as in account_check_multiproof (nothing launched, n_changed None); OLD_ROOT: the old values do
+        not fold to old_root; NEW_ROOT: they do, and the new values fold to something other than new_root.  The new root is the fold of
+        the new state for VALID and NEW_ROOT and None otherwise.  new_root=None: compute only.  old_present / new_present: [count],
+        None for all present.  nodes: [n_nodes][7], or None for none.  No ledger is needed and the resident witness is not touched."""
+        idx = _np_u64(indices).reshape(-1)
+        n = idx.size
+        old, new = _np_u64(old_values).reshape(-1, 14), _np_u64(new_values).reshape(-1, 14)
+        if old.shape[0] != n or new.shape[0] != n:
+            raise ValueError("one old and one new value per index")
+        flags = []
+        for present in (old_present, new_present):
+            pres = None if present is None else np.ascontiguousarray(present, np.uint8).reshape(-1)
+            if pres is not None and pres.size != n:
+                raise ValueError("one present flag per index")
+            flags.append(pres)
+        nd = None if nodes is None else _np_u64(nodes).reshape(-1, 7)
+        if nd is not None and nd.shape[0] == 0:
+            nd = None
+        r_old = _np_u64(old_root).reshape(7)
+        r_new = None if new_root is None else _np_u64(new_root).reshape(7)
+        verdict, at, n_changed = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        out = np.zeros(7, np.uint64)
+        check(self.lib.cstark_account_check_update(self.ctx, C.c_uint32(depth), C.c_uint32(n), self._hptr(idx), self._hptr(old),
+                                                   None if flags[0] is None else self._hptr(flags[0], u8p), self._hptr(new),
+                                                   None if flags[1] is None else self._hptr(flags[1], u8p), None if nd is None else self._hptr(nd),
+                                                   C.c_uint32(0 if nd is None else nd.shape[0]), self._hptr(r_old),
+                                                   None if r_new is None else self._hptr(r_new), C.byref(verdict), C.byref(at), self._hptr(out),
+                                                   C.byref(n_changed)))
+        launched = verdict.value not in (self.UPDATE_INDEX, self.UPDATE_NODE_COUNT)
+        folded = verdict.value in (self.UPDATE_VALID, self.UPDATE_NEW_ROOT)
+        return verdict.value, at.value, out if folded else None, n_changed.value if launched else None
 
     def ledger_apply(self, led, depth, s_indices, r_indices, deltas, sig_rx, sig_s, want_witness=True, check_signatures=False):
         """cstark_ledger_apply: -> (refused_at, reason, arrays).  Applied (refused_at == -1): the batch's witness is resident in this

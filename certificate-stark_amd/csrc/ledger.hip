@@ -20,6 +20,13 @@
 // k_ledger_gather, no hashing); cstark_account_check_multiproof, which needs no ledger, folds it level by level in a block of its own:
 //   k_multi_level     one level of a multiproof's fold in the shape of k_ledger_merge: the leaf hashes, a level's job list, or the
 //                     root's one job with the compare against the stated root
+// cstark_account_check_update, which needs no ledger either, folds ONE multiproof over the old and the new state of its accounts:
+//   k_multi_update    k_multi_level with two sides per job: the launches of one check for both folds, the new side hashing only above
+//                     a changed leaf and reading the proof nodes where the old side reads them
+// A partial ledger (cstark_ledger_create_partial, multiproof_plan.h: plan_seed) is a ledger built from a multi-opening: one upload puts
+// the proof nodes into their final pool slots, k_ledger_merge hashes the leaves and folds the levels straight into the stored nodes, and
+// the root is compared on the host before the index is committed.  It knows the opened accounts only (Index::is_known): apply refuses
+// a transfer with an unknown account, the other calls refuse unknown indices (all_known), the audit skips the opaque proof nodes.
 #include <stdio.h>
 #include <string.h>
 #include <new>
@@ -141,6 +148,88 @@ __global__ __launch_bounds__(64) void k_multi_level(fp *block, uint32_t block_sl
         const unsigned long long differ = __ballot(inside && e < 7 && v != stated[e]);
         if (active && e < 7) result[1 + e] = v;
         if (active && e == 0) result[0] = (!inside || (differ & 0x7Full) || *fault != 0) ? (fp)CSTARK_MULTI_ROOT : (fp)CSTARK_MULTI_VALID;
+    }
+}
+
+// cstark_account_check_update: one launch of the fold of ONE multiproof over two states of its leaves (multiproof_plan.h, plan_update), in
+// the lane shape of k_multi_level.  A job has two sides and a wave carries two jobs: hash s = 2 * (job within the wave) + side, side 0 the
+// old state and side 1 the new one, which sit in neighbouring groups of 14 lanes.  The new side hashes only where the job's flag says a
+// changed leaf lies below; elsewhere it takes the old side's digest from the lanes 14 below by a cross-lane move that every lane executes.
+// The new side's slots are the old side's through multi::update_new_slot: a proof node is read from the one slot it has.  The uses:
+//   old_values != null    the leaf launch: job j hashes old_values[j] into slot j and, where state[j] says changed, new_values[j] into the
+//                         new leaf slot; an absent side writes the all-zero digest
+//   jobs != null          a level: out = merge(left, right) on either side, for jobs [0, n_jobs)
+//   result != null        with jobs, the launch of level 0 (one job): both roots meet the stated ones (stated[0..7) old, stated[8..15) new,
+//                         the latter only with have_new) in one wave ballot; result word 0 = the verdict (as 64 bits), words 1..7 = the
+//                         new side's fold, all by plain vector stores
+// Every slot is tested against the old side's slots before it is mapped and against block_slots before it is read or written; a job that
+// names one outside is inactive on that side and sets *fault, as in k_multi_level, and a set fault makes the verdict OLD_ROOT.  No launch
+// waits for another workgroup, and a workgroup without a job leaves ahead of its first barrier.
+static_assert((int)CSTARK_UPDATE_VALID == (int)multi::UPDATE_VALID && (int)CSTARK_UPDATE_INDEX == (int)multi::UPDATE_INDEX &&
+                  (int)CSTARK_UPDATE_NODE_COUNT == (int)multi::UPDATE_NODE_COUNT && (int)CSTARK_UPDATE_OLD_ROOT == (int)multi::UPDATE_OLD_ROOT &&
+                  (int)CSTARK_UPDATE_NEW_ROOT == (int)multi::UPDATE_NEW_ROOT,
+              "k_multi_update writes the values of cstark_update_verdict");
+__global__ __launch_bounds__(64) void k_multi_update(fp *block, uint32_t block_slots, uint32_t count, uint32_t n_nodes, uint32_t old_slots,
+                                                     const ledger::Job *__restrict__ jobs, const fp *__restrict__ old_values,
+                                                     const fp *__restrict__ new_values, const uint8_t *__restrict__ state, uint32_t n_jobs, uint32_t *fault,
+                                                     const fp *__restrict__ stated, uint32_t have_new, fp *result) {
+    __shared__ fp st[4][14];
+    if (2 * blockIdx.x >= n_jobs) return; // the whole workgroup
+    const int lane = threadIdx.x;
+    const bool is_state = lane < 56;
+    const int s = is_state ? lane / 14 : 0, e = is_state ? lane % 14 : 0;
+    const int side = s & 1;
+    const uint32_t j = 2 * blockIdx.x + (s >> 1);
+    const bool active = is_state && j < n_jobs;
+    fp mrow[14];
+#pragma unroll
+    for (int k = 0; k < 14; k++) mrow[k] = c_mds[e * 14 + k];
+    uint32_t left = 0, right = 0, out = 0;
+    bool inside = false, hashing = false, copies = false; // inside: active and every slot in the block; copies: the new digest is the old one
+    fp v = 0;
+    if (old_values) { // uniform
+        inside = active && j < count && j < old_slots;
+        out = j;
+        if (inside && side) {
+            out = multi::update_new_slot(j, count, n_nodes, old_slots);
+            inside = out < block_slots;
+        }
+        const uint8_t is = inside ? state[j] : 0;
+        copies = inside && side && !(is & multi::STATE_CHANGED);
+        hashing = inside && !copies && (is & (side ? multi::STATE_NEW_PRESENT : multi::STATE_OLD_PRESENT));
+        if (hashing) v = (side ? new_values : old_values)[(size_t)14 * j + e];
+    } else {
+        if (active) {
+            left = jobs[j].left; right = jobs[j].right; out = jobs[j].out;
+            inside = left < old_slots && right < old_slots && out < old_slots;
+            copies = inside && side && !jobs[j].reserved;
+        }
+        if (inside && side) {
+            out = multi::update_new_slot(out, count, n_nodes, old_slots);
+            if (!copies) {
+                left = multi::update_new_slot(left, count, n_nodes, old_slots);
+                right = multi::update_new_slot(right, count, n_nodes, old_slots);
+            }
+        }
+        inside = inside && left < block_slots && right < block_slots && out < block_slots;
+        copies = copies && inside;
+        hashing = inside && !copies;
+        if (hashing) v = e < 7 ? block[(size_t)7 * left + e] : block[(size_t)7 * right + e - 7];
+    }
+    for (int cyc = 0; cyc < 7; cyc++) v = rescue_round_lane(v, st[s], mrow, e, cyc, hashing);
+    if (!hashing) v = 0; // an absent leaf
+    const fp old_digest = __shfl(v, side ? lane - 14 : lane, 64); // every lane; the old side of hash s is hash s - 1
+    if (copies) v = old_digest;
+    if (inside && e < 7) block[(size_t)7 * out + e] = v;
+    if (active && !inside && e == 0) *fault = 1;
+    if (result) { // uniform: one job, hashes s = 0 (old) and s = 1 (new)
+        const unsigned long long differ = __ballot(inside && e < 7 && v != stated[8 * side + e]);
+        const unsigned long long outside = __ballot(active && !inside); // either side: this launch's own fault, whatever *fault shows yet
+        if (active && side && e < 7) result[1 + e] = v;
+        if (active && s == 0 && e == 0) {
+            const bool old_bad = (differ & 0x3FFFull) || outside || *fault != 0, new_bad = ((differ >> 14) & 0x3FFFull) && have_new;
+            result[0] = old_bad ? (fp)CSTARK_UPDATE_OLD_ROOT : new_bad ? (fp)CSTARK_UPDATE_NEW_ROOT : (fp)CSTARK_UPDATE_VALID;
+        }
     }
 }
 
@@ -298,6 +387,31 @@ int create_impl(cstark_ledger *L) {
     plan_empty_digests(L->index.depth, scratch_base, q);
     RC_TRY(run_plan(L, q, nullptr, 0));
     HIP_TRY(cs::stream_wait(c->stream)); // the plan's host block is read by the copy
+    return CSTARK_OK;
+}
+
+// cstark_ledger_create_partial behind its argument checks and host verdicts (sp is plan_seed's).  The pool is reserved with exactly the
+// plan's stored slots, so the scratch follows them; the empty-subtree digests as in create_impl, then ONE upload (proof nodes into their
+// final slots, values and job list into the scratch), the leaf launch and one launch per level of k_ledger_merge straight into the stored
+// nodes, and the root read back.  *matches = the fold is the stated root; the caller commits the index only then.
+int create_partial_impl(cstark_ledger *L, const cs::multi::SeedPlan &sp, const uint64_t *root, bool *matches) {
+    cstark_ctx *c = L->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const Plan &p = sp.plan;
+    Plan sizes, empty;
+    plan_empty_digests(L->index.depth, 0, sizes); // sizes only
+    const uint64_t scratch = std::max<uint64_t>(p.pool_slots - (EMPTY_SLOTS + p.extended), (sizes.upload.size() + 6) / 7);
+    L->capacity = p.extended; // reserve_pool keeps a capacity that covers the need
+    uint32_t scratch_base;
+    RC_TRY(reserve_pool(L, 0, scratch, &scratch_base));
+    if (scratch_base != EMPTY_SLOTS + p.extended) return fail(CSTARK_ERR_INVALID_ARG, "ledger: pool layout differs from the plan's");
+    plan_empty_digests(L->index.depth, scratch_base, empty);
+    RC_TRY(run_plan(L, empty, nullptr, 0));
+    RC_TRY(run_plan(L, p, nullptr, 0));
+    uint64_t fold[7];
+    HIP_TRY(hipMemcpyAsync(fold, L->pool + (size_t)7 * p.final_root_slot, 56, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream)); // the fold is on the host; the plans' host blocks are read by the copies
+    *matches = memcmp(fold, root, 56) == 0;
     return CSTARK_OK;
 }
 
@@ -578,6 +692,63 @@ int check_multi_impl(cstark_ctx *c, uint32_t depth, uint32_t count, const uint64
     return CSTARK_OK;
 }
 
+// cstark_account_check_update behind its argument checks and its host verdicts (the plan exists with its changed flags, n_nodes is the
+// shape's).  The device block is the multiproof checks' (multi_buf: both calls are synchronous, upload everything they read and keep
+// nothing in it between calls, so they share the one block, grown to the larger need), here in 64-bit words:
+//   digest slots [update_block_slots][7] | old values [count][14] | new values [count][14] |
+//   upload: old root [7], fault word, new root [7] (zeros without one), a spare word, jobs [n_merges][2], result [8] | state [count] bytes
+// The upload block goes up in one copy; values, nodes and state go up as they are.  Then the leaf launch and one launch per level, as
+// many as ONE cstark_account_check_multiproof takes, ordered by the stream.  Nothing of the resident witness, path_buf, tail_buf or the
+// statement caches is read or written.
+int check_update_impl(cstark_ctx *c, uint32_t depth, uint32_t count, const uint64_t *old_values, const uint64_t *new_values, const uint64_t *nodes,
+                      const uint64_t *old_root, const uint64_t *new_root, const cs::multi::CheckPlan &p, const std::vector<uint8_t> &state, uint32_t *verdict,
+                      uint64_t *fold_out) {
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = count, n_jobs = p.jobs.size();
+    const uint32_t n_nodes = p.shape.n_nodes, block_slots = (uint32_t)cs::multi::update_block_slots(count, n_nodes, p.shape.n_merges); // below 2^20 * 126
+    const size_t slot_words = (size_t)7 * block_slots, value_words = 14 * n, upload_words = 16 + 2 * n_jobs;
+    const size_t bytes = (slot_words + 2 * value_words + upload_words + 8) * 8 + n;
+    if (c->multi_bytes < bytes) {
+        if (c->multi_buf) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->multi_buf)); c->multi_buf = nullptr; c->multi_bytes = 0; }
+        HIP_TRY(hipMalloc(&c->multi_buf, bytes));
+        c->multi_bytes = bytes;
+    }
+    uint64_t *d_slots = (uint64_t *)c->multi_buf, *d_old = d_slots + slot_words, *d_new = d_old + value_words, *d_upload = d_new + value_words;
+    uint64_t *d_result = d_upload + upload_words;
+    uint8_t *d_state = (uint8_t *)(d_result + 8);
+    std::vector<uint64_t> upload(upload_words + 8, 0); // word 7: the fault word, cleared; the result words behind the jobs: no verdict yet
+    std::fill(upload.end() - 8, upload.end(), ~(uint64_t)0);
+    memcpy(upload.data(), old_root, 56);
+    if (new_root) memcpy(upload.data() + 8, new_root, 56);
+    memcpy(upload.data() + 16, p.jobs.data(), 16 * n_jobs);
+    HIP_TRY(hipMemcpyAsync(d_old, old_values, n * 112, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_new, new_values, n * 112, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_state, state.data(), n, hipMemcpyHostToDevice, c->stream));
+    if (n_nodes) HIP_TRY(hipMemcpyAsync(d_slots + 7 * n, nodes, (size_t)56 * n_nodes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_upload, upload.data(), upload.size() * 8, hipMemcpyHostToDevice, c->stream));
+    uint32_t *d_fault = (uint32_t *)(d_upload + 7);
+    const Job *d_jobs = (const Job *)(d_upload + 16);
+    hipLaunchKernelGGL(cs::k_multi_update, dim3((count + 1) / 2), dim3(64), 0, c->stream, d_slots, block_slots, count, n_nodes, p.slots, (const Job *)nullptr,
+                       d_old, d_new, d_state, count, d_fault, (const uint64_t *)nullptr, 0u, (uint64_t *)nullptr);
+    HIP_TRY(hipGetLastError());
+    for (uint32_t k = 0; k < depth; k++) {
+        const uint32_t m = p.launch[k + 1] - p.launch[k];
+        const bool last = k + 1 == depth; // level 0: one job
+        hipLaunchKernelGGL(cs::k_multi_update, dim3((m + 1) / 2), dim3(64), 0, c->stream, d_slots, block_slots, count, n_nodes, p.slots, d_jobs + p.launch[k],
+                           (const uint64_t *)nullptr, (const uint64_t *)nullptr, (const uint8_t *)nullptr, m, d_fault, last ? d_upload : nullptr,
+                           new_root ? 1u : 0u, last ? d_result : nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    uint64_t result[8];
+    HIP_TRY(hipMemcpyAsync(result, d_result, 64, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream)); // synchronous: the verdict is on the host, the caller's arrays and the upload block are free again
+    if (result[0] != CSTARK_UPDATE_VALID && result[0] != CSTARK_UPDATE_OLD_ROOT && result[0] != CSTARK_UPDATE_NEW_ROOT)
+        return fail(CSTARK_ERR_HIP, "cstark_account_check_update: the kernel wrote no verdict");
+    *verdict = (uint32_t)result[0];
+    memcpy(fold_out, result + 1, 56);
+    return CSTARK_OK;
+}
+
 // the first word >= p of a [rows][per_row] array, named as `name[row][col]` (paths: `name[row][entry][word]`)
 bool reduced_words(const char *who, const char *name, const uint64_t *a, size_t rows, size_t per_row, bool entries) {
     for (size_t i = 0; i < rows * per_row; i++)
@@ -607,6 +778,18 @@ int usable(cstark_ctx *c, cstark_ledger *L, const char *who) {
     if (!c || !L) return fail(CSTARK_ERR_INVALID_ARG, "%s: null argument", who);
     if (L->ctx != c) return fail(CSTARK_ERR_INVALID_ARG, "%s: the ledger belongs to another context", who);
     if (L->broken) return fail(CSTARK_ERR_HIP, "%s: an earlier HIP failure left this ledger unusable", who);
+    return CSTARK_OK;
+}
+
+// a partial ledger refuses every index it does not know (a full one knows every leaf): the first such position is named, nothing is done
+int all_known(cstark_ledger *L, const char *who, uint32_t count, const uint64_t *indices) {
+    if (!L->index.partial) return CSTARK_OK;
+    for (uint32_t i = 0; i < count; i++)
+        if (!L->index.is_known(indices[i])) {
+            char where[96];
+            snprintf(where, sizeof where, "%s: indices[%u]", who, i);
+            return fail(CSTARK_ERR_INVALID_ARG, "%s is not among the accounts this partial ledger knows", where);
+        }
     return CSTARK_OK;
 }
 
@@ -663,6 +846,57 @@ int cstark_ledger_create(cstark_ctx *c, uint32_t merkle_depth, cstark_ledger **o
     return CSTARK_OK;
 }
 
+int cstark_ledger_create_partial(cstark_ctx *c, uint32_t merkle_depth, uint32_t count, const uint64_t *indices, const uint64_t *values, const uint8_t *present,
+                                 const uint64_t *nodes, uint32_t n_nodes, const uint64_t root[7], cstark_ledger **out, uint32_t *verdict, uint32_t *at) {
+    const char *who = "cstark_ledger_create_partial";
+    if (!c || !indices || !values || !root || !out || !verdict || !at) return fail(CSTARK_ERR_INVALID_ARG, "%s: null argument", who);
+    const uint32_t d = merkle_depth;
+    if (d == 0 || ((d + 1) & d) != 0 || d > MAX_DEPTH) return fail(CSTARK_ERR_INVALID_ARG, "%s: tree depth must be one less than a power of 2 and at most 31", who);
+    if (count == 0 || count > cs::multi::MAX_COUNT) return fail(CSTARK_ERR_INVALID_ARG, "%s: count must be 1 .. 2^20", who);
+    if (!nodes != !n_nodes) return fail(CSTARK_ERR_INVALID_ARG, "%s: nodes is null iff n_nodes is 0", who);
+    if (n_nodes > cs::multi::MAX_COUNT * MAX_DEPTH) return fail(CSTARK_ERR_INVALID_ARG, "%s: n_nodes is beyond any multiproof", who);
+    if (!reduced_words(who, "values", values, count, 14, false)) return CSTARK_ERR_INVALID_ARG;
+    if (nodes && !reduced_words(who, "nodes", nodes, n_nodes, 7, false)) return CSTARK_ERR_INVALID_ARG;
+    if (!reduced_words(who, "root", root, 1, 7, false)) return CSTARK_ERR_INVALID_ARG;
+    // the shape of an untrusted opening is data: these two are verdicts, and nothing is launched for them
+    const cs::multi::Shape s = cs::multi::multiproof_shape(d, count, indices);
+    if (!s.ok || n_nodes != s.n_nodes) {
+        *out = nullptr;
+        *verdict = s.ok ? CSTARK_MULTI_NODE_COUNT : CSTARK_MULTI_INDEX;
+        *at = s.ok ? s.n_nodes : s.bad_at;
+        return CSTARK_OK;
+    }
+    cs::multi::SeedPlan sp;
+    if (!cs::multi::plan_seed(d, count, indices, values, present, nodes, sp)) return fail(CSTARK_ERR_UNSUPPORTED, "%s: the opening is too large to plan", who);
+    cstark_ledger *L = new (std::nothrow) cstark_ledger(c, d);
+    if (!L) return fail(CSTARK_ERR_OOM, "%s: out of host memory", who);
+    bool matches = false;
+    const int rc = create_partial_impl(L, sp, root, &matches);
+    if (rc || !matches) cstark_ledger_destroy(L); // nothing stays allocated; the index was never committed
+    if (rc) return rc;
+    if (matches) cs::multi::commit_seed(L->index, sp, count, indices);
+    *out = matches ? L : nullptr;
+    *verdict = matches ? CSTARK_MULTI_VALID : CSTARK_MULTI_ROOT;
+    *at = 0;
+    return CSTARK_OK;
+}
+
+int cstark_ledger_known(cstark_ctx *c, cstark_ledger *L, uint32_t count, const uint64_t *indices, uint8_t *known_out) {
+    RC_TRY(usable(c, L, "cstark_ledger_known"));
+    if (count && (!indices || !known_out)) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_known: null argument");
+    for (uint32_t i = 0; i < count; i++) known_out[i] = L->index.is_known(indices[i]);
+    return CSTARK_OK;
+}
+
+int cstark_ledger_partial_info(cstark_ctx *c, cstark_ledger *L, uint32_t *is_partial, uint64_t *n_known, uint64_t *n_opaque) {
+    RC_TRY(usable(c, L, "cstark_ledger_partial_info"));
+    if (!is_partial || !n_known || !n_opaque) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_partial_info: null argument");
+    *is_partial = L->index.partial;
+    *n_known = L->index.partial ? L->index.known.size() : L->index.accounts.size();
+    *n_opaque = L->index.n_opaque;
+    return CSTARK_OK;
+}
+
 void cstark_ledger_destroy(cstark_ledger *L) {
     if (!L) return;
     (void)hipSetDevice(L->ctx->device);
@@ -675,12 +909,14 @@ void cstark_ledger_destroy(cstark_ledger *L) {
 int cstark_ledger_set_accounts(cstark_ctx *c, cstark_ledger *L, uint32_t count, const uint64_t *indices, const uint64_t *values) {
     RC_TRY(usable(c, L, "cstark_ledger_set_accounts"));
     if (count == 0 || count > MAX_TRANSFERS || !indices || !values) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_set_accounts: bad argument");
+    RC_TRY(all_known(L, "cstark_ledger_set_accounts", count, indices));
     return guard(L, set_accounts_impl(L, count, indices, values));
 }
 
 int cstark_ledger_get_accounts(cstark_ctx *c, cstark_ledger *L, uint32_t count, const uint64_t *indices, uint64_t *values_out, uint8_t *present_out) {
     RC_TRY(usable(c, L, "cstark_ledger_get_accounts"));
     if (count && (!indices || !values_out || !present_out)) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_get_accounts: null argument");
+    RC_TRY(all_known(L, "cstark_ledger_get_accounts", count, indices));
     for (uint32_t i = 0; i < count; i++) {
         const auto it = L->index.accounts.find(indices[i]);
         present_out[i] = it != L->index.accounts.end();
@@ -701,6 +937,7 @@ int cstark_ledger_open_accounts(cstark_ctx *c, cstark_ledger *L, uint32_t count,
             snprintf(where, sizeof where, "indices[%u]", i);
             return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_open_accounts: %s is out of range", where);
         }
+    RC_TRY(all_known(L, "cstark_ledger_open_accounts", count, indices));
     return guard(L, open_impl(L, count, indices, values_out, present_out, paths_out, root_out));
 }
 
@@ -752,6 +989,7 @@ int cstark_ledger_open_accounts_at(cstark_ctx *c, cstark_ledger *L, uint64_t id,
             snprintf(where, sizeof where, "indices[%u]", i);
             return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_open_accounts_at: %s is out of range", where);
         }
+    RC_TRY(all_known(L, "cstark_ledger_open_accounts_at", count, indices));
     return guard(L, open_impl(L, count, indices, values_out, present_out, paths_out, root_out, (size_t)at));
 }
 
@@ -799,6 +1037,7 @@ int cstark_ledger_open_multi(cstark_ctx *c, cstark_ledger *L, uint64_t id, uint3
     if (at < 0) return CSTARK_ERR_INVALID_ARG;
     const cs::multi::Shape s = cs::multi::multiproof_shape(L->index.depth, count, indices);
     if (!s.ok) return unsorted(who, s.bad_at);
+    RC_TRY(all_known(L, who, count, indices)); // an opening through an opaque node would read empty digests beneath it
     if (nodes_capacity < s.n_nodes) {
         *n_nodes = s.n_nodes;
         char need[96];
@@ -842,6 +1081,46 @@ int cstark_account_check_multiproof(cstark_ctx *c, uint32_t depth, uint32_t coun
     RC_TRY(check_multi_impl(c, depth, count, values, present, leaves, nodes, root, p, &v, root_out));
     *verdict = v;
     *at = 0;
+    return CSTARK_OK;
+}
+
+int cstark_account_check_update(cstark_ctx *c, uint32_t depth, uint32_t count, const uint64_t *indices, const uint64_t *old_values, const uint8_t *old_present,
+                                const uint64_t *new_values, const uint8_t *new_present, const uint64_t *nodes, uint32_t n_nodes, const uint64_t old_root[7],
+                                const uint64_t *new_root, uint32_t *verdict, uint32_t *at, uint64_t *new_root_out, uint32_t *n_changed) {
+    const char *who = "cstark_account_check_update";
+    if (!c || !indices || !old_values || !new_values || !old_root || !verdict || !at) return fail(CSTARK_ERR_INVALID_ARG, "%s: null argument", who);
+    if (depth == 0 || depth > MAX_DEPTH) return fail(CSTARK_ERR_INVALID_ARG, "%s: depth must be 1 .. 31", who);
+    if (count == 0 || count > cs::multi::MAX_COUNT) return fail(CSTARK_ERR_INVALID_ARG, "%s: count must be 1 .. 2^20", who);
+    if (!nodes != !n_nodes) return fail(CSTARK_ERR_INVALID_ARG, "%s: nodes is null iff n_nodes is 0", who);
+    if (n_nodes > cs::multi::MAX_COUNT * MAX_DEPTH) return fail(CSTARK_ERR_INVALID_ARG, "%s: n_nodes is beyond any multiproof", who);
+    if (!reduced_words(who, "old_values", old_values, count, 14, false)) return CSTARK_ERR_INVALID_ARG;
+    if (!reduced_words(who, "new_values", new_values, count, 14, false)) return CSTARK_ERR_INVALID_ARG;
+    if (nodes && !reduced_words(who, "nodes", nodes, n_nodes, 7, false)) return CSTARK_ERR_INVALID_ARG;
+    if (!reduced_words(who, "old_root", old_root, 1, 7, false)) return CSTARK_ERR_INVALID_ARG;
+    if (new_root && !reduced_words(who, "new_root", new_root, 1, 7, false)) return CSTARK_ERR_INVALID_ARG;
+    // the shape of an untrusted opening is data: these two are verdicts, and nothing is launched for them
+    const cs::multi::Shape s = cs::multi::multiproof_shape(depth, count, indices);
+    if (!s.ok) {
+        *verdict = CSTARK_UPDATE_INDEX;
+        *at = s.bad_at;
+        return CSTARK_OK;
+    }
+    if (n_nodes != s.n_nodes) {
+        *verdict = CSTARK_UPDATE_NODE_COUNT;
+        *at = s.n_nodes;
+        return CSTARK_OK;
+    }
+    std::vector<uint8_t> state;
+    const uint32_t changed = cs::multi::update_states(count, old_values, old_present, new_values, new_present, state);
+    cs::multi::CheckPlan p;
+    if (!cs::multi::plan_update(depth, count, indices, state.data(), p)) return fail(CSTARK_ERR_INVALID_ARG, "%s: the indices lost their shape", who);
+    uint32_t v = 0;
+    uint64_t fold[7];
+    RC_TRY(check_update_impl(c, depth, count, old_values, new_values, nodes, old_root, new_root, p, state, &v, fold));
+    *verdict = v;
+    *at = 0;
+    if (new_root_out && v != CSTARK_UPDATE_OLD_ROOT) memcpy(new_root_out, fold, 56);
+    if (n_changed) *n_changed = changed;
     return CSTARK_OK;
 }
 

@@ -53,7 +53,7 @@ struct Emit { uint32_t slot, word; };
 static_assert(sizeof(Job) == 16 && sizeof(Emit) == 8, "lists are copied to the device as they are");
 
 // cstark_ledger_reason (include/cstark.h)
-enum Reason : int32_t { REASON_NONE = 0, REASON_INDEX = 1, REASON_SELF = 2, REASON_ABSENT = 3, REASON_BALANCE = 4, REASON_SIGNATURE = 5 };
+enum Reason : int32_t { REASON_NONE = 0, REASON_INDEX = 1, REASON_SELF = 2, REASON_ABSENT = 3, REASON_BALANCE = 4, REASON_SIGNATURE = 5, REASON_UNKNOWN = 6 };
 
 typedef std::array<uint64_t, 14> Value; // pk.x(6) pk.y(6) balance nonce, memory form
 
@@ -76,7 +76,17 @@ struct Index {
     std::vector<uint32_t> free_slots;             // allocated slots nothing names any more; taken (from the back) before the pool is extended
     std::vector<Checkpoint> checkpoints;          // live ones, oldest first
     uint64_t next_id = 1;                         // ids count from 1 and are never reused
+    // a partial ledger (cstark_ledger_create_partial): built from a multi-opening, it holds the opened leaves, the proof
+    // nodes and the nodes of the fold.  `opaque` names the proof nodes: taken on trust under the root, nothing stored beneath them.  A leaf
+    // is known iff it has no opaque ancestor-or-self, which is the sorted list `known` of the opened indices.  Both are fixed for the
+    // ledger's life: no known leaf's path holds an opaque node, so no write ever reaches one.  A full ledger knows every leaf.
+    bool partial = false;
+    std::vector<uint64_t> known;
+    std::vector<std::unordered_set<uint64_t>> opaque; // [depth + 1] when partial
+    uint64_t n_opaque = 0;
     explicit Index(uint32_t d) : depth(d), node(d + 1) {}
+    bool is_known(uint64_t a) const { return partial ? std::binary_search(known.begin(), known.end(), a) : !(a >> depth); }
+    bool is_opaque(uint32_t level, uint64_t x) const { return partial && opaque[level].count(x) != 0; }
     uint32_t slot(uint32_t level, uint64_t x) const {
         const auto it = node[level].find(x);
         return it == node[level].end() ? level : it->second;
@@ -261,6 +271,7 @@ inline bool plan_apply(const Index &ix, uint32_t scratch_base, uint32_t n_tx, co
         const uint64_t si = s_idx[t], ri = r_idx[t], delta = deltas[t];
         if (si >= size || ri >= size) return refuse(t, REASON_INDEX);
         if (si == ri) return refuse(t, REASON_SELF);
+        if (!ix.is_known(si) || !ix.is_known(ri)) return refuse(t, REASON_UNKNOWN); // a partial ledger only; a full one knows every leaf
         Value *sv = value_of(si), *rv = value_of(ri);
         if (!sv || !rv) return refuse(t, REASON_ABSENT);
         if (to_u64(delta) > to_u64((*sv)[12])) return refuse(t, REASON_BALANCE);
@@ -497,6 +508,7 @@ inline bool plan_audit(const Index &ix, size_t at, const NodeMap &m /* nodes_at(
         std::sort(sorted.begin(), sorted.end());
         for (size_t i = 0; i < sorted.size(); i++) {
             const uint64_t x = sorted[i].first;
+            if (ix.is_opaque(l, x)) continue; // a proof node of a partial ledger is not tested itself: its parent's job reads it
             if (l == d) {
                 const Value *v = ix.value_at(at, x); // a stored leaf without an account fails its job against the zero value
                 if (v) memcpy(&p.upload[14 * i], v->data(), sizeof *v);

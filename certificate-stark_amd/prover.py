@@ -143,6 +143,18 @@ def check_account_multiproof(depth, indices, nodes, root, values=None, present=N
     return MultiproofCheck(*(backend or Backend()).account_check_multiproof(depth, indices, nodes, root, values=values, present=present, leaves=leaves))
 
 
+UpdateCheck = collections.namedtuple("UpdateCheck", "verdict at new_root n_changed")
+
+
+def check_account_update(depth, indices, old_values, new_values, nodes, old_root, new_root=None, old_present=None, new_present=None, backend=None):
+    """A claimed change of state checked by someone who holds only roots, on the GPU: the multi-opening (indices, old_values,
+    old_present, nodes) under old_root, and the same accounts' new values -> UpdateCheck(verdict, at, new_root, n_changed); verdict 0 =
+    valid, Backend.UPDATE_*; see Backend.account_check_update.  new_root=None computes the root the change leads to.  Both states are
+    folded in one pass that shares the proof nodes.  No ledger is needed."""
+    return UpdateCheck(*(backend or Backend()).account_check_update(depth, indices, old_values, new_values, nodes, old_root, new_root=new_root,
+                                                                    old_present=old_present, new_present=new_present))
+
+
 class AccountMultiOpening:
     """What Ledger.open_multi returns: the accounts at the ascending, distinct `indices` (values [count][14], present [count]) and ONE
     multiproof for all of them under `root`: nodes [n_nodes][7], the siblings no opened leaf accounts for, level `depth` first and
@@ -161,19 +173,65 @@ class AccountMultiOpening:
         """-> MultiproofCheck: verdict 0 for an honest opening, .root the fold, .n_merges the merges it took"""
         return check_account_multiproof(self.depth, self.indices, self.nodes, self.root, self.values, self.present, backend=backend or self._backend)
 
+    def to_ledger(self, backend=None):
+        """-> Ledger.from_opening(self): a partial ledger that knows exactly these accounts"""
+        return Ledger.from_opening(self, backend=backend)
+
+    def check_update(self, new_values, new_present=None, new_root=None, backend=None):
+        """-> UpdateCheck: this opening as the old state under .root, new_values [count][14] (new_present [count], None: all present)
+        as the new state of the same accounts, in the order of .indices.  With new_root the transition .root -> new_root is checked;
+        without it .new_root of the answer is the root the change leads to."""
+        return check_account_update(self.depth, self.indices, self.values, new_values, self.nodes, self.root, new_root=new_root,
+                                    old_present=self.present, new_present=new_present, backend=backend or self._backend)
+
 
 class Ledger:
     """The account tree an operator holds, resident on the GPU (cstark_ledger_*): set_accounts, then apply(transfers) per batch -- the
     counterpart of the sequential loop of TransactionMetadata::build_random (src/lib.rs:341-422) on real accounts and transfers.
     apply() leaves the batch's witness resident in the backend: backend.prove(options) follows without an upload."""
-    INDEX_RANGE, SELF_TRANSFER, ABSENT, BALANCE, SIGNATURE = 1, 2, 3, 4, 5
+    INDEX_RANGE, SELF_TRANSFER, ABSENT, BALANCE, SIGNATURE, UNKNOWN = 1, 2, 3, 4, 5, 6
     REASONS = {1: "index out of range", 2: "sender equals receiver", 3: "account absent", 4: "delta above the sender's balance",
-               5: "signature does not verify"}
+               5: "signature does not verify", 6: "account not among those a partial ledger knows"}
 
     def __init__(self, depth=15, backend=None):
         self.backend = backend or Backend()
         self.depth = int(depth)
         self._led = self.backend.ledger_create(self.depth)
+
+    @classmethod
+    def from_opening(cls, opening, backend=None):
+        """-> a PARTIAL ledger built from an AccountMultiOpening, or from (depth, indices, values, present, nodes, root), under the root
+        the opening states (cstark_ledger_create_partial): it knows exactly the opened accounts, present or absent, and for them it
+        behaves as the full ledger does -- apply (the witness stays resident for prove), set_accounts, root, open, open_multi,
+        checkpoints, audit.  A transfer that names an unknown account is refused with reason UNKNOWN, every other call with an unknown
+        index raises CstarkError.  One opening per ledger.  Raises ValueError carrying the verdict (.verdict, .at: Backend.MULTI_*) when
+        the opening does not fold to its root or has no shape."""
+        if isinstance(opening, AccountMultiOpening):
+            backend = backend or opening._backend
+            opening = (opening.depth, opening.indices, opening.values, opening.present, opening.nodes, opening.root)
+        depth, indices, values, present, nodes, root = opening
+        backend = backend or Backend()
+        led, verdict, at = backend.ledger_create_partial(int(depth), indices, values, present, nodes, root)
+        if led is None:
+            err = ValueError("the opening gives no ledger: verdict %d (at %d)" % (verdict, at))
+            err.verdict, err.at = verdict, at
+            raise err
+        self = cls.__new__(cls)
+        self.backend, self.depth, self._led = backend, int(depth), led
+        return self
+
+    @property
+    def partial(self):
+        """True for a ledger built by from_opening"""
+        return self.backend.ledger_partial_info(self._led)[0]
+
+    def partial_info(self):
+        """-> (is_partial, n_known, n_opaque): opened indices and proof nodes of a partial ledger; (False, accounts, 0) of a full one"""
+        return self.backend.ledger_partial_info(self._led)
+
+    def known(self, indices):
+        """-> bool [count]: the leaves this ledger knows (a full ledger: every index below 2^depth)"""
+        return self.backend.ledger_known(self._led, indices)
 
     def close(self):
         if getattr(self, "_led", None) and getattr(self.backend, "ctx", None):
@@ -214,6 +272,15 @@ class Ledger:
         idx, inverse = np.unique(asked, return_inverse=True)
         return AccountMultiOpening(self.depth, idx, *self.backend.ledger_open_multi(self._led, self.depth, idx, at=at), inverse=inverse.reshape(-1),
                                    backend=self.backend)
+
+    def open_multi_for(self, transfers, at=None):
+        """-> AccountMultiOpening of the distinct senders and receivers of `transfers` (what apply() takes): everything a batch reads,
+        for someone who does not hold the tree: .to_ledger() gives them a partial ledger that applies the batch and leaves its witness
+        resident for prove, and .check_update(*ledger.accounts(opening.indices), new_root=ledger.root()) confirms the transition."""
+        if hasattr(transfers, "s_indices"):
+            transfers = (transfers.s_indices, transfers.r_indices)
+        named = np.concatenate([np.ascontiguousarray(transfers[0], np.uint64).reshape(-1), np.ascontiguousarray(transfers[1], np.uint64).reshape(-1)])
+        return self.open_multi(named, at=at)
 
     def checkpoint(self):
         """-> an id that names the ledger's state as it is now (an integer >= 1, never reused).  No device work; old states are kept by

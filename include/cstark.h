@@ -475,7 +475,9 @@ typedef enum cstark_ledger_reason {
     CSTARK_LEDGER_SELF_TRANSFER = 2, /* sender equals receiver */
     CSTARK_LEDGER_ABSENT = 3,       /* sender or receiver has no account */
     CSTARK_LEDGER_BALANCE = 4,      /* delta above the sender's balance, both as canonical integers */
-    CSTARK_LEDGER_SIGNATURE = 5     /* cstark_ledger_apply_checked only: the transfer's signature has another verdict than CSTARK_SIG_VALID */
+    CSTARK_LEDGER_SIGNATURE = 5,    /* cstark_ledger_apply_checked only: the transfer's signature has another verdict than CSTARK_SIG_VALID */
+    CSTARK_LEDGER_UNKNOWN = 6       /* a partial ledger only: sender or receiver is not among the accounts it knows; tested after the self
+                                       transfer and before absence (index range, self transfer, unknown, absent, balance, signature) */
 } cstark_ledger_reason;
 /* An empty tree of depth 1, 3, 7, 15 or 31 (the depths cstark_tx_witness_upload accepts).  Destroy it before its context. */
 int cstark_ledger_create(cstark_ctx *ctx, uint32_t merkle_depth, cstark_ledger **out);
@@ -644,6 +646,68 @@ int cstark_account_check_multiproof(cstark_ctx *ctx, uint32_t depth, uint32_t co
                                     const uint64_t *leaves /* [count][7] or NULL */, const uint64_t *nodes /* [n_nodes][7] */, uint32_t n_nodes,
                                     const uint64_t root[7], uint32_t *verdict /* cstark_multi_verdict */, uint32_t *at,
                                     uint64_t *root_out /* optional [7] */, uint32_t *n_merges /* optional */);
+
+/* ---- a partial ledger from a multi-opening ----------------------------------------------------------------------------
+ * A ledger of someone who does not hold the tree: built from a multi-opening (indices, values, present, nodes) under a stated root, it
+ * stores the leaf of every opened PRESENT account, every proof node (opaque: taken on trust under the root, nothing stored beneath it)
+ * and every node of the fold.  A leaf is KNOWN iff it has no opaque ancestor-or-self: exactly the opened indices, present or absent, for
+ * the ledger's life.  For known accounts every ledger call behaves as on a full ledger: apply and apply_checked (the resident witness
+ * follows), set_accounts (which may create an opened absent account), root, open, open_multi, checkpoint, revert, release, audit.  What
+ * would touch an unknown account is refused: a transfer with an unknown sender or receiver with CSTARK_LEDGER_UNKNOWN (nothing changed),
+ * and cstark_ledger_set_accounts, _get_accounts, _open_accounts(_at) and _open_multi with an unknown index with CSTARK_ERR_INVALID_ARG,
+ * nothing changed, outputs untouched, cstark_last_error naming the first such position.  cstark_ledger_audit does not test an opaque
+ * node itself (its parent's test reads it); n_nodes of the report still counts every stored node.
+ * merkle_depth as for cstark_ledger_create; count 1 .. 2^20; indices strictly ascending below 2^depth; a NULL present: all present.  The
+ * shape of an untrusted opening is data, as in cstark_account_check_multiproof: CSTARK_MULTI_INDEX and _NODE_COUNT are verdicts with
+ * status CSTARK_OK, *at as there, nothing launched and *out = NULL.  A fold that differs from `root` is the verdict CSTARK_MULTI_ROOT with
+ * *out = NULL and nothing left allocated; CSTARK_MULTI_VALID gives a ledger whose cstark_ledger_root is `root`.  Null ctx, indices,
+ * values, root, out, verdict or at, a bad depth or count, nodes null with n_nodes != 0 or the reverse, or a word >= p in values, nodes or
+ * root is CSTARK_ERR_INVALID_ARG before anything is launched, outputs untouched; cstark_last_error names the first such word, in that
+ * order of the arrays.  Device work: one upload that puts the proof nodes into their final pool slots and the values into scratch, the
+ * leaf hashes and one launch per level straight into the new ledger's pool, the root read back.  The resident witness is not touched.
+ * One opening per ledger: several openings cannot be combined, and none can be added later. */
+int cstark_ledger_create_partial(cstark_ctx *ctx, uint32_t merkle_depth, uint32_t count, const uint64_t *indices,
+                                 const uint64_t *values /* [count][14] */, const uint8_t *present /* [count] or NULL */,
+                                 const uint64_t *nodes /* [n_nodes][7], NULL iff n_nodes == 0 */, uint32_t n_nodes, const uint64_t root[7],
+                                 cstark_ledger **out, uint32_t *verdict /* cstark_multi_verdict */, uint32_t *at);
+/* known_out[i] = 1 iff the ledger knows leaf indices[i]; a full ledger knows every index below 2^depth. */
+int cstark_ledger_known(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t count, const uint64_t *indices, uint8_t *known_out);
+/* Full ledger: is_partial = 0, n_opaque = 0, n_known = the number of accounts.  Partial: n_known opened indices, n_opaque proof nodes. */
+int cstark_ledger_partial_info(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t *is_partial, uint64_t *n_known, uint64_t *n_opaque);
+
+/* ---- a root update checked without a ledger -------------------------------------------------------------------------
+ * Whoever holds only roots checks "these accounts changed from old_values to new_values, and that takes old_root to new_root", or
+ * computes the root the change leads to.  The opening (indices, old_values, old_present, nodes) is a multi-opening under old_root as
+ * cstark_ledger_open_multi gives it; the new state of the SAME positions is (new_values, new_present), and the proof nodes, which no
+ * opened leaf lies under, serve both states.  The verdict is the first that applies. */
+typedef enum cstark_update_verdict {
+    CSTARK_UPDATE_VALID = 0,
+    CSTARK_UPDATE_INDEX = 1,      /* as CSTARK_MULTI_INDEX */
+    CSTARK_UPDATE_NODE_COUNT = 2, /* as CSTARK_MULTI_NODE_COUNT */
+    CSTARK_UPDATE_OLD_ROOT = 3,   /* the old values do not fold to old_root; nothing is said about the new side */
+    CSTARK_UPDATE_NEW_ROOT = 4    /* the old side is valid, the new values fold to something other than new_root */
+} cstark_update_verdict;
+/* Folds both states on the device in ONE pass: the leaf hashes in one launch, then one launch per level, as many launches as one
+ * cstark_account_check_multiproof takes.  A node of the new state is hashed only where a changed leaf lies below it and is the old
+ * state's digest elsewhere, so one changed account among many costs `depth` more hashes than the check of the opening alone.  Any depth
+ * 1 .. 31 and count 1 .. 2^20.  A NULL old_present or new_present means all present; where a flag is 0 the leaf is the all-zero digest
+ * and the value words do not enter the fold.  new_root == NULL means "compute only": the verdict is then VALID or OLD_ROOT.  new_root_out
+ * (optional) receives the fold of the new state for VALID and NEW_ROOT and is untouched otherwise; n_changed (optional) receives, for
+ * VALID, OLD_ROOT and NEW_ROOT, the number of positions whose (value, presence) differ -- two absent positions are equal whatever their
+ * value words.  INDEX and NODE_COUNT are verdicts with *at as in cstark_account_check_multiproof: the status is CSTARK_OK and nothing is
+ * launched.  *at is 0 for the other verdicts.
+ * Null ctx, indices, old_values, new_values, old_root, verdict or at, depth outside 1 .. 31, count outside 1 .. 2^20, nodes null with
+ * n_nodes != 0 or the reverse, or a word >= p in old_values, new_values, nodes, old_root or new_root is CSTARK_ERR_INVALID_ARG before
+ * anything is launched and with the outputs untouched; cstark_last_error names the first such word, in that order of the arrays.
+ * Synchronous, on the context's stream, in the device block of cstark_account_check_multiproof, which neither call keeps anything in
+ * between calls: the resident witness and the blocks of the path and signature checks are neither read nor written, so a proof after
+ * a check is the proof without it. */
+int cstark_account_check_update(cstark_ctx *ctx, uint32_t depth, uint32_t count, const uint64_t *indices,
+                                const uint64_t *old_values /* [count][14] */, const uint8_t *old_present /* [count] or NULL */,
+                                const uint64_t *new_values /* [count][14] */, const uint8_t *new_present /* [count] or NULL */,
+                                const uint64_t *nodes /* [n_nodes][7] */, uint32_t n_nodes, const uint64_t old_root[7],
+                                const uint64_t *new_root /* [7] or NULL */, uint32_t *verdict /* cstark_update_verdict */, uint32_t *at,
+                                uint64_t *new_root_out /* optional [7] */, uint32_t *n_changed /* optional */);
 
 /* ---- verification (TransactionExample::verify, src/lib.rs:144-150: winterfell::verify over this library's own proof layout) -------
  * The call's status (cstark_status) is kept apart from the proof's verdict.  A verdict names the FIRST check that fails, in this

@@ -247,6 +247,30 @@ inline MultiproofCheck check_account_multiproof(Context &ctx, unsigned depth, co
                                           (uint32_t)(nodes.size() / 7), root.data(), &r.verdict, &r.at, r.root.data(), &r.n_merges));
     return r;
 }
+// cstark_account_check_update
+struct UpdateCheck {
+    uint32_t verdict = 0;   // cstark_update_verdict (CSTARK_UPDATE_VALID = 0)
+    uint32_t at = 0;        // INDEX: the offending position; NODE_COUNT: the needed number of nodes
+    uint32_t n_changed = 0; // positions whose (value, presence) differ; for VALID, OLD_ROOT and NEW_ROOT
+    Hash new_root{};        // the fold of the new state, for VALID and NEW_ROOT
+};
+// The opening `old` under old.root against the new state of the same accounts (new_values in the order of old.indices; new_present
+// optional: all present), both folded in one pass: with new_root the transition old.root -> *new_root is checked, without it the answer's
+// new_root is the root the change leads to.  A wrong order of the indices or a wrong number of nodes is a verdict, not an Error.  No
+// ledger is needed and a resident witness is not touched.
+inline UpdateCheck check_account_update(Context &ctx, const AccountMultiOpening &old, const std::vector<std::array<BaseElement, 14>> &new_values,
+                                        const std::vector<uint8_t> *new_present = nullptr, const Hash *new_root = nullptr) {
+    const size_t n = old.indices.size();
+    if (n == 0 || old.values.size() != n || (!old.present.empty() && old.present.size() != n) || new_values.size() != n || old.nodes.size() % 7 ||
+        (new_present && new_present->size() != n))
+        throw Error(CSTARK_ERR_INVALID_ARG, "update vectors are not of matching length");
+    UpdateCheck r;
+    check(cstark_account_check_update(ctx.raw(), old.depth, (uint32_t)n, old.indices.data(), old.values[0].data(),
+                                      old.present.empty() ? nullptr : old.present.data(), new_values[0].data(), new_present ? new_present->data() : nullptr,
+                                      old.nodes.empty() ? nullptr : old.nodes.data(), (uint32_t)(old.nodes.size() / 7), old.root.data(),
+                                      new_root ? new_root->data() : nullptr, &r.verdict, &r.at, r.new_root.data(), &r.n_changed));
+    return r;
+}
 // The account tree an operator holds, resident on the GPU (cstark_ledger_*): what replaces the sequential loop of
 // TransactionMetadata::build_random (src/lib.rs:341-422) on real accounts.  apply() leaves the batch's witness resident in the context:
 // TransactionProver::prove_resident follows without an upload.
@@ -256,6 +280,39 @@ class Ledger {
     ~Ledger() { cstark_ledger_destroy(led_); }
     Ledger(const Ledger &) = delete;
     Ledger &operator=(const Ledger &) = delete;
+    // A PARTIAL ledger (cstark_ledger_create_partial) built from a multi-opening under the root it states: it knows exactly the opened
+    // accounts, present or absent, and for them behaves as the full ledger does (apply, set_accounts, root, open, open_multi,
+    // checkpoints, audit; apply() leaves the witness resident).  A transfer that names an unknown account is refused with
+    // CSTARK_LEDGER_UNKNOWN, every other call with an unknown index throws.  Throws Error(CSTARK_ERR_INVALID_ARG) naming the verdict when
+    // the opening has no shape or does not fold to its root; *verdict (optional) receives the cstark_multi_verdict either way.  Returned
+    // by value: the class cannot be copied or moved, the caller binds the result (`cstark::Ledger p = cstark::Ledger::from_multiproof(..)`)
+    static Ledger from_multiproof(Context &ctx, const AccountMultiOpening &o, uint32_t *verdict = nullptr) {
+        const size_t n = o.indices.size();
+        if (n == 0 || o.values.size() != n || (!o.present.empty() && o.present.size() != n) || o.nodes.size() % 7)
+            throw Error(CSTARK_ERR_INVALID_ARG, "multiproof vectors are not of matching length");
+        cstark_ledger *led = nullptr;
+        uint32_t v = 0, at = 0;
+        check(cstark_ledger_create_partial(ctx.raw(), o.depth, (uint32_t)n, o.indices.data(), o.values[0].data(), o.present.empty() ? nullptr : o.present.data(),
+                                           o.nodes.empty() ? nullptr : o.nodes.data(), (uint32_t)(o.nodes.size() / 7), o.root.data(), &led, &v, &at));
+        if (verdict) *verdict = v;
+        if (!led) throw Error(CSTARK_ERR_INVALID_ARG, "the opening gives no ledger: cstark_multi_verdict " + std::to_string(v) + " at " + std::to_string(at));
+        return Ledger(ctx, o.depth, led);
+    }
+    // which of the given leaves the ledger knows (a full ledger: every index below 2^depth)
+    std::vector<uint8_t> known(const std::vector<uint64_t> &indices) const {
+        std::vector<uint8_t> k(indices.size());
+        if (!indices.empty()) check(cstark_ledger_known(ctx_.raw(), led_, (uint32_t)indices.size(), indices.data(), k.data()));
+        return k;
+    }
+    struct PartialInfo { bool is_partial; uint64_t n_known, n_opaque; };
+    // partial: opened indices and proof nodes; full: {false, number of accounts, 0}
+    PartialInfo partial_info() const {
+        uint32_t partial = 0;
+        PartialInfo r{};
+        check(cstark_ledger_partial_info(ctx_.raw(), led_, &partial, &r.n_known, &r.n_opaque));
+        r.is_partial = partial != 0;
+        return r;
+    }
     void set_accounts(const std::vector<uint64_t> &indices, const std::vector<std::array<BaseElement, 14>> &values) {
         if (indices.size() != values.size() || indices.empty()) throw Error(CSTARK_ERR_INVALID_ARG, "one value per account index");
         check(cstark_ledger_set_accounts(ctx_.raw(), led_, (uint32_t)indices.size(), indices.data(), values[0].data()));
@@ -351,6 +408,7 @@ class Ledger {
     TransactionMetadata apply_checked(const Transfers &t) { return apply(t, true); }
 
   private:
+    Ledger(Context &ctx, unsigned depth, cstark_ledger *led) : ctx_(ctx), depth_(depth), led_(led) {}
     TransactionMetadata apply(const Transfers &t, bool check_signatures) {
         const size_t n = t.s_indices.size();
         if (n == 0 || t.r_indices.size() != n || t.deltas.size() != n || t.sig_rx.size() != n || t.sig_s.size() != n)
