@@ -717,6 +717,72 @@ class Backend:
                                                        self._hptr(verdicts, u8p), self._hptr(x) if want_rx else None))
         return (verdicts, x) if want_rx else verdicts
 
+    # cstark_sign_status.  A signer for building batches, tests and benchmarks (small integer keys): it is not a wallet.
+    SIGN_OK, SIGN_NEGATIVE, SIGN_RANGE, SIGN_INFINITY, SIGN_EXHAUSTED = 0, 1, 2, 3, 4
+    SIG_MAX_SECRET = 255
+
+    def schnorr_public_keys(self, secrets):
+        """cstark_schnorr_public_keys: secrets[i] * G for secrets in 1 .. 255 -> uint64 [count][12], affine (x, y) in memory form"""
+        sk = _np_u64(secrets).reshape(-1)
+        keys = np.zeros((sk.size, 12), np.uint64)
+        check(self.lib.cstark_schnorr_public_keys(self.ctx, C.c_uint32(sk.size), self._hptr(sk), self._hptr(keys)))
+        return keys
+
+    @staticmethod
+    def _sign_inputs(messages, secrets):
+        m, sk = _np_u64(messages).reshape(-1, 28), _np_u64(secrets).reshape(-1)
+        if m.shape[0] != sk.size:
+            raise ValueError("the signing arrays state different numbers of signatures")
+        return m, sk, np.zeros((sk.size, 6), np.uint64), np.zeros((sk.size, 32), np.uint8), np.zeros(sk.size, np.uint8)
+
+    def schnorr_sign_nonces(self, messages, secrets, nonces):
+        """cstark_schnorr_sign_nonces: one signing attempt per entry with the caller's nonce (uint64 [count][5] little-endian limbs,
+        below 2^264) -> (sig_rx [count][6], sig_s [count][32], status uint8 [count]); every output is defined whatever the status."""
+        m, sk, rx, s, status = self._sign_inputs(messages, secrets)
+        r = _np_u64(nonces).reshape(-1, 5)
+        if r.shape[0] != sk.size:
+            raise ValueError("the signing arrays state different numbers of signatures")
+        check(self.lib.cstark_schnorr_sign_nonces(self.ctx, C.c_uint32(sk.size), self._hptr(m), self._hptr(sk), self._hptr(r), self._hptr(rx),
+                                                  self._hptr(s, u8p), self._hptr(status, u8p)))
+        return rx, s, status
+
+    def schnorr_sign(self, messages, secrets, seed=0, max_attempts=256):
+        """cstark_schnorr_sign: the seeded signer -> (sig_rx, sig_s, attempts uint32 [count], status uint8 [count]); the result of a
+        signature is that of the first accepted attempt of its own nonce stream, SIGN_EXHAUSTED (zero outputs) without one."""
+        m, sk, rx, s, status = self._sign_inputs(messages, secrets)
+        attempts = np.zeros(sk.size, np.uint32)
+        check(self.lib.cstark_schnorr_sign(self.ctx, C.c_uint32(sk.size), self._hptr(m), self._hptr(sk), C.c_uint64(seed), C.c_uint32(max_attempts),
+                                           self._hptr(rx), self._hptr(s, u8p), self._hptr(attempts, C.POINTER(C.c_uint32)), self._hptr(status, u8p)))
+        return rx, s, attempts, status
+
+    def ledger_messages(self, led, s_indices, r_indices, deltas):
+        """cstark_ledger_messages: -> (refused_at, reason, messages [n_tx][28]): what each transfer of the batch has to sign, or the
+        refusal cstark_ledger_apply would give (messages is None then).  Read-only."""
+        s, r, dl = _np_u64(s_indices).reshape(-1), _np_u64(r_indices).reshape(-1), _np_u64(deltas).reshape(-1)
+        if not (r.size == dl.size == s.size):
+            raise ValueError("the transfer arrays state different numbers of transfers")
+        out = np.zeros((s.size, 28), np.uint64)
+        at, reason = C.c_int32(-1), C.c_int32(0)
+        check(self.lib.cstark_ledger_messages(self.ctx, led, C.c_uint32(s.size), self._hptr(s), self._hptr(r), self._hptr(dl), self._hptr(out),
+                                              C.byref(at), C.byref(reason)))
+        return at.value, reason.value, out if at.value < 0 else None
+
+    def ledger_sign(self, led, s_indices, r_indices, deltas, secrets, seed=0, max_attempts=256):
+        """cstark_ledger_sign: -> (refused_at, reason, sig_rx, sig_s, attempts); refused (reason 7: a secret is not its sender's key, or
+        a reason of cstark_ledger_apply): the three arrays are None.  Read-only."""
+        s, r, dl, sk = (_np_u64(a).reshape(-1) for a in (s_indices, r_indices, deltas, secrets))
+        n = s.size
+        if not (r.size == dl.size == sk.size == n):
+            raise ValueError("the transfer arrays state different numbers of transfers")
+        rx, ss, attempts = np.zeros((n, 6), np.uint64), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint32)
+        at, reason = C.c_int32(-1), C.c_int32(0)
+        check(self.lib.cstark_ledger_sign(self.ctx, led, C.c_uint32(n), self._hptr(s), self._hptr(r), self._hptr(dl), self._hptr(sk), C.c_uint64(seed),
+                                          C.c_uint32(max_attempts), self._hptr(rx), self._hptr(ss, u8p), self._hptr(attempts, C.POINTER(C.c_uint32)),
+                                          C.byref(at), C.byref(reason)))
+        if at.value >= 0:
+            return at.value, reason.value, None, None, None
+        return -1, 0, rx, ss, attempts
+
     def schnorr_build_trace(self):
         out = self.empty_u64(56, self.n_tx * 512)
         check(self.lib.cstark_schnorr_build_trace(self.ctx, self._ptr(out)))

@@ -5,8 +5,11 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <deque>
+#include <mutex>
 #include <new>
+#include <unordered_map>
 #include <vector>
 #include "../../include/cstark.h"
 #include "air_tx_host.h"
@@ -18,6 +21,7 @@
 #include "generator_fold.h"
 #include "hostfield.h"
 #include "ntt.h"
+#include "sign_plan.h"
 #include "trace_gen.h"
 
 namespace cs { thread_local char g_err[512] = ""; }
@@ -41,6 +45,28 @@ struct DevGuard {
     void release() { armed = false; }
     ~DevGuard() { if (armed) for (void *q : ptrs) (void)hipFree(q); }
 };
+
+// The fixed-base table of the signing calls (trace_gen.h: 990 multiples of G, constants only), one per context: built on the context's
+// stream by its first signing call, found again by the context's address, freed by cstark_ctx_destroy.  It is kept beside struct
+// cstark_ctx, not in it: it is no function of anything a call passes in, so no call history can change what it holds.
+std::mutex &g_sign_tables_lock = *new std::mutex; // never destroyed: a context may be destroyed while the process exits
+std::unordered_map<const cstark_ctx *, uint64_t *> &g_sign_tables = *new std::unordered_map<const cstark_ctx *, uint64_t *>;
+uint64_t *sign_table_find(const cstark_ctx *c) {
+    std::lock_guard<std::mutex> hold(g_sign_tables_lock);
+    const auto it = g_sign_tables.find(c);
+    return it == g_sign_tables.end() ? nullptr : it->second;
+}
+void sign_table_keep(const cstark_ctx *c, uint64_t *table) {
+    std::lock_guard<std::mutex> hold(g_sign_tables_lock);
+    g_sign_tables[c] = table;
+}
+void sign_table_release(const cstark_ctx *c) {
+    std::lock_guard<std::mutex> hold(g_sign_tables_lock);
+    const auto it = g_sign_tables.find(c);
+    if (it == g_sign_tables.end()) return;
+    (void)hipFree(it->second);
+    g_sign_tables.erase(it);
+}
 
 int get_plan(cstark_ctx *c, unsigned log_n, const NttPlan **out) {
     for (const NttPlan &p : c->plans)
@@ -551,6 +577,7 @@ void cstark_ctx_destroy(cstark_ctx *c) {
     if (c->rb_host) (void)hipHostFree(c->rb_host);
     if (c->tail_buf) (void)hipFree(c->tail_buf);
     if (c->sig_buf) (void)hipFree(c->sig_buf);
+    sign_table_release(c);
     if (c->path_buf) (void)hipFree(c->path_buf);
     if (c->multi_buf) (void)hipFree(c->multi_buf);
     for (cs::RawPeriodic &t : c->raw_periodic) (void)hipFree(t.tab);
@@ -1402,6 +1429,178 @@ int signature_check(cstark_ctx *c, const char *who, uint32_t count, const uint64
     HIP_TRY(hipStreamSynchronize(c->stream)); // synchronous: the verdicts are on the host, the caller's arrays are free again
     return CSTARK_OK;
 }
+
+// ---- signing (cstark_schnorr_public_keys, cstark_schnorr_sign_nonces, cstark_schnorr_sign) --------------------------------------------
+// They run in the device block of the signature check (c->sig_buf, grown when needed): both kinds of call are synchronous, upload
+// everything they read and keep nothing in the block between calls, so sharing it is invisible to either.  The fixed-base table is
+// built by the context's first call that signs (sign_table_find, above).  Nothing of the resident witness (c->wit, c->wit_buf,
+// c->tail_buf, the Schnorr statement caches) is read or written.
+static_assert(cs::SIGN_OK == CSTARK_SIGN_OK && cs::SIGN_NEGATIVE == CSTARK_SIGN_NEGATIVE && cs::SIGN_RANGE == CSTARK_SIGN_RANGE &&
+                  cs::SIGN_INFINITY == CSTARK_SIGN_INFINITY && (int)cs::sign::EXHAUSTED == CSTARK_SIGN_EXHAUSTED && (int)cs::sign::OK == CSTARK_SIGN_OK,
+              "k_sign_scalar and sign_plan.h write the values of cstark_sign_status");
+static_assert(cs::sign::MAX_SECRET == CSTARK_SIG_MAX_SECRET, "the documented cap is the plan's");
+namespace {
+
+int sign_scratch(cstark_ctx *c, size_t bytes, const uint64_t **table) {
+    HIP_TRY(hipSetDevice(c->device));
+    uint64_t *t = sign_table_find(c);
+    if (!t) {
+        HIP_TRY(hipMalloc(&t, cs::SIGN_TABLE_WORDS * 8));
+        const hipError_t e = cs::launch_sign_table(t, c->stream);
+        if (e != hipSuccess) { (void)hipFree(t); HIP_TRY(e); }
+        sign_table_keep(c, t);
+    }
+    *table = t;
+    if (c->sig_bytes < bytes) {
+        if (c->sig_buf) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->sig_buf)); c->sig_buf = nullptr; c->sig_bytes = 0; }
+        HIP_TRY(hipMalloc(&c->sig_buf, bytes));
+        c->sig_bytes = bytes;
+    }
+    return CSTARK_OK;
+}
+
+// the block of `rows` attempts for n signatures: every array starts on an 8-byte boundary
+struct SignBlock {
+    uint64_t *msg, *secrets, *gathered, *nonces, *rx, *h, *s;
+    uint32_t *owner;
+    uint8_t *infinity, *status;
+    static size_t bytes(size_t n, size_t rows) { return n * 29 * 8 + rows * (28 + 5 + 6 + 4 + 4) * 8 + (rows * 4 + 7) / 8 * 8 + 2 * rows; }
+    SignBlock(void *base, size_t n, size_t rows) {
+        msg = (uint64_t *)base; secrets = msg + 28 * n; gathered = secrets + n; nonces = gathered + 28 * rows; rx = nonces + 5 * rows; h = rx + 6 * rows;
+        s = h + 4 * rows; owner = (uint32_t *)(s + 4 * rows); infinity = (uint8_t *)owner + (rows * 4 + 7) / 8 * 8; status = infinity + rows;
+    }
+};
+
+// the misuse rules the three signing calls share; the first offender is named
+int sign_arguments(const char *who, uint32_t count, const uint64_t *messages, const uint64_t *secrets, const uint64_t *nonces) {
+    char text[160];
+    if (count == 0 || count > cs::sign::MAX_COUNT) return fail(CSTARK_ERR_INVALID_ARG, "%s: count must be 1 .. 2^20", who);
+    for (uint32_t i = 0; i < count; i++)
+        if (secrets[i] == 0 || secrets[i] > cs::sign::MAX_SECRET) {
+            snprintf(text, sizeof text, "%s: secrets[%u] is not in 1 .. %u", who, i, (unsigned)cs::sign::MAX_SECRET);
+            return fail(CSTARK_ERR_INVALID_ARG, "%s", text);
+        }
+    if (nonces)
+        for (uint32_t i = 0; i < count; i++)
+            if (nonces[5 * (size_t)i + 4] >> 8) {
+                snprintf(text, sizeof text, "%s: nonces[%u] is not below 2^264", who, i);
+                return fail(CSTARK_ERR_INVALID_ARG, "%s", text);
+            }
+    if (messages)
+        for (size_t i = 0; i < (size_t)28 * count; i++)
+            if (messages[i] >= cs::host::P) {
+                snprintf(text, sizeof text, "%s: messages[%zu][%zu] is not a reduced field element", who, i / 28, i % 28);
+                return fail(CSTARK_ERR_INVALID_ARG, "%s", text);
+            }
+    return CSTARK_OK;
+}
+
+} // namespace
+
+int sign_public_keys(cstark_ctx *c, uint32_t count, const uint64_t *secrets, uint64_t *keys_out) {
+    const size_t n = count;
+    const uint64_t *table;
+    RC_TRY(sign_scratch(c, n * (5 + 12) * 8 + n, &table));
+    uint64_t *d_nonces = (uint64_t *)c->sig_buf, *d_points = d_nonces + 5 * n;
+    uint8_t *d_inf = (uint8_t *)(d_points + 12 * n);
+    std::vector<uint64_t> nonces(5 * n, 0); // sk*G by the comb: the nonce is the secret
+    for (size_t i = 0; i < n; i++) nonces[5 * i] = secrets[i];
+    HIP_TRY(hipMemcpyAsync(d_nonces, nonces.data(), n * 40, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(cs::launch_sign_points(table, d_nonces, d_points, nullptr, d_inf, count, c->stream));
+    HIP_TRY(hipMemcpyAsync(keys_out, d_points, n * 96, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CSTARK_OK;
+}
+
+static int sign_with_nonces(cstark_ctx *c, uint32_t count, const uint64_t *messages, const uint64_t *secrets, const uint64_t *nonces, uint64_t *sig_rx,
+                            uint8_t *sig_s, uint8_t *status) {
+    const size_t n = count;
+    const uint64_t *table;
+    RC_TRY(sign_scratch(c, SignBlock::bytes(n, n), &table));
+    const SignBlock b(c->sig_buf, n, n);
+    HIP_TRY(hipMemcpyAsync(b.msg, messages, n * 28 * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b.secrets, secrets, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b.nonces, nonces, n * 40, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(cs::launch_sign_attempts(table, b.msg, nullptr, nullptr, b.secrets, b.nonces, b.rx, b.infinity, b.h, (uint8_t *)b.s, b.status, count,
+                                     c->stream));
+    HIP_TRY(hipMemcpyAsync(sig_rx, b.rx, n * 48, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(sig_s, b.s, n * 32, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(status, b.status, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CSTARK_OK;
+}
+
+int sign_seeded(cstark_ctx *c, uint32_t count, const uint64_t *messages, const uint64_t *secrets, uint64_t seed, uint32_t max_attempts, uint64_t *sig_rx,
+                uint8_t *sig_s, uint32_t *attempts_out, uint8_t *status) {
+    const size_t n = count;
+    cs::sign::Plan plan(count, secrets, seed, max_attempts);
+    size_t cap = 0; // rows of the largest round
+    for (size_t t = 0; t < n && cap < cs::sign::ROUND_ATTEMPTS; t++) cap += std::min<size_t>((secrets[t] + 2) / 2, max_attempts);
+    cap = std::min<size_t>(cap, cs::sign::ROUND_ATTEMPTS);
+    const uint64_t *table;
+    RC_TRY(sign_scratch(c, SignBlock::bytes(n, cap), &table));
+    const SignBlock b(c->sig_buf, n, cap);
+    HIP_TRY(hipMemcpyAsync(b.msg, messages, n * 28 * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b.secrets, secrets, n * 8, hipMemcpyHostToDevice, c->stream));
+    cs::sign::Round round;
+    std::vector<uint64_t> rx;
+    std::vector<uint8_t> s, st;
+    std::vector<std::pair<uint32_t, uint32_t>> accepted;
+    while (plan.next_round(round)) {
+        const size_t rows = round.rows();
+        if (rows > cap) return fail(CSTARK_ERR_UNSUPPORTED, "cstark_schnorr_sign: a round outgrew its scratch");
+        rx.resize(6 * rows); s.resize(32 * rows); st.resize(rows);
+        HIP_TRY(hipMemcpyAsync(b.owner, round.owner.data(), rows * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(b.nonces, round.nonces.data(), rows * 40, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(cs::launch_sign_attempts(table, b.msg, b.owner, b.gathered, b.secrets, b.nonces, b.rx, b.infinity, b.h, (uint8_t *)b.s, b.status,
+                                         (uint32_t)rows, c->stream));
+        HIP_TRY(hipMemcpyAsync(st.data(), b.status, rows, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(rx.data(), b.rx, rows * 48, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(s.data(), b.s, rows * 32, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        accepted.clear();
+        plan.select(round, st.data(), accepted);
+        for (const auto &hit : accepted) {
+            memcpy(sig_rx + 6 * (size_t)hit.first, &rx[6 * (size_t)hit.second], 48);
+            memcpy(sig_s + 32 * (size_t)hit.first, &s[32 * (size_t)hit.second], 32);
+        }
+    }
+    for (size_t t = 0; t < n; t++) {
+        const cs::sign::Signature &sg = plan.sigs[t];
+        status[t] = sg.status;
+        if (attempts_out) attempts_out[t] = sg.attempts;
+        if (sg.status != cs::sign::OK) {
+            memset(sig_rx + 6 * t, 0, 48);
+            memset(sig_s + 32 * t, 0, 32);
+        }
+    }
+    return CSTARK_OK;
+}
+
+extern "C" {
+
+int cstark_schnorr_public_keys(cstark_ctx *c, uint32_t count, const uint64_t *secrets, uint64_t *keys_out) {
+    if (!c || !secrets || !keys_out) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_public_keys: null argument");
+    RC_TRY(sign_arguments("cstark_schnorr_public_keys", count, nullptr, secrets, nullptr));
+    return sign_public_keys(c, count, secrets, keys_out);
+}
+
+int cstark_schnorr_sign_nonces(cstark_ctx *c, uint32_t count, const uint64_t *messages, const uint64_t *secrets, const uint64_t *nonces, uint64_t *sig_rx,
+                               uint8_t *sig_s, uint8_t *status) {
+    if (!c || !messages || !secrets || !nonces || !sig_rx || !sig_s || !status) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_sign_nonces: null argument");
+    RC_TRY(sign_arguments("cstark_schnorr_sign_nonces", count, messages, secrets, nonces));
+    return sign_with_nonces(c, count, messages, secrets, nonces, sig_rx, sig_s, status);
+}
+
+int cstark_schnorr_sign(cstark_ctx *c, uint32_t count, const uint64_t *messages, const uint64_t *secrets, uint64_t seed, uint32_t max_attempts,
+                        uint64_t *sig_rx, uint8_t *sig_s, uint32_t *attempts_out, uint8_t *status) {
+    if (!c || !messages || !secrets || !sig_rx || !sig_s || !status) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_sign: null argument");
+    RC_TRY(sign_arguments("cstark_schnorr_sign", count, messages, secrets, nullptr));
+    if (max_attempts == 0 || max_attempts > cs::sign::MAX_ATTEMPTS) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_sign: max_attempts must be 1 .. 4096");
+    return sign_seeded(c, count, messages, secrets, seed, max_attempts, sig_rx, sig_s, attempts_out, status);
+}
+
+} // extern "C"
 
 extern "C" {
 

@@ -213,7 +213,7 @@ struct cstark_ctx {
     size_t shard_bit37_words = 0;
     void *rb_dev = nullptr, *rb_host = nullptr; // cstark_range_prove_batch: one device block and one pinned host block, carved per call
     size_t rb_dev_bytes = 0, rb_host_bytes = 0;
-    void *sig_buf = nullptr; // cstark_schnorr_check_signatures: its inputs, scratch and outputs on the device (never the resident witness)
+    void *sig_buf = nullptr; // cstark_schnorr_check_signatures, cstark_schnorr_sign ...: inputs, scratch and outputs on the device (never the resident witness)
     size_t sig_bytes = 0;
     void *path_buf = nullptr; // cstark_account_check_paths (ledger.hip): its inputs and outputs on the device, likewise
     size_t path_bytes = 0;
@@ -227,6 +227,11 @@ struct cstark_ctx {
 // messages of ledger_plan.h).  `who` names the public call in the error text.
 int signature_check(cstark_ctx *c, const char *who, uint32_t count, const uint64_t *messages, const uint64_t *sig_rx, const uint8_t *sig_s,
                     uint8_t *verdicts, uint64_t *rx_out);
+// internal (capi.hip): cstark_schnorr_public_keys and cstark_schnorr_sign behind their argument checks (cstark_ledger_sign calls them with
+// the messages of ledger_plan.h).  sign_seeded leaves an exhausted signature's outputs zero and its status CSTARK_SIGN_EXHAUSTED.
+int sign_public_keys(cstark_ctx *c, uint32_t count, const uint64_t *secrets, uint64_t *keys_out);
+int sign_seeded(cstark_ctx *c, uint32_t count, const uint64_t *messages, const uint64_t *secrets, uint64_t seed, uint32_t max_attempts, uint64_t *sig_rx,
+                uint8_t *sig_s, uint32_t *attempts_out, uint8_t *status);
 // internal (capi.hip): the resident witness of n transfers at depth d, for cstark_tx_witness_upload and cstark_ledger_apply.  reserve: the
 // allocation (grown when needed; sz / off as witness_segments fills them); bind: the context's view, once the segments are written
 int tx_witness_reserve(cstark_ctx *c, size_t n, size_t d, size_t *sz, size_t *off);

@@ -1157,4 +1157,81 @@ int cstark_ledger_apply_checked(cstark_ctx *c, cstark_ledger *L, uint32_t n_tx, 
     return apply_entry(c, L, n_tx, s_indices, r_indices, deltas, sig_rx, sig_s, out, refused_at, reason, true);
 }
 
+// cstark_ledger_messages and cstark_ledger_sign: the walk of plan_apply on the index as it stands, for its messages and its refusal.  The
+// plan itself is dropped: nothing is reserved, launched or committed.
+static int messages_entry(cstark_ledger *L, const char *who, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices, const uint64_t *deltas,
+                          std::vector<uint64_t> &messages, int32_t *refused_at, int32_t *reason) {
+    for (uint32_t t = 0; t < n_tx; t++)
+        if (deltas[t] >= cs::host::P) return fail(CSTARK_ERR_INVALID_ARG, "%s: a delta is not a reduced field element", who);
+    uint64_t cap = L->capacity ? L->capacity : 1024;
+    while (cap < (uint64_t)L->index.n_stored + max_new_nodes(L->index.depth, 2 * (uint64_t)n_tx)) cap *= 2;
+    if (EMPTY_SLOTS + cap > MAX_POOL_SLOTS) return fail(CSTARK_ERR_UNSUPPORTED, "ledger: the batch needs more than 2^28 digest slots");
+    Plan p;
+    if (!plan_apply(L->index, (uint32_t)(EMPTY_SLOTS + cap), n_tx, s_indices, r_indices, deltas, p, &messages))
+        return fail(CSTARK_ERR_UNSUPPORTED, "%s: the batch is too large to plan", who);
+    *refused_at = p.refused_at;
+    *reason = p.reason;
+    return CSTARK_OK;
+}
+
+int cstark_ledger_messages(cstark_ctx *c, cstark_ledger *L, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices, const uint64_t *deltas,
+                           uint64_t *messages_out, int32_t *refused_at, int32_t *reason) {
+    RC_TRY(usable(c, L, "cstark_ledger_messages"));
+    if (n_tx == 0 || n_tx > MAX_TRANSFERS || !s_indices || !r_indices || !deltas || !messages_out || !refused_at || !reason)
+        return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_messages: bad argument");
+    std::vector<uint64_t> messages;
+    int32_t at, why;
+    RC_TRY(messages_entry(L, "cstark_ledger_messages", n_tx, s_indices, r_indices, deltas, messages, &at, &why));
+    *refused_at = at;
+    *reason = why;
+    if (at < 0) memcpy(messages_out, messages.data(), messages.size() * 8);
+    return CSTARK_OK;
+}
+
+int cstark_ledger_sign(cstark_ctx *c, cstark_ledger *L, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices, const uint64_t *deltas,
+                       const uint64_t *secrets, uint64_t seed, uint32_t max_attempts, uint64_t *sig_rx_out, uint8_t *sig_s_out, uint32_t *attempts_out,
+                       int32_t *refused_at, int32_t *reason) {
+    RC_TRY(usable(c, L, "cstark_ledger_sign"));
+    if (n_tx == 0 || n_tx > MAX_TRANSFERS || !s_indices || !r_indices || !deltas || !secrets || !sig_rx_out || !sig_s_out || !refused_at || !reason)
+        return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_sign: bad argument");
+    char text[96];
+    for (uint32_t t = 0; t < n_tx; t++)
+        if (secrets[t] == 0 || secrets[t] > CSTARK_SIG_MAX_SECRET) {
+            snprintf(text, sizeof text, "cstark_ledger_sign: secrets[%u] is not in 1 .. %u", t, CSTARK_SIG_MAX_SECRET);
+            return fail(CSTARK_ERR_INVALID_ARG, "%s", text);
+        }
+    if (max_attempts == 0 || max_attempts > 4096) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_sign: max_attempts must be 1 .. 4096");
+    std::vector<uint64_t> messages;
+    int32_t at, why;
+    RC_TRY(messages_entry(L, "cstark_ledger_sign", n_tx, s_indices, r_indices, deltas, messages, &at, &why));
+    // the secrets of the transfers the plan accepted against the senders' keys, all of them or those before its refusal
+    const uint32_t n_msg = (uint32_t)(messages.size() / 28);
+    if (n_msg) {
+        std::vector<uint64_t> keys((size_t)12 * n_msg);
+        RC_TRY(sign_public_keys(c, n_msg, secrets, keys.data()));
+        for (uint32_t t = 0; t < n_msg; t++)
+            if (memcmp(&keys[(size_t)12 * t], &messages[(size_t)28 * t], 96) != 0) {
+                *refused_at = (int32_t)t;
+                *reason = REASON_KEY;
+                return CSTARK_OK;
+            }
+    }
+    *refused_at = at;
+    *reason = why;
+    if (at >= 0) return CSTARK_OK;
+    std::vector<uint64_t> rx((size_t)6 * n_tx);
+    std::vector<uint8_t> s((size_t)32 * n_tx), status(n_tx);
+    std::vector<uint32_t> attempts(n_tx);
+    RC_TRY(sign_seeded(c, n_tx, messages.data(), secrets, seed, max_attempts, rx.data(), s.data(), attempts.data(), status.data()));
+    for (uint32_t t = 0; t < n_tx; t++)
+        if (status[t] != CSTARK_SIGN_OK) {
+            snprintf(text, sizeof text, "cstark_ledger_sign: transfer %u has no accepted attempt among %u", t, max_attempts);
+            return fail(CSTARK_ERR_UNSUPPORTED, "%s", text);
+        }
+    memcpy(sig_rx_out, rx.data(), rx.size() * 8);
+    memcpy(sig_s_out, s.data(), s.size());
+    if (attempts_out) memcpy(attempts_out, attempts.data(), attempts.size() * 4);
+    return CSTARK_OK;
+}
+
 } // extern "C"

@@ -53,7 +53,7 @@ struct Emit { uint32_t slot, word; };
 static_assert(sizeof(Job) == 16 && sizeof(Emit) == 8, "lists are copied to the device as they are");
 
 // cstark_ledger_reason (include/cstark.h)
-enum Reason : int32_t { REASON_NONE = 0, REASON_INDEX = 1, REASON_SELF = 2, REASON_ABSENT = 3, REASON_BALANCE = 4, REASON_SIGNATURE = 5, REASON_UNKNOWN = 6 };
+enum Reason : int32_t { REASON_NONE = 0, REASON_INDEX = 1, REASON_SELF = 2, REASON_ABSENT = 3, REASON_BALANCE = 4, REASON_SIGNATURE = 5, REASON_UNKNOWN = 6, REASON_KEY = 7 };
 
 typedef std::array<uint64_t, 14> Value; // pk.x(6) pk.y(6) balance nonce, memory form
 

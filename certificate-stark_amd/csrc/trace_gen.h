@@ -47,4 +47,22 @@ enum : uint8_t { SIG_VALID = 0, SIG_MISMATCH = 1, SIG_KEY_NOT_ON_CURVE = 2, SIG_
 hipError_t launch_signature_check(const uint64_t *d_messages, const uint64_t *d_sig_rx, const uint8_t *d_sig_s, uint64_t *d_h_limbs, uint64_t *d_points,
                                   uint8_t *d_verdicts, uint64_t *d_rx_out, uint32_t count, hipStream_t stream);
 
+// Signing (cstark_schnorr_sign ...).  The fixed-base table: SIGN_WINDOWS x 15 entries of 24 words, entry 15 w + d - 1 = the affine point
+// d * 16^w * G as (x, y, b3*x, b3*y) in memory form; launch_sign_table fills it (once per context).
+constexpr int SIGN_WINDOWS = 66; // base-16 digits of a nonce below 2^264
+constexpr size_t SIGN_TABLE_WORDS = (size_t)SIGN_WINDOWS * 15 * 24;
+enum : uint8_t { SIGN_OK = 0, SIGN_NEGATIVE = 1, SIGN_RANGE = 2, SIGN_INFINITY = 3 }; // the values of cstark_sign_status
+hipError_t launch_sign_table(uint64_t *d_table, hipStream_t stream);
+// r*G for `count` nonces ([count][5] little-endian limbs, r < 2^264), one wave each: d_points [count][12] affine (x, y), d_rx [count][6]
+// affine x (either may be null), d_infinity [count] = 1 where the point is the one at infinity (its coordinates are written as zeros)
+hipError_t launch_sign_points(const uint64_t *d_table, const uint64_t *d_nonces, uint64_t *d_points, uint64_t *d_rx, uint8_t *d_infinity, uint32_t count,
+                              hipStream_t stream);
+// one signing attempt per nonce: R = r*G -> d_rx, d_infinity; h = hash_message(R.x, message) by the check's own k_sig_hash -> d_h_limbs
+// [count][4]; d = r - sk*h -> d_sig_s [count][32] (bits 0..255 of d, 8-byte aligned) and d_status [count].  d_owner == null: attempt a
+// signs d_messages[a] with d_secrets[a]; otherwise it signs d_messages[d_owner[a]] with d_secrets[d_owner[a]], and d_gathered
+// [count][28] is scratch for the attempts' messages.
+hipError_t launch_sign_attempts(const uint64_t *d_table, const uint64_t *d_messages, const uint32_t *d_owner, uint64_t *d_gathered, const uint64_t *d_secrets,
+                                const uint64_t *d_nonces, uint64_t *d_rx, uint8_t *d_infinity, uint64_t *d_h_limbs, uint8_t *d_sig_s, uint8_t *d_status,
+                                uint32_t count, hipStream_t stream);
+
 } // namespace cs

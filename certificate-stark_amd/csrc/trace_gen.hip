@@ -910,4 +910,176 @@ hipError_t launch_signature_check(const uint64_t *d_messages, const uint64_t *d_
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Signing (cstark_schnorr_sign ...): schnorr::sign (src/schnorr/mod.rs:197-217) with the integer scalar step of csrc/witness_gen.hip,
+// s = r - sk*h accepted when 0 <= s < 2^255.  The base point of R = r*G is fixed, so a table T[w][d] = d * 16^w * G (w = 0..65,
+// d = 1..15) turns the 264-bit scalar multiplication into at most 66 mixed additions and no doubling: a sixth of the dependent point
+// operations of a 255-bit ladder, in a kernel whose time is the latency of that chain.  An entry is 24 words in memory form,
+// (x, y, K = b3*x, K2 = b3*y): the mixed addition's two per-point constants are stored with the point (190 KB for the 990 entries),
+// so that no F_p6 product by one lane sits between two additions.
+namespace {
+
+constexpr int SIGN_DIGITS = 15, SIGN_ENTRY = 24;
+static_assert(SIGN_TABLE_WORDS == (size_t)SIGN_WINDOWS * SIGN_DIGITS * SIGN_ENTRY, "the context allocates what the kernels index");
+static_assert(SK2 == SK + 1 && SPY == SPX + 1, "an entry is copied into two slot pairs");
+
+// One wave per entry, k_sig_ladder's shape with a variable bit length: the ladder programs over the 4 + 4w bits of d * 16^w, then one
+// fp6_inv for the affine x and y.  d >= 1 and d * 16^w < 2^264 is no multiple of the group order: Z != 0.
+__global__ __launch_bounds__(64) void k_sign_table(fp *__restrict__ table) {
+    if (blockIdx.x >= SIGN_WINDOWS * SIGN_DIGITS) return; // uniform over the workgroup, ahead of every barrier
+    __shared__ fp slots[NSLOT][6];
+    __shared__ Fp2 prods[LROLE][6];
+    __shared__ LadderLds pg;
+    const int w = blockIdx.x / SIGN_DIGITS, d = blockIdx.x % SIGN_DIGITS + 1, lane = threadIdx.x;
+    fp(*slot)[6] = slots;
+    load_programs(pg, lane, 64);
+    if (lane < 6) {
+        slot[SX][lane] = 0;
+        slot[SY][lane] = lane == 0 ? FP_ONE : 0;
+        slot[SZ][lane] = 0;
+        slot[SB3][lane] = c_b3[lane];
+        slot[SPX][lane] = c_generator[lane];
+        slot[SPY][lane] = c_generator[6 + lane];
+        slot[26][lane] = fp_add(slot[SPX][lane], slot[SPY][lane]);
+        slot[SW][lane] = 0;
+    }
+    __syncthreads();
+    if (lane < 2) fp6_store(slot[SK + lane], fp6_mul(fp6_load(slot[SB3]), fp6_load(slot[SPX + lane])));
+    __syncthreads();
+    for (int i = 4 * w + 3; i >= 0; i--) { // MSB first, as the trace's ladders
+        run_ladder_op<OP_DOUBLE>(pg, slot, prods, lane);
+        if (i >= 4 * w && ((d >> (i - 4 * w)) & 1)) run_ladder_op<OP_ADD_MIXED>(pg, slot, prods, lane); // uniform over the wave
+    }
+    if (lane != 0) return;
+    const Fp6 zi = fp6_inv(fp6_load(slots[SZ])), b3 = fp6_load(slots[SB3]);
+    const Fp6 x = fp6_mul(fp6_load(slots[SX]), zi), y = fp6_mul(fp6_load(slots[SY]), zi);
+    fp *e = table + (size_t)SIGN_ENTRY * blockIdx.x;
+    fp6_store(e, x);
+    fp6_store(e + 6, y);
+    fp6_store(e + 12, fp6_mul(b3, x));
+    fp6_store(e + 18, fp6_mul(b3, y));
+}
+
+// One wave per nonce: acc = (0 : 1 : 0), then acc += T[w][digit_w(r)] for every non-zero base-16 digit of r (uniform over the wave).
+// The mixed addition is the reference's complete formula (compute_add_mixed, src/utils/ecc.rs:330-404), valid for every pair of
+// points: the partial sum meeting an equal table point, its negative, or the identity the sum starts from needs no special case.
+// The next entry is fetched into registers while the current addition runs.  nonces [n][5] little-endian limbs, r < 2^264.
+// points (optional) [n][12] affine (x, y), rx (optional) [n][6] affine x, infinity [n]: 1 where r*G is the point at infinity, whose
+// coordinates are written as zeros.
+__global__ __launch_bounds__(64) void k_sign_comb(const fp *__restrict__ table, const uint64_t *__restrict__ nonces, fp *__restrict__ points,
+                                                  fp *__restrict__ rx, uint8_t *__restrict__ infinity, uint32_t n) {
+    if (blockIdx.x >= n) return; // uniform over the workgroup, ahead of every barrier
+    __builtin_amdgcn_s_setprio(CS_RECUR_PRIO);
+    __shared__ fp slots[NSLOT][6];
+    __shared__ Fp2 prods[LROLE][6];
+    __shared__ uint8_t dig[SIGN_WINDOWS + 1];
+    __shared__ LadderLds pg;
+    const uint32_t t = blockIdx.x;
+    const int lane = threadIdx.x;
+    fp(*slot)[6] = slots;
+    load_programs(pg, lane, 64);
+    if (lane < 6) {
+        slot[SX][lane] = 0;
+        slot[SY][lane] = lane == 0 ? FP_ONE : 0;
+        slot[SZ][lane] = 0;
+        slot[SB3][lane] = c_b3[lane];
+        slot[SW][lane] = 0;
+    }
+    for (int w = lane; w <= SIGN_WINDOWS; w += 64) dig[w] = w < SIGN_WINDOWS ? (uint8_t)((nonces[5 * (size_t)t + w / 16] >> (4 * (w % 16))) & 15) : 0;
+    __syncthreads();
+    // lanes 0..23 carry the entry's words into slots SPX, SPY, SK, SK2; lanes 24..29 the operand qx + qy (slot 26)
+    const int part = lane / 6, word = lane % 6;
+    const int dst = part < 2 ? SPX + part : part < 4 ? SK + part - 2 : 26;
+    auto fetch = [&](int w, int d) -> fp {
+        const fp *e = table + (size_t)SIGN_ENTRY * (SIGN_DIGITS * w + d - 1);
+        return lane < 24 ? e[lane] : lane < 30 ? fp_add(e[word], e[6 + word]) : 0;
+    };
+    fp next = dig[0] ? fetch(0, dig[0]) : 0;
+    for (int w = 0; w < SIGN_WINDOWS; w++) {
+        const int d = dig[w], dn = dig[w + 1];
+        const fp cur = next;
+        if (dn) next = fetch(w + 1, dn);
+        if (d) {
+            if (lane < 30) slot[dst][word] = cur;
+            __syncthreads();
+            run_ladder_op<OP_ADD_MIXED>(pg, slot, prods, lane);
+        }
+    }
+    if (lane != 0) return;
+    const Fp6 z = fp6_load(slots[SZ]);
+    bool finite = false;
+#pragma unroll
+    for (int i = 0; i < 6; i++) finite |= z.c[i] != 0;
+    Fp6 x = {}, y = {};
+    if (finite) { // Z = 0 is tested before anything uses fp6_inv(0)
+        const Fp6 zi = fp6_inv(z);
+        x = fp6_mul(fp6_load(slots[SX]), zi);
+        y = fp6_mul(fp6_load(slots[SY]), zi);
+    }
+    if (points) {
+        fp6_store(points + 12 * (size_t)t, x);
+        fp6_store(points + 12 * (size_t)t + 6, y);
+    }
+    if (rx) fp6_store(rx + 6 * (size_t)t, x);
+    infinity[t] = finite ? 0 : 1;
+}
+
+// the message of attempt a is that of the signature it belongs to: [count][28] gathered through owner [count]
+__global__ __launch_bounds__(256) void k_sign_gather(const fp *__restrict__ messages, const uint32_t *__restrict__ owner, fp *__restrict__ out, uint32_t count) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)28 * count) return;
+    out[i] = messages[28 * (size_t)owner[i / 28] + i % 28];
+}
+
+// One thread per attempt: the 320-bit two's-complement d = r - sk*h in five limbs (64 x 64 -> 128 products), sig_s = bits 0..255 of d
+// whatever the status (the values of cstark_sign_status).  h: four canonical limbs, each below p; sk <= 255; r < 2^264: no limb is lost.
+// owner (optional): the signature an attempt belongs to, whose secret it uses; null: attempt a uses secrets[a].
+__global__ __launch_bounds__(256) void k_sign_scalar(const uint64_t *__restrict__ nonces, const uint64_t *__restrict__ secrets, const uint32_t *__restrict__ owner,
+                                                     const uint64_t *__restrict__ h_limbs, const uint8_t *__restrict__ infinity, uint64_t *__restrict__ sig_s,
+                                                     uint8_t *__restrict__ status, uint32_t count) {
+    typedef unsigned __int128 u128;
+    const size_t a = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (a >= count) return;
+    const uint64_t sk = secrets[owner ? owner[a] : a];
+    uint64_t skh[5], d[5];
+    u128 c = 0;
+    for (int i = 0; i < 4; i++) { c += (u128)h_limbs[4 * a + i] * sk; skh[i] = (uint64_t)c; c >>= 64; }
+    skh[4] = (uint64_t)c;
+    uint64_t borrow = 0;
+    for (int i = 0; i < 5; i++) {
+        const u128 x = (u128)nonces[5 * a + i] - skh[i] - borrow;
+        d[i] = (uint64_t)x;
+        borrow = (uint64_t)(x >> 64) & 1;
+    }
+    for (int i = 0; i < 4; i++) sig_s[4 * a + i] = d[i];
+    status[a] = infinity[a] ? SIGN_INFINITY : borrow ? SIGN_NEGATIVE : (d[4] != 0 || (d[3] >> 63)) ? SIGN_RANGE : SIGN_OK;
+}
+
+} // namespace
+
+hipError_t launch_sign_table(uint64_t *d_table, hipStream_t stream) {
+    hipLaunchKernelGGL(k_sign_table, dim3(SIGN_WINDOWS * SIGN_DIGITS), dim3(64), 0, stream, d_table);
+    return hipGetLastError();
+}
+
+hipError_t launch_sign_points(const uint64_t *d_table, const uint64_t *d_nonces, uint64_t *d_points, uint64_t *d_rx, uint8_t *d_infinity, uint32_t count,
+                              hipStream_t stream) {
+    hipLaunchKernelGGL(k_sign_comb, dim3(count), dim3(64), 0, stream, (const fp *)d_table, d_nonces, d_points, d_rx, d_infinity, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_sign_attempts(const uint64_t *d_table, const uint64_t *d_messages, const uint32_t *d_owner, uint64_t *d_gathered, const uint64_t *d_secrets,
+                                const uint64_t *d_nonces, uint64_t *d_rx, uint8_t *d_infinity, uint64_t *d_h_limbs, uint8_t *d_sig_s, uint8_t *d_status,
+                                uint32_t count, hipStream_t stream) {
+    hipLaunchKernelGGL(k_sign_comb, dim3(count), dim3(64), 0, stream, (const fp *)d_table, d_nonces, (fp *)nullptr, d_rx, d_infinity, count);
+    if (d_owner) {
+        hipLaunchKernelGGL(k_sign_gather, dim3((unsigned)(((size_t)28 * count + 255) / 256)), dim3(256), 0, stream, d_messages, d_owner, d_gathered, count);
+        d_messages = d_gathered;
+    }
+    hipLaunchKernelGGL(k_sig_hash, dim3((count + 3) / 4), dim3(64), 0, stream, d_messages, (const fp *)d_rx, d_h_limbs, count);
+    hipLaunchKernelGGL(k_sign_scalar, dim3((count + 255) / 256), dim3(256), 0, stream, d_nonces, d_secrets, d_owner, (const uint64_t *)d_h_limbs,
+                       (const uint8_t *)d_infinity, (uint64_t *)d_sig_s, d_status, count);
+    return hipGetLastError();
+}
+
 } // namespace cs

@@ -189,9 +189,10 @@ class Ledger:
     """The account tree an operator holds, resident on the GPU (cstark_ledger_*): set_accounts, then apply(transfers) per batch -- the
     counterpart of the sequential loop of TransactionMetadata::build_random (src/lib.rs:341-422) on real accounts and transfers.
     apply() leaves the batch's witness resident in the backend: backend.prove(options) follows without an upload."""
-    INDEX_RANGE, SELF_TRANSFER, ABSENT, BALANCE, SIGNATURE, UNKNOWN = 1, 2, 3, 4, 5, 6
+    INDEX_RANGE, SELF_TRANSFER, ABSENT, BALANCE, SIGNATURE, UNKNOWN, KEY = 1, 2, 3, 4, 5, 6, 7
     REASONS = {1: "index out of range", 2: "sender equals receiver", 3: "account absent", 4: "delta above the sender's balance",
-               5: "signature does not verify", 6: "account not among those a partial ledger knows"}
+               5: "signature does not verify", 6: "account not among those a partial ledger knows",
+               7: "secret is not the secret of the sender's public key"}
 
     def __init__(self, depth=15, backend=None):
         self.backend = backend or Backend()
@@ -317,6 +318,38 @@ class Ledger:
         if at >= 0:
             raise TransferRefused(at, reason)
         return None if arrays is None else TransactionMetadata(*[arrays[f] for f in TransactionMetadata.FIELDS])
+
+    @staticmethod
+    def _unsigned(transfers):
+        if hasattr(transfers, "s_indices"):
+            return tuple(getattr(transfers, f) for f in ("s_indices", "r_indices", "deltas"))
+        return tuple(transfers[:3])
+
+    def messages(self, transfers):
+        """-> uint64 [n][28]: the message each transfer of the batch has to sign (sender's key, receiver's key, delta, the sender's
+        nonce as the transfers before it leave it, two zeros).  transfers: (s_indices, r_indices, deltas, ...) or an object with these
+        attributes.  Raises TransferRefused where apply() would, with its reason.  Read-only."""
+        at, reason, out = self.backend.ledger_messages(self._led, *self._unsigned(transfers))
+        if at >= 0:
+            raise TransferRefused(at, reason)
+        return out
+
+    def sign(self, transfers, secrets, seed=0, max_attempts=256):
+        """-> (s_indices, r_indices, deltas, sig_rx, sig_s), exactly what apply() takes: the batch signed on the device with the senders'
+        secret keys (secrets[t] signs transfer t).  Raises TransferRefused where apply() would, with its reason, or with reason KEY at
+        the first transfer whose secret is not the secret of its sender's public key.  Read-only.  Secrets are small integers,
+        1 .. 255 (public_keys): a signer for building batches, tests and benchmarks.  It is not a wallet."""
+        s, r, d = (np.ascontiguousarray(a, np.uint64).reshape(-1) for a in self._unsigned(transfers))
+        at, reason, rx, ss, _ = self.backend.ledger_sign(self._led, s, r, d, secrets, seed=seed, max_attempts=max_attempts)
+        if at >= 0:
+            raise TransferRefused(at, reason)
+        return s, r, d, rx, ss
+
+
+def public_keys(secrets, backend=None):
+    """-> uint64 [count][12]: secrets[i] * G, the public key (x, y in memory form) of each secret in 1 .. 255, computed on the device:
+    words 0..11 of an account of Ledger.set_accounts."""
+    return (backend or Backend()).schnorr_public_keys(secrets)
 
 
 class TransactionProver:
@@ -504,6 +537,22 @@ class SchnorrExample(_ResidentWitness):
         _lib.check(_lib.load().cstark_schnorr_witness_generate(C.c_uint32(n), C.c_uint64(seed), msg.ctypes.data_as(_lib.u64p),
                                                                rx.ctypes.data_as(_lib.u64p), s.ctypes.data_as(_lib.u8p)))
         return cls(options, msg, rx, s, backend)
+
+    @classmethod
+    def sign(cls, secrets, payloads, seed=0, options=None, backend=None, max_attempts=256):
+        """An example over chosen signers and payloads: message i = public key of secrets[i] || payloads[i] (16 words in memory form),
+        as src/schnorr/mod.rs:94-99, keys and signatures made on the device (Backend.schnorr_public_keys, schnorr_sign).  Secrets are
+        small integers, 1 .. 255: a signer for building batches, tests and benchmarks.  It is not a wallet.  Raises ValueError when a
+        signature found no accepted attempt among max_attempts."""
+        backend = backend or Backend()
+        sk = np.ascontiguousarray(secrets, np.uint64).reshape(-1)
+        messages = np.zeros((sk.size, 28), np.uint64)
+        messages[:, 12:] = np.ascontiguousarray(payloads, np.uint64).reshape(sk.size, 16)
+        messages[:, :12] = backend.schnorr_public_keys(sk)
+        rx, s, _, status = backend.schnorr_sign(messages, sk, seed=seed, max_attempts=max_attempts)
+        if status.any():
+            raise ValueError("signature %d found no accepted attempt among %d" % (int(np.flatnonzero(status)[0]), max_attempts))
+        return cls(options or get_example_options(), messages, rx, s, backend)
 
     def _witness_arrays(self):
         return [self.messages, self.sig_rx, self.sig_s]

@@ -454,6 +454,47 @@ typedef enum cstark_sig_verdict {
 int cstark_schnorr_check_signatures(cstark_ctx *ctx, uint32_t count, const uint64_t *messages, const uint64_t *sig_rx,
                                     const uint8_t *sig_s, uint8_t *verdicts, uint64_t *rx_out);
 
+/* ---- signing: schnorr::sign (src/schnorr/mod.rs:197-217) and generator() * skey (mod.rs:92) on the device -------------
+ * The scheme is the one of cstark_tx_witness_generate (csrc/witness_gen.hip), callable with chosen inputs.  The order of the curve's
+ * scalar field is stated nowhere in the reference tree, so signatures use integer arithmetic: R = r*G, h = hash_message(R.x, message)
+ * read as a 4-limb integer, s = r - sk*h, accepted when 0 <= s < 2^255; then s*G + h*(sk*G) = R holds in the group whatever its order.
+ * This forces rejection sampling: an attempt is accepted with probability about 2 / (sk + 2), so secret keys are small integers,
+ * 1 .. CSTARK_SIG_MAX_SECRET.  With such keys this is a signer for building batches, tests and benchmarks.  It is not a wallet.
+ * r*G and sk*G are sums of entries of a table of multiples of G (d * 16^w * G, built on the device by the context's first signing call
+ * and kept by it): at most 66 complete mixed additions and no doubling.
+ * Misuse of the three calls -- a null pointer (attempts_out may be null), count == 0, count > 2^20, a secret of 0 or above the
+ * maximum, a nonce >= 2^264, a message word >= p, max_attempts outside 1 .. 4096 -- is CSTARK_ERR_INVALID_ARG before anything is
+ * launched and with the outputs untouched; cstark_last_error names the first offender.  The calls are synchronous, on the context's
+ * stream, in the device scratch of cstark_schnorr_check_signatures, which the context keeps and frees (nothing stays in it between
+ * calls): the resident witness is neither read nor written, so a proof after a signing call is the proof without it.  All arrays are
+ * host memory. */
+#define CSTARK_SIG_MAX_SECRET 255u
+/* the status of one signing attempt.  INFINITY is tested first, then NEGATIVE, then RANGE (the latter two exclude each other). */
+typedef enum cstark_sign_status {
+    CSTARK_SIGN_OK = 0,
+    CSTARK_SIGN_NEGATIVE = 1,   /* r < sk*h */
+    CSTARK_SIGN_RANGE = 2,      /* r - sk*h >= 2^255 */
+    CSTARK_SIGN_INFINITY = 3,   /* r*G is the point at infinity (r = 0, or a multiple of the group order) */
+    CSTARK_SIGN_EXHAUSTED = 4   /* cstark_schnorr_sign only: no accepted attempt among max_attempts */
+} cstark_sign_status;
+/* keys_out [count][12] = secrets[i] * G, affine (x, y) in memory form: what an account of cstark_ledger_set_accounts holds in words
+ * 0..11 and a Schnorr message in words 0..11. */
+int cstark_schnorr_public_keys(cstark_ctx *ctx, uint32_t count, const uint64_t *secrets, uint64_t *keys_out);
+/* One attempt per entry with the caller's nonce: nonces [count][5] little-endian limbs, r < 2^264.  Every output is defined whatever
+ * the status: sig_rx [count][6] = x(r*G), all zero on INFINITY; sig_s [count][32] = bits 0..255 of r - sk*h, little-endian; status
+ * [count] (cstark_sign_status).  The key inside the message (words 0..11) is hashed as given and not compared with sk*G: a signature
+ * over a message with someone else's key is simply one that cstark_schnorr_check_signatures calls MISMATCH. */
+int cstark_schnorr_sign_nonces(cstark_ctx *ctx, uint32_t count, const uint64_t *messages, const uint64_t *secrets, const uint64_t *nonces,
+                               uint64_t *sig_rx, uint8_t *sig_s, uint8_t *status);
+/* The seeded signer.  Signature t has a SplitMix64 stream of its own, state seed ^ (0xD1B54A32D192ED03 * (t + 1)); attempt a = 0, 1, 2 ...
+ * draws five outputs from it (r[0..3], then hi = next % (sk + 2); r[3] &= 2^62 - 1; hi << 62 is added into limbs 3 and 4: r uniform in
+ * [0, (sk + 2) * 2^254)), exactly as the host signer of cstark_tx_witness_generate.  The result of signature t is that of its first
+ * attempt whose status is OK, and attempts_out[t] (optional) = a + 1; how many attempts run together on the device does not show in it.
+ * Without an OK attempt below max_attempts (1 .. 4096): status CSTARK_SIGN_EXHAUSTED, zero sig_rx and sig_s, attempts_out[t] =
+ * max_attempts.  status [count]: CSTARK_SIGN_OK or CSTARK_SIGN_EXHAUSTED. */
+int cstark_schnorr_sign(cstark_ctx *ctx, uint32_t count, const uint64_t *messages, const uint64_t *secrets, uint64_t seed,
+                        uint32_t max_attempts, uint64_t *sig_rx, uint8_t *sig_s, uint32_t *attempts_out, uint8_t *status);
+
 /* ---- account ledger: the witness from what an operator holds (replaces the sequential loop of TransactionMetadata::build_random,
  * src/lib.rs:341-422: record the root and the sender's path, apply the transfer, re-hash two leaf-to-root paths, record the receiver's
  * path) ------------------------------------------------------------------------------------------------------------------------------
@@ -476,8 +517,9 @@ typedef enum cstark_ledger_reason {
     CSTARK_LEDGER_ABSENT = 3,       /* sender or receiver has no account */
     CSTARK_LEDGER_BALANCE = 4,      /* delta above the sender's balance, both as canonical integers */
     CSTARK_LEDGER_SIGNATURE = 5,    /* cstark_ledger_apply_checked only: the transfer's signature has another verdict than CSTARK_SIG_VALID */
-    CSTARK_LEDGER_UNKNOWN = 6       /* a partial ledger only: sender or receiver is not among the accounts it knows; tested after the self
+    CSTARK_LEDGER_UNKNOWN = 6,      /* a partial ledger only: sender or receiver is not among the accounts it knows; tested after the self
                                        transfer and before absence (index range, self transfer, unknown, absent, balance, signature) */
+    CSTARK_LEDGER_KEY = 7           /* cstark_ledger_sign only: the transfer's secret is not the secret of its sender's public key */
 } cstark_ledger_reason;
 /* An empty tree of depth 1, 3, 7, 15 or 31 (the depths cstark_tx_witness_upload accepts).  Destroy it before its context. */
 int cstark_ledger_create(cstark_ctx *ctx, uint32_t merkle_depth, cstark_ledger **out);
@@ -549,6 +591,24 @@ int cstark_ledger_apply(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t n_tx, c
 int cstark_ledger_apply_checked(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices,
                                 const uint64_t *deltas, const uint64_t *sig_rx, const uint8_t *sig_s, cstark_tx_witness *out,
                                 int32_t *refused_at, int32_t *reason);
+/* The message each transfer of a batch has to sign (build_tx_message, as above): messages_out [n_tx][28].  The walk is the one
+ * cstark_ledger_apply makes, run read-only: the call refuses exactly where cstark_ledger_apply would, with the same reason
+ * (CSTARK_LEDGER_UNKNOWN on a partial ledger included), and then messages_out is not written.  Root, pool, host index, checkpoints and
+ * the resident witness are unchanged whatever the outcome; nothing is launched. */
+int cstark_ledger_messages(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices,
+                           const uint64_t *deltas, uint64_t *messages_out, int32_t *refused_at, int32_t *reason);
+/* Signs a batch for cstark_ledger_apply_checked: the messages of cstark_ledger_messages, then cstark_schnorr_sign with secrets [n_tx]
+ * (the sender's secret key of every transfer, 1 .. CSTARK_SIG_MAX_SECRET), seed and max_attempts (its misuse rules apply).  Before
+ * anything is signed every secret's public key is derived on the device and compared with the sender's key in the message: the first
+ * transfer whose secret is not its sender's key refuses the batch with CSTARK_LEDGER_KEY.  Within a transfer that reason comes after
+ * the plan's: a batch whose first unappliable transfer is k is refused at the first transfer below k with a wrong secret, else at k with
+ * its own reason.  A refused batch writes none of the outputs.  sig_rx_out [n_tx][6], sig_s_out [n_tx][32], attempts_out (optional)
+ * [n_tx].  A signature without an accepted attempt among max_attempts is CSTARK_ERR_UNSUPPORTED, and cstark_last_error names the
+ * transfer.  The call is read-only: root, pool, host index, checkpoints and the resident witness are unchanged.  This signs with small
+ * integer keys (see "signing" above): a signer for building batches, tests and benchmarks.  It is not a wallet. */
+int cstark_ledger_sign(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices,
+                       const uint64_t *deltas, const uint64_t *secrets, uint64_t seed, uint32_t max_attempts, uint64_t *sig_rx_out,
+                       uint8_t *sig_s_out, uint32_t *attempts_out, int32_t *refused_at, int32_t *reason);
 
 /* ---- ledger checkpoints: take a batch back, open accounts under a past root, audit the resident tree -----------------------------
  * A checkpoint names the ledger's state at the moment it is taken.  Old states are kept by not overwriting them: while a checkpoint is

@@ -406,6 +406,33 @@ class Ledger {
     // the same with every transfer's signature checked on the device first (cstark_ledger_apply_checked): TransferRefused with reason
     // CSTARK_LEDGER_SIGNATURE at the first transfer whose signature does not verify
     TransactionMetadata apply_checked(const Transfers &t) { return apply(t, true); }
+    // the message each transfer of the batch has to sign, [n][28] (cstark_ledger_messages; sig_rx and sig_s of `t` are not read): throws
+    // TransferRefused where apply would, with its reason.  Read-only
+    std::vector<std::array<BaseElement, 28>> messages(const Transfers &t) const {
+        const size_t n = t.s_indices.size();
+        if (n == 0 || t.r_indices.size() != n || t.deltas.size() != n) throw Error(CSTARK_ERR_INVALID_ARG, "transfer vectors are not of equal length");
+        std::vector<std::array<BaseElement, 28>> out(n);
+        int32_t at = -1, reason = 0;
+        check(cstark_ledger_messages(ctx_.raw(), led_, (uint32_t)n, t.s_indices.data(), t.r_indices.data(), t.deltas.data(), out[0].data(), &at, &reason));
+        if (at >= 0) throw TransferRefused(at, reason);
+        return out;
+    }
+    // the batch signed on the device with the senders' secret keys (cstark_ledger_sign; secrets[t] signs transfer t, 1 .. 255): what
+    // apply_checked takes.  Throws TransferRefused where apply would, or with CSTARK_LEDGER_KEY at the first transfer whose secret is not
+    // its sender's key.  Read-only.  A signer for building batches, tests and benchmarks.  It is not a wallet.
+    Transfers sign(const Transfers &t, const std::vector<uint64_t> &secrets, uint64_t seed = 0, uint32_t max_attempts = 256) const {
+        const size_t n = t.s_indices.size();
+        if (n == 0 || t.r_indices.size() != n || t.deltas.size() != n || secrets.size() != n)
+            throw Error(CSTARK_ERR_INVALID_ARG, "transfer vectors are not of equal length");
+        Transfers out{t.s_indices, t.r_indices, t.deltas, {}, {}};
+        out.sig_rx.resize(n);
+        out.sig_s.resize(n);
+        int32_t at = -1, reason = 0;
+        check(cstark_ledger_sign(ctx_.raw(), led_, (uint32_t)n, t.s_indices.data(), t.r_indices.data(), t.deltas.data(), secrets.data(), seed, max_attempts,
+                                 out.sig_rx[0].data(), out.sig_s[0].data(), nullptr, &at, &reason));
+        if (at >= 0) throw TransferRefused(at, reason);
+        return out;
+    }
 
   private:
     Ledger(Context &ctx, unsigned depth, cstark_ledger *led) : ctx_(ctx), depth_(depth), led_(led) {}
@@ -768,6 +795,41 @@ inline std::vector<uint8_t> schnorr_check(Context &ctx, const std::vector<BaseEl
     check(cstark_schnorr_check_signatures(ctx.raw(), (uint32_t)n, messages.data(), sig_rx.data(), sig_s.data(), verdicts.data(),
                                           rx_out ? rx_out->data() : nullptr));
     return verdicts;
+}
+// ---- signing with small integer keys, 1 .. CSTARK_SIG_MAX_SECRET (see "signing" in cstark.h): a signer for building batches, tests and
+// benchmarks.  It is not a wallet.
+// secrets[i] * G -> [n][12] affine (x, y): words 0..11 of an account and of a Schnorr message
+inline std::vector<std::array<BaseElement, 12>> schnorr_public_keys(Context &ctx, const std::vector<uint64_t> &secrets) {
+    if (secrets.empty()) throw Error(CSTARK_ERR_INVALID_ARG, "no secret");
+    std::vector<std::array<BaseElement, 12>> keys(secrets.size());
+    check(cstark_schnorr_public_keys(ctx.raw(), (uint32_t)secrets.size(), secrets.data(), keys[0].data()));
+    return keys;
+}
+struct Signatures {
+    std::vector<BaseElement> sig_rx;  // [n][6]
+    std::vector<uint8_t> sig_s;       // [n][32]
+    std::vector<uint8_t> status;      // [n] cstark_sign_status
+    std::vector<uint32_t> attempts;   // [n], schnorr_sign only: index of the accepted attempt + 1
+};
+// one attempt per message with the caller's nonce ([n][5] little-endian limbs, below 2^264); every output is defined whatever the status
+inline Signatures schnorr_sign_nonces(Context &ctx, const std::vector<BaseElement> &messages, const std::vector<uint64_t> &secrets,
+                                      const std::vector<uint64_t> &nonces) {
+    const size_t n = secrets.size();
+    if (n == 0 || messages.size() != 28 * n || nonces.size() != 5 * n) throw Error(CSTARK_ERR_INVALID_ARG, "signing vectors are not of equal length");
+    Signatures s{std::vector<BaseElement>(6 * n), std::vector<uint8_t>(32 * n), std::vector<uint8_t>(n), {}};
+    check(cstark_schnorr_sign_nonces(ctx.raw(), (uint32_t)n, messages.data(), secrets.data(), nonces.data(), s.sig_rx.data(), s.sig_s.data(), s.status.data()));
+    return s;
+}
+// the seeded signer: the first accepted attempt of every signature's own nonce stream; status CSTARK_SIGN_EXHAUSTED (zero outputs)
+// where none of max_attempts is accepted
+inline Signatures schnorr_sign(Context &ctx, const std::vector<BaseElement> &messages, const std::vector<uint64_t> &secrets, uint64_t seed = 0,
+                               uint32_t max_attempts = 256) {
+    const size_t n = secrets.size();
+    if (n == 0 || messages.size() != 28 * n) throw Error(CSTARK_ERR_INVALID_ARG, "signing vectors are not of equal length");
+    Signatures s{std::vector<BaseElement>(6 * n), std::vector<uint8_t>(32 * n), std::vector<uint8_t>(n), std::vector<uint32_t>(n)};
+    check(cstark_schnorr_sign(ctx.raw(), (uint32_t)n, messages.data(), secrets.data(), seed, max_attempts, s.sig_rx.data(), s.sig_s.data(), s.attempts.data(),
+                              s.status.data()));
+    return s;
 }
 // schnorr::SchnorrExample (src/schnorr/mod.rs:52-186)
 class SchnorrExample {
