@@ -5,6 +5,6 @@ plumbing on torch tensors/streams), prover.py (host-side mirror of the reference
 """
 from . import _lib  # noqa: F401
 from ._lib import CstarkError  # noqa: F401
-from .verify import VERDICTS, VerifierError, inspect_proof  # noqa: F401
+from .verify import VERDICTS, VerifierError, inspect_proof, proof_form  # noqa: F401
 
-__all__ = ["_lib", "CstarkError", "VERDICTS", "VerifierError", "inspect_proof"]
+__all__ = ["_lib", "CstarkError", "VERDICTS", "VerifierError", "inspect_proof", "proof_form"]

@@ -1000,6 +1000,22 @@ class Backend:
         check(self.lib.cstark_prove_stage_ms(self.ctx, ms))
         return dict(zip(self.PROVE_STAGES, [float(v) for v in ms]))
 
+    PROOF_FORMS = ("plain", "compact")
+
+    @property
+    def proof_form(self):
+        """cstark_ctx_proof_form / cstark_ctx_set_proof_form: "plain" (the default: one authentication path per opened row) or "compact"
+        (one Merkle multiproof per tree) -- the form every single-GPU prover of this backend writes; the sharded phases refuse "compact"."""
+        f = C.c_uint32(0)
+        check(self.lib.cstark_ctx_proof_form(self.ctx, C.byref(f)))
+        return self.PROOF_FORMS[f.value]
+
+    @proof_form.setter
+    def proof_form(self, form):
+        if form not in self.PROOF_FORMS:
+            raise ValueError("proof_form is 'plain' or 'compact', not %r" % (form,))
+        check(self.lib.cstark_ctx_set_proof_form(self.ctx, C.c_uint32(self.PROOF_FORMS.index(form))))
+
     def prove_channel(self):
         """cstark_prove_channel: "device" when the Fiat-Shamir channel of the last proof ran on the GPU (the host waited once), "host" when
         the host absorbed and drew between the stages (Sha3 coin, proof of work, sharded proofs, CSTARK_HOST_CHANNEL=1)"""

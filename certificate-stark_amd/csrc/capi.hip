@@ -68,6 +68,15 @@ void sign_table_release(const cstark_ctx *c) {
     g_sign_tables.erase(it);
 }
 
+// The proof form of the contexts that were set to another than CSTARK_FORM_PLAIN (cstark_ctx_set_proof_form), by the context's address
+// like the table above; the entry goes with the context.  One word that only its setter writes: no prover, verifier or ledger call
+// reads or changes anything else by it, and no call but the setter changes it.
+std::unordered_map<const cstark_ctx *, uint32_t> &g_proof_forms = *new std::unordered_map<const cstark_ctx *, uint32_t>;
+void proof_form_release(const cstark_ctx *c) {
+    std::lock_guard<std::mutex> hold(g_sign_tables_lock);
+    g_proof_forms.erase(c);
+}
+
 int get_plan(cstark_ctx *c, unsigned log_n, const NttPlan **out) {
     for (const NttPlan &p : c->plans)
         if (p.log_n == log_n) { *out = &p; return CSTARK_OK; }
@@ -130,6 +139,11 @@ int ensure_ws(cstark_ctx *c, size_t bytes) {
 }
 
 } // namespace
+uint32_t cs::ctx_proof_form(const cstark_ctx *c) {
+    std::lock_guard<std::mutex> hold(g_sign_tables_lock);
+    const auto it = g_proof_forms.find(c);
+    return it == g_proof_forms.end() ? (uint32_t)CSTARK_FORM_PLAIN : it->second;
+}
 int plan_tables(cstark_ctx *c, unsigned log_n, const uint64_t **w, const uint64_t **winv) {
     const NttPlan *p;
     RC_TRY(get_plan(c, log_n, &p));
@@ -578,6 +592,7 @@ void cstark_ctx_destroy(cstark_ctx *c) {
     if (c->tail_buf) (void)hipFree(c->tail_buf);
     if (c->sig_buf) (void)hipFree(c->sig_buf);
     sign_table_release(c);
+    proof_form_release(c);
     if (c->path_buf) (void)hipFree(c->path_buf);
     if (c->multi_buf) (void)hipFree(c->multi_buf);
     for (cs::RawPeriodic &t : c->raw_periodic) (void)hipFree(t.tab);
@@ -588,6 +603,20 @@ void cstark_ctx_destroy(cstark_ctx *c) {
     for (hipEvent_t e : c->lde_ev) (void)hipEventDestroy(e);
     if (c->owns_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
+}
+
+int cstark_ctx_set_proof_form(cstark_ctx *c, uint32_t form) {
+    if (!c) return fail(CSTARK_ERR_INVALID_ARG, "null context");
+    if (form != CSTARK_FORM_PLAIN && form != CSTARK_FORM_COMPACT) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ctx_set_proof_form: CSTARK_FORM_PLAIN or CSTARK_FORM_COMPACT");
+    std::lock_guard<std::mutex> hold(g_sign_tables_lock);
+    if (form == CSTARK_FORM_PLAIN) g_proof_forms.erase(c);
+    else g_proof_forms[c] = form;
+    return CSTARK_OK;
+}
+int cstark_ctx_proof_form(cstark_ctx *c, uint32_t *form) {
+    if (!c || !form) return fail(CSTARK_ERR_INVALID_ARG, "null argument");
+    *form = cs::ctx_proof_form(c);
+    return CSTARK_OK;
 }
 
 int cstark_ctx_synchronize(cstark_ctx *c) {

@@ -156,6 +156,8 @@ struct AirStageRequest {
 };
 struct ProveArena; // prove.hip
 void prove_arena_free(ProveArena *a);
+// CSTARK_FORM_*: the form the context's single-GPU provers write (cstark_ctx_set_proof_form, capi.hip; CSTARK_FORM_PLAIN unless set)
+uint32_t ctx_proof_form(const cstark_ctx *c);
 struct VerifyArena; // verify.hip: the verifier's staging and scratch (never shared with the prover's buffers)
 void verify_arena_free(VerifyArena *a);
 

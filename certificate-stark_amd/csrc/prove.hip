@@ -370,23 +370,24 @@ struct OpenSrc {
     const uint64_t *clde; uint64_t *const *layer; unsigned log_s;
     const uint32_t *counts, *dcount;
     const uint64_t *shard_rows; uint32_t shard_lvl0;
+    const uint32_t *pos = nullptr; // the positions, 256 slots per layer (null: a->d_pos)
 };
 // Gathers into d_block at the offsets O (positions: a->d_pos, 256 slots per layer) and enqueues the copy of d_block[0, O.bytes) to a->h_open.
 int open_stage(cstark_ctx *c, ProveArena *a, const ProofShape &S, const OpenSrc &src, uint8_t *d_block, const OpenBlock &O) {
     hipStream_t st = c->stream;
-    const uint32_t nq = S.nq, W = S.width;
+    const uint32_t nq = S.nq, W = S.width, *d_pos = src.pos ? src.pos : a->d_pos;
     GatherList gl;
     uint32_t trace_lvl0 = 0;
     if (src.shard_rows) { // sharded: rows and the bottom levels of the paths come from the owning ranks
         trace_lvl0 = src.shard_lvl0;
         k_split_shard_rows<<<nq, 128, 0, st>>>(src.shard_rows, W, trace_lvl0, S.log_N, (uint64_t *)(d_block + O.trows), (uint64_t *)(d_block + O.tpaths));
         HIP_TRY(hipGetLastError());
-    } else gl.rows(a->lde, W, S.log_n, S.log_b, a->d_pos, d_block + O.trows, nq, src.log_s);
-    gl.paths(a->tnodes, S.log_N, a->d_pos, d_block + O.tpaths, nq, nullptr, trace_lvl0);
-    gl.rows(src.clde, S.ce * S.m, S.log_n, S.log_b, a->d_pos, d_block + O.crows, nq);
-    gl.paths(a->cnodes, S.log_N, a->d_pos, d_block + O.cpaths, nq);
+    } else gl.rows(a->lde, W, S.log_n, S.log_b, d_pos, d_block + O.trows, nq, src.log_s);
+    gl.paths(a->tnodes, S.log_N, d_pos, d_block + O.tpaths, nq, nullptr, trace_lvl0);
+    gl.rows(src.clde, S.ce * S.m, S.log_n, S.log_b, d_pos, d_block + O.crows, nq);
+    gl.paths(a->cnodes, S.log_N, d_pos, d_block + O.cpaths, nq);
     for (unsigned l = 0; l < S.n_layers; l++) {
-        const uint32_t np = src.counts ? src.counts[l] : nq, lr = layer_log_rows(S, l), *pos = a->d_pos + 256 * (l + 1), *dc = src.dcount ? src.dcount + l : nullptr;
+        const uint32_t np = src.counts ? src.counts[l] : nq, lr = layer_log_rows(S, l), *pos = d_pos + 256 * (l + 1), *dc = src.dcount ? src.dcount + l : nullptr;
         gl.rows(src.layer[l], S.f * S.m, lr, 0, pos, d_block + O.lrows[l], np, 0, dc);
         gl.paths(a->lnodes[l], lr, pos, d_block + O.lpaths[l], np, dc);
     }
@@ -646,11 +647,14 @@ int fri_commit(cstark_ctx *c, ProveArena *a, ProofRun &R, uint32_t *d_fri, uint3
 }
 
 // The proof bytes (proof_layout.h), straight into the caller's buffer.  `p`: roots, frame, nonce and remainder; the openings are the
-// sections O of the host copy `h` of an opening block, `counts` positions per layer.
-int finish_proof(const ProofShape &S, ProofParts p, const uint8_t *h, const OpenBlock &O, const uint32_t *counts, uint8_t *proof, size_t capacity, size_t *proof_len) {
+// sections O of the host copy `h` of an opening block, `counts` positions per layer.  form: the context's (CSTARK_FORM_*); the compact
+// form is selected from the same block and needs the positions on the host: pos [nq], then layer l's at pos + lstride * (l + 1).
+int finish_proof(const ProofShape &S, ProofParts p, const uint8_t *h, const OpenBlock &O, const uint32_t *counts, uint32_t form, const uint32_t *pos,
+                 size_t lstride, uint8_t *proof, size_t capacity, size_t *proof_len) {
     p.trows = h + O.trows; p.tpaths = h + O.tpaths; p.crows = h + O.crows; p.cpaths = h + O.cpaths;
     p.counts = counts;
-    for (unsigned l = 0; l < S.n_layers; l++) { p.lrows[l] = h + O.lrows[l]; p.lpaths[l] = h + O.lpaths[l]; }
+    p.form = form; p.pos = pos;
+    for (unsigned l = 0; l < S.n_layers; l++) { p.lrows[l] = h + O.lrows[l]; p.lpaths[l] = h + O.lpaths[l]; p.lpos[l] = pos + lstride * (l + 1); }
     if (write_proof(S, p, proof, capacity, proof_len)) return fail(CSTARK_ERR_INVALID_ARG, "proof buffer too small (required size returned in *proof_len)");
     return CSTARK_OK;
 }
@@ -828,7 +832,7 @@ int phase_open(cstark_ctx *c, ProveArena *a, ProofRun &R, const uint64_t *d_trac
     ProofParts p{};
     p.trace_root = R.trace_root; p.cons_root = R.cons_root; p.layer_roots = R.layer_roots.data(); p.rem_commit = R.rem_commit;
     p.ood_trace = R.ood_trace.data(); p.ood_comp = R.ood_comp.data(); p.nonce = R.q.nonce; p.remainder = R.remainder.data();
-    return finish_proof(S, p, a->h_open, O, R.q.counts, proof, capacity, proof_len);
+    return finish_proof(S, p, a->h_open, O, R.q.counts, R.sharded() ? (uint32_t)CSTARK_FORM_PLAIN : ctx_proof_form(c), R.q.hpos.data(), 256, proof, capacity, proof_len);
 }
 
 // every host-channel proof on one GPU
@@ -871,6 +875,10 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
     const size_t o_troot = take(32), o_croot = take(32), o_rem = take(32), o_cnt = take(4 * 64), o_ood = take(n_ood * 8), o_lroots = take(32 * (size_t)n_layers),
                  o_remainder = take(rem_len * 8);
     const ProofShape &S = R.shape;
+    // the compact form is selected on the host and needs the positions there: the channel then draws them into the result block, where
+    // the gathers read them and the one copy takes them along (the plain form keeps a->d_pos and a block without them)
+    const bool compact = ctx_proof_form(c) == CSTARK_FORM_COMPACT;
+    const size_t o_pos = compact ? take(4 * 256 * ((size_t)n_layers + 1)) : 0;
     const OpenBlock O = open_block(S, nullptr, off, 256); // the openings: the tail of the block, nq slots in every layer
     off = O.bytes;
     uint8_t *d_res;
@@ -891,7 +899,7 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
         RC_TRY(arena_extra(c, a, 49, &dcoef, 3 * n * 8));
     }
     uint64_t *d_pts = d_chan, *d_scal = d_chan + 4 * m, *d_deepc = d_chan + 12 * m, *d_ood = (uint64_t *)(d_res + o_ood);
-    uint32_t *d_cnt = (uint32_t *)(d_res + o_cnt);
+    uint32_t *d_cnt = (uint32_t *)(d_res + o_cnt), *d_qpos = compact ? (uint32_t *)(d_res + o_pos) : a->d_pos;
     RC_TRY(host_open_block(a, off)); // before the first launch: replacing a pinned block waits for the device
     RC_TRY(desc_reserve(c, ood_frames_dev_scratch_bytes((uint32_t)W, (uint32_t)ce, log_n, m))); // the frame's scratch, likewise
     // the coefficient blocks the channel draws into, one per component: TransactionAir's evaluator reads the context's cstark_tx_coeffs
@@ -983,11 +991,11 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
         s.absorb[0].kind = CHAN_ELEMS; s.absorb[0].ptr = d_res + o_remainder; s.absorb[0].count = (uint32_t)rem_len; s.absorb[0].copy_out = d_res + o_rem;
         s.absorb[1].kind = CHAN_INT; s.absorb[1].value = 1;
         s.draw = CHAN_DRAW_QUERIES; s.count = (uint32_t)nq; s.log_domain = log_N; s.log_f = R.log_f; s.n_layers = n_layers; s.slot = 256;
-        s.pos = a->d_pos; s.cnt = d_cnt;
+        s.pos = d_qpos; s.cnt = d_cnt;
         HIP_TRY(channel_step(s, st));
     }
     // at most nq rows per layer; how many: cnt[l + 1], on the device.  The copy takes the whole result block.
-    RC_TRY(open_stage(c, a, S, {R.clde, R.layer.data(), R.log_s(), nullptr, d_cnt + 1, nullptr, 0}, d_res, O));
+    RC_TRY(open_stage(c, a, S, {R.clde, R.layer.data(), R.log_s(), nullptr, d_cnt + 1, nullptr, 0, d_qpos}, d_res, O));
     STAGE();
     static const bool hostprof = getenv("CSTARK_HOSTPROF") != nullptr; // debugging: where the host's time goes
     const auto hp1 = std::chrono::steady_clock::now();
@@ -1003,7 +1011,7 @@ int prove_core_dev(cstark_ctx *c, const cstark_options *opt, AirJob &job0, uint8
     p.trace_root = h + o_troot; p.cons_root = h + o_croot; p.layer_roots = h + o_lroots; p.rem_commit = h + o_rem;
     p.ood_trace = h + o_ood; p.ood_comp = h + o_ood + ood_trace_bytes(S); p.remainder = h + o_remainder;
     p.nonce = 1; // grinding_factor 0
-    RC_TRY(finish_proof(S, p, h, O, cnt + 1, proof, capacity, proof_len));
+    RC_TRY(finish_proof(S, p, h, O, cnt + 1, ctx_proof_form(c), (const uint32_t *)(h + o_pos), 256, proof, capacity, proof_len));
     if (hostprof) {
         const auto hp3 = std::chrono::steady_clock::now();
         auto us = [](auto d) { return std::chrono::duration<double, std::micro>(d).count(); };
@@ -1458,12 +1466,14 @@ struct RangeBatch {
     }
     // the proof bytes, proof t at proofs + stride t (the caller has checked that any proof of this shape fits a stride)
     int write(uint8_t *proofs, size_t stride, size_t *lens) {
+        const uint32_t form = ctx_proof_form(c);
         return parallel_for(B, [&](size_t t) {
             const uint64_t *f = h_ood + RB_FRAME * t;
             ProofParts p{};
             p.trace_root = h_troot + 32 * t; p.cons_root = h_croot + 32 * t; p.layer_roots = h_lroot + 32 * t; p.rem_commit = &rem_commit[32 * t];
             p.ood_trace = f; p.ood_comp = f + 2 * RB_W; p.nonce = nonces[t]; p.remainder = h_rem + S.R * t;
-            (void)finish_proof(S, p, h_open + O.bytes * t, O, h_lcount + t, proofs + stride * t, stride, &lens[t]);
+            // the positions of proof t and, B * nq words behind them, its folded ones: h_lpos follows h_pos in the block
+            (void)finish_proof(S, p, h_open + O.bytes * t, O, h_lcount + t, form, h_pos + S.nq * t, (size_t)(h_lpos - h_pos), proofs + stride * t, stride, &lens[t]);
         });
     }
 };
@@ -1550,6 +1560,7 @@ static int shard_run(cstark_ctx *c, int min_phase, ProofRun **out) {
 }
 int cstark_tx_shard_commit(cstark_ctx *c, const cstark_options *opt, uint32_t k0, uint32_t nk, uint8_t *d_leaves_local) {
     if (!c || !opt || !d_leaves_local) return fail(CSTARK_ERR_INVALID_ARG, "cstark_tx_shard_commit: null argument");
+    if (ctx_proof_form(c) != CSTARK_FORM_PLAIN) return fail(CSTARK_ERR_UNSUPPORTED, "sharded proofs are written in the plain form only");
     if (!c->wit_buf || c->wit.n_tx == 0 || c->wit.msg_tail) return fail(CSTARK_ERR_INVALID_ARG, "no transaction witness uploaded");
     if (c->wit.n_tx & (c->wit.n_tx - 1)) return fail(CSTARK_ERR_INVALID_ARG, "the number of transactions must be a power of two");
     if (nk == 0 || nk >= 8 || (nk & (nk - 1)) || k0 % nk || k0 + nk > 8) return fail(CSTARK_ERR_INVALID_ARG, "a rank owns 1, 2 or 4 consecutive cosets of the 8 (world size 8, 4 or 2)");
@@ -1612,6 +1623,7 @@ int cstark_tx_shard_open_rows(cstark_ctx *c, const uint32_t *positions, uint32_t
     return CSTARK_OK;
 }
 int cstark_tx_shard_finish(cstark_ctx *c, const uint64_t *d_rows, uint8_t *proof, size_t capacity, size_t *proof_len) {
+    if (c && ctx_proof_form(c) != CSTARK_FORM_PLAIN) return fail(CSTARK_ERR_UNSUPPORTED, "sharded proofs are written in the plain form only");
     ProofRun *R;
     RC_TRY(shard_run(c, 3, &R));
     if (!d_rows || !proof_len) return fail(CSTARK_ERR_INVALID_ARG, "cstark_tx_shard_finish: null argument");
@@ -1687,9 +1699,8 @@ int cstark_range_prove_batch(cstark_ctx *c, const cstark_options *opt, const uin
         canon[t] = host::to_u64(numbers[t]);
         if (canon[t] >> 63) return fail(CSTARK_ERR_INVALID_ARG, "range proofs cover 63-bit field elements (src/range/tests.rs:54-62)");
     }
-    uint32_t all_nq[VMAX_LAYERS]; // the longest proof of this shape: nq distinct positions in every layer
-    std::fill(all_nq, all_nq + VMAX_LAYERS, S.nq);
-    if (stride < proof_size(S, all_nq)) return fail(CSTARK_ERR_INVALID_ARG, "cstark_range_prove_batch: stride too small (cstark_tx_proof_size_bound(1, opt) is sufficient)");
+    // the longest proof of this shape and form: nq distinct positions in every layer
+    if (stride < proof_size_bound(S, ctx_proof_form(c))) return fail(CSTARK_ERR_INVALID_ARG, "cstark_range_prove_batch: stride too small (cstark_tx_proof_size_bound(1, opt) is sufficient)");
     HIP_TRY(hipSetDevice(c->device));
     if (c->arena) c->arena->timed = false; // cstark_prove_stage_ms describes the generic prover's last proof: none after a batch
 

@@ -11,8 +11,9 @@
 //           per (AIR, extension degree m) present: (SchnorrAir: the statement's 31 values at z) -> out-of-domain frames (periodic columns at z^(n/cycle) from cached coefficients, the frame
 //           sampled along t -> e(t) for m > 1) -> the AIR's constraints on every frame (constraints.hip, launch_eval_frames_air) -> merge
 //           and compare with sum_i H_i z^i; DEEP + FRI, one lane per (proof, query)
-//           all proofs: Merkle openings, one lane per opened row (leaf hash + path walk, Blake3 or Sha3); remainder degree (exact,
-//           one workgroup per component); reduction to one verdict per proof -> ONE device-to-host copy
+//           all proofs: Merkle openings, one lane per opened row (leaf hash + path walk, Blake3 or Sha3) -- the trees of compact
+//           proofs (proof_layout.h: one multiproof per tree) fold in one workgroup each instead (k_vfy_multi_open); remainder degree
+//           (exact, one workgroup per component); reduction to one verdict per proof -> ONE device-to-host copy
 // Every check writes one result slot with a plain store: the rank of its failure in the verdict order of cstark.h (or none); the
 // reduction takes the smallest.  The number of launches per chunk does not depend on the number of proofs.
 #include <hip/hip_runtime.h>
@@ -94,7 +95,7 @@ struct VDesc {
     uint32_t lrows[VMAX_LAYERS];
     uint32_t log_n, log_N, nq, log_f, n_layers, m, R, log_b, hash, grinding, log_rem, npos[VMAX_LAYERS];
     uint32_t slot0;     // result slots: [0] out-of-domain, then openings, then nq queries, then m remainder components
-    uint32_t n_open;
+    uint32_t n_open;    // opening slots: one per opened row, or (compact proof) one per tree
 };
 __device__ __forceinline__ TOff toff(const VDesc &d) { return toff(d.a, d.m, d.n_layers, d.nq); }
 struct VOpen {
@@ -102,6 +103,11 @@ struct VOpen {
     uint32_t words, depth, layer, t, rank, slot, hash; // layer = VNO_LAYER: trace / composition row of query t; else row t of that layer
 };
 constexpr uint32_t VNO_LAYER = 0xffffffffu;
+// one tree of a compact proof: `count` opened rows of `words` words from byte offset `rows` on, `n_nodes` multiproof nodes from `nodes` on
+struct VMulti {
+    uint32_t proof, rows, nodes, n_nodes, root; // byte offsets inside the proof (and the stated node count)
+    uint32_t words, depth, layer, count, rank, slot, hash; // layer = VNO_LAYER: the trace / composition tree; else that layer's
+};
 
 // ---- device helpers ---------------------------------------------------------------------------------------------------------------
 // proof bytes are 4-aligned only (each layer's count word shifts what follows by 4)
@@ -232,6 +238,162 @@ __global__ __launch_bounds__(128) void k_vfy_openings(const uint8_t *__restrict_
         for (int i = 0; i < 4; i++) match &= h[i] == ld64(root + 8 * i);
     }
     slots[o.slot] = !canonical ? (uint32_t)RK_MALFORMED : match ? (uint32_t)RK_NONE : rank;
+}
+
+// ---- the multiproof of one tree of a compact proof ----------------------------------------------------------------------------------
+// Digests travel as eight 32-bit words under either hash.  The parent of two digests, as k_vfy_openings forms it.
+template <int HASH> __device__ __forceinline__ void multi_parent(const uint32_t (&l)[8], const uint32_t (&r)[8], uint32_t (&out)[8]) {
+    if constexpr (HASH == 0) {
+        uint32_t m[16];
+#pragma unroll
+        for (int i = 0; i < 8; i++) { m[i] = l[i]; m[8 + i] = r[i]; }
+        out[0] = IV0; out[1] = IV1; out[2] = IV2; out[3] = IV3; out[4] = IV4; out[5] = IV5; out[6] = IV6; out[7] = IV7;
+        compress(out, m, 64, CHUNK_START | CHUNK_END | ROOT);
+    } else {
+        uint64_t s[25]; // in registers: every lane index is a compile-time constant
+#pragma unroll
+        for (int i = 0; i < 25; i++) s[i] = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            s[i] = (uint64_t)l[2 * i] | ((uint64_t)l[2 * i + 1] << 32);
+            s[4 + i] = (uint64_t)r[2 * i] | ((uint64_t)r[2 * i + 1] << 32);
+        }
+        s[8] ^= 0x06;
+        s[16] ^= 0x80ull << 56;
+        keccak::permute(s);
+#pragma unroll
+        for (int i = 0; i < 4; i++) { out[2 * i] = (uint32_t)s[i]; out[2 * i + 1] = (uint32_t)(s[i] >> 32); }
+    }
+}
+// Order-preserving positions of the threads that flag a (pa) and b (pb) among the 128 of the workgroup, and the two totals: a ballot per
+// wave, the other wave's counts through LDS (compact_position of channel.hip, two flags at once).  Called by all threads; the caller
+// synchronises before the next call (it does anyway, after writing what the positions index).
+__device__ __forceinline__ void multi_scan(uint32_t (&cnt)[2][2], bool a, bool b, uint32_t &pa, uint32_t &pb, uint32_t &ta, uint32_t &tb) {
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint64_t va = __ballot(a), vb = __ballot(b), below = (1ull << lane) - 1;
+    if (lane == 0) { cnt[wave][0] = (uint32_t)__popcll(va); cnt[wave][1] = (uint32_t)__popcll(vb); }
+    __syncthreads();
+    pa = (wave ? cnt[0][0] : 0u) + (uint32_t)__popcll(va & below);
+    pb = (wave ? cnt[0][1] : 0u) + (uint32_t)__popcll(vb & below);
+    ta = cnt[0][0] + cnt[1][0];
+    tb = cnt[0][1] + cnt[1][1];
+}
+// One workgroup of 128 threads per tree (HASH: 0 Blake3, 1 Sha3; the list holds the trees of one hash).  Positions come from the replayed
+// transcript, as in k_vfy_openings; a layer from the first one whose count differs has its rows checked for canonical words only.
+//   1 leaves    thread t < count hashes row t (proof order)
+//   2 sort      the rank of every position among the count <= 128 (O(n^2) over LDS); equal positions must carry equal digests and
+//               collapse to one entry
+//   3 fold      for l = depth .. 1: entry i of K_l (ascending) is the left half of a pair inside K_l, its right half, or single; a single
+//               takes the next proof node -- its index is the number of singles before it (multi_scan) behind the nodes of the levels
+//               below; every entry but a right half hashes one parent into the other buffer, at its position among those
+//   4 verdict   accepted iff exactly n_nodes nodes were consumed and the last digest is the committed root
+// Everything a thread indexes is bounded by count <= 128 (parse_layout: num_queries, n_positions) and, for the proof nodes, by the
+// stated n_nodes, which parse_layout has placed inside the proof; no flags between workgroups, no atomics.
+template <int HASH>
+__global__ __launch_bounds__(128) void k_vfy_multi_open(const uint8_t *__restrict__ buf, const VDesc *__restrict__ desc, const VMulti *__restrict__ trees,
+                                                        const uint64_t *__restrict__ tbase, uint32_t *__restrict__ slots) {
+    __shared__ uint32_t dig[2][128][8];
+    __shared__ uint32_t key[2][128];
+    __shared__ uint32_t cnt[2][2];
+    const VMulti o = trees[blockIdx.x];
+    const VDesc &d = desc[o.proof];
+    const uint8_t *pb = buf + d.base;
+    const uint64_t *tb = tbase + d.tb;
+    const TOff to = toff(d);
+    const uint32_t tid = threadIdx.x;
+    const bool placed = o.layer == VNO_LAYER || o.layer < (uint32_t)tb[to.st]; // uniform: the tree's positions are known
+    bool canonical = true, bad = false;
+    uint32_t cv[8] = {}, pos = 0xffffffffu;
+    if (tid < o.count) {
+        const uint8_t *row = pb + o.rows + 8 * (size_t)tid * o.words;
+        if constexpr (HASH == 0) b3_words(row, o.words, cv, canonical);
+        else {
+            uint64_t h[4];
+            sha3_words(row, o.words, h, canonical);
+#pragma unroll
+            for (int i = 0; i < 4; i++) { cv[2 * i] = (uint32_t)h[i]; cv[2 * i + 1] = (uint32_t)(h[i] >> 32); }
+        }
+        if (placed) pos = o.layer == VNO_LAYER ? (uint32_t)tb[to.pos + tid] : (uint32_t)tb[to.lpos + o.layer * d.nq + tid];
+    }
+    key[0][tid] = pos;
+    const int malformed = __syncthreads_or(!canonical);
+    if (malformed || !placed) {
+        if (tid == 0) slots[o.slot] = malformed ? (uint32_t)RK_MALFORMED : (uint32_t)RK_NONE;
+        return;
+    }
+    // ---- sort into buffer 1, collapse into buffer 0
+    if (tid < o.count) {
+        uint32_t r = 0;
+        for (uint32_t j = 0; j < o.count; j++) {
+            const uint32_t kj = key[0][j];
+            r += (kj < pos || (kj == pos && j < tid)) ? 1u : 0u;
+        }
+        key[1][r] = pos;
+#pragma unroll
+        for (int i = 0; i < 8; i++) dig[1][r][i] = cv[i];
+    }
+    __syncthreads();
+    uint32_t n, used = 0;
+    {
+        bool first = false;
+        if (tid < o.count) {
+            pos = key[1][tid];
+            first = tid == 0 || key[1][tid - 1] != pos;
+#pragma unroll
+            for (int i = 0; i < 8; i++) { cv[i] = dig[1][tid][i]; if (!first) bad |= cv[i] != dig[1][tid - 1][i]; }
+        }
+        uint32_t at, unused0, unused1;
+        multi_scan(cnt, first, false, at, unused0, n, unused1);
+        if (first) {
+            key[0][at] = pos;
+#pragma unroll
+            for (int i = 0; i < 8; i++) dig[0][at][i] = cv[i];
+        }
+        __syncthreads();
+    }
+    // ---- fold
+    uint32_t cur = 0;
+    for (uint32_t l = o.depth; l >= 1; l--) {
+        const bool in = tid < n;
+        const uint32_t x = in ? key[cur][tid] : 0u;
+        const bool right_half = in && (x & 1) && tid > 0 && key[cur][tid - 1] == x - 1;
+        const bool left_half = in && !(x & 1) && tid + 1 < n && key[cur][tid + 1] == x + 1;
+        const bool parent = in && !right_half, single = parent && !left_half;
+        uint32_t at, node, n_next, n_single;
+        multi_scan(cnt, parent, single, at, node, n_next, n_single);
+        if (parent) {
+            uint32_t own[8], sib[8], out[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) own[i] = dig[cur][tid][i];
+            if (left_half) {
+#pragma unroll
+                for (int i = 0; i < 8; i++) sib[i] = dig[cur][tid + 1][i];
+            } else if (used + node < o.n_nodes) {
+                const uint32_t *src = reinterpret_cast<const uint32_t *>(pb + o.nodes + 32 * (size_t)(used + node));
+#pragma unroll
+                for (int i = 0; i < 8; i++) sib[i] = src[i];
+            } else { // the proof states fewer nodes than the positions ask for
+                bad = true;
+#pragma unroll
+                for (int i = 0; i < 8; i++) sib[i] = 0;
+            }
+            if (x & 1) multi_parent<HASH>(sib, own, out);
+            else multi_parent<HASH>(own, sib, out);
+            key[cur ^ 1][at] = x >> 1;
+#pragma unroll
+            for (int i = 0; i < 8; i++) dig[cur ^ 1][at][i] = out[i];
+        }
+        __syncthreads();
+        n = n_next; used += n_single; cur ^= 1;
+    }
+    // ---- verdict
+    if (tid == 0) {
+        const uint32_t *root = reinterpret_cast<const uint32_t *>(pb + o.root);
+        bad |= n != 1 || used != o.n_nodes;
+        for (int i = 0; i < 8; i++) bad |= dig[cur][0][i] != root[i];
+    }
+    const int refused = __syncthreads_or(bad);
+    if (tid == 0) slots[o.slot] = refused ? o.rank : (uint32_t)RK_NONE;
 }
 
 template <int R, class F> __device__ __forceinline__ void static_down(F &&f) {
@@ -1129,7 +1291,7 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
     // blocks and the statements' values at z live on the device only
     size_t off = 0, t_words = 0, sp_words = 0;
     std::vector<size_t> pofs(P), tofs(P);
-    size_t n_open = 0, n_slots = 0;
+    size_t n_open = 0, n_multi = 0, n_slots = 0; // opened rows of the plain proofs, trees of the compact ones
     for (uint32_t i = 0; i < P; i++) {
         const Layout &L = st[i].L;
         off = (off + 15) & ~(size_t)15; pofs[i] = off; off += L.rem + 8 * (size_t)L.R * L.m;
@@ -1140,14 +1302,16 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
         tofs[i] = t_words; t_words += (toff(st[i].d.a, L.m, L.n_layers, L.nq).words + 1) & ~(size_t)1;
         uint32_t no = 2 * L.nq;
         for (uint32_t l = 0; l < L.n_layers; l++) no += L.npos[l];
+        if (L.form == CSTARK_FORM_COMPACT) { no = 2 + L.n_layers; n_multi += no; }
+        else n_open += no;
         st[i].d.n_open = no;
         st[i].d.slot0 = (uint32_t)n_slots;
-        n_open += no;
         n_slots += 1 + no + L.nq + L.m;
     }
     const size_t desc_off = (off + 15) & ~(size_t)15;
     const size_t open_off = (desc_off + P * sizeof(VDesc) + 15) & ~(size_t)15;
-    const size_t grp_off = (open_off + n_open * sizeof(VOpen) + 15) & ~(size_t)15;
+    const size_t multi_off = (open_off + n_open * sizeof(VOpen) + 15) & ~(size_t)15; // (no compact proof: empty, the block is as before)
+    const size_t grp_off = (multi_off + n_multi * sizeof(VMulti) + 15) & ~(size_t)15;
     const size_t total = grp_off + (size_t)P * 4 + 16;
     if (total > a->stage_bytes) {
         HIP_TRY(hipStreamSynchronize(s));
@@ -1162,6 +1326,7 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
     uint8_t *H = a->h_stage;
     VDesc *hd = reinterpret_cast<VDesc *>(H + desc_off);
     VOpen *ho = reinterpret_cast<VOpen *>(H + open_off);
+    VMulti *hm = reinterpret_cast<VMulti *>(H + multi_off);
     uint32_t *hg = reinterpret_cast<uint32_t *>(H + grp_off); // [P]: the proofs of each (AIR, extension degree), group after group
     // samples per frame: a constraint of degree <= D in the frame has degree <= D (m - 1) along t; any K above that is exact
     Group grp[5 * 3];
@@ -1174,6 +1339,8 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
     for (uint32_t g = 0, o = 0; g < 15; g++) { grp[g].start = o; o += grp[g].count; grp[g].frames = grp[g].count * grp[g].K; grp[g].count = 0; }
     std::vector<VOpen> opens;
     opens.reserve(n_open);
+    std::vector<VMulti> multis;
+    multis.reserve(n_multi);
     for (uint32_t i = 0; i < P; i++) {
         Staged &S = st[i];
         const Layout &L = S.L;
@@ -1204,6 +1371,14 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
         const uint32_t TW = d.a.w, TCE = d.a.ce;
         const uint32_t hash = L.opt[3];
         uint32_t sl = d.slot0 + 1;
+        if (L.form == CSTARK_FORM_COMPACT) { // one entry per tree, in the verdict order: trace, composition, the layers
+            multis.push_back(VMulti{i, (uint32_t)L.trows, (uint32_t)L.tpaths, L.nodes[0], 52u, TW, L.log_N, VNO_LAYER, L.nq, RK_OPENING0, sl++, hash});
+            multis.push_back(VMulti{i, (uint32_t)L.crows, (uint32_t)L.cpaths, L.nodes[1], 84u, TCE * L.m, L.log_N, VNO_LAYER, L.nq, RK_OPENING0 + 1, sl++, hash});
+            for (uint32_t l = 0; l < L.n_layers; l++)
+                multis.push_back(VMulti{i, (uint32_t)L.lrows[l], (uint32_t)L.lpaths[l], L.nodes[2 + l], (uint32_t)(120 + 32 * l), L.f * L.m,
+                                        layer_log_rows(L, l), l, L.npos[l], RK_LAYER0 + 3 * l + 1, sl++, hash});
+            continue;
+        }
         for (uint32_t q = 0; q < L.nq; q++) {
             opens.push_back(VOpen{i, (uint32_t)(L.trows + 8 * (size_t)q * TW), (uint32_t)(L.tpaths + 32 * (size_t)q * L.log_N), 52u, TW, L.log_N,
                                   VNO_LAYER, q, RK_OPENING0 + 2 * q, sl++, hash});
@@ -1226,6 +1401,9 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
         return x.hash != y.hash ? x.hash < y.hash : x.words != y.words ? x.words < y.words : x.depth < y.depth;
     });
     memcpy(ho, opens.data(), opens.size() * sizeof(VOpen));
+    // the trees of one hash side by side: one launch of k_vfy_multi_open per hash present
+    const size_t n_multi_b3 = std::stable_partition(multis.begin(), multis.end(), [](const VMulti &x) { return x.hash == 0; }) - multis.begin();
+    if (n_multi) memcpy(hm, multis.data(), multis.size() * sizeof(VMulti));
     const auto t1 = std::chrono::steady_clock::now();
     host_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
 
@@ -1270,6 +1448,7 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
     const uint8_t *dbuf = a->d_stage;
     const VDesc *d_desc = reinterpret_cast<const VDesc *>(dbuf + desc_off);
     const VOpen *d_open = reinterpret_cast<const VOpen *>(dbuf + open_off);
+    const VMulti *d_multi = reinterpret_cast<const VMulti *>(dbuf + multi_off);
     const uint32_t *d_grp = reinterpret_cast<const uint32_t *>(dbuf + grp_off);
 
     for (int e = 0; e < VFY_EVENTS; e++)
@@ -1309,6 +1488,14 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
     HIP_TRY(hipEventRecord(a->ev[3], s));
     if (n_open) {
         hipLaunchKernelGGL(k_vfy_openings, dim3((unsigned)((n_open + 127) / 128)), dim3(128), 0, s, dbuf, d_desc, d_open, (uint32_t)n_open, d_tb, d_slots);
+        HIP_TRY(hipGetLastError());
+    }
+    if (n_multi_b3) {
+        hipLaunchKernelGGL(k_vfy_multi_open<0>, dim3((unsigned)n_multi_b3), dim3(128), 0, s, dbuf, d_desc, d_multi, d_tb, d_slots);
+        HIP_TRY(hipGetLastError());
+    }
+    if (n_multi > n_multi_b3) {
+        hipLaunchKernelGGL(k_vfy_multi_open<1>, dim3((unsigned)(n_multi - n_multi_b3)), dim3(128), 0, s, dbuf, d_desc, d_multi + n_multi_b3, d_tb, d_slots);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(a->ev[4], s));
@@ -1354,6 +1541,14 @@ int cstark_proof_inspect(const uint8_t *proof, size_t len, cstark_proof_info *in
     // the header words as read (all zero unless the magic matched)
     info->air = L.air; info->trace_width = L.width; info->log_n = L.log_n; info->header_word = L.word;
     memcpy(&info->options, L.opt, sizeof L.opt);
+    return CSTARK_OK;
+}
+
+int cstark_proof_form(const uint8_t *proof, size_t len, uint32_t *form) {
+    if (!proof || !form) return fail(CSTARK_ERR_INVALID_ARG, "cstark_proof_form: null argument");
+    const int f = proof_form_of(proof, len);
+    if (f < 0) return fail(CSTARK_ERR_INVALID_ARG, "cstark_proof_form: neither a plain nor a compact proof");
+    *form = (uint32_t)f;
     return CSTARK_OK;
 }
 

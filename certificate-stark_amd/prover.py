@@ -11,6 +11,7 @@ Names and argument meaning follow the reference so tests read like its own:
 All device work goes through the C ABI (include/cstark.h); there is no CPU path here.
 """
 import collections
+import contextlib
 
 import numpy as np
 
@@ -417,6 +418,21 @@ class TransactionProver:
         return self.backend.prove(self.options)
 
 
+@contextlib.contextmanager
+def _proof_form(backend, compact):
+    """prove(compact=True): the backend's proof form set to "compact" (one Merkle multiproof per tree, include/cstark.h) for one prove()
+    and restored after it.  compact=False leaves the backend as it is: the proof takes Backend.proof_form, "plain" unless set."""
+    if not compact:
+        yield
+        return
+    before = backend.proof_form
+    backend.proof_form = "compact"
+    try:
+        yield
+    finally:
+        backend.proof_form = before
+
+
 def get_example_options():
     """The options of get_example (src/lib.rs:75-89)."""
     return ProofOptions(42, 8, 0, ProofOptions.BLAKE3_256, ProofOptions.EXT_NONE, 4, 256)
@@ -431,8 +447,9 @@ class TransactionExample:
         self.options, self.tx_metadata = options, tx_metadata
         self.prover = TransactionProver(options, backend)
 
-    def prove(self):
-        return self.prover.prove(self.tx_metadata)
+    def prove(self, compact=False):
+        with _proof_form(self.prover.backend, compact):
+            return self.prover.prove(self.tx_metadata)
 
     def verify(self, proof):
         """winterfell::verify::<TransactionAir>(proof, pub_inputs) (src/lib.rs:144-150): the proof's own options are accepted."""
@@ -503,10 +520,11 @@ class MerkleExample(_ResidentWitness):
     def _witness_arrays(self):
         return [getattr(self.tx_metadata, f) for f in TransactionMetadata.FIELDS]
 
-    def prove(self):
+    def prove(self, compact=False):
         """The witness is uploaded by the first call and stays resident (_ResidentWitness: read-only on the host until invalidate())."""
         self._ensure_resident(lambda: self.backend.upload_witness(self.tx_metadata))
-        return self.backend.air_prove(Backend.AIR_MERKLE, self.options)
+        with _proof_form(self.backend, compact):
+            return self.backend.air_prove(Backend.AIR_MERKLE, self.options)
 
     def pub_inputs(self):
         return self.tx_metadata.initial_roots[0], self.tx_metadata.final_root
@@ -557,10 +575,11 @@ class SchnorrExample(_ResidentWitness):
     def _witness_arrays(self):
         return [self.messages, self.sig_rx, self.sig_s]
 
-    def prove(self):
+    def prove(self, compact=False):
         """The witness is uploaded by the first call and stays resident (_ResidentWitness: read-only on the host until invalidate())."""
         self._ensure_resident(lambda: self.backend.upload_schnorr_witness(self.messages, self.sig_rx, self.sig_s))
-        return self.backend.air_prove(Backend.AIR_SCHNORR, self.options)
+        with _proof_form(self.backend, compact):
+            return self.backend.air_prove(Backend.AIR_SCHNORR, self.options)
 
     def check(self):
         """verify_signature (src/schnorr/mod.rs:220-245) for every signature of this example, on the device: verdicts uint8 [n]
@@ -595,8 +614,9 @@ class RescueExample:
         r2 = pow(2, 64, _P)
         self.seed = np.array([(v * r2) % _P for v in range(42, 49)], np.uint64) if seed is None else np.ascontiguousarray(seed, np.uint64)
 
-    def prove(self):
-        return self.backend.rescue_prove(self.options, self.seed, self.chain_length)
+    def prove(self, compact=False):
+        with _proof_form(self.backend, compact):
+            return self.backend.rescue_prove(self.options, self.seed, self.chain_length)
 
     def pub_inputs(self):
         """seed and result; the result is the rate half of the chain's last row (RescueProver::get_pub_inputs, benches/rescue.rs:331-354),
@@ -625,8 +645,9 @@ class RangeProofExample:
         self.options, self.number = options, int(number)
         self.backend = backend or Backend()
 
-    def prove(self):
-        return self.backend.air_prove(Backend.AIR_RANGE, self.options, self.number)
+    def prove(self, compact=False):
+        with _proof_form(self.backend, compact):
+            return self.backend.air_prove(Backend.AIR_RANGE, self.options, self.number)
 
     def verify(self, proof):
         """src/range/mod.rs:103-110; raises VerifierError on rejection"""

@@ -47,8 +47,18 @@ class ProofInfo:
         return self.verdict == 0
 
 
+def proof_form(proof):
+    """cstark_proof_form: "plain" or "compact" by the proof's magic (host only); ValueError when it has neither"""
+    b = bytes(proof)
+    buf = (C.c_uint8 * max(1, len(b))).from_buffer_copy(b if b else b"\0")
+    form = C.c_uint32(0)
+    if _lib.load().cstark_proof_form(buf, C.c_size_t(len(b)), C.byref(form)) != 0:
+        raise ValueError("neither a plain nor a compact proof")
+    return ("plain", "compact")[form.value]
+
+
 def inspect_proof(proof):
-    """cstark_proof_inspect: the complete layout check of a proof of any of the five AIRs, on the host (no GPU, no context)."""
+    """cstark_proof_inspect: the complete layout check of a proof of any of the five AIRs, in either form, on the host (no GPU, no context)."""
     b = bytes(proof)
     buf = (C.c_uint8 * max(1, len(b))).from_buffer_copy(b if b else b"\0")
     info, verdict = ProofInfoStruct(), C.c_int32(-1)

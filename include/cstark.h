@@ -271,8 +271,29 @@ int cstark_fri_fold(cstark_ctx *ctx, const uint64_t *d_evals, uint64_t *d_out, u
  *   trace rows [q][94], paths [q][log N][32] | composition rows [q][8], paths [q][log N][32]      (q = num_queries, N = blowup * n)
  *   per layer: u32 n_positions, rows [n_positions][f], paths [n_positions][log rows][32]          (f = fri_folding_factor, rows = N_layer / f)
  *   u32 remainder_len, remainder[remainder_len]
- * Query positions are not stored: the verifier re-derives them from the channel.  Paths list siblings leaf-upwards. */
+ * Query positions are not stored: the verifier re-derives them from the channel.  Paths list siblings leaf-upwards.
+ *
+ * The compact form (CSTARK_FORM_COMPACT; cstark_ctx_set_proof_form) has the magic "CSTC" (same version) and replaces each of the
+ * 2 + n_layers path sections by
+ *   u32 n_nodes, nodes[n_nodes][32]
+ * the Merkle multiproof of that tree for the sorted distinct positions opened in it: with K_d those positions at the leaf level d, for
+ * l = d .. 1 every x of K_l, ascending, contributes the node (l, x ^ 1) iff x ^ 1 is not in K_l, and K_(l-1) is the set of parents
+ * (the order of cstark_ledger_open_multi).  A leaf is the hash of its row and a parent the hash of its two children, as in the plain
+ * form.  Every other byte -- header words, roots, frame, nonce, all rows in the same order (rows keep their multiplicity when positions
+ * repeat), remainder -- is the plain form's: the channel seed does not contain the form, so both forms of one statement under one
+ * option set open the same positions.  n_nodes <= n_positions * depth is a layout matter (MALFORMED); whether it is the count the
+ * re-derived positions ask for is part of that tree's opening check. */
 #define CSTARK_PROOF_VERSION 1
+#define CSTARK_FORM_PLAIN   0
+#define CSTARK_FORM_COMPACT 1
+/* The form of the proofs the context's provers write: cstark_tx_prove, cstark_air_prove, cstark_rescue_prove, cstark_range_prove_bits and
+ * cstark_range_prove_batch, on either Fiat-Shamir channel.  CSTARK_FORM_PLAIN is the default and any other value than the two is
+ * CSTARK_ERR_INVALID_ARG.  The compact form is selected on the host from the same gathered openings: no launch, copy or wait is added
+ * (the device channel's result block carries the positions too).  cstark_tx_proof_size_bound is a sufficient capacity for both
+ * forms.  The sharded phases write the plain form only: cstark_tx_shard_commit and cstark_tx_shard_finish return
+ * CSTARK_ERR_UNSUPPORTED while the compact form is set. */
+int cstark_ctx_set_proof_form(cstark_ctx *ctx, uint32_t form);
+int cstark_ctx_proof_form(cstark_ctx *ctx, uint32_t *form);
 #define CSTARK_PROVE_NUM_STAGES 10
 int cstark_tx_prove(cstark_ctx *ctx, const cstark_options *opt, uint8_t *proof, size_t capacity, size_t *proof_len);
 /* The same for the standalone AIRs (MerkleExample / SchnorrExample / RangeProofExample ::prove, src/merkle/update/mod.rs:84-107,
@@ -772,7 +793,8 @@ int cstark_account_check_update(cstark_ctx *ctx, uint32_t depth, uint32_t count,
 /* ---- verification (TransactionExample::verify, src/lib.rs:144-150: winterfell::verify over this library's own proof layout) -------
  * The call's status (cstark_status) is kept apart from the proof's verdict.  A verdict names the FIRST check that fails, in this
  * order: layout (MALFORMED, then UNSUPPORTED) | OPTIONS_MISMATCH | OOD | REMAINDER_COMMITMENT | POW | per query q = 0..nq-1:
- * TRACE_OPENING(q), COMPOSITION_OPENING(q) | per FRI layer l: LAYER_COUNT(l), LAYER_OPENING(l), LAYER_FOLDING(l) (layer 0: the DEEP
+ * TRACE_OPENING(q), COMPOSITION_OPENING(q) (a compact proof: TRACE_OPENING, then COMPOSITION_OPENING, one multiproof each: a wrong
+ * n_nodes, a wrong node or a wrong row of the tree) | per FRI layer l: LAYER_COUNT(l), LAYER_OPENING(l), LAYER_FOLDING(l) (layer 0: the DEEP
  * values against the layer-0 rows) | REMAINDER_FOLDING | REMAINDER_DEGREE.  A field element word >= p anywhere in the proof is
  * MALFORMED (the prover never writes one). */
 typedef enum cstark_verdict {
@@ -802,6 +824,9 @@ typedef struct cstark_proof_info {
  * enforces) and fills *info (zeroed when the header cannot be read).  *verdict = CSTARK_PROOF_OK or CSTARK_PROOF_MALFORMED; field
  * elements are not read (their canonical form is checked by cstark_tx_verify).  Returns CSTARK_ERR_INVALID_ARG only for null pointers. */
 int cstark_proof_inspect(const uint8_t *proof, size_t len, cstark_proof_info *info, int32_t *verdict);
+/* Host only: *form = CSTARK_FORM_PLAIN or CSTARK_FORM_COMPACT by the proof's magic; CSTARK_ERR_INVALID_ARG for null pointers, fewer than
+ * four bytes or neither magic.  Says nothing about the rest of the layout (cstark_proof_inspect accepts both forms). */
+int cstark_proof_form(const uint8_t *proof, size_t len, uint32_t *form);
 
 /* TransactionExample::verify for `count` proofs in one call (count = 1 for a single proof).  initial_roots / final_roots: [count][7],
  * memory form.  expected: NULL = each proof's own options (the reference's semantics), else every proof must state exactly these.

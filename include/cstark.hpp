@@ -81,10 +81,24 @@ class Context {
         check(cstark_prove_channel(ctx_, &channel));
         return channel;
     }
+    // CSTARK_FORM_PLAIN (the default) / CSTARK_FORM_COMPACT: the form of the proofs every single-GPU prover of this context writes
+    void set_proof_form(uint32_t form) { check(cstark_ctx_set_proof_form(ctx_, form)); }
+    uint32_t proof_form() const {
+        uint32_t form = CSTARK_FORM_PLAIN;
+        check(cstark_ctx_proof_form(ctx_, &form));
+        return form;
+    }
 
   private:
     cstark_ctx *ctx_ = nullptr;
 };
+
+// CSTARK_FORM_PLAIN / CSTARK_FORM_COMPACT by the proof's magic (host only); throws when the bytes carry neither
+inline uint32_t proof_form(const std::vector<uint8_t> &proof) {
+    uint32_t form = CSTARK_FORM_PLAIN;
+    check(cstark_proof_form(proof.data(), proof.size(), &form));
+    return form;
+}
 
 // Series of transfers in the account tree (src/lib.rs:183-194).  Paths are [leaf, sibling_0 .. sibling_{depth-1}].
 struct TransactionMetadata {
