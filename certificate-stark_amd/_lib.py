@@ -67,6 +67,21 @@ def air_trace_shape(air, log_n):
 _lib = None
 
 
+def _declare_convert(lib):
+    """prototypes of the convert calls (include/cstark.h): their verify call's arguments, then form, out, capacities, out_lens,
+    verdicts.  A CSTARK_LIB library built before the calls existed loads without them; calling one then fails by name."""
+    if not hasattr(lib, "cstark_tx_convert"):
+        return
+    u8pp, sizes, i32p = C.POINTER(u8p), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)
+    options, tail = C.POINTER(OptionsStruct), [C.c_uint32, u8pp, sizes, sizes, i32p]
+    lib.cstark_proof_convert_bound.argtypes = [u8p, C.c_size_t, C.c_uint32, sizes]
+    lib.cstark_tx_convert.argtypes = [C.c_void_p, C.c_uint32, u8pp, sizes, u64p, u64p, options] + tail
+    lib.cstark_air_convert.argtypes = [C.c_void_p, C.c_uint32, u8pp, sizes, i32p, u64p, options] + tail
+    lib.cstark_schnorr_convert.argtypes = [C.c_void_p, C.c_uint32, u8pp, sizes, C.POINTER(SchnorrStatementStruct), options] + tail
+    for fn in (lib.cstark_proof_convert_bound, lib.cstark_tx_convert, lib.cstark_air_convert, lib.cstark_schnorr_convert):
+        fn.restype = C.c_int
+
+
 def load():
     """Returns the loaded library; raises if it has not been built (python -m certificate_stark_amd.build)."""
     global _lib
@@ -80,6 +95,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
         lib.cstark_last_error.restype = C.c_char_p
         lib.cstark_version.restype = C.c_char_p
+        _declare_convert(lib)
         _lib = lib
     return _lib
 

@@ -80,6 +80,36 @@ class TraceReport:
         return "TraceReport(%s)" % self
 
 
+class _Conversion:
+    """The output arguments of one cstark_*_convert call: one buffer per proof, sized by cstark_proof_convert_bound (a proof whose
+    layout does not parse has no bound and is never converted: its buffer is a single byte)"""
+
+    def __init__(self, backend, form):
+        if form not in backend.PROOF_FORMS:
+            raise ValueError("form is 'plain' or 'compact', not %r" % (form,))
+        self.form, self.bufs = backend.PROOF_FORMS.index(form), []
+
+    def allocate(self, proofs):
+        from .verify import convert_bound
+        for p in proofs:
+            try:
+                cap = convert_bound(p, self.form)
+            except ValueError:
+                cap = 1
+            self.bufs.append((C.c_uint8 * cap)())
+
+    def args(self, count):
+        out = (C.POINTER(C.c_uint8) * max(1, count))()
+        caps = (C.c_size_t * max(1, count))()
+        self.lens = (C.c_size_t * max(1, count))()
+        for i, b in enumerate(self.bufs):
+            out[i], caps[i] = C.cast(b, C.POINTER(C.c_uint8)), len(b)
+        return (C.c_uint32(self.form), out, caps, self.lens)
+
+    def results(self, verdicts):
+        return [bytes(memoryview(b)[:self.lens[i]]) if int(verdicts[i]) == 0 else None for i, b in enumerate(self.bufs)]
+
+
 class Backend:
     """One cstark_ctx bound to a torch device and the current torch stream."""
 
@@ -1028,10 +1058,15 @@ class Backend:
         """TransactionExample::verify for a list of proofs (bytes) or a ProofBatch, in one call.  initial_roots / final_roots: [count][7]
         (or [7] for every proof), memory form.  options: None = each proof's own options, else every proof must state exactly these.
         Returns the verdicts, int32 [count] (0 = accepted; names: certificate_stark_amd.VERDICTS)."""
+        return self._tx_call(self.lib.cstark_tx_verify, proofs, initial_roots, final_roots, options)
+
+    def _tx_call(self, fn, proofs, initial_roots, final_roots, options, convert=None):
+        """cstark_tx_verify, or cstark_tx_convert with convert = _Conversion: the arguments the two share"""
         count = len(proofs)
         verdicts = np.zeros(count, np.int32)
+        vp = verdicts.ctypes.data_as(C.POINTER(C.c_int32))
         if count == 0:
-            check(self.lib.cstark_tx_verify(self.ctx, C.c_uint32(0), None, None, None, None, None, verdicts.ctypes.data_as(C.POINTER(C.c_int32))))
+            check(fn(self.ctx, C.c_uint32(0), None, None, None, None, None, *((convert.args(0) if convert else ()) + (vp,))))
             return verdicts
         ptrs = (C.POINTER(C.c_uint8) * count)()
         lens = (C.c_size_t * count)()
@@ -1049,8 +1084,10 @@ class Backend:
         ir = np.ascontiguousarray(np.broadcast_to(np.asarray(initial_roots, np.uint64).reshape(-1, 7), (count, 7)))
         fr = np.ascontiguousarray(np.broadcast_to(np.asarray(final_roots, np.uint64).reshape(-1, 7), (count, 7)))
         o = None if options is None else C.byref(self._options_struct(options))
-        check(self.lib.cstark_tx_verify(self.ctx, C.c_uint32(count), ptrs, lens, ir.ctypes.data_as(u64p), fr.ctypes.data_as(u64p), o,
-                                        verdicts.ctypes.data_as(C.POINTER(C.c_int32))))
+        if convert:
+            convert.allocate(keep if isinstance(keep, list) else [bytes(p) for p in keep])
+        check(fn(self.ctx, C.c_uint32(count), ptrs, lens, ir.ctypes.data_as(u64p), fr.ctypes.data_as(u64p), o,
+                 *((convert.args(count) if convert else ()) + (vp,))))
         del keep
         return verdicts
 
@@ -1059,6 +1096,10 @@ class Backend:
         each proof is expected to be (Backend.AIR_*; one value for all, or one per proof).  public_inputs: [count][14] words (or [14] for
         every proof), memory form -- initial root | final root, seed | result, or the range number in word 0.  numbers (instead of
         public_inputs, RangeProofAir only): one number for all proofs or [count] numbers.  options: as for tx_verify.  Returns the verdicts, int32 [count]; SchnorrAir proofs are UNSUPPORTED here (schnorr_verify takes their statement)."""
+        return self._air_call(self.lib.cstark_air_verify, proofs, airs, public_inputs, options, numbers)
+
+    def _air_call(self, fn, proofs, airs, public_inputs, options, numbers, convert=None):
+        """cstark_air_verify, or cstark_air_convert with convert = _Conversion"""
         count = len(proofs)
         verdicts = np.zeros(count, np.int32)
         if count == 0:
@@ -1083,8 +1124,10 @@ class Backend:
                 raise ValueError("public_inputs must be [count][14] or [14]")
             pub = np.ascontiguousarray(np.broadcast_to(pub.reshape(-1, 14), (count, 14)))
         o = None if options is None else C.byref(self._options_struct(options))
-        check(self.lib.cstark_air_verify(self.ctx, C.c_uint32(count), ptrs, lens, ids.ctypes.data_as(C.POINTER(C.c_int32)),
-                                         pub.ctypes.data_as(u64p), o, verdicts.ctypes.data_as(C.POINTER(C.c_int32))))
+        if convert:
+            convert.allocate(keep)
+        check(fn(self.ctx, C.c_uint32(count), ptrs, lens, ids.ctypes.data_as(C.POINTER(C.c_int32)), pub.ctypes.data_as(u64p), o,
+                 *((convert.args(count) if convert else ()) + (verdicts.ctypes.data_as(C.POINTER(C.c_int32)),))))
         del keep
         return verdicts
 
@@ -1092,11 +1135,15 @@ class Backend:
         """cstark_schnorr_verify: SchnorrAir proofs (bytes) against their statements in one call.  statements: one (messages [n][28],
         sig_rx [n][6], sig_s [n][32]) triple per proof -- or an object with those attributes, such as a SchnorrExample -- memory form;
         the batch may mix numbers of signatures, hashes, extensions and options.  options: as for tx_verify.  Returns the verdicts, int32 [count]."""
+        return self._schnorr_call(self.lib.cstark_schnorr_verify, proofs, statements, options)
+
+    def _schnorr_call(self, fn, proofs, statements, options, convert=None):
+        """cstark_schnorr_verify, or cstark_schnorr_convert with convert = _Conversion"""
         count = len(proofs)
         verdicts = np.zeros(count, np.int32)
         vp = verdicts.ctypes.data_as(C.POINTER(C.c_int32))
         if count == 0:
-            check(self.lib.cstark_schnorr_verify(self.ctx, C.c_uint32(0), None, None, None, None, vp))
+            check(fn(self.ctx, C.c_uint32(0), None, None, None, None, *((convert.args(0) if convert else ()) + (vp,))))
             return verdicts
         if len(statements) != count:
             raise ValueError("one statement per proof")
@@ -1118,9 +1165,34 @@ class Backend:
             stm[i].n_sig = msg.shape[0]
             stm[i].messages, stm[i].sig_rx, stm[i].sig_s = msg.ctypes.data_as(u64p), rx.ctypes.data_as(u64p), s.ctypes.data_as(_lib.u8p)
         o = None if options is None else C.byref(self._options_struct(options))
-        check(self.lib.cstark_schnorr_verify(self.ctx, C.c_uint32(count), ptrs, lens, stm, o, vp))
+        if convert:
+            convert.allocate(keep)
+        check(fn(self.ctx, C.c_uint32(count), ptrs, lens, stm, o, *((convert.args(count) if convert else ()) + (vp,))))
         del keep, arrays
         return verdicts
+
+    # ---- conversion between the proof forms (cstark_tx_convert, cstark_air_convert, cstark_schnorr_convert) -----------------------
+    def tx_convert(self, proofs, initial_roots, final_roots, form, options=None):
+        """cstark_tx_convert: tx_verify that also writes every accepted proof in `form` ("plain" or "compact"), byte for byte what the
+        prover writes in that form; a proof already in it comes back unchanged.  Returns (converted, verdicts): converted[i] is the bytes,
+        or None where verdicts[i] is not OK; the verdicts are tx_verify's for the same arguments.  The prover's state and proof_form are
+        not touched."""
+        cv = _Conversion(self, form)
+        verdicts = self._tx_call(self.lib.cstark_tx_convert, proofs, initial_roots, final_roots, options, cv)
+        return cv.results(verdicts), verdicts
+
+    def air_convert(self, proofs, airs, public_inputs=None, form=None, options=None, numbers=None):
+        """cstark_air_convert: air_verify that also writes every accepted proof in `form`; returns (converted, verdicts) as tx_convert.  A
+        SchnorrAir proof is UNSUPPORTED here and not converted (schnorr_convert)."""
+        cv = _Conversion(self, form)
+        verdicts = self._air_call(self.lib.cstark_air_convert, proofs, airs, public_inputs, options, numbers, cv)
+        return cv.results(verdicts), verdicts
+
+    def schnorr_convert(self, proofs, statements, form, options=None):
+        """cstark_schnorr_convert: schnorr_verify that also writes every accepted proof in `form`; returns (converted, verdicts)"""
+        cv = _Conversion(self, form)
+        verdicts = self._schnorr_call(self.lib.cstark_schnorr_convert, proofs, statements, options, cv)
+        return cv.results(verdicts), verdicts
 
     def schnorr_public_at(self, messages, sig_rx, z):
         """cstark_schnorr_public_at: the 19 public-input columns and the 12 sequence-value polynomials of the statement at z (m words,

@@ -293,6 +293,56 @@ inline int parse_layout(const uint8_t *b, size_t len, Layout &L) {
     return CSTARK_PROOF_OK;
 }
 
+// ---- conversion between the forms ------------------------------------------------------------------------------------------------
+// Tree t of a parsed proof (0: trace, 1: composition, 2 + l: layer l): the rows opened in it, its depth, where its path section begins
+// in the proof (compact: at the count word) and how long it is.
+struct TreeSection { uint32_t count; unsigned depth; size_t at, bytes; };
+inline TreeSection tree_section(const Layout &L, unsigned t) {
+    const uint32_t count = t < 2 ? L.nq : L.npos[t - 2];
+    const unsigned depth = t < 2 ? L.log_N : layer_log_rows(L, t - 2);
+    const size_t paths = t == 0 ? L.tpaths : t == 1 ? L.cpaths : L.lpaths[t - 2];
+    if (L.form == CSTARK_FORM_COMPACT) return {count, depth, paths - 4, 4 + 32 * (size_t)L.nodes[t]};
+    return {count, depth, paths, 32 * (size_t)count * depth};
+}
+// a capacity that holds the parsed proof in `form` whatever its positions: the exact plain length (it follows from the header and every
+// layer's n_positions), plus one count word per tree for the compact form (a multiproof never holds more nodes than the paths it is
+// selected from)
+inline size_t convert_bound(const Layout &L, uint32_t form) {
+    return proof_size(L, L.npos) + (form == CSTARK_FORM_COMPACT ? 4 * (size_t)(2 + L.n_layers) : 0);
+}
+// The new path sections of a proof that changes its form, tree by tree.  To the plain form: data[t] = paths [count][depth][32] in proof
+// order (nodes[t] is not read).  To the compact form: data[t] = nodes[t] multiproof nodes in the canonical order.
+struct PathSections { const uint8_t *data[MAX_TREES]; uint32_t nodes[MAX_TREES]; };
+// `src` (parsed into L) in `form`: everything outside the path sections is copied, the magic states the form, every path section is
+// replaced by ps's.  A proof already in `form` is copied as it is (ps is not read).  *len is always set; a buffer that is null or too
+// small is left untouched and the call returns CSTARK_ERR_INVALID_ARG, as write_proof does.
+inline int convert_proof(const uint8_t *src, const Layout &L, uint32_t form, const PathSections &ps, uint8_t *dst, size_t capacity, size_t *len) {
+    const size_t src_len = L.rem + remainder_bytes(L);
+    const unsigned trees = 2 + L.n_layers;
+    const bool same = L.form == form, compact = form == CSTARK_FORM_COMPACT;
+    size_t n = src_len;
+    for (unsigned t = 0; !same && t < trees; t++) {
+        const TreeSection s = tree_section(L, t);
+        n = n - s.bytes + (compact ? 4 + 32 * (size_t)ps.nodes[t] : 32 * (size_t)s.count * s.depth);
+    }
+    *len = n;
+    if (!dst || capacity < n) return CSTARK_ERR_INVALID_ARG;
+    if (same) { memcpy(dst, src, src_len); return CSTARK_OK; }
+    size_t from = 0, to = 0;
+    for (unsigned t = 0; t < trees; t++) {
+        const TreeSection s = tree_section(L, t);
+        memcpy(dst + to, src + from, s.at - from);
+        to += s.at - from; from = s.at + s.bytes;
+        if (compact) { memcpy(dst + to, &ps.nodes[t], 4); to += 4; }
+        const size_t bytes = compact ? 32 * (size_t)ps.nodes[t] : 32 * (size_t)s.count * s.depth;
+        if (bytes) memcpy(dst + to, ps.data[t], bytes);
+        to += bytes;
+    }
+    memcpy(dst + to, src + from, src_len - from);
+    memcpy(dst, compact ? "CSTC" : "CSTK", 4);
+    return CSTARK_OK;
+}
+
 // every field element section below p (the kernels check the same on the device; this host scan runs only where no kernel reads the
 // proof: a proof whose options differ from the expected ones)
 inline bool elements_canonical(const uint8_t *b, const Layout &L) {

@@ -396,6 +396,221 @@ __global__ __launch_bounds__(128) void k_vfy_multi_open(const uint8_t *__restric
     if (tid == 0) slots[o.slot] = refused ? o.rank : (uint32_t)RK_NONE;
 }
 
+// ---- conversion between the proof forms (cstark_*_convert) -------------------------------------------------------------------------
+// The leaf digest of an opened row as eight words, the leaf step of k_vfy_multi_open.
+template <int HASH> __device__ __forceinline__ void multi_leaf(const uint8_t *row, uint32_t words, uint32_t (&cv)[8], bool &canonical) {
+    if constexpr (HASH == 0) b3_words(row, words, cv, canonical);
+    else {
+        uint64_t h[4];
+        sha3_words(row, words, h, canonical);
+#pragma unroll
+        for (int i = 0; i < 4; i++) { cv[2 * i] = (uint32_t)h[i]; cv[2 * i + 1] = (uint32_t)(h[i] >> 32); }
+    }
+}
+// Compact -> plain: k_vfy_multi_open for a tree whose proof is being expanded, launched instead of it: the same leaves, sort, collapse,
+// fold and result slot, and beside them the tree's paths [count][depth][32] at byte out_at[blockIdx.x] of the output block `outb` (the
+// host sized that region from the parsed layout; out_at is a multiple of 32).  The paths fall out of the fold: at level l every entry of the ascending
+// list knows its sibling digest -- the neighbouring entry of a pair, or the proof node a single consumes -- and where its parent lands
+// in the next list (its own `at`; a right half: its left neighbour's, at - 1).  Both go to LDS (sib, nxt); the thread of opened row q
+// holds the index of the entry its position is below, stores that entry's sibling as entry depth - l of path q and follows nxt.  The
+// sorted list is treated alike: nxt of sorted place r is the entry it collapsed to, so equal positions get equal paths.  A refused tree
+// writes nothing or digests it has in hand, inside its own region; a node index at or past n_nodes is never read.
+template <int HASH>
+__global__ __launch_bounds__(128) void k_vfy_multi_expand(const uint8_t *__restrict__ buf, const VDesc *__restrict__ desc, const VMulti *__restrict__ trees,
+                                                          const uint64_t *__restrict__ tbase, uint32_t *__restrict__ slots,
+                                                          const uint64_t *__restrict__ out_at, uint8_t *__restrict__ outb) {
+    __shared__ uint32_t dig[2][128][8];
+    __shared__ uint32_t key[2][128];
+    __shared__ uint32_t sib[128][8];
+    __shared__ uint32_t nxt[128];
+    __shared__ uint32_t cnt[2][2];
+    const VMulti o = trees[blockIdx.x];
+    const VDesc &d = desc[o.proof];
+    const uint8_t *pb = buf + d.base;
+    const uint64_t *tb = tbase + d.tb;
+    const TOff to = toff(d);
+    const uint32_t tid = threadIdx.x;
+    const bool placed = o.layer == VNO_LAYER || o.layer < (uint32_t)tb[to.st]; // uniform: the tree's positions are known
+    bool canonical = true, bad = false;
+    uint32_t cv[8] = {}, pos = 0xffffffffu;
+    if (tid < o.count) {
+        multi_leaf<HASH>(pb + o.rows + 8 * (size_t)tid * o.words, o.words, cv, canonical);
+        if (placed) pos = o.layer == VNO_LAYER ? (uint32_t)tb[to.pos + tid] : (uint32_t)tb[to.lpos + o.layer * d.nq + tid];
+    }
+    key[0][tid] = pos;
+    const int malformed = __syncthreads_or(!canonical);
+    if (malformed || !placed) {
+        if (tid == 0) slots[o.slot] = malformed ? (uint32_t)RK_MALFORMED : (uint32_t)RK_NONE;
+        return;
+    }
+    // ---- sort into buffer 1, collapse into buffer 0
+    uint32_t entry = 0; // row tid's place in the list at hand: sorted place, then the entry above it level by level
+    if (tid < o.count) {
+        uint32_t r = 0;
+        for (uint32_t j = 0; j < o.count; j++) {
+            const uint32_t kj = key[0][j];
+            r += (kj < pos || (kj == pos && j < tid)) ? 1u : 0u;
+        }
+        key[1][r] = pos;
+#pragma unroll
+        for (int i = 0; i < 8; i++) dig[1][r][i] = cv[i];
+        entry = r;
+    }
+    __syncthreads();
+    uint32_t n, used = 0;
+    {
+        bool first = false;
+        if (tid < o.count) {
+            pos = key[1][tid];
+            first = tid == 0 || key[1][tid - 1] != pos;
+#pragma unroll
+            for (int i = 0; i < 8; i++) { cv[i] = dig[1][tid][i]; if (!first) bad |= cv[i] != dig[1][tid - 1][i]; }
+        }
+        uint32_t at, unused0, unused1;
+        multi_scan(cnt, first, false, at, unused0, n, unused1);
+        if (first) {
+            key[0][at] = pos;
+#pragma unroll
+            for (int i = 0; i < 8; i++) dig[0][at][i] = cv[i];
+        }
+        if (tid < o.count) nxt[tid] = first ? at : at - 1; // not first: tid > 0 and a first lies before it, so at >= 1
+        __syncthreads();
+        if (tid < o.count) entry = nxt[entry];
+    }
+    // ---- fold
+    uint8_t *paths = outb + out_at[blockIdx.x] + 32 * (size_t)tid * o.depth; // row tid's path (tid < count)
+    uint32_t cur = 0;
+    for (uint32_t l = o.depth; l >= 1; l--) {
+        const bool in = tid < n;
+        const uint32_t x = in ? key[cur][tid] : 0u;
+        const bool right_half = in && (x & 1) && tid > 0 && key[cur][tid - 1] == x - 1;
+        const bool left_half = in && !(x & 1) && tid + 1 < n && key[cur][tid + 1] == x + 1;
+        const bool parent = in && !right_half, single = parent && !left_half;
+        uint32_t at, node, n_next, n_single;
+        multi_scan(cnt, parent, single, at, node, n_next, n_single); // its barrier: every row has read sib and nxt of the level below
+        if (in) {
+            uint32_t own[8], sb[8];
+            const uint32_t other = right_half ? tid - 1 : tid + 1;
+#pragma unroll
+            for (int i = 0; i < 8; i++) own[i] = dig[cur][tid][i];
+            if (left_half || right_half) {
+#pragma unroll
+                for (int i = 0; i < 8; i++) sb[i] = dig[cur][other][i];
+            } else if (used + node < o.n_nodes) {
+                const uint32_t *src = reinterpret_cast<const uint32_t *>(pb + o.nodes + 32 * (size_t)(used + node));
+#pragma unroll
+                for (int i = 0; i < 8; i++) sb[i] = src[i];
+            } else { // the proof states fewer nodes than the positions ask for
+                bad = true;
+#pragma unroll
+                for (int i = 0; i < 8; i++) sb[i] = 0;
+            }
+#pragma unroll
+            for (int i = 0; i < 8; i++) sib[tid][i] = sb[i];
+            nxt[tid] = right_half ? at - 1 : at; // a right half: its left neighbour is a parent before it, so at >= 1
+            if (parent) {
+                uint32_t out[8];
+                if (x & 1) multi_parent<HASH>(sb, own, out);
+                else multi_parent<HASH>(own, sb, out);
+                key[cur ^ 1][at] = x >> 1;
+#pragma unroll
+                for (int i = 0; i < 8; i++) dig[cur ^ 1][at][i] = out[i];
+            }
+        }
+        __syncthreads();
+        if (tid < o.count) { // entry < n: it came from nxt of the level below, which is below n_next there
+            uint4 *dst = reinterpret_cast<uint4 *>(paths + 32 * (size_t)(o.depth - l));
+            dst[0] = make_uint4(sib[entry][0], sib[entry][1], sib[entry][2], sib[entry][3]);
+            dst[1] = make_uint4(sib[entry][4], sib[entry][5], sib[entry][6], sib[entry][7]);
+            entry = nxt[entry];
+        }
+        n = n_next; used += n_single; cur ^= 1;
+    }
+    // ---- verdict
+    if (tid == 0) {
+        const uint32_t *root = reinterpret_cast<const uint32_t *>(pb + o.root);
+        bad |= n != 1 || used != o.n_nodes;
+        for (int i = 0; i < 8; i++) bad |= dig[cur][0][i] != root[i];
+    }
+    const int refused = __syncthreads_or(bad);
+    if (tid == 0) slots[o.slot] = refused ? o.rank : (uint32_t)RK_NONE;
+}
+
+// Plain -> compact: one tree of a plain proof that is being compacted (its verdict stays k_vfy_openings').  paths: byte offset of the
+// tree's paths [count][depth][32] inside the proof; the selected nodes go to byte `out` of the output block (room for count * depth of
+// them) and their number to counts[index].
+struct VSelect { uint32_t proof, paths, depth, layer, count, index; uint64_t out; };
+// One workgroup of 128 threads per tree, no hashing: select_multiproof (proof_layout.h) on the device.  The positions are ranked and
+// collapsed in LDS as in k_vfy_multi_open, every entry carrying one row below it (of equal positions the first in proof order, of a
+// pair the left half's, as the host's `below`); the levels are walked on the keys alone, and a single entry x at level l copies entry
+// depth - l of its row's path -- node (l, x ^ 1) -- to node slot used + node.  A layer from the first one whose count differs from the
+// derived positions has none (the proof's verdict is LAYER_COUNT and it is not converted): its count stays 0.
+__global__ __launch_bounds__(128) void k_vfy_multi_select(const uint8_t *__restrict__ buf, const VDesc *__restrict__ desc, const VSelect *__restrict__ trees,
+                                                          const uint64_t *__restrict__ tbase, uint32_t *__restrict__ counts, uint8_t *__restrict__ outb) {
+    __shared__ uint32_t key[2][128];
+    __shared__ uint32_t row[2][128];
+    __shared__ uint32_t cnt[2][2];
+    const VSelect o = trees[blockIdx.x];
+    const VDesc &d = desc[o.proof];
+    const uint8_t *pb = buf + d.base;
+    const uint64_t *tb = tbase + d.tb;
+    const TOff to = toff(d);
+    const uint32_t tid = threadIdx.x;
+    if (o.layer != VNO_LAYER && o.layer >= (uint32_t)tb[to.st]) { // uniform
+        if (tid == 0) counts[o.index] = 0;
+        return;
+    }
+    uint32_t pos = 0xffffffffu;
+    if (tid < o.count) pos = o.layer == VNO_LAYER ? (uint32_t)tb[to.pos + tid] : (uint32_t)tb[to.lpos + o.layer * d.nq + tid];
+    key[0][tid] = pos;
+    __syncthreads();
+    if (tid < o.count) {
+        uint32_t r = 0;
+        for (uint32_t j = 0; j < o.count; j++) {
+            const uint32_t kj = key[0][j];
+            r += (kj < pos || (kj == pos && j < tid)) ? 1u : 0u;
+        }
+        key[1][r] = pos;
+        row[1][r] = tid;
+    }
+    __syncthreads();
+    uint32_t n, used = 0;
+    {
+        bool first = false;
+        uint32_t q = 0;
+        if (tid < o.count) {
+            pos = key[1][tid];
+            q = row[1][tid];
+            first = tid == 0 || key[1][tid - 1] != pos;
+        }
+        uint32_t at, unused0, unused1;
+        multi_scan(cnt, first, false, at, unused0, n, unused1);
+        if (first) { key[0][at] = pos; row[0][at] = q; }
+        __syncthreads();
+    }
+    const uint32_t room = o.count * o.depth; // node slots of the tree's region
+    uint32_t cur = 0;
+    for (uint32_t l = o.depth; l >= 1; l--) {
+        const bool in = tid < n;
+        const uint32_t x = in ? key[cur][tid] : 0u, q = in ? row[cur][tid] : 0u;
+        const bool right_half = in && (x & 1) && tid > 0 && key[cur][tid - 1] == x - 1;
+        const bool left_half = in && !(x & 1) && tid + 1 < n && key[cur][tid + 1] == x + 1;
+        const bool parent = in && !right_half, single = parent && !left_half;
+        uint32_t at, node, n_next, n_single;
+        multi_scan(cnt, parent, single, at, node, n_next, n_single);
+        if (single && used + node < room) { // always: a multiproof never holds more nodes than the paths it is selected from
+            const uint32_t *src = reinterpret_cast<const uint32_t *>(pb + o.paths + 32 * ((size_t)q * o.depth + (o.depth - l)));
+            uint4 *dst = reinterpret_cast<uint4 *>(outb + o.out + 32 * (size_t)(used + node));
+            dst[0] = make_uint4(src[0], src[1], src[2], src[3]);
+            dst[1] = make_uint4(src[4], src[5], src[6], src[7]);
+        }
+        if (parent) { key[cur ^ 1][at] = x >> 1; row[cur ^ 1][at] = q; }
+        __syncthreads();
+        n = n_next; used += n_single; cur ^= 1;
+    }
+    if (tid == 0) counts[o.index] = used < room ? used : room;
+}
+
 template <int R, class F> __device__ __forceinline__ void static_down(F &&f) {
     f(std::integral_constant<int, R>{});
     if constexpr (R > 0) static_down<R - 1>(f);
@@ -1055,6 +1270,8 @@ struct VerifyArena {
     float ms[CSTARK_VERIFY_NUM_STAGES] = {};
     uint64_t h2d_bytes = 0;              // bytes copied host -> device by the last verify call
     bool timed = false;
+    uint8_t *h_out = nullptr;            // convert calls: the new path sections of a chunk, copied back (pinned)
+    size_t out_bytes = 0;
 };
 
 void verify_arena_free(VerifyArena *a) {
@@ -1063,6 +1280,7 @@ void verify_arena_free(VerifyArena *a) {
     if (a->d_stage) (void)hipFree(a->d_stage);
     if (a->d_scratch) (void)hipFree(a->d_scratch);
     if (a->h_verdicts) (void)hipHostFree(a->h_verdicts);
+    if (a->h_out) (void)hipHostFree(a->h_out);
     if (a->d_pcoef) (void)hipFree(a->d_pcoef);
     for (hipEvent_t e : a->ev) if (e) (void)hipEventDestroy(e);
     delete a;
@@ -1077,7 +1295,11 @@ struct Staged {
     Layout L;
     VDesc d;
     uint32_t D;         // the AIR's largest constraint degree (AirInfo)
+    size_t out_at[MAX_TREES] = {}; // convert calls, a proof that changes its form: where tree t's new section lies in the output block
+    uint32_t count_at = 0;         // ... to the compact form: its trees' node counts are counts[count_at + t]
 };
+// What a convert call adds to a verify call: the target form and the caller's buffers (verify_batch has checked the capacities).
+struct Convert { uint32_t form; uint8_t *const *out; const size_t *capacities; size_t *out_lens; };
 // the proofs of one (AIR, extension degree) of a chunk: their list, the frames sampled for them (K each) and the constraint values
 struct Group {
     uint32_t start = 0, count = 0, K = 0, frames = 0, tiles = 0; // tiles: SchnorrAir, those of the group's largest statement
@@ -1284,7 +1506,7 @@ template <class T> T *carve(uint8_t *base, size_t &off, size_t count) {
 }
 
 // Verifies the staged proofs of one chunk; verdicts[i] for staged[i].
-int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *out, double host_ms) {
+int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *out, double host_ms, const Convert *cv) {
     const hipStream_t s = c->stream;
     const uint32_t P = (uint32_t)st.size();
     // ---- staging block: proofs (a SchnorrAir proof is followed by its statement) | descriptors | openings | group lists; the transcript
@@ -1292,6 +1514,7 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
     size_t off = 0, t_words = 0, sp_words = 0;
     std::vector<size_t> pofs(P), tofs(P);
     size_t n_open = 0, n_multi = 0, n_slots = 0; // opened rows of the plain proofs, trees of the compact ones
+    size_t n_expand = 0, n_select = 0, out_bytes = 0; // convert calls: trees to expand (among n_multi), trees to select from, the output block
     for (uint32_t i = 0; i < P; i++) {
         const Layout &L = st[i].L;
         off = (off + 15) & ~(size_t)15; pofs[i] = off; off += L.rem + 8 * (size_t)L.R * L.m;
@@ -1307,12 +1530,26 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
         st[i].d.n_open = no;
         st[i].d.slot0 = (uint32_t)n_slots;
         n_slots += 1 + no + L.nq + L.m;
+        if (cv && L.form != cv->form) { // the output block holds every tree's paths: the new sections, or room for the nodes selected from them
+            if (L.form == CSTARK_FORM_COMPACT) n_expand += 2 + L.n_layers;
+            else { st[i].count_at = (uint32_t)n_select; n_select += 2 + L.n_layers; }
+            for (uint32_t t = 0; t < 2 + L.n_layers; t++) {
+                const uint32_t np = t < 2 ? L.nq : L.npos[t - 2];
+                st[i].out_at[t] = out_bytes;
+                out_bytes += 32 * (size_t)np * (t < 2 ? L.log_N : layer_log_rows(L, t - 2));
+            }
+        }
     }
     const size_t desc_off = (off + 15) & ~(size_t)15;
     const size_t open_off = (desc_off + P * sizeof(VDesc) + 15) & ~(size_t)15;
     const size_t multi_off = (open_off + n_open * sizeof(VOpen) + 15) & ~(size_t)15; // (no compact proof: empty, the block is as before)
     const size_t grp_off = (multi_off + n_multi * sizeof(VMulti) + 15) & ~(size_t)15;
-    const size_t total = grp_off + (size_t)P * 4 + 16;
+    // a convert call: behind the group lists, the output offset of every tree that is expanded (in the order of their records) and the
+    // trees that are selected from.  A verify call stages what it staged.
+    const size_t xat_off = (grp_off + (size_t)P * 4 + 15) & ~(size_t)15;
+    const size_t sel_off = (xat_off + n_expand * sizeof(uint64_t) + 15) & ~(size_t)15;
+    const size_t copy_bytes = cv ? sel_off + n_select * sizeof(VSelect) : grp_off + (size_t)P * 4;
+    const size_t total = copy_bytes + 16;
     if (total > a->stage_bytes) {
         HIP_TRY(hipStreamSynchronize(s));
         if (a->h_stage) { HIP_TRY(hipHostFree(a->h_stage)); a->h_stage = nullptr; }
@@ -1341,6 +1578,10 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
     opens.reserve(n_open);
     std::vector<VMulti> multis;
     multis.reserve(n_multi);
+    std::vector<std::pair<VMulti, uint64_t>> expands; // convert calls: the trees of the proofs that are expanded, and where their paths go
+    std::vector<VSelect> selects;                     // ... the trees of the proofs that are compacted
+    expands.reserve(n_expand);
+    selects.reserve(n_select);
     for (uint32_t i = 0; i < P; i++) {
         Staged &S = st[i];
         const Layout &L = S.L;
@@ -1371,13 +1612,26 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
         const uint32_t TW = d.a.w, TCE = d.a.ce;
         const uint32_t hash = L.opt[3];
         uint32_t sl = d.slot0 + 1;
+        const bool changes = cv && L.form != cv->form;
         if (L.form == CSTARK_FORM_COMPACT) { // one entry per tree, in the verdict order: trace, composition, the layers
-            multis.push_back(VMulti{i, (uint32_t)L.trows, (uint32_t)L.tpaths, L.nodes[0], 52u, TW, L.log_N, VNO_LAYER, L.nq, RK_OPENING0, sl++, hash});
-            multis.push_back(VMulti{i, (uint32_t)L.crows, (uint32_t)L.cpaths, L.nodes[1], 84u, TCE * L.m, L.log_N, VNO_LAYER, L.nq, RK_OPENING0 + 1, sl++, hash});
+            uint32_t t = 0;
+            auto tree = [&](const VMulti &m) { // a proof that is expanded: the same record, for k_vfy_multi_expand
+                if (changes) expands.emplace_back(m, (uint64_t)S.out_at[t]);
+                else multis.push_back(m);
+                t++;
+            };
+            tree(VMulti{i, (uint32_t)L.trows, (uint32_t)L.tpaths, L.nodes[0], 52u, TW, L.log_N, VNO_LAYER, L.nq, RK_OPENING0, sl++, hash});
+            tree(VMulti{i, (uint32_t)L.crows, (uint32_t)L.cpaths, L.nodes[1], 84u, TCE * L.m, L.log_N, VNO_LAYER, L.nq, RK_OPENING0 + 1, sl++, hash});
             for (uint32_t l = 0; l < L.n_layers; l++)
-                multis.push_back(VMulti{i, (uint32_t)L.lrows[l], (uint32_t)L.lpaths[l], L.nodes[2 + l], (uint32_t)(120 + 32 * l), L.f * L.m,
-                                        layer_log_rows(L, l), l, L.npos[l], RK_LAYER0 + 3 * l + 1, sl++, hash});
+                tree(VMulti{i, (uint32_t)L.lrows[l], (uint32_t)L.lpaths[l], L.nodes[2 + l], (uint32_t)(120 + 32 * l), L.f * L.m,
+                            layer_log_rows(L, l), l, L.npos[l], RK_LAYER0 + 3 * l + 1, sl++, hash});
             continue;
+        }
+        if (changes) { // a plain proof that is compacted: its opening records below as ever, and one selection per tree
+            selects.push_back(VSelect{i, (uint32_t)L.tpaths, L.log_N, VNO_LAYER, L.nq, S.count_at, (uint64_t)S.out_at[0]});
+            selects.push_back(VSelect{i, (uint32_t)L.cpaths, L.log_N, VNO_LAYER, L.nq, S.count_at + 1, (uint64_t)S.out_at[1]});
+            for (uint32_t l = 0; l < L.n_layers; l++)
+                selects.push_back(VSelect{i, (uint32_t)L.lpaths[l], layer_log_rows(L, l), l, L.npos[l], S.count_at + 2 + l, (uint64_t)S.out_at[2 + l]});
         }
         for (uint32_t q = 0; q < L.nq; q++) {
             opens.push_back(VOpen{i, (uint32_t)(L.trows + 8 * (size_t)q * TW), (uint32_t)(L.tpaths + 32 * (size_t)q * L.log_N), 52u, TW, L.log_N,
@@ -1404,6 +1658,14 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
     // the trees of one hash side by side: one launch of k_vfy_multi_open per hash present
     const size_t n_multi_b3 = std::stable_partition(multis.begin(), multis.end(), [](const VMulti &x) { return x.hash == 0; }) - multis.begin();
     if (n_multi) memcpy(hm, multis.data(), multis.size() * sizeof(VMulti));
+    // behind them the trees that are expanded, again one hash after the other, each with its place in the output block
+    const size_t n_open_multi = multis.size();
+    const size_t n_expand_b3 = std::stable_partition(expands.begin(), expands.end(), [](const std::pair<VMulti, uint64_t> &x) { return x.first.hash == 0; }) - expands.begin();
+    for (size_t k = 0; k < n_expand; k++) {
+        hm[n_open_multi + k] = expands[k].first;
+        reinterpret_cast<uint64_t *>(H + xat_off)[k] = expands[k].second;
+    }
+    if (n_select) memcpy(H + sel_off, selects.data(), n_select * sizeof(VSelect));
     const auto t1 = std::chrono::steady_clock::now();
     host_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
 
@@ -1417,6 +1679,9 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
             const VAir &A = air_info(g / 3).a;
             need += 8 * (size_t)grp[g].frames * (2 * A.w + A.nper + A.naux + A.nc) + 4 * (size_t)grp[g].count + 5 * 16;
         }
+    // a convert call: the output block behind them -- the node counts of the selected trees, then every changing tree's region
+    const size_t counts_bytes = (4 * n_select + 31) & ~(size_t)31, block_bytes = counts_bytes + out_bytes;
+    if (block_bytes) need += block_bytes + 16;
     if (need > a->scratch_bytes) {
         HIP_TRY(hipStreamSynchronize(s));
         if (a->d_scratch) { HIP_TRY(hipFree(a->d_scratch)); a->d_scratch = nullptr; }
@@ -1445,6 +1710,13 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
         grp[g].val = carve<fp>(D, so, (size_t)grp[g].frames * A.nc);
         grp[g].bad = carve<uint32_t>(D, so, grp[g].count);
     }
+    uint8_t *d_block = block_bytes ? carve<uint8_t>(D, so, block_bytes) : nullptr;
+    if (block_bytes > a->out_bytes) {
+        if (a->h_out) { HIP_TRY(hipHostFree(a->h_out)); a->h_out = nullptr; }
+        a->out_bytes = 0;
+        HIP_TRY(hipHostMalloc(&a->h_out, block_bytes, hipHostMallocDefault));
+        a->out_bytes = block_bytes;
+    }
     const uint8_t *dbuf = a->d_stage;
     const VDesc *d_desc = reinterpret_cast<const VDesc *>(dbuf + desc_off);
     const VOpen *d_open = reinterpret_cast<const VOpen *>(dbuf + open_off);
@@ -1454,7 +1726,6 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
     for (int e = 0; e < VFY_EVENTS; e++)
         if (!a->ev[e]) HIP_TRY(hipEventCreate(&a->ev[e]));
     HIP_TRY(hipEventRecord(a->ev[0], s));
-    const size_t copy_bytes = grp_off + (size_t)P * 4;
     HIP_TRY(hipMemcpyAsync(a->d_stage, H, copy_bytes, hipMemcpyHostToDevice, s));
     a->h2d_bytes += copy_bytes;
     HIP_TRY(hipEventRecord(a->ev[1], s));
@@ -1494,8 +1765,25 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
         hipLaunchKernelGGL(k_vfy_multi_open<0>, dim3((unsigned)n_multi_b3), dim3(128), 0, s, dbuf, d_desc, d_multi, d_tb, d_slots);
         HIP_TRY(hipGetLastError());
     }
-    if (n_multi > n_multi_b3) {
-        hipLaunchKernelGGL(k_vfy_multi_open<1>, dim3((unsigned)(n_multi - n_multi_b3)), dim3(128), 0, s, dbuf, d_desc, d_multi + n_multi_b3, d_tb, d_slots);
+    if (n_open_multi > n_multi_b3) {
+        hipLaunchKernelGGL(k_vfy_multi_open<1>, dim3((unsigned)(n_open_multi - n_multi_b3)), dim3(128), 0, s, dbuf, d_desc, d_multi + n_multi_b3, d_tb, d_slots);
+        HIP_TRY(hipGetLastError());
+    }
+    // a convert call: the trees that are expanded fold in k_vfy_multi_expand instead, the plain proofs that are compacted are selected from
+    const uint64_t *d_xat = reinterpret_cast<const uint64_t *>(dbuf + xat_off);
+    uint8_t *d_out = d_block + counts_bytes;
+    if (n_expand_b3) {
+        hipLaunchKernelGGL(k_vfy_multi_expand<0>, dim3((unsigned)n_expand_b3), dim3(128), 0, s, dbuf, d_desc, d_multi + n_open_multi, d_tb, d_slots, d_xat, d_out);
+        HIP_TRY(hipGetLastError());
+    }
+    if (n_expand > n_expand_b3) {
+        hipLaunchKernelGGL(k_vfy_multi_expand<1>, dim3((unsigned)(n_expand - n_expand_b3)), dim3(128), 0, s, dbuf, d_desc, d_multi + n_open_multi + n_expand_b3,
+                           d_tb, d_slots, d_xat + n_expand_b3, d_out);
+        HIP_TRY(hipGetLastError());
+    }
+    if (n_select) {
+        hipLaunchKernelGGL(k_vfy_multi_select, dim3((unsigned)n_select), dim3(128), 0, s, dbuf, d_desc, reinterpret_cast<const VSelect *>(dbuf + sel_off), d_tb,
+                           reinterpret_cast<uint32_t *>(d_block), d_out);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(a->ev[4], s));
@@ -1523,6 +1811,39 @@ int run_chunk(cstark_ctx *c, VerifyArena *a, std::vector<Staged> &st, int32_t *o
         HIP_TRY(hipEventElapsedTime(&t, a->ev[e - 1], a->ev[e]));
         a->ms[e] += t;
     }
+    if (!cv) return CSTARK_OK;
+    // ---- a convert call: the accepted proofs in the target form.  One copy back of the part of the output block that accepted proofs
+    // own (and the selected trees' counts), after the verdicts: nothing is copied for a chunk without an accepted proof that changes.
+    size_t lo = out_bytes, hi = 0;
+    bool selected = false;
+    for (uint32_t i = 0; i < P; i++) {
+        const Layout &L = st[i].L;
+        if (a->h_verdicts[i] != CSTARK_PROOF_OK || L.form == cv->form) continue;
+        const TreeSection last = tree_section(L, 1 + L.n_layers);
+        lo = std::min(lo, st[i].out_at[0]);
+        hi = std::max(hi, st[i].out_at[1 + L.n_layers] + 32 * (size_t)last.count * last.depth);
+        selected |= L.form == CSTARK_FORM_PLAIN;
+    }
+    const auto c0 = std::chrono::steady_clock::now();
+    if (selected) HIP_TRY(hipMemcpyAsync(a->h_out, d_block, 4 * n_select, hipMemcpyDeviceToHost, s));
+    if (hi > lo) HIP_TRY(hipMemcpyAsync(a->h_out + counts_bytes + lo, d_out + lo, hi - lo, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const auto c1 = std::chrono::steady_clock::now();
+    a->ms[VFY_EVENTS - 1] += (float)std::chrono::duration<double, std::milli>(c1 - c0).count();
+    const uint32_t *counts = reinterpret_cast<const uint32_t *>(a->h_out);
+    for (uint32_t i = 0; i < P; i++) {
+        const Layout &L = st[i].L;
+        if (a->h_verdicts[i] != CSTARK_PROOF_OK) continue;
+        PathSections ps{};
+        for (uint32_t t = 0; L.form != cv->form && t < 2 + L.n_layers; t++) {
+            ps.data[t] = a->h_out + counts_bytes + st[i].out_at[t];
+            if (L.form == CSTARK_FORM_PLAIN) ps.nodes[t] = counts[st[i].count_at + t];
+        }
+        const uint32_t at = st[i].index;
+        if (convert_proof(st[i].bytes, L, cv->form, ps, cv->out[at], cv->capacities[at], &cv->out_lens[at]) != CSTARK_OK)
+            return fail(CSTARK_ERR_INVALID_ARG, "convert: a proof does not fit the capacity that was checked");
+    }
+    a->ms[0] += (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c1).count();
     return CSTARK_OK;
 }
 
@@ -1554,13 +1875,17 @@ int cstark_proof_form(const uint8_t *proof, size_t len, uint32_t *form) {
 
 // All verify calls.  airs: the AIR the caller states for each proof (null: all TransactionAir); the 14 public words of proof i are
 // pub_lo[i * stride .. +7) | pub_hi[i * stride .. +7).  stm (cstark_schnorr_verify; then airs and the public words are null): every proof is
-// stated to be SchnorrAir's, with statement stm[i].
+// stated to be SchnorrAir's, with statement stm[i].  cv (the convert calls; null: a verify call): every accepted proof is also written to
+// the caller's buffer in cv->form; the verdicts are those of the verify call.
 static int verify_batch(const char *who, cstark_ctx *c, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens, const int32_t *airs,
                         const uint64_t *pub_lo, const uint64_t *pub_hi, size_t stride, const cstark_schnorr_statement *stm,
-                        const cstark_options *expected, int32_t *verdicts) {
+                        const cstark_options *expected, int32_t *verdicts, const Convert *cv = nullptr) {
     if (!c) return fail(CSTARK_ERR_INVALID_ARG, "%s: null context", who);
+    if (cv && cv->form != CSTARK_FORM_PLAIN && cv->form != CSTARK_FORM_COMPACT)
+        return fail(CSTARK_ERR_INVALID_ARG, "%s: form must be CSTARK_FORM_PLAIN or CSTARK_FORM_COMPACT", who);
     if (count == 0) return CSTARK_OK;
     if (!proofs || !proof_lens || (!stm && (!pub_lo || !pub_hi)) || !verdicts) return fail(CSTARK_ERR_INVALID_ARG, "%s: null argument", who);
+    if (cv && (!cv->out || !cv->capacities || !cv->out_lens)) return fail(CSTARK_ERR_INVALID_ARG, "%s: null output argument", who);
     for (uint32_t i = 0; stm && i < count; i++) {
         const cstark_schnorr_statement &S = stm[i];
         if (!S.messages || !S.sig_rx || !S.sig_s) return fail(CSTARK_ERR_INVALID_ARG, "%s: null statement array", who);
@@ -1580,6 +1905,19 @@ static int verify_batch(const char *who, cstark_ctx *c, uint32_t count, const ui
                 return fail(CSTARK_ERR_INVALID_ARG, "%s: a public input word is not a field element", who);
         if (!proofs[i] && proof_lens[i]) return fail(CSTARK_ERR_INVALID_ARG, "%s: null proof", who);
     }
+    // every capacity before anything is launched, for every proof whose layout parses: no output is written by a call that is refused
+    for (uint32_t i = 0; cv && i < count; i++) {
+        Layout L;
+        if (!proofs[i] || parse_layout(proofs[i], proof_lens[i], L) != CSTARK_PROOF_OK) continue;
+        const size_t bound = convert_bound(L, cv->form);
+        if (!cv->out[i] || cv->capacities[i] < bound) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "%s: the buffer of proof %u holds %zu bytes, cstark_proof_convert_bound asks for %zu", who, i,
+                     cv->out[i] ? cv->capacities[i] : (size_t)0, bound);
+            return fail(CSTARK_ERR_INVALID_ARG, "%s", msg);
+        }
+    }
+    for (uint32_t i = 0; cv && i < count; i++) cv->out_lens[i] = 0;
     HIP_TRY(hipSetDevice(c->device));
     if (!c->verify) c->verify = new VerifyArena();
     VerifyArena *a = c->verify;
@@ -1622,7 +1960,7 @@ static int verify_batch(const char *who, cstark_ctx *c, uint32_t count, const ui
                              sizeof(VOpen) * (2 + S.L.nq * (size_t)(2 + S.L.n_layers)) + 256;
         if (!st.empty() && chunk_bytes + bytes > VFY_CHUNK_BYTES) {
             host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            RC_TRY(run_chunk(c, a, st, verdicts, host_ms));
+            RC_TRY(run_chunk(c, a, st, verdicts, host_ms, cv));
             st.clear(); chunk_bytes = 0; host_ms = 0;
             t0 = std::chrono::steady_clock::now();
         }
@@ -1630,7 +1968,7 @@ static int verify_batch(const char *who, cstark_ctx *c, uint32_t count, const ui
         chunk_bytes += bytes;
     }
     host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (!st.empty()) RC_TRY(run_chunk(c, a, st, verdicts, host_ms));
+    if (!st.empty()) RC_TRY(run_chunk(c, a, st, verdicts, host_ms, cv));
     else a->ms[0] += (float)host_ms;
     a->timed = true;
     return CSTARK_OK;
@@ -1651,6 +1989,40 @@ int cstark_schnorr_verify(cstark_ctx *c, uint32_t count, const uint8_t *const *p
                           const cstark_options *expected, int32_t *verdicts) {
     if (c && count && !statements) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_verify: null argument");
     return verify_batch("cstark_schnorr_verify", c, count, proofs, proof_lens, nullptr, nullptr, nullptr, 0, statements, expected, verdicts);
+}
+
+int cstark_proof_convert_bound(const uint8_t *proof, size_t len, uint32_t form, size_t *bound) {
+    if (!proof || !bound) return fail(CSTARK_ERR_INVALID_ARG, "cstark_proof_convert_bound: null argument");
+    if (form != CSTARK_FORM_PLAIN && form != CSTARK_FORM_COMPACT)
+        return fail(CSTARK_ERR_INVALID_ARG, "cstark_proof_convert_bound: form must be CSTARK_FORM_PLAIN or CSTARK_FORM_COMPACT");
+    Layout L;
+    if (parse_layout(proof, len, L) != CSTARK_PROOF_OK) return fail(CSTARK_ERR_INVALID_ARG, "cstark_proof_convert_bound: the proof's layout does not parse");
+    *bound = convert_bound(L, form);
+    return CSTARK_OK;
+}
+
+int cstark_tx_convert(cstark_ctx *c, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens, const uint64_t *initial_roots,
+                      const uint64_t *final_roots, const cstark_options *expected, uint32_t form, uint8_t *const *out, const size_t *capacities,
+                      size_t *out_lens, int32_t *verdicts) {
+    const Convert cv{form, out, capacities, out_lens};
+    return verify_batch("cstark_tx_convert", c, count, proofs, proof_lens, nullptr, initial_roots, final_roots, 7, nullptr, expected, verdicts, &cv);
+}
+
+int cstark_air_convert(cstark_ctx *c, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens, const int32_t *airs,
+                       const uint64_t *public_inputs, const cstark_options *expected, uint32_t form, uint8_t *const *out, const size_t *capacities,
+                       size_t *out_lens, int32_t *verdicts) {
+    if (c && count && (!airs || !public_inputs)) return fail(CSTARK_ERR_INVALID_ARG, "cstark_air_convert: null argument");
+    const Convert cv{form, out, capacities, out_lens};
+    return verify_batch("cstark_air_convert", c, count, proofs, proof_lens, airs, public_inputs, public_inputs ? public_inputs + 7 : nullptr, 14, nullptr, expected,
+                        verdicts, &cv);
+}
+
+int cstark_schnorr_convert(cstark_ctx *c, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens, const cstark_schnorr_statement *statements,
+                           const cstark_options *expected, uint32_t form, uint8_t *const *out, const size_t *capacities, size_t *out_lens,
+                           int32_t *verdicts) {
+    if (c && count && !statements) return fail(CSTARK_ERR_INVALID_ARG, "cstark_schnorr_convert: null argument");
+    const Convert cv{form, out, capacities, out_lens};
+    return verify_batch("cstark_schnorr_convert", c, count, proofs, proof_lens, nullptr, nullptr, nullptr, 0, statements, expected, verdicts, &cv);
 }
 
 // k_vfy_schnorr_public + k_vfy_schnorr_public_sum for one statement and the caller's z, through a descriptor that holds what the two read

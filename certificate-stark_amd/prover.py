@@ -459,6 +459,12 @@ class TransactionExample:
         if v != 0:
             raise VerifierError(v)
 
+    def convert(self, proof, compact=True):
+        """the verified proof in the compact form (compact=False: the plain form), the bytes prove(compact=...) writes; raises
+        VerifierError when verify() would (cstark_tx_convert)"""
+        initial_root, final_root = self.pub_inputs()
+        return _converted_or_raise(*self.prover.backend.tx_convert([proof], initial_root, final_root, _form_name(compact)))
+
     def pub_inputs(self):
         return self.tx_metadata.initial_roots[0], self.tx_metadata.final_root
 
@@ -478,6 +484,22 @@ def _air_verify_or_raise(backend, proof, air, public_inputs=None, numbers=None):
     v = int(backend.air_verify([proof], air, public_inputs, numbers=numbers)[0])
     if v != 0:
         raise VerifierError(v)
+
+
+def _form_name(compact):
+    return "compact" if compact else "plain"
+
+
+def _converted_or_raise(converted, verdicts):
+    from .verify import VerifierError
+    if int(verdicts[0]) != 0:
+        raise VerifierError(int(verdicts[0]))
+    return converted[0]
+
+
+def _air_convert_or_raise(backend, proof, compact, air, public_inputs=None, numbers=None):
+    """_air_verify_or_raise that returns the proof in the other form (cstark_air_convert)"""
+    return _converted_or_raise(*backend.air_convert([proof], air, public_inputs, _form_name(compact), numbers=numbers))
 
 
 class _ResidentWitness:
@@ -532,6 +554,10 @@ class MerkleExample(_ResidentWitness):
     def verify(self, proof):
         """src/merkle/update/mod.rs:109-127; raises VerifierError on rejection, like TransactionExample.verify"""
         _air_verify_or_raise(self.backend, proof, Backend.AIR_MERKLE, np.concatenate(self.pub_inputs()))
+
+    def convert(self, proof, compact=True):
+        """as TransactionExample.convert"""
+        return _air_convert_or_raise(self.backend, proof, compact, Backend.AIR_MERKLE, np.concatenate(self.pub_inputs()))
 
     def validate(self, want_cycles=False, want_frame=False):
         """as TransactionExample.validate, for the MerkleAir trace of the witness"""
@@ -594,6 +620,10 @@ class SchnorrExample(_ResidentWitness):
         if v != 0:
             raise VerifierError(v)
 
+    def convert(self, proof, compact=True):
+        """as TransactionExample.convert, through cstark_schnorr_convert"""
+        return _converted_or_raise(*self.backend.schnorr_convert([proof], [self], _form_name(compact)))
+
     def validate(self, want_cycles=False, want_frame=False):
         """as TransactionExample.validate: the SchnorrAir trace against the resident statement; a forged signature shows as a failing
         boundary entry at the last row of its block (str(report): "boundary entry 55: register 0 at step 1023")"""
@@ -630,6 +660,10 @@ class RescueExample:
         """benches/rescue.rs:88-94; raises VerifierError on rejection"""
         _air_verify_or_raise(self.backend, proof, Backend.AIR_RESCUE_CHAIN, np.concatenate(self.pub_inputs()))
 
+    def convert(self, proof, compact=True):
+        """as TransactionExample.convert"""
+        return _air_convert_or_raise(self.backend, proof, compact, Backend.AIR_RESCUE_CHAIN, np.concatenate(self.pub_inputs()))
+
     def validate(self, want_cycles=False, want_frame=False):
         """as TransactionExample.validate: the chain's trace against seed and result"""
         trace = self.backend.rescue_chain_build_trace(self.seed, self.chain_length)
@@ -652,6 +686,10 @@ class RangeProofExample:
     def verify(self, proof):
         """src/range/mod.rs:103-110; raises VerifierError on rejection"""
         _air_verify_or_raise(self.backend, proof, Backend.AIR_RANGE, numbers=self.number)
+
+    def convert(self, proof, compact=True):
+        """as TransactionExample.convert"""
+        return _air_convert_or_raise(self.backend, proof, compact, Backend.AIR_RANGE, numbers=self.number)
 
     def validate(self, want_cycles=False, want_frame=False):
         """as TransactionExample.validate: the 64-row accumulator trace against the number"""

@@ -1,4 +1,5 @@
-"""Verification surfaces that need no GPU: the verdict names of include/cstark.h, VerifierError, and inspect_proof (the host parser).
+"""Verification surfaces that need no GPU: the verdict names of include/cstark.h, VerifierError, inspect_proof (the host parser) and
+convert_bound (the capacity of a proof in the other form).
 
 The verifier itself is Backend.tx_verify / TransactionExample.verify (cstark_tx_verify on the GPU)."""
 import ctypes as C
@@ -55,6 +56,21 @@ def proof_form(proof):
     if _lib.load().cstark_proof_form(buf, C.c_size_t(len(b)), C.byref(form)) != 0:
         raise ValueError("neither a plain nor a compact proof")
     return ("plain", "compact")[form.value]
+
+
+def convert_bound(proof, form):
+    """cstark_proof_convert_bound: a capacity that holds `proof` converted to `form` ("plain" or "compact"; 0 / 1 are accepted too)
+    whatever its positions -- to "plain" the exact plain length, to "compact" the plain length plus 4 bytes per tree.  Host only;
+    ValueError for another form or a proof whose layout does not parse."""
+    b = bytes(proof)
+    buf = (C.c_uint8 * max(1, len(b))).from_buffer_copy(b if b else b"\0")
+    form = {"plain": 0, "compact": 1}.get(form, form)
+    if form not in (0, 1):
+        raise ValueError("form is 'plain' or 'compact', not %r" % (form,))
+    bound = C.c_size_t(0)
+    if _lib.load().cstark_proof_convert_bound(buf, C.c_size_t(len(b)), C.c_uint32(form), C.byref(bound)) != 0:
+        raise ValueError("the proof's layout does not parse")
+    return int(bound.value)
 
 
 def inspect_proof(proof):

@@ -862,6 +862,36 @@ typedef struct cstark_schnorr_statement {
 } cstark_schnorr_statement;
 int cstark_schnorr_verify(cstark_ctx *ctx, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens,
                           const cstark_schnorr_statement *statements, const cstark_options *expected, int32_t *verdicts);
+/* ---- conversion between the proof forms: a proof of either form and its statement -> the same proof in the other form, byte for byte
+ * what the prover would have written (a proof written before the compact form existed, a sharded proof -- the sharded phases write the
+ * plain form only -- or a compact proof for a consumer that reads paths).
+ * cstark_proof_convert_bound (host only): a capacity that holds `proof` converted to `form` whatever its positions.  To
+ * CSTARK_FORM_PLAIN: the exact plain length (it follows from the header and each layer's stated n_positions).  To CSTARK_FORM_COMPACT:
+ * the plain length plus 4 bytes per tree (a multiproof never holds more nodes than the paths it is selected from; each tree gains a count
+ * word).  CSTARK_ERR_INVALID_ARG for a null pointer, another form, or a layout that does not parse (cstark_proof_inspect).
+ * The three convert calls ARE their verify calls: the same arguments, misuse rules, chunking and verdicts -- verdicts[i] is what the
+ * verify call returns for the same inputs, whatever the neighbours are and wherever the chunks divide -- and each also writes every proof
+ * whose verdict is CSTARK_PROOF_OK to out[i] in `form`, out_lens[i] its length.  Plain to compact: every path section becomes the
+ * canonical multiproof of its tree ("Proof layout"), selected on the device next to the replayed positions.  Compact to plain: one path
+ * per opened row in proof order, from the inner nodes the multiproof's fold computes on the device.  Everything outside the path sections
+ * is copied unchanged; a proof already in `form` is copied through unchanged.  A proof with any other verdict is not converted:
+ * out_lens[i] = 0 and out[i] is not written.  form must be CSTARK_FORM_PLAIN or CSTARK_FORM_COMPACT.  Null out, capacities or out_lens
+ * with count > 0 is CSTARK_ERR_INVALID_ARG.  Every capacities[i] is checked against cstark_proof_convert_bound before anything is
+ * launched, for every proof whose layout parses: a short one (or a null out[i]) is CSTARK_ERR_INVALID_ARG, cstark_last_error names the
+ * proof, and no output is written.  The verifier's buffers belong to the context; the prover's arena, the resident witness and the
+ * context's proof form setting are neither read nor changed.  cstark_verify_stage_ms and cstark_verify_h2d_bytes describe a convert call
+ * as they describe a verify call: the conversion's kernels count under the openings stage, its copy back under the last stage, the
+ * host's writing of the proofs under the first. */
+int cstark_proof_convert_bound(const uint8_t *proof, size_t len, uint32_t form, size_t *bound);
+int cstark_tx_convert(cstark_ctx *ctx, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens,
+                      const uint64_t *initial_roots, const uint64_t *final_roots, const cstark_options *expected,
+                      uint32_t form, uint8_t *const *out, const size_t *capacities, size_t *out_lens, int32_t *verdicts);
+int cstark_air_convert(cstark_ctx *ctx, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens, const int32_t *airs,
+                       const uint64_t *public_inputs, const cstark_options *expected,
+                       uint32_t form, uint8_t *const *out, const size_t *capacities, size_t *out_lens, int32_t *verdicts);
+int cstark_schnorr_convert(cstark_ctx *ctx, uint32_t count, const uint8_t *const *proofs, const size_t *proof_lens,
+                           const cstark_schnorr_statement *statements, const cstark_options *expected,
+                           uint32_t form, uint8_t *const *out, const size_t *capacities, size_t *out_lens, int32_t *verdicts);
 /* Stage entry point, like the other stages: the 19 public-input columns (12 public-key words, 7 hash-input words) and the 12
  * sequence-value polynomials (R.x at step 0, at step 511) of a statement at one point z of the degree-m extension, m in {1, 2, 3};
  * out [31][m], memory form, host memory.  CSTARK_ERR_INVALID_ARG if z^n = 1 (n = 512 n_sig) or n_sig is not a power of two (at most 4096). */

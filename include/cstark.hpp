@@ -555,6 +555,95 @@ inline std::vector<int32_t> verify_batch(Context &ctx, const std::vector<std::ve
     return verdicts;
 }
 
+// ---- conversion between the proof forms (cstark_*_convert: the verify call that also writes every accepted proof in `form`) ----
+// cstark_proof_convert_bound (host only): a capacity that holds `proof` in `form` whatever its positions; throws when it does not parse
+inline size_t convert_bound(const std::vector<uint8_t> &proof, uint32_t form) {
+    size_t bound = 0;
+    check(cstark_proof_convert_bound(proof.data(), proof.size(), form, &bound));
+    return bound;
+}
+// what a convert call returns: verdicts[i] as the verify call gives it, proofs[i] the proof in the target form (empty unless accepted)
+struct Converted {
+    std::vector<std::vector<uint8_t>> proofs;
+    std::vector<int32_t> verdicts;
+};
+namespace detail {
+// the output arguments of one convert call: a buffer per proof sized by its bound (a proof that does not parse is never converted)
+struct ConvertBuffers {
+    Converted result;
+    std::vector<uint8_t *> out;
+    std::vector<size_t> capacities, lens;
+    ConvertBuffers(const std::vector<const uint8_t *> &ptrs, const std::vector<size_t> &in_lens, uint32_t form)
+        : out(ptrs.size()), capacities(ptrs.size()), lens(ptrs.size(), 0) {
+        result.proofs.resize(ptrs.size());
+        result.verdicts.assign(ptrs.size(), -1);
+        for (size_t i = 0; i < ptrs.size(); i++) {
+            size_t bound = 1;
+            if (cstark_proof_convert_bound(ptrs[i], in_lens[i], form, &bound) != CSTARK_OK) bound = 1;
+            result.proofs[i].resize(bound);
+            out[i] = result.proofs[i].data();
+            capacities[i] = bound;
+        }
+    }
+    Converted finish() {
+        for (size_t i = 0; i < out.size(); i++) result.proofs[i].resize(result.verdicts[i] == CSTARK_PROOF_OK ? lens[i] : 0);
+        return std::move(result);
+    }
+};
+// one proof: its bytes in `form`, or VerifierError with the verdict
+inline std::vector<uint8_t> converted_or_throw(Converted c) {
+    if (c.verdicts.at(0) != CSTARK_PROOF_OK) throw VerifierError(c.verdicts[0]);
+    return std::move(c.proofs[0]);
+}
+} // namespace detail
+// cstark_tx_convert for many proofs in one call, as verify_batch
+inline Converted convert_batch(Context &ctx, const std::vector<std::vector<uint8_t>> &proofs, const std::vector<PublicInputs> &pub, uint32_t form,
+                               const ProofOptions *expected = nullptr) {
+    if (pub.size() != proofs.size()) throw Error(CSTARK_ERR_INVALID_ARG, "one PublicInputs per proof");
+    std::vector<const uint8_t *> ptrs(proofs.size());
+    std::vector<size_t> lens(proofs.size());
+    std::vector<uint64_t> r0(7 * proofs.size()), r1(7 * proofs.size());
+    for (size_t i = 0; i < proofs.size(); i++) {
+        ptrs[i] = proofs[i].data();
+        lens[i] = proofs[i].size();
+        for (int k = 0; k < 7; k++) { r0[7 * i + k] = pub[i].initial_root[k]; r1[7 * i + k] = pub[i].final_root[k]; }
+    }
+    detail::ConvertBuffers b(ptrs, lens, form);
+    cstark_options o{};
+    if (expected) o = expected->raw();
+    check(cstark_tx_convert(ctx.raw(), (uint32_t)proofs.size(), ptrs.data(), lens.data(), r0.data(), r1.data(), expected ? &o : nullptr, form,
+                            b.out.data(), b.capacities.data(), b.lens.data(), b.result.verdicts.data()));
+    return b.finish();
+}
+// cstark_air_convert: proofs[i] is stated to be of airs[i], with the 14 public words pub[i]
+inline Converted air_convert_batch(Context &ctx, const std::vector<std::vector<uint8_t>> &proofs, const std::vector<int32_t> &airs,
+                                   const std::vector<std::array<uint64_t, 14>> &pub, uint32_t form, const ProofOptions *expected = nullptr) {
+    if (pub.size() != proofs.size() || airs.size() != proofs.size()) throw Error(CSTARK_ERR_INVALID_ARG, "one AIR id and 14 public words per proof");
+    std::vector<const uint8_t *> ptrs(proofs.size());
+    std::vector<size_t> lens(proofs.size());
+    for (size_t i = 0; i < proofs.size(); i++) { ptrs[i] = proofs[i].data(); lens[i] = proofs[i].size(); }
+    detail::ConvertBuffers b(ptrs, lens, form);
+    cstark_options o{};
+    if (expected) o = expected->raw();
+    check(cstark_air_convert(ctx.raw(), (uint32_t)proofs.size(), ptrs.data(), lens.data(), airs.data(), pub.empty() ? nullptr : pub[0].data(),
+                             expected ? &o : nullptr, form, b.out.data(), b.capacities.data(), b.lens.data(), b.result.verdicts.data()));
+    return b.finish();
+}
+// cstark_schnorr_convert: proofs[i] against statements[i]
+inline Converted schnorr_convert_batch(Context &ctx, const std::vector<std::vector<uint8_t>> &proofs, const std::vector<cstark_schnorr_statement> &statements,
+                                       uint32_t form, const ProofOptions *expected = nullptr) {
+    if (statements.size() != proofs.size()) throw Error(CSTARK_ERR_INVALID_ARG, "one statement per proof");
+    std::vector<const uint8_t *> ptrs(proofs.size());
+    std::vector<size_t> lens(proofs.size());
+    for (size_t i = 0; i < proofs.size(); i++) { ptrs[i] = proofs[i].data(); lens[i] = proofs[i].size(); }
+    detail::ConvertBuffers b(ptrs, lens, form);
+    cstark_options o{};
+    if (expected) o = expected->raw();
+    check(cstark_schnorr_convert(ctx.raw(), (uint32_t)proofs.size(), ptrs.data(), lens.data(), statements.data(), expected ? &o : nullptr, form,
+                                 b.out.data(), b.capacities.data(), b.lens.data(), b.result.verdicts.data()));
+    return b.finish();
+}
+
 // ---- trace validation (cstark_air_validate_trace) ----
 // What the validation of a device trace found: step < 0 and boundary < 0 is a clean trace.  cycle = step / cycle length (one transfer,
 // signature or link; the whole trace for RangeProofAir), row_in_cycle = step % cycle length.
@@ -638,6 +727,10 @@ class TransactionExample {
         if (v != CSTARK_PROOF_OK) throw VerifierError(v);
     }
     // Trace::validate of the reference's debug builds, on the device: the trace of this witness against every transition constraint and
+    // the accepted proof in `form` (cstark_tx_convert): the bytes a prover set to that form writes; throws VerifierError as verify() does
+    std::vector<uint8_t> convert(const std::vector<uint8_t> &proof, uint32_t form = CSTARK_FORM_COMPACT) const {
+        return detail::converted_or_throw(convert_batch(ctx_, {proof}, {pub_inputs()}, form));
+    }
     // the statement verify() is given
     TraceReport validate(bool want_cycles = false, bool want_frame = false) const {
         uint64_t pub[14];
@@ -666,6 +759,12 @@ inline void air_verify(Context &ctx, int32_t air, const std::vector<uint8_t> &pr
     check(cstark_air_verify(ctx.raw(), 1, &ptr, &len, &air, pub, nullptr, &v));
     if (v != CSTARK_PROOF_OK) throw VerifierError(v);
 }
+// cstark_air_convert for one proof: its bytes in `form`; throws VerifierError on rejection
+inline std::vector<uint8_t> air_convert(Context &ctx, int32_t air, const std::vector<uint8_t> &proof, const uint64_t (&pub)[14], uint32_t form) {
+    std::array<uint64_t, 14> words;
+    for (int k = 0; k < 14; k++) words[k] = pub[k];
+    return converted_or_throw(air_convert_batch(ctx, {proof}, {air}, {words}, form));
+}
 inline std::vector<uint8_t> air_prove(Context &ctx, int air, const ProofOptions &options, uint64_t number, size_t rows) {
     const cstark_options o = options.raw();
     std::vector<uint8_t> proof(2 * cstark_tx_proof_size_bound((uint32_t)((rows + 1023) / 1024), &o));
@@ -693,6 +792,11 @@ class MerkleExample {
         for (int k = 0; k < 7; k++) { pub[k] = p.initial_root[k]; pub[7 + k] = p.final_root[k]; }
         detail::air_verify(ctx_, CSTARK_AIR_MERKLE_UPDATE, proof, pub);
     }
+    std::vector<uint8_t> convert(const std::vector<uint8_t> &proof, uint32_t form = CSTARK_FORM_COMPACT) const {
+        uint64_t pub[14];
+        detail::root_words(pub_inputs(), pub);
+        return detail::air_convert(ctx_, CSTARK_AIR_MERKLE_UPDATE, proof, pub, form);
+    }
     TraceReport validate(bool want_cycles = false, bool want_frame = false) const {
         uint64_t pub[14];
         detail::root_words(pub_inputs(), pub);
@@ -716,6 +820,10 @@ class RangeProofExample {
     void verify(const std::vector<uint8_t> &proof) const {
         const uint64_t pub[14] = {number_};
         detail::air_verify(ctx_, CSTARK_AIR_RANGE, proof, pub);
+    }
+    std::vector<uint8_t> convert(const std::vector<uint8_t> &proof, uint32_t form = CSTARK_FORM_COMPACT) const {
+        const uint64_t pub[14] = {number_};
+        return detail::air_convert(ctx_, CSTARK_AIR_RANGE, proof, pub, form);
     }
     TraceReport validate(bool want_cycles = false, bool want_frame = false) const {
         const uint64_t pub[14] = {number_};
@@ -779,6 +887,12 @@ class RescueExample {
         uint64_t pub[14];
         for (int k = 0; k < 7; k++) { pub[k] = seed[k]; pub[7 + k] = r[k]; }
         detail::air_verify(ctx_, CSTARK_AIR_RESCUE_CHAIN, proof, pub);
+    }
+    std::vector<uint8_t> convert(const std::vector<uint8_t> &proof, uint32_t form = CSTARK_FORM_COMPACT) const {
+        const std::array<BaseElement, 7> r = result();
+        uint64_t pub[14];
+        for (int k = 0; k < 7; k++) { pub[k] = seed[k]; pub[7 + k] = r[k]; }
+        return detail::air_convert(ctx_, CSTARK_AIR_RESCUE_CHAIN, proof, pub, form);
     }
     TraceReport validate(bool want_cycles = false, bool want_frame = false) const {
         const std::array<BaseElement, 7> r = result();
@@ -868,6 +982,10 @@ class SchnorrExample {
         int32_t v = -1;
         check(cstark_schnorr_verify(ctx_.raw(), 1, &ptr, &len, &st, nullptr, &v));
         if (v != CSTARK_PROOF_OK) throw VerifierError(v);
+    }
+    std::vector<uint8_t> convert(const std::vector<uint8_t> &proof, uint32_t form = CSTARK_FORM_COMPACT) const {
+        const cstark_schnorr_statement st{(uint32_t)(messages.size() / 28), messages.data(), sig_rx.data(), sig_s.data()};
+        return detail::converted_or_throw(schnorr_convert_batch(ctx_, {proof}, {st}, form));
     }
     // the trace of the signatures held here against the transitions and the 61 assertions: a forged signature is the failing boundary
     // entry at the last row of its block
