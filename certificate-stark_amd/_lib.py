@@ -53,6 +53,13 @@ class LedgerAuditReportStruct(C.Structure):
                 ("slots_free", C.c_uint64)]
 
 
+class WitnessReportStruct(C.Structure):
+    _fields_ = [("n_tx", C.c_uint32), ("merkle_depth", C.c_uint32), ("first_bad", C.c_int32), ("first_verdict", C.c_uint32),
+                ("n_bad", C.c_uint32), ("reserved", C.c_uint32), ("final_root", C.c_uint64 * 7)]
+
+
+WITNESS_CHECK_SIGNATURES = 1   # CSTARK_WITNESS_CHECK_SIGNATURES
+
 TRACE_CLEAN = 0xFFFFFFFF
 AIR_CYCLE_NAMES = ("transfer", "transfer", "signature", "trace", "link")   # per cstark_air_id: what one cycle of the trace is
 

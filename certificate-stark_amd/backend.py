@@ -153,9 +153,9 @@ class Backend:
         return C.cast(C.c_void_p(t.data_ptr()), typ)
 
     # ---- K1 ----
-    def upload_witness(self, w):
-        """w: any object with the TransactionMetadata arrays as numpy attributes (see prover.TransactionMetadata)."""
-        self.resident = None
+    @staticmethod
+    def _witness_struct(w):
+        """-> (TxWitnessStruct over w's arrays, the arrays it points into: keep them alive for the call)"""
         s = _lib.TxWitnessStruct()
         s.n_tx, s.merkle_depth = int(w.n_tx), int(w.depth)
         keep = []
@@ -165,6 +165,12 @@ class Backend:
             a = np.ascontiguousarray(getattr(w, f), dtype=np.uint8 if typ is u8p else np.uint64)
             keep.append(a)
             setattr(s, f, a.ctypes.data_as(typ))
+        return s, keep
+
+    def upload_witness(self, w):
+        """w: any object with the TransactionMetadata arrays as numpy attributes (see prover.TransactionMetadata)."""
+        self.resident = None
+        s, keep = self._witness_struct(w)
         check(self.lib.cstark_tx_witness_upload(self.ctx, C.byref(s)))
         self.n_tx, self.depth = int(w.n_tx), int(w.depth)
 
@@ -310,6 +316,38 @@ class Backend:
                                                   self._hptr(p), self._hptr(r), C.c_uint32(r.shape[0]), self._hptr(verdicts, u8p),
                                                   self._hptr(out) if want_roots else None))
         return (verdicts, out) if want_roots else verdicts
+
+    # cstark_witness_verdict
+    (WITNESS_VALID, WITNESS_INDEX_RANGE, WITNESS_SELF_TRANSFER, WITNESS_SENDER_LEAF, WITNESS_SENDER_PATH, WITNESS_BALANCE, WITNESS_MIDDLE_ROOT,
+     WITNESS_RECEIVER_LEAF, WITNESS_NEXT_ROOT, WITNESS_SIGNATURE) = range(10)
+
+    def tx_witness_check(self, metadata=None, final_root=None, check_signatures=False, want_folds=False):
+        """cstark_tx_witness_check: is a transaction witness consistent?  One launch, one workgroup per transfer -> (report, verdicts)
+        or, with want_folds, (report, verdicts, folds): report a _lib.WitnessReportStruct (n_tx, merkle_depth, first_bad (-1: none),
+        first_verdict, n_bad, final_root[7] = the root the batch leaves, computed whatever the verdicts), verdicts uint8 [n_tx]
+        (Backend.WITNESS_*, 0 = valid, the first test a transfer fails), folds uint64 [n_tx][4][7] (sender-old, sender-new,
+        receiver-old, receiver-new).  metadata: any object with the TransactionMetadata arrays; it is checked in device scratch of its
+        own and final_root must be None (the witness states its own).  metadata=None: the RESIDENT witness (upload_witness,
+        ledger_apply) is checked where it lies against final_root, or without the last transfer's NEXT_ROOT test when that is None.
+        check_signatures: every transfer's signature against the message its own row of the witness states.  Read-only: the resident
+        witness and every ledger are as before, a proof after a check is the proof without it."""
+        if metadata is None:
+            n, arg, keep = self.n_tx, None, None
+            root = None if final_root is None else _np_u64(final_root).reshape(7)
+        else:
+            if final_root is not None:
+                raise ValueError("final_root is for the resident witness; a metadata object states its own")
+            n, root = int(metadata.n_tx), None
+            s, keep = self._witness_struct(metadata)
+            arg = C.byref(s)
+        report = _lib.WitnessReportStruct()
+        verdicts = np.zeros(max(n, 1), np.uint8)
+        folds = np.zeros((max(n, 1), 4, 7), np.uint64) if want_folds else None
+        check(self.lib.cstark_tx_witness_check(self.ctx, arg, None if root is None else self._hptr(root),
+                                               C.c_uint32(_lib.WITNESS_CHECK_SIGNATURES if check_signatures else 0), C.byref(report),
+                                               self._hptr(verdicts, u8p), self._hptr(folds) if want_folds else None))
+        verdicts = verdicts[:report.n_tx]
+        return (report, verdicts, folds[:report.n_tx]) if want_folds else (report, verdicts)
 
     MULTI_VALID, MULTI_INDEX, MULTI_NODE_COUNT, MULTI_ROOT = 0, 1, 2, 3   # cstark_multi_verdict
 

@@ -595,6 +595,7 @@ void cstark_ctx_destroy(cstark_ctx *c) {
     proof_form_release(c);
     if (c->path_buf) (void)hipFree(c->path_buf);
     if (c->multi_buf) (void)hipFree(c->multi_buf);
+    witness_check_release(c);
     for (cs::RawPeriodic &t : c->raw_periodic) (void)hipFree(t.tab);
     if (c->val_buf) (void)hipFree(c->val_buf);
     if (c->arena) cs::prove_arena_free(c->arena);
@@ -1427,6 +1428,20 @@ int tx_shard_combine(cstark_ctx *c, const uint64_t *d_parts, uint64_t *d_out, ui
 static_assert(cs::SIG_VALID == CSTARK_SIG_VALID && cs::SIG_MISMATCH == CSTARK_SIG_MISMATCH && cs::SIG_KEY_NOT_ON_CURVE == CSTARK_SIG_KEY_NOT_ON_CURVE &&
                   cs::SIG_SCALAR_RANGE == CSTARK_SIG_SCALAR_RANGE,
               "k_sig_final writes the values of cstark_sig_verdict");
+// that block for `count` signatures, carved (also for cstark_tx_witness_check, whose messages and signatures are on the device already)
+int signature_block(cstark_ctx *c, uint32_t count, cstark_sig_block *b) {
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = count, bytes = n * (80 * 8 + 32 + 1);
+    if (c->sig_bytes < bytes) {
+        if (c->sig_buf) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->sig_buf)); c->sig_buf = nullptr; c->sig_bytes = 0; }
+        HIP_TRY(hipMalloc(&c->sig_buf, bytes));
+        c->sig_bytes = bytes;
+    }
+    b->messages = (uint64_t *)c->sig_buf; b->sig_rx = b->messages + 28 * n; b->h_limbs = b->sig_rx + 6 * n; b->points = b->h_limbs + 4 * n;
+    b->x = b->points + 36 * n;
+    b->sig_s = (uint8_t *)(b->x + 6 * n); b->verdicts = b->sig_s + 32 * n;
+    return CSTARK_OK;
+}
 int signature_check(cstark_ctx *c, const char *who, uint32_t count, const uint64_t *messages, const uint64_t *sig_rx, const uint8_t *sig_s,
                     uint8_t *verdicts, uint64_t *rx_out) {
     char where[96];
@@ -1440,15 +1455,11 @@ int signature_check(cstark_ctx *c, const char *who, uint32_t count, const uint64
             snprintf(where, sizeof where, "%s: sig_rx[%zu][%zu]", who, i / 6, i % 6);
             return fail(CSTARK_ERR_INVALID_ARG, "%s is not a reduced field element", where);
         }
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t n = count, bytes = n * (80 * 8 + 32 + 1);
-    if (c->sig_bytes < bytes) {
-        if (c->sig_buf) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->sig_buf)); c->sig_buf = nullptr; c->sig_bytes = 0; }
-        HIP_TRY(hipMalloc(&c->sig_buf, bytes));
-        c->sig_bytes = bytes;
-    }
-    uint64_t *d_msg = (uint64_t *)c->sig_buf, *d_rx = d_msg + 28 * n, *d_h = d_rx + 6 * n, *d_pts = d_h + 4 * n, *d_x = d_pts + 36 * n;
-    uint8_t *d_s = (uint8_t *)(d_x + 6 * n), *d_verdicts = d_s + 32 * n;
+    cstark_sig_block b;
+    RC_TRY(signature_block(c, count, &b));
+    const size_t n = count;
+    uint64_t *d_msg = b.messages, *d_rx = b.sig_rx, *d_h = b.h_limbs, *d_pts = b.points, *d_x = b.x;
+    uint8_t *d_s = b.sig_s, *d_verdicts = b.verdicts;
     HIP_TRY(hipMemcpyAsync(d_msg, messages, n * 28 * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_rx, sig_rx, n * 6 * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_s, sig_s, n * 32, hipMemcpyHostToDevice, c->stream));

@@ -229,6 +229,17 @@ struct cstark_ctx {
 // messages of ledger_plan.h).  `who` names the public call in the error text.
 int signature_check(cstark_ctx *c, const char *who, uint32_t count, const uint64_t *messages, const uint64_t *sig_rx, const uint8_t *sig_s,
                     uint8_t *verdicts, uint64_t *rx_out);
+// internal (capi.hip): the device block of the signature check for `count` signatures (c->sig_buf, grown when needed), for a caller whose
+// messages and signatures are on the device already (cstark_tx_witness_check): the caller writes messages, launches
+// cs::launch_signature_check on the context's stream with these pointers and its own d_sig_rx / d_sig_s, and reads verdicts.
+struct cstark_sig_block {
+    uint64_t *messages, *sig_rx, *h_limbs, *points, *x;
+    uint8_t *sig_s, *verdicts;
+};
+int signature_block(cstark_ctx *c, uint32_t count, cstark_sig_block *b);
+// internal (ledger.hip): frees the device block of cstark_tx_witness_check, which is kept by the context's address beside this struct
+// (cstark_ctx_destroy calls it)
+void witness_check_release(const cstark_ctx *c);
 // internal (capi.hip): cstark_schnorr_public_keys and cstark_schnorr_sign behind their argument checks (cstark_ledger_sign calls them with
 // the messages of ledger_plan.h).  sign_seeded leaves an exhausted signature's outputs zero and its status CSTARK_SIGN_EXHAUSTED.
 int sign_public_keys(cstark_ctx *c, uint32_t count, const uint64_t *secrets, uint64_t *keys_out);

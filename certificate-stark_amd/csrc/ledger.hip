@@ -27,9 +27,15 @@
 // the proof nodes into their final pool slots, k_ledger_merge hashes the leaves and folds the levels straight into the stored nodes, and
 // the root is compared on the host before the index is committed.  It knows the opened accounts only (Index::is_known): apply refuses
 // a transfer with an unknown account, the other calls refuse unknown indices (all_known), the audit skips the opaque proof nodes.
+// cstark_tx_witness_check, which needs no ledger, tests a whole transaction witness, the host's or the resident one, in one launch:
+//   k_witness_check     k_path_check's four chains given to ONE transfer: sender-old, sender-new, receiver-old, receiver-new, all leaves
+//                       hashed from values, the four folds met in wave ballots, one verdict byte per transfer
+//   k_witness_messages  the message every transfer signs, gathered from its witness row for the signature check (trace_gen.hip)
 #include <stdio.h>
 #include <string.h>
+#include <mutex>
 #include <new>
+#include <unordered_map>
 #include "../../include/cstark.h"
 #include "ctx.h"
 #include "ledger_plan.h"
@@ -296,6 +302,98 @@ __global__ __launch_bounds__(64) void k_path_check(const uint64_t *__restrict__ 
                       : (root_bad & mine) ? CSTARK_PATH_ROOT
                                           : CSTARK_PATH_VALID;
     }
+}
+
+// cstark_tx_witness_check: the body of k_path_check with its four chains given to ONE transfer.  One 64-lane workgroup per transfer;
+// lanes 0..55 = (chain s, state element e), lanes 56..63 only attend the barriers.  Chain 0 folds the sender's old leaf, 1 the sender's
+// new leaf, 2 the receiver's old leaf, 3 the receiver's new leaf; chains 0/1 read the siblings of s_paths and the bits of s_index,
+// chains 2/3 those of r_paths and r_index.  Every chain hashes its leaf from values: chain 1 forms balance - delta and nonce + 1,
+// chain 3 balance + delta in the lane that holds the word (field arithmetic, src/lib.rs:373-375).  The stated digests s_paths[t][0]
+// and r_paths[t][0] are no chain inputs: chain 0's leaf is compared with the first, chain 3's with the second, and both chains then go
+// on from the STATED digest, so that the path tests are tests of the paths as stated.  The four folds meet their counterparts in one
+// wave ballot: chain 0 initial_roots[t], chain 1 the fold of chain 2 (a cross-lane move that every lane executes), chain 3
+// initial_roots[t + 1] or, for the last transfer, final_root (null: that test does not run).  Lane e = 0 of chain 0 stores the verdict
+// byte; the lanes e < 7 of every chain store their fold.  Nothing else is written: no atomics, no flag, nothing waits for another
+// workgroup.  depth is uniform, so every lane reaches every barrier.  Every read is inside transfer t < n_tx of its segment.
+static_assert(CSTARK_WITNESS_VALID == 0 && CSTARK_WITNESS_INDEX_RANGE == 1 && CSTARK_WITNESS_SELF_TRANSFER == 2 && CSTARK_WITNESS_SENDER_LEAF == 3 &&
+                  CSTARK_WITNESS_SENDER_PATH == 4 && CSTARK_WITNESS_BALANCE == 5 && CSTARK_WITNESS_MIDDLE_ROOT == 6 && CSTARK_WITNESS_RECEIVER_LEAF == 7 &&
+                  CSTARK_WITNESS_NEXT_ROOT == 8 && CSTARK_WITNESS_SIGNATURE == 9,
+              "the order of cstark_witness_verdict is the order of the tests");
+__global__ __launch_bounds__(64) void k_witness_check(const fp *__restrict__ initial_roots, const fp *__restrict__ s_old, const fp *__restrict__ r_old,
+                                                      const uint64_t *__restrict__ s_idx, const uint64_t *__restrict__ r_idx,
+                                                      const fp *__restrict__ s_paths, const fp *__restrict__ r_paths, const fp *__restrict__ deltas,
+                                                      const fp *__restrict__ final_root, uint32_t n_tx, uint32_t depth, uint8_t *__restrict__ verdicts,
+                                                      fp *__restrict__ folds) {
+    __shared__ fp st[4][14];
+    const uint32_t t = blockIdx.x;
+    if (t >= n_tx) return; // the whole workgroup, ahead of its first barrier
+    const int lane = threadIdx.x;
+    const bool active = lane < 56;
+    const int s = active ? lane / 14 : 0, e = active ? lane % 14 : 0;
+    const bool low = e < 7;
+    const int w = low ? e : e - 7;
+    const int from = low ? lane : lane - 7;
+    const bool sender = s < 2;
+    fp mrow[14];
+#pragma unroll
+    for (int k = 0; k < 14; k++) mrow[k] = c_mds[e * 14 + k];
+    const uint64_t si = s_idx[t], ri = r_idx[t];
+    const uint32_t bits = (uint32_t)(sender ? si : ri); // the fold reads bits 0 .. depth - 1 <= 30 only
+    const fp *path = (sender ? s_paths : r_paths) + (size_t)7 * (depth + 1) * t + w; // this lane's word of entry 0
+    const fp delta = deltas[t];
+    fp v = (sender ? s_old : r_old)[(size_t)14 * t + e];
+    if (s == 1 && e == 12) v = fp_sub(v, delta);
+    if (s == 1 && e == 13) v = fp_add(v, FP_ONE);
+    if (s == 3 && e == 12) v = fp_add(v, delta); // may wrap past p: no verdict, as in the ledger
+    const fp stated_leaf = path[0];
+    fp sib = path[7]; // depth >= 1
+    for (int cyc = 0; cyc < 7; cyc++) v = rescue_round_lane(v, st[s], mrow, e, cyc, active);
+    const unsigned long long leaf_bad = __ballot(active && low && v != stated_leaf); // read for chains 0 and 3 only
+    fp cur = (s == 0 || s == 3) ? stated_leaf : v;
+    for (uint32_t k = 0; k < depth; k++) {
+        const bool right = (bits >> k) & 1; // this node is the right child: the sibling is the left half
+        const fp moved = __shfl(cur, from, 64);
+        v = low == right ? sib : moved;
+        if (k + 1 < depth) sib = path[7 * (k + 2)];
+        for (int cyc = 0; cyc < 7; cyc++) v = rescue_round_lane(v, st[s], mrow, e, cyc, active);
+        cur = v;
+    }
+    const fp above = __shfl(cur, (lane + 14) & 63, 64); // chain s + 1's fold: chain 1 meets chain 2
+    const bool last = t + 1 == n_tx;
+    fp want = cur; // chain 2, and chain 3 of the last transfer without a stated root: no test
+    if (active && low) {
+        if (s == 0) want = initial_roots[(size_t)7 * t + e];
+        else if (s == 1) want = above;
+        else if (s == 3 && !last) want = initial_roots[(size_t)7 * (t + 1) + e];
+        else if (s == 3 && final_root) want = final_root[e];
+        folds[(size_t)7 * (4 * t + s) + e] = cur;
+    }
+    const unsigned long long fold_bad = __ballot(active && low && cur != want);
+    if (lane == 0) {
+        const unsigned long long chain = 0x7Full;
+        const bool range = (si >> depth) || (ri >> depth);
+        const bool balance = fp_to_u64(delta) > fp_to_u64(s_old[(size_t)14 * t + 12]);
+        verdicts[t] = range ? CSTARK_WITNESS_INDEX_RANGE
+                      : si == ri ? CSTARK_WITNESS_SELF_TRANSFER
+                      : (leaf_bad & chain) ? CSTARK_WITNESS_SENDER_LEAF
+                      : (fold_bad & chain) ? CSTARK_WITNESS_SENDER_PATH
+                      : balance ? CSTARK_WITNESS_BALANCE
+                      : (fold_bad & (chain << 14)) ? CSTARK_WITNESS_MIDDLE_ROOT
+                      : (leaf_bad & (chain << 42)) ? CSTARK_WITNESS_RECEIVER_LEAF
+                      : (fold_bad & (chain << 42)) ? CSTARK_WITNESS_NEXT_ROOT
+                                                   : CSTARK_WITNESS_VALID;
+    }
+}
+
+// The messages of cstark_tx_witness_check's signature test, one lane per word: transfer t signs build_tx_message (src/lib.rs:467-481)
+// of its own witness row -- the sender's key, the receiver's key, delta, the sender's old nonce, two zeros -- into messages [n_tx][28].
+__global__ __launch_bounds__(256) void k_witness_messages(const fp *__restrict__ s_old, const fp *__restrict__ r_old, const fp *__restrict__ deltas,
+                                                          uint32_t n_tx, fp *__restrict__ messages) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t t = i / 28;
+    const uint32_t k = (uint32_t)(i % 28);
+    if (t >= n_tx) return;
+    messages[i] = k < 12 ? s_old[14 * t + k] : k < 24 ? r_old[14 * t + k - 12] : k == 24 ? deltas[t] : k == 25 ? s_old[14 * t + 13] : (fp)0;
 }
 
 } // namespace
@@ -769,6 +867,92 @@ int unsorted(const char *who, uint32_t i) {
     return fail(CSTARK_ERR_INVALID_ARG, "%s is out of range or not above its predecessor (indices are strictly ascending)", where);
 }
 
+// The device block of cstark_tx_witness_check, one per context that made such a call: grown when a larger request comes, otherwise reused
+// as it is, freed by cstark_ctx_destroy (witness_check_release).  It is kept by the context's address beside struct cstark_ctx, like the
+// signing table and the proof form of capi.hip: every call uploads or computes all it reads there, so nothing in it outlives a call.
+struct WitnessCheckBlock {
+    void *buf;
+    size_t bytes;
+};
+std::mutex &g_wcheck_lock = *new std::mutex; // never destroyed: a context may be destroyed while the process exits
+std::unordered_map<const cstark_ctx *, WitnessCheckBlock> &g_wcheck_blocks = *new std::unordered_map<const cstark_ctx *, WitnessCheckBlock>;
+int witness_check_block(cstark_ctx *c, size_t bytes, void **out) {
+    std::lock_guard<std::mutex> hold(g_wcheck_lock);
+    WitnessCheckBlock &b = g_wcheck_blocks[c]; // a new entry is {nullptr, 0}
+    if (b.bytes < bytes) {
+        if (b.buf) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(b.buf)); b.buf = nullptr; b.bytes = 0; }
+        HIP_TRY(hipMalloc(&b.buf, bytes));
+        b.bytes = bytes;
+    }
+    *out = b.buf;
+    return CSTARK_OK;
+}
+
+// cstark_tx_witness_check behind its argument checks.  One device block of the context, grown when needed:
+//   stated final root [7] | folds [n][4][7] | verdicts [n] (padded to 256 bytes) | host form only: the witness, as witness_layout.h lays it out
+// host != null: its arrays go up into the block's own witness; otherwise `dev` is the resident witness, read where it lies.  The
+// signature test runs in the signature check's block (signature_block, capi.hip) on messages gathered there, with sig_rx and sig_s
+// read from the witness that is being checked.  Nothing of the resident witness, tail_buf or the statement caches is written.
+int witness_check_impl(cstark_ctx *c, const cstark_tx_witness *host, cs::TxWitnessDev dev, const uint64_t *final_root, bool signatures,
+                       cstark_witness_report *report, uint8_t *verdicts_out, uint64_t *folds_out) {
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = dev.n_tx, d = dev.depth;
+    const size_t out_bytes = (56 + n * 224 + n + 255) & ~(size_t)255;
+    size_t sz[cs::WIT_NUM_SEGMENTS], off[cs::WIT_NUM_SEGMENTS + 1];
+    cs::witness_segments(n, d, sz, off);
+    const size_t bytes = out_bytes + (host ? off[cs::WIT_NUM_SEGMENTS] : 0);
+    void *block = nullptr;
+    RC_TRY(witness_check_block(c, bytes, &block));
+    uint64_t *d_root = (uint64_t *)block, *d_folds = d_root + 7;
+    uint8_t *d_verdicts = (uint8_t *)(d_folds + 28 * n);
+    if (host) {
+        char *base = (char *)block + out_bytes;
+        const void *src[cs::WIT_NUM_SEGMENTS] = {host->initial_roots, host->s_old_values, host->r_old_values, host->s_indices, host->r_indices, host->s_paths,
+                                                 host->r_paths, host->deltas, host->sig_rx, nullptr, host->sig_s};
+        for (int i = 0; i < cs::WIT_NUM_SEGMENTS; i++)
+            if (src[i]) HIP_TRY(hipMemcpyAsync(base + off[i], src[i], sz[i], hipMemcpyHostToDevice, c->stream));
+        dev.initial_roots = (const uint64_t *)(base + off[cs::WIT_INITIAL_ROOTS]);
+        dev.s_old = (const uint64_t *)(base + off[cs::WIT_S_OLD]);
+        dev.r_old = (const uint64_t *)(base + off[cs::WIT_R_OLD]);
+        dev.s_idx = (const uint64_t *)(base + off[cs::WIT_S_IDX]);
+        dev.r_idx = (const uint64_t *)(base + off[cs::WIT_R_IDX]);
+        dev.s_paths = (const uint64_t *)(base + off[cs::WIT_S_PATHS]);
+        dev.r_paths = (const uint64_t *)(base + off[cs::WIT_R_PATHS]);
+        dev.deltas = (const uint64_t *)(base + off[cs::WIT_DELTAS]);
+        dev.sig_rx = (const uint64_t *)(base + off[cs::WIT_SIG_RX]);
+        dev.sig_s = (const uint8_t *)(base + off[cs::WIT_SIG_S]);
+    }
+    if (final_root) HIP_TRY(hipMemcpyAsync(d_root, final_root, 56, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(cs::k_witness_check, dim3((uint32_t)n), dim3(64), 0, c->stream, dev.initial_roots, dev.s_old, dev.r_old, dev.s_idx, dev.r_idx, dev.s_paths,
+                       dev.r_paths, dev.deltas, final_root ? d_root : nullptr, (uint32_t)n, (uint32_t)d, d_verdicts, d_folds);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint8_t> verdicts(n), sig(signatures ? n : 0);
+    cstark_witness_report r = {};
+    if (signatures) {
+        cstark_sig_block b;
+        RC_TRY(signature_block(c, (uint32_t)n, &b));
+        hipLaunchKernelGGL(cs::k_witness_messages, dim3((uint32_t)((28 * n + 255) / 256)), dim3(256), 0, c->stream, dev.s_old, dev.r_old, dev.deltas, (uint32_t)n,
+                           b.messages);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(cs::launch_signature_check(b.messages, dev.sig_rx, dev.sig_s, b.h_limbs, b.points, b.verdicts, b.x, (uint32_t)n, c->stream));
+        HIP_TRY(hipMemcpyAsync(sig.data(), b.verdicts, n, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(verdicts.data(), d_verdicts, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(r.final_root, d_folds + 28 * (n - 1) + 21, 56, hipMemcpyDeviceToHost, c->stream));
+    if (folds_out) HIP_TRY(hipMemcpyAsync(folds_out, d_folds, n * 224, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream)); // synchronous: the verdicts are on the host, the caller's arrays are free again
+    r.n_tx = (uint32_t)n; r.merkle_depth = (uint32_t)d; r.first_bad = -1;
+    for (size_t t = 0; t < n; t++) {
+        if (signatures && verdicts[t] == CSTARK_WITNESS_VALID && sig[t] != CSTARK_SIG_VALID) verdicts[t] = CSTARK_WITNESS_SIGNATURE;
+        if (verdicts[t] == CSTARK_WITNESS_VALID) continue;
+        if (r.first_bad < 0) { r.first_bad = (int32_t)t; r.first_verdict = verdicts[t]; }
+        r.n_bad++;
+    }
+    if (verdicts_out) memcpy(verdicts_out, verdicts.data(), n);
+    *report = r;
+    return CSTARK_OK;
+}
+
 // a HIP failure inside a ledger call leaves the pool in an unknown state: every later call fails
 int guard(cstark_ledger *L, int rc) {
     if (rc == CSTARK_ERR_HIP || rc == CSTARK_ERR_OOM) L->broken = true;
@@ -802,6 +986,14 @@ ptrdiff_t checkpoint_position(cstark_ledger *L, uint64_t id, const char *who) {
 }
 
 } // namespace
+
+void witness_check_release(const cstark_ctx *c) {
+    std::lock_guard<std::mutex> hold(g_wcheck_lock);
+    const auto it = g_wcheck_blocks.find(c);
+    if (it == g_wcheck_blocks.end()) return;
+    (void)hipFree(it->second.buf);
+    g_wcheck_blocks.erase(it);
+}
 
 // internal, for the test-only library (include/cstark_debug_ledger.h): XORs `mask` into word `word` of the digest that the lookup at
 // checkpoint `id` finds for node (level, index), or, with level == 0xFFFFFFFF, of empty-subtree slot `index`.  One word down, one word
@@ -1013,6 +1205,35 @@ int cstark_account_check_paths(cstark_ctx *c, uint32_t count, uint32_t depth, co
     if (!reduced_words(who, "paths", paths, count, (size_t)7 * (depth + 1), true)) return CSTARK_ERR_INVALID_ARG;
     if (!reduced_words(who, "roots", roots, n_roots, 7, false)) return CSTARK_ERR_INVALID_ARG;
     return check_paths_impl(c, count, depth, indices, values, present, paths, roots, n_roots, verdicts, roots_out);
+}
+
+int cstark_tx_witness_check(cstark_ctx *c, const cstark_tx_witness *w, const uint64_t *final_root, uint32_t flags, cstark_witness_report *report,
+                            uint8_t *verdicts_out, uint64_t *folds_out) {
+    const char *who = "cstark_tx_witness_check";
+    if (!c || !report) return fail(CSTARK_ERR_INVALID_ARG, "%s: null argument", who);
+    if (flags & ~CSTARK_WITNESS_CHECK_SIGNATURES) return fail(CSTARK_ERR_INVALID_ARG, "%s: unknown flag", who);
+    const bool signatures = flags & CSTARK_WITNESS_CHECK_SIGNATURES;
+    if (!w) {
+        if (!c->wit_buf || c->wit.n_tx == 0 || c->wit.msg_tail) return fail(CSTARK_ERR_INVALID_ARG, "%s: no transaction witness uploaded", who);
+        if (c->wit.n_tx > MAX_TRANSFERS) return fail(CSTARK_ERR_INVALID_ARG, "%s: the resident witness has more than 2^20 transfers", who);
+        if (final_root && !reduced_words(who, "final_root", final_root, 1, 7, false)) return CSTARK_ERR_INVALID_ARG;
+        return witness_check_impl(c, nullptr, c->wit, final_root, signatures, report, verdicts_out, folds_out);
+    }
+    if (final_root) return fail(CSTARK_ERR_INVALID_ARG, "%s: final_root is for the resident form; a host witness states its own", who);
+    const size_t n = w->n_tx, d = w->merkle_depth;
+    if (n == 0 || n > MAX_TRANSFERS) return fail(CSTARK_ERR_INVALID_ARG, "%s: n_tx must be 1 .. 2^20", who);
+    if (d == 0 || ((d + 1) & d) != 0 || d > MAX_DEPTH) return fail(CSTARK_ERR_INVALID_ARG, "%s: tree depth must be one less than a power of 2 and at most 31", who);
+    if (!w->initial_roots || !w->final_root || !w->s_old_values || !w->r_old_values || !w->s_indices || !w->r_indices || !w->s_paths || !w->r_paths ||
+        !w->deltas || !w->sig_rx || !w->sig_s)
+        return fail(CSTARK_ERR_INVALID_ARG, "%s: witness array pointer is null", who);
+    if (!reduced_words(who, "initial_roots", w->initial_roots, n, 7, false) || !reduced_words(who, "final_root", w->final_root, 1, 7, false) ||
+        !reduced_words(who, "s_old_values", w->s_old_values, n, 14, false) || !reduced_words(who, "r_old_values", w->r_old_values, n, 14, false) ||
+        !reduced_words(who, "s_paths", w->s_paths, n, 7 * (d + 1), true) || !reduced_words(who, "r_paths", w->r_paths, n, 7 * (d + 1), true) ||
+        !reduced_words(who, "deltas", w->deltas, n, 1, false) || !reduced_words(who, "sig_rx", w->sig_rx, n, 6, false))
+        return CSTARK_ERR_INVALID_ARG;
+    cs::TxWitnessDev view{};
+    view.n_tx = (uint32_t)n; view.depth = (uint32_t)d;
+    return witness_check_impl(c, w, view, w->final_root, signatures, report, verdicts_out, folds_out);
 }
 
 int cstark_account_multiproof_shape(uint32_t depth, uint32_t count, const uint64_t *indices, uint32_t *n_nodes, uint32_t *n_merges) {

@@ -44,6 +44,34 @@ class ProofOptions:
         return self.blowup_factor.bit_length() - 1
 
 
+# cstark_witness_verdict by value: what Backend.tx_witness_check's verdict bytes mean
+WITNESS_VERDICTS = ("VALID", "INDEX_RANGE", "SELF_TRANSFER", "SENDER_LEAF", "SENDER_PATH", "BALANCE", "MIDDLE_ROOT", "RECEIVER_LEAF", "NEXT_ROOT",
+                    "SIGNATURE")
+
+
+class WitnessCheck:
+    """What a witness check found: ok; first_bad (the first transfer whose verdict is not VALID, None when ok) and verdict, the name of
+    its verdict (WITNESS_VERDICTS; "VALID" when ok); n_bad; verdicts uint8 [n_tx]; final_root [7], the root the batch leaves as the
+    device folded it, whatever the verdicts; folds [n_tx][4][7] when they were asked for."""
+
+    def __init__(self, report, verdicts, folds=None):
+        self.n_tx, self.depth, self.n_bad = int(report.n_tx), int(report.merkle_depth), int(report.n_bad)
+        self.first_bad = None if report.first_bad < 0 else int(report.first_bad)
+        self.verdict = WITNESS_VERDICTS[int(report.first_verdict)]
+        self.verdicts, self.folds = verdicts, folds
+        self.final_root = np.array(list(report.final_root), np.uint64)
+
+    @property
+    def ok(self):
+        return self.first_bad is None
+
+    def __str__(self):
+        return "consistent" if self.ok else "transfer %d: %s (%d of %d transfers bad)" % (self.first_bad, self.verdict, self.n_bad, self.n_tx)
+
+    def __repr__(self):
+        return "WitnessCheck(%s)" % self
+
+
 class TransactionMetadata:
     """Series of transfers in the account tree (src/lib.rs:183-194); arrays are uint64 in BaseElement memory form."""
     FIELDS = ("initial_roots", "final_root", "s_old_values", "r_old_values", "s_indices", "r_indices",
@@ -101,6 +129,13 @@ class TransactionMetadata:
 
     def save(self, path):
         np.savez_compressed(path, **{f: getattr(self, f) for f in self.FIELDS})
+
+    def check(self, backend=None, check_signatures=False, want_folds=False):
+        """Is this witness consistent?  Every transfer's indices, leaves, paths, balance and roots (and, with check_signatures, its
+        signature) tested on the GPU in one launch, before any trace is built -> WitnessCheck: .ok, .first_bad, .verdict
+        ("SENDER_PATH", ...), .verdicts, .final_root.  n_tx need not be a power of two.  A witness resident in the backend is left
+        alone (cstark_tx_witness_check)."""
+        return WitnessCheck(*(backend or Backend()).tx_witness_check(self, check_signatures=check_signatures, want_folds=want_folds))
 
 
 class TransferRefused(Exception):
@@ -467,6 +502,12 @@ class TransactionExample:
 
     def pub_inputs(self):
         return self.tx_metadata.initial_roots[0], self.tx_metadata.final_root
+
+    def check_witness(self, check_signatures=False, want_folds=False):
+        """TransactionMetadata.check of this example's witness on its own backend -> WitnessCheck; str() of it names the first
+        inconsistent transfer and what is wrong with it, e.g. "transfer 3: SENDER_PATH (1 of 8 transfers bad)".  Unlike validate() it
+        builds no trace and, with check_signatures, it catches a forged signature, which still proves and verifies."""
+        return self.tx_metadata.check(self.prover.backend, check_signatures=check_signatures, want_folds=want_folds)
 
     def validate(self, want_cycles=False, want_frame=False):
         """Trace::validate of the reference's debug builds, on the device: builds the trace of this example's witness and checks every

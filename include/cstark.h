@@ -631,6 +631,61 @@ int cstark_ledger_sign(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t n_tx, co
                        const uint64_t *deltas, const uint64_t *secrets, uint64_t seed, uint32_t max_attempts, uint64_t *sig_rx_out,
                        uint8_t *sig_s_out, uint32_t *attempts_out, int32_t *refused_at, int32_t *reason);
 
+/* ---- witness check: is a cstark_tx_witness consistent?  Needs no ledger ---------------------------------------------------------------
+ * What cstark_tx_prove starts from, tested transfer by transfer before a trace is built: the indices, the sender's leaf and path under
+ * initial_roots[t], the balance, the root between the two updates, the receiver's leaf and path under the next root and, when asked for,
+ * the signature.  With s_new = (pk, balance - delta, nonce + 1) of s_old_values[t] and r_new = (pk, balance + delta, nonce) of
+ * r_old_values[t] (field arithmetic, src/lib.rs:373-375, as cstark_ledger_apply), leaf(v) = merge(v[0..7], v[7..14]) and fold the one
+ * cstark_account_check_paths states, "s siblings" = s_paths[t][1..], "r siblings" = r_paths[t][1..].  A transfer's verdict is the FIRST
+ * that applies in the order of the values; every test of every transfer runs whatever the others give, so one bad transfer does not hide
+ * the next.  A receiver balance that wraps past p is no verdict: cstark_ledger_apply does not refuse it either. */
+typedef enum cstark_witness_verdict {
+    CSTARK_WITNESS_VALID = 0,
+    CSTARK_WITNESS_INDEX_RANGE = 1,   /* s_index or r_index >= 2^merkle_depth */
+    CSTARK_WITNESS_SELF_TRANSFER = 2, /* s_index == r_index */
+    CSTARK_WITNESS_SENDER_LEAF = 3,   /* s_paths[t][0] != leaf(s_old) */
+    CSTARK_WITNESS_SENDER_PATH = 4,   /* fold(s_paths[t][0], s siblings, s_index) != initial_roots[t] */
+    CSTARK_WITNESS_BALANCE = 5,       /* delta > sender balance, both as canonical integers (the ledger's rule) */
+    CSTARK_WITNESS_MIDDLE_ROOT = 6,   /* fold(leaf(s_new), s siblings, s_index) != fold(leaf(r_old), r siblings, r_index) */
+    CSTARK_WITNESS_RECEIVER_LEAF = 7, /* r_paths[t][0] != leaf(r_new) */
+    CSTARK_WITNESS_NEXT_ROOT = 8,     /* fold(r_paths[t][0], r siblings, r_index) != initial_roots[t + 1], or the final root for the last transfer */
+    CSTARK_WITNESS_SIGNATURE = 9      /* only with CSTARK_WITNESS_CHECK_SIGNATURES: verdict other than CSTARK_SIG_VALID */
+} cstark_witness_verdict;
+#define CSTARK_WITNESS_CHECK_SIGNATURES 1u
+typedef struct cstark_witness_report {
+    uint32_t n_tx, merkle_depth; /* of the witness that was checked */
+    int32_t first_bad;           /* the first transfer whose verdict is not VALID; -1: none */
+    uint32_t first_verdict;      /* its cstark_witness_verdict (VALID when first_bad == -1) */
+    uint32_t n_bad;              /* transfers whose verdict is not VALID */
+    uint32_t reserved;           /* 0 */
+    uint64_t final_root[7];      /* the receiver-new fold of the last transfer, whatever the verdicts: the root the batch leaves */
+} cstark_witness_report;
+/* Checks a witness on the device in one launch, one workgroup per transfer.  Two forms:
+ *  - w != NULL, the host form: w's arrays are host memory, n_tx 1 .. 2^20 and need not be a power of two, merkle_depth one that
+ *    cstark_tx_witness_upload accepts; w->final_root is the stated final root and the final_root argument must be NULL.  A null field, or
+ *    a word >= p in any field of field elements (in the order of the struct's fields; sig_rx included, whatever the flags), is
+ *    CSTARK_ERR_INVALID_ARG before anything is launched and with the outputs untouched; cstark_last_error names the first such word.
+ *    The witness goes into a device block of its own, which the context keeps and frees: the RESIDENT witness is not replaced.
+ *  - w == NULL, the resident form: the witness that cstark_tx_witness_upload or cstark_ledger_apply left in the context is checked as it
+ *    lies; nothing is uploaded but final_root ([7], reduced words), which is optional: without it the last transfer's NEXT_ROOT test does
+ *    not run.  No resident transaction witness, or one of more than 2^20 transfers, is CSTARK_ERR_INVALID_ARG.  The resident words are
+ *    not tested against p (cstark_tx_witness_upload does not test them either): a transfer with such a word gets the verdict its
+ *    arithmetic happens to give, every read stays inside the witness, and a sig_rx word >= p can equal no x coordinate, so that
+ *    transfer's signature verdict is CSTARK_WITNESS_SIGNATURE.
+ * flags: 0 or CSTARK_WITNESS_CHECK_SIGNATURES.  With it the message of transfer t -- build_tx_message of s_old_values[t],
+ * r_old_values[t], deltas[t] and the sender's old nonce, what cstark_ledger_apply_checked signs against -- is gathered on the device
+ * and the device run of cstark_schnorr_check_signatures follows, in that call's scratch; a transfer whose verdict is VALID so far and
+ * whose signature verdict is anything but CSTARK_SIG_VALID becomes CSTARK_WITNESS_SIGNATURE.
+ * report (required) is described above; verdicts_out (optional) [n_tx]: one cstark_witness_verdict each; folds_out (optional)
+ * [n_tx][4][7]: the four folds of every transfer, sender-old, sender-new, receiver-old, receiver-new, whatever the verdicts (the first
+ * and last from the stated leaf digests).  An inconsistency is a finding, not a failure: the status is CSTARK_OK.  Synchronous and
+ * read-only: the resident witness, the statement caches and every ledger are neither written nor moved, so a proof after a check is
+ * the proof without it. */
+int cstark_tx_witness_check(cstark_ctx *ctx, const cstark_tx_witness *w /* NULL: the RESIDENT witness */,
+                            const uint64_t *final_root /* [7]; resident form only, may be NULL */, uint32_t flags,
+                            cstark_witness_report *report, uint8_t *verdicts_out /* [n_tx] or NULL */,
+                            uint64_t *folds_out /* [n_tx][4][7] or NULL: sender-old, sender-new, receiver-old, receiver-new */);
+
 /* ---- ledger checkpoints: take a batch back, open accounts under a past root, audit the resident tree -----------------------------
  * A checkpoint names the ledger's state at the moment it is taken.  Old states are kept by not overwriting them: while a checkpoint is
  * live, the first change of a tree node since the newest checkpoint goes to a fresh slot of the device pool and the old slot stays as it

@@ -145,6 +145,40 @@ struct TransactionMetadata {
     }
 };
 
+// What check_witness found: the report of cstark_tx_witness_check (first_bad -1: consistent; final_root: the root the batch leaves,
+// folded on the device whatever the verdicts), one cstark_witness_verdict per transfer, and the four folds of every transfer
+// ([n_tx][4][7] words: sender-old, sender-new, receiver-old, receiver-new) when they were asked for
+struct WitnessCheck {
+    cstark_witness_report report{};
+    std::vector<uint8_t> verdicts;
+    std::vector<BaseElement> folds;
+    bool ok() const { return report.first_bad < 0; }
+};
+// cstark_tx_witness_check of a host witness: every transfer's indices, leaves, paths, balance and roots (with check_signatures its
+// signature too) tested on the device in one launch, before any trace is built.  The number of transfers need not be a power of two.
+// The witness resident in the context is neither replaced nor touched.
+inline WitnessCheck check_witness(Context &ctx, const TransactionMetadata &m, bool check_signatures = false, bool want_folds = false) {
+    m.validate();
+    WitnessCheck out;
+    out.verdicts.resize(m.len());
+    if (want_folds) out.folds.resize(m.len() * 28);
+    const cstark_tx_witness w = m.view();
+    check(cstark_tx_witness_check(ctx.raw(), &w, nullptr, check_signatures ? CSTARK_WITNESS_CHECK_SIGNATURES : 0u, &out.report, out.verdicts.data(),
+                                  want_folds ? out.folds.data() : nullptr));
+    return out;
+}
+// ... and of the witness RESIDENT in the context (TransactionProver::load, Ledger::apply), checked where it lies: n_tx its number of
+// transfers; final_root (optional) the root it must lead to -- without it the last transfer's NEXT_ROOT test does not run and
+// report.final_root is where that root is read
+inline WitnessCheck check_resident_witness(Context &ctx, size_t n_tx, const Hash *final_root = nullptr, bool check_signatures = false, bool want_folds = false) {
+    WitnessCheck out;
+    out.verdicts.resize(n_tx);
+    if (want_folds) out.folds.resize(n_tx * 28);
+    check(cstark_tx_witness_check(ctx.raw(), nullptr, final_root ? final_root->data() : nullptr, check_signatures ? CSTARK_WITNESS_CHECK_SIGNATURES : 0u,
+                                  &out.report, out.verdicts.data(), want_folds ? out.folds.data() : nullptr));
+    return out;
+}
+
 // src/prover.rs:20-134.  The trace lives in device memory (the reference's TraceTable is a host object); prove() is the
 // whole of Prover::prove including trace generation.
 class TransactionProver {
