@@ -53,6 +53,11 @@ class LedgerAuditReportStruct(C.Structure):
                 ("slots_free", C.c_uint64)]
 
 
+class LedgerSelectionStruct(C.Structure):
+    _fields_ = [("n_candidates", C.c_uint32), ("n_selected", C.c_uint32), ("n_sig_checked", C.c_uint32), ("n_chunks", C.c_uint32),
+                ("counts", C.c_uint32 * 10), ("root_after", C.c_uint64 * 7)]
+
+
 class WitnessReportStruct(C.Structure):
     _fields_ = [("n_tx", C.c_uint32), ("merkle_depth", C.c_uint32), ("first_bad", C.c_int32), ("first_verdict", C.c_uint32),
                 ("n_bad", C.c_uint32), ("reserved", C.c_uint32), ("final_root", C.c_uint64 * 7)]

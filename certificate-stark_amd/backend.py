@@ -478,6 +478,50 @@ class Backend:
         self.n_tx, self.depth = n, depth
         return -1, 0, arrays
 
+    SELECT_CHECK_SIGNATURES, SELECT_POW2, SELECT_APPLY = 1, 2, 4   # CSTARK_SELECT_*
+
+    def ledger_select(self, led, depth, s_indices, r_indices, deltas, sig_rx, sig_s, want, flags=0, chunk=0, want_messages=False, want_witness=True):
+        """cstark_ledger_select: -> (status uint8 [n], selected uint32 [n_selected], messages [n][28] or None, report, arrays): the status
+        of every candidate of the pool (cstark_ledger_reason, 8 = HELD, 9 = NOT_REACHED), the selected candidate numbers, and with
+        SELECT_APPLY the witness of the applied selection (the dict of its eleven fields, None without want_witness or with nothing
+        selected), which is then resident in this backend.  sig_rx / sig_s may be None without SELECT_CHECK_SIGNATURES and SELECT_APPLY."""
+        s, r, dl = _np_u64(s_indices).reshape(-1), _np_u64(r_indices).reshape(-1), _np_u64(deltas).reshape(-1)
+        n = s.size
+        rx = None if sig_rx is None else _np_u64(sig_rx).reshape(-1, 6)
+        ss = None if sig_s is None else np.ascontiguousarray(sig_s, np.uint8).reshape(-1, 32)
+        if not (r.size == dl.size == n) or (rx is not None and rx.shape[0] != n) or (ss is not None and ss.shape[0] != n):
+            raise ValueError("the candidate arrays state different numbers of candidates")
+        cap = max(1, min(int(want), n))
+        status, selected = np.zeros(n, np.uint8), np.zeros(cap, np.uint32)
+        messages = np.zeros((n, 28), np.uint64) if want_messages else None
+        arrays, out = None, None
+        if (flags & self.SELECT_APPLY) and want_witness:
+            arrays = dict(initial_roots=np.zeros((cap, 7), np.uint64), final_root=np.zeros(7, np.uint64),
+                          s_old_values=np.zeros((cap, 14), np.uint64), r_old_values=np.zeros((cap, 14), np.uint64),
+                          s_indices=np.zeros(cap, np.uint64), r_indices=np.zeros(cap, np.uint64),
+                          s_paths=np.zeros((cap, depth + 1, 7), np.uint64), r_paths=np.zeros((cap, depth + 1, 7), np.uint64),
+                          deltas=np.zeros(cap, np.uint64), sig_rx=np.zeros((cap, 6), np.uint64), sig_s=np.zeros((cap, 32), np.uint8))
+            st = _lib.TxWitnessStruct()
+            st.n_tx, st.merkle_depth = cap, depth
+            for f, a in arrays.items():
+                setattr(st, f, a.ctypes.data_as(u8p if f == "sig_s" else u64p))
+            out = C.byref(st)
+        report = _lib.LedgerSelectionStruct()
+        check(self.lib.cstark_ledger_select(self.ctx, led, C.c_uint32(n), self._hptr(s), self._hptr(r), self._hptr(dl),
+                                            None if rx is None else self._hptr(rx), None if ss is None else self._hptr(ss, u8p),
+                                            C.c_uint32(want), C.c_uint32(flags), C.c_uint32(chunk), self._hptr(status, u8p),
+                                            selected.ctypes.data_as(C.POINTER(C.c_uint32)), None if messages is None else self._hptr(messages),
+                                            C.byref(report), out))
+        m = report.n_selected
+        if (flags & self.SELECT_APPLY) and m:
+            self.resident = None   # as ledger_apply: the selection's witness is the resident one now
+            self.n_tx, self.depth = m, depth
+            if arrays is not None:
+                arrays = {f: (a if f == "final_root" else a[:m].copy()) for f, a in arrays.items()}
+        else:
+            arrays = None
+        return status, selected[:m].copy(), messages, report, arrays
+
     # ---- K2 / K3 ----
     def field_generator(self):
         self.lib.cstark_field_generator.restype = C.c_uint64

@@ -31,6 +31,9 @@
 //   k_witness_check     k_path_check's four chains given to ONE transfer: sender-old, sender-new, receiver-old, receiver-new, all leaves
 //                       hashed from values, the four folds met in wave ballots, one verdict byte per transfer
 //   k_witness_messages  the message every transfer signs, gathered from its witness row for the signature check (trace_gen.hip)
+// cstark_ledger_select picks a provable batch out of a pool of candidates (ledger_plan.h: select_prepare, select_walk).  The pool goes up
+// once; per pass of the signature check the host uploads candidate numbers only:
+//   k_select_gather     messages, sig_rx and sig_s of the listed candidates, compacted into the signature check's block
 #include <stdio.h>
 #include <string.h>
 #include <mutex>
@@ -396,6 +399,35 @@ __global__ __launch_bounds__(256) void k_witness_messages(const fp *__restrict__
     messages[i] = k < 12 ? s_old[14 * t + k] : k < 24 ? r_old[14 * t + k - 12] : k == 24 ? deltas[t] : k == 25 ? s_old[14 * t + 13] : (fp)0;
 }
 
+// One pass of cstark_ledger_select's signature check: entry j of the pass is candidate list[j] of the pool that was uploaded once
+// (account table rows [n_rows][14], candidate table cands [n], sig_rx [n][6], sig_s [n][32] as four words).  One thread per 64-bit output
+// word, 38 per entry, compacted into the signature check's block: the message (ledger_plan.h, select_message: the sender's key, the
+// receiver's key, delta, the stored nonce + k_t, two zeros), sig_rx and sig_s.  A candidate number outside the pool or a row outside
+// the table writes zeros; nothing else is written.
+__global__ __launch_bounds__(256) void k_select_gather(const fp *__restrict__ rows, uint32_t n_rows, const ledger::Candidate *__restrict__ cands,
+                                                       const fp *__restrict__ sig_rx, const uint64_t *__restrict__ sig_s, uint32_t n,
+                                                       const uint32_t *__restrict__ list, uint32_t m, fp *__restrict__ messages, fp *__restrict__ rx_out,
+                                                       uint64_t *__restrict__ s_out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t j = i / 38;
+    const uint32_t k = (uint32_t)(i % 38);
+    if (j >= m) return;
+    const uint32_t t = list[j];
+    uint64_t v = 0;
+    if (t < n) {
+        if (k < 28) {
+            const uint32_t s_row = cands[t].s_row, r_row = cands[t].r_row;
+            if (s_row < n_rows && r_row < n_rows)
+                v = k < 12 ? rows[(size_t)14 * s_row + k] : k < 24 ? rows[(size_t)14 * r_row + k - 12] : k == 24 ? cands[t].delta
+                  : k == 25 ? fp_add(rows[(size_t)14 * s_row + 13], cands[t].k) : (fp)0;
+        } else if (k < 34) v = sig_rx[(size_t)6 * t + k - 28];
+        else v = sig_s[(size_t)4 * t + k - 34];
+    }
+    if (k < 28) messages[28 * j + k] = v;
+    else if (k < 34) rx_out[6 * j + k - 28] = v;
+    else s_out[4 * j + k - 34] = v;
+}
+
 } // namespace
 } // namespace cs
 
@@ -539,7 +571,8 @@ int root_impl(cstark_ledger *L, uint64_t *root, size_t at = HEAD) {
 }
 
 int apply_impl(cstark_ledger *L, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices, const uint64_t *deltas, const uint64_t *sig_rx,
-               const uint8_t *sig_s, cstark_tx_witness *out, int32_t *refused_at, int32_t *reason, bool check_signatures) {
+               const uint8_t *sig_s, cstark_tx_witness *out, int32_t *refused_at, int32_t *reason, bool check_signatures,
+               uint64_t *root_out = nullptr /* cstark_ledger_select: the root the batch leaves, read inside the call's one wait */) {
     cstark_ctx *c = L->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t d = L->index.depth, ne = 2 * n_tx;
@@ -592,6 +625,7 @@ int apply_impl(cstark_ledger *L, uint32_t n_tx, const uint64_t *s_indices, const
         memcpy((void *)out->sig_rx, sig_rx, sz[cs::WIT_SIG_RX]);
         memcpy((void *)out->sig_s, sig_s, sz[cs::WIT_SIG_S]);
     }
+    if (root_out) HIP_TRY(hipMemcpyAsync(root_out, L->pool + (size_t)7 * L->index.root_slot(), 56, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(cs::stream_wait(c->stream)); // the caller's arrays and the plan's host block are read by the copies
     return CSTARK_OK;
 }
@@ -950,6 +984,92 @@ int witness_check_impl(cstark_ctx *c, const cstark_tx_witness *host, cs::TxWitne
     }
     if (verdicts_out) memcpy(verdicts_out, verdicts.data(), n);
     *report = r;
+    return CSTARK_OK;
+}
+
+// cstark_ledger_select behind its argument checks.  The host walk (ledger_plan.h) decides everything; the device checks signatures in
+// passes.  The pool of the call lives in the context's witness-check block (both calls are synchronous and upload all they read there):
+//   account table [n_rows][14] | candidate table [n][3] | sig_rx [n][6] | sig_s [n][32] | candidate numbers of the pass [<= n] (4 bytes each)
+// uploaded once, the list per pass.  k_select_gather compacts the pass into the signature check's block (signature_block),
+// launch_signature_check follows unchanged and one verdict byte per entry comes back.  Statically refused candidates never go up in a
+// list.  Nothing of the ledger is read or written on the device unless the selection is applied, and that is apply_impl on the compacted
+// selection: cstark_ledger_apply's launches, with root_after read inside apply's own wait.  The outputs are written at the very end,
+// after the last step that can fail; the messages that came back are kept compact until then (224 bytes per candidate SENT, not per candidate).
+int select_impl(cstark_ledger *L, uint32_t n, const uint64_t *s_indices, const uint64_t *r_indices, const uint64_t *deltas, const uint64_t *sig_rx,
+                const uint8_t *sig_s, uint32_t want, uint32_t flags, uint32_t chunk, uint8_t *status_out, uint32_t *selected_out, uint64_t *messages_out,
+                cstark_ledger_selection *report, cstark_tx_witness *out) {
+    cstark_ctx *c = L->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool check = flags & CSTARK_SELECT_CHECK_SIGNATURES;
+    Selection s;
+    select_prepare(L->index, n, s_indices, r_indices, deltas, check ? sig_rx : nullptr, want, check, s);
+    cstark_ledger_selection rep = {};
+    std::vector<uint64_t> sent_messages; // [n_sig_checked][28], in the order of `sent`
+    std::vector<uint32_t> list, sent;
+    std::vector<uint8_t> verdicts;
+    uint64_t *d_rows = nullptr, *d_cands = nullptr, *d_rx = nullptr, *d_s = nullptr;
+    uint32_t *d_list = nullptr;
+    while (!select_walk(s)) {
+        if (!d_rows) { // the first verdict the walk needs: the pool goes up, once
+            const size_t n_rows = s.n_rows(), words = 14 * n_rows + (size_t)(3 + 6 + 4) * n;
+            void *block = nullptr;
+            RC_TRY(witness_check_block(c, words * 8 + (size_t)4 * n, &block));
+            d_rows = (uint64_t *)block; d_cands = d_rows + 14 * n_rows; d_rx = d_cands + (size_t)3 * n; d_s = d_rx + (size_t)6 * n;
+            d_list = (uint32_t *)(d_s + (size_t)4 * n);
+            HIP_TRY(hipMemcpyAsync(d_rows, s.rows.data(), n_rows * 112, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(d_cands, s.cands.data(), (size_t)24 * n, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(d_rx, sig_rx, (size_t)48 * n, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(d_s, sig_s, (size_t)32 * n, hipMemcpyHostToDevice, c->stream));
+        }
+        select_chunk(s, chunk ? chunk : select_default_chunk(s), list);
+        const uint32_t m = (uint32_t)list.size();
+        if (m == 0 || list[0] != s.at) return fail(CSTARK_ERR_UNSUPPORTED, "cstark_ledger_select: the walk waits for a candidate no pass can hold");
+        cstark_sig_block b;
+        RC_TRY(signature_block(c, m, &b));
+        HIP_TRY(hipMemcpyAsync(d_list, list.data(), (size_t)4 * m, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(cs::k_select_gather, dim3((uint32_t)(((size_t)38 * m + 255) / 256)), dim3(256), 0, c->stream, d_rows, s.n_rows(),
+                           (const Candidate *)d_cands, d_rx, d_s, n, d_list, m, b.messages, b.sig_rx, (uint64_t *)b.sig_s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(cs::launch_signature_check(b.messages, b.sig_rx, b.sig_s, b.h_limbs, b.points, b.verdicts, b.x, m, c->stream));
+        verdicts.resize(m);
+        HIP_TRY(hipMemcpyAsync(verdicts.data(), b.verdicts, m, hipMemcpyDeviceToHost, c->stream));
+        if (messages_out) {
+            sent_messages.resize((size_t)28 * (sent.size() + m)); // before the copy is enqueued: the vector does not move under it
+            HIP_TRY(hipMemcpyAsync(&sent_messages[(size_t)28 * sent.size()], b.messages, (size_t)224 * m, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream)); // the verdicts are on the host; the list and, after the first pass, the pool's host arrays are free
+        for (uint32_t j = 0; j < m; j++) s.verdict[list[j]] = verdicts[j] == NO_VERDICT ? (uint8_t)CSTARK_SIG_MISMATCH : verdicts[j];
+        if (messages_out) sent.insert(sent.end(), list.begin(), list.end());
+        rep.n_sig_checked += m;
+        rep.n_chunks++;
+    }
+    select_finish(s, flags & CSTARK_SELECT_POW2);
+    rep.n_candidates = n;
+    rep.n_selected = s.n_selected;
+    for (uint32_t t = 0; t < n; t++) rep.counts[s.status[t]]++;
+    if ((flags & CSTARK_SELECT_APPLY) && s.n_selected) {
+        std::vector<uint64_t> bs, br, bd, brx((size_t)6 * s.n_selected);
+        std::vector<uint8_t> bss((size_t)32 * s.n_selected);
+        select_batch(s, s_indices, r_indices, deltas, bs, br, bd);
+        for (uint32_t i = 0; i < s.n_selected; i++) {
+            memcpy(&brx[(size_t)6 * i], sig_rx + (size_t)6 * s.selected[i], 48);
+            memcpy(&bss[(size_t)32 * i], sig_s + (size_t)32 * s.selected[i], 32);
+        }
+        int32_t at = -1, why = REASON_NONE;
+        RC_TRY(apply_impl(L, s.n_selected, bs.data(), br.data(), bd.data(), brx.data(), bss.data(), out, &at, &why, false, rep.root_after));
+        if (at >= 0) {
+            char text[96];
+            snprintf(text, sizeof text, "selected candidate %u (reason %d)", s.selected[at], why);
+            return fail(CSTARK_ERR_UNSUPPORTED, "cstark_ledger_select: the plan refuses %s", text);
+        }
+    }
+    memcpy(status_out, s.status.data(), n);
+    if (selected_out && s.n_selected) memcpy(selected_out, s.selected.data(), (size_t)4 * s.n_selected);
+    if (messages_out) {
+        memset(messages_out, 0, (size_t)224 * n);
+        for (size_t j = 0; j < sent.size(); j++) memcpy(messages_out + (size_t)28 * sent[j], &sent_messages[(size_t)28 * j], 224);
+    }
+    *report = rep;
     return CSTARK_OK;
 }
 
@@ -1453,6 +1573,34 @@ int cstark_ledger_sign(cstark_ctx *c, cstark_ledger *L, uint32_t n_tx, const uin
     memcpy(sig_s_out, s.data(), s.size());
     if (attempts_out) memcpy(attempts_out, attempts.data(), attempts.size() * 4);
     return CSTARK_OK;
+}
+
+static_assert(CSTARK_LEDGER_HELD == STATUS_HELD && CSTARK_LEDGER_NOT_REACHED == STATUS_NOT_REACHED, "select_walk writes the values of cstark_ledger_reason");
+int cstark_ledger_select(cstark_ctx *c, cstark_ledger *L, uint32_t n, const uint64_t *s_indices, const uint64_t *r_indices, const uint64_t *deltas,
+                         const uint64_t *sig_rx, const uint8_t *sig_s, uint32_t want, uint32_t flags, uint32_t chunk, uint8_t *status_out,
+                         uint32_t *selected_out, uint64_t *messages_out, cstark_ledger_selection *report, cstark_tx_witness *out) {
+    RC_TRY(usable(c, L, "cstark_ledger_select"));
+    const uint32_t all = CSTARK_SELECT_CHECK_SIGNATURES | CSTARK_SELECT_POW2 | CSTARK_SELECT_APPLY;
+    if (n == 0 || n > MAX_TRANSFERS || want == 0 || want > MAX_TRANSFERS || chunk > MAX_TRANSFERS || (flags & ~all))
+        return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_select: n and want are 1 .. 2^20, chunk is at most 2^20, flags are CSTARK_SELECT_*");
+    if (!s_indices || !r_indices || !deltas || !status_out || !report) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_select: null argument");
+    if ((flags & (CSTARK_SELECT_CHECK_SIGNATURES | CSTARK_SELECT_APPLY)) && (!sig_rx || !sig_s))
+        return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_select: sig_rx and sig_s may be null only without CHECK_SIGNATURES and APPLY");
+    if (out) {
+        if (!(flags & CSTARK_SELECT_APPLY)) return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_select: an output witness needs CSTARK_SELECT_APPLY");
+        if (out->n_tx < std::min(want, n) || out->merkle_depth != L->index.depth)
+            return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_select: the output witness has another depth or holds fewer than min(want, n) transfers");
+        if (!out->initial_roots || !out->final_root || !out->s_old_values || !out->r_old_values || !out->s_indices || !out->r_indices || !out->s_paths ||
+            !out->r_paths || !out->deltas || !out->sig_rx || !out->sig_s)
+            return fail(CSTARK_ERR_INVALID_ARG, "cstark_ledger_select: output witness array pointer is null (the caller allocates every array)");
+    }
+    for (uint32_t t = 0; t < n; t++)
+        if (deltas[t] >= cs::host::P) {
+            char where[64];
+            snprintf(where, sizeof where, "cstark_ledger_select: deltas[%u]", t);
+            return fail(CSTARK_ERR_INVALID_ARG, "%s is not a reduced field element", where);
+        }
+    return guard(L, select_impl(L, n, s_indices, r_indices, deltas, sig_rx, sig_s, want, flags, chunk, status_out, selected_out, messages_out, report, out));
 }
 
 } // extern "C"

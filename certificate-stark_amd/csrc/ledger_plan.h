@@ -372,6 +372,153 @@ inline bool plan_apply(const Index &ix, uint32_t scratch_base, uint32_t n_tx, co
     return p.pool_slots <= MAX_POOL_SLOTS;
 }
 
+// ---- cstark_ledger_select: a provable batch out of a pool of candidates ------------------------------------------------------------
+// Candidates are examined in list order, each against the accounts as the candidates selected before it leave them, and get the first
+// status that applies: NOT_REACHED (`want` are selected already), INDEX, SELF, UNKNOWN, ABSENT, HELD, BALANCE, SIGNATURE, else selected
+// (REASON_NONE).  THE HOLD: a refused candidate whose sender index is in range holds that sender for the rest of the call -- its later
+// candidates are HELD whatever they say; a held account still receives.  A wallet signs nonce n, n + 1, ... expecting all of them to
+// be accepted, so after one refusal the sender's later candidates carry the wrong nonce anyway.  With the hold, every candidate that
+// reaches the signature test has all earlier candidates of its sender selected, so its message is known before any verdict is:
+// sender's key, receiver's key (keys never change in a transfer), delta, the STORED nonce + k_t (k_t = earlier candidates in the list
+// with the same sender index), two zeros.  Signatures are therefore checked in passes over many candidates, not in rounds.
+//   select_prepare   once per call: the static tests (INDEX, SELF, UNKNOWN, ABSENT: they read the index only), k_t, the table of the
+//                    distinct accounts that checkable candidates name (a candidate is checkable when it passes the static tests), and
+//                    per candidate {sender row, receiver row, delta, k_t in memory form}: what k_select_gather (ledger.hip) reads
+//   select_walk      resumable: HELD, BALANCE (plan_apply's arithmetic) and the signature verdicts in list order; it stops at the
+//                    first candidate whose verdict it needs and does not have
+//   select_chunk     the candidates of the next pass of the signature check: the one the walk waits for and the checkable ones after it
+//   select_finish    the cut to a power of two; select_batch compacts the selection into what plan_apply takes, unchanged
+constexpr uint8_t STATUS_HELD = 8, STATUS_NOT_REACHED = 9; // cstark_ledger_reason beyond Reason
+constexpr uint8_t NO_VERDICT = 0xFF;
+constexpr uint32_t NO_ROW = 0xFFFFFFFFu;
+struct Candidate { uint32_t s_row, r_row; uint64_t delta, k; };
+static_assert(sizeof(Candidate) == 24, "the candidate table is copied to the device as it is");
+
+struct Selection {
+    // the call
+    uint32_t n = 0, want = 0;
+    uint64_t size = 0; // 2^depth
+    bool check_signatures = false;
+    const uint64_t *s_idx = nullptr;
+    // preparation
+    std::vector<uint8_t> fixed;      // [n] the static status, REASON_NONE: checkable
+    std::vector<uint8_t> rx_ok;      // [n] every sig_rx word is below p (all 1 without signatures)
+    std::vector<Candidate> cands;    // [n] rows NO_ROW where not checkable
+    std::vector<uint64_t> rows;      // [n_rows][14] the accounts as stored
+    // the walk
+    uint32_t at = 0, n_selected = 0;
+    std::vector<uint64_t> balance;   // [n_rows] memory form, as the selected candidates so far leave it
+    std::unordered_set<uint64_t> held;
+    std::vector<uint8_t> status, verdict; // [n]; verdict: cstark_sig_verdict, NO_VERDICT where none came back yet
+    std::vector<uint32_t> selected;  // candidate numbers, ascending
+    uint32_t n_rows() const { return (uint32_t)(rows.size() / 14); }
+};
+
+inline void select_prepare(const Index &ix, uint32_t n, const uint64_t *s_idx, const uint64_t *r_idx, const uint64_t *deltas, const uint64_t *sig_rx /* or null */,
+                           uint32_t want, bool check_signatures, Selection &s) {
+    s.n = n; s.want = want; s.size = (uint64_t)1 << ix.depth; s.check_signatures = check_signatures; s.s_idx = s_idx;
+    s.fixed.assign(n, REASON_NONE);
+    s.rx_ok.assign(n, 1);
+    s.cands.assign(n, Candidate{NO_ROW, NO_ROW, 0, 0});
+    s.status.assign(n, STATUS_NOT_REACHED);
+    s.verdict.assign(n, NO_VERDICT);
+    std::unordered_map<uint64_t, uint32_t> seen, row_of; // sender index -> candidates so far; leaf -> row
+    auto row = [&](uint64_t a, const Value &v) {
+        const auto it = row_of.emplace(a, s.n_rows());
+        if (it.second) s.rows.insert(s.rows.end(), v.begin(), v.end());
+        return it.first->second;
+    };
+    for (uint32_t t = 0; t < n; t++) {
+        const uint64_t si = s_idx[t], ri = r_idx[t];
+        const uint32_t k = seen[si]++;
+        if (sig_rx)
+            for (int w = 0; w < 6; w++)
+                if (sig_rx[(size_t)6 * t + w] >= host::P) s.rx_ok[t] = 0;
+        if (si >= s.size || ri >= s.size) { s.fixed[t] = REASON_INDEX; continue; }
+        if (si == ri) { s.fixed[t] = REASON_SELF; continue; }
+        if (!ix.is_known(si) || !ix.is_known(ri)) { s.fixed[t] = REASON_UNKNOWN; continue; }
+        const auto sv = ix.accounts.find(si), rv = ix.accounts.find(ri);
+        if (sv == ix.accounts.end() || rv == ix.accounts.end()) { s.fixed[t] = REASON_ABSENT; continue; }
+        const uint32_t s_row = row(si, sv->second); // two statements: the sender's row is numbered first
+        const uint32_t r_row = row(ri, rv->second);
+        s.cands[t] = Candidate{s_row, r_row, deltas[t], host::from_u64(k)};
+    }
+    s.balance.resize(s.n_rows());
+    for (uint32_t i = 0; i < s.n_rows(); i++) s.balance[i] = s.rows[(size_t)14 * i + 12];
+}
+
+// the message candidate t signs, as k_select_gather builds it on the device; zeros for a candidate that is not checkable
+inline void select_message(const Selection &s, uint32_t t, uint64_t *out /* [28] */) {
+    memset(out, 0, 28 * 8);
+    const Candidate &c = s.cands[t];
+    if (c.s_row >= s.n_rows() || c.r_row >= s.n_rows()) return;
+    memcpy(out, &s.rows[(size_t)14 * c.s_row], 96);
+    memcpy(out + 12, &s.rows[(size_t)14 * c.r_row], 96);
+    out[24] = c.delta;
+    out[25] = host::add(s.rows[(size_t)14 * c.s_row + 13], c.k);
+}
+
+// true: every candidate has its status.  false: the walk stands at candidate s.at and needs s.verdict[s.at]
+inline bool select_walk(Selection &s) {
+    using namespace cs::host;
+    for (; s.at < s.n; s.at++) {
+        const uint32_t t = s.at;
+        if (s.n_selected == s.want) { s.status[t] = STATUS_NOT_REACHED; continue; }
+        const uint64_t si = s.s_idx[t];
+        const Candidate &c = s.cands[t];
+        uint8_t st = s.fixed[t];
+        if (st == REASON_NONE) {
+            if (s.held.count(si)) st = STATUS_HELD;
+            else if (to_u64(c.delta) > to_u64(s.balance[c.s_row])) st = REASON_BALANCE;
+            else if (s.check_signatures) {
+                if (!s.rx_ok[t]) st = REASON_SIGNATURE; // equals no canonical x: never sent to the device
+                else if (s.verdict[t] == NO_VERDICT) return false;
+                else if (s.verdict[t] != 0) st = REASON_SIGNATURE;
+            }
+        }
+        s.status[t] = st;
+        if (st != REASON_NONE) {
+            if (si < s.size) s.held.insert(si);
+            continue;
+        }
+        s.balance[c.s_row] = sub(s.balance[c.s_row], c.delta);
+        s.balance[c.r_row] = add(s.balance[c.r_row], c.delta);
+        s.selected.push_back(t);
+        s.n_selected++;
+    }
+    return true;
+}
+
+// the default size of a pass: the selections still missing, rounded up to a multiple of 1,024 (the count whose check costs what one
+// signature's costs)
+inline uint32_t select_default_chunk(const Selection &s) { return (s.want - s.n_selected + 1023) / 1024 * 1024; }
+
+// after select_walk returned false: the candidate it waits for, then the checkable candidates after it that have no verdict yet and
+// whose sender is not held by now (a hold is for the rest of the call), `chunk` at the most, in list order
+inline void select_chunk(const Selection &s, uint32_t chunk, std::vector<uint32_t> &list) {
+    list.clear();
+    for (uint32_t t = s.at; t < s.n && list.size() < chunk; t++)
+        if (s.fixed[t] == REASON_NONE && s.rx_ok[t] && s.verdict[t] == NO_VERDICT && !s.held.count(s.s_idx[t])) list.push_back(t);
+}
+
+// after select_walk returned true.  pow2: the selection is cut to the largest power of two it holds, as if `want` had been that
+// number -- what precedes the cut does not depend on `want`, so everything after the last selected candidate becomes NOT_REACHED
+inline void select_finish(Selection &s, bool pow2) {
+    if (!pow2 || s.selected.empty()) return;
+    uint32_t keep = 1;
+    while (2 * keep <= s.n_selected) keep *= 2;
+    if (keep == s.n_selected) return;
+    for (uint32_t t = s.selected[keep - 1] + 1; t < s.n; t++) s.status[t] = STATUS_NOT_REACHED;
+    s.selected.resize(keep);
+    s.n_selected = keep;
+}
+
+// the selection as the batch plan_apply takes
+inline void select_batch(const Selection &s, const uint64_t *s_idx, const uint64_t *r_idx, const uint64_t *deltas, std::vector<uint64_t> &bs,
+                         std::vector<uint64_t> &br, std::vector<uint64_t> &bd) {
+    for (const uint32_t t : s.selected) { bs.push_back(s_idx[t]); br.push_back(r_idx[t]); bd.push_back(deltas[t]); }
+}
+
 // cstark_ledger_open_accounts: the authentication paths of `count` leaves of the tree as it stands, in the witness's form (path[0] = the
 // leaf, path[k + 1] = the sibling at level depth - k).  One emit list of count (depth + 1) entries, `witness`, whose word offsets count
 // from the staging area [stage_slot, stage_slot + count (depth + 1)) that follows the list in the scratch: path i starts at word

@@ -225,10 +225,11 @@ class Ledger:
     """The account tree an operator holds, resident on the GPU (cstark_ledger_*): set_accounts, then apply(transfers) per batch -- the
     counterpart of the sequential loop of TransactionMetadata::build_random (src/lib.rs:341-422) on real accounts and transfers.
     apply() leaves the batch's witness resident in the backend: backend.prove(options) follows without an upload."""
-    INDEX_RANGE, SELF_TRANSFER, ABSENT, BALANCE, SIGNATURE, UNKNOWN, KEY = 1, 2, 3, 4, 5, 6, 7
+    APPLIED, INDEX_RANGE, SELF_TRANSFER, ABSENT, BALANCE, SIGNATURE, UNKNOWN, KEY, HELD, NOT_REACHED = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
     REASONS = {1: "index out of range", 2: "sender equals receiver", 3: "account absent", 4: "delta above the sender's balance",
                5: "signature does not verify", 6: "account not among those a partial ledger knows",
-               7: "secret is not the secret of the sender's public key"}
+               7: "secret is not the secret of the sender's public key",
+               8: "an earlier candidate of the same sender was refused in this selection", 9: "enough candidates were selected before this one"}
 
     def __init__(self, depth=15, backend=None):
         self.backend = backend or Backend()
@@ -380,6 +381,45 @@ class Ledger:
         if at >= 0:
             raise TransferRefused(at, reason)
         return s, r, d, rx, ss
+
+    def select(self, transfers, want, check_signatures=True, pow2=True, apply=False, chunk=0, want_messages=False):
+        """-> Selection: a provable batch out of a pool of candidate transfers in arrival order (cstark_ledger_select).  transfers:
+        (s_indices, r_indices, deltas, sig_rx, sig_s) or an object with these attributes; the signatures may be left out (or None)
+        without check_signatures and apply.  Nothing is refused as a whole: every candidate gets a status -- APPLIED (0, selected), a
+        reason of apply(), HELD (an earlier candidate of the same sender was refused in this call: the sender is held for the rest of
+        it, though the account still receives) or NOT_REACHED (`want` were selected before it).  Candidates are examined in order against
+        the accounts as the selected ones before them leave them; check_signatures checks the signatures on the device in passes of
+        `chunk` candidates (0: the library's choice), whatever the bad candidates do.  pow2: the selection is cut to the largest power
+        of two it holds, what prove() needs.  apply: the selection is applied as apply(selection.transfers) would apply it and its
+        witness is resident for prove(); otherwise the call is read-only."""
+        if hasattr(transfers, "s_indices"):
+            transfers = tuple(getattr(transfers, f, None) for f in ("s_indices", "r_indices", "deltas", "sig_rx", "sig_s"))
+        s, r, d = (np.ascontiguousarray(a, np.uint64).reshape(-1) for a in transfers[:3])
+        rx, ss = (tuple(transfers[3:5]) + (None, None))[:2]
+        B = self.backend
+        flags = (B.SELECT_CHECK_SIGNATURES if check_signatures else 0) | (B.SELECT_POW2 if pow2 else 0) | (B.SELECT_APPLY if apply else 0)
+        status, selected, messages, report, arrays = B.ledger_select(self._led, self.depth, s, r, d, rx, ss, want, flags=flags, chunk=chunk,
+                                                                     want_messages=want_messages)
+        witness = None if arrays is None else TransactionMetadata(*[arrays[f] for f in TransactionMetadata.FIELDS])
+        pool = (s, r, d, None if rx is None else np.ascontiguousarray(rx, np.uint64).reshape(-1, 6),
+                None if ss is None else np.ascontiguousarray(ss, np.uint8).reshape(-1, 32))
+        return Selection(status, selected, pool, report, messages, witness)
+
+
+class Selection:
+    """What Ledger.select returns.  status: uint8 [n], one cstark_ledger_reason per candidate (Ledger.APPLIED = 0: selected);
+    selected: the selected candidate numbers, ascending; transfers: the five arrays of the selection, what Ledger.apply takes (the
+    signatures None when the pool had none); counts: candidates per status, a list of ten; report: n_candidates, n_selected,
+    n_sig_checked, n_chunks, root_after; messages: [n][28] with want_messages (the message of every candidate sent to the device, zeros
+    elsewhere); witness: the TransactionMetadata of the applied selection (apply=True and something selected), else None."""
+
+    def __init__(self, status, selected, pool, report, messages=None, witness=None):
+        self.status, self.selected, self.report, self.messages, self.witness = status, selected, report, messages, witness
+        self.transfers = tuple(None if a is None else a[selected] for a in pool)
+        self.counts = [int(k) for k in report.counts]
+
+    def __len__(self):
+        return len(self.selected)
 
 
 def public_keys(secrets, backend=None):

@@ -540,7 +540,9 @@ typedef enum cstark_ledger_reason {
     CSTARK_LEDGER_SIGNATURE = 5,    /* cstark_ledger_apply_checked only: the transfer's signature has another verdict than CSTARK_SIG_VALID */
     CSTARK_LEDGER_UNKNOWN = 6,      /* a partial ledger only: sender or receiver is not among the accounts it knows; tested after the self
                                        transfer and before absence (index range, self transfer, unknown, absent, balance, signature) */
-    CSTARK_LEDGER_KEY = 7           /* cstark_ledger_sign only: the transfer's secret is not the secret of its sender's public key */
+    CSTARK_LEDGER_KEY = 7,          /* cstark_ledger_sign only: the transfer's secret is not the secret of its sender's public key */
+    CSTARK_LEDGER_HELD = 8,         /* cstark_ledger_select only: an earlier candidate of the call with the same sender index was refused */
+    CSTARK_LEDGER_NOT_REACHED = 9   /* cstark_ledger_select only: `want` candidates were selected before this one */
 } cstark_ledger_reason;
 /* An empty tree of depth 1, 3, 7, 15 or 31 (the depths cstark_tx_witness_upload accepts).  Destroy it before its context. */
 int cstark_ledger_create(cstark_ctx *ctx, uint32_t merkle_depth, cstark_ledger **out);
@@ -630,6 +632,51 @@ int cstark_ledger_messages(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t n_tx
 int cstark_ledger_sign(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t n_tx, const uint64_t *s_indices, const uint64_t *r_indices,
                        const uint64_t *deltas, const uint64_t *secrets, uint64_t seed, uint32_t max_attempts, uint64_t *sig_rx_out,
                        uint8_t *sig_s_out, uint32_t *attempts_out, int32_t *refused_at, int32_t *reason);
+
+/* Selects a provable batch from a pool of n candidate transfers in arrival order: every candidate gets a status (status_out [n], a
+ * cstark_ledger_reason), up to `want` of them are selected, and nothing is refused as a whole.  Candidates are examined in list order,
+ * each against the accounts as the candidates SELECTED before it leave them, and a candidate gets the first status that applies, in this
+ * order: NOT_REACHED (`want` candidates are selected already), INDEX_RANGE, SELF_TRANSFER, UNKNOWN (a partial ledger only), ABSENT, HELD,
+ * BALANCE (cstark_ledger_apply's arithmetic), SIGNATURE (only with CSTARK_SELECT_CHECK_SIGNATURES), else APPLIED: selected.
+ * THE HOLD: a refused candidate (any status but NOT_REACHED) whose sender index is in range holds that sender for the rest of the call:
+ * the sender's later candidates are HELD.  A held account still receives.  A wallet signs nonce n, n + 1, ... expecting all of them to
+ * be accepted; after a refusal the sender's later candidates carry the wrong nonce anyway, so honest senders lose nothing.  The hold
+ * makes the message of every candidate that reaches the signature test known before any verdict is: the sender's key, the receiver's
+ * key, delta, the sender's STORED nonce + k (k = the earlier candidates in the list with the same sender index), two zeros.  So the
+ * signatures are checked in passes of many candidates on the device, whatever the bad candidates do: a sender who submits 1,000
+ * transfers for one nonce costs one pass, not 1,000 retries.
+ * flags: CSTARK_SELECT_CHECK_SIGNATURES -- any verdict other than CSTARK_SIG_VALID is SIGNATURE; a candidate that reaches the
+ *   signature test with a sig_rx word >= p is SIGNATURE without being sent to the device (it equals no canonical x).
+ * CSTARK_SELECT_POW2 -- with A candidates selected under `want`, the result is that of the same call with want = the largest power of
+ *   two <= A: everything after that many selected candidates is NOT_REACHED (cstark_tx_prove needs a power of two).
+ * CSTARK_SELECT_APPLY -- the selected candidates, in order, are applied exactly as cstark_ledger_apply applies that batch (the witness
+ *   resident, live checkpoints honoured, report->root_after the root they leave); `out` (optional, APPLY only): a witness the caller
+ *   allocated for merkle_depth and at least min(want, n) transfers (out->n_tx states the capacity), whose first report->n_selected rows
+ *   are filled.  With nothing selected nothing changes.  Without APPLY the call is read-only: root, pool, host index, checkpoints and the
+ *   resident witness are unchanged and a proof after the call is the proof without it.
+ * chunk: the checkable candidates (those that pass the tests before HELD) sent to the device per pass; 0: the number still missing from
+ *   `want`, rounded up to a multiple of 1,024.  Statuses and selection never depend on it; report->n_sig_checked and n_chunks do, and
+ *   so do the rows of messages_out of candidates whose verdict was not needed in the end.
+ * selected_out (optional) [min(want, n)]: the selected candidate numbers, ascending, report->n_selected of them.  messages_out
+ * (optional) [n][28]: the message of every candidate sent to the device, zeros elsewhere.
+ * n and want are 1 .. 2^20 (want may exceed n); chunk <= 2^20; sig_rx and sig_s may be NULL only without CHECK_SIGNATURES and APPLY.
+ * Unknown flag bits, null required pointers, a ledger of another context, `out` without APPLY or of another shape, or a delta word
+ * >= p (cstark_last_error names it) are CSTARK_ERR_INVALID_ARG, raised before any launch with the outputs untouched.  Synchronous. */
+#define CSTARK_SELECT_CHECK_SIGNATURES 1u
+#define CSTARK_SELECT_POW2 2u
+#define CSTARK_SELECT_APPLY 4u
+typedef struct cstark_ledger_selection {
+    uint32_t n_candidates;
+    uint32_t n_selected;
+    uint32_t n_sig_checked;     /* signatures sent to the device, all passes */
+    uint32_t n_chunks;          /* passes of the signature check */
+    uint32_t counts[10];        /* candidates per cstark_ledger_reason */
+    uint64_t root_after[7];     /* with CSTARK_SELECT_APPLY: the root the selection leaves; zero otherwise */
+} cstark_ledger_selection;
+int cstark_ledger_select(cstark_ctx *ctx, cstark_ledger *ledger, uint32_t n, const uint64_t *s_indices, const uint64_t *r_indices,
+                         const uint64_t *deltas, const uint64_t *sig_rx, const uint8_t *sig_s, uint32_t want, uint32_t flags,
+                         uint32_t chunk, uint8_t *status_out, uint32_t *selected_out, uint64_t *messages_out,
+                         cstark_ledger_selection *report, cstark_tx_witness *out);
 
 /* ---- witness check: is a cstark_tx_witness consistent?  Needs no ledger ---------------------------------------------------------------
  * What cstark_tx_prove starts from, tested transfer by transfer before a trace is built: the indices, the sender's leaf and path under

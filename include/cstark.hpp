@@ -481,6 +481,57 @@ class Ledger {
         if (at >= 0) throw TransferRefused(at, reason);
         return out;
     }
+    // What select returns: one cstark_ledger_reason per candidate (CSTARK_LEDGER_APPLIED: selected), the selected candidate numbers in
+    // ascending order, their transfers (what apply takes), the report, and with apply_selection the witness of the applied selection
+    struct Selection {
+        std::vector<uint8_t> status;
+        std::vector<uint32_t> selected;
+        Transfers transfers;
+        cstark_ledger_selection report{};
+        std::vector<std::array<BaseElement, 28>> messages; // with want_messages: the message of every candidate sent to the device, zeros elsewhere
+        TransactionMetadata witness;                        // with apply_selection and something selected
+    };
+    // A provable batch out of a pool of candidates in arrival order (cstark_ledger_select): every candidate gets a status, up to `want`
+    // are selected, nothing is refused as a whole.  A refused candidate holds its sender for the rest of the call (CSTARK_LEDGER_HELD for
+    // the sender's later candidates; the account still receives), so the signatures are checked on the device in passes of `chunk`
+    // candidates (0: the library's choice) whatever the bad ones do.  flags: CSTARK_SELECT_CHECK_SIGNATURES, CSTARK_SELECT_POW2 (the
+    // selection cut to a power of two, what prove needs), CSTARK_SELECT_APPLY (the selection applied as apply would apply it, its witness
+    // resident for prove_resident; otherwise the call is read-only).  The pool's signatures may be empty without CHECK and APPLY.
+    Selection select(const Transfers &pool, uint32_t want, uint32_t flags = CSTARK_SELECT_CHECK_SIGNATURES | CSTARK_SELECT_POW2, uint32_t chunk = 0,
+                     bool want_messages = false) {
+        const size_t n = pool.s_indices.size();
+        const bool signatures = !pool.sig_rx.empty() || !pool.sig_s.empty();
+        if (n == 0 || pool.r_indices.size() != n || pool.deltas.size() != n || (signatures && (pool.sig_rx.size() != n || pool.sig_s.size() != n)))
+            throw Error(CSTARK_ERR_INVALID_ARG, "candidate vectors are not of equal length");
+        const size_t cap = std::max<size_t>(1, std::min<size_t>(want, n));
+        Selection r;
+        r.status.resize(n);
+        r.selected.resize(cap);
+        if (want_messages) r.messages.resize(n);
+        TransactionMetadata &m = r.witness;
+        cstark_tx_witness w{};
+        const bool apply_selection = flags & CSTARK_SELECT_APPLY;
+        if (apply_selection) {
+            m.merkle_depth = depth_;
+            m.initial_roots.resize(cap); m.s_old_values.resize(cap); m.r_old_values.resize(cap); m.s_indices.resize(cap); m.r_indices.resize(cap);
+            m.s_paths.resize(cap * (depth_ + 1) * 7); m.r_paths.resize(cap * (depth_ + 1) * 7); m.deltas.resize(cap); m.sig_rx.resize(cap); m.sig_s.resize(cap);
+            w = m.view();
+        }
+        check(cstark_ledger_select(ctx_.raw(), led_, (uint32_t)n, pool.s_indices.data(), pool.r_indices.data(), pool.deltas.data(),
+                                   signatures ? pool.sig_rx[0].data() : nullptr, signatures ? pool.sig_s[0].data() : nullptr, want, flags, chunk, r.status.data(),
+                                   r.selected.data(), want_messages ? r.messages[0].data() : nullptr, &r.report, apply_selection ? &w : nullptr));
+        const size_t k = r.report.n_selected;
+        r.selected.resize(k);
+        for (const uint32_t t : r.selected) {
+            r.transfers.s_indices.push_back(pool.s_indices[t]); r.transfers.r_indices.push_back(pool.r_indices[t]); r.transfers.deltas.push_back(pool.deltas[t]);
+            if (signatures) { r.transfers.sig_rx.push_back(pool.sig_rx[t]); r.transfers.sig_s.push_back(pool.sig_s[t]); }
+        }
+        if (apply_selection) {
+            m.initial_roots.resize(k); m.s_old_values.resize(k); m.r_old_values.resize(k); m.s_indices.resize(k); m.r_indices.resize(k);
+            m.s_paths.resize(k * (depth_ + 1) * 7); m.r_paths.resize(k * (depth_ + 1) * 7); m.deltas.resize(k); m.sig_rx.resize(k); m.sig_s.resize(k);
+        }
+        return r;
+    }
 
   private:
     Ledger(Context &ctx, unsigned depth, cstark_ledger *led) : ctx_(ctx), depth_(depth), led_(led) {}
